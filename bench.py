@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the hot path (BASELINE.json metric: Mrays/s).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--full] [--dump-outputs DIR]
     N > 1 either under a launcher that sets RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* (the driver:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...) or as a plain
     command: without WORLD_SIZE in the environment this process only spawns the N rank processes (before
@@ -10,8 +10,12 @@
 A "step" is one pass of the hot path over one synthetic frame: every rank renders its framebuffer
 tiles (64x64, dealt round-robin) with inputs resident in HBM, the tiles are gathered to rank 0
 over RCCL and de-tiled there.  value = rays traced by all ranks / max-over-ranks wall time.
-Rank 0 prints ONE JSON line (with `roofline` for the dominant kernel and `cpu_baseline` = the CPU
-oracle timed on this box's host cores, N=1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+fields (metric, value, unit, higher_is_better, dtype, ms_per_step, config).  --full adds, after the timed
+region, the parity gate against the oracle, and for N=1 `one_frame_at_a_time`, `roofline` for the dominant
+kernel and `cpu_baseline` = the CPU oracle timed on the host cores this process may use.
+--dump-outputs DIR writes the frame of the last timed step as DIR/rgb.npy (float32, H x W x 3); the
+inputs are fixed and seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -34,12 +38,17 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="tri1m_1080p_4spp",
                     help="tri1m_1080p_4spp (metric config) | spheres8_1080p_4spp (configs[1]) | terrain1m_1080p_4spp, tri16m_1080p_4spp (context)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity gate (the timed frame checked against the oracle after the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the parity gate, the one-frame-at-a-time timing, the roofline (with its rocprofv3 PMC "
+                         "child runs) and the CPU baseline; a plain run does only set-up, warm-up, the timed steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the frame a caller receives, float32) as DIR/rgb.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity gate (the timed frame checked against the oracle after the timed region)")
     ap.add_argument("--stub-step", action="store_true", help=argparse.SUPPRESS)  # CPU test of the launcher + N>1 control flow (gloo, no GPU, no kernels)
     ap.add_argument("--stub-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)  # run under rocprofv3 by measure_traffic()
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC child runs (roofline.traffic = null)")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the rocprofv3 PMC child runs (roofline.traffic = null)")
     ap.add_argument("--frames-in-flight", type=int, default=0,
                     help="frame lanes (0 = the workload's default: 3 for path B, 4 for path A - one per hardware queue, measured "
                          "0.406 against 0.432 ms per step with 3): consecutive steps go round-robin to this many independent contexts (own stream, own "
@@ -52,7 +61,24 @@ def parse():
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="debug only: all ranks share cuda:0 and gather through host memory over gloo (exercises the N>1 "
                          "control flow on a 1-GPU box; the line it prints is marked rehearsal and is not a measurement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy (float32 / float64 as computed), 64 MB at most in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def host_threads():
@@ -808,6 +834,8 @@ def main():
     # set-up, not warm-up: every lane renders one frame so that its buffers exist (the first frame of a context
     # allocates pyramid / wavefront state) whatever --warmup is; the lane rotation then starts at lane 0 again
     dt = timed_region(step, fence, n_lanes, args.warmup, args.steps, lambda: state.update(i=0))
+    if args.dump_outputs and rank == 0:  # the frame of the last timed step (for N > 1 the gathered, de-tiled one)
+        dump_outputs(args.dump_outputs, {"rgb": lanes[(args.warmup + args.steps - 1) % n_lanes].frame.cpu().numpy()})
 
     rays_rank = wl.rays_per_step()
     dt, rays = reduce_over_ranks(dist, world, dt, rays_rank, "cpu" if args.rehearse_one_gpu else dev)
@@ -827,7 +855,7 @@ def main():
             # the de-tiled frame of the split render must equal a single-context render of the same frame
             import numpy as np
             split = [ln.frame.cpu().numpy().copy() for ln in lanes[:max(1, min(n_lanes, args.steps + args.warmup))]]
-        timed_frame = None if args.no_parity or args.rehearse_one_gpu else lanes[0].frame.cpu().numpy()
+        timed_frame = None if not args.full or args.no_parity or args.rehearse_one_gpu else lanes[0].frame.cpu().numpy()
         if multi:
             torch.cuda.synchronize()
             r.set_stream(None)
@@ -839,11 +867,11 @@ def main():
             r.synchronize()
             single = frame.cpu().numpy()
             out["rehearsal_split_equals_single"] = bool(all((single == f).all() for f in split))
-        if not args.no_parity and not args.rehearse_one_gpu:
-            # parity gate, run with every measurement: the last frame lane 0 rendered inside the
+        if args.full and not args.no_parity and not args.rehearse_one_gpu:
+            # parity gate, run with every --full measurement: the last frame lane 0 rendered inside the
             # timed region (for N > 1 the gathered, de-tiled frame on rank 0) against the oracle, same process
             out["parity"] = wl.parity(timed_frame, int(rays))
-        if not multi:
+        if args.full and not multi:
             # the regime the roofline block is measured in, next to the timed one: the same K steps on lane 0 alone, one frame after the
             # other (per-kernel HIP-event durations in `roofline` are those of a frame that has the GPU to itself; with several lanes the
             # kernels of different frames run side by side and stretch each other while the frame rate goes up)

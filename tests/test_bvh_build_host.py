@@ -3,6 +3,8 @@
 (tests/native/bvh_check.cpp); its threads under ThreadSanitizer, and its output must not depend on the
 number of threads.  No GPU."""
 import os
+import platform
+import shutil
 import subprocess
 
 import pytest
@@ -34,24 +36,34 @@ def checker_tsan(tmp_path_factory):
     return str(exe)
 
 
+def run_tsan(cmd):
+    """ThreadSanitizer of older toolchains cannot start when the kernel places mappings with more random bits than its shadow
+    layout expects ("unexpected memory mapping", vm.mmap_rnd_bits = 32): then the same program runs once more with address-space
+    randomisation off for that one process (setarch -R), which is what TSan itself does in newer toolchains."""
+    out = subprocess.run(cmd, capture_output=True, text=True)
+    if out.returncode != 0 and "unexpected memory mapping" in out.stderr and shutil.which("setarch"):
+        out = subprocess.run(["setarch", platform.machine(), "-R"] + cmd, capture_output=True, text=True)
+    return out
+
+
 def test_builder_threads_are_race_free_and_deterministic(checker_tsan):
     """150 000 triangles: subtree threads, the chunked binning of big nodes, the per-subtree dynamic program
     and the level-parallel node emission all run; ThreadSanitizer must stay silent and one thread must
     produce the very same nodes and leaf order as all of them."""
-    many = subprocess.run([checker_tsan, "150000", "11", "0.2"], capture_output=True, text=True)
+    many = run_tsan([checker_tsan, "150000", "11", "0.2"])
     assert many.returncode == 0 and many.stdout.startswith("OK") and "ThreadSanitizer" not in many.stderr, many.stdout + many.stderr
-    one = subprocess.run(["taskset", "-c", "0", checker_tsan, "150000", "11", "0.2"], capture_output=True, text=True)
+    one = run_tsan(["taskset", "-c", "0", checker_tsan, "150000", "11", "0.2"])
     assert one.returncode == 0 and one.stdout == many.stdout, one.stdout + one.stderr
 
 
 def test_two_level_cut_is_race_free_and_deterministic(checker_tsan):
     """The SAH cut of the two-level build splits leaves side by side and bins big leaves on several threads: ThreadSanitizer
     must stay silent, and one CPU must produce the very same flattened tree (hash of nodes + leaf order) as all of them."""
-    many = subprocess.run([checker_tsan, "150000", "11", "0.2", "64"], capture_output=True, text=True)
+    many = run_tsan([checker_tsan, "150000", "11", "0.2", "64"])
     assert many.returncode == 0 and many.stdout.startswith("OK") and "ThreadSanitizer" not in many.stderr, many.stdout + many.stderr
-    one = subprocess.run(["taskset", "-c", "0", checker_tsan, "150000", "11", "0.2", "64"], capture_output=True, text=True)
+    one = run_tsan(["taskset", "-c", "0", checker_tsan, "150000", "11", "0.2", "64"])
     assert one.returncode == 0 and one.stdout == many.stdout, one.stdout + one.stderr
-    odd = subprocess.run([checker_tsan, "150000", "11", "0.2", "37"], capture_output=True, text=True)  # not a power of two: the fullest leaves split first
+    odd = run_tsan([checker_tsan, "150000", "11", "0.2", "37"])  # not a power of two: the fullest leaves split first
     assert odd.returncode == 0 and odd.stdout.startswith("OK") and "ThreadSanitizer" not in odd.stderr, odd.stdout + odd.stderr
 
 

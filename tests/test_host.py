@@ -199,3 +199,9 @@ def test_bench_launches_its_own_ranks():
     # under an external launcher the environment decides; a mismatch is refused
     mism = subprocess.run([sys.executable, bench, "--gpus", "2", "--stub-step"], env=dict(env, WORLD_SIZE="1", RANK="0"), capture_output=True, text=True, timeout=120)
     assert mism.returncode != 0 and "WORLD_SIZE=1" in mism.stderr
+
+
+def test_bench_refuses_zero_steps():
+    """ms_per_step is the time of one timed step: a run without a timed step has none, and is refused before any set-up."""
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--stub-step"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 2 and "--steps must be at least 1" in res.stderr

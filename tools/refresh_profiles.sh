@@ -13,11 +13,11 @@ cd /tmp
 export TMPDIR=/tmp
 if [ $STAGE != B ]; then
 for W in tri1m_1080p_4spp terrain1m_1080p_4spp spheres8_1080p_4spp; do
-    python3 $R/bench.py --workload $W > $O/bench_$W.json 2> $O/bench_$W.err
+    python3 $R/bench.py --full --workload $W > $O/bench_$W.json 2> $O/bench_$W.err
     # kernel durations: one frame at a time (what roofline.avg_kernel_ms measures, with HIP events, on lane 0 alone) ...
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$W -- python3 $R/bench.py --workload $W --frames-in-flight 1 --no-traffic --no-cpu-baseline --no-parity > $O/bench_1lane_$W.json 2> /dev/null
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$W -- python3 $R/bench.py --full --workload $W --frames-in-flight 1 --no-traffic --no-cpu-baseline --no-parity > $O/bench_1lane_$W.json 2> /dev/null
     # ... and the default command (three frame lanes: kernels of different frames overlap and stretch each other)
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats3_$W -- python3 $R/bench.py --workload $W --no-traffic --no-cpu-baseline --no-parity > /dev/null 2>&1
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats3_$W -- python3 $R/bench.py --full --workload $W --no-traffic --no-cpu-baseline --no-parity > /dev/null 2>&1
     echo "done $W"
 done
 fi
