@@ -7,7 +7,7 @@
 // Everything GPU-side goes through librt_amd.so; this file contains no kernels and no fallbacks.
 //
 //   rt_host [--size WxH] [--yaw R] [--pitch R] [--pos x,y,z] [--move right,forward,up] [--spp N]
-//           [--scene default|soup:N] [--two-level] [--bounces N] [--seed N] [--frames N] [--out file.ppm|file.pfm]
+//           [--scene default|soup:N] [--two-level] [--bvh host|device] [--bounces N] [--seed N] [--frames N] [--out file.ppm|file.pfm]
 //           [--march 1|2|3] [--repeat x,y,z] [--mirror N[,reflectivity]] [--transmit N[,transparency[,index]]] [--inflight K]
 #include <chrono>
 #include <cmath>
@@ -16,6 +16,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "../include/rt_abi.h"
 
@@ -107,6 +109,7 @@ int main(int argc, char** argv) {
     std::string scene = "default", out = "frame.ppm";
     uint32_t march = 0, inflight = 0, mirror = 0;
     bool two_level = false;  // soup scenes: top-level BVH over 64 bottom-level chunks (rt_set_mesh_ex)
+    std::string bvh = "host";  // soup scenes: "device" uploads the mesh and builds the BVH on the GPU (rt_set_mesh_device)
     float repeat[3] = {0, 0, 0}, reflectivity = 0.5f, transparency = 0.5f, refraction_index = 1.0f;
     unsigned transmit = 0;
     for (int i = 1; i < argc; i++) {
@@ -128,10 +131,11 @@ int main(int argc, char** argv) {
         else if (a == "--mirror") std::sscanf(next(), "%u,%f", &mirror, &reflectivity);
         else if (a == "--transmit") std::sscanf(next(), "%u,%f,%f", &transmit, &transparency, &refraction_index);
         else if (a == "--two-level") two_level = true;
+        else if (a == "--bvh" && i + 1 < argc && (std::strcmp(argv[i + 1], "host") == 0 || std::strcmp(argv[i + 1], "device") == 0)) bvh = next();
         else if (a == "--inflight") inflight = (uint32_t)std::atoi(next());
         else {
             std::fprintf(stderr, "usage: rt_host [--size WxH] [--yaw R] [--pitch R] [--pos x,y,z] [--move r,f,u] [--spp N] "
-                                 "[--scene default|soup:N] [--two-level] [--bounces N] [--seed N] [--frames N] [--out file.ppm|file.pfm] "
+                                 "[--scene default|soup:N] [--two-level] [--bvh host|device] [--bounces N] [--seed N] [--frames N] [--out file.ppm|file.pfm] "
                                  "[--march 1|2|3] [--repeat x,y,z] [--mirror N[,reflectivity]] [--transmit N[,transparency[,index]]] [--inflight K]\n");
             return 2;
         }
@@ -164,8 +168,34 @@ int main(int argc, char** argv) {
         const uint32_t n = (uint32_t)std::atoi(scene.c_str() + 5);
         std::vector<float> verts, albedo, emission;
         soup_scene(n < 3 ? 3 : n, 1, n >= 500000 ? 0.08f : 0.25f, verts, albedo, emission);
-        const rt_mesh_options opt{two_level ? 2u : 1u, 0u};
-        if ((rc = rt_set_mesh_ex(ctx, verts.data(), albedo.data(), emission.data(), n < 3 ? 3 : n, &opt))) return fail(ctx, "rt_set_mesh_ex", rc);
+        const uint32_t n_tris = n < 3 ? 3 : n;
+        if (bvh == "device") {
+            if (two_level) {
+                std::fprintf(stderr, "rt_host: --bvh device builds a single-level BVH (no --two-level)\n");
+                rt_destroy(ctx);
+                return 2;
+            }
+            // the mesh as a producer on the GPU would hold it: device arrays, read by the build on the GPU
+            void* d[3] = {nullptr, nullptr, nullptr};
+            const std::vector<float>* src[3] = {&verts, &albedo, &emission};
+            hipError_t e = hipSuccess;
+            for (int k = 0; k < 3 && e == hipSuccess; k++) {
+                e = hipMalloc(&d[k], src[k]->size() * sizeof(float));
+                if (e == hipSuccess) e = hipMemcpy(d[k], src[k]->data(), src[k]->size() * sizeof(float), hipMemcpyHostToDevice);
+            }
+            rc = e == hipSuccess ? rt_set_mesh_device(ctx, d[0], d[1], d[2], n_tris) : 0;
+            for (void* p : d)
+                if (p) (void)hipFree(p);
+            if (e != hipSuccess) {
+                std::fprintf(stderr, "rt_host: mesh upload failed: %s\n", hipGetErrorString(e));
+                rt_destroy(ctx);
+                return 1;
+            }
+            if (rc) return fail(ctx, "rt_set_mesh_device", rc);
+        } else {
+            const rt_mesh_options opt{two_level ? 2u : 1u, 0u};
+            if ((rc = rt_set_mesh_ex(ctx, verts.data(), albedo.data(), emission.data(), n_tris, &opt))) return fail(ctx, "rt_set_mesh_ex", rc);
+        }
         prm.spp = spp;
         prm.bounces = bounces;
         prm.seed = seed;

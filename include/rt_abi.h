@@ -322,6 +322,18 @@ int rt_mesh_chunk_info(rt_ctx* ctx, uint32_t chunk, uint32_t* count, uint32_t* t
  * coordinate range of the mesh as first set (RT_ERR_INVALID otherwise: set the mesh again).  Transactional: on any error
  * other than RT_ERR_STATE the mesh is exactly as it was; RT_ERR_STATE means an upload failed and the mesh was dropped. */
 int rt_update_mesh_chunk(rt_ctx* ctx, uint32_t chunk, const float* verts, uint32_t n_tris);
+/* Path B mesh from device-resident arrays; the BVH is built on the GPU (LBVH -> compressed BVH8, the same node format as
+ * rt_set_mesh's, so frames are bit-identical to those of a host-built tree).  verts / albedo / emission have rt_set_mesh's
+ * layouts and are device pointers on the context's device (each allocation must hold the whole array).  They are read on
+ * the context's stream, after the work already enqueued there; the call is synchronous on return and does not reference
+ * them afterwards.  RT_ERR_INVALID, with the previous mesh untouched: a NULL, host or other-device pointer, n_tris outside
+ * [1, 2^28), or a non-finite vertex coordinate.  The result is a single-level mesh (rt_update_mesh_chunk: RT_ERR_STATE);
+ * rt_pt_stats.bvh_build_ms is the HIP-event time of the build's kernels.  The same input gives byte-identical trees. */
+int rt_set_mesh_device(rt_ctx* ctx, const void* verts_dev, const void* albedo_dev, const void* emission_dev, uint32_t n_tris);
+/* Test hook: node words (n_nodes x 20 u32, bvh_build.h layout) and leaf order (leaf position -> original triangle index,
+ * n_tris u32) of the current mesh, host- or device-built.  NULL outputs: only *n_nodes is written (capacity query);
+ * a non-NULL output whose capacity is too small: RT_ERR_INVALID.  No mesh: RT_ERR_STATE. */
+int rt_read_bvh(rt_ctx* ctx, uint32_t* nodes_out, uint32_t node_capacity, uint32_t* leaf_tris_out, uint32_t tri_capacity, uint32_t* n_nodes);
 /* Synchronous path-traced frame of the current view (rt_resize) into host memory.
  * Every |pos| component must be <= 32 x max(1, largest |vertex coordinate| of the mesh): that is the range
  * over which the BVH's conservative box padding covers the fp32 rounding of the ray/box test (beyond it the

@@ -733,6 +733,89 @@ int update_chunk_impl(Ctx* c, uint32_t chunk, const float* verts, uint32_t n_tri
     return RT_OK;
 }
 
+// a device allocation of `c`'s device that holds at least `bytes` bytes from p on
+int check_device_array(Ctx* c, const void* p, size_t bytes, const char* what) {
+    if (!p) return c->fail(RT_ERR_INVALID, "%s is NULL", what);
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return c->fail(RT_ERR_INVALID, "%s is not a device pointer", what);
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != c->device)
+        return c->fail(RT_ERR_INVALID, "%s is not device memory of device %d (memory type %d, device %d)", what, c->device, (int)a.type, a.device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return c->fail(RT_ERR_INVALID, "%s: allocation range unknown", what);
+    }
+    if (static_cast<const char*>(p) + bytes > static_cast<const char*>(base) + size)
+        return c->fail(RT_ERR_INVALID, "%s: the allocation holds fewer than the %zu bytes of %s", what, bytes, what);
+    return RT_OK;
+}
+
+int set_mesh_device_impl(Ctx* c, const void* verts, const void* albedo, const void* emission, uint32_t n_tris) {
+    if (n_tris == 0 || n_tris >= (1u << 28)) return c->fail(RT_ERR_INVALID, "n_tris %u out of [1, 2^28)", n_tris);
+    if (int rc = bind(c)) return rc;
+    if (int rc = check_device_array(c, verts, (size_t)n_tris * 36, "verts")) return rc;
+    if (int rc = check_device_array(c, albedo, (size_t)n_tris * 12, "albedo")) return rc;
+    if (int rc = check_device_array(c, emission, (size_t)n_tris * 12, "emission")) return rc;
+    // the new mesh is complete before the old one is dropped: any failure up to here leaves the context as it was
+    rt::DeviceMesh m;
+    if (int rc = rt::build_bvh_device(c, static_cast<const float*>(verts), static_cast<const float*>(albedo), static_cast<const float*>(emission), n_tris, &m))
+        return rc;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && c->aux_stream) e = hipStreamSynchronize(c->aux_stream);
+    if (e != hipSuccess) {
+        (void)hipFree(m.nodes);
+        (void)hipFree(m.tris);
+        (void)hipFree(m.albedo);
+        (void)hipFree(m.emission);
+        (void)hipFree(m.lights);
+        return c->fail(RT_ERR_HIP, "rt_set_mesh_device: %s", hipGetErrorString(e));
+    }
+    rt::frames_drop_mesh(c);  // frame-slot lanes render with this mesh
+    PtData& pt = c->pt;
+    free_mesh(pt);  // also pt.host: a device-built mesh is single-level
+    c->state_version++;
+    pt.d_nodes = m.nodes;
+    pt.d_tris = m.tris;
+    pt.d_albedo = m.albedo;
+    pt.d_emission = m.emission;
+    pt.d_lights = m.lights;
+    pt.cap_nodes = m.n_nodes;
+    pt.n_tris = n_tris;
+    pt.n_lights = m.n_lights;
+    pt.bvh_build_ms = m.build_ms;
+    pt.stats = rt_pt_stats{};
+    pt.stats.n_tris = n_tris;
+    pt.stats.n_lights = m.n_lights;
+    rt::BvhResult shape;  // what publish_bvh_stats reads: counts, padding, coordinate range
+    shape.n_nodes = m.n_nodes;
+    shape.depth = m.depth;
+    shape.stack_need = m.stack_need;
+    shape.pad = m.pad;
+    shape.maxabs = m.maxabs;
+    publish_bvh_stats(pt, shape);
+    return RT_OK;
+}
+
+int read_bvh_impl(Ctx* c, uint32_t* nodes_out, uint32_t node_capacity, uint32_t* leaf_tris_out, uint32_t tri_capacity, uint32_t* n_nodes) {
+    const PtData& pt = c->pt;
+    if (!pt.n_tris) return c->fail(RT_ERR_STATE, "no mesh has been set");
+    if (n_nodes) *n_nodes = pt.n_nodes;
+    if (nodes_out && node_capacity < pt.n_nodes) return c->fail(RT_ERR_INVALID, "nodes_out holds %u of %u nodes", node_capacity, pt.n_nodes);
+    if (leaf_tris_out && tri_capacity < pt.n_tris) return c->fail(RT_ERR_INVALID, "leaf_tris_out holds %u of %u triangles", tri_capacity, pt.n_tris);
+    if (!nodes_out && !leaf_tris_out) return RT_OK;
+    if (int rc = bind(c)) return rc;
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    if (nodes_out) RT_HIP(c, hipMemcpy(nodes_out, pt.d_nodes, (size_t)pt.n_nodes * 80, hipMemcpyDeviceToHost));
+    // leaf order = word 9 of every 48-byte triangle record (the original index), whichever builder made the mesh
+    if (leaf_tris_out)
+        RT_HIP(c, hipMemcpy2D(leaf_tris_out, 4, reinterpret_cast<const char*>(pt.d_tris) + 36, 48, 4, pt.n_tris, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 template <class F>
 int guarded(Ctx* c, const char* what, F&& f, bool drop_mesh = true) {  // drop_mesh = false: the callee has put the mesh back before it threw
     // the builder allocates host vectors sized by n_tris and starts std::threads: nothing may leave an entry point
@@ -786,6 +869,19 @@ int rt_update_mesh_chunk(rt_ctx* ctx, uint32_t chunk, const float* verts, uint32
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
     return guarded(c, "chunk rebuild", [&] { return update_chunk_impl(c, chunk, verts, n_tris); }, false);
+}
+
+int rt_set_mesh_device(rt_ctx* ctx, const void* verts_dev, const void* albedo_dev, const void* emission_dev, uint32_t n_tris) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    // the previous mesh is only replaced once the new one is complete: a failure leaves it in place
+    return guarded(c, "device mesh build", [&] { return set_mesh_device_impl(c, verts_dev, albedo_dev, emission_dev, n_tris); }, false);
+}
+
+int rt_read_bvh(rt_ctx* ctx, uint32_t* nodes_out, uint32_t node_capacity, uint32_t* leaf_tris_out, uint32_t tri_capacity, uint32_t* n_nodes) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    return read_bvh_impl(c, nodes_out, node_capacity, leaf_tris_out, tri_capacity, n_nodes);
 }
 
 int rt_render_pt(rt_ctx* ctx, const float rot[4], const float pos[3], const rt_pt_params* params, float* rgb_out) {

@@ -298,4 +298,18 @@ int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const 
 void pt_free(Ctx* c);
 void comm_free(Ctx* c);  // rt_abi_comm.hip
 
+// bvh_build_gpu.hip: path B mesh arrays built on the GPU from device-resident triangles (rt_set_mesh_device), on c->stream.
+// On success the five arrays belong to the caller; on failure nothing is allocated and nothing else has changed.
+struct DeviceMesh {
+    float4* nodes = nullptr;     // n_nodes x 80 B, bvh_build.h layout
+    float4* tris = nullptr;      // leaf order, 48 B per triangle (PtScene::tris)
+    float4* albedo = nullptr;    // leaf order
+    float4* emission = nullptr;  // leaf order
+    uint32_t* lights = nullptr;  // max(n_lights, 1) entries
+    uint32_t n_nodes = 0, n_lights = 0, depth = 0, stack_need = 0;
+    float pad = 0.0f, maxabs = 1.0f, build_ms = 0.0f;
+    size_t scratch_bytes = 0;  // peak temporary device memory of the build
+};
+int build_bvh_device(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out);
+
 }  // namespace rt

@@ -126,6 +126,7 @@ class Renderer:
     def __init__(self, device=0):
         self._lib = _lib.load()
         self._ctx = C.c_void_p()
+        self.device = int(device)
         rc = self._lib.rt_create(C.byref(self._ctx), int(device))
         if rc != 0:
             raise RtError(rc, self._lib.rt_last_error(None).decode())
@@ -304,6 +305,47 @@ class Renderer:
             raise ValueError("verts/albedo/emission disagree on the triangle count")
         opt = _lib.MeshOptions(bvh_levels, blas_chunks)
         self._check(self._lib.rt_set_mesh_ex(self._ctx, _fptr(verts), _fptr(albedo), _fptr(emission), len(verts), C.byref(opt)))
+
+    def set_mesh_device(self, verts, albedo, emission):
+        """Mesh from torch tensors on this renderer's device; the BVH is built on the GPU (rt_set_mesh_device).  float32,
+        contiguous, shapes (n, 9) / (n, 3) or flat.  Work torch has queued on its current stream is finished first."""
+        import torch
+
+        def check(t, name, width):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+            if t.dtype != torch.float32:
+                raise ValueError(f"{name} must be float32, got {t.dtype}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
+            if t.dim() == 2 and t.shape[1] == width:
+                return t.shape[0]
+            if t.dim() == 1 and t.numel() % width == 0:
+                return t.numel() // width
+            raise ValueError(f"{name} must have shape (n, {width}) or ({width} n,), got {tuple(t.shape)}")
+
+        n = check(verts, "verts", 9)
+        if check(albedo, "albedo", 3) != n or check(emission, "emission", 3) != n:
+            raise ValueError("verts/albedo/emission disagree on the triangle count")
+        if n == 0:
+            raise ValueError("the mesh has no triangles")
+        torch.cuda.current_stream(self.device).synchronize()  # writers on torch's stream are done before the build reads
+        self._check(self._lib.rt_set_mesh_device(self._ctx, C.c_void_p(verts.data_ptr()), C.c_void_p(albedo.data_ptr()),
+                                                 C.c_void_p(emission.data_ptr()), n))
+
+    def read_bvh(self):
+        """Test hook: (node words uint32 (n_nodes, 20), leaf order uint32 (n_tris,)) of the current mesh."""
+        n_nodes = C.c_uint32()
+        self._check(self._lib.rt_read_bvh(self._ctx, None, 0, None, 0, C.byref(n_nodes)))
+        n_tris = self.pt_stats()["n_tris"]
+        nodes = np.empty((n_nodes.value, 20), np.uint32)
+        leaf = np.empty(n_tris, np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        self._check(self._lib.rt_read_bvh(self._ctx, nodes.ctypes.data_as(u32), n_nodes.value, leaf.ctypes.data_as(u32), n_tris,
+                                          C.byref(n_nodes)))
+        return nodes, leaf
 
     def mesh_chunk(self, chunk):
         """Original triangle indices of bottom-level chunk `chunk` of a two-level mesh, in rt_update_mesh_chunk's order."""
