@@ -274,7 +274,7 @@ typedef struct rt_pt_params {
 typedef struct rt_pt_stats {
     uint32_t n_tris, n_nodes, bvh_depth, n_lights; /* n_nodes / bvh_depth of the compressed 8-wide BVH */
     uint32_t stack_need;       /* worst-case traversal stack entries for this BVH */
-    float bvh_build_ms;
+    float bvh_build_ms;        /* last build or refit of the mesh (rt_refit_mesh_device: HIP-event time of its kernels) */
     uint32_t stack_overflow;   /* must be 0: traversal stack never exceeded */
     uint64_t camera_rays, bounce_rays, shadow_rays; /* last render: rays handed to BVH traversal */
     uint64_t nodes_visited, tris_tested;            /* per-lane closest-hit traversal (pt_trace<closest>, alone or inside a fused launch): BVH node
@@ -330,6 +330,19 @@ int rt_update_mesh_chunk(rt_ctx* ctx, uint32_t chunk, const float* verts, uint32
  * [1, 2^28), or a non-finite vertex coordinate.  The result is a single-level mesh (rt_update_mesh_chunk: RT_ERR_STATE);
  * rt_pt_stats.bvh_build_ms is the HIP-event time of the build's kernels.  The same input gives byte-identical trees. */
 int rt_set_mesh_device(rt_ctx* ctx, const void* verts_dev, const void* albedo_dev, const void* emission_dev, uint32_t n_tris);
+/* New vertex positions for the current single-level mesh (rt_set_mesh with bvh_levels = 1, or rt_set_mesh_device): the
+ * tree's topology, leaf order, materials and light list stay; every box is recomputed on the GPU from the new vertices with
+ * the padding of a build (2e-5 x the new largest |coordinate|, at least 1) and quantised outward as a build does, so frames
+ * stay bit-identical to the oracle on the moved mesh and unchanged vertices give the tree byte for byte.  Works on host- and
+ * device-built trees; the tree's quality degrades as triangles move apart (rebuild then: DESIGN.md §6.10).  verts_dev has
+ * rt_set_mesh's layout (n_tris x 9 floats, original triangle order), is a device pointer on the context's device whose
+ * allocation holds n_tris x 36 bytes, and is read on the context's stream after the work already enqueued there; the call is
+ * synchronous on return.  The camera range of rt_render_pt* follows the new coordinates.  Errors, all with the mesh exactly as
+ * it was: RT_ERR_INVALID for a NULL, host or other-device pointer, a too short allocation, n_tris other than the mesh's, a
+ * non-finite coordinate; RT_ERR_STATE when there is no mesh or it is two-level (rt_update_mesh_chunk updates those);
+ * RT_ERR_OOM if the scratch (24 B per node, allocated by the first refit of a mesh, freed with it) cannot be allocated.  A HIP
+ * failure after the first write drops the mesh and returns RT_ERR_STATE, as rt_update_mesh_chunk does for a failed upload. */
+int rt_refit_mesh_device(rt_ctx* ctx, const void* verts_dev, uint32_t n_tris);
 /* Test hook: node words (n_nodes x 20 u32, bvh_build.h layout) and leaf order (leaf position -> original triangle index,
  * n_tris u32) of the current mesh, host- or device-built.  NULL outputs: only *n_nodes is written (capacity query);
  * a non-NULL output whose capacity is too small: RT_ERR_INVALID.  No mesh: RT_ERR_STATE. */

@@ -3,7 +3,9 @@
 // Produces exactly the node format of bvh_build.h (80-byte compressed 8-wide nodes, one triangle per leaf slot,
 // breadth-first order, inner children and leaf triangles consecutive per node), so the traversal kernels cannot tell
 // the difference.  The tree itself is an LBVH (Karras, "Maximizing Parallelism in the Construction of BVHs, Octrees,
-// and k-d Trees", HPG 2012) collapsed top-down into 8-wide nodes; stages and their launches: DESIGN.md §6.9.
+// and k-d Trees", HPG 2012) collapsed top-down into 8-wide nodes; stages and their launches: DESIGN.md §6.9.  The refit of a
+// single-level tree, host- or device-built, to new vertices (rt_refit_mesh_device) is here too: it shares the
+// validation and the quantiser with the build.
 //
 // Rules every kernel here keeps:
 //  - no data passes between workgroups inside a launch: every dependency is a launch boundary (no flags, no look-back,
@@ -14,6 +16,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "rt_internal.h"
@@ -487,24 +490,11 @@ __global__ __launch_bounds__(kThreads) void bvhd_plan(TreeView tv, const int32_t
     counts[w] = ((unsigned long long)inner << 32) | leaves;
 }
 
-// node words (quantised as write() of bvh_build.cpp: power-of-two scale per axis, floor / ceil outward in double), the next
-// level's binary nodes and the leaf order
-__global__ __launch_bounds__(kThreads) void bvhd_write(TreeView tv, const Plan* __restrict__ plan, const unsigned long long* __restrict__ excl,
-                                                       uint32_t count, uint32_t level_base, uint32_t tri_before, uint32_t node_cap,
-                                                       const unsigned long long* __restrict__ keys, uint32_t* __restrict__ nodes,
-                                                       int32_t* __restrict__ next_level, uint32_t* __restrict__ order) {
-    const uint32_t w = blockIdx.x * kThreads + threadIdx.x;
-    if (w >= count) return;
-    const Plan p = plan[w];
-    const unsigned long long ex = excl[w];
-    const uint32_t inner0 = (uint32_t)(ex >> 32), child_base = level_base + count + inner0, tri_base = tri_before + (uint32_t)ex;
-    DBox cb[8], nb;
-    box_empty(nb);
-    for (int s = 0; s < 8; s++) {
-        if (p.slot[s] == kEmpty) continue;
-        cb[s] = tv.box(p.slot[s]);
-        box_grow(nb, cb[s]);
-    }
+// quantisation of write() in bvh_build.cpp, the one copy that bvhd_write and the refit share so that they cannot drift: frame origin
+// nb.lo, a power-of-two scale per axis with 255 * scale >= extent, child planes floor / ceil outward in double, clamped to [0, 255];
+// a slot not in `occ` gets the inverted box (lo 255, hi 0).  Writes wd[0..2] (origin), wd[3] (exponent bytes; bits 24-31, imask,
+// are left 0) and wd[8..19] (planes); wd[4..7] are not touched
+__device__ __forceinline__ void quantise(const DBox& nb, const DBox* cb, uint32_t occ, uint32_t* wd) {
     uint32_t e_byte[3];
     double scale[3];
     for (int a = 0; a < 3; a++) {
@@ -515,22 +505,10 @@ __global__ __launch_bounds__(kThreads) void bvhd_write(TreeView tv, const Plan* 
         e_byte[a] = (uint32_t)(e + 127);
         scale[a] = ldexp(1.0, e);
     }
-    uint32_t wd[20];
-    uint32_t imask = 0, leafmask = 0, rank = 0, off = 0;
     uint8_t q[6][8];
     for (int s = 0; s < 8; s++) {
         for (int a = 0; a < 6; a++) q[a][s] = a < 3 ? 255 : 0;  // empty slot: inverted box
-        const int32_t r = p.slot[s];
-        if (r == kEmpty) continue;
-        if (r >= 0) {
-            imask |= 1u << s;
-            const uint32_t at = inner0 + rank++;
-            if (at < node_cap) next_level[at] = r;
-        } else {
-            leafmask |= 1u << s;
-            const uint32_t li = tri_base + off++;
-            if (li < tv.n) order[li] = (uint32_t)keys[(uint32_t)~r];  // low word of the key: original triangle index
-        }
+        if (!((occ >> s) & 1u)) continue;
         for (int a = 0; a < 3; a++) {
             double ql = floor(((double)cb[s].lo[a] - (double)nb.lo[a]) / scale[a]);
             double qh = ceil(((double)cb[s].hi[a] - (double)nb.lo[a]) / scale[a]);
@@ -543,15 +521,49 @@ __global__ __launch_bounds__(kThreads) void bvhd_write(TreeView tv, const Plan* 
     wd[0] = __float_as_uint(nb.lo[0]);
     wd[1] = __float_as_uint(nb.lo[1]);
     wd[2] = __float_as_uint(nb.lo[2]);
-    wd[3] = e_byte[0] | (e_byte[1] << 8) | (e_byte[2] << 16) | (imask << 24);
-    wd[4] = child_base;
-    wd[5] = tri_base;
-    wd[6] = leafmask;
-    wd[7] = 0;
+    wd[3] = e_byte[0] | (e_byte[1] << 8) | (e_byte[2] << 16);
     for (int a = 0; a < 6; a++) {
         wd[8 + 2 * a] = q[a][0] | (q[a][1] << 8) | (q[a][2] << 16) | ((uint32_t)q[a][3] << 24);
         wd[9 + 2 * a] = q[a][4] | (q[a][5] << 8) | (q[a][6] << 16) | ((uint32_t)q[a][7] << 24);
     }
+}
+
+// node words (quantise()), the next level's binary nodes and the leaf order
+__global__ __launch_bounds__(kThreads) void bvhd_write(TreeView tv, const Plan* __restrict__ plan, const unsigned long long* __restrict__ excl,
+                                                       uint32_t count, uint32_t level_base, uint32_t tri_before, uint32_t node_cap,
+                                                       const unsigned long long* __restrict__ keys, uint32_t* __restrict__ nodes,
+                                                       int32_t* __restrict__ next_level, uint32_t* __restrict__ order) {
+    const uint32_t w = blockIdx.x * kThreads + threadIdx.x;
+    if (w >= count) return;
+    const Plan p = plan[w];
+    const unsigned long long ex = excl[w];
+    const uint32_t inner0 = (uint32_t)(ex >> 32), child_base = level_base + count + inner0, tri_base = tri_before + (uint32_t)ex;
+    DBox cb[8], nb;
+    box_empty(nb);
+    uint32_t occ = 0, imask = 0, leafmask = 0, rank = 0, off = 0;
+    for (int s = 0; s < 8; s++) {
+        const int32_t r = p.slot[s];
+        if (r == kEmpty) continue;
+        occ |= 1u << s;
+        cb[s] = tv.box(r);
+        box_grow(nb, cb[s]);
+        if (r >= 0) {
+            imask |= 1u << s;
+            const uint32_t at = inner0 + rank++;
+            if (at < node_cap) next_level[at] = r;
+        } else {
+            leafmask |= 1u << s;
+            const uint32_t li = tri_base + off++;
+            if (li < tv.n) order[li] = (uint32_t)keys[(uint32_t)~r];  // low word of the key: original triangle index
+        }
+    }
+    uint32_t wd[20];
+    quantise(nb, cb, occ, wd);
+    wd[3] |= imask << 24;
+    wd[4] = child_base;
+    wd[5] = tri_base;
+    wd[6] = leafmask;
+    wd[7] = 0;
     const uint32_t node = level_base + w;
     if (node >= node_cap) return;
     uint4* dst = reinterpret_cast<uint4*>(nodes + (size_t)node * 20);
@@ -590,6 +602,101 @@ __global__ __launch_bounds__(kThreads) void bvhd_lights(const uint32_t* __restri
                                                         uint32_t n, uint32_t n_lights, uint32_t* __restrict__ lights) {
     const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
     if (t < n && flag[t] && slot[t] < n_lights) lights[slot[t]] = leaf_pos[t];
+}
+
+// ---- refit (rt_refit_mesh_device): new vertices, the same topology and leaf order; DESIGN.md §6.10 ------------------------------
+constexpr int kRefitTopThreads = 512;  // the top levels: one workgroup, a barrier between levels (512: 256 VGPRs, no spill)
+constexpr uint32_t kRefitTopNodes = 1024;  // levels from the root down that hold at most this many nodes each are refitted by it
+constexpr uint32_t kRefitTopMax = 16;
+
+struct RefitTop {  // level j of the top = nodes [start[j], start[j + 1]), j < levels
+    uint32_t start[kRefitTopMax + 1];
+    uint32_t levels;
+};
+
+// triangle record of leaf position li: words 0-8 from the new vertices of triangle t = word 9 (edges formed in fp32 as in
+// bvhd_payload / set_mesh_impl), words 9-11 (index, light flag) kept.  Coalesced record traffic, gathered vertex reads
+__global__ __launch_bounds__(kThreads) void bvhr_tris(const float* __restrict__ v, uint32_t n, float4* __restrict__ tris) {
+    const uint32_t li = blockIdx.x * kThreads + threadIdx.x;
+    if (li >= n) return;
+    const float4 w2 = tris[3 * (size_t)li + 2];
+    const uint32_t t = __float_as_uint(w2.y);
+    if (t >= n) return;
+    const float* p = v + 9 * (size_t)t;
+    float x[9];
+    for (int i = 0; i < 9; i++) x[i] = p[i];
+    float e1[3], e2[3];
+    for (int a = 0; a < 3; a++) {
+        e1[a] = x[3 + a] - x[a];
+        e2[a] = x[6 + a] - x[a];
+    }
+    tris[3 * (size_t)li] = make_float4(x[0], x[1], x[2], e1[0]);
+    tris[3 * (size_t)li + 1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
+    tris[3 * (size_t)li + 2] = make_float4(e2[2], w2.y, w2.z, w2.w);
+}
+
+// padded box of the triangle at leaf position li, from its record: tri_box's expression (v0 + e1 = p0 + (p1 - p0))
+__device__ __forceinline__ DBox record_box(const float4* __restrict__ tris, uint32_t li, float pad) {
+    const float4 r0 = tris[3 * (size_t)li], r1 = tris[3 * (size_t)li + 1], r2 = tris[3 * (size_t)li + 2];
+    const float v0[3] = {r0.x, r0.y, r0.z}, e1[3] = {r0.w, r1.x, r1.y}, e2[3] = {r1.z, r1.w, r2.x};
+    DBox b;
+    for (int a = 0; a < 3; a++) {
+        const float p0 = v0[a], p1 = p0 + e1[a], p2 = p0 + e2[a];
+        b.lo[a] = fminf(p0, fminf(p1, p2)) - pad;
+        b.hi[a] = fmaxf(p0, fmaxf(p1, p2)) + pad;
+    }
+    return b;
+}
+
+// node k: every slot's exact box (a leaf slot's padded triangle box, an inner slot's box as its child stored it one level deeper),
+// their union, the quantised frame and planes (words 0-3 with imask kept, words 8-19; words 4-7 untouched) and the node's exact
+// box for its parent.  Indices come from the node's own words and are checked before they are used
+__device__ __forceinline__ void refit_node(uint32_t* __restrict__ nodes, const float4* __restrict__ tris, uint32_t n, uint32_t n_nodes, float pad,
+                                           DBox* __restrict__ box, uint32_t k) {
+    uint4* nd = reinterpret_cast<uint4*>(nodes + (size_t)k * 20);
+    const uint32_t w3 = nd[0].w;
+    const uint4 topo = nd[1];  // child_base, tri_base, leafmask, 0
+    const uint32_t imask = w3 >> 24, leafmask = topo.z & 0xffu & ~imask;
+    DBox cb[8], nb;
+    box_empty(nb);
+    uint32_t rank = 0, off = 0;
+    for (int s = 0; s < 8; s++) {
+        box_empty(cb[s]);
+        if ((imask >> s) & 1u) {
+            const uint32_t ch = topo.x + rank++;
+            if (ch < n_nodes) cb[s] = box[ch];
+        } else if ((leafmask >> s) & 1u) {
+            const uint32_t li = topo.y + off++;
+            if (li < n) cb[s] = record_box(tris, li, pad);
+        } else {
+            continue;
+        }
+        box_grow(nb, cb[s]);
+    }
+    uint32_t wd[20];
+    quantise(nb, cb, imask | leafmask, wd);
+    nd[0] = make_uint4(wd[0], wd[1], wd[2], wd[3] | (w3 & 0xff000000u));
+    nd[2] = make_uint4(wd[8], wd[9], wd[10], wd[11]);
+    nd[3] = make_uint4(wd[12], wd[13], wd[14], wd[15]);
+    nd[4] = make_uint4(wd[16], wd[17], wd[18], wd[19]);
+    box[k] = nb;
+}
+
+// one level [k0, k1), one thread per node; the level below was finished by the previous launch
+__global__ __launch_bounds__(kThreads) void bvhr_level(uint32_t* __restrict__ nodes, const float4* __restrict__ tris, uint32_t n, uint32_t n_nodes,
+                                                       float pad, DBox* __restrict__ box, uint32_t k0, uint32_t k1) {
+    const uint32_t k = k0 + blockIdx.x * kThreads + threadIdx.x;
+    if (k < k1 && k < n_nodes) refit_node(nodes, tris, n, n_nodes, pad, box, k);
+}
+
+// the top levels, deepest first, by one workgroup (a barrier between levels, no other workgroup involved)
+__global__ __launch_bounds__(kRefitTopThreads) void bvhr_top(uint32_t* __restrict__ nodes, const float4* __restrict__ tris, uint32_t n, uint32_t n_nodes,
+                                                             float pad, DBox* __restrict__ box, RefitTop top) {
+    for (int j = (int)top.levels - 1; j >= 0; j--) {
+        const uint32_t k1 = min(top.start[j + 1], n_nodes);
+        for (uint32_t k = top.start[j] + threadIdx.x; k < k1; k += kRefitTopThreads) refit_node(nodes, tris, n, n_nodes, pad, box, k);
+        __syncthreads();
+    }
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
@@ -783,6 +890,7 @@ int build(Ctx* c, const float* verts, const float* albedo, const float* emission
     RT_HIP(c, hipMemcpyAsync(s.level[0], &root, sizeof root, hipMemcpyHostToDevice, c->stream));
     uint32_t level_base = 0, level_size = 1, tri_count = 0, depth = 0;
     int lv = 0;
+    out->level_start.assign(1, 0u);
     while (level_size) {
         if (++depth > kMaxLevels || (size_t)level_base + level_size > m) return c->fail(RT_ERR_STATE, "device BVH build: the collapse did not converge (internal error)");
         hipLaunchKernelGGL(bvhd_plan, dim3(blocks_for(level_size)), dim3(kThreads), 0, c->stream, tv, (const int32_t*)s.level[lv], level_size, s.plan, s.counts);
@@ -794,6 +902,7 @@ int build(Ctx* c, const float* verts, const float* albedo, const float* emission
         unsigned long long tot = 0;
         if (int rc = read_back(c, &tot, s.total, 1)) return rc;
         level_base += level_size;
+        out->level_start.push_back(level_base);
         level_size = (uint32_t)(tot >> 32);
         tri_count += (uint32_t)tot;
         lv ^= 1;
@@ -847,7 +956,68 @@ int build(Ctx* c, const float* verts, const float* albedo, const float* emission
     return RT_OK;
 }
 
+size_t refit_scratch_bytes(uint32_t n_nodes) {
+    Bump b;
+    b.take<float>(kReduceBlocks);
+    b.take<uint32_t>(kReduceBlocks);
+    b.take<DBox>(n_nodes);
+    return b.used;
+}
+
 }  // namespace
+
+size_t refit_scratch_size(uint32_t n_nodes) { return refit_scratch_bytes(n_nodes); }
+
+int refit_measure(Ctx* c, const float* verts, uint32_t n, void* scratch, hipEvent_t begin, float* maxabs) {
+    Bump bump{static_cast<char*>(scratch), 0};
+    float* part_max = bump.take<float>(kReduceBlocks);
+    uint32_t* part_bad = bump.take<uint32_t>(kReduceBlocks);
+    const uint32_t red_blocks = std::min<uint32_t>(kReduceBlocks, blocks_for(n));
+    RT_HIP(c, hipEventRecord(begin, c->stream));
+    hipLaunchKernelGGL(bvhd_validate, dim3(red_blocks), dim3(kThreads), 0, c->stream, verts, n, part_max, part_bad);
+    BVHD_LAUNCH(c);
+    // ONE read-back: the two partial arrays are adjacent in the scratch (part_bad starts 4 * kReduceBlocks bytes after part_max)
+    static_assert((kReduceBlocks * sizeof(float)) % 256 == 0, "part_bad must follow part_max directly");
+    std::vector<uint32_t> part(2 * kReduceBlocks);
+    if (int rc = read_back(c, part.data(), reinterpret_cast<const uint32_t*>(part_max), part.size())) return rc;
+    float m = 0.0f;
+    uint32_t bad = 0;
+    for (uint32_t b = 0; b < red_blocks; b++) {
+        float x;
+        std::memcpy(&x, &part[b], 4);
+        m = std::max(m, x);
+        bad |= part[kReduceBlocks + b];
+    }
+    if (bad) return c->fail(RT_ERR_INVALID, "vertex data is not finite");
+    *maxabs = m;
+    return RT_OK;
+}
+
+int refit_write(Ctx* c, const float* verts, uint32_t n, float pad, uint32_t n_nodes, float4* nodes, float4* tris, const std::vector<uint32_t>& level_start,
+                void* scratch, hipEvent_t begin, hipEvent_t end, float* ms) {
+    const uint32_t levels = (uint32_t)level_start.size() - 1u;
+    if (level_start.size() < 2 || level_start.front() != 0 || level_start.back() != n_nodes)
+        return c->fail(RT_ERR_STATE, "refit: the mesh's level ranges do not describe its %u nodes (internal error)", n_nodes);
+    Bump bump{static_cast<char*>(scratch), 0};
+    (void)bump.take<float>(kReduceBlocks);
+    (void)bump.take<uint32_t>(kReduceBlocks);
+    DBox* box = bump.take<DBox>(n_nodes);
+    uint32_t* words = reinterpret_cast<uint32_t*>(nodes);
+    hipLaunchKernelGGL(bvhr_tris, dim3(blocks_for(n)), dim3(kThreads), 0, c->stream, verts, n, tris);
+    RefitTop top{};
+    while (top.levels < levels && top.levels < kRefitTopMax && level_start[top.levels + 1] - level_start[top.levels] <= kRefitTopNodes) top.levels++;
+    for (uint32_t j = 0; j <= top.levels; j++) top.start[j] = level_start[j];
+    for (uint32_t j = levels; j-- > top.levels;) {
+        const uint32_t k0 = level_start[j], k1 = level_start[j + 1];
+        hipLaunchKernelGGL(bvhr_level, dim3(blocks_for(k1 - k0)), dim3(kThreads), 0, c->stream, words, (const float4*)tris, n, n_nodes, pad, box, k0, k1);
+    }
+    if (top.levels) hipLaunchKernelGGL(bvhr_top, dim3(1), dim3(kRefitTopThreads), 0, c->stream, words, (const float4*)tris, n, n_nodes, pad, box, top);
+    BVHD_LAUNCH(c);
+    RT_HIP(c, hipEventRecord(end, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    RT_HIP(c, hipEventElapsedTime(ms, begin, end));
+    return RT_OK;
+}
 
 int build_bvh_device(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out) {
     Owned own;

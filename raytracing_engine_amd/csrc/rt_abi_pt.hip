@@ -65,6 +65,12 @@ void free_mesh(PtData& pt) {
     dfree(pt.d_emission);
     dfree(pt.d_lights);
     dfree(pt.d_spill);
+    dfree(pt.d_refit);
+    for (hipEvent_t& e : pt.ev_refit) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    pt.level_start.clear();
     pt.spill_words = 0;
     pt.host.reset();
     pt.cap_nodes = 0;
@@ -519,6 +525,24 @@ void pack_leaf_range(const rt::BvhResult& bvh, const float* v0, const float* e1,
     }
 }
 
+// level ranges of a breadth-first tree (both builders emit one): level 0 = the root, level d + 1 = the inner children of level d,
+// consecutive.  Empty if the words do not describe such a tree of n_nodes nodes
+std::vector<uint32_t> level_starts(const std::vector<uint32_t>& nodes, uint32_t n_nodes) {
+    std::vector<uint32_t> start{0};
+    uint32_t first = 0, count = n_nodes ? 1u : 0u;
+    while (count) {
+        if ((uint64_t)first + count > n_nodes) return {};
+        uint64_t next = 0;
+        for (uint32_t k = first; k < first + count; k++) next += (uint32_t)__builtin_popcount(nodes[(size_t)k * 20 + 3] >> 24);
+        first += count;
+        start.push_back(first);
+        if (next > n_nodes) return {};
+        count = (uint32_t)next;
+    }
+    if (first != n_nodes) return {};
+    return start;
+}
+
 void publish_bvh_stats(PtData& pt, const rt::BvhResult& bvh) {
     pt.n_nodes = bvh.n_nodes;
     pt.bvh_depth = bvh.depth;
@@ -614,6 +638,7 @@ int set_mesh_impl(Ctx* c, const float* verts, const float* albedo, const float* 
         pt.stats.ms_build_tlas = (float)pt.host->tl.ms_tlas;
         pt.stats.ms_build_flatten = (float)pt.host->tl.ms_flatten;
     }
+    if (levels == 1u) pt.level_start = level_starts(bvh.nodes, bvh.n_nodes);  // what a refit walks
     publish_bvh_stats(pt, bvh);
     return RT_OK;
 }
@@ -787,6 +812,7 @@ int set_mesh_device_impl(Ctx* c, const void* verts, const void* albedo, const vo
     pt.n_tris = n_tris;
     pt.n_lights = m.n_lights;
     pt.bvh_build_ms = m.build_ms;
+    pt.level_start.swap(m.level_start);
     pt.stats = rt_pt_stats{};
     pt.stats.n_tris = n_tris;
     pt.stats.n_lights = m.n_lights;
@@ -797,6 +823,48 @@ int set_mesh_device_impl(Ctx* c, const void* verts, const void* albedo, const vo
     shape.pad = m.pad;
     shape.maxabs = m.maxabs;
     publish_bvh_stats(pt, shape);
+    return RT_OK;
+}
+
+int refit_mesh_device_impl(Ctx* c, const void* verts, uint32_t n_tris) {
+    PtData& pt = c->pt;
+    if (!pt.n_tris) return c->fail(RT_ERR_STATE, "no mesh has been set");
+    if (pt.host) return c->fail(RT_ERR_STATE, "rt_refit_mesh_device needs a single-level mesh (a two-level mesh updates with rt_update_mesh_chunk)");
+    if (pt.borrowed_mesh || pt.level_start.size() < 2) return c->fail(RT_ERR_STATE, "rt_refit_mesh_device: the mesh is not refittable by this context");
+    if (n_tris != pt.n_tris) return c->fail(RT_ERR_INVALID, "the mesh holds %u triangles, n_tris is %u", pt.n_tris, n_tris);
+    if (int rc = bind(c)) return rc;
+    if (int rc = check_device_array(c, verts, (size_t)n_tris * 36, "verts")) return rc;
+    if (!pt.d_refit) {  // first refit of this mesh: scratch and timing events stay until the mesh is freed
+        if (hipMalloc(&pt.d_refit, rt::refit_scratch_size(pt.n_nodes)) != hipSuccess) {
+            (void)hipGetLastError();
+            pt.d_refit = nullptr;
+            return c->fail(RT_ERR_OOM, "refit scratch for %u nodes", pt.n_nodes);
+        }
+        for (hipEvent_t& e : pt.ev_refit)
+            if (!e) RT_HIP(c, hipEventCreate(&e));
+    }
+    // 1. validate and measure: the last point at which the call may refuse; nothing of the mesh has been written
+    const float* v = static_cast<const float*>(verts);
+    float maxabs = 0.0f;
+    if (int rc = rt::refit_measure(c, v, n_tris, pt.d_refit, pt.ev_refit[0], &maxabs)) return rc;
+    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    // 2. commit: frame-slot lanes are idled (they re-borrow the mesh on their next submit), then the arrays are rewritten in place
+    rt::frames_drop_mesh(c);
+    c->state_version++;
+    const float m = std::max(maxabs, 1.0f), pad = 2e-5f * m;  // build_bvh's padding, for the NEW coordinate range
+    float ms = 0.0f;
+    if (int rc = rt::refit_write(c, v, n_tris, pad, pt.n_nodes, pt.d_nodes, pt.d_tris, pt.level_start, pt.d_refit, pt.ev_refit[0], pt.ev_refit[1], &ms)) {
+        (void)rc;
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipGetLastError();
+        const std::string why = c->err;
+        free_mesh(pt);  // boxes and records may disagree: no frame may be traced against them
+        return c->fail(RT_ERR_STATE, "refit failed after the mesh was written (%s): the mesh has been dropped, set it again", why.c_str());
+    }
+    pt.bvh_maxabs = m;
+    pt.bvh_pad = pad;
+    pt.bvh_build_ms = ms;
+    pt.stats.bvh_build_ms = ms;
     return RT_OK;
 }
 
@@ -876,6 +944,13 @@ int rt_set_mesh_device(rt_ctx* ctx, const void* verts_dev, const void* albedo_de
     if (!c) return RT_ERR_INVALID;
     // the previous mesh is only replaced once the new one is complete: a failure leaves it in place
     return guarded(c, "device mesh build", [&] { return set_mesh_device_impl(c, verts_dev, albedo_dev, emission_dev, n_tris); }, false);
+}
+
+int rt_refit_mesh_device(rt_ctx* ctx, const void* verts_dev, uint32_t n_tris) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    // every refusal comes before the first write; a HIP failure after it drops the mesh itself (RT_ERR_STATE)
+    return guarded(c, "mesh refit", [&] { return refit_mesh_device_impl(c, verts_dev, n_tris); }, false);
 }
 
 int rt_read_bvh(rt_ctx* ctx, uint32_t* nodes_out, uint32_t node_capacity, uint32_t* leaf_tris_out, uint32_t tri_capacity, uint32_t* n_nodes) {

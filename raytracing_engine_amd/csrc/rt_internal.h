@@ -199,6 +199,10 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     float4* d_emission = nullptr;
     uint32_t* d_lights = nullptr;
     uint32_t stack_need = 0;  // worst-case traversal stack occupancy reported by the builder
+    // single-level meshes: level d of the breadth-first tree = nodes [level_start[d], level_start[d + 1]) (empty: no refit)
+    std::vector<uint32_t> level_start;
+    void* d_refit = nullptr;  // rt_refit_mesh_device scratch (refit_scratch_size), allocated by the first refit, freed with the mesh
+    hipEvent_t ev_refit[2] = {nullptr, nullptr};
     unsigned long long* d_spill = nullptr;
     size_t spill_words = 0, spill_half = 0;
     hipEvent_t ev_shaded = nullptr, ev_shadowed = nullptr;  // ordering between the main and the auxiliary stream
@@ -309,7 +313,18 @@ struct DeviceMesh {
     uint32_t n_nodes = 0, n_lights = 0, depth = 0, stack_need = 0;
     float pad = 0.0f, maxabs = 1.0f, build_ms = 0.0f;
     size_t scratch_bytes = 0;  // peak temporary device memory of the build
+    std::vector<uint32_t> level_start;  // PtData::level_start of the tree
 };
 int build_bvh_device(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out);
+
+// bvh_build_gpu.hip: refit of a single-level mesh to new vertices (rt_refit_mesh_device), on c->stream, in two steps.
+// refit_measure validates verts and returns the largest |coordinate| (build_bvh's maxabs, before the max with 1); it writes only
+// the scratch, so a refusal (RT_ERR_INVALID: a non-finite coordinate) leaves the mesh as it was.  refit_write rewrites words 0-8 of
+// every triangle record and every node's box words bottom-up, one launch per level (the top levels in one workgroup), and is
+// synchronous on return; *ms = HIP-event time from `begin` (recorded by refit_measure) to its last kernel.
+size_t refit_scratch_size(uint32_t n_nodes);  // exact node boxes (24 B per node) + the validation partials
+int refit_measure(Ctx* c, const float* verts, uint32_t n, void* scratch, hipEvent_t begin, float* maxabs);
+int refit_write(Ctx* c, const float* verts, uint32_t n, float pad, uint32_t n_nodes, float4* nodes, float4* tris, const std::vector<uint32_t>& level_start,
+                void* scratch, hipEvent_t begin, hipEvent_t end, float* ms);
 
 }  // namespace rt

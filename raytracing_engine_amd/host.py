@@ -306,26 +306,31 @@ class Renderer:
         opt = _lib.MeshOptions(bvh_levels, blas_chunks)
         self._check(self._lib.rt_set_mesh_ex(self._ctx, _fptr(verts), _fptr(albedo), _fptr(emission), len(verts), C.byref(opt)))
 
+    def _device_rows(self, t, name, width):
+        """Rows of `width` floats in torch tensor `t`, which must be float32, contiguous, on this renderer's device and of shape
+        (n, width) or flat; ValueError otherwise."""
+        import torch
+
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
+        if t.dim() == 2 and t.shape[1] == width:
+            return t.shape[0]
+        if t.dim() == 1 and t.numel() % width == 0:
+            return t.numel() // width
+        raise ValueError(f"{name} must have shape (n, {width}) or ({width} n,), got {tuple(t.shape)}")
+
     def set_mesh_device(self, verts, albedo, emission):
         """Mesh from torch tensors on this renderer's device; the BVH is built on the GPU (rt_set_mesh_device).  float32,
         contiguous, shapes (n, 9) / (n, 3) or flat.  Work torch has queued on its current stream is finished first."""
         import torch
 
-        def check(t, name, width):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
-            if t.dtype != torch.float32:
-                raise ValueError(f"{name} must be float32, got {t.dtype}")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be contiguous")
-            if t.device.type != "cuda" or t.device.index != self.device:
-                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
-            if t.dim() == 2 and t.shape[1] == width:
-                return t.shape[0]
-            if t.dim() == 1 and t.numel() % width == 0:
-                return t.numel() // width
-            raise ValueError(f"{name} must have shape (n, {width}) or ({width} n,), got {tuple(t.shape)}")
-
+        check = self._device_rows
         n = check(verts, "verts", 9)
         if check(albedo, "albedo", 3) != n or check(emission, "emission", 3) != n:
             raise ValueError("verts/albedo/emission disagree on the triangle count")
@@ -334,6 +339,16 @@ class Renderer:
         torch.cuda.current_stream(self.device).synchronize()  # writers on torch's stream are done before the build reads
         self._check(self._lib.rt_set_mesh_device(self._ctx, C.c_void_p(verts.data_ptr()), C.c_void_p(albedo.data_ptr()),
                                                  C.c_void_p(emission.data_ptr()), n))
+
+    def refit_mesh_device(self, verts):
+        """New vertex positions (torch tensor as set_mesh_device's verts, original triangle order) for the current single-level
+        mesh: the tree keeps its topology and leaf order, its boxes are recomputed on the GPU (rt_refit_mesh_device).  Work
+        torch has queued on its current stream is finished first."""
+        import torch
+
+        n = self._device_rows(verts, "verts", 9)
+        torch.cuda.current_stream(self.device).synchronize()  # writers on torch's stream are done before the refit reads
+        self._check(self._lib.rt_refit_mesh_device(self._ctx, C.c_void_p(verts.data_ptr()), n))
 
     def read_bvh(self):
         """Test hook: (node words uint32 (n_nodes, 20), leaf order uint32 (n_tris,)) of the current mesh."""
