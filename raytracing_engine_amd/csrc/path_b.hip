@@ -500,7 +500,11 @@ __global__ __launch_bounds__(kAppendThreads) void pt_generate(const PtFrame f, P
 // The owner learns its new tmax / its occlusion after the flush; until then it may enter nodes a tighter tmax would
 // have culled, which never changes a result (boxes are conservative, the hit is a minimum over
 // every triangle tested).  The ring is drained before any lane retires, so a ray's result is complete when it is stored.
-constexpr uint32_t kPoolRing = 128;  // groups; a flush is due at <= 64, a round adds <= 64
+// Ring bound: a round starts with at most kPoolRing - 64 groups pending and adds at most 64.  A flush tests 64 groups but puts
+// back every one with further hit slots (all 64 of them, possibly), so one pass per round would let the ring grow by up to 64
+// a round; the flush is therefore repeated until the bound holds again (each pass takes one hit slot from every group it tests,
+// and flush_at <= 64 makes it fire whenever more than 64 groups are pending).
+constexpr uint32_t kPoolRing = 128;  // groups
 // The pool is read and written by different lanes of ONE wave: DS operations of a wave execute in program order, so no
 // barrier instruction is needed; pool_sync() only keeps the COMPILER from moving LDS accesses across the phase boundaries
 // (the pointers are not volatile: volatile accesses would stay on generic pointers and become flat_* instructions).
@@ -734,7 +738,8 @@ __device__ __forceinline__ void trace_queue(const PtScene& sc, const PtState& st
             }
             waited = P.count ? waited + 1u : 0u;
             if (P.count >= flush_at || waited >= wait_max) {
-                pool_test<ANY, COUNT>(sc.tris, r, P, lane, tc);
+                do pool_test<ANY, COUNT>(sc.tris, r, P, lane, tc);
+                while (P.count > kPoolRing - 64u);
                 flushed = true;
                 waited = 0;
             }

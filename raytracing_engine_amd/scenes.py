@@ -122,3 +122,73 @@ def terrain_scene(grid=708, seed=1, light_emission=(6.0, 6.0, 6.0)):
     albedo = np.concatenate([albedo, np.zeros((2, 3), f)])
     emission = np.concatenate([emission, np.tile(np.asarray(light_emission, f), (2, 1))])
     return verts, albedo, emission
+
+
+def sliver_stack_scene(n_layers=2048, n_targets=48, seed=1):
+    """Adversarial scene for the traversal's leaf-hit buffers: n_layers parallel triangles stacked along the view axis (y in [4, 6]),
+    every one covering the half x + z < 0 of the square x, z in [-8, 8].  A ray through the other half passes through every
+    layer's box and hits none, so every leaf-parent node it visits hands it up to 8 leaf hits and its tmax never culls.
+    n_targets small rectangles (two triangles each) at hashed depths inside the stack, in the half x + z > 0, give such rays
+    different closest hits; a backdrop at y = 10 and an emitter between the camera and the stack (out of a 90-degree view from
+    the origin) send bounce and shadow rays back through it.  Camera at the origin looking +Y.
+    Returns (verts[n,9], albedo[n,3], emission[n,3]) float32."""
+    f = np.float32
+    n = int(n_layers)
+    ys = (np.float64(4.0) + 2.0 * (np.arange(n, dtype=np.float64) + 0.5) / n).astype(f)
+    layers = np.zeros((n, 9), f)
+    layers[:, 0], layers[:, 2] = -8.0, -8.0  # (x, z) = (-8, -8), (8, -8), (-8, 8)
+    layers[:, 3], layers[:, 5] = 8.0, -8.0
+    layers[:, 6], layers[:, 8] = -8.0, 8.0
+    layers[:, 1] = layers[:, 4] = layers[:, 7] = ys
+    u = [_uniform(seed, 40 + k, n_targets) for k in range(6)]
+    tris = [layers]
+    for i in range(n_targets):  # centre in the miss half, 0.4 .. 1.6 wide, depth strictly inside the stack
+        cx, cz = f(u[0][i] * 7.0 - 0.5), f(u[1][i] * 7.0 - 0.5)
+        cx, cz = (cx, cz) if cx + cz > 1.0 else (f(cx + 2.0), f(cz + 2.0))
+        hx, hz = f(0.2 + 0.6 * u[2][i]), f(0.2 + 0.6 * u[3][i])
+        y = f(4.05 + 1.9 * u[4][i])
+        tris.append(np.array(_quad(np.array([cx - hx, y, cz - hz], f), np.array([cx + hx, y, cz - hz], f),
+                                   np.array([cx + hx, y, cz + hz], f), np.array([cx - hx, y, cz + hz], f)), f))
+    back = _quad(np.array([-20, 10, -20], f), np.array([20, 10, -20], f), np.array([20, 10, 20], f), np.array([-20, 10, 20], f))
+    light = _quad(np.array([2, 1, 2], f), np.array([2, 1, 5], f), np.array([5, 1, 5], f), np.array([5, 1, 2], f))
+    tris += [np.array(back, f), np.array(light, f)]
+    verts = np.concatenate(tris).astype(f)
+    m = len(verts)
+    albedo = np.empty((m, 3), f)
+    albedo[:n] = (0.7, 0.7, 0.7)
+    tu = [_uniform(seed, 50 + k, m - n - 4) for k in range(3)]
+    albedo[n:m - 4] = np.stack(tu, 1) * f(0.7) + f(0.2)
+    albedo[m - 4:m - 2] = (0.6, 0.6, 0.6)
+    albedo[m - 2:] = 0.0
+    emission = np.zeros((m, 3), f)
+    emission[m - 2:] = (20.0, 20.0, 20.0)
+    return verts, albedo, emission
+
+
+def deep_scene(n_clusters=48, per_cluster=24, ratio=0.45, spread=0.2, scale=4.0, seed=1):
+    """Adversarial scene for the traversal stack and the BVH's depth: n_clusters clusters of per_cluster small triangles at
+    geometrically shrinking sizes and distances from the origin (cluster k: centre ratio^k * scale * (0.5, 1, 0.3), triangles
+    within spread * ratio^k * scale of it).  Binary SAH splits peel one cluster per level, down to the builder's depth cap, and
+    the 8-wide collapse spends a node's slots on the big peeled cluster rather than on the small rest, so the compressed tree
+    is about as deep as the binary one.  A backdrop at y = 3 * scale and an emitter above close the scene; a camera at the
+    origin looking +Y starts inside every deep box.  Returns (verts[n,9], albedo[n,3], emission[n,3]) float32."""
+    f = np.float32
+    m = int(n_clusters) * int(per_cluster)
+    k = np.repeat(np.arange(n_clusters, dtype=np.float64), per_cluster)
+    s = (ratio ** k * scale)[:, None]
+    u = [_uniform(seed, 60 + j, m).astype(np.float64) * 2.0 - 1.0 for j in range(9)]
+    v0 = np.array([0.5, 1.0, 0.3]) * s + np.stack(u[0:3], 1) * spread * s
+    v1 = v0 + np.stack(u[3:6], 1) * spread * s
+    v2 = v0 + np.stack(u[6:9], 1) * spread * s
+    verts = np.concatenate([v0, v1, v2], 1).astype(f)
+    a = [_uniform(seed, 70 + j, m) for j in range(3)]
+    albedo = (np.stack(a, 1) * f(0.6) + f(0.3)).astype(f)
+    S, Y = f(4.0 * scale), f(3.0 * scale)
+    back = _quad(np.array([-S, Y, -S], f), np.array([S, Y, -S], f), np.array([S, Y, S], f), np.array([-S, Y, S], f))
+    light = _quad(np.array([-1, 1, 1.5], f) * f(scale), np.array([-1, 2, 1.5], f) * f(scale), np.array([1, 2, 1.5], f) * f(scale),
+                  np.array([1, 1, 1.5], f) * f(scale))
+    verts = np.concatenate([verts, np.array(back + light, f)])
+    albedo = np.concatenate([albedo, np.array([[0.6, 0.6, 0.6]] * 2 + [[0, 0, 0]] * 2, f)])
+    emission = np.zeros((m + 4, 3), f)
+    emission[m + 2:] = (12.0, 12.0, 12.0)
+    return verts, albedo, emission

@@ -1,6 +1,7 @@
 // bvh_check.cpp — host-side structural check of the compressed 8-wide BVH (csrc/bvh_build.cpp),
 // built with -fsanitize=address,undefined by tests/test_bvh_build_host.py.  No GPU involved.
 //   bvh_check <n_tris> <seed> <edge> [chunks [chunk-to-rebuild]]
+//   bvh_check --mesh <file>    (the mesh: raw float32, 9 per triangle = v0, v1, v2 as rt_set_mesh takes them)
 // Verifies: the leaf order is a permutation; every triangle is reachable exactly once; inner-child
 // indexing (child_base + popcount(imask below slot)) and leaf indexing (one triangle per leaf slot, tri_base +
 // popcount(leafmask below slot)) are consistent; empty slots hold inverted boxes; every leaf triangle lies inside its de-quantised child box; depth <= stack_need - 1.
@@ -18,23 +19,53 @@ static uint32_t hash32(uint32_t x) {
     return x;
 }
 
+// A mesh file as rt_set_mesh takes it: edges are formed as rt_abi_pt.hip forms them (v1 - v0, v2 - v0 in float).
+static bool load_mesh(const char* path, std::vector<float>& v0, std::vector<float>& e1, std::vector<float>& e2) {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return false;
+    std::vector<float> raw;
+    float buf[9];
+    while (std::fread(buf, sizeof(float), 9, f) == 9) raw.insert(raw.end(), buf, buf + 9);
+    const bool whole = std::feof(f) && !std::ferror(f);
+    std::fclose(f);
+    const size_t n = raw.size() / 9;
+    if (!whole || n == 0) return false;
+    v0.resize(3 * n);
+    e1.resize(3 * n);
+    e2.resize(3 * n);
+    for (size_t i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++) {
+            v0[3 * i + a] = raw[9 * i + a];
+            e1[3 * i + a] = raw[9 * i + 3 + a] - raw[9 * i + a];
+            e2[3 * i + a] = raw[9 * i + 6 + a] - raw[9 * i + a];
+        }
+    return true;
+}
+
 int main(int argc, char** argv) {
-    const uint32_t n = argc > 1 ? (uint32_t)std::atoi(argv[1]) : 1000;
+    const bool from_file = argc > 2 && std::strcmp(argv[1], "--mesh") == 0;
+    std::vector<float> v0, e1, e2;
+    if (from_file && !load_mesh(argv[2], v0, e1, e2)) { std::puts("FAIL cannot read the mesh file"); return 1; }
+    const uint32_t n = from_file ? (uint32_t)(v0.size() / 3) : argc > 1 ? (uint32_t)std::atoi(argv[1]) : 1000;
     const uint32_t seed = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 1;
     const float edge = argc > 3 ? (float)std::atof(argv[3]) : 0.5f;
-    std::vector<float> v0(3 * (size_t)n), e1(3 * (size_t)n), e2(3 * (size_t)n);
+    if (!from_file) {
+        v0.resize(3 * (size_t)n);
+        e1.resize(3 * (size_t)n);
+        e2.resize(3 * (size_t)n);
+    }
     uint32_t s = hash32(seed);
     auto u = [&]() { s = hash32(s + 0x9e3779b9u); return (float)(s >> 8) * 0x1p-24f; };
-    for (size_t i = 0; i < (size_t)n * 3; i++) {
+    for (size_t i = 0; !from_file && i < (size_t)n * 3; i++) {
         v0[i] = u() * 20.0f - 10.0f;
         e1[i] = (u() * 2.0f - 1.0f) * edge;
         e2[i] = (u() * 2.0f - 1.0f) * edge;
     }
-    if (n > 10) {  // degenerate and duplicate triangles must survive
+    if (!from_file && n > 10) {  // degenerate and duplicate triangles must survive
         for (int a = 0; a < 3; a++) e1[3 * 5 + a] = e2[3 * 5 + a] = 0.0f;
         for (int a = 0; a < 3; a++) { v0[3 * 7 + a] = v0[3 * 6 + a]; e1[3 * 7 + a] = e1[3 * 6 + a]; e2[3 * 7 + a] = e2[3 * 6 + a]; }
     }
-    const uint32_t chunks = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 0;  // > 0: two-level build (top level over `chunks` bottom-level BVHs, flattened)
+    const uint32_t chunks = !from_file && argc > 4 ? (uint32_t)std::atoi(argv[4]) : 0;  // > 0: two-level build (top level over `chunks` bottom-level BVHs, flattened)
     rt::BvhResult b;
     rt::TwoLevelBvh tl;
     if (chunks) {
@@ -56,12 +87,15 @@ int main(int argc, char** argv) {
     struct Item { uint32_t node, level; };
     std::vector<Item> stack{{0, 1}};
     uint32_t max_level = 0, n_visited = 0;
+    std::vector<uint32_t> level_nodes;  // nodes per level (root = level 1)
     while (!stack.empty()) {
         const Item it = stack.back();
         stack.pop_back();
         if (it.node >= b.n_nodes) { std::puts("FAIL node index out of range"); return 1; }
         n_visited++;
         max_level = it.level > max_level ? it.level : max_level;
+        if (level_nodes.size() < it.level) level_nodes.resize(it.level, 0u);
+        level_nodes[it.level - 1]++;
         const uint32_t* w = &b.nodes[(size_t)it.node * 20];
         float p[3];
         std::memcpy(p, w, 12);
@@ -103,6 +137,8 @@ int main(int argc, char** argv) {
     unsigned long long h = 1469598103934665603ull;  // FNV-1a over the node words and the leaf order: the builder's whole output
     for (uint32_t w : b.nodes) h = (h ^ w) * 1099511628211ull;
     for (uint32_t w : b.order) h = (h ^ w) * 1099511628211ull;
-    std::printf("OK n=%u nodes=%u depth=%u tris/node=%.2f hash=%016llx\n", n, b.n_nodes, b.depth, (double)n / b.n_nodes, h);
+    uint32_t small_levels = 0;  // levels from the root down with at most 1024 nodes each (what the GPU refit gives one workgroup)
+    while (small_levels < level_nodes.size() && level_nodes[small_levels] <= 1024u) small_levels++;
+    std::printf("OK n=%u nodes=%u depth=%u tris/node=%.2f hash=%016llx small_levels=%u\n", n, b.n_nodes, b.depth, (double)n / b.n_nodes, h, small_levels);
     return 0;
 }
