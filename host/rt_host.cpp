@@ -9,6 +9,7 @@
 //   rt_host [--size WxH] [--yaw R] [--pitch R] [--pos x,y,z] [--move right,forward,up] [--spp N]
 //           [--scene default|soup:N] [--two-level] [--bvh host|device] [--bounces N] [--seed N] [--frames N] [--out file.ppm|file.pfm]
 //           [--march 1|2|3] [--repeat x,y,z] [--mirror N[,reflectivity]] [--transmit N[,transparency[,index]]] [--inflight K]
+//           [--surfaces mirror_frac,glass_frac[,ior]]   (soup scenes: mirror and glass triangles)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -112,6 +113,8 @@ int main(int argc, char** argv) {
     std::string bvh = "host";  // soup scenes: "device" uploads the mesh and builds the BVH on the GPU (rt_set_mesh_device)
     float repeat[3] = {0, 0, 0}, reflectivity = 0.5f, transparency = 0.5f, refraction_index = 1.0f;
     unsigned transmit = 0;
+    float surf[3] = {0.0f, 0.0f, 1.5f};  // soup scenes: mirror fraction, glass fraction, index of refraction (rt_set_mesh_surfaces)
+    bool surfaces = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -130,13 +133,15 @@ int main(int argc, char** argv) {
         else if (a == "--repeat") std::sscanf(next(), "%f,%f,%f", &repeat[0], &repeat[1], &repeat[2]);
         else if (a == "--mirror") std::sscanf(next(), "%u,%f", &mirror, &reflectivity);
         else if (a == "--transmit") std::sscanf(next(), "%u,%f,%f", &transmit, &transparency, &refraction_index);
+        else if (a == "--surfaces") surfaces = std::sscanf(next(), "%f,%f,%f", &surf[0], &surf[1], &surf[2]) >= 2;
         else if (a == "--two-level") two_level = true;
         else if (a == "--bvh" && i + 1 < argc && (std::strcmp(argv[i + 1], "host") == 0 || std::strcmp(argv[i + 1], "device") == 0)) bvh = next();
         else if (a == "--inflight") inflight = (uint32_t)std::atoi(next());
         else {
             std::fprintf(stderr, "usage: rt_host [--size WxH] [--yaw R] [--pitch R] [--pos x,y,z] [--move r,f,u] [--spp N] "
                                  "[--scene default|soup:N] [--two-level] [--bvh host|device] [--bounces N] [--seed N] [--frames N] [--out file.ppm|file.pfm] "
-                                 "[--march 1|2|3] [--repeat x,y,z] [--mirror N[,reflectivity]] [--transmit N[,transparency[,index]]] [--inflight K]\n");
+                                 "[--march 1|2|3] [--repeat x,y,z] [--mirror N[,reflectivity]] [--transmit N[,transparency[,index]]] [--inflight K] "
+                                 "[--surfaces mirror_frac,glass_frac[,ior]]\n");
             return 2;
         }
     }
@@ -195,6 +200,17 @@ int main(int argc, char** argv) {
         } else {
             const rt_mesh_options opt{two_level ? 2u : 1u, 0u};
             if ((rc = rt_set_mesh_ex(ctx, verts.data(), albedo.data(), emission.data(), n_tris, &opt))) return fail(ctx, "rt_set_mesh_ex", rc);
+        }
+        if (surfaces) {  // same kinds as raytracing_engine_amd/scenes.py soup_surfaces: stream 12 of the counter hash, the light stays Lambert
+            std::vector<uint32_t> kind(n_tris, RT_SURFACE_LAMBERT);
+            std::vector<float> ior(n_tris, surf[2]);
+            const float m = surf[0], g = surf[0] + surf[1];
+            const uint32_t base = hash32(1u * 0x9E3779B9u + 12u);
+            for (uint32_t i = 0; i + 2 < n_tris; i++) {
+                const float u = (float)(hash32(i + base) >> 8) * 0x1p-24f;
+                kind[i] = u < m ? RT_SURFACE_MIRROR : u < g ? RT_SURFACE_GLASS : RT_SURFACE_LAMBERT;
+            }
+            if ((rc = rt_set_mesh_surfaces(ctx, kind.data(), ior.data(), n_tris))) return fail(ctx, "rt_set_mesh_surfaces", rc);
         }
         prm.spp = spp;
         prm.bounces = bounces;

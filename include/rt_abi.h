@@ -343,6 +343,22 @@ int rt_set_mesh_device(rt_ctx* ctx, const void* verts_dev, const void* albedo_de
  * RT_ERR_OOM if the scratch (24 B per node, allocated by the first refit of a mesh, freed with it) cannot be allocated.  A HIP
  * failure after the first write drops the mesh and returns RT_ERR_STATE, as rt_update_mesh_chunk does for a failed upload. */
 int rt_refit_mesh_device(rt_ctx* ctx, const void* verts_dev, uint32_t n_tris);
+/* Surface of every triangle of the current mesh.  Until this is called every triangle is a Lambert reflector
+ * (§6.4).  kind[n_tris], original triangle order: RT_SURFACE_LAMBERT; RT_SURFACE_MIRROR (perfect reflection, tinted by the
+ * albedo); RT_SURFACE_GLASS (a dielectric interface of index ior[i], 1 <= ior <= 4: Fresnel-weighted choice between reflection
+ * and refraction, tinted by the albedo, albedo 1 = clear glass; the ray enters on the side e1 x e2 points to, so closed solids
+ * need outward winding).  Emissive triangles stay lights whatever their kind.  Mirror and glass vertices take no next-event
+ * estimation (shadow rays are still blocked by them); a light reached through them is counted when the path hits it.  ior is
+ * read only where kind is GLASS and may be NULL when no kind is; kind == NULL resets the mesh to all Lambert.  Host arrays,
+ * copied.  Works on every mesh (host-built single- and two-level, device-built); kept by rt_refit_mesh_device and
+ * rt_update_mesh_chunk; any rt_set_mesh* starts the mesh all Lambert again.  Runs on the context's stream after the work already
+ * enqueued there and is synchronous on return.  Errors, with the surfaces exactly as they were: RT_ERR_STATE (no mesh),
+ * RT_ERR_INVALID (n_tris other than the mesh's, a kind above 2, a GLASS entry whose ior is not finite or outside [1, 4],
+ * ior == NULL while some kind is GLASS), RT_ERR_OOM.  A HIP failure after the first write drops the mesh (RT_ERR_STATE). */
+#define RT_SURFACE_LAMBERT 0u
+#define RT_SURFACE_MIRROR 1u
+#define RT_SURFACE_GLASS 2u
+int rt_set_mesh_surfaces(rt_ctx* ctx, const uint32_t* kind, const float* ior, uint32_t n_tris);
 /* Test hook: node words (n_nodes x 20 u32, bvh_build.h layout) and leaf order (leaf position -> original triangle index,
  * n_tris u32) of the current mesh, host- or device-built.  NULL outputs: only *n_nodes is written (capacity query);
  * a non-NULL output whose capacity is too small: RT_ERR_INVALID.  No mesh: RT_ERR_STATE. */

@@ -69,6 +69,31 @@ __device__ __forceinline__ v3 cosine_dir(v3 n, float u1, float u2) {
               __builtin_fmaf(n.z, z, __builtin_fmaf(b2.z, y, b1.z * x)));
 }
 
+// ---- spec §6.11: mirror and glass vertices ---------------------------------------------------------
+// w = the triangle's surface word (albedo.w): < 0 mirror, >= 1 glass of index w.  n = the shading normal, already turned
+// against d (flipped: it was; the ray leaves the glass then).  u = rnd(key, depth, 7).  Returns the continuation
+// direction; below = true for a refraction, whose origin lies on the far side of the surface.
+__device__ __forceinline__ v3 delta_dir(v3 d, v3 n, float w, bool flipped, float u, bool& below) {
+    const float c = -dot(n, d);
+    below = false;
+    if (w > 0.0f) {
+        const float eta = flipped ? w : 1.0f / w;
+        const float s2 = (eta * eta) * __builtin_fmaf(-c, c, 1.0f);
+        if (s2 < 1.0f) {  // otherwise total internal reflection
+            const float ct = __builtin_sqrtf(1.0f - s2);
+            const float a = eta * c, b = eta * ct;
+            const float rs = (a - ct) / (a + ct), rp = (c - b) / (c + b);
+            const float F = __builtin_fmaf(rs, rs, rp * rp) * 0.5f;
+            if (!(u < F)) {
+                below = true;
+                const float k = a - ct;
+                return mk(__builtin_fmaf(n.x, k, eta * d.x), __builtin_fmaf(n.y, k, eta * d.y), __builtin_fmaf(n.z, k, eta * d.z));
+            }
+        }
+    }
+    return fma3(n, c + c, d);
+}
+
 // ---- spec §6.3: ray / triangle -------------------------------------------------------------------
 __device__ __forceinline__ bool tri_test(v3 o, v3 d, v3 v0, v3 e1, v3 e2, float& t_out) {
     const v3 pvec = cross(d, e2);
@@ -1615,6 +1640,9 @@ __global__ __launch_bounds__(256) void pt_trace_packet_ia(const PtScene sc, cons
 }
 
 // ---- shade ----------------------------------------------------------------------------------------
+// SURF = false: every triangle is a Lambert reflector or a light (§6.4).  SURF = true: also mirror and glass triangles
+// (§6.11, albedo.w != 0); thr.w = 1 marks a path whose last vertex was one of them, so the light it hits next is counted.
+template <bool SURF>
 __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, const PtFrame f, PtState st, const uint32_t* __restrict__ queue,
                                                            const uint32_t* __restrict__ count_ptr, uint32_t depth, uint32_t* __restrict__ next_queue,
                                                            uint32_t* __restrict__ next_ctr, uint32_t sort_rays) {
@@ -1653,7 +1681,7 @@ __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, 
             } else {
                 const float4 ta = sc.tris[(size_t)li * 3 + 0], tb = sc.tris[(size_t)li * 3 + 1], tc = sc.tris[(size_t)li * 3 + 2];
                 if (__float_as_uint(tc.z) != 0u) {  // emissive (flag in the triangle record); lights are seen directly only by camera rays
-                    if (depth == 0) {
+                    if (depth == 0 || (SURF && T.w != 0.0f)) {  // and by rays that leave a mirror or glass vertex
                         const float4 em = sc.emission[li];
                         L.x = __builtin_fmaf(T.x, em.x, L.x);
                         L.y = __builtin_fmaf(T.y, em.y, L.y);
@@ -1663,7 +1691,8 @@ __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, 
                 } else {
                     const float4 alb = sc.albedo[li];
                     v3 nrm = normalize(cross(mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x)));
-                    if (dot(nrm, d) > 0.0f) nrm = -nrm;
+                    const bool flipped = dot(nrm, d) > 0.0f;
+                    if (flipped) nrm = -nrm;
                     const v3 pt = fma3(d, hrec.x, o);
                     const v3 po = fma3(nrm, f.ray_eps, pt);
                     // path id -> rng key
@@ -1671,7 +1700,17 @@ __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, 
                     uint32_t px, py, lx, ly, k;
                     slot_pixel(f, slot, px, py, lx, ly, k);
                     const uint32_t key = path_key(py * f.width + px, s, f.seed);
-                    if (sc.n_lights > 0) {  // next-event estimation
+                    const bool delta = SURF && alb.w != 0.0f;  // mirror or glass: no next-event estimation; on as a bounce ray or the path ends
+                    if (delta && depth < f.bounces) {
+                        bool below;
+                        const v3 nd = delta_dir(d, nrm, alb.w, flipped, rnd(key, depth, 7), below);
+                        const v3 no = below ? fma3(nrm, -f.ray_eps, pt) : po;
+                        bounce = true;
+                        st.ray_o[pid] = make_float4(no.x, no.y, no.z, 0.0f);
+                        st.ray_d[pid] = make_float4(nd.x, nd.y, nd.z, 0.0f);
+                        st.thr[pid] = make_float4(T.x * alb.x, T.y * alb.y, T.z * alb.z, 1.0f);
+                    }
+                    if (!delta && sc.n_lights > 0) {  // next-event estimation
                         uint32_t kk = (uint32_t)(rnd(key, depth, 2) * (float)sc.n_lights);
                         if (kk > sc.n_lights - 1) kk = sc.n_lights - 1;
                         const uint32_t lt = sc.lights[kk];
@@ -1694,7 +1733,7 @@ __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, 
                             scn = make_float4(((T.x * alb.x) * le.x) * w, ((T.y * alb.y) * le.y) * w, ((T.z * alb.z) * le.z) * w, 0.0f);
                         }
                     }
-                    if (depth < f.bounces) {
+                    if (!delta && depth < f.bounces) {
                         const v3 nd = cosine_dir(nrm, rnd(key, depth, 5), rnd(key, depth, 6));
                         bounce = true;
                         st.ray_o[pid] = make_float4(po.x, po.y, po.z, 0.0f);
@@ -1808,6 +1847,17 @@ __global__ __launch_bounds__(256) void pt_trace_rays(const PtScene sc, const flo
     }
 }
 
+// ---- surfaces (rt_set_mesh_surfaces, §6.11) -------------------------------------------------------
+// albedo.w of every leaf position from the surface words in original triangle order: word 9 of the triangle record names
+// the triangle, whichever builder wrote the records.  surf == nullptr: every triangle Lambert (0)
+__global__ __launch_bounds__(256) void pt_scatter_surfaces(const float4* __restrict__ tris, const float* __restrict__ surf, float4* __restrict__ albedo,
+                                                           uint32_t n) {
+    const uint32_t li = blockIdx.x * 256u + threadIdx.x;
+    if (li >= n) return;
+    const uint32_t t = __float_as_uint(tris[(size_t)li * 3 + 2].y);
+    reinterpret_cast<float*>(albedo)[(size_t)li * 4 + 3] = surf && t < n ? surf[t] : 0.0f;
+}
+
 // ---- launchers ------------------------------------------------------------------------------------
 int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* queue, uint32_t* ctr) {
     hipLaunchKernelGGL(pt_generate, dim3((f.n_paths + kAppendThreads - 1u) / kAppendThreads), dim3(kAppendThreads), 0, c->stream, f, st, queue, ctr);
@@ -1895,9 +1945,19 @@ int launch_pt_trace_packet(Ctx* c, const PtScene& sc, const PtFrame& f, const Pt
 }
 
 int launch_pt_shade(Ctx* c, const PtScene& sc, const PtFrame& f, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr,
-                    uint32_t depth, uint32_t* next_queue, uint32_t* next_ctr, uint32_t grid, uint32_t sort_rays) {
-    hipLaunchKernelGGL(pt_shade, dim3(grid), dim3(kAppendThreads), 0, c->stream, sc, f, st, queue, count_ptr, depth, next_queue, next_ctr,
-                       sort_rays);
+                    uint32_t depth, uint32_t* next_queue, uint32_t* next_ctr, uint32_t grid, uint32_t sort_rays, bool surfaces) {
+    if (surfaces)
+        hipLaunchKernelGGL(pt_shade<true>, dim3(grid), dim3(kAppendThreads), 0, c->stream, sc, f, st, queue, count_ptr, depth, next_queue, next_ctr,
+                           sort_rays);
+    else
+        hipLaunchKernelGGL(pt_shade<false>, dim3(grid), dim3(kAppendThreads), 0, c->stream, sc, f, st, queue, count_ptr, depth, next_queue, next_ctr,
+                           sort_rays);
+    RT_HIP(c, hipGetLastError());
+    return RT_OK;
+}
+
+int launch_pt_scatter_surfaces(Ctx* c, const float4* tris, const float* surf, float4* albedo, uint32_t n) {
+    hipLaunchKernelGGL(pt_scatter_surfaces, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, tris, surf, albedo, n);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }

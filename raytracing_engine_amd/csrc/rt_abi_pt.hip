@@ -74,6 +74,7 @@ void free_mesh(PtData& pt) {
     pt.spill_words = 0;
     pt.host.reset();
     pt.cap_nodes = 0;
+    pt.has_surfaces = false;
     pt.n_tris = pt.n_nodes = pt.n_lights = 0;
     pt.stats = rt_pt_stats{};
 }
@@ -319,7 +320,9 @@ int render_pt_common(Ctx* c, const float rot[4], const float pos[3], const rt_pt
             {
                 rt::RoctxRange rr("rt.path_b.shade depth", d);
                 tm.begin(2);
-                if (int rc = rt::launch_pt_shade(c, sc, f, pt.st, d == 0 && packet ? nullptr : q, ctr_d + rt::PT_CTR_COUNT, d, qn, ctr_n, grid_stride, prm->tune_sort_rays)) return rc;
+                if (int rc = rt::launch_pt_shade(c, sc, f, pt.st, d == 0 && packet ? nullptr : q, ctr_d + rt::PT_CTR_COUNT, d, qn, ctr_n, grid_stride, prm->tune_sort_rays,
+                                                   pt.has_surfaces))
+                    return rc;
                 tm.end();
             }
             if (pt.n_lights) {
@@ -454,6 +457,7 @@ void pt_borrow_mesh(Ctx* lane, const Ctx* owner) {  // owner == nullptr: only fo
     if (!owner || !owner->pt.n_tris) return;
     const PtData& s = owner->pt;
     d.borrowed_mesh = true;
+    d.has_surfaces = s.has_surfaces;
     d.n_tris = s.n_tris;
     d.n_nodes = s.n_nodes;
     d.n_lights = s.n_lights;
@@ -502,9 +506,10 @@ int rt_default_pt_params(rt_pt_params* p) {
 
 namespace {
 
-// leaf-order records [li0, li1) of the device triangle / material arrays from the host copies
-void pack_leaf_range(const rt::BvhResult& bvh, const float* v0, const float* e1, const float* e2, const float* albedo, const float* emission, size_t li0,
-                     size_t li1, float* tris, float* alb, float* emi) {
+// leaf-order records [li0, li1) of the device triangle / material arrays from the host copies; surf (may be NULL = all Lambert):
+// albedo.w per original triangle
+void pack_leaf_range(const rt::BvhResult& bvh, const float* v0, const float* e1, const float* e2, const float* albedo, const float* emission,
+                     const float* surf, size_t li0, size_t li1, float* tris, float* alb, float* emi) {
     for (size_t li = li0; li < li1; li++) {
         const uint32_t t = bvh.order[li];
         float* r = &tris[12 * (li - li0)];
@@ -521,7 +526,8 @@ void pack_leaf_range(const rt::BvhResult& bvh, const float* v0, const float* e1,
             alb[4 * (li - li0) + a] = albedo[3 * (size_t)t + a];
             emi[4 * (li - li0) + a] = emission[3 * (size_t)t + a];
         }
-        alb[4 * (li - li0) + 3] = emi[4 * (li - li0) + 3] = 0.0f;
+        alb[4 * (li - li0) + 3] = surf ? surf[t] : 0.0f;
+        emi[4 * (li - li0) + 3] = 0.0f;
     }
 }
 
@@ -598,7 +604,7 @@ int set_mesh_impl(Ctx* c, const float* verts, const float* albedo, const float* 
 
     // leaf-order triangle records + materials; lights in ascending original index
     std::vector<float> tris(12 * n), alb(4 * n), emi(4 * n);
-    pack_leaf_range(bvh, v0.data(), e1.data(), e2.data(), albedo, emission, 0, n, tris.data(), alb.data(), emi.data());
+    pack_leaf_range(bvh, v0.data(), e1.data(), e2.data(), albedo, emission, nullptr, 0, n, tris.data(), alb.data(), emi.data());
     std::vector<uint32_t> leaf_pos(n);
     for (size_t li = 0; li < n; li++) leaf_pos[bvh.order[li]] = (uint32_t)li;
     std::vector<uint32_t> lights, light_ids;
@@ -719,7 +725,8 @@ int update_chunk_impl(Ctx* c, uint32_t chunk, const float* verts, uint32_t n_tri
         tris.resize(12 * (size_t)count);
         alb.resize(4 * (size_t)count);
         emi.resize(4 * (size_t)count);
-        pack_leaf_range(bvh, h.v0.data(), h.e1.data(), h.e2.data(), h.albedo.data(), h.emission.data(), li0, li1, tris.data(), alb.data(), emi.data());
+        pack_leaf_range(bvh, h.v0.data(), h.e1.data(), h.e2.data(), h.albedo.data(), h.emission.data(), h.surf.empty() ? nullptr : h.surf.data(), li0, li1,
+                        tris.data(), alb.data(), emi.data());  // the surfaces stay with their triangles
         if (!h.light_ids.empty()) {  // lights are listed by leaf position, in ascending original index
             bool moved = false;
             for (size_t li = li0; li < li1 && !moved; li++) moved = std::binary_search(h.light_ids.begin(), h.light_ids.end(), bvh.order[li]);
@@ -868,6 +875,63 @@ int refit_mesh_device_impl(Ctx* c, const void* verts, uint32_t n_tris) {
     return RT_OK;
 }
 
+// DESIGN.md §6.11.  Everything is checked on the host before anything is written: a refusal leaves the surfaces as they were
+int set_surfaces_impl(Ctx* c, const uint32_t* kind, const float* ior, uint32_t n_tris) {
+    PtData& pt = c->pt;
+    if (!pt.n_tris || pt.borrowed_mesh) return c->fail(RT_ERR_STATE, "no mesh has been set");
+    if (n_tris != pt.n_tris) return c->fail(RT_ERR_INVALID, "the mesh holds %u triangles, n_tris is %u", pt.n_tris, n_tris);
+    // surface word per triangle, the leaf-order albedo.w: 0 Lambert, -1 mirror, eta glass.  Empty: all Lambert
+    std::vector<float> w;
+    if (kind) {
+        w.assign(n_tris, 0.0f);
+        bool any = false;
+        for (uint32_t i = 0; i < n_tris; i++) {
+            if (kind[i] == RT_SURFACE_LAMBERT) continue;
+            if (kind[i] == RT_SURFACE_MIRROR) {
+                w[i] = -1.0f;
+            } else if (kind[i] == RT_SURFACE_GLASS) {
+                if (!ior) return c->fail(RT_ERR_INVALID, "triangle %u is glass and ior is NULL", i);
+                if (!(std::isfinite(ior[i]) && ior[i] >= 1.0f && ior[i] <= 4.0f))
+                    return c->fail(RT_ERR_INVALID, "triangle %u: index of refraction %g outside [1, 4]", i, (double)ior[i]);
+                w[i] = ior[i];
+            } else {
+                return c->fail(RT_ERR_INVALID, "triangle %u: surface kind %u (0 .. 2)", i, kind[i]);
+            }
+            any = true;
+        }
+        if (!any) w.clear();
+    }
+    if (int rc = bind(c)) return rc;
+    float* d_w = nullptr;
+    if (!w.empty() && !dalloc(d_w, w.size())) {
+        (void)hipGetLastError();
+        return c->fail(RT_ERR_OOM, "surface words of %u triangles", n_tris);
+    }
+    if (c->aux_stream) {
+        const hipError_t e = hipStreamSynchronize(c->aux_stream);
+        if (e != hipSuccess) {
+            dfree(d_w);
+            return c->fail(RT_ERR_HIP, "rt_set_mesh_surfaces: %s", hipGetErrorString(e));
+        }
+    }
+    // commit: frame-slot lanes are idled (they re-borrow the mesh and its flag on their next submit), then albedo.w is rewritten
+    // on the context's stream behind the frames already enqueued there
+    rt::frames_drop_mesh(c);
+    c->state_version++;
+    hipError_t e = d_w ? hipMemcpyAsync(d_w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, c->stream) : hipSuccess;
+    int rc = e == hipSuccess ? rt::launch_pt_scatter_surfaces(c, pt.d_tris, d_w, pt.d_albedo, n_tris) : RT_OK;
+    if (e == hipSuccess && rc == RT_OK) e = hipStreamSynchronize(c->stream);
+    dfree(d_w);
+    if (e != hipSuccess || rc != RT_OK) {
+        (void)hipGetLastError();
+        free_mesh(pt);  // some albedo.w may have been written: no frame may be traced against half the surfaces
+        return c->fail(RT_ERR_STATE, "surface upload failed: the mesh has been dropped, set it again");
+    }
+    pt.has_surfaces = !w.empty();
+    if (pt.host) pt.host->surf.swap(w);  // a chunk rebuild packs them again
+    return RT_OK;
+}
+
 int read_bvh_impl(Ctx* c, uint32_t* nodes_out, uint32_t node_capacity, uint32_t* leaf_tris_out, uint32_t tri_capacity, uint32_t* n_nodes) {
     const PtData& pt = c->pt;
     if (!pt.n_tris) return c->fail(RT_ERR_STATE, "no mesh has been set");
@@ -951,6 +1015,13 @@ int rt_refit_mesh_device(rt_ctx* ctx, const void* verts_dev, uint32_t n_tris) {
     if (!c) return RT_ERR_INVALID;
     // every refusal comes before the first write; a HIP failure after it drops the mesh itself (RT_ERR_STATE)
     return guarded(c, "mesh refit", [&] { return refit_mesh_device_impl(c, verts_dev, n_tris); }, false);
+}
+
+int rt_set_mesh_surfaces(rt_ctx* ctx, const uint32_t* kind, const float* ior, uint32_t n_tris) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    // every refusal comes before the first write; a HIP failure after it drops the mesh itself (RT_ERR_STATE)
+    return guarded(c, "surfaces", [&] { return set_surfaces_impl(c, kind, ior, n_tris); }, false);
 }
 
 int rt_read_bvh(rt_ctx* ctx, uint32_t* nodes_out, uint32_t node_capacity, uint32_t* leaf_tris_out, uint32_t tri_capacity, uint32_t* n_nodes) {

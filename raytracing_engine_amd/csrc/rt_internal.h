@@ -185,12 +185,14 @@ struct MeshHost {  // host side of a two-level mesh: what rt_update_mesh_chunk n
     std::vector<float> v0, e1, e2;          // original triangle order
     std::vector<float> albedo, emission;    // original triangle order, 3 floats each
     std::vector<uint32_t> light_ids;        // emissive triangles, ascending
+    std::vector<float> surf;                // albedo.w per triangle, original order (rt_set_mesh_surfaces); empty = all Lambert
 };
 
 struct PtData {  // device residency of one mesh + the wavefront buffers
     std::unique_ptr<MeshHost> host;  // two-level meshes only
     size_t cap_nodes = 0;            // nodes d_nodes has room for
     bool borrowed_mesh = false;  // the mesh arrays belong to another context (frame-slot lanes share their parent's mesh)
+    bool has_surfaces = false;   // some triangle is a mirror or glass (albedo.w != 0): frames take pt_shade<true>, DESIGN.md §6.11
     uint32_t n_tris = 0, n_nodes = 0, n_lights = 0, bvh_depth = 0;
     float bvh_build_ms = 0.0f, bvh_pad = 0.0f, bvh_maxabs = 1.0f;  // bvh_maxabs = max(1, largest |vertex coordinate|): what the padding covers
     float4* d_nodes = nullptr;
@@ -295,7 +297,9 @@ int launch_pt_trace_fused(Ctx* c, const PtScene& sc, const PtState& st, const ui
 uint32_t pt_pool_lds_bytes(uint32_t tri_mode);  // static LDS a 256-thread workgroup of the per-lane kernels needs beyond the stacks and the octant table
 int launch_pt_trace_packet(Ctx* c, const PtScene& sc, const PtFrame& f, const PtState& st, unsigned long long* stats, bool count, uint32_t mode);
 int launch_pt_shade(Ctx* c, const PtScene& sc, const PtFrame& f, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr,
-                    uint32_t depth, uint32_t* next_queue, uint32_t* next_ctr, uint32_t grid, uint32_t sort_rays);
+                    uint32_t depth, uint32_t* next_queue, uint32_t* next_ctr, uint32_t grid, uint32_t sort_rays, bool surfaces);
+// albedo.w of the n leaf-order triangles from surf[original index] (nullptr: all 0 = Lambert), on c->stream
+int launch_pt_scatter_surfaces(Ctx* c, const float4* tris, const float* surf, float4* albedo, uint32_t n);
 int launch_pt_resolve(Ctx* c, const PtFrame& f, const PtState& st, float* acc, float* dst, int tile_major);
 int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const float* dirs, uint32_t n, int any_hit, float* t_out,
                          int* tri_out, uint32_t* counts, const StackCfg& sk, uint32_t grid);

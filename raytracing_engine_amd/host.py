@@ -350,6 +350,29 @@ class Renderer:
         torch.cuda.current_stream(self.device).synchronize()  # writers on torch's stream are done before the refit reads
         self._check(self._lib.rt_refit_mesh_device(self._ctx, C.c_void_p(verts.data_ptr()), n))
 
+    SURFACE_LAMBERT, SURFACE_MIRROR, SURFACE_GLASS = 0, 1, 2
+
+    def set_surfaces(self, kind, ior=None):
+        """Surface of every triangle of the current mesh, original triangle order (rt_set_mesh_surfaces):
+        kind[i] 0 = Lambert, 1 = mirror, 2 = glass of index ior[i] (1..4; ior is read only where kind is 2).  kind=None: all
+        Lambert again.  1-D numpy arrays of one length; the library checks it against the mesh."""
+        if kind is None:
+            self._check(self._lib.rt_set_mesh_surfaces(self._ctx, None, None, self.pt_stats()["n_tris"]))
+            return
+        kind = np.asarray(kind)
+        if kind.ndim != 1 or not (kind.dtype.kind in "iu" or kind.size == 0):
+            raise ValueError(f"kind must be a 1-D integer array, got shape {kind.shape} dtype {kind.dtype}")
+        if (kind < 0).any():
+            raise ValueError("kind must not be negative")
+        kind = np.ascontiguousarray(kind, np.uint32)
+        iorp = None
+        if ior is not None:
+            ior = np.ascontiguousarray(ior, np.float32)
+            if ior.shape != kind.shape:
+                raise ValueError(f"ior must have the shape of kind {kind.shape}, got {ior.shape}")
+            iorp = _fptr(ior)
+        self._check(self._lib.rt_set_mesh_surfaces(self._ctx, kind.ctypes.data_as(C.POINTER(C.c_uint32)), iorp, len(kind)))
+
     def read_bvh(self):
         """Test hook: (node words uint32 (n_nodes, 20), leaf order uint32 (n_tris,)) of the current mesh."""
         n_nodes = C.c_uint32()

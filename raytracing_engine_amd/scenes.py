@@ -83,6 +83,38 @@ def cornell_tri_scene():
     return np.array(tris, f), np.array(alb, f), np.array(emi, f)
 
 
+SURFACE_LAMBERT, SURFACE_MIRROR, SURFACE_GLASS = 0, 1, 2  # rt_set_mesh_surfaces kinds
+
+
+def cornell_surfaces_scene(ior=1.5):
+    """cornell_tri_scene with a mirror box and a glass box: the tall box (triangles 14-25) is a mirror
+    tinted 0.9, the short box (26-37) clear glass (albedo 1) of index `ior`; both are wound outward, as glass needs.
+    Returns (verts, albedo, emission, kind[n] uint32, ior[n] float32)."""
+    v, a, e = cornell_tri_scene()
+    n = len(v)
+    kind = np.full(n, SURFACE_LAMBERT, np.uint32)
+    eta = np.ones(n, np.float32)
+    kind[14:26] = SURFACE_MIRROR
+    a[14:26] = 0.9
+    kind[26:38] = SURFACE_GLASS
+    a[26:38] = 1.0
+    eta[26:38] = ior
+    return v, a, e, kind, eta
+
+
+def soup_surfaces(n_tris, seed=1, mirror_frac=0.1, glass_frac=0.1, ior=1.5):
+    """Surface kinds for soup_scene(n_tris, seed): with u = stream 12 of the counter hash (soup_scene uses 0-11), triangle i
+    is a mirror if u_i < mirror_frac, glass if u_i < mirror_frac + glass_frac (fp32 sum), Lambert otherwise; the light quad
+    stays Lambert.  Returns (kind[n] uint32, ior[n] float32, `ior` everywhere)."""
+    n = int(n_tris)
+    u = _uniform(seed, 12, n)
+    m = np.float32(mirror_frac)
+    g = np.float32(m + np.float32(glass_frac))
+    kind = np.where(u < m, SURFACE_MIRROR, np.where(u < g, SURFACE_GLASS, SURFACE_LAMBERT)).astype(np.uint32)
+    kind[n - 2:] = SURFACE_LAMBERT
+    return kind, np.full(n, np.float32(ior), np.float32)
+
+
 def terrain_scene(grid=708, seed=1, light_emission=(6.0, 6.0, 6.0)):
     """A closed-surface scene for context (the soup is a participating-medium-like worst case): a
     height field of grid x grid cells = 2*grid^2 triangles over x in [-30,30], y in [2,62] (the camera at
