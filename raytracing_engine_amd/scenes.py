@@ -224,3 +224,96 @@ def deep_scene(n_clusters=48, per_cluster=24, ratio=0.45, spread=0.2, scale=4.0,
     emission = np.zeros((m + 4, 3), f)
     emission[m + 2:] = (12.0, 12.0, 12.0)
     return verts, albedo, emission
+
+
+# ---- many-light meshes (one light per Lambert vertex is picked uniformly from the light list) ---------------------
+
+LIGHT_PATTERNS = ("none", "all", "first", "last", "every", "indices", "block", "random")
+
+
+def light_mask(n_tris, pattern, *args):
+    """Which of n_tris triangles (original indices) a named pattern lights, as a bool array: "none", "all", "first", "last",
+    ("every", step): 0, step, 2 step, ...; ("indices", list); ("block", lo, hi): lo <= i < hi; ("random", frac, seed): triangle i
+    is lit if u_i < frac (fp32), u = stream 80 of the counter hash."""
+    n = int(n_tris)
+    m = np.zeros(n, bool)
+    if pattern == "none":
+        assert not args
+    elif pattern == "all":
+        assert not args
+        m[:] = True
+    elif pattern == "first":
+        assert not args
+        m[0] = True
+    elif pattern == "last":
+        assert not args
+        m[n - 1] = True
+    elif pattern == "every":
+        (step,) = args
+        assert int(step) >= 1
+        m[::int(step)] = True
+    elif pattern == "indices":
+        (ids,) = args
+        ids = np.asarray(ids, np.int64)
+        assert ids.size == 0 or (0 <= ids.min() and ids.max() < n)
+        m[ids] = True
+    elif pattern == "block":
+        lo, hi = args
+        assert 0 <= lo <= hi <= n
+        m[int(lo):int(hi)] = True
+    elif pattern == "random":
+        frac, seed = args
+        m = _uniform(int(seed), 80, n) < np.float32(frac)
+    else:
+        raise ValueError(f"unknown light pattern {pattern!r} (one of {LIGHT_PATTERNS})")
+    return m
+
+
+def light_emission(n_tris, level=6.0):
+    """The emission triangle i has when a pattern lights it: level * (0.25 + 1.5 u_i) per channel, u = streams 81-83 of the
+    counter hash with seed 0, so it depends on the original index alone and no two lights of a mesh share a colour.  A frame
+    therefore changes when a light list holds the right set in another order or an emission is gathered from another triangle."""
+    u = np.stack([_uniform(0, 81 + k, int(n_tris)) for k in range(3)], 1)
+    return (np.float32(level) * (np.float32(0.25) + np.float32(1.5) * u)).astype(np.float32)
+
+
+def with_lights(mesh, pattern, *args, level=6.0):
+    """A copy of mesh = (verts, albedo, emission) whose emission array is light_emission(n, level) on the triangles that
+    light_mask(n, pattern, *args) names and zero elsewhere (lights the mesh had before are put out).
+    Returns (verts[n,9], albedo[n,3], emission[n,3]) float32."""
+    v = np.ascontiguousarray(mesh[0], np.float32).reshape(-1, 9).copy()
+    a = np.ascontiguousarray(mesh[1], np.float32).reshape(-1, 3).copy()
+    m = light_mask(len(v), pattern, *args)
+    e = np.where(m[:, None], light_emission(len(v), level), np.float32(0.0)).astype(np.float32)
+    return v, a, e
+
+
+TESS_LIGHT = dict(x=(-2.0, 2.0), y=(8.0, 12.0), z=3.0, radiance=40.0, floor_z=-2.0, floor_albedo=0.8)  # tessellated_light_scene's geometry
+
+
+def tessellated_light_scene(k, ratio=1.0):
+    """A diffuse floor (z = -2, albedo 0.8, x in [-50, 50], y in [0, 100]) under a rectangular light (x in [-2, 2], y in [8, 12],
+    z = 3, radiance 40) cut along x into k strips whose widths form a geometric series with quotient `ratio`, two triangles per
+    strip: 2 k lights whose areas span ratio^(k-1), the same emitter for every (k, ratio).  Neighbouring strips share their
+    fp32 edge, and the outer edges are exactly -2 and 2.  Returns (verts[2+2k,9], albedo, emission) float32; the floor is
+    triangles 0 and 1."""
+    f = np.float32
+    k = int(k)
+    assert k >= 1 and ratio > 0
+    g = TESS_LIGHT
+    w = np.float64(ratio) ** np.arange(k, dtype=np.float64)
+    x0, x1 = g["x"]
+    edges = np.concatenate([[x0], x0 + (x1 - x0) * np.cumsum(w) / w.sum()]).astype(f)
+    edges[-1] = x1
+    assert (np.diff(edges) > 0).all(), "a strip is narrower than fp32 resolves"
+    y0, y1, z, fz = f(g["y"][0]), f(g["y"][1]), f(g["z"]), f(g["floor_z"])
+    tris = _quad(np.array([-50, 0, fz], f), np.array([50, 0, fz], f), np.array([50, 100, fz], f), np.array([-50, 100, fz], f))
+    for j in range(k):
+        a, b = edges[j], edges[j + 1]
+        tris += _quad(np.array([a, y0, z], f), np.array([b, y0, z], f), np.array([b, y1, z], f), np.array([a, y1, z], f))
+    n = 2 + 2 * k
+    albedo = np.zeros((n, 3), f)
+    albedo[:2] = g["floor_albedo"]
+    emission = np.zeros((n, 3), f)
+    emission[2:] = g["radiance"]
+    return np.array(tris, f), albedo, emission

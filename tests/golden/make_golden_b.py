@@ -22,3 +22,8 @@ if __name__ == "__main__":
     rgb, ct = O.TriScene(v, a, e).render(96, 54, spp=2, bounces=1, seed=5, sky=(0.3, 0.3, 0.4))
     np.savez_compressed(os.path.join(HERE, "path_b_soup2k_96x54.npz"), rgb=rgb, counters=np.array([ct["camera_rays"], ct["bounce_rays"], ct["shadow_rays"]], np.uint64))
     print(ct)
+    # many lights: every 7th triangle of a 3000-triangle soup emits (429 lights, each with its own colour)
+    v, a, e = scenes.with_lights(scenes.soup_scene(3000, seed=3, edge=1.5), "every", 7)
+    rgb, ct = O.TriScene(v, a, e).render(96, 54, spp=2, bounces=2, seed=5, sky=(0.3, 0.3, 0.4))
+    np.savez_compressed(os.path.join(HERE, "path_b_lights3k_96x54.npz"), rgb=rgb, counters=np.array([ct["camera_rays"], ct["bounce_rays"], ct["shadow_rays"]], np.uint64))
+    print(ct)
