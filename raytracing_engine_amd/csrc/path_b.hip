@@ -20,6 +20,8 @@
 #include "rt_device_math.h"
 #include "rt_internal.h"
 
+#include <type_traits>
+
 namespace rt {
 using namespace rtk;
 
@@ -112,20 +114,29 @@ __device__ __forceinline__ bool tri_test(v3 o, v3 d, v3 v0, v3 e1, v3 e2, float&
     return true;
 }
 
-// tri_test() for the lanes of a wave that hold a triangle, as straight-line code: the same operations in the same order, the
-// per-lane early returns replaced by lane masks combined on the scalar unit and ONE wave-uniform way out before the division.
-__device__ __forceinline__ bool tri_test_flat(v3 o, v3 d, v3 v0, v3 e1, v3 e2, float& t_out) {
+// tri_test() up to its division, for a whole wave as straight-line code: the same operations in the same order, the per-lane early
+// returns (about sixty scalar instructions per triangle in exec-mask bookkeeping) replaced by lane masks.  Returns the lanes of `lanes`
+// whose ray passes through the triangle; their t is  dot(e2, qvec) / det.
+__device__ __forceinline__ unsigned long long tri_inside_mask(v3 o, v3 d, v3 v0, v3 e1, v3 e2, unsigned long long lanes, float& det, v3& qvec) {
     const v3 pvec = cross(d, e2);
-    const float det = dot(e1, pvec);
+    det = dot(e1, pvec);
     const v3 tvec = o - v0;
     const float u = dot(tvec, pvec);
-    const v3 qvec = cross(tvec, e1);
+    qvec = cross(tvec, e1);
     const float v = dot(d, qvec);
     const float uv = u + v;
+    // (ballots, combined as 64-bit scalars: boolean expressions come back as branches or through v_cndmask + v_cmp)
     const unsigned long long m_pos = __builtin_amdgcn_ballot_w64(det > 0.0f), m_nz = __builtin_amdgcn_ballot_w64(det != 0.0f);
     const unsigned long long out_pos = __builtin_amdgcn_ballot_w64(u < 0.0f) | __builtin_amdgcn_ballot_w64(v < 0.0f) | __builtin_amdgcn_ballot_w64(uv > det);
     const unsigned long long out_neg = __builtin_amdgcn_ballot_w64(u > 0.0f) | __builtin_amdgcn_ballot_w64(v > 0.0f) | __builtin_amdgcn_ballot_w64(uv < det);
-    const unsigned long long inside = m_nz & ((m_pos & ~out_pos) | (~m_pos & ~out_neg));  // (ballots hold the active lanes only)
+    return lanes & m_nz & ((m_pos & ~out_pos) | (~m_pos & ~out_neg));
+}
+
+// tri_test() for the lanes of a wave that hold a triangle: ONE wave-uniform way out before the division.
+__device__ __forceinline__ bool tri_test_flat(v3 o, v3 d, v3 v0, v3 e1, v3 e2, float& t_out) {
+    float det;
+    v3 qvec;
+    const unsigned long long inside = tri_inside_mask(o, d, v0, e1, e2, ~0ull, det, qvec);  // (ballots hold the active lanes only)
     if (inside == 0ull) return false;
     t_out = dot(e2, qvec) / det;
     return __builtin_amdgcn_inverse_ballot_w64(inside);
@@ -146,6 +157,10 @@ struct TRay {
     float tmax;
     uint32_t oct_inv;   // 7 - octant: slot ^ oct_inv enumerates a node's children front to back
 };
+// 7 - octant of a direction, by sign BIT, like safe_inv's copysign: a -0.0 component has a negative reciprocal and must take the far plane first
+__device__ __forceinline__ uint32_t octant_inv(v3 d) {
+    return ((__float_as_uint(d.x) >> 31) ? 0u : 4u) | ((__float_as_uint(d.y) >> 31) ? 0u : 2u) | ((__float_as_uint(d.z) >> 31) ? 0u : 1u);
+}
 __device__ __forceinline__ TRay make_tray(v3 o, v3 d, float tmax) {
     TRay r;
     r.o = o;
@@ -153,8 +168,7 @@ __device__ __forceinline__ TRay make_tray(v3 o, v3 d, float tmax) {
     r.inv = safe_inv(d);
     r.noi = mk(-(o.x * r.inv.x), -(o.y * r.inv.y), -(o.z * r.inv.z));
     r.tmax = tmax;
-    // by sign BIT, like safe_inv's copysign: a -0.0 component has a negative reciprocal and must take the far plane first
-    r.oct_inv = ((__float_as_uint(d.x) >> 31) ? 0u : 4u) | ((__float_as_uint(d.y) >> 31) ? 0u : 2u) | ((__float_as_uint(d.z) >> 31) ? 0u : 1u);
+    r.oct_inv = octant_inv(d);
     return r;
 }
 
@@ -290,35 +304,13 @@ __device__ __forceinline__ void build_perm_lut(uint8_t* lut) {
     __syncthreads();
 }
 
-// Test the next pending triangle of triangle group T.  Returns true when an any-hit ray found an occluder.
-template <bool ANY, bool COUNT>
-__device__ __forceinline__ bool tri_step(const float4* __restrict__ tris, TRay& r, Hit& best, Group& T, TravCounters& tc) {
+// Test the next pending triangle of triangle group T.  is_any: what a hit means to this lane's ray - a compile-time constant where a
+// kernel traces one kind of ray, a per-lane flag in the loop that carries both.  Returns true when an any-hit ray found an occluder.
+template <bool COUNT>
+__device__ __forceinline__ bool tri_step(const float4* __restrict__ tris, TRay& r, Hit& best, Group& T, TravCounters& tc, bool is_any) {
     const uint32_t bit = (uint32_t)__builtin_ctz(T.y);  // lowest pending leaf slot (caller checked has_tris)
     T.y &= T.y - 1u;
     const uint32_t li = T.x + (uint32_t)__builtin_popcount((T.y >> 8) & ~(0xffffffffu << bit));  // rank of the slot among the node's leaves
-    const float4* tp = tris + (size_t)li * 3;
-    const float4 a = tp[0], b = tp[1], c = tp[2];
-    if (COUNT) tc.tris++;
-    float t;
-    if (tri_test_flat(r.o, r.d, mk(a.x, a.y, a.z), mk(a.w, b.x, b.y), mk(b.z, b.w, c.x), t) && t > 0.0f) {
-        if (ANY) return t < kShadowTmax;
-        const uint32_t id = __float_as_uint(c.y);
-        if (t < best.t || (t == best.t && id < best.id)) {
-            best.t = t;
-            best.li = (int)li;
-            best.id = id;
-            r.tmax = t;
-        }
-    }
-    return false;
-}
-
-// tri_step for a wave whose lanes carry both kinds of ray (trace_queue_mixed): the kind is a per-lane flag.
-template <bool COUNT>
-__device__ __forceinline__ bool tri_step_mixed(const float4* __restrict__ tris, TRay& r, Hit& best, Group& T, TravCounters& tc, bool is_any) {
-    const uint32_t bit = (uint32_t)__builtin_ctz(T.y);
-    T.y &= T.y - 1u;
-    const uint32_t li = T.x + (uint32_t)__builtin_popcount((T.y >> 8) & ~(0xffffffffu << bit));
     const float4* tp = tris + (size_t)li * 3;
     const float4 a = tp[0], b = tp[1], c = tp[2];
     if (COUNT) tc.tris++;
@@ -335,26 +327,59 @@ __device__ __forceinline__ bool tri_step_mixed(const float4* __restrict__ tris, 
     }
     return false;
 }
+template <bool ANY, bool COUNT>
+__device__ __forceinline__ bool tri_step(const float4* __restrict__ tris, TRay& r, Hit& best, Group& T, TravCounters& tc) { return tri_step<COUNT>(tris, r, best, T, tc, ANY); }
 
 __device__ __forceinline__ Group root_group() { return Group{0u, 0x80000000u}; }  // "child 0 of nothing" = node 0
 
-// Whole-ray traversal for one lane (used by the rt_trace_rays test hook; the render kernels drive
-// the same step functions from a refilling persistent loop).
-template <bool ANY, bool COUNT>
-__device__ __forceinline__ bool traverse(const float4* __restrict__ nodes, const float4* __restrict__ tris, const uint8_t* perm_lut, v3 o, v3 d, TravStack& stk,
-                                         Hit& best, TravCounters& tc) {
-    TRay r = make_tray(o, d, ANY ? kShadowTmax : best.t);
+// Put a ray into a lane: traversal form, no hit yet, at the root with an empty stack.
+__device__ __forceinline__ void start_ray(bool is_any, v3 o, v3 d, TRay& r, Hit& best, Group& G, Group& T, TravStack& stk) {
+    r = make_tray(o, d, is_any ? kShadowTmax : __builtin_inff());
+    if (!is_any) best = Hit{__builtin_inff(), -1, 0xffffffffu};
+    G = root_group();
+    T = Group{0u, 0u};
     stk.sp = 0;
-    Group G = root_group(), T{0u, 0u};
-    for (;;) {
+}
+
+// One round of the inline schedule: lanes without pending triangles visit their next node, then every lane that holds a leaf hit
+// tests up to tris_per_round triangles.  alive: the lane has traversal work; returns whether it still has.  occluded: set when its
+// any-hit ray found an occluder.  UNORDERED: see node_step.
+// (alive goes in and out by value: a flag that the loops carry from round to round through a reference stays a byte in a vector
+// register, with an and + compare wherever a branch needs it as a lane mask)
+template <bool COUNT, bool UNORDERED>
+__device__ __forceinline__ bool inline_round(const PtScene& sc, const uint8_t* perm_lut, TRay& r, Hit& best, Group& G, Group& T, TravStack& stk, TravCounters& tc,
+                                             bool alive, bool& occluded, bool is_any, int tris_per_round) {
+    // node phase
+    if (alive && !has_tris(T)) {
         if (!has_nodes(G)) {
-            if (stk.sp == 0) return false;
-            G = stk.pop();
+            if (stk.sp) G = stk.pop();
+            else alive = false;
         }
-        node_step<COUNT>(nodes, perm_lut, r, G, T, stk, tc);
-        while (has_tris(T))
-            if (tri_step<ANY, COUNT>(tris, r, best, T, tc)) return true;
+        if (alive) node_step<COUNT, UNORDERED>(sc.nodes, perm_lut, r, G, T, stk, tc);
     }
+    // triangle phase: one test, then what a hit means to this lane's kind of ray
+#pragma unroll 1
+    for (int it = 0; it < tris_per_round; it++) {
+        if (alive && has_tris(T)) {
+            if (tri_step<COUNT>(sc.tris, r, best, T, tc, is_any)) {
+                occluded = true;
+                alive = false;
+            }
+        }
+    }
+    return alive;
+}
+
+// Whole-ray traversal for one lane (used by the rt_trace_rays test hook; the render kernels drive the same rounds from a refilling
+// persistent loop).  Returns true when an any-hit ray found an occluder.
+template <bool ANY, bool COUNT>
+__device__ __forceinline__ bool traverse(const PtScene& sc, const uint8_t* perm_lut, v3 o, v3 d, TravStack& stk, Hit& best, TravCounters& tc) {
+    TRay r;
+    Group G, T;
+    start_ray(ANY, o, d, r, best, G, T, stk);
+    bool alive = true, occluded = false;
+    while (alive) alive = inline_round<COUNT, false>(sc, perm_lut, r, best, G, T, stk, tc, alive, occluded, ANY, 1);
+    return occluded;
 }
 
 // ---- pixel slots ---------------------------------------------------------------------------------
@@ -615,6 +640,214 @@ constexpr int kTrisPerRound = 1;
 //               phase runs when enough lanes hold a group (or enough of them can do nothing else)
 enum { TRI_INLINE = TRI_MODE_INLINE, TRI_POOL = TRI_MODE_POOL, TRI_DEFER = TRI_MODE_DEFER, TRI_INLINE_PF = TRI_MODE_INLINE_PF };
 
+// Words of the device-side statistics block (rt_render_pt reads them back by number)
+enum {
+    PT_STAT_NODES = 0,          // closest-hit rays of the per-lane kernels: node visits, + 1: triangle tests
+    PT_STAT_OVERFLOW = 2,       // != 0: some traversal stack overflowed
+    PT_STAT_SHADOW = 4,         // shadow rays of a launch of their own: node visits, + 1: triangle tests
+    PT_STAT_ROUNDS = 6,         // wave-rounds of the loops that carry closest-hit rays, + 1: alive lane-rounds
+    PT_STAT_PACKETS = 8,        // packet kernels: waves, + 1: node records fetched, + 2: triangle records fetched
+    PT_STAT_FUSED_SHADOW = 11,  // shadow rays inside the fused launch: node visits, + 1: triangle tests
+    PT_STAT_FLUSHES = 13,       // TRI_POOL: pool_test passes, TRI_DEFER: triangle phases
+    PT_STAT_ROUNDS_ALL = 14     // wave-rounds of every per-lane loop
+};
+
+// Retire a finished ray: a closest-hit ray stores (t, triangle) for pt_shade, an unoccluded shadow ray adds its contribution to its path.
+__device__ __forceinline__ void retire_ray(const PtState& st, bool is_any, uint32_t slot, bool occluded, const Hit& best) {
+    if (is_any) {
+        if (!occluded) {
+            const uint32_t pid = __float_as_uint(st.sh_o[slot].w);
+            const float4 c = st.sh_c[slot];
+            float4 L = st.rad[pid];
+            L.x += c.x;
+            L.y += c.y;
+            L.z += c.z;
+            st.rad[pid] = L;
+        }
+    } else {
+        st.hit[slot] = make_float2(best.t, __int_as_float(best.li));
+    }
+}
+
+// Entry i of a queue -> its ray.  Returns the ray's slot: the path id of a closest-hit ray, the shadow-queue index of a shadow ray.
+__device__ __forceinline__ uint32_t load_ray(const PtState& st, const uint32_t* __restrict__ queue, bool is_any, uint32_t i, v3& o, v3& d) {
+    if (is_any) {
+        const float4 so = st.sh_o[i], sd = st.sh_d[i];
+        o = mk(so.x, so.y, so.z);
+        d = mk(sd.x, sd.y, sd.z);
+        return i;
+    }
+    const uint32_t slot = queue[i];
+    const float4 ro = st.ray_o[slot], rd = st.ray_d[slot];
+    o = mk(ro.x, ro.y, ro.z);
+    d = mk(rd.x, rd.y, rd.z);
+    return slot;
+}
+
+// Stream-local entry j of stream k is queue entry ((j / 64) * PT_HEADS + k) * 64 + j % 64 (rt_internal.h).
+__device__ __forceinline__ uint32_t stream_entry(uint32_t stream, uint32_t j) { return (((j >> 6) * PT_HEADS + stream) << 6) | (j & 63u); }
+
+// The stream a wave starts to pull from.
+// (readfirstlane: threadIdx.x >> 6 is wave-uniform, but only this tells the compiler, and everything the stream index touches -
+// the dry-stream test, `exhausted`, the refill branch - would otherwise live in vector registers under lane masks)
+__device__ __forceinline__ uint32_t home_stream() { return uniform((blockIdx.x * 4u + (threadIdx.x >> 6)) & (PT_HEADS - 1u)); }
+
+// Where a wave stands in a queue (all wave-uniform): it pulls from one stream until it finds it dry, then from the next one.
+struct QueueCursor {
+    uint32_t n;     // entries in the queue
+    uint32_t* head;  // the queue's PT_HEADS stream heads
+    uint32_t stream, dry_streams;
+    __device__ __forceinline__ uint32_t* head_word() const { return head + stream * PT_HEAD_STRIDE; }
+    // One returning atomic on the wave's stream head reserves `want` stream-local entries; the first one is returned to every lane.
+    __device__ __forceinline__ uint32_t reserve(uint32_t want, uint32_t lane) const {
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(head_word(), want);
+        return uniform(base);
+    }
+    // je = the end of a reservation.  Past the queue's end the stream is dry (entries grow with j) and the wave moves on; returns
+    // true when that was the last stream, i.e. the queue is dry.
+    __device__ __forceinline__ bool advance_if_dry(uint32_t je) {
+        if (stream_entry(stream, je) < n) return false;
+        stream = (stream + 1u) & (PT_HEADS - 1u);
+        return ++dry_streams >= PT_HEADS;
+    }
+};
+
+// rt_pt_params.tune_refill_min, byte 1: triangle tests per round of the inline schedules
+__device__ __forceinline__ int tris_per_round_of(uint32_t refill_min) { return (int)((refill_min >> 8) & 0xffu) ? (int)((refill_min >> 8) & 0xffu) : kTrisPerRound; }
+
+__device__ __forceinline__ void add_wave_total(unsigned long long* word, uint32_t v, uint32_t lane) {  // one atomic per wave
+    unsigned long long a = v;
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off);
+    if (lane == 0) atomicAdd(word, a);
+}
+// What a wave's loop leaves in stats[].  kinds: bit 0 = the loop carried closest-hit rays (counted in `closest`), bit 1 = shadow rays
+// (`shadow`, added at shadow_word: PT_STAT_SHADOW or PT_STAT_FUSED_SHADOW); node / triangle counts per lane, the rest wave-uniform.
+template <bool COUNT>
+__device__ __forceinline__ void flush_trace_counters(unsigned long long* __restrict__ stats, uint32_t lane, uint32_t kinds, const TravCounters& closest,
+                                                     const TravCounters& shadow, uint32_t shadow_word, uint32_t rounds, uint32_t alive_rounds, uint32_t flushes,
+                                                     uint32_t overflow) {
+    if (COUNT) {
+        if (kinds & 1u) {
+            add_wave_total(&stats[PT_STAT_NODES], closest.nodes, lane);
+            add_wave_total(&stats[PT_STAT_NODES + 1], closest.tris, lane);
+        }
+        if (kinds & 2u) {
+            add_wave_total(&stats[shadow_word], shadow.nodes, lane);
+            add_wave_total(&stats[shadow_word + 1u], shadow.tris, lane);
+        }
+        if (lane == 0) {
+            if (kinds & 1u) {  // occupancy of the rounds: wave-rounds and alive lane-rounds
+                atomicAdd(&stats[PT_STAT_ROUNDS], (unsigned long long)rounds);
+                atomicAdd(&stats[PT_STAT_ROUNDS + 1], (unsigned long long)alive_rounds);
+            }
+            atomicAdd(&stats[PT_STAT_FLUSHES], (unsigned long long)flushes);
+            atomicAdd(&stats[PT_STAT_ROUNDS_ALL], (unsigned long long)rounds);
+        }
+    }
+    if (overflow) atomicOr((unsigned int*)&stats[PT_STAT_OVERFLOW], 1u);
+}
+
+struct QueueRef {  // a device-resident ray queue: its size and its stream heads (the rays: PtState)
+    const uint32_t* count;
+    uint32_t* head;
+};
+
+// ---- the inline schedule -----------------------------------------------------------------------------
+// KIND: the rays a loop carries.  RAYS_BOTH is the fused launch.  A loop for the closest-hit queue followed by one for the shadow
+// queue makes every wave DRAIN between the two: once the closest-hit queue is dry a wave gets no refills, its lanes run out one by
+// one (a tenth of its rounds, at nine of 64 lanes alive) and only then does it turn to the shadow queue.  The node step is the same
+// for both kinds of ray and the triangle step differs only in what a hit means, so with RAYS_BOTH the kind is a per-lane flag: when
+// the closest-hit queue is dry the wave's idle lanes are refilled from the shadow queue while its last closest-hit rays are still
+// walking.  One tail per wave and launch instead of two.  Every ray is traced by exactly the step functions of the one-kind loops,
+// where the flag is a constant that folds away, so frames and counts are unchanged.
+enum { RAYS_CLOSEST = 0, RAYS_ANY = 1, RAYS_BOTH = 2 };
+
+template <int KIND, bool COUNT>
+__device__ __forceinline__ void trace_queue_inline(const PtScene& sc, const PtState& st, const uint32_t* __restrict__ queue, QueueRef closest_q, QueueRef shadow_q,
+                                                   unsigned long long* __restrict__ stats, TravStack& stk, const uint8_t* perm_lut, uint32_t refill_min,
+                                                   uint32_t shadow_stat) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const uint32_t n_closest = KIND == RAYS_ANY ? 0u : uniform(*closest_q.count), n_shadow = KIND == RAYS_CLOSEST ? 0u : uniform(*shadow_q.count);
+    const int tris_per_round = tris_per_round_of(refill_min);
+    refill_min &= 0xffu;
+    TravCounters tc{0, 0, 0};                            // COUNT: the current ray of this lane (one kind: every ray)
+    TravCounters cl_done{0, 0, 0}, any_done{0, 0, 0};  // COUNT, RAYS_BOTH: retired rays of this lane, by kind
+
+    TRay r = make_tray(mk(0.0f, 0.0f, 0.0f), mk(0.0f, 1.0f, 0.0f), 0.0f);
+    Hit best{0.0f, -1, 0u};
+    Group G{0u, 0u}, T{0u, 0u};
+    uint32_t slot = 0;  // closest: path id; any-hit: shadow-queue index
+    bool has_ray = false, occluded = false;
+    bool alive = false;             // this lane still has traversal work for its ray
+    bool is_any = KIND == RAYS_ANY;  // the kind of this lane's ray
+    // wave-uniform: which queue the wave refills from, and where it stands in it
+    uint32_t phase = KIND == RAYS_ANY || (KIND == RAYS_BOTH && n_closest == 0u) ? 1u : 0u;  // 0 = closest-hit queue, 1 = shadow queue
+    const uint32_t stream0 = home_stream();
+    QueueCursor cur{phase == 0u ? n_closest : n_shadow, phase == 0u ? closest_q.head : shadow_q.head, stream0, 0u};
+    bool exhausted = cur.n == 0u;           // every stream of the last queue has been found dry
+    uint32_t rounds = 0, alive_rounds = 0;  // COUNT only
+
+    for (;;) {
+        const unsigned long long idle = __ballot(!alive);
+        if (idle == ~0ull || (!exhausted && (uint32_t)__popcll(idle) >= refill_min)) {
+            if (!alive && has_ray) {
+                retire_ray(st, is_any, slot, occluded, best);
+                if (COUNT && KIND == RAYS_BOTH) {
+                    if (is_any) {
+                        any_done.nodes += tc.nodes;
+                        any_done.tris += tc.tris;
+                    } else {
+                        cl_done.nodes += tc.nodes;
+                        cl_done.tris += tc.tris;
+                    }
+                    tc.nodes = tc.tris = 0;
+                }
+                has_ray = false;
+            }
+            if (!exhausted) {  // exactly what the idle lanes need, assigned by ballot + prefix popcount
+                const uint32_t want = (uint32_t)__popcll(idle);
+                const uint32_t base = cur.reserve(want, lane);
+                const uint32_t i = !alive ? stream_entry(cur.stream, base + (uint32_t)__popcll(idle & lt_mask)) : cur.n;  // >= n: nothing for this lane
+                if (!alive && i < cur.n) {
+                    const auto take = [&](bool any) {  // (the kind as a constant: one make_tray per kind, as the loads differ anyway)
+                        v3 o, d;
+                        slot = load_ray(st, queue, any, i, o, d);
+                        start_ray(any, o, d, r, best, G, T, stk);
+                        is_any = any;
+                    };
+                    if (KIND == RAYS_ANY || (KIND == RAYS_BOTH && phase != 0u)) take(true);
+                    else take(false);
+                    occluded = false;
+                    has_ray = true;
+                    alive = true;
+                }
+                if (cur.advance_if_dry(base + want)) {  // this queue is dry: on to the shadow queue, or done
+                    if (KIND == RAYS_BOTH && phase == 0u && n_shadow != 0u) {
+                        phase = 1u;
+                        cur = QueueCursor{n_shadow, shadow_q.head, stream0, 0u};
+                    } else {
+                        exhausted = true;
+                    }
+                }
+            }
+            // every lane retired and nothing handed out: a one-kind loop is done (the streams this wave has not seen are drained by the
+            // waves that started on them), the loop for both queues goes on until it has found the last stream of the last queue dry
+            if (__ballot(alive) == 0ull && (KIND != RAYS_BOTH || exhausted)) break;
+        }
+        if (COUNT) {  // occupancy of the round: wave-rounds and alive lane-rounds
+            rounds++;
+            alive_rounds += (uint32_t)__popcll(__ballot(alive));
+        }
+        // (UNORDERED for the any-hit rays of an all-shadow launch)
+        alive = inline_round<COUNT, KIND == RAYS_ANY>(sc, perm_lut, r, best, G, T, stk, tc, alive, occluded, is_any, tris_per_round);
+    }
+    flush_trace_counters<COUNT>(stats, lane, KIND == RAYS_BOTH ? 3u : KIND == RAYS_ANY ? 2u : 1u, KIND == RAYS_BOTH ? cl_done : tc, KIND == RAYS_BOTH ? any_done : tc,
+                                shadow_stat, rounds, alive_rounds, 0u, tc.overflow);
+}
+
+// ---- the pooled and the postponed schedule -------------------------------------------------------------
 struct PoolMem {  // LDS of one wave's pool (TRI_POOL kernels only)
     lds_u64* ring;
     lds_u64* best;
@@ -622,15 +855,13 @@ struct PoolMem {  // LDS of one wave's pool (TRI_POOL kernels only)
 };
 
 template <bool ANY, bool COUNT, int MODE>
-__device__ __forceinline__ void trace_queue(const PtScene& sc, const PtState& st, const uint32_t* __restrict__ queue,
-                                            const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ head,
+__device__ __forceinline__ void trace_queue(const PtScene& sc, const PtState& st, const uint32_t* __restrict__ queue, QueueRef q,
                                             unsigned long long* __restrict__ stats, TravStack& stk, const uint8_t* perm_lut, uint32_t refill_min,
                                             const PoolMem& pm, uint32_t tri_cfg /* TRI_POOL: byte 0 = groups that trigger a flush, byte 1 = rounds a group may wait */,
-                                            uint32_t shadow_stat /* word of the shadow-ray node counter: 4 alone, 11 inside the fused launch */ = 4u) {
+                                            uint32_t shadow_stat) {
+    static_assert(MODE == TRI_POOL || MODE == TRI_DEFER, "the inline schedules have loops of their own");
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const uint32_t n = uniform(*count_ptr);
-    const int tris_per_round = (int)((refill_min >> 8) & 0xffu) ? (int)((refill_min >> 8) & 0xffu) : kTrisPerRound;
     refill_min &= 0xffu;
     TravCounters tc{0, 0, 0};
 
@@ -639,12 +870,9 @@ __device__ __forceinline__ void trace_queue(const PtScene& sc, const PtState& st
     Group G{0u, 0u}, T{0u, 0u}, T2{0u, 0u};  // T2: TRI_DEFER's second parking slot
     uint32_t slot = 0;  // closest: path id; any-hit: shadow-queue index
     bool has_ray = false, occluded = false;
-    bool exhausted = n == 0;  // wave-uniform: every stream of the queue has been found dry
-    // (readfirstlane: threadIdx.x >> 6 is wave-uniform, but only this tells the compiler, and everything the stream index touches -
-    // the dry-stream test, `exhausted`, the refill branch - would otherwise live in vector registers under lane masks)
-    uint32_t stream = uniform((blockIdx.x * 4u + (threadIdx.x >> 6)) & (PT_HEADS - 1u));  // wave-uniform: the stream this wave pulls from
-    uint32_t dry_streams = 0;                                                    // wave-uniform
-    uint32_t rounds = 0, alive_rounds = 0;                // COUNT only
+    QueueCursor cur{uniform(*q.count), q.head, home_stream(), 0u};
+    bool exhausted = cur.n == 0u;            // wave-uniform: every stream of the queue has been found dry
+    uint32_t rounds = 0, alive_rounds = 0;  // COUNT only
     bool alive = false;       // this lane still has traversal work for its ray
 
     // TRI_POOL state (all wave-uniform)
@@ -666,7 +894,7 @@ __device__ __forceinline__ void trace_queue(const PtScene& sc, const PtState& st
                 }
                 waited = 0;
             }
-            if (!alive && has_ray) {  // retire
+            if (!alive && has_ray) {
                 if (MODE == TRI_POOL) {
                     if (ANY) occluded = best32[2u * lane] != 0u;
                     else {
@@ -674,61 +902,29 @@ __device__ __forceinline__ void trace_queue(const PtScene& sc, const PtState& st
                         best.li = (int)pm.li[lane];
                     }
                 }
-                if (ANY) {
-                    if (!occluded) {
-                        const uint32_t pid = __float_as_uint(st.sh_o[slot].w);
-                        const float4 c = st.sh_c[slot];
-                        float4 L = st.rad[pid];
-                        L.x += c.x;
-                        L.y += c.y;
-                        L.z += c.z;
-                        st.rad[pid] = L;
-                    }
-                } else {
-                    st.hit[slot] = make_float2(best.t, __int_as_float(best.li));
-                }
+                retire_ray(st, ANY, slot, occluded, best);
                 has_ray = false;
             }
-            if (!exhausted) {
-                // One returning atomic on the wave's stream head reserves exactly what the idle lanes
-                // need.  Stream-local entry j of stream k is queue entry ((j / 64) * PT_HEADS + k) * 64 + j % 64.
+            if (!exhausted) {  // exactly what the idle lanes need, assigned by ballot + prefix popcount
                 const uint32_t want = (uint32_t)__popcll(idle);
-                const uint32_t my_rank = (uint32_t)__popcll(idle & lt_mask);
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(head + stream * PT_HEAD_STRIDE, want);
-                base = __builtin_amdgcn_readfirstlane(base);
-                const uint32_t j = base + my_rank, je = base + want;
-                const uint32_t i = !alive ? ((((j >> 6) * PT_HEADS + stream) << 6) | (j & 63u)) : n;  // >= n: nothing for this lane
-                if (((((je >> 6) * PT_HEADS + stream) << 6) | (je & 63u)) >= n) {  // this stream is dry (entries grow with j): move on
-                    stream = (stream + 1u) & (PT_HEADS - 1u);
-                    exhausted = ++dry_streams >= PT_HEADS;
-                }
-                if (!alive && i < n) {
-                    if (ANY) {
-                        const float4 so = st.sh_o[i], sd = st.sh_d[i];
-                        r = make_tray(mk(so.x, so.y, so.z), mk(sd.x, sd.y, sd.z), kShadowTmax);
-                        slot = i;
-                        occluded = false;
-                        if (MODE == TRI_POOL) pm.best[lane] = 0ull;
-                    } else {
-                        slot = queue[i];
-                        const float4 ro = st.ray_o[slot], rd = st.ray_d[slot];
-                        r = make_tray(mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z), __builtin_inff());
-                        best = Hit{__builtin_inff(), -1, 0xffffffffu};
-                        if (MODE == TRI_POOL) {
-                            pm.best[lane] = kPoolNoHit;
-                            pm.li[lane] = 0xffffffffu;
-                        }
-                    }
+                const uint32_t base = cur.reserve(want, lane);
+                const uint32_t i = !alive ? stream_entry(cur.stream, base + (uint32_t)__popcll(idle & lt_mask)) : cur.n;  // >= n: nothing for this lane
+                if (!alive && i < cur.n) {
+                    v3 o, d;
+                    slot = load_ray(st, queue, ANY, i, o, d);
+                    start_ray(ANY, o, d, r, best, G, T, stk);
+                    T2 = Group{0u, 0u};
+                    occluded = false;
                     has_ray = true;
                     alive = true;
-                    G = root_group();
-                    T = Group{0u, 0u};
-                    T2 = Group{0u, 0u};
-                    stk.sp = 0;
+                    if (MODE == TRI_POOL) {
+                        pm.best[lane] = ANY ? 0ull : kPoolNoHit;
+                        if (!ANY) pm.li[lane] = 0xffffffffu;
+                    }
                 }
+                exhausted = cur.advance_if_dry(base + want);
             }
-            if (__ballot(alive) == 0ull) break;  // queue drained and every lane retired
+            if (__ballot(alive) == 0ull) break;  // nothing left for this wave: the streams it has not seen are drained by their own waves
         }
         if (COUNT) {  // occupancy of the round: wave-rounds and alive lane-rounds
             rounds++;
@@ -768,7 +964,7 @@ __device__ __forceinline__ void trace_queue(const PtScene& sc, const PtState& st
                 flushed = true;
                 waited = 0;
             }
-        } else if (MODE == TRI_DEFER) {
+        } else {
             // node phase: a lane visits its next node as long as it has somewhere to park a leaf-hit group
             bool stuck = false;  // holds a group and cannot visit a node: out of nodes, or both parking slots taken
             if (alive) {
@@ -804,200 +1000,9 @@ __device__ __forceinline__ void trace_queue(const PtScene& sc, const PtState& st
                 }
                 if (COUNT) tc.flushes++;
             }
-        } else {
-            // node phase: lanes without pending triangles visit their next node
-            if (alive && !has_tris(T)) {
-                if (!has_nodes(G)) {
-                    if (stk.sp) G = stk.pop();
-                    else alive = false;
-                }
-                if (alive) node_step<COUNT, ANY>(sc.nodes, perm_lut, r, G, T, stk, tc);
-            }
-            // triangle phase
-#pragma unroll 1
-            for (int it = 0; it < tris_per_round; it++) {
-                if (alive && has_tris(T)) {
-                    if (tri_step<ANY, COUNT>(sc.tris, r, best, T, tc)) {
-                        occluded = true;
-                        alive = false;
-                    }
-                }
-            }
         }
     }
-    if (COUNT) {
-        // wave reduction of the traversal counters, one atomic per wave
-        unsigned long long a = tc.nodes, b = tc.tris;
-        for (int off = 32; off > 0; off >>= 1) {
-            a += __shfl_down(a, off);
-            b += __shfl_down(b, off);
-        }
-        if (lane == 0) {
-            if (!ANY) {
-                atomicAdd(&stats[6], (unsigned long long)rounds);
-                atomicAdd(&stats[7], (unsigned long long)alive_rounds);
-            }
-            atomicAdd(&stats[13], (unsigned long long)tc.flushes);
-            atomicAdd(&stats[14], (unsigned long long)rounds);
-            atomicAdd(&stats[ANY ? shadow_stat : 0u], a);
-            atomicAdd(&stats[ANY ? shadow_stat + 1u : 1u], b);
-        }
-    }
-    if (tc.overflow) atomicOr((unsigned int*)&stats[2], 1u);
-}
-
-// ---- one loop for both queues of a fused launch ---------------------------------------------------
-// trace_queue<closest> followed by trace_queue<any> makes every wave DRAIN between the two: once the closest-hit queue is dry a
-// wave gets no refills, its lanes run out one by one (a tenth of its rounds, at nine of 64 lanes alive) and only then does it
-// turn to the shadow queue.  The node step is the same for both kinds of ray and the triangle step differs only in what a hit
-// means, so here the kind is a per-lane flag: when the closest-hit queue is dry the wave's idle lanes are refilled from the shadow
-// queue while its last closest-hit rays are still walking.  One tail per wave and launch instead of two.  Every ray is traced by
-// exactly the step functions of the separate loops, so frames and counts are unchanged.
-template <bool COUNT>
-__device__ __forceinline__ void trace_queue_mixed(const PtScene& sc, const PtState& st, const uint32_t* __restrict__ queue,
-                                                  const uint32_t* __restrict__ closest_count, uint32_t* __restrict__ closest_head,
-                                                  const uint32_t* __restrict__ shadow_count, uint32_t* __restrict__ shadow_head,
-                                                  unsigned long long* __restrict__ stats, TravStack& stk, const uint8_t* perm_lut, uint32_t refill_min) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const uint32_t n_closest = uniform(*closest_count), n_shadow = uniform(*shadow_count);
-    const int tris_per_round = (int)((refill_min >> 8) & 0xffu) ? (int)((refill_min >> 8) & 0xffu) : kTrisPerRound;
-    refill_min &= 0xffu;
-    TravCounters tc{0, 0, 0};                          // COUNT: the current ray of this lane
-    uint32_t cl_nodes = 0, cl_tris = 0, any_nodes = 0, any_tris = 0;  // COUNT: retired rays of this lane, by kind
-
-    TRay r = make_tray(mk(0.0f, 0.0f, 0.0f), mk(0.0f, 1.0f, 0.0f), 0.0f);
-    Hit best{0.0f, -1, 0u};
-    Group G{0u, 0u}, T{0u, 0u};
-    uint32_t slot = 0;  // closest: path id; any-hit: shadow-queue index
-    bool has_ray = false, occluded = false, alive = false;
-    bool is_any = false;  // the kind of this lane's ray
-    // wave-uniform: which queue the wave refills from, and its state
-    uint32_t phase = n_closest == 0u ? 1u : 0u;  // 0 = closest-hit queue, 1 = shadow queue
-    uint32_t n = phase == 0u ? n_closest : n_shadow;
-    uint32_t* head = phase == 0u ? closest_head : shadow_head;
-    bool exhausted = n == 0u;  // both queues dry
-    const uint32_t stream0 = uniform((blockIdx.x * 4u + (threadIdx.x >> 6)) & (PT_HEADS - 1u));
-    uint32_t stream = stream0, dry_streams = 0;
-    uint32_t rounds = 0, alive_rounds = 0;  // COUNT only
-
-    for (;;) {
-        const unsigned long long idle = __ballot(!alive);
-        if (idle == ~0ull || (!exhausted && (uint32_t)__popcll(idle) >= refill_min)) {
-            if (!alive && has_ray) {  // retire
-                if (is_any) {
-                    if (!occluded) {
-                        const uint32_t pid = __float_as_uint(st.sh_o[slot].w);
-                        const float4 c = st.sh_c[slot];
-                        float4 L = st.rad[pid];
-                        L.x += c.x;
-                        L.y += c.y;
-                        L.z += c.z;
-                        st.rad[pid] = L;
-                    }
-                    if (COUNT) {
-                        any_nodes += tc.nodes;
-                        any_tris += tc.tris;
-                    }
-                } else {
-                    st.hit[slot] = make_float2(best.t, __int_as_float(best.li));
-                    if (COUNT) {
-                        cl_nodes += tc.nodes;
-                        cl_tris += tc.tris;
-                    }
-                }
-                if (COUNT) tc.nodes = tc.tris = 0;
-                has_ray = false;
-            }
-            if (!exhausted) {
-                // (as trace_queue: one returning atomic on the wave's stream head reserves what the idle lanes need)
-                const uint32_t want = (uint32_t)__popcll(idle);
-                const uint32_t my_rank = (uint32_t)__popcll(idle & lt_mask);
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(head + stream * PT_HEAD_STRIDE, want);
-                base = __builtin_amdgcn_readfirstlane(base);
-                const uint32_t j = base + my_rank, je = base + want;
-                const uint32_t i = !alive ? ((((j >> 6) * PT_HEADS + stream) << 6) | (j & 63u)) : n;
-                const bool take = !alive && i < n;
-                if (take) {
-                    if (phase != 0u) {
-                        const float4 so = st.sh_o[i], sd = st.sh_d[i];
-                        r = make_tray(mk(so.x, so.y, so.z), mk(sd.x, sd.y, sd.z), kShadowTmax);
-                        slot = i;
-                        occluded = false;
-                        is_any = true;
-                    } else {
-                        slot = queue[i];
-                        const float4 ro = st.ray_o[slot], rd = st.ray_d[slot];
-                        r = make_tray(mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z), __builtin_inff());
-                        best = Hit{__builtin_inff(), -1, 0xffffffffu};
-                        is_any = false;
-                    }
-                    has_ray = true;
-                    alive = true;
-                    G = root_group();
-                    T = Group{0u, 0u};
-                    stk.sp = 0;
-                }
-                if (((((je >> 6) * PT_HEADS + stream) << 6) | (je & 63u)) >= n) {  // this stream is dry: move on
-                    stream = (stream + 1u) & (PT_HEADS - 1u);
-                    if (++dry_streams >= PT_HEADS) {  // this queue is dry: on to the shadow queue, or done
-                        if (phase == 0u && n_shadow != 0u) {
-                            phase = 1u;
-                            n = n_shadow;
-                            head = shadow_head;
-                            stream = stream0;
-                            dry_streams = 0u;
-                        } else {
-                            exhausted = true;
-                        }
-                    }
-                }
-            }
-            if (__ballot(alive) == 0ull && exhausted) break;  // both queues drained and every lane retired
-        }
-        if (COUNT) {
-            rounds++;
-            alive_rounds += (uint32_t)__popcll(__ballot(alive));
-        }
-        // node phase: lanes without pending triangles visit their next node
-        if (alive && !has_tris(T)) {
-            if (!has_nodes(G)) {
-                if (stk.sp) G = stk.pop();
-                else alive = false;
-            }
-            if (alive) node_step<COUNT>(sc.nodes, perm_lut, r, G, T, stk, tc);
-        }
-        // triangle phase: one test, then what a hit means to this lane's kind of ray
-#pragma unroll 1
-        for (int it = 0; it < tris_per_round; it++) {
-            if (alive && has_tris(T)) {
-                if (tri_step_mixed<COUNT>(sc.tris, r, best, T, tc, is_any)) {
-                    occluded = true;
-                    alive = false;
-                }
-            }
-        }
-    }
-    if (COUNT) {
-        unsigned long long a = cl_nodes, b = cl_tris, c = any_nodes, d = any_tris;
-        for (int off = 32; off > 0; off >>= 1) {
-            a += __shfl_down(a, off);
-            b += __shfl_down(b, off);
-            c += __shfl_down(c, off);
-            d += __shfl_down(d, off);
-        }
-        if (lane == 0) {
-            atomicAdd(&stats[6], (unsigned long long)rounds);
-            atomicAdd(&stats[7], (unsigned long long)alive_rounds);
-            atomicAdd(&stats[14], (unsigned long long)rounds);
-            atomicAdd(&stats[0], a);
-            atomicAdd(&stats[1], b);
-            atomicAdd(&stats[11], c);
-            atomicAdd(&stats[12], d);
-        }
-    }
-    if (tc.overflow) atomicOr((unsigned int*)&stats[2], 1u);
+    flush_trace_counters<COUNT>(stats, lane, ANY ? 2u : 1u, tc, tc, shadow_stat, rounds, alive_rounds, tc.flushes, tc.overflow);
 }
 
 // ---- software-pipelined refill (TRI_INLINE_PF) ------------------------------------------------------
@@ -1015,14 +1020,12 @@ typedef float f4v __attribute__((ext_vector_type(4)));  // native vector: HIP's 
 typedef __attribute__((address_space(3))) f4v lds_f4;
 
 template <bool ANY, bool COUNT>
-__device__ __forceinline__ void trace_queue_pf(const PtScene& sc, const PtState& st, const uint32_t* __restrict__ queue,
-                                               const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ head,
+__device__ __forceinline__ void trace_queue_pf(const PtScene& sc, const PtState& st, const uint32_t* __restrict__ queue, QueueRef q,
                                                unsigned long long* __restrict__ stats, TravStack& stk, const uint8_t* perm_lut, uint32_t refill_min,
-                                               lds_f4* ring /* 2 x kPfRing: origin as loaded, (direction, slot bits) */, uint32_t shadow_stat = 4u) {
+                                               lds_f4* ring /* 2 x kPfRing: origin as loaded, (direction, slot bits) */, uint32_t shadow_stat) {
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const uint32_t n = uniform(*count_ptr);
-    const int tris_per_round = (int)((refill_min >> 8) & 0xffu) ? (int)((refill_min >> 8) & 0xffu) : kTrisPerRound;
+    const int tris_per_round = tris_per_round_of(refill_min);
     const uint32_t pop_min = (refill_min & 0xffu) ? ((refill_min & 0xffu) < 64u ? (refill_min & 0xffu) : 64u) : 8u;
     TravCounters tc{0, 0, 0};
 
@@ -1034,8 +1037,8 @@ __device__ __forceinline__ void trace_queue_pf(const PtScene& sc, const PtState&
     uint32_t rounds = 0, alive_rounds = 0;  // COUNT only
 
     // fetch pipeline (wave-uniform unless noted)
-    uint32_t stream = uniform((blockIdx.x * 4u + (threadIdx.x >> 6)) & (PT_HEADS - 1u));
-    uint32_t dry_streams = 0;
+    QueueCursor cur{uniform(*q.count), q.head, home_stream(), 0u};
+    const uint32_t n = cur.n;
     uint32_t fetch_done = n == 0u ? 1u : 0u;  // every stream of the queue has been found dry
     uint32_t pf_stage = 0;                // 0 idle, 1 entries reserved, 2 queue entries read (closest-hit only), 3 rays read
     uint32_t pf_base = 0;                 // lane 0: what the head atomic returned
@@ -1051,8 +1054,8 @@ __device__ __forceinline__ void trace_queue_pf(const PtScene& sc, const PtState&
         pf_stage = uniform(pf_stage);
         ring_head = uniform(ring_head);
         ring_count = uniform(ring_count);
-        stream = uniform(stream);
-        dry_streams = uniform(dry_streams);
+        cur.stream = uniform(cur.stream);
+        cur.dry_streams = uniform(cur.dry_streams);
         fetch_done = uniform(fetch_done);
         // ---- one pipeline stage per round; every value used here was requested a round ago ----
         if (pf_stage == 3u) {
@@ -1075,14 +1078,9 @@ __device__ __forceinline__ void trace_queue_pf(const PtScene& sc, const PtState&
             pf_d = *reinterpret_cast<const f4v*>(&st.ray_d[pf_slot]);
             pf_stage = 3u;
         } else if (pf_stage == 1u) {
-            // Stream-local entry j of stream k is queue entry ((j / 64) * PT_HEADS + k) * 64 + j % 64.
             const uint32_t base = uniform(pf_base);
-            const uint32_t j = base + lane, je = base + kPfBatch;
-            pf_idx = lane < kPfBatch ? ((((j >> 6) * PT_HEADS + stream) << 6) | (j & 63u)) : n;
-            if (((((je >> 6) * PT_HEADS + stream) << 6) | (je & 63u)) >= n) {  // this stream is dry (entries grow with j): move on
-                stream = (stream + 1u) & (PT_HEADS - 1u);
-                fetch_done = ++dry_streams >= PT_HEADS ? 1u : 0u;
-            }
+            pf_idx = lane < kPfBatch ? stream_entry(cur.stream, base + lane) : n;
+            if (cur.advance_if_dry(base + kPfBatch)) fetch_done = 1u;
             const uint32_t safe = pf_idx < n ? pf_idx : n - 1u;  // n > 0 here
             if (ANY) {
                 pf_o = *reinterpret_cast<const f4v*>(&st.sh_o[safe]);
@@ -1095,7 +1093,7 @@ __device__ __forceinline__ void trace_queue_pf(const PtScene& sc, const PtState&
             }
         }
         if (pf_stage == 0u && !fetch_done && ring_count + kPfBatch <= kPfRing) {
-            if (lane == 0) pf_base = atomicAdd(head + stream * PT_HEAD_STRIDE, kPfBatch);
+            if (lane == 0) pf_base = atomicAdd(cur.head_word(), kPfBatch);  // (QueueCursor::reserve without the wait for the answer)
             pf_stage = 1u;
         }
 
@@ -1104,20 +1102,8 @@ __device__ __forceinline__ void trace_queue_pf(const PtScene& sc, const PtState&
         const uint32_t n_idle = (uint32_t)__popcll(idle);
         const bool drained = fetch_done && pf_stage == 0u && ring_count == 0u;
         if ((ring_count != 0u && n_idle >= pop_min) || (n_idle == 64u && (ring_count != 0u || drained))) {
-            if (!alive && has_ray) {  // retire
-                if (ANY) {
-                    if (!occluded) {
-                        const uint32_t pid = __float_as_uint(st.sh_o[slot].w);
-                        const float4 c = st.sh_c[slot];
-                        float4 L = st.rad[pid];
-                        L.x += c.x;
-                        L.y += c.y;
-                        L.z += c.z;
-                        st.rad[pid] = L;
-                    }
-                } else {
-                    st.hit[slot] = make_float2(best.t, __int_as_float(best.li));
-                }
+            if (!alive && has_ray) {
+                retire_ray(st, ANY, slot, occluded, best);
                 has_ray = false;
             }
             const uint32_t m = n_idle < ring_count ? n_idle : ring_count;
@@ -1126,18 +1112,10 @@ __device__ __forceinline__ void trace_queue_pf(const PtScene& sc, const PtState&
                 const uint32_t pos = (ring_head + rank) & (kPfRing - 1u);
                 const f4v ro = ring[2u * pos], rd = ring[2u * pos + 1u];
                 slot = __float_as_uint(rd.w);
-                if (ANY) {
-                    r = make_tray(mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z), kShadowTmax);
-                    occluded = false;
-                } else {
-                    r = make_tray(mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z), __builtin_inff());
-                    best = Hit{__builtin_inff(), -1, 0xffffffffu};
-                }
+                start_ray(ANY, mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z), r, best, G, T, stk);
+                occluded = false;
                 has_ray = true;
                 alive = true;
-                G = root_group();
-                T = Group{0u, 0u};
-                stk.sp = 0;
             }
             ring_head = uniform(ring_head + m);
             ring_count = uniform(ring_count - m);
@@ -1148,42 +1126,9 @@ __device__ __forceinline__ void trace_queue_pf(const PtScene& sc, const PtState&
             rounds++;
             alive_rounds += (uint32_t)__popcll(__ballot(alive));
         }
-        // node phase: lanes without pending triangles visit their next node
-        if (alive && !has_tris(T)) {
-            if (!has_nodes(G)) {
-                if (stk.sp) G = stk.pop();
-                else alive = false;
-            }
-            if (alive) node_step<COUNT>(sc.nodes, perm_lut, r, G, T, stk, tc);
-        }
-        // triangle phase
-#pragma unroll 1
-        for (int it = 0; it < tris_per_round; it++) {
-            if (alive && has_tris(T)) {
-                if (tri_step<ANY, COUNT>(sc.tris, r, best, T, tc)) {
-                    occluded = true;
-                    alive = false;
-                }
-            }
-        }
+        alive = inline_round<COUNT, false>(sc, perm_lut, r, best, G, T, stk, tc, alive, occluded, ANY, tris_per_round);
     }
-    if (COUNT) {
-        unsigned long long a = tc.nodes, b = tc.tris;
-        for (int off = 32; off > 0; off >>= 1) {
-            a += __shfl_down(a, off);
-            b += __shfl_down(b, off);
-        }
-        if (lane == 0) {
-            if (!ANY) {
-                atomicAdd(&stats[6], (unsigned long long)rounds);
-                atomicAdd(&stats[7], (unsigned long long)alive_rounds);
-            }
-            atomicAdd(&stats[14], (unsigned long long)rounds);
-            atomicAdd(&stats[ANY ? shadow_stat : 0u], a);
-            atomicAdd(&stats[ANY ? shadow_stat + 1u : 1u], b);
-        }
-    }
-    if (tc.overflow) atomicOr((unsigned int*)&stats[2], 1u);
+    flush_trace_counters<COUNT>(stats, lane, ANY ? 2u : 1u, tc, tc, shadow_stat, rounds, alive_rounds, 0u, tc.overflow);
 }
 
 // LDS of a 256-thread workgroup of the per-lane kernels: the traversal stacks (dynamic), the octant table and, for TRI_POOL
@@ -1204,7 +1149,6 @@ struct PoolLds<TRI_POOL> {
 template <>
 struct PoolLds<TRI_INLINE_PF> {
     f4v rays[4][2 * kPfRing];
-    __device__ __forceinline__ PoolMem get(uint32_t) { return PoolMem{nullptr, nullptr, nullptr}; }
     __device__ __forceinline__ lds_f4* ring(uint32_t wave) { return (lds_f4*)rays[wave]; }
 };
 constexpr uint32_t kPoolLdsBytes = 4u * (kPoolRing * 8u + 64u * 8u + 64u * 4u);
@@ -1212,19 +1156,35 @@ constexpr uint32_t kPfLdsBytes = 4u * 2u * kPfRing * 16u;
 constexpr int kInlineWaves = 8;  // (7 = 72 VGPRs compiles to the same instruction count)
 constexpr int kPfWaves = 6;    // TRI_INLINE_PF: the prefetch registers (two 16-byte tuples, index, slot) do not fit 72 VGPRs without spills in the loop
 constexpr int kPoolWaves = 7;  // waves per SIMD the TRI_POOL / TRI_DEFER kernels are compiled for (72 VGPRs; the default stack split leaves room for seven workgroups per CU anyway)
+constexpr int trace_waves(int mode) { return mode == TRI_INLINE ? kInlineWaves : mode == TRI_INLINE_PF ? kPfWaves : kPoolWaves; }
+
+// This thread's traversal stack: column threadIdx.x of the workgroup's dynamic LDS (sk.lds_cap x 256 entries), then its spill column
+__device__ __forceinline__ TravStack make_trav_stack(unsigned long long* lds_stack, const StackCfg& sk) {
+    const size_t gtid = (size_t)blockIdx.x * 256u + threadIdx.x;
+    return TravStack{(lds_u64*)&lds_stack[threadIdx.x], sk.spill + gtid, sk.spill_stride, sk.lds_cap, sk.spill_cap, 0};
+}
+
+// One queue with the schedule MODE, for a wave whose stack, octant table and pool memory stand
+template <bool ANY, bool COUNT, int MODE>
+__device__ __forceinline__ void trace_one_queue(const PtScene& sc, const PtState& st, const uint32_t* __restrict__ queue, QueueRef q,
+                                                unsigned long long* __restrict__ stats, TravStack& stk, const uint8_t* perm_lut, PoolLds<MODE>& pool,
+                                                uint32_t refill_min, uint32_t tri_cfg, uint32_t shadow_stat) {
+    const uint32_t wave = threadIdx.x >> 6;
+    if constexpr (MODE == TRI_INLINE_PF) trace_queue_pf<ANY, COUNT>(sc, st, queue, q, stats, stk, perm_lut, refill_min, pool.ring(wave), shadow_stat);
+    else if constexpr (MODE == TRI_INLINE) trace_queue_inline<ANY ? RAYS_ANY : RAYS_CLOSEST, COUNT>(sc, st, queue, q, q, stats, stk, perm_lut, refill_min, shadow_stat);
+    else trace_queue<ANY, COUNT, MODE>(sc, st, queue, q, stats, stk, perm_lut, refill_min, pool.get(wave), tri_cfg, shadow_stat);
+}
 
 template <bool ANY, bool COUNT, int MODE>
-__global__ __launch_bounds__(256, MODE == TRI_INLINE ? kInlineWaves : MODE == TRI_INLINE_PF ? kPfWaves : kPoolWaves) void pt_trace(const PtScene sc, PtState st, const uint32_t* __restrict__ queue,
-                                                const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ head,
-                                                unsigned long long* __restrict__ stats, const StackCfg sk, uint32_t refill_min, uint32_t tri_cfg) {
+__global__ __launch_bounds__(256, trace_waves(MODE)) void pt_trace(const PtScene sc, PtState st, const uint32_t* __restrict__ queue,
+                                                                   const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ head,
+                                                                   unsigned long long* __restrict__ stats, const StackCfg sk, uint32_t refill_min, uint32_t tri_cfg) {
     extern __shared__ unsigned long long lds_stack[];  // sk.lds_cap x 256 entries
     __shared__ uint8_t perm_lut[2048];
     __shared__ PoolLds<MODE> pool;
     build_perm_lut(perm_lut);
-    const size_t gtid = (size_t)blockIdx.x * 256u + threadIdx.x;
-    TravStack stk{(lds_u64*)&lds_stack[threadIdx.x], sk.spill + gtid, sk.spill_stride, sk.lds_cap, sk.spill_cap, 0};
-    if constexpr (MODE == TRI_INLINE_PF) trace_queue_pf<ANY, COUNT>(sc, st, queue, count_ptr, head, stats, stk, perm_lut, refill_min, pool.ring(threadIdx.x >> 6));
-    else trace_queue<ANY, COUNT, MODE>(sc, st, queue, count_ptr, head, stats, stk, perm_lut, refill_min, pool.get(threadIdx.x >> 6), tri_cfg);
+    TravStack stk = make_trav_stack(lds_stack, sk);
+    trace_one_queue<ANY, COUNT, MODE>(sc, st, queue, QueueRef{count_ptr, head}, stats, stk, perm_lut, pool, refill_min, tri_cfg, PT_STAT_SHADOW);
 }
 
 // closest-hit rays of depth d + 1 and the shadow rays of depth d in ONE persistent launch: the two are independent (the
@@ -1232,31 +1192,25 @@ __global__ __launch_bounds__(256, MODE == TRI_INLINE ? kInlineWaves : MODE == TR
 // closest-hit queue - the frame's critical path: shade(d + 1) waits for it - and moves on to the shadow queue when that one
 // is dry, instead of leaving the machine to the few long rays of a launch's tail.  One tail per bounce instead of two.
 template <bool COUNT, int MODE>
-__global__ __launch_bounds__(256, MODE == TRI_INLINE ? kInlineWaves : MODE == TRI_INLINE_PF ? kPfWaves : kPoolWaves) void pt_trace_fused(const PtScene sc, PtState st, const uint32_t* __restrict__ queue,
-                                                      const uint32_t* __restrict__ closest_count, uint32_t* __restrict__ closest_head,
-                                                      const uint32_t* __restrict__ shadow_count, uint32_t* __restrict__ shadow_head,
-                                                      unsigned long long* __restrict__ stats, const StackCfg sk, uint32_t refill_min, uint32_t tri_cfg) {
+__global__ __launch_bounds__(256, trace_waves(MODE)) void pt_trace_fused(const PtScene sc, PtState st, const uint32_t* __restrict__ queue,
+                                                                         const uint32_t* __restrict__ closest_count, uint32_t* __restrict__ closest_head,
+                                                                         const uint32_t* __restrict__ shadow_count, uint32_t* __restrict__ shadow_head,
+                                                                         unsigned long long* __restrict__ stats, const StackCfg sk, uint32_t refill_min, uint32_t tri_cfg) {
     extern __shared__ unsigned long long lds_stack[];
     __shared__ uint8_t perm_lut[2048];
     __shared__ PoolLds<MODE> pool;
     build_perm_lut(perm_lut);
-    const size_t gtid = (size_t)blockIdx.x * 256u + threadIdx.x;
-    TravStack stk{(lds_u64*)&lds_stack[threadIdx.x], sk.spill + gtid, sk.spill_stride, sk.lds_cap, sk.spill_cap, 0};
-    if constexpr (MODE == TRI_INLINE_PF) {
-        trace_queue_pf<false, COUNT>(sc, st, queue, closest_count, closest_head, stats, stk, perm_lut, refill_min, pool.ring(threadIdx.x >> 6));
-        trace_queue_pf<true, COUNT>(sc, st, nullptr, shadow_count, shadow_head, stats, stk, perm_lut, refill_min, pool.ring(threadIdx.x >> 6), 11u);
-    } else if constexpr (MODE == TRI_INLINE) {
-        if (tri_cfg & 1u) {  // tuning: the two loops one after the other (every wave drains between the queues)
-            const PoolMem pm = pool.get(threadIdx.x >> 6);
-            trace_queue<false, COUNT, MODE>(sc, st, queue, closest_count, closest_head, stats, stk, perm_lut, refill_min, pm, tri_cfg);
-            trace_queue<true, COUNT, MODE>(sc, st, nullptr, shadow_count, shadow_head, stats, stk, perm_lut, refill_min, pm, tri_cfg, 11u);
-        } else {
-            trace_queue_mixed<COUNT>(sc, st, queue, closest_count, closest_head, shadow_count, shadow_head, stats, stk, perm_lut, refill_min);
-        }
+    TravStack stk = make_trav_stack(lds_stack, sk);
+    const QueueRef closest_q{closest_count, closest_head}, shadow_q{shadow_count, shadow_head};
+    // the inline schedule carries both kinds of ray in one loop; the other schedules, and as a tuning variant the inline one too
+    // (tri_cfg bit 0), run the two loops one after the other (every wave drains between the queues)
+    // (the one loop in the else branch, not first behind an early return: there the compiler lays it out with its header block last,
+    // two more taken branches per round - 2 % of the fused launch on the terrain scene, profiles/refactor_trace_loops.txt)
+    if (MODE != TRI_INLINE || (tri_cfg & 1u)) {
+        trace_one_queue<false, COUNT, MODE>(sc, st, queue, closest_q, stats, stk, perm_lut, pool, refill_min, tri_cfg, PT_STAT_SHADOW);
+        trace_one_queue<true, COUNT, MODE>(sc, st, nullptr, shadow_q, stats, stk, perm_lut, pool, refill_min, tri_cfg, PT_STAT_FUSED_SHADOW);
     } else {
-        const PoolMem pm = pool.get(threadIdx.x >> 6);
-        trace_queue<false, COUNT, MODE>(sc, st, queue, closest_count, closest_head, stats, stk, perm_lut, refill_min, pm, tri_cfg);
-        trace_queue<true, COUNT, MODE>(sc, st, nullptr, shadow_count, shadow_head, stats, stk, perm_lut, refill_min, pm, tri_cfg, 11u);
+        trace_queue_inline<RAYS_BOTH, COUNT>(sc, st, queue, closest_q, shadow_q, stats, stk, perm_lut, refill_min, PT_STAT_FUSED_SHADOW);
     }
 }
 
@@ -1274,6 +1228,43 @@ __global__ __launch_bounds__(256, MODE == TRI_INLINE ? kInlineWaves : MODE == TR
 constexpr int kPkStack = (int)kPacketStackEntries;  // one pending sibling group per tree level; render_pt_common sends trees whose stack_need exceeds it
                                                    // (single-level: depth <= kBvhMaxDepth / 3 + 2; a flattened two-level tree adds its top level) to the per-lane kernel
 
+// What both packet kernels do first - the generate stage, fused: the kernel makes the camera rays it traces (pt_shade(0) needs only
+// the direction) - and last.  Returns whether path pid exists.
+struct PacketRays {
+    v3 o;  // wave-uniform
+    v3 d, inv, noi;
+    uint32_t oct_inv;
+};
+__device__ __forceinline__ bool packet_camera_ray(const PtFrame& f, const PtState& st, uint32_t pid, PacketRays& p) {
+    bool alive = false;
+    p.d = mk(0.0f, 1.0f, 0.0f);
+    if (pid < f.n_paths) {
+        const uint32_t slot = pid / f.spp_batch;
+        uint32_t px, py, lx, ly, k;
+        alive = slot_pixel(f, slot, px, py, lx, ly, k);
+        if (alive) {
+            p.d = camera_dir(f, px, py, f.sample0 + (pid - slot * f.spp_batch));
+            st.ray_d[pid] = make_float4(p.d.x, p.d.y, p.d.z, 0.0f);
+        }
+    }
+    p.o = mk(f.cam.pos[0], f.cam.pos[1], f.cam.pos[2]);
+    p.inv = safe_inv(p.d);
+    p.noi = mk(-(p.o.x * p.inv.x), -(p.o.y * p.inv.y), -(p.o.z * p.inv.z));
+    p.oct_inv = octant_inv(p.d);
+    return alive;
+}
+template <bool COUNT>
+__device__ __forceinline__ void packet_finish(const PtState& st, unsigned long long* __restrict__ stats, uint32_t pid, uint32_t lane, bool alive, const Hit& best,
+                                              uint32_t n_nodes, uint32_t n_tris, uint32_t overflow /* the last three wave-uniform */) {
+    if (alive) st.hit[pid] = make_float2(best.t, __int_as_float(best.li));
+    if (COUNT && lane == 0) {  // records fetched once per wave
+        atomicAdd(&stats[PT_STAT_PACKETS + 1], (unsigned long long)n_nodes);
+        atomicAdd(&stats[PT_STAT_PACKETS + 2], (unsigned long long)n_tris);
+        atomicAdd(&stats[PT_STAT_PACKETS], 1ull);
+    }
+    if (overflow && lane == 0) atomicOr((unsigned int*)&stats[PT_STAT_OVERFLOW], 1u);
+}
+
 template <bool COUNT>
 __global__ __launch_bounds__(256) void pt_trace_packet(const PtScene sc, const PtFrame f, PtState st, unsigned long long* __restrict__ stats) {
     // (PtState is passed by value: its pointers are written through)
@@ -1284,21 +1275,10 @@ __global__ __launch_bounds__(256) void pt_trace_packet(const PtScene sc, const P
     unsigned long long* stack = s_stack[wv];
     const uint32_t pid = (blockIdx.x * 4u + wv) * 64u + lane;
 
-    bool alive = false;
-    v3 d = mk(0.0f, 1.0f, 0.0f);
-    if (pid < f.n_paths) {  // the generate stage, fused: this kernel makes the camera rays it traces (pt_shade(0) needs only the direction)
-        const uint32_t slot = pid / f.spp_batch;
-        uint32_t px, py, lx, ly, k;
-        alive = slot_pixel(f, slot, px, py, lx, ly, k);
-        if (alive) {
-            d = camera_dir(f, px, py, f.sample0 + (pid - slot * f.spp_batch));
-            st.ray_d[pid] = make_float4(d.x, d.y, d.z, 0.0f);
-        }
-    }
-    const v3 o = mk(f.cam.pos[0], f.cam.pos[1], f.cam.pos[2]);  // wave-uniform
-    const v3 inv = safe_inv(d);
-    const v3 noi = mk(-(o.x * inv.x), -(o.y * inv.y), -(o.z * inv.z));
-    const uint32_t oct_inv = ((__float_as_uint(d.x) >> 31) ? 0u : 4u) | ((__float_as_uint(d.y) >> 31) ? 0u : 2u) | ((__float_as_uint(d.z) >> 31) ? 0u : 1u);
+    PacketRays pr;
+    const bool alive = packet_camera_ray(f, st, pid, pr);
+    const v3 o = pr.o, d = pr.d, inv = pr.inv, noi = pr.noi;
+    const uint32_t oct_inv = pr.oct_inv;
     Hit best{__builtin_inff(), -1, 0xffffffffu};
 
     // lane k < 48 decodes plane k of a node: byte 32 + k = qlo.x[8] qlo.y[8] qlo.z[8] qhi.x[8] qhi.y[8] qhi.z[8]
@@ -1395,13 +1375,7 @@ __global__ __launch_bounds__(256) void pt_trace_packet(const PtScene sc, const P
             gy = inner_hits | imask;
         }
     }
-    if (alive) st.hit[pid] = make_float2(best.t, __int_as_float(best.li));
-    if (COUNT && lane == 0) {  // records fetched once per wave
-        atomicAdd(&stats[9], (unsigned long long)n_nodes);
-        atomicAdd(&stats[10], (unsigned long long)n_tris);
-        atomicAdd(&stats[8], 1ull);
-    }
-    if (overflow && lane == 0) atomicOr((unsigned int*)&stats[2], 1u);
+    packet_finish<COUNT>(st, stats, pid, lane, alive, best, n_nodes, n_tris, overflow);
 }
 
 // ---- packet trace, interval form ---------------------------------------------------------------------
@@ -1421,30 +1395,26 @@ typedef __attribute__((address_space(3))) float lds_f32;
 // v = max(v, v of the lane the DPP control names); written out because the builtin form (v_mov_dpp, then fmaxf) pays a
 // canonicalising v_max per operand.  s_nop 1: a DPP read of a VGPR needs two wait states behind the VALU write, which the
 // compiler does not insert for text it does not parse.
-#define RT_DPP_MAX(v, ctrl) asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 " ctrl " row_mask:0xf bank_mask:0xf" : "+v"(v))
-// largest of a wave-uniform set of NON-NEGATIVE floats, one per lane (integer order = float order): rows by DPP, then the scalar unit
-__device__ __forceinline__ float wave_max_nonneg(float v) {
-    RT_DPP_MAX(v, "quad_perm:[1,0,3,2]");
-    RT_DPP_MAX(v, "quad_perm:[2,3,0,1]");
-    RT_DPP_MAX(v, "row_half_mirror");
-    RT_DPP_MAX(v, "row_mirror");
+#define RT_DPP_F32(op, v, ctrl) asm("s_nop 1\n\tv_" op "_f32_dpp %0, %0, %0 " ctrl " row_mask:0xf bank_mask:0xf" : "+v"(v))
+#define RT_DPP_MAX(v, ctrl) RT_DPP_F32("max", v, ctrl)
+#define RT_DPP_ROWS(op, v)                    \
+    do {                                      \
+        RT_DPP_F32(op, v, "quad_perm:[1,0,3,2]"); \
+        RT_DPP_F32(op, v, "quad_perm:[2,3,0,1]"); \
+        RT_DPP_F32(op, v, "row_half_mirror");     \
+        RT_DPP_F32(op, v, "row_mirror");          \
+    } while (0)
+// largest (IS_MAX) or smallest of a wave-uniform set of NON-NEGATIVE floats, one per lane (integer order = float order): rows by DPP,
+// then the scalar unit
+template <bool IS_MAX>
+__device__ __forceinline__ float wave_reduce_nonneg(float v) {
+    if (IS_MAX) RT_DPP_ROWS("max", v);
+    else RT_DPP_ROWS("min", v);
     const uint32_t b = __float_as_uint(v);
     const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)b, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)b, 16);
     const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)b, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)b, 48);
-    const uint32_t m01 = r0 > r1 ? r0 : r1, m23 = r2 > r3 ? r2 : r3;
-    return __uint_as_float(m01 > m23 ? m01 : m23);
-}
-#define RT_DPP_MIN(v, ctrl) asm("s_nop 1\n\tv_min_f32_dpp %0, %0, %0 " ctrl " row_mask:0xf bank_mask:0xf" : "+v"(v))
-__device__ __forceinline__ float wave_min_nonneg(float v) {
-    RT_DPP_MIN(v, "quad_perm:[1,0,3,2]");
-    RT_DPP_MIN(v, "quad_perm:[2,3,0,1]");
-    RT_DPP_MIN(v, "row_half_mirror");
-    RT_DPP_MIN(v, "row_mirror");
-    const uint32_t b = __float_as_uint(v);
-    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)b, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)b, 16);
-    const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)b, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)b, 48);
-    const uint32_t m01 = r0 < r1 ? r0 : r1, m23 = r2 < r3 ? r2 : r3;
-    return __uint_as_float(m01 < m23 ? m01 : m23);
+    const uint32_t m01 = (IS_MAX ? r0 > r1 : r0 < r1) ? r0 : r1, m23 = (IS_MAX ? r2 > r3 : r2 < r3) ? r2 : r3;
+    return __uint_as_float((IS_MAX ? m01 > m23 : m01 < m23) ? m01 : m23);
 }
 template <bool COUNT, bool PURE, bool FARCAP>
 __global__ __launch_bounds__(256) void pt_trace_packet_ia(const PtScene sc, const PtFrame f, PtState st, unsigned long long* __restrict__ stats) {
@@ -1454,21 +1424,10 @@ __global__ __launch_bounds__(256) void pt_trace_packet_ia(const PtScene sc, cons
     lds_f4* planes4 = (lds_f4*)s_planes[wv];
     const uint32_t pid = (blockIdx.x * 4u + wv) * 64u + lane;
 
-    bool alive = false;
-    v3 d = mk(0.0f, 1.0f, 0.0f);
-    if (pid < f.n_paths) {
-        const uint32_t slot = pid / f.spp_batch;
-        uint32_t px, py, lx, ly, k;
-        alive = slot_pixel(f, slot, px, py, lx, ly, k);
-        if (alive) {
-            d = camera_dir(f, px, py, f.sample0 + (pid - slot * f.spp_batch));
-            st.ray_d[pid] = make_float4(d.x, d.y, d.z, 0.0f);
-        }
-    }
-    const v3 o = mk(f.cam.pos[0], f.cam.pos[1], f.cam.pos[2]);  // wave-uniform
-    const v3 inv = safe_inv(d);
-    const v3 noi = mk(-(o.x * inv.x), -(o.y * inv.y), -(o.z * inv.z));
-    const uint32_t oct_inv = ((__float_as_uint(d.x) >> 31) ? 0u : 4u) | ((__float_as_uint(d.y) >> 31) ? 0u : 2u) | ((__float_as_uint(d.z) >> 31) ? 0u : 1u);
+    PacketRays pr;
+    const bool alive = packet_camera_ray(f, st, pid, pr);
+    const v3 o = pr.o, d = pr.d, inv = pr.inv, noi = pr.noi;
+    const uint32_t oct_inv = pr.oct_inv;
     Hit best{__builtin_inff(), -1, 0xffffffffu};
 
     // lane 8c + k: plane k of child c
@@ -1488,9 +1447,9 @@ __global__ __launch_bounds__(256) void pt_trace_packet_ia(const PtScene sc, cons
         // (by magnitude - rows by DPP, the four rows on the scalar unit in integer order - and the pass's sign put back; which end is
         // "min" does not matter: the bounds below take the smaller of the two products)
         const float ax = __builtin_fabsf(inv.x), ay = __builtin_fabsf(inv.y), az = __builtin_fabsf(inv.z);
-        const float ix0 = wave_min_nonneg(act ? ax : inf), ix1 = wave_max_nonneg(act ? ax : 0.0f);
-        const float iy0 = wave_min_nonneg(act ? ay : inf), iy1 = wave_max_nonneg(act ? ay : 0.0f);
-        const float iz0 = wave_min_nonneg(act ? az : inf), iz1 = wave_max_nonneg(act ? az : 0.0f);
+        const float ix0 = wave_reduce_nonneg<false>(act ? ax : inf), ix1 = wave_reduce_nonneg<true>(act ? ax : 0.0f);
+        const float iy0 = wave_reduce_nonneg<false>(act ? ay : inf), iy1 = wave_reduce_nonneg<true>(act ? ay : 0.0f);
+        const float iz0 = wave_reduce_nonneg<false>(act ? az : inf), iz1 = wave_reduce_nonneg<true>(act ? az : 0.0f);
         const float i_sign = ((oct >> (2u - (p_axis < 2u ? p_axis : 2u))) & 1u) != 0u ? 1.0f : -1.0f;  // oct bit set: direction >= 0
         const float imin = i_sign * (p_axis == 0u ? ix0 : p_axis == 1u ? iy0 : iz0), imax = i_sign * (p_axis == 0u ? ix1 : p_axis == 1u ? iy1 : iz1);
         // near lanes bound t from below: min(u * imin, u * imax); far lanes bound -t from below: min(u * -imin, u * -imax)
@@ -1589,23 +1548,11 @@ __global__ __launch_bounds__(256) void pt_trace_packet_ia(const PtScene sc, cons
                 const uint32_t li = tri_base + (uint32_t)__builtin_popcount(leafmask & ((1u << c) - 1u));
                 const float* __restrict__ tp = reinterpret_cast<const float*>(sc.tris) + (size_t)li * 12u;  // wave-uniform address
                 if (COUNT) n_tris++;
-                // tri_test() with the same operations in the same order, but as straight-line code with lane masks and ONE wave-uniform
-                // way out: its per-lane early returns cost about sixty scalar instructions per triangle in exec-mask bookkeeping
-                const v3 v0 = mk(tp[0], tp[1], tp[2]), e1 = mk(tp[3], tp[4], tp[5]), e2 = mk(tp[6], tp[7], tp[8]);
-                const v3 pvec = cross(d, e2);
-                const float det = dot(e1, pvec);
-                const v3 tvec = o - v0;
-                const float u = dot(tvec, pvec);
-                const v3 qvec = cross(tvec, e1);
-                const float v = dot(d, qvec);
-                const float uv = u + v;
-                // (ballots, combined as 64-bit scalars: boolean expressions come back as branches or through v_cndmask + v_cmp)
-                const unsigned long long m_pos = __builtin_amdgcn_ballot_w64(det > 0.0f), m_nz = __builtin_amdgcn_ballot_w64(det != 0.0f);
-                const unsigned long long out_pos = __builtin_amdgcn_ballot_w64(u < 0.0f) | __builtin_amdgcn_ballot_w64(v < 0.0f) | __builtin_amdgcn_ballot_w64(uv > det);
-                const unsigned long long out_neg = __builtin_amdgcn_ballot_w64(u > 0.0f) | __builtin_amdgcn_ballot_w64(v > 0.0f) | __builtin_amdgcn_ballot_w64(uv < det);
-                const unsigned long long inside = act_mask & m_nz & ((m_pos & ~out_pos) | (~m_pos & ~out_neg));
+                float det;
+                v3 qvec;
+                const unsigned long long inside = tri_inside_mask(o, d, mk(tp[0], tp[1], tp[2]), mk(tp[3], tp[4], tp[5]), mk(tp[6], tp[7], tp[8]), act_mask, det, qvec);
                 if (inside == 0ull) continue;
-                const float t = dot(e2, qvec) / det;
+                const float t = dot(mk(tp[6], tp[7], tp[8]), qvec) / det;
                 const uint32_t id = __float_as_uint(tp[9]);
                 const unsigned long long closer = __builtin_amdgcn_ballot_w64(t < best.t) | (__builtin_amdgcn_ballot_w64(t == best.t) & __builtin_amdgcn_ballot_w64(id < best.id));
                 const unsigned long long take = inside & __builtin_amdgcn_ballot_w64(t > 0.0f) & closer;
@@ -1616,7 +1563,7 @@ __global__ __launch_bounds__(256) void pt_trace_packet_ia(const PtScene sc, cons
                 best.id = mine ? id : best.id;
             }
             if (FARCAP && improved != 0ull) {
-                const float maxbest = wave_max_nonneg(act ? best.t : 0.0f);
+                const float maxbest = wave_reduce_nonneg<true>(act ? best.t : 0.0f);
                 if (pk == 7u) ia_m = maxbest;
             }
             gx = child_base;
@@ -1630,13 +1577,7 @@ __global__ __launch_bounds__(256) void pt_trace_packet_ia(const PtScene sc, cons
         }
         if (sp_max > 63u) overflow = 1;
     }
-    if (alive) st.hit[pid] = make_float2(best.t, __int_as_float(best.li));
-    if (COUNT && lane == 0) {  // records fetched once per wave
-        atomicAdd(&stats[9], (unsigned long long)n_nodes);
-        atomicAdd(&stats[10], (unsigned long long)n_tris);
-        atomicAdd(&stats[8], 1ull);
-    }
-    if (overflow && lane == 0) atomicOr((unsigned int*)&stats[2], 1u);
+    packet_finish<COUNT>(st, stats, pid, lane, alive, best, n_nodes, n_tris, overflow);
 }
 
 // ---- shade ----------------------------------------------------------------------------------------
@@ -1814,12 +1755,12 @@ __device__ __forceinline__ void trace_one_ray(const PtScene& sc, const float* __
     const v3 o = mk(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]), d = mk(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]);
     if (any_hit) {
         Hit h{kShadowTmax, -1, 0u};
-        const bool occ = traverse<true, COUNT>(sc.nodes, sc.tris, perm_lut, o, d, stk, h, tc);
+        const bool occ = traverse<true, COUNT>(sc, perm_lut, o, d, stk, h, tc);
         t_out[i] = occ ? 1.0f : 0.0f;
         tri_out[i] = occ ? 1 : 0;
     } else {
         Hit h{__builtin_inff(), -1, 0xffffffffu};
-        traverse<false, COUNT>(sc.nodes, sc.tris, perm_lut, o, d, stk, h, tc);
+        traverse<false, COUNT>(sc, perm_lut, o, d, stk, h, tc);
         t_out[i] = h.t;
         tri_out[i] = h.li < 0 ? -1 : (int)h.id;
     }
@@ -1835,9 +1776,8 @@ __global__ __launch_bounds__(256) void pt_trace_rays(const PtScene sc, const flo
     __shared__ uint8_t perm_lut[2048];
     build_perm_lut(perm_lut);
     // grid-stride so the spill columns (one per launched thread) stay within sk.spill_stride
-    const size_t gtid = (size_t)blockIdx.x * 256u + threadIdx.x;
-    TravStack stk{(lds_u64*)&lds_stack[threadIdx.x], sk.spill + gtid, sk.spill_stride, sk.lds_cap, sk.spill_cap, 0};
-    for (uint32_t i = (uint32_t)gtid; i < n; i += gridDim.x * 256u) {
+    TravStack stk = make_trav_stack(lds_stack, sk);
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         TravCounters tc{0, 0, 0};
         trace_one_ray<COUNT>(sc, origins, dirs, i, any_hit, t_out, tri_out, stk, perm_lut, tc);
         if (COUNT) {
@@ -1865,31 +1805,35 @@ int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* qu
     return RT_OK;
 }
 
+// Call f with v as a compile-time constant (std::integral_constant): the launchers' way from run-time switches to template arguments.
+template <class F>
+static void with_bool(bool v, F&& f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+static void with_tri_mode(uint32_t tri_mode, F&& f) {
+    if (tri_mode == TRI_POOL) f(std::integral_constant<int, TRI_POOL>{});
+    else if (tri_mode == TRI_DEFER) f(std::integral_constant<int, TRI_DEFER>{});
+    else if (tri_mode == TRI_INLINE_PF) f(std::integral_constant<int, TRI_INLINE_PF>{});
+    else f(std::integral_constant<int, TRI_INLINE>{});
+}
+
+static bool valid_stack_cfg(const StackCfg& sk, uint32_t grid) { return sk.lds_cap >= 1 && sk.lds_cap <= 160 && (size_t)grid * 256u <= sk.spill_stride; }
+static size_t stack_lds_bytes(const StackCfg& sk) { return (size_t)sk.lds_cap * 256 * sizeof(unsigned long long); }
+
 int launch_pt_trace(Ctx* c, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,
                     uint32_t tri_cfg) {
-    if (stack_cap.lds_cap < 1 || stack_cap.lds_cap > 160 || (size_t)grid * 256u > stack_cap.spill_stride)
-        return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
-    const dim3 g(grid), b(256);
-    const size_t lds = (size_t)stack_cap.lds_cap * 256 * sizeof(unsigned long long);
-#define RT_LAUNCH_TRACE(ANY, COUNT, MODE) \
-    hipLaunchKernelGGL((pt_trace<ANY, COUNT, MODE>), g, b, lds, c->stream, sc, st, queue, count_ptr, head, stats, stack_cap, refill_min, tri_cfg)
-#define RT_LAUNCH_TRACE_MODE(ANY, COUNT)                         \
-    do {                                                         \
-        if (tri_mode == TRI_POOL) RT_LAUNCH_TRACE(ANY, COUNT, TRI_POOL); \
-        else if (tri_mode == TRI_DEFER) RT_LAUNCH_TRACE(ANY, COUNT, TRI_DEFER); \
-        else if (tri_mode == TRI_INLINE_PF) RT_LAUNCH_TRACE(ANY, COUNT, TRI_INLINE_PF); \
-        else RT_LAUNCH_TRACE(ANY, COUNT, TRI_INLINE);            \
-    } while (0)
-    if (any_hit) {
-        if (count) RT_LAUNCH_TRACE_MODE(true, true);
-        else RT_LAUNCH_TRACE_MODE(true, false);
-    } else {
-        if (count) RT_LAUNCH_TRACE_MODE(false, true);
-        else RT_LAUNCH_TRACE_MODE(false, false);
-    }
-#undef RT_LAUNCH_TRACE_MODE
-#undef RT_LAUNCH_TRACE
+    if (!valid_stack_cfg(stack_cap, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
+    with_bool(any_hit, [&](auto any) {
+        with_bool(count, [&](auto cnt) {
+            with_tri_mode(tri_mode, [&](auto mode) {
+                hipLaunchKernelGGL((pt_trace<decltype(any)::value, decltype(cnt)::value, decltype(mode)::value>), dim3(grid), dim3(256), stack_lds_bytes(stack_cap),
+                                   c->stream, sc, st, queue, count_ptr, head, stats, stack_cap, refill_min, tri_cfg);
+            });
+        });
+    });
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -1897,26 +1841,13 @@ int launch_pt_trace(Ctx* c, const PtScene& sc, const PtState& st, const uint32_t
 int launch_pt_trace_fused(Ctx* c, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* closest_count, uint32_t* closest_head,
                           const uint32_t* shadow_count, uint32_t* shadow_head, unsigned long long* stats, bool count, uint32_t grid,
                           const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode, uint32_t tri_cfg) {
-    if (stack_cap.lds_cap < 1 || stack_cap.lds_cap > 160 || (size_t)grid * 256u > stack_cap.spill_stride)
-        return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
-    const size_t lds = (size_t)stack_cap.lds_cap * 256 * sizeof(unsigned long long);
-#define RT_LAUNCH_FUSED(COUNT, MODE)                                                                                                                  \
-    hipLaunchKernelGGL((pt_trace_fused<COUNT, MODE>), dim3(grid), dim3(256), lds, c->stream, sc, st, queue, closest_count, closest_head, shadow_count, \
-                       shadow_head, stats, stack_cap, refill_min, tri_cfg)
-    if (tri_mode == TRI_POOL) {
-        if (count) RT_LAUNCH_FUSED(true, TRI_POOL);
-        else RT_LAUNCH_FUSED(false, TRI_POOL);
-    } else if (tri_mode == TRI_DEFER) {
-        if (count) RT_LAUNCH_FUSED(true, TRI_DEFER);
-        else RT_LAUNCH_FUSED(false, TRI_DEFER);
-    } else if (tri_mode == TRI_INLINE_PF) {
-        if (count) RT_LAUNCH_FUSED(true, TRI_INLINE_PF);
-        else RT_LAUNCH_FUSED(false, TRI_INLINE_PF);
-    } else {
-        if (count) RT_LAUNCH_FUSED(true, TRI_INLINE);
-        else RT_LAUNCH_FUSED(false, TRI_INLINE);
-    }
-#undef RT_LAUNCH_FUSED
+    if (!valid_stack_cfg(stack_cap, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
+    with_bool(count, [&](auto cnt) {
+        with_tri_mode(tri_mode, [&](auto mode) {
+            hipLaunchKernelGGL((pt_trace_fused<decltype(cnt)::value, decltype(mode)::value>), dim3(grid), dim3(256), stack_lds_bytes(stack_cap), c->stream, sc, st, queue,
+                               closest_count, closest_head, shadow_count, shadow_head, stats, stack_cap, refill_min, tri_cfg);
+        });
+    });
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -1970,10 +1901,11 @@ int launch_pt_resolve(Ctx* c, const PtFrame& f, const PtState& st, float* acc, f
 
 int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const float* dirs, uint32_t n, int any_hit, float* t_out, int* tri_out,
                          uint32_t* counts, const StackCfg& sk, uint32_t grid) {
-    if ((size_t)grid * 256u > sk.spill_stride) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
-    const size_t lds = (size_t)sk.lds_cap * 256 * sizeof(unsigned long long);
-    if (counts) hipLaunchKernelGGL(pt_trace_rays<true>, dim3(grid), dim3(256), lds, c->stream, sc, origins, dirs, n, any_hit, t_out, tri_out, counts, sk);
-    else hipLaunchKernelGGL(pt_trace_rays<false>, dim3(grid), dim3(256), lds, c->stream, sc, origins, dirs, n, any_hit, t_out, tri_out, counts, sk);
+    if (!valid_stack_cfg(sk, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
+    with_bool(counts != nullptr, [&](auto cnt) {
+        hipLaunchKernelGGL(pt_trace_rays<decltype(cnt)::value>, dim3(grid), dim3(256), stack_lds_bytes(sk), c->stream, sc, origins, dirs, n, any_hit, t_out, tri_out,
+                           counts, sk);
+    });
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
