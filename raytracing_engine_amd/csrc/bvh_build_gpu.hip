@@ -793,14 +793,6 @@ int read_back(Ctx* c, T* host, const T* dev, size_t count) {
     return RT_OK;
 }
 
-struct Owned {  // device allocations of one build; freed unless released to the caller
-    void* p[6] = {};
-    ~Owned() {
-        for (void* q : p)
-            if (q) (void)hipFree(q);
-    }
-};
-
 struct Events {
     hipEvent_t e[2] = {nullptr, nullptr};
     ~Events() {
@@ -809,16 +801,13 @@ struct Events {
     }
 };
 
-int build(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out, Owned& own, Events& ev) {
+int build(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out, DevPtr<char>& scratch, Events& ev) {
     const size_t m = std::max<uint32_t>(n - 1u, 1u);
     Bump sizing;
     Scratch s{};
     carve(sizing, s, n);
-    if (hipMalloc(&own.p[0], sizing.used) != hipSuccess) {
-        (void)hipGetLastError();
-        return c->fail(RT_ERR_OOM, "device BVH build: %zu bytes of scratch for %u triangles", sizing.used, n);
-    }
-    Bump bump{static_cast<char*>(own.p[0]), 0};
+    if (!dalloc(scratch, sizing.used)) return c->fail(RT_ERR_OOM, "device BVH build: %zu bytes of scratch for %u triangles", sizing.used, n);
+    Bump bump{scratch.get(), 0};
     carve(bump, s, n);
     RT_HIP(c, hipEventCreate(&ev.e[0]));
     RT_HIP(c, hipEventCreate(&ev.e[1]));
@@ -913,18 +902,10 @@ int build(Ctx* c, const float* verts, const float* albedo, const float* emission
     out->stack_need = depth + 1;  // at most one pending sibling group per level (bvh_build.cpp)
 
     // 8. the mesh's own arrays
-    float4 *nodes = nullptr, *tris = nullptr, *alb = nullptr, *emi = nullptr;
-    uint32_t* lights = nullptr;
-    const bool ok = hipMalloc(&own.p[1], (size_t)out->n_nodes * 80) == hipSuccess && hipMalloc(&own.p[2], (size_t)n * 48) == hipSuccess &&
-                    hipMalloc(&own.p[3], (size_t)n * 16) == hipSuccess && hipMalloc(&own.p[4], (size_t)n * 16) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
+    if (!dalloc(out->nodes, (size_t)out->n_nodes * 5) || !dalloc(out->tris, (size_t)n * 3) || !dalloc(out->albedo, n) || !dalloc(out->emission, n))
         return c->fail(RT_ERR_OOM, "mesh of %u triangles", n);
-    }
-    nodes = static_cast<float4*>(own.p[1]);
-    tris = static_cast<float4*>(own.p[2]);
-    alb = static_cast<float4*>(own.p[3]);
-    emi = static_cast<float4*>(own.p[4]);
+    out->cap_nodes = out->n_nodes;
+    float4 *nodes = out->nodes.get(), *tris = out->tris.get(), *alb = out->albedo.get(), *emi = out->emission.get();
     RT_HIP(c, hipMemcpyAsync(nodes, s.nodes, (size_t)out->n_nodes * 80, hipMemcpyDeviceToDevice, c->stream));
     hipLaunchKernelGGL(bvhd_payload, dim3(blocks_for(n)), dim3(kThreads), 0, c->stream, verts, albedo, emission, (const uint32_t*)s.order, n, tris, alb, emi,
                        s.leaf_pos, s.flag);
@@ -932,27 +913,17 @@ int build(Ctx* c, const float* verts, const float* albedo, const float* emission
     if (int rc = scan<uint32_t>(c, s.flag, s.flag_excl, n, reinterpret_cast<uint32_t*>(s.sums), reinterpret_cast<uint32_t*>(s.total))) return rc;
     uint32_t n_lights = 0;
     if (int rc = read_back(c, &n_lights, reinterpret_cast<const uint32_t*>(s.total), 1)) return rc;
-    if (hipMalloc(&own.p[5], (size_t)std::max<uint32_t>(n_lights, 1u) * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return c->fail(RT_ERR_OOM, "light list of %u triangles", n_lights);
-    }
-    lights = static_cast<uint32_t*>(own.p[5]);
+    if (!dalloc(out->lights, std::max<uint32_t>(n_lights, 1u))) return c->fail(RT_ERR_OOM, "light list of %u triangles", n_lights);
     hipLaunchKernelGGL(bvhd_lights, dim3(blocks_for(n)), dim3(kThreads), 0, c->stream, (const uint32_t*)s.flag, (const uint32_t*)s.flag_excl,
-                       (const uint32_t*)s.leaf_pos, n, n_lights, lights);
+                       (const uint32_t*)s.leaf_pos, n, n_lights, out->lights.get());
     BVHD_LAUNCH(c);
     RT_HIP(c, hipEventRecord(ev.e[1], c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     RT_HIP(c, hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
     out->build_ms = ms;
+    out->n_tris = n;
     out->n_lights = n_lights;
-    out->scratch_bytes = sizing.used;
-    out->nodes = nodes;
-    out->tris = tris;
-    out->albedo = alb;
-    out->emission = emi;
-    out->lights = lights;
-    for (int i = 1; i < 6; i++) own.p[i] = nullptr;  // released to the caller; the scratch (p[0]) is freed here
     return RT_OK;
 }
 
@@ -1020,10 +991,13 @@ int refit_write(Ctx* c, const float* verts, uint32_t n, float pad, uint32_t n_no
 }
 
 int build_bvh_device(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out) {
-    Owned own;
+    DevPtr<char> scratch;  // freed here; the mesh's own arrays go to *out
     Events ev;
-    const int rc = build(c, verts, albedo, emission, n, out, own, ev);
-    if (rc != RT_OK) (void)hipStreamSynchronize(c->stream);  // nothing enqueued may still use the scratch when it is freed
+    const int rc = build(c, verts, albedo, emission, n, out, scratch, ev);
+    if (rc != RT_OK) {
+        (void)hipStreamSynchronize(c->stream);  // nothing enqueued may still use the scratch or the arrays when they are freed
+        *out = DeviceMesh{};
+    }
     return rc;
 }
 

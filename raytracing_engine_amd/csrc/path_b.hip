@@ -640,18 +640,6 @@ constexpr int kTrisPerRound = 1;
 //               phase runs when enough lanes hold a group (or enough of them can do nothing else)
 enum { TRI_INLINE = TRI_MODE_INLINE, TRI_POOL = TRI_MODE_POOL, TRI_DEFER = TRI_MODE_DEFER, TRI_INLINE_PF = TRI_MODE_INLINE_PF };
 
-// Words of the device-side statistics block (rt_render_pt reads them back by number)
-enum {
-    PT_STAT_NODES = 0,          // closest-hit rays of the per-lane kernels: node visits, + 1: triangle tests
-    PT_STAT_OVERFLOW = 2,       // != 0: some traversal stack overflowed
-    PT_STAT_SHADOW = 4,         // shadow rays of a launch of their own: node visits, + 1: triangle tests
-    PT_STAT_ROUNDS = 6,         // wave-rounds of the loops that carry closest-hit rays, + 1: alive lane-rounds
-    PT_STAT_PACKETS = 8,        // packet kernels: waves, + 1: node records fetched, + 2: triangle records fetched
-    PT_STAT_FUSED_SHADOW = 11,  // shadow rays inside the fused launch: node visits, + 1: triangle tests
-    PT_STAT_FLUSHES = 13,       // TRI_POOL: pool_test passes, TRI_DEFER: triangle phases
-    PT_STAT_ROUNDS_ALL = 14     // wave-rounds of every per-lane loop
-};
-
 // Retire a finished ray: a closest-hit ray stores (t, triangle) for pt_shade, an unoccluded shadow ray adds its contribution to its path.
 __device__ __forceinline__ void retire_ray(const PtState& st, bool is_any, uint32_t slot, bool occluded, const Hit& best) {
     if (is_any) {
@@ -1822,7 +1810,7 @@ static void with_tri_mode(uint32_t tri_mode, F&& f) {
 static bool valid_stack_cfg(const StackCfg& sk, uint32_t grid) { return sk.lds_cap >= 1 && sk.lds_cap <= 160 && (size_t)grid * 256u <= sk.spill_stride; }
 static size_t stack_lds_bytes(const StackCfg& sk) { return (size_t)sk.lds_cap * 256 * sizeof(unsigned long long); }
 
-int launch_pt_trace(Ctx* c, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
+int launch_pt_trace(Ctx* c, hipStream_t stream, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,
                     uint32_t tri_cfg) {
     if (!valid_stack_cfg(stack_cap, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
@@ -1830,7 +1818,7 @@ int launch_pt_trace(Ctx* c, const PtScene& sc, const PtState& st, const uint32_t
         with_bool(count, [&](auto cnt) {
             with_tri_mode(tri_mode, [&](auto mode) {
                 hipLaunchKernelGGL((pt_trace<decltype(any)::value, decltype(cnt)::value, decltype(mode)::value>), dim3(grid), dim3(256), stack_lds_bytes(stack_cap),
-                                   c->stream, sc, st, queue, count_ptr, head, stats, stack_cap, refill_min, tri_cfg);
+                                   stream, sc, st, queue, count_ptr, head, stats, stack_cap, refill_min, tri_cfg);
             });
         });
     });

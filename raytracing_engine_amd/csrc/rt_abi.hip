@@ -51,11 +51,6 @@ void free_frame(Ctx* c) {
     c->frame_valid = false;
 }
 
-int bind(Ctx* c) {
-    RT_HIP(c, hipSetDevice(c->device));
-    return RT_OK;
-}
-
 void fill_sphere_set(const rt_mutable_data& s, rt::SphereSet* out) {
     for (uint32_t i = 0; i < RT_MAX_OBJECTS; i++)
         out->s[i] = make_float4(s.objs[i].pos[0], s.objs[i].pos[1], s.objs[i].pos[2], s.objs[i].size);
@@ -75,11 +70,6 @@ void fill_shade_set(const rt_mutable_data& s, rt::ShadeSet* out) {
         out->light_color[i] = make_float4(s.lights[i].color[0], s.lights[i].color[1], s.lights[i].color[2], 0.0f);
     }
     out->light_count = s.lightCount;
-}
-
-uint32_t owned_tiles(const rt::Partition& p) {
-    const uint32_t total = p.tiles_x * p.tiles_y;
-    return total > p.rank ? (total - p.rank + p.n_ranks - 1u) / p.n_ranks : 0u;
 }
 
 // spp must be n*n; returns n or 0
@@ -228,7 +218,7 @@ int render_common(Ctx* c, const float rot[4], const float pos[3], uint32_t spp, 
     if (!c->width) return c->fail(RT_ERR_STATE, "rt_resize has not been called");
     const uint32_t n_strata = strata_of(spp);
     if (!n_strata) return c->fail(RT_ERR_INVALID, "spp %u is not a square n*n (n <= 64)", spp);
-    if (int rc = bind(c)) return rc;
+    if (int rc = rt::bind(c)) return rc;
 
     const bool stage_events = c->cfg.profile_stages != 0;
     RT_HIP(c, hipMemsetAsync(c->d_counters, 0, 4 * 1024 * sizeof(uint64_t), c->stream));
@@ -451,7 +441,7 @@ int rt_resize(rt_ctx* ctx, uint32_t width, uint32_t height, const float ratio[2]
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
     if (width == 0 || height == 0 || width > 16384 || height > 16384) return c->fail(RT_ERR_INVALID, "view %ux%u out of range", width, height);
-    if (int rc = bind(c)) return rc;
+    if (int rc = rt::bind(c)) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
     rt::frames_free(c);  // slots are sized for the old view
     free_frame(c);
@@ -509,14 +499,14 @@ int rt_tile_info(const rt_ctx* ctx, uint32_t* tiles_x, uint32_t* tiles_y, uint32
     if (!c || !c->width) return RT_ERR_STATE;
     if (tiles_x) *tiles_x = c->part.tiles_x;
     if (tiles_y) *tiles_y = c->part.tiles_y;
-    if (owned) *owned = owned_tiles(c->part);
+    if (owned) *owned = rt::owned_tiles(c->part);
     return RT_OK;
 }
 
 int rt_set_stream(rt_ctx* ctx, void* hip_stream) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
-    if (int rc = bind(c)) return rc;
+    if (int rc = rt::bind(c)) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
     c->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
     return RT_OK;
@@ -527,7 +517,7 @@ int rt_render_spp(rt_ctx* ctx, const float rot[4], const float pos[3], uint32_t 
     if (!c) return RT_ERR_INVALID;
     if (c->part.n_ranks > 1) {
         // a partitioned context only fills its own tiles; clear the rest so the frame is defined
-        if (int rc = bind(c)) return rc;
+        if (int rc = rt::bind(c)) return rc;
         if (c->d_rgb) RT_HIP(c, hipMemsetAsync(c->d_rgb, 0, (size_t)c->width * c->height * 3 * sizeof(float), c->stream));
     }
     int rc = render_common(c, rot, pos, spp, c->d_rgb, 0, true);
@@ -561,14 +551,14 @@ int rt_detile_device(rt_ctx* ctx, const void* tiles_dev, uint32_t n_ranks, uint3
     if (!tiles_dev || !rgb_dev || n_ranks == 0) return c->fail(RT_ERR_INVALID, "NULL buffer or n_ranks = 0");
     const uint32_t total = c->part.tiles_x * c->part.tiles_y;
     if ((uint64_t)tiles_per_rank * n_ranks < total) return c->fail(RT_ERR_INVALID, "%u ranks x %u tiles < %u tiles", n_ranks, tiles_per_rank, total);
-    if (int rc = bind(c)) return rc;
+    if (int rc = rt::bind(c)) return rc;
     return rt::launch_detile(c, static_cast<const float*>(tiles_dev), n_ranks, tiles_per_rank, static_cast<float*>(rgb_dev));
 }
 
 int rt_synchronize(rt_ctx* ctx) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
-    if (int rc = bind(c)) return rc;
+    if (int rc = rt::bind(c)) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
     if (c->frame_valid && c->ev_end) {
         float ms = 0.0f;
@@ -582,7 +572,7 @@ int rt_read_level(rt_ctx* ctx, uint32_t level, float* out, uint32_t* w, uint32_t
     if (!c) return RT_ERR_INVALID;
     if (!c->frame_valid) return c->fail(RT_ERR_STATE, "no frame rendered yet");
     if (level >= c->level_count) return c->fail(RT_ERR_INVALID, "level %u >= %u", level, c->level_count);
-    if (int rc = bind(c)) return rc;
+    if (int rc = rt::bind(c)) return rc;
     if (w) *w = c->dims[level][0];
     if (h) *h = c->dims[level][1];
     if (out) {
@@ -598,7 +588,7 @@ int rt_read_rgba8(rt_ctx* ctx, uint8_t* rgba_out) {
     if (!c) return RT_ERR_INVALID;
     if (!rgba_out) return c->fail(RT_ERR_INVALID, "rgba_out is NULL");
     if (!c->frame_valid) return c->fail(RT_ERR_STATE, "no frame rendered yet");
-    if (int rc = bind(c)) return rc;
+    if (int rc = rt::bind(c)) return rc;
     const uint64_t n = (uint64_t)c->width * c->height;
     // staging buffer of the view's size, kept until rt_resize / rt_destroy: this call sits in a per-frame loop
     if (!c->d_rgba8 && hipMalloc((void**)&c->d_rgba8, n * 4) != hipSuccess) {
@@ -615,7 +605,7 @@ int rt_selftest_math(rt_ctx* ctx, uint64_t* mismatches) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
     if (!mismatches) return c->fail(RT_ERR_INVALID, "mismatches is NULL");
-    if (int rc = bind(c)) return rc;
+    if (int rc = rt::bind(c)) return rc;
     unsigned long long* d = nullptr;
     if (hipMalloc((void**)&d, sizeof *d) != hipSuccess) return c->fail(RT_ERR_OOM, "self-test counter");
     hipError_t e = hipMemsetAsync(d, 0, sizeof *d, c->stream);

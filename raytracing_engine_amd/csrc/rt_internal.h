@@ -132,6 +132,19 @@ enum {
     PT_CTR_STRIDE = PT_HEAD_STRIDE * (1 + 2 * PT_HEADS)
 };
 
+// Words of the device-side statistics block (PtData::d_stats): the kernels add to them, the frame's read-back names them
+enum {
+    PT_STAT_NODES = 0,          // closest-hit rays of the per-lane kernels: node visits, + 1: triangle tests
+    PT_STAT_OVERFLOW = 2,       // != 0: some traversal stack overflowed
+    PT_STAT_SHADOW = 4,         // shadow rays of a launch of their own: node visits, + 1: triangle tests
+    PT_STAT_ROUNDS = 6,         // wave-rounds of the loops that carry closest-hit rays, + 1: alive lane-rounds
+    PT_STAT_PACKETS = 8,        // packet kernels: waves, + 1: node records fetched, + 2: triangle records fetched
+    PT_STAT_FUSED_SHADOW = 11,  // shadow rays inside the fused launch: node visits, + 1: triangle tests
+    PT_STAT_FLUSHES = 13,       // TRI_POOL: pool_test passes, TRI_DEFER: triangle phases
+    PT_STAT_ROUNDS_ALL = 14,    // wave-rounds of every per-lane loop
+    PT_STAT_WORDS = 16
+};
+
 struct PtScene {
     const float4* nodes;     // 5 x float4 (80 B) per compressed 8-wide BVH node (bvh_build.h layout)
     const float4* tris;      // 3 x float4 per triangle, leaf order: v0.xyz e1.x | e1.yz e2.xy | e2.z id emissive-flag -
@@ -188,36 +201,62 @@ struct MeshHost {  // host side of a two-level mesh: what rt_update_mesh_chunk n
     std::vector<float> surf;                // albedo.w per triangle, original order (rt_set_mesh_surfaces); empty = all Lambert
 };
 
-struct PtData {  // device residency of one mesh + the wavefront buffers
-    std::unique_ptr<MeshHost> host;  // two-level meshes only
-    size_t cap_nodes = 0;            // nodes d_nodes has room for
-    bool borrowed_mesh = false;  // the mesh arrays belong to another context (frame-slot lanes share their parent's mesh)
-    bool has_surfaces = false;   // some triangle is a mirror or glass (albedo.w != 0): frames take pt_shade<true>, DESIGN.md §6.11
-    uint32_t n_tris = 0, n_nodes = 0, n_lights = 0, bvh_depth = 0;
-    float bvh_build_ms = 0.0f, bvh_pad = 0.0f, bvh_maxabs = 1.0f;  // bvh_maxabs = max(1, largest |vertex coordinate|): what the padding covers
-    float4* d_nodes = nullptr;
-    float4* d_tris = nullptr;
-    float4* d_albedo = nullptr;
-    float4* d_emission = nullptr;
-    uint32_t* d_lights = nullptr;
+// Move-only owner of one hipMalloc allocation
+struct HipFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+template <class T>
+using DevPtr = std::unique_ptr<T, HipFree>;
+
+template <class T>
+bool dalloc(DevPtr<T>& p, size_t count) {  // frees what p held first; false: out of device memory, p is empty
+    p.reset();
+    T* raw = nullptr;
+    if (hipMalloc((void**)&raw, count * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    p.reset(raw);
+    return true;
+}
+
+// A mesh resident on the device: the arrays the kernels read and what the host knows about them.  Made by the host build
+// (rt_abi_mesh.hip) or by build_bvh_device, owned by one context (PtData::own), read through a pointer by that context's frame-slot lanes.
+struct DeviceMesh {
+    DevPtr<float4> nodes;     // cap_nodes x 80 B of which n_nodes are used, bvh_build.h layout
+    DevPtr<float4> tris;      // leaf order, 48 B per triangle (PtScene::tris)
+    DevPtr<float4> albedo;    // leaf order
+    DevPtr<float4> emission;  // leaf order
+    DevPtr<uint32_t> lights;  // max(n_lights, 1) entries
+    uint32_t n_tris = 0, n_nodes = 0, n_lights = 0, depth = 0;
     uint32_t stack_need = 0;  // worst-case traversal stack occupancy reported by the builder
+    float pad = 0.0f, maxabs = 1.0f, build_ms = 0.0f;  // maxabs = max(1, largest |vertex coordinate|): what the padding covers
+    size_t cap_nodes = 0;       // nodes the node array has room for
+    bool has_surfaces = false;  // some triangle is a mirror or glass (albedo.w != 0): frames take pt_shade<true>, DESIGN.md §6.11
     // single-level meshes: level d of the breadth-first tree = nodes [level_start[d], level_start[d + 1]) (empty: no refit)
     std::vector<uint32_t> level_start;
-    void* d_refit = nullptr;  // rt_refit_mesh_device scratch (refit_scratch_size), allocated by the first refit, freed with the mesh
+};
+
+struct PtData {  // device residency of one mesh + the wavefront buffers
+    DeviceMesh own;                        // the mesh this context owns (n_tris = 0: none)
+    const DeviceMesh* borrowed = nullptr;  // frame-slot lanes: the parent's mesh, which the parent takes back (frames_drop_mesh) before it frees or replaces it
+    const DeviceMesh& mesh() const { return borrowed ? *borrowed : own; }  // what frames render
+    std::unique_ptr<MeshHost> host;  // two-level meshes only
+    DevPtr<char> d_refit;  // rt_refit_mesh_device scratch (refit_scratch_size), allocated by the first refit, freed with the mesh
     hipEvent_t ev_refit[2] = {nullptr, nullptr};
-    unsigned long long* d_spill = nullptr;
+    DevPtr<unsigned long long> d_spill;
     size_t spill_words = 0, spill_half = 0;
     hipEvent_t ev_shaded = nullptr, ev_shadowed = nullptr;  // ordering between the main and the auxiliary stream
     std::vector<hipEvent_t> ev_pool;  // profile_stages: timing events, created on this context's device, freed by pt_free
-    // wavefront buffers, sized for cap_paths
+    // wavefront buffers, sized for cap_paths; st, d_queue and d_acc point into the allocations `wavefront` owns
     uint64_t cap_paths = 0;
-    uint32_t cap_depth = 0;
+    DevPtr<char> wavefront[11];
     PtState st{};
     uint32_t* d_queue[2] = {nullptr, nullptr};
-    uint32_t* d_ctr = nullptr;
-    unsigned long long* d_stats = nullptr;
     float* d_acc = nullptr;  // per-slot running sums across sample batches
     uint64_t cap_slots = 0;
+    DevPtr<uint32_t> d_ctr;
+    DevPtr<unsigned long long> d_stats;  // PT_STAT_WORDS words
     rt_pt_stats stats{};
 };
 
@@ -272,9 +311,20 @@ struct Ctx {
         if (e_ != hipSuccess) return (ctx)->fail(RT_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
+inline int bind(Ctx* c) {
+    RT_HIP(c, hipSetDevice(c->device));
+    return RT_OK;
+}
+
+inline uint32_t owned_tiles(const Partition& p) {
+    const uint32_t total = p.tiles_x * p.tiles_y;
+    return total > p.rank ? (total - p.rank + p.n_ranks - 1u) / p.n_ranks : 0u;
+}
+
 void frames_free(Ctx* c);          // rt_abi_frames.hip: waits for frames in flight, releases every slot
-void frames_drop_mesh(Ctx* c);     // rt_abi_frames.hip: the parent's mesh is about to be freed: idle the lanes, forget the borrowed arrays
-void pt_borrow_mesh(Ctx* lane, const Ctx* owner);  // rt_abi_pt.hip: lane renders with owner's device mesh
+void frames_drop_mesh(Ctx* c);     // rt_abi_frames.hip: the parent's mesh is about to be freed: idle the lanes, forget the borrowed mesh
+void pt_borrow_mesh(Ctx* lane, const Ctx* owner);  // rt_abi_mesh.hip: lane renders with owner's device mesh
+void pt_free_mesh(PtData& pt);     // rt_abi_mesh.hip: the mesh (owned or borrowed) and everything sized for it
 
 // path_a.hip
 int launch_cone_level(Ctx* c, const SphereSet& spheres, uint32_t n_obj, const ConeLevelParams& p, const float* parent,
@@ -288,9 +338,9 @@ int launch_to_rgba8(Ctx* c, const float* rgb, uint8_t* rgba, uint64_t n_pixels);
 
 // path_b.hip
 int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* queue, uint32_t* ctr);
-int launch_pt_trace(Ctx* c, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
+int launch_pt_trace(Ctx* c, hipStream_t stream, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,
-                    uint32_t tri_cfg);
+                    uint32_t tri_cfg);  // on `stream` (c->stream or c->aux_stream)
 int launch_pt_trace_fused(Ctx* c, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* closest_count, uint32_t* closest_head,
                           const uint32_t* shadow_count, uint32_t* shadow_head, unsigned long long* stats, bool count, uint32_t grid,
                           const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode, uint32_t tri_cfg);
@@ -306,19 +356,8 @@ int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const 
 void pt_free(Ctx* c);
 void comm_free(Ctx* c);  // rt_abi_comm.hip
 
-// bvh_build_gpu.hip: path B mesh arrays built on the GPU from device-resident triangles (rt_set_mesh_device), on c->stream.
-// On success the five arrays belong to the caller; on failure nothing is allocated and nothing else has changed.
-struct DeviceMesh {
-    float4* nodes = nullptr;     // n_nodes x 80 B, bvh_build.h layout
-    float4* tris = nullptr;      // leaf order, 48 B per triangle (PtScene::tris)
-    float4* albedo = nullptr;    // leaf order
-    float4* emission = nullptr;  // leaf order
-    uint32_t* lights = nullptr;  // max(n_lights, 1) entries
-    uint32_t n_nodes = 0, n_lights = 0, depth = 0, stack_need = 0;
-    float pad = 0.0f, maxabs = 1.0f, build_ms = 0.0f;
-    size_t scratch_bytes = 0;  // peak temporary device memory of the build
-    std::vector<uint32_t> level_start;  // PtData::level_start of the tree
-};
+// bvh_build_gpu.hip: path B mesh built on the GPU from device-resident triangles (rt_set_mesh_device), on c->stream.
+// On failure *out is empty and nothing else has changed.
 int build_bvh_device(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out);
 
 // bvh_build_gpu.hip: refit of a single-level mesh to new vertices (rt_refit_mesh_device), on c->stream, in two steps.

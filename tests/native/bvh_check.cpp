@@ -19,7 +19,7 @@ static uint32_t hash32(uint32_t x) {
     return x;
 }
 
-// A mesh file as rt_set_mesh takes it: edges are formed as rt_abi_pt.hip forms them (v1 - v0, v2 - v0 in float).
+// A mesh file as rt_set_mesh takes it: edges are formed as rt_abi_mesh.hip forms them (v1 - v0, v2 - v0 in float).
 static bool load_mesh(const char* path, std::vector<float>& v0, std::vector<float>& e1, std::vector<float>& e2) {
     FILE* f = std::fopen(path, "rb");
     if (!f) return false;

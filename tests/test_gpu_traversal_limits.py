@@ -36,7 +36,7 @@ def check_frame_against(r, k, w, h, **knobs):
 
 
 def levels_of(nodes):
-    """Node counts of the breadth-first levels of a tree read back by Renderer.read_bvh() (rt_abi_pt.hip: level_starts)."""
+    """Node counts of the breadth-first levels of a tree read back by Renderer.read_bvh() (rt_abi_mesh.hip: level_starts)."""
     n_in = np.array([bin(int(w) >> 24).count("1") for w in nodes[:, 3]])
     sizes, first, count = [], 0, 1
     while count:
