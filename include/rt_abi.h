@@ -359,6 +359,15 @@ int rt_refit_mesh_device(rt_ctx* ctx, const void* verts_dev, uint32_t n_tris);
 #define RT_SURFACE_MIRROR 1u
 #define RT_SURFACE_GLASS 2u
 int rt_set_mesh_surfaces(rt_ctx* ctx, const uint32_t* kind, const float* ior, uint32_t n_tris);
+/* Contexts of one process that are given the same host mesh on the same device (rt_set_mesh / rt_set_mesh_ex: every byte of the three
+ * arrays, the triangle count and the build options equal) render one resident copy of it: the first builds and uploads, the others take
+ * the copy that is there, and it is freed with the last of them.  A context that changes its mesh (rt_refit_mesh_device,
+ * rt_update_mesh_chunk, rt_set_mesh_surfaces) continues with a copy of its own if others render the mesh too, so no context ever sees
+ * another's change; when that copy cannot be allocated the call returns RT_ERR_OOM and nothing has changed.  rt_pt_stats' build times
+ * are those of the build that made the copy.  Meshes from rt_set_mesh_device are never shared.  RT_AMD_MESH_SHARING=0 in the
+ * environment, read by each rt_set_mesh*, makes that call build and upload for itself.
+ * Returns the number of contexts that render this context's device mesh: 0 = no mesh, 1 = only this one; RT_ERR_INVALID for NULL. */
+int rt_mesh_sharers(rt_ctx* ctx);
 /* Test hook: node words (n_nodes x 20 u32, bvh_build.h layout) and leaf order (leaf position -> original triangle index,
  * n_tris u32) of the current mesh, host- or device-built.  NULL outputs: only *n_nodes is written (capacity query);
  * a non-NULL output whose capacity is too small: RT_ERR_INVALID.  No mesh: RT_ERR_STATE. */

@@ -133,6 +133,7 @@ PROTOTYPES = {
     "rt_set_mesh_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32]),
     "rt_refit_mesh_device": (C.c_int, [_vp, _vp, C.c_uint32]),
     "rt_set_mesh_surfaces": (C.c_int, [_vp, _u32p, _fp, C.c_uint32]),
+    "rt_mesh_sharers": (C.c_int, [_vp]),
     "rt_read_bvh": (C.c_int, [_vp, _u32p, C.c_uint32, _u32p, C.c_uint32, _u32p]),
     "rt_render_pt": (C.c_int, [_vp, _fp, _fp, C.POINTER(PtParams), _fp]),
     "rt_render_pt_device": (C.c_int, [_vp, _fp, _fp, C.POINTER(PtParams), _vp, C.c_int]),

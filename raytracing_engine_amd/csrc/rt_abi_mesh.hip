@@ -1,9 +1,11 @@
 // rt_abi_mesh.hip — lifetime of path B's device mesh behind the C ABI: set (host and device build), chunk rebuild, refit,
-// surfaces, read-back, and the borrowing of a parent's mesh by its frame-slot lanes.  No reference counterpart
+// surfaces, read-back, the sharing of one resident mesh among the contexts that were given it, and the borrowing
+// of a parent's mesh by its frame-slot lanes.  No reference counterpart
 // (include/rt_abi.h, "Path B").  The frames that render the mesh are in rt_abi_pt.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <stdexcept>
@@ -11,6 +13,7 @@
 #include <vector>
 
 #include "bvh_build.h"
+#include "mesh_registry.h"
 #include "rt_internal.h"
 
 using rt::Ctx;
@@ -19,8 +22,8 @@ using rt::PtData;
 
 namespace rt {
 void pt_free_mesh(PtData& pt) {
-    pt.borrowed = nullptr;  // another context owns those arrays
-    pt.own = DeviceMesh{};
+    pt.borrowed = nullptr;  // the parent context holds those arrays
+    pt.own.reset();         // the arrays go with their last holder
     pt.d_spill.reset();
     pt.spill_words = 0;
     pt.d_refit.reset();
@@ -28,7 +31,6 @@ void pt_free_mesh(PtData& pt) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
     }
-    pt.host.reset();
     pt.stats = rt_pt_stats{};
 }
 }  // namespace rt
@@ -40,7 +42,7 @@ using rt::pt_free_mesh;
 // The mesh part of rt_pt_stats, from the record (and the host side of a two-level mesh) the context renders
 void publish_mesh_stats(PtData& pt) {
     const DeviceMesh& m = pt.mesh();
-    const rt::TwoLevelBvh* tl = pt.host ? &pt.host->tl : nullptr;
+    const rt::TwoLevelBvh* tl = pt.host() ? &pt.host()->tl : nullptr;
     rt_pt_stats& s = pt.stats;
     s.n_tris = m.n_tris;
     s.n_nodes = m.n_nodes;
@@ -116,21 +118,82 @@ int retire_mesh(Ctx* c) {
     RT_HIP(c, hipStreamSynchronize(c->stream));
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
     rt::frames_drop_mesh(c);  // frame-slot lanes render with this mesh
-    pt_free_mesh(c->pt);      // also pt.host
+    pt_free_mesh(c->pt);
     c->state_version++;
     return RT_OK;
 }
 
-// A finished mesh of either builder becomes the context's mesh, after retire_mesh (host: two-level meshes only)
-void adopt_mesh(Ctx* c, DeviceMesh&& m, std::unique_ptr<rt::MeshHost> host) {
+// A finished mesh of either builder, or one that other contexts render already, becomes the context's mesh, after retire_mesh
+void adopt_mesh(Ctx* c, std::shared_ptr<DeviceMesh> m) {
     c->pt.own = std::move(m);
-    c->pt.host = std::move(host);
     publish_mesh_stats(c->pt);
 }
 
-// The host build: BVH (one or two levels), leaf-order records, upload, light list.  *host: what a chunk rebuild needs (two levels only)
-int build_mesh_host(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n_tris, uint32_t levels, uint32_t chunks, DeviceMesh* m,
-                    std::unique_ptr<rt::MeshHost>* host) {
+// ---- one resident mesh for the contexts that were given the same one --------------------------------------
+// Host-built meshes only.  A listed mesh is complete (its uploads were waited for before it was listed) and nobody writes into it:
+// a context that is about to passes detach_mesh first.
+rt::WeakRegistry<DeviceMesh>& resident_meshes() {
+    static auto* r = new rt::WeakRegistry<DeviceMesh>;  // never destroyed: contexts may be closed while the process exits
+    return *r;
+}
+
+bool sharing_enabled() {  // RT_AMD_MESH_SHARING=0: every rt_set_mesh builds and uploads for itself
+    const char* e = std::getenv("RT_AMD_MESH_SHARING");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+
+uint32_t builder_constants() {
+    uint32_t cost;
+    const float cost_prim = rt::BvhResult{}.cost_prim;
+    std::memcpy(&cost, &cost_prim, 4);
+    return cost ^ rt::kBvhMaxDepth;
+}
+
+// A copy of `src` in device memory of its own, complete on return
+int clone_mesh(Ctx* c, const DeviceMesh& src, DeviceMesh* m) {
+    const size_t n = src.n_tris, n_lights = std::max<size_t>(src.n_lights, 1);
+    if (!dalloc(m->nodes, src.cap_nodes * 5) || !dalloc(m->tris, n * 3) || !dalloc(m->albedo, n) || !dalloc(m->emission, n) || !dalloc(m->lights, n_lights))
+        return c->fail(RT_ERR_OOM, "copy of a shared mesh of %u triangles (the mesh is unchanged)", src.n_tris);
+    RT_HIP(c, hipMemcpy(m->nodes.get(), src.nodes.get(), (size_t)src.n_nodes * 80, hipMemcpyDeviceToDevice));
+    RT_HIP(c, hipMemcpy(m->tris.get(), src.tris.get(), n * 48, hipMemcpyDeviceToDevice));
+    RT_HIP(c, hipMemcpy(m->albedo.get(), src.albedo.get(), n * 16, hipMemcpyDeviceToDevice));
+    RT_HIP(c, hipMemcpy(m->emission.get(), src.emission.get(), n * 16, hipMemcpyDeviceToDevice));
+    RT_HIP(c, hipMemcpy(m->lights.get(), src.lights.get(), n_lights * 4, hipMemcpyDeviceToDevice));
+    RT_HIP(c, hipDeviceSynchronize());  // null-stream copies before anything on the context's non-blocking streams
+    m->n_tris = src.n_tris;
+    m->n_nodes = src.n_nodes;
+    m->n_lights = src.n_lights;
+    m->depth = src.depth;
+    m->stack_need = src.stack_need;
+    m->pad = src.pad;
+    m->maxabs = src.maxabs;
+    m->build_ms = src.build_ms;
+    m->cap_nodes = src.cap_nodes;
+    m->has_surfaces = src.has_surfaces;
+    m->level_start = src.level_start;
+    if (src.host) m->host.reset(new rt::MeshHost(*src.host));
+    return RT_OK;
+}
+
+// Copy on write: every entry point that writes into the context's mesh calls this first, after its last refusal.  On return the
+// context is the mesh's only holder and the mesh is not listed, so no other context sees what is written: a mesh others render
+// too is left to them (and stays listed) and the context goes on with a copy.  A failure leaves everything as it was.
+int detach_mesh(Ctx* c) {
+    PtData& pt = c->pt;
+    if (!resident_meshes().shared_or_unlist(pt.own)) return RT_OK;
+    auto copy = std::make_shared<DeviceMesh>();
+    if (int rc = clone_mesh(c, *pt.own, copy.get())) return rc;
+    // the context's own frames may still read the arrays it lets go of, which the other holders may free at any time
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    rt::frames_drop_mesh(c);
+    pt.own = std::move(copy);
+    return RT_OK;
+}
+
+// The host build: BVH (one or two levels), leaf-order records, upload, light list.  m->host: what a chunk rebuild needs (two levels only)
+int build_mesh_host(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n_tris, uint32_t levels, uint32_t chunks, DeviceMesh* m) {
+    std::unique_ptr<rt::MeshHost>* host = &m->host;
     const size_t n = n_tris;
     // spec section 6.1: edges are formed once, in fp32
     std::vector<float> v0(3 * n), e1(3 * n), e2(3 * n);
@@ -201,21 +264,29 @@ int set_mesh_impl(Ctx* c, const float* verts, const float* albedo, const float* 
     if (int rc = rt::bind(c)) return rc;
     // the old mesh goes before the new one is built (peak device memory stays one mesh): a failure from here on leaves the context without a mesh
     if (int rc = retire_mesh(c)) return rc;
-    DeviceMesh m;
-    std::unique_ptr<rt::MeshHost> host;
-    if (int rc = build_mesh_host(c, verts, albedo, emission, n_tris, levels, chunks, &m, &host)) return rc;
-    adopt_mesh(c, std::move(m), std::move(host));
+    const bool share = sharing_enabled();
+    rt::MeshKey key;
+    if (share) {
+        key = rt::mesh_key(c->device, verts, albedo, emission, n_tris, levels, chunks, builder_constants());
+        if (std::shared_ptr<DeviceMesh> resident = resident_meshes().find(key)) {  // another context renders this very mesh: no build, no upload
+            adopt_mesh(c, std::move(resident));
+            return RT_OK;
+        }
+    }
+    auto m = std::make_shared<DeviceMesh>();
+    if (int rc = build_mesh_host(c, verts, albedo, emission, n_tris, levels, chunks, m.get())) return rc;
+    if (share) resident_meshes().insert(key, m);  // complete: build_mesh_host waited for its uploads
+    adopt_mesh(c, std::move(m));
     return RT_OK;
 }
 
 int update_chunk_impl(Ctx* c, uint32_t chunk, const float* verts, uint32_t n_tris) {
     PtData& pt = c->pt;
-    if (!pt.host || pt.borrowed) return c->fail(RT_ERR_STATE, "rt_update_mesh_chunk needs a two-level mesh (rt_set_mesh_ex with bvh_levels = 2) owned by this context");
-    rt::MeshHost& h = *pt.host;
-    DeviceMesh& m = pt.own;
-    if (chunk >= h.tl.blas.size()) return c->fail(RT_ERR_INVALID, "chunk %u of %zu", chunk, h.tl.blas.size());
+    if (!pt.host()) return c->fail(RT_ERR_STATE, "rt_update_mesh_chunk needs a two-level mesh (rt_set_mesh_ex with bvh_levels = 2) owned by this context");
+    const rt::TwoLevelBvh& tl = pt.host()->tl;
+    if (chunk >= tl.blas.size()) return c->fail(RT_ERR_INVALID, "chunk %u of %zu", chunk, tl.blas.size());
     if (!verts) return c->fail(RT_ERR_INVALID, "verts is NULL");
-    const uint32_t first = h.tl.first[chunk], count = h.tl.first[chunk + 1] - first;
+    const uint32_t first = tl.first[chunk], count = tl.first[chunk + 1] - first;
     if (n_tris != count) return c->fail(RT_ERR_INVALID, "chunk %u holds %u triangles, verts holds %u (rt_mesh_chunk_info)", chunk, count, n_tris);
     for (size_t i = 0; i < (size_t)count * 9; i++)
         if (!std::isfinite(verts[i])) return c->fail(RT_ERR_INVALID, "vertex data is not finite at float %zu", i);
@@ -224,6 +295,9 @@ int update_chunk_impl(Ctx* c, uint32_t chunk, const float* verts, uint32_t n_tri
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
     rt::frames_drop_mesh(c);  // lanes re-borrow the mesh on their next submit
     c->state_version++;
+    if (int rc = detach_mesh(c)) return rc;  // from here on `tl` may be another context's
+    rt::MeshHost& h = *pt.host();
+    DeviceMesh& m = *pt.own;
     const auto t0 = std::chrono::steady_clock::now();
     // Transactional: the host copy and the chunk's bottom-level structure change first and are put back if anything up to
     // the device allocation fails; the device arrays are written only after everything host-side (and the node array's
@@ -347,25 +421,24 @@ int set_mesh_device_impl(Ctx* c, const void* verts, const void* albedo, const vo
     if (int rc = check_device_array(c, albedo, (size_t)n_tris * 12, "albedo")) return rc;
     if (int rc = check_device_array(c, emission, (size_t)n_tris * 12, "emission")) return rc;
     // the new mesh is complete before the old one is dropped: any failure up to here leaves the context as it was
-    DeviceMesh m;
-    if (int rc = rt::build_bvh_device(c, static_cast<const float*>(verts), static_cast<const float*>(albedo), static_cast<const float*>(emission), n_tris, &m))
+    auto m = std::make_shared<DeviceMesh>();  // never listed: device-resident inputs are not compared
+    if (int rc = rt::build_bvh_device(c, static_cast<const float*>(verts), static_cast<const float*>(albedo), static_cast<const float*>(emission), n_tris, m.get()))
         return rc;
     if (int rc = retire_mesh(c)) return rc;
-    adopt_mesh(c, std::move(m), nullptr);  // a device-built mesh is single-level
+    adopt_mesh(c, std::move(m));  // a device-built mesh is single-level
     return RT_OK;
 }
 
 int refit_mesh_device_impl(Ctx* c, const void* verts, uint32_t n_tris) {
     PtData& pt = c->pt;
-    DeviceMesh& m = pt.own;
     if (!pt.mesh().n_tris) return c->fail(RT_ERR_STATE, "no mesh has been set");
-    if (pt.host) return c->fail(RT_ERR_STATE, "rt_refit_mesh_device needs a single-level mesh (a two-level mesh updates with rt_update_mesh_chunk)");
-    if (pt.borrowed || m.level_start.size() < 2) return c->fail(RT_ERR_STATE, "rt_refit_mesh_device: the mesh is not refittable by this context");
-    if (n_tris != m.n_tris) return c->fail(RT_ERR_INVALID, "the mesh holds %u triangles, n_tris is %u", m.n_tris, n_tris);
+    if (pt.host()) return c->fail(RT_ERR_STATE, "rt_refit_mesh_device needs a single-level mesh (a two-level mesh updates with rt_update_mesh_chunk)");
+    if (!pt.own || pt.own->level_start.size() < 2) return c->fail(RT_ERR_STATE, "rt_refit_mesh_device: the mesh is not refittable by this context");
+    if (n_tris != pt.own->n_tris) return c->fail(RT_ERR_INVALID, "the mesh holds %u triangles, n_tris is %u", pt.own->n_tris, n_tris);
     if (int rc = rt::bind(c)) return rc;
     if (int rc = check_device_array(c, verts, (size_t)n_tris * 36, "verts")) return rc;
     if (!pt.d_refit) {  // first refit of this mesh: scratch and timing events stay until the mesh is freed
-        if (!dalloc(pt.d_refit, rt::refit_scratch_size(m.n_nodes))) return c->fail(RT_ERR_OOM, "refit scratch for %u nodes", m.n_nodes);
+        if (!dalloc(pt.d_refit, rt::refit_scratch_size(pt.own->n_nodes))) return c->fail(RT_ERR_OOM, "refit scratch for %u nodes", pt.own->n_nodes);
         for (hipEvent_t& e : pt.ev_refit)
             if (!e) RT_HIP(c, hipEventCreate(&e));
     }
@@ -374,6 +447,8 @@ int refit_mesh_device_impl(Ctx* c, const void* verts, uint32_t n_tris) {
     float maxabs = 0.0f;
     if (int rc = rt::refit_measure(c, v, n_tris, pt.d_refit.get(), pt.ev_refit[0], &maxabs)) return rc;
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    if (int rc = detach_mesh(c)) return rc;  // a mesh other contexts render too is left to them
+    DeviceMesh& m = *pt.own;
     // 2. commit: frame-slot lanes are idled (they re-borrow the mesh on their next submit), then the arrays are rewritten in place
     rt::frames_drop_mesh(c);
     c->state_version++;
@@ -397,9 +472,8 @@ int refit_mesh_device_impl(Ctx* c, const void* verts, uint32_t n_tris) {
 // DESIGN.md §6.11.  Everything is checked on the host before anything is written: a refusal leaves the surfaces as they were
 int set_surfaces_impl(Ctx* c, const uint32_t* kind, const float* ior, uint32_t n_tris) {
     PtData& pt = c->pt;
-    DeviceMesh& m = pt.own;
-    if (!m.n_tris) return c->fail(RT_ERR_STATE, "no mesh has been set");  // none, or a borrowed one
-    if (n_tris != m.n_tris) return c->fail(RT_ERR_INVALID, "the mesh holds %u triangles, n_tris is %u", m.n_tris, n_tris);
+    if (!pt.own) return c->fail(RT_ERR_STATE, "no mesh has been set");  // none, or a borrowed one
+    if (n_tris != pt.own->n_tris) return c->fail(RT_ERR_INVALID, "the mesh holds %u triangles, n_tris is %u", pt.own->n_tris, n_tris);
     // surface word per triangle, the leaf-order albedo.w: 0 Lambert, -1 mirror, eta glass.  Empty: all Lambert
     std::vector<float> w;
     if (kind) {
@@ -425,6 +499,8 @@ int set_surfaces_impl(Ctx* c, const uint32_t* kind, const float* ior, uint32_t n
     rt::DevPtr<float> d_w;
     if (!w.empty() && !dalloc(d_w, w.size())) return c->fail(RT_ERR_OOM, "surface words of %u triangles", n_tris);
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    if (int rc = detach_mesh(c)) return rc;  // a mesh other contexts render too is left to them
+    DeviceMesh& m = *pt.own;
     // commit: frame-slot lanes are idled (they re-borrow the mesh and its flag on their next submit), then albedo.w is rewritten
     // on the context's stream behind the frames already enqueued there
     rt::frames_drop_mesh(c);
@@ -438,7 +514,7 @@ int set_surfaces_impl(Ctx* c, const uint32_t* kind, const float* ior, uint32_t n
         return c->fail(RT_ERR_STATE, "surface upload failed: the mesh has been dropped, set it again");
     }
     m.has_surfaces = !w.empty();
-    if (pt.host) pt.host->surf.swap(w);  // a chunk rebuild packs them again
+    if (m.host) m.host->surf.swap(w);  // a chunk rebuild packs them again
     return RT_OK;
 }
 
@@ -485,8 +561,8 @@ namespace rt {
 // before it frees or replaces the mesh (frames_drop_mesh).
 void pt_borrow_mesh(Ctx* lane, const Ctx* owner) {  // owner == nullptr: only forget what was borrowed
     pt_free_mesh(lane->pt);
-    if (!owner || !owner->pt.own.n_tris) return;
-    lane->pt.borrowed = &owner->pt.own;
+    if (!owner || !owner->pt.own) return;
+    lane->pt.borrowed = owner->pt.own.get();
     publish_mesh_stats(lane->pt);
 }
 }  // namespace rt
@@ -506,8 +582,8 @@ int rt_set_mesh_ex(rt_ctx* ctx, const float* verts, const float* albedo, const f
 int rt_mesh_chunk_info(rt_ctx* ctx, uint32_t chunk, uint32_t* count, uint32_t* tri_ids, uint32_t capacity) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
-    if (!c->pt.host) return c->fail(RT_ERR_STATE, "not a two-level mesh");
-    const rt::TwoLevelBvh& tl = c->pt.host->tl;
+    if (!c->pt.host()) return c->fail(RT_ERR_STATE, "not a two-level mesh");
+    const rt::TwoLevelBvh& tl = c->pt.host()->tl;
     if (chunk >= tl.blas.size()) return c->fail(RT_ERR_INVALID, "chunk %u of %zu", chunk, tl.blas.size());
     const uint32_t first = tl.first[chunk], n = tl.first[chunk + 1] - first;
     if (count) *count = n;
@@ -543,6 +619,12 @@ int rt_set_mesh_surfaces(rt_ctx* ctx, const uint32_t* kind, const float* ior, ui
     if (!c) return RT_ERR_INVALID;
     // every refusal comes before the first write; a HIP failure after it drops the mesh itself (RT_ERR_STATE)
     return guarded(c, "surfaces", [&] { return set_surfaces_impl(c, kind, ior, n_tris); }, false);
+}
+
+int rt_mesh_sharers(rt_ctx* ctx) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    return (int)resident_meshes().holders(c->pt.own);
 }
 
 int rt_read_bvh(rt_ctx* ctx, uint32_t* nodes_out, uint32_t node_capacity, uint32_t* leaf_tris_out, uint32_t tri_capacity, uint32_t* n_nodes) {

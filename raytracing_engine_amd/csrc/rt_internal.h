@@ -221,7 +221,9 @@ bool dalloc(DevPtr<T>& p, size_t count) {  // frees what p held first; false: ou
 }
 
 // A mesh resident on the device: the arrays the kernels read and what the host knows about them.  Made by the host build
-// (rt_abi_mesh.hip) or by build_bvh_device, owned by one context (PtData::own), read through a pointer by that context's frame-slot lanes.
+// (rt_abi_mesh.hip) or by build_bvh_device.  Contexts hold it through a shared pointer (PtData::own): contexts that were given the same host
+// mesh hold the same record and treat it as read-only; whoever writes into it makes sure first that it is the only holder (detach_mesh,
+// DESIGN.md §6.12).  A context's frame-slot lanes read it through a plain pointer.
 struct DeviceMesh {
     DevPtr<float4> nodes;     // cap_nodes x 80 B of which n_nodes are used, bvh_build.h layout
     DevPtr<float4> tris;      // leaf order, 48 B per triangle (PtScene::tris)
@@ -235,13 +237,17 @@ struct DeviceMesh {
     bool has_surfaces = false;  // some triangle is a mirror or glass (albedo.w != 0): frames take pt_shade<true>, DESIGN.md §6.11
     // single-level meshes: level d of the breadth-first tree = nodes [level_start[d], level_start[d + 1]) (empty: no refit)
     std::vector<uint32_t> level_start;
+    std::unique_ptr<MeshHost> host;  // two-level meshes only
 };
 
 struct PtData {  // device residency of one mesh + the wavefront buffers
-    DeviceMesh own;                        // the mesh this context owns (n_tris = 0: none)
+    std::shared_ptr<DeviceMesh> own;       // the mesh this context holds, alone or with other contexts (empty: none)
     const DeviceMesh* borrowed = nullptr;  // frame-slot lanes: the parent's mesh, which the parent takes back (frames_drop_mesh) before it frees or replaces it
-    const DeviceMesh& mesh() const { return borrowed ? *borrowed : own; }  // what frames render
-    std::unique_ptr<MeshHost> host;  // two-level meshes only
+    const DeviceMesh& mesh() const {       // what frames render (n_tris = 0: nothing)
+        static const DeviceMesh none;
+        return borrowed ? *borrowed : own ? *own : none;
+    }
+    MeshHost* host() const { return own ? own->host.get() : nullptr; }  // lanes do not see it
     DevPtr<char> d_refit;  // rt_refit_mesh_device scratch (refit_scratch_size), allocated by the first refit, freed with the mesh
     hipEvent_t ev_refit[2] = {nullptr, nullptr};
     DevPtr<unsigned long long> d_spill;
@@ -324,7 +330,7 @@ inline uint32_t owned_tiles(const Partition& p) {
 void frames_free(Ctx* c);          // rt_abi_frames.hip: waits for frames in flight, releases every slot
 void frames_drop_mesh(Ctx* c);     // rt_abi_frames.hip: the parent's mesh is about to be freed: idle the lanes, forget the borrowed mesh
 void pt_borrow_mesh(Ctx* lane, const Ctx* owner);  // rt_abi_mesh.hip: lane renders with owner's device mesh
-void pt_free_mesh(PtData& pt);     // rt_abi_mesh.hip: the mesh (owned or borrowed) and everything sized for it
+void pt_free_mesh(PtData& pt);     // rt_abi_mesh.hip: this context's hold on its mesh (held or borrowed) and everything sized for it
 
 // path_a.hip
 int launch_cone_level(Ctx* c, const SphereSet& spheres, uint32_t n_obj, const ConeLevelParams& p, const float* parent,

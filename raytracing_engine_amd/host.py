@@ -373,6 +373,13 @@ class Renderer:
             iorp = _fptr(ior)
         self._check(self._lib.rt_set_mesh_surfaces(self._ctx, kind.ctypes.data_as(C.POINTER(C.c_uint32)), iorp, len(kind)))
 
+    def mesh_sharers(self):
+        """Contexts that render this renderer's device mesh (rt_mesh_sharers): 0 = no mesh, 1 = only this one."""
+        n = self._lib.rt_mesh_sharers(self._ctx)
+        if n < 0:
+            self._check(n)
+        return n
+
     def read_bvh(self):
         """Test hook: (node words uint32 (n_nodes, 20), leaf order uint32 (n_tris,)) of the current mesh."""
         n_nodes = C.c_uint32()
