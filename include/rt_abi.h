@@ -368,7 +368,7 @@ int rt_set_mesh_surfaces(rt_ctx* ctx, const uint32_t* kind, const float* ior, ui
  * environment, read by each rt_set_mesh*, makes that call build and upload for itself.
  * Returns the number of contexts that render this context's device mesh: 0 = no mesh, 1 = only this one; RT_ERR_INVALID for NULL. */
 int rt_mesh_sharers(rt_ctx* ctx);
-/* Test hook: node words (n_nodes x 20 u32, bvh_build.h layout) and leaf order (leaf position -> original triangle index,
+/* Test hook: node words (n_nodes x 20 u32, csrc/bvh_node.h layout) and leaf order (leaf position -> original triangle index,
  * n_tris u32) of the current mesh, host- or device-built.  NULL outputs: only *n_nodes is written (capacity query);
  * a non-NULL output whose capacity is too small: RT_ERR_INVALID.  No mesh: RT_ERR_STATE. */
 int rt_read_bvh(rt_ctx* ctx, uint32_t* nodes_out, uint32_t node_capacity, uint32_t* leaf_tris_out, uint32_t tri_capacity, uint32_t* n_nodes);

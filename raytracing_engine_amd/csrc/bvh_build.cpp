@@ -9,10 +9,8 @@
 // "Efficient Incoherent Ray Traversal on GPUs Through Compressed Wide BVHs", HPG 2017): traversal on
 // gfx950 is bound by the vector L1's request rate (one lane-address per cycle; a divergent 16-byte
 // load is 64 of them), so the node format minimises 16-byte fetches per ray: 8 children in 5 fetches.
-// Layout: bvh_build.h.
+// Layout, quantisation and slot assignment: bvh_node.h.
 #include "bvh_build.h"
-
-#include <sched.h>
 
 #include <algorithm>
 #include <atomic>
@@ -22,6 +20,9 @@
 #include <limits>
 #include <system_error>
 #include <thread>
+
+#include "bvh_node.h"
+#include "host_parallel.h"
 
 #ifdef RT_BVH_TIMING
 #include <chrono>
@@ -36,80 +37,10 @@
 namespace rt {
 namespace {
 
-// CPUs this process may run on (the GPU boxes grant a slice of the machine), at most 32
-int host_threads() {
-    cpu_set_t set;
-    int n = 1;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) n = CPU_COUNT(&set);
-    return std::min(std::max(n, 1), 32);
-}
-
-// fn(i) for i in [0, n) on up to `threads` threads (contiguous chunks; fn must only touch item i's data).
-// Nothing escapes a worker thread: an exception inside fn is carried back and rethrown here after every
-// thread has been joined, and chunks whose thread could not be created (std::system_error: thread or
-// process limit of the box) run on the calling thread, so the result never depends on how many started.
-template <typename F>
-void parallel_for(size_t n, int threads, size_t kMinPerThread, F fn) {
-    const size_t want = std::min<size_t>((size_t)std::max(threads, 1), (n + kMinPerThread - 1) / kMinPerThread);
-    if (want <= 1) {
-        for (size_t i = 0; i < n; i++) fn(i);
-        return;
-    }
-    std::vector<std::thread> pool;
-    pool.reserve(want - 1);
-    std::vector<std::exception_ptr> errs(want);
-    const size_t chunk = (n + want - 1) / want;
-    auto run = [&](size_t t) noexcept {
-        try {
-            for (size_t i = t * chunk; i < std::min(n, (t + 1) * chunk); i++) fn(i);
-        } catch (...) {
-            errs[t] = std::current_exception();
-        }
-    };
-    for (size_t t = 1; t < want; t++) {
-        try {
-            pool.emplace_back(run, t);
-        } catch (const std::system_error&) {
-            break;
-        }
-    }
-    run(0);
-    for (size_t t = pool.size() + 1; t < want; t++) run(t);
-    for (auto& th : pool) th.join();
-    for (auto& e : errs)
-        if (e) std::rethrow_exception(e);
-}
-
-struct Box {
-    float lo[3], hi[3];
-    void reset() {
-        for (int a = 0; a < 3; a++) {
-            lo[a] = std::numeric_limits<float>::infinity();
-            hi[a] = -std::numeric_limits<float>::infinity();
-        }
-    }
-    void grow(const Box& b) {
-        for (int a = 0; a < 3; a++) {
-            lo[a] = std::min(lo[a], b.lo[a]);
-            hi[a] = std::max(hi[a], b.hi[a]);
-        }
-    }
-    void grow(const float p[3]) {
-        for (int a = 0; a < 3; a++) {
-            lo[a] = std::min(lo[a], p[a]);
-            hi[a] = std::max(hi[a], p[a]);
-        }
-    }
-    float half_area() const {
-        const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-        return dx * dy + dy * dz + dz * dx;
-    }
-};
-
 constexpr int kBins = 16;
 
 struct Builder {
-    const std::vector<Box>& tri_box;
+    const std::vector<Box>& tri_boxes;
     const std::vector<float>& centroid;  // n*3
     std::vector<uint32_t>& order;
     std::vector<float>& nodes;  // 16 floats per node
@@ -129,10 +60,23 @@ struct Builder {
     };
 
     Box range_box(uint32_t first, uint32_t count) const {
-        Box b;
-        b.reset();
-        for (uint32_t i = 0; i < count; i++) b.grow(tri_box[order[first + i]]);
+        Box b = Box::empty();
+        for (uint32_t i = 0; i < count; i++) b.grow(tri_boxes[order[first + i]]);
         return b;
+    }
+
+    // binary node `me`, 16 floats: the two children's boxes (lo.xyz, hi.xyz each) with the padding on, their references, 0, 0
+    void write_node(uint32_t me, const Box& b0, int32_t r0, const Box& b1, int32_t r1) {
+        float* n = &nodes[(size_t)me * 16];
+        const Box* side[2] = {&b0, &b1};
+        for (int s = 0; s < 2; s++)
+            for (int a = 0; a < 3; a++) {
+                n[6 * s + a] = side[s]->lo[a] - pad;
+                n[6 * s + 3 + a] = side[s]->hi[a] + pad;
+            }
+        std::memcpy(&n[12], &r0, 4);
+        std::memcpy(&n[13], &r1, 4);
+        n[14] = n[15] = 0.0f;
     }
 
     static int32_t leaf_ref(uint32_t first, uint32_t count) { return ~(int32_t)((first << 2) | (count - 1u)); }
@@ -219,7 +163,7 @@ struct Builder {
                 Bins& P = part[c];
                 for (int a = 0; a < 3; a++)
                     for (int b = 0; b < kBins; b++) {
-                        P.bb[a][b].reset();
+                        P.bb[a][b] = Box::empty();
                         P.bc[a][b] = 0;
                     }
                 const uint32_t i1 = std::min<uint32_t>(count, (uint32_t)(c + 1) * chunk);
@@ -229,7 +173,7 @@ struct Builder {
                         if (!(kk[a] > 0.0f)) continue;
                         int bin = (int)((centroid[3 * (size_t)t + a] - clo[a]) * kk[a]);
                         bin = std::min(std::max(bin, 0), kBins - 1);
-                        P.bb[a][bin].grow(tri_box[t]);
+                        P.bb[a][bin].grow(tri_boxes[t]);
                         P.bc[a][bin]++;
                     }
                 }
@@ -248,8 +192,7 @@ struct Builder {
                 }
                 float right_area[kBins];
                 uint32_t right_cnt[kBins];
-                Box acc;
-                acc.reset();
+                Box acc = Box::empty();
                 uint32_t cnt = 0;
                 for (int b = kBins - 1; b > 0; b--) {
                     acc.grow(bb[b]);
@@ -257,7 +200,7 @@ struct Builder {
                     right_area[b] = cnt ? acc.half_area() : 0.0f;
                     right_cnt[b] = cnt;
                 }
-                acc.reset();
+                acc = Box::empty();
                 cnt = 0;
                 for (int b = 0; b < kBins - 1; b++) {
                     acc.grow(bb[b]);
@@ -342,15 +285,7 @@ struct Builder {
             s0 = build(first, mid, depth + 1, me + 1u);
             s1 = build(first + mid, count - mid, depth + 1, me + mid);
         }
-        const int32_t r0 = s0.ref, r1 = s1.ref;
-        float* n = &nodes[(size_t)me * 16];
-        const float p = pad;
-        n[0] = b0.lo[0] - p; n[1] = b0.lo[1] - p; n[2] = b0.lo[2] - p; n[3] = b0.hi[0] + p;
-        n[4] = b0.hi[1] + p; n[5] = b0.hi[2] + p; n[6] = b1.lo[0] - p; n[7] = b1.lo[1] - p;
-        n[8] = b1.lo[2] - p; n[9] = b1.hi[0] + p; n[10] = b1.hi[1] + p; n[11] = b1.hi[2] + p;
-        std::memcpy(&n[12], &r0, 4);
-        std::memcpy(&n[13], &r1, 4);
-        n[14] = n[15] = 0.0f;
+        write_node(me, b0, s0.ref, b1, s1.ref);
         // tree-shaped sums: the same value whatever the thread count
         return Sub{(int32_t)me, std::max(depth, std::max(s0.depth_reached, s1.depth_reached)),
                    ((double)b0.half_area() + (double)b1.half_area()) + (s0.sah + s1.sah)};
@@ -364,17 +299,12 @@ struct Builder {
 namespace {
 
 struct Child {
-    float box[6];  // lo.xyz, hi.xyz (already padded)
-    int32_t ref;   // >= 0: binary inner node that becomes an 8-wide node; < 0: leaf ~((first << 2) | (count - 1)), count <= 3
+    Box box;      // already padded
+    int32_t ref;  // >= 0: binary inner node that becomes an 8-wide node; < 0: leaf ~((first << 2) | (count - 1)), count <= 3
 };
 
-inline float box_area(const float b[6]) {
-    const float dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2];
-    return dx * dy + dy * dz + dz * dx;
-}
-
-// Binary SAH tree (one triangle per leaf) -> compressed 8-wide BVH (layout in bvh_build.h).
-// Which binary nodes become 8-wide nodes and how the 8 (every leaf is one triangle: bvh_build.h)
+// Binary SAH tree (one triangle per leaf) -> compressed 8-wide BVH (layout in bvh_node.h).
+// Which binary nodes become 8-wide nodes and how the 8 (every leaf is one triangle: bvh_node.h)
 // child slots of every node are spent is chosen by the dynamic program of Ylitie et al. 2017 (§4.1):
 //   C(n,1)   = min( A(n) P(n) c_prim  [P(n) == 1],   A(n) c_node + D(n,8) )
 //   C(n,i>1) = min( D(n,i), C(n,i-1) ),   D(n,i) = min_{0<k<i} C(left,k) + C(right,i-k)
@@ -396,13 +326,18 @@ struct Cw8Builder {
         uint8_t prev;      // bit i set: C(n,i) = C(n,i-1)
         uint8_t is_leaf;   // C(n,1) chose the leaf
         uint32_t first, prims;
-        float box[6];
+        Box box;
     };
     std::vector<Dp> dp;
     int max_threads = 0;  // 0 = every CPU the process may use
     int thread_count() const { return max_threads > 0 ? std::min(max_threads, host_threads()) : host_threads(); }
 
-    void child_box(int32_t node2, int side, float out[6]) const { std::memcpy(out, &n2[(size_t)node2 * 16 + 6 * side], 24); }
+    Box child_box(int32_t node2, int side) const {  // six floats of the binary node: lo.xyz, hi.xyz
+        Box b;
+        std::memcpy(b.lo, &n2[(size_t)node2 * 16 + 6 * side], 12);
+        std::memcpy(b.hi, &n2[(size_t)node2 * 16 + 6 * side + 3], 12);
+        return b;
+    }
     int32_t child_ref(int32_t node2, int side) const {
         int32_t r;
         std::memcpy(&r, &n2[(size_t)node2 * 16 + 12 + side], 4);
@@ -452,13 +387,14 @@ struct Cw8Builder {
         {
             const int32_t j = (int32_t)jj;
             Dp& d = dp[jj];
-            float cb[2][6], carea[2];
+            Box cb[2];
+            float carea[2];
             int32_t cr[2];
             uint32_t cprims[2], cfirst[2];
             for (int s = 0; s < 2; s++) {
-                child_box(j, s, cb[s]);
+                cb[s] = child_box(j, s);
                 cr[s] = child_ref(j, s);
-                carea[s] = box_area(cb[s]);
+                carea[s] = cb[s].half_area();
                 if (cr[s] < 0) {
                     const uint32_t ref = ~(uint32_t)cr[s];
                     cfirst[s] = ref >> 2;
@@ -472,10 +408,8 @@ struct Cw8Builder {
                 if (cr[s] < 0) return carea[s] * (float)cprims[s] * kCostPrim;
                 return dp[cr[s]].cost[i > 7 ? 7 : i];
             };
-            for (int a = 0; a < 3; a++) {
-                d.box[a] = std::min(cb[0][a], cb[1][a]);
-                d.box[3 + a] = std::max(cb[0][3 + a], cb[1][3 + a]);
-            }
+            d.box = cb[0];
+            d.box.grow(cb[1]);
             const bool same = cr[0] < 0 && cr[0] == cr[1];  // tiny mesh: both slots name one leaf
             d.first = std::min(cfirst[0], cfirst[1]);
             d.prims = same ? cprims[0] : cprims[0] + cprims[1];
@@ -494,7 +428,7 @@ struct Cw8Builder {
                 D[i] = best;
                 d.split[i] = (uint8_t)bk;
             }
-            const float area = box_area(d.box);
+            const float area = d.box.half_area();
             const float c_leaf = d.prims <= 1 ? area * (float)d.prims * kCostPrim : std::numeric_limits<float>::infinity();  // leaves are single triangles
             const float c_int = D[8] + area * kCostNode;
             d.is_leaf = c_leaf <= c_int;
@@ -513,9 +447,9 @@ struct Cw8Builder {
     }
 
     // represent binary subtree `ref` (box `box`) as a forest of at most `budget` roots
-    void expand(int32_t ref, const float box[6], int budget, Child* out, int& k) const {
+    void expand(int32_t ref, const Box& box, int budget, Child* out, int& k) const {
         if (ref < 0) {
-            std::memcpy(out[k].box, box, 24);
+            out[k].box = box;
             out[k++].ref = ref;
             return;
         }
@@ -523,7 +457,7 @@ struct Cw8Builder {
         if (budget > 7) budget = 7;
         while (budget > 1 && ((d.prev >> budget) & 1)) budget--;
         if (budget == 1) {
-            std::memcpy(out[k].box, d.box, 24);
+            out[k].box = d.box;
             out[k++].ref = d.is_leaf ? ~(int32_t)((d.first << 2) | (d.prims - 1u)) : ref;
             return;
         }
@@ -531,9 +465,7 @@ struct Cw8Builder {
     }
     void distribute(int32_t node2, int budget, Child* out, int& k) const {
         const int kl = dp[node2].split[budget];
-        float b0[6], b1[6];
-        child_box(node2, 0, b0);
-        child_box(node2, 1, b1);
+        const Box b0 = child_box(node2, 0), b1 = child_box(node2, 1);
         const int32_t r0 = child_ref(node2, 0), r1 = child_ref(node2, 1);
         if (r0 < 0 && r0 == r1) {  // tiny mesh
             expand(r0, b0, 1, out, k);
@@ -556,7 +488,7 @@ struct Cw8Builder {
         Child ch[8];
         int k;
         int child_in[8];  // slot -> child, -1 = empty
-        float lo[3], hi[3];
+        Box box;
         uint32_t n_inner, n_tris;
         uint32_t child_base, tri_base;
     };
@@ -567,58 +499,23 @@ struct Cw8Builder {
         int k = 0;
         if (dp[pd.node2].is_leaf && pd.level == 0) {  // whole mesh fits one leaf: root node with a single leaf child
             const Dp& d = dp[pd.node2];
-            std::memcpy(ch[0].box, d.box, 24);
+            ch[0].box = d.box;
             ch[0].ref = ~(int32_t)((d.first << 2) | (d.prims - 1u));
             k = 1;
         } else {
             distribute(pd.node2, 8, ch, k);
         }
         w.k = k;
-        float* lo = w.lo;
-        float* hi = w.hi;
-        for (int a = 0; a < 3; a++) {
-            lo[a] = ch[0].box[a];
-            hi[a] = ch[0].box[3 + a];
-            for (int i = 1; i < k; i++) {
-                lo[a] = std::min(lo[a], ch[i].box[a]);
-                hi[a] = std::max(hi[a], ch[i].box[3 + a]);
-            }
-        }
-        // slot assignment: slot bits (x,y,z) = which side of the node centre the child sits on, so that
-        // slot ^ (7 - ray octant) orders children front to back; greedy on dot(child centre - node centre, slot dir)
-        int slot_of[8];
-        int* child_in = w.child_in;
-        for (int i = 0; i < 8; i++) slot_of[i] = child_in[i] = -1;
-        float score[8][8];
+        Box cb[8];
+        w.box = Box::empty();
         for (int i = 0; i < k; i++) {
-            float off[3];
-            for (int a = 0; a < 3; a++) off[a] = 0.5f * (ch[i].box[a] + ch[i].box[3 + a]) - 0.5f * (lo[a] + hi[a]);
-            for (int s = 0; s < 8; s++) {
-                float c = 0.0f;
-                for (int a = 0; a < 3; a++) c += ((s >> (2 - a)) & 1) ? off[a] : -off[a];
-                score[i][s] = c;
-            }
+            cb[i] = ch[i].box;
+            w.box.grow(cb[i]);
         }
-        for (int round = 0; round < k; round++) {
-            float best = -std::numeric_limits<float>::infinity();
-            int bi = -1, bs = -1;
-            for (int i = 0; i < k; i++) {
-                if (slot_of[i] >= 0) continue;
-                for (int s = 0; s < 8; s++) {
-                    if (child_in[s] >= 0) continue;
-                    if (score[i][s] > best) {
-                        best = score[i][s];
-                        bi = i;
-                        bs = s;
-                    }
-                }
-            }
-            slot_of[bi] = bs;
-            child_in[bs] = bi;
-        }
+        assign_slots(cb, k, w.box, w.child_in);
         w.n_inner = w.n_tris = 0;
         for (int s = 0; s < 8; s++) {
-            const int i = child_in[s];
+            const int i = w.child_in[s];
             if (i < 0) continue;
             if (ch[i].ref >= 0) w.n_inner++;
             else w.n_tris += (~(uint32_t)ch[i].ref & 3u) + 1u;
@@ -628,37 +525,14 @@ struct Cw8Builder {
     // node words, leaf triangle order and the next level's entries of one planned node (storage is sized by the caller)
     void write(const Work& wk, Pending* next_level, uint32_t next_level_base) {
         const Child* ch = wk.ch;
-        const int* child_in = wk.child_in;
-        const float* lo = wk.lo;
-        const float* hi = wk.hi;
-        // quantisation frame: p = lo, per-axis power-of-two scale with 255 * scale >= extent
-        uint32_t e_byte[3];
-        double scale[3];
-        for (int a = 0; a < 3; a++) {
-            const double ext = (double)hi[a] - (double)lo[a];
-            int e = ext > 0.0 ? (int)std::ceil(std::log2(ext / 255.0)) : -126;
-            e = std::min(std::max(e, -126), 127);
-            while (e < 127 && std::ldexp(255.0, e) < ext) e++;
-            e_byte[a] = (uint32_t)(e + 127);
-            scale[a] = std::ldexp(1.0, e);
-        }
-        uint32_t* w = &nodes[(size_t)wk.pd.index * 20];
-        std::memcpy(w, lo, 12);
-        uint32_t imask = 0;
-        for (int s = 0; s < 8; s++)
-            if (child_in[s] >= 0 && ch[child_in[s]].ref >= 0) imask |= 1u << s;
-        w[3] = e_byte[0] | (e_byte[1] << 8) | (e_byte[2] << 16) | (imask << 24);
-        w[4] = wk.child_base;
-        w[5] = wk.tri_base;
-        uint8_t q[6][8];
-        uint32_t leafmask = 0;
-        for (int a = 0; a < 6; a++)
-            for (int s = 0; s < 8; s++) q[a][s] = a < 3 ? 255 : 0;  // empty slot: inverted box, in neither mask
-        uint32_t rank = 0, off = 0;
+        Box cb[8];
+        uint32_t imask = 0, leafmask = 0, rank = 0, off = 0;
         for (int s = 0; s < 8; s++) {
-            const int i = child_in[s];
+            const int i = wk.child_in[s];
             if (i < 0) continue;
+            cb[s] = ch[i].box;
             if (ch[i].ref >= 0) {
+                imask |= 1u << s;
                 next_level[wk.child_base + rank - next_level_base] = Pending{ch[i].ref, wk.child_base + rank, wk.pd.level + 1};
                 rank++;
             } else {
@@ -667,18 +541,10 @@ struct Cw8Builder {
                 order8[(size_t)wk.tri_base + off] = order2[first];
                 off += 1;
             }
-            for (int a = 0; a < 3; a++) {
-                double ql = std::floor(((double)ch[i].box[a] - (double)lo[a]) / scale[a]);
-                double qh = std::ceil(((double)ch[i].box[3 + a] - (double)lo[a]) / scale[a]);
-                ql = std::min(std::max(ql, 0.0), 255.0);
-                qh = std::min(std::max(qh, 0.0), 255.0);
-                q[a][s] = (uint8_t)ql;
-                q[3 + a][s] = (uint8_t)qh;
-            }
         }
-        w[6] = leafmask;
-        w[7] = 0;
-        for (int a = 0; a < 6; a++) std::memcpy(&w[8 + 2 * a], q[a], 8);
+        uint32_t* w = node_at(nodes.data(), wk.pd.index);
+        quantise(wk.box, cb, imask | leafmask, w);
+        node_set_topology(w, imask, wk.child_base, wk.tri_base, leafmask);
     }
 
     void build() {
@@ -704,7 +570,7 @@ struct Cw8Builder {
                 node_count += w.n_inner;
                 tri_count += w.n_tris;
             }
-            nodes.resize((size_t)node_count * 20, 0u);
+            nodes.resize((size_t)node_count * kNodeWords, 0u);
             order8.resize(tri_count);
             next.resize(node_count - next_base);
             parallel_for(work.size(), threads, 256, [&](size_t i) { write(work[i], next.data(), next_base); });
@@ -718,24 +584,16 @@ struct Cw8Builder {
 bool build_bvh(const float* v0, const float* e1, const float* e2, uint32_t n, uint32_t max_depth, BvhResult* out) {
     if (!v0 || !e1 || !e2 || n == 0 || n >= (1u << 29) || !out) return false;
     RT_BVH_T(t_start);
-    std::vector<Box> tri_box(n);
+    std::vector<Box> tri_boxes(n);
     std::vector<float> centroid(3 * (size_t)n);
     float maxabs = 0.0f;
     for (uint32_t i = 0; i < n; i++) {
-        Box b;
-        b.reset();
-        float p0[3], p1[3], p2[3];
         for (int a = 0; a < 3; a++) {
-            p0[a] = v0[3 * (size_t)i + a];
-            p1[a] = p0[a] + e1[3 * (size_t)i + a];
-            p2[a] = p0[a] + e2[3 * (size_t)i + a];
-            centroid[3 * (size_t)i + a] = p0[a] + (e1[3 * (size_t)i + a] + e2[3 * (size_t)i + a]) * (1.0f / 3.0f);
-            maxabs = std::max(maxabs, std::max(std::fabs(p0[a]), std::max(std::fabs(p1[a]), std::fabs(p2[a]))));
+            const float p0 = v0[3 * (size_t)i + a], p1 = p0 + e1[3 * (size_t)i + a], p2 = p0 + e2[3 * (size_t)i + a];
+            centroid[3 * (size_t)i + a] = p0 + (e1[3 * (size_t)i + a] + e2[3 * (size_t)i + a]) * (1.0f / 3.0f);
+            maxabs = std::max(maxabs, std::max(std::fabs(p0), std::max(std::fabs(p1), std::fabs(p2))));
         }
-        b.grow(p0);
-        b.grow(p1);
-        b.grow(p2);
-        tri_box[i] = b;
+        tri_boxes[i] = tri_box(&v0[3 * (size_t)i], &e1[3 * (size_t)i], &e2[3 * (size_t)i], 0.0f);  // the padding goes on when the boxes are stored in nodes
     }
     out->order.resize(n);
     for (uint32_t i = 0; i < n; i++) out->order[i] = i;
@@ -746,21 +604,14 @@ bool build_bvh(const float* v0, const float* e1, const float* e2, uint32_t n, ui
     const uint32_t leaf_max = 1;  // the binary tree goes down to single triangles; the collapse keeps them as one-triangle leaves
     const int threads = out->max_threads > 0 ? std::min(out->max_threads, host_threads()) : host_threads();
     std::atomic<int> spare_threads{threads - 1};
-    Builder b{tri_box, centroid, out->order, binary, out->pad, max_depth, leaf_max, &spare_threads, threads};
+    Builder b{tri_boxes, centroid, out->order, binary, out->pad, max_depth, leaf_max, &spare_threads, threads};
     out->sah_area = 0.0;
     if (n <= leaf_max) {
         // one node whose two slots name the same leaf (testing it twice is idempotent)
         binary.resize(16);
-        Box bx = b.range_box(0, n);
-        float* nd = binary.data();
-        const float p = out->pad;
-        const float box[6] = {bx.lo[0] - p, bx.lo[1] - p, bx.lo[2] - p, bx.hi[0] + p, bx.hi[1] + p, bx.hi[2] + p};
-        std::memcpy(nd, box, 24);
-        std::memcpy(nd + 6, box, 24);
+        const Box bx = b.range_box(0, n);
         const int32_t r = Builder::leaf_ref(0, n);
-        std::memcpy(nd + 12, &r, 4);
-        std::memcpy(nd + 13, &r, 4);
-        nd[14] = nd[15] = 0.0f;
+        b.write_node(0, bx, r, bx, r);
         out->depth = 1;
     } else {
         RT_BVH_T(t_prep);
@@ -782,7 +633,7 @@ bool build_bvh(const float* v0, const float* e1, const float* e2, uint32_t n, ui
     RT_BVH_T(t_c1);
     RT_BVH_REPORT("collapse + emit", t_c0, t_c1);
     if (out->order.size() != n) return false;
-    out->n_nodes = (uint32_t)(out->nodes.size() / 20);
+    out->n_nodes = (uint32_t)(out->nodes.size() / kNodeWords);
     out->depth = cw.depth;
     out->stack_need = cw.depth + 1;  // at most one pending sibling group per level
     return true;

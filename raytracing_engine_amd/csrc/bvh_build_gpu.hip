@@ -1,11 +1,11 @@
 // bvh_build_gpu.hip — path B's BVH built on the GPU from device-resident triangles (rt_set_mesh_device).
 //
-// Produces exactly the node format of bvh_build.h (80-byte compressed 8-wide nodes, one triangle per leaf slot,
+// Produces exactly the node format of bvh_node.h (80-byte compressed 8-wide nodes, one triangle per leaf slot,
 // breadth-first order, inner children and leaf triangles consecutive per node), so the traversal kernels cannot tell
 // the difference.  The tree itself is an LBVH (Karras, "Maximizing Parallelism in the Construction of BVHs, Octrees,
 // and k-d Trees", HPG 2012) collapsed top-down into 8-wide nodes; stages and their launches: DESIGN.md §6.9.  The refit of a
 // single-level tree, host- or device-built, to new vertices (rt_refit_mesh_device) is here too: it shares the
-// validation and the quantiser with the build.
+// validation with the build, and the quantiser (bvh_node.h) with the build and with the host builder.
 //
 // Rules every kernel here keeps:
 //  - no data passes between workgroups inside a launch: every dependency is a launch boundary (no flags, no look-back,
@@ -19,6 +19,7 @@
 #include <cstring>
 #include <vector>
 
+#include "bvh_node.h"
 #include "rt_internal.h"
 
 namespace rt {
@@ -32,43 +33,19 @@ constexpr uint32_t kTopLevelNodes = 4096;              // segment-tree levels th
 constexpr int32_t kEmpty = INT_MIN;                    // empty child slot in a plan
 constexpr uint32_t kMaxLevels = 128;                   // the binary tree is at most 62 deep (key bits); a guard only
 
-struct DBox {
-    float lo[3], hi[3];
-};
-
 struct Plan {  // one 8-wide node: child reference per slot (>= 0 binary inner node, < 0 ~sorted leaf position, kEmpty)
     int32_t slot[8];
 };
 
-__device__ __forceinline__ void box_empty(DBox& b) {
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = INFINITY;
-        b.hi[a] = -INFINITY;
-    }
-}
-
-__device__ __forceinline__ void box_grow(DBox& b, const DBox& o) {
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = fminf(b.lo[a], o.lo[a]);
-        b.hi[a] = fmaxf(b.hi[a], o.hi[a]);
-    }
-}
-
-__device__ __forceinline__ float half_area(const DBox& b) {
-    const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
-    return dx * dy + dy * dz + dz * dx;
-}
-
-// padded box of triangle t over the vertices rebuilt in fp32 from the edges, as build_bvh forms it (set_mesh_impl's edges)
-__device__ __forceinline__ DBox tri_box(const float* __restrict__ v, uint32_t t, float pad) {
+// padded box of triangle t, its edges formed in fp32 as set_mesh_impl forms them for build_bvh
+__device__ __forceinline__ Box tri_box_at(const float* __restrict__ v, uint32_t t, float pad) {
     const float* p = v + 9 * (size_t)t;
-    DBox b;
+    float e1[3], e2[3];
     for (int a = 0; a < 3; a++) {
-        const float p0 = p[a], p1 = p0 + (p[3 + a] - p0), p2 = p0 + (p[6 + a] - p0);
-        b.lo[a] = fminf(p0, fminf(p1, p2)) - pad;
-        b.hi[a] = fmaxf(p0, fmaxf(p1, p2)) + pad;
+        e1[a] = p[3 + a] - p[a];
+        e2[a] = p[6 + a] - p[a];
     }
-    return b;
+    return tri_box(p, e1, e2, pad);
 }
 
 template <class T, class Op>
@@ -148,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void bvhd_validate(const float* __restric
 __global__ __launch_bounds__(kThreads) void bvhd_bounds(const float* __restrict__ v, uint32_t n, float pad, float* __restrict__ part) {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (size_t t = (size_t)blockIdx.x * kThreads + threadIdx.x; t < n; t += (size_t)gridDim.x * kThreads) {
-        const DBox b = tri_box(v, (uint32_t)t, pad);
+        const Box b = tri_box_at(v, (uint32_t)t, pad);
         for (int a = 0; a < 3; a++) {
             const float c = 0.5f * (b.lo[a] + b.hi[a]);
             lo[a] = fminf(lo[a], c);
@@ -188,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void bvhd_keys(const float* __restrict__ 
                                                       unsigned long long* __restrict__ keys) {
     const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
     if (t >= n) return;
-    const DBox b = tri_box(v, t, pad);
+    const Box b = tri_box_at(v, t, pad);
     uint32_t q[3];
     for (int a = 0; a < 3; a++) {
         const float c = 0.5f * (b.lo[a] + b.hi[a]), lo = bounds[a], ext = bounds[3 + a] - lo;
@@ -351,26 +328,26 @@ __global__ __launch_bounds__(kThreads) void bvhd_karras(const unsigned long long
 
 // ---- 6. boxes: a min/max segment tree over the sorted leaf boxes (tree[n + i] = leaf i, tree[k] = tree[2k] u tree[2k+1]) --
 __global__ __launch_bounds__(kThreads) void bvhd_leaf_boxes(const float* __restrict__ v, const unsigned long long* __restrict__ keys, uint32_t n,
-                                                            float pad, DBox* __restrict__ tree) {
+                                                            float pad, Box* __restrict__ tree) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    if (i < n) tree[(size_t)n + i] = tri_box(v, (uint32_t)keys[i], pad);
+    if (i < n) tree[(size_t)n + i] = tri_box_at(v, (uint32_t)keys[i], pad);
 }
 
-__global__ __launch_bounds__(kThreads) void bvhd_box_level(DBox* __restrict__ tree, uint32_t k0, uint32_t k1) {
+__global__ __launch_bounds__(kThreads) void bvhd_box_level(Box* __restrict__ tree, uint32_t k0, uint32_t k1) {
     const uint32_t k = k0 + blockIdx.x * kThreads + threadIdx.x;
     if (k >= k1) return;
-    DBox b = tree[2 * (size_t)k];
-    box_grow(b, tree[2 * (size_t)k + 1]);
+    Box b = tree[2 * (size_t)k];
+    b.grow(tree[2 * (size_t)k + 1]);
     tree[k] = b;
 }
 
 // the small top levels [1, 2^(jtop+1)) by one workgroup, level after level (a barrier between levels, no other workgroup involved)
-__global__ __launch_bounds__(kThreads) void bvhd_box_top(DBox* __restrict__ tree, uint32_t n, int jtop) {
+__global__ __launch_bounds__(kThreads) void bvhd_box_top(Box* __restrict__ tree, uint32_t n, int jtop) {
     for (int j = jtop; j >= 0; j--) {
         const uint32_t k1 = std::min<uint32_t>(2u << j, n);
         for (uint32_t k = (1u << j) + threadIdx.x; k < k1; k += kThreads) {
-            DBox b = tree[2 * (size_t)k];
-            box_grow(b, tree[2 * (size_t)k + 1]);
+            Box b = tree[2 * (size_t)k];
+            b.grow(tree[2 * (size_t)k + 1]);
             tree[k] = b;
         }
         __syncthreads();
@@ -378,17 +355,16 @@ __global__ __launch_bounds__(kThreads) void bvhd_box_top(DBox* __restrict__ tree
 }
 
 // box of internal node i = union of its leaf range, composed from O(log n) segment-tree pieces (min / max: exact)
-__global__ __launch_bounds__(kThreads) void bvhd_inner_boxes(const DBox* __restrict__ tree, const uint2* __restrict__ range, uint32_t n,
-                                                             DBox* __restrict__ ibox) {
+__global__ __launch_bounds__(kThreads) void bvhd_inner_boxes(const Box* __restrict__ tree, const uint2* __restrict__ range, uint32_t n,
+                                                             Box* __restrict__ ibox) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     if (i + 1 >= n) return;
     const uint2 r = range[i];
     size_t lo = (size_t)r.x + n, hi = (size_t)r.y + n + 1;
-    DBox b;
-    box_empty(b);
+    Box b = Box::empty();
     while (lo < hi) {
-        if (lo & 1) box_grow(b, tree[lo++]);
-        if (hi & 1) box_grow(b, tree[--hi]);
+        if (lo & 1) b.grow(tree[lo++]);
+        if (hi & 1) b.grow(tree[--hi]);
         lo >>= 1;
         hi >>= 1;
     }
@@ -398,14 +374,13 @@ __global__ __launch_bounds__(kThreads) void bvhd_inner_boxes(const DBox* __restr
 // ---- 7. collapse to 8-wide nodes, one level at a time -----------------------------------------------------------------------
 struct TreeView {
     const int2* child;
-    const DBox* ibox;
-    const DBox* tree;
+    const Box* ibox;
+    const Box* tree;
     uint32_t n;
-    __device__ DBox box(int32_t ref) const { return ref >= 0 ? ibox[ref] : tree[(size_t)n + (uint32_t)~ref]; }
+    __device__ Box box(int32_t ref) const { return ref >= 0 ? ibox[ref] : tree[(size_t)n + (uint32_t)~ref]; }
 };
 
-// children of one 8-wide node and their slots (plan() of bvh_build.cpp: greedy on dot(child centre - node centre, slot direction),
-// so that slot ^ (7 - ray octant) runs front to back); counts = inner << 32 | leaves
+// children of one 8-wide node and their slots (assign_slots, as the host builder's plan()); counts = inner << 32 | leaves
 __global__ __launch_bounds__(kThreads) void bvhd_plan(TreeView tv, const int32_t* __restrict__ level, uint32_t count, Plan* __restrict__ plan,
                                                       unsigned long long* __restrict__ counts) {
     const uint32_t w = blockIdx.x * kThreads + threadIdx.x;
@@ -426,7 +401,7 @@ __global__ __launch_bounds__(kThreads) void bvhd_plan(TreeView tv, const int32_t
             float best_a = -1.0f;
             for (int i = 0; i < k; i++) {
                 if (ch[i] < 0) continue;
-                const float a = half_area(tv.ibox[ch[i]]);
+                const float a = tv.ibox[ch[i]].half_area();
                 if (a > best_a) {
                     best_a = a;
                     best = i;
@@ -438,46 +413,13 @@ __global__ __launch_bounds__(kThreads) void bvhd_plan(TreeView tv, const int32_t
             ch[k++] = cc.y;
         }
     }
-    DBox cb[8], nb;
-    box_empty(nb);
+    Box cb[8], nb = Box::empty();
     for (int i = 0; i < k; i++) {
         cb[i] = tv.box(ch[i]);
-        box_grow(nb, cb[i]);
+        nb.grow(cb[i]);
     }
-    float score[8][8];
-    for (int i = 0; i < k; i++) {
-        float off[3];
-        for (int a = 0; a < 3; a++) off[a] = 0.5f * (cb[i].lo[a] + cb[i].hi[a]) - 0.5f * (nb.lo[a] + nb.hi[a]);
-        for (int s = 0; s < 8; s++) {
-            float c = 0.0f;
-            for (int a = 0; a < 3; a++) c += ((s >> (2 - a)) & 1) ? off[a] : -off[a];
-            score[i][s] = c;
-        }
-    }
-    int slot_of[8], child_in[8];
-    for (int i = 0; i < 8; i++) slot_of[i] = child_in[i] = -1;
-    for (int round = 0; round < k; round++) {
-        float best = -INFINITY;
-        int bi = -1, bs = -1;
-        for (int i = 0; i < k; i++) {
-            if (slot_of[i] >= 0) continue;
-            for (int s = 0; s < 8; s++) {
-                if (child_in[s] >= 0) continue;
-                if (score[i][s] > best) {
-                    best = score[i][s];
-                    bi = i;
-                    bs = s;
-                }
-            }
-        }
-        if (bi < 0) {  // only with non-finite scores (not for finite input): first free child into the first free slot
-            bi = bs = 0;
-            while (slot_of[bi] >= 0) bi++;
-            while (child_in[bs] >= 0) bs++;
-        }
-        slot_of[bi] = bs;
-        child_in[bs] = bi;
-    }
+    int child_in[8];
+    assign_slots(cb, k, nb, child_in);
     Plan p;
     uint32_t inner = 0, leaves = 0;
     for (int s = 0; s < 8; s++) {
@@ -490,44 +432,6 @@ __global__ __launch_bounds__(kThreads) void bvhd_plan(TreeView tv, const int32_t
     counts[w] = ((unsigned long long)inner << 32) | leaves;
 }
 
-// quantisation of write() in bvh_build.cpp, the one copy that bvhd_write and the refit share so that they cannot drift: frame origin
-// nb.lo, a power-of-two scale per axis with 255 * scale >= extent, child planes floor / ceil outward in double, clamped to [0, 255];
-// a slot not in `occ` gets the inverted box (lo 255, hi 0).  Writes wd[0..2] (origin), wd[3] (exponent bytes; bits 24-31, imask,
-// are left 0) and wd[8..19] (planes); wd[4..7] are not touched
-__device__ __forceinline__ void quantise(const DBox& nb, const DBox* cb, uint32_t occ, uint32_t* wd) {
-    uint32_t e_byte[3];
-    double scale[3];
-    for (int a = 0; a < 3; a++) {
-        const double ext = (double)nb.hi[a] - (double)nb.lo[a];
-        int e = ext > 0.0 ? (int)ceil(log2(ext / 255.0)) : -126;
-        e = min(max(e, -126), 127);
-        while (e < 127 && ldexp(255.0, e) < ext) e++;
-        e_byte[a] = (uint32_t)(e + 127);
-        scale[a] = ldexp(1.0, e);
-    }
-    uint8_t q[6][8];
-    for (int s = 0; s < 8; s++) {
-        for (int a = 0; a < 6; a++) q[a][s] = a < 3 ? 255 : 0;  // empty slot: inverted box
-        if (!((occ >> s) & 1u)) continue;
-        for (int a = 0; a < 3; a++) {
-            double ql = floor(((double)cb[s].lo[a] - (double)nb.lo[a]) / scale[a]);
-            double qh = ceil(((double)cb[s].hi[a] - (double)nb.lo[a]) / scale[a]);
-            ql = fmin(fmax(ql, 0.0), 255.0);
-            qh = fmin(fmax(qh, 0.0), 255.0);
-            q[a][s] = (uint8_t)ql;
-            q[3 + a][s] = (uint8_t)qh;
-        }
-    }
-    wd[0] = __float_as_uint(nb.lo[0]);
-    wd[1] = __float_as_uint(nb.lo[1]);
-    wd[2] = __float_as_uint(nb.lo[2]);
-    wd[3] = e_byte[0] | (e_byte[1] << 8) | (e_byte[2] << 16);
-    for (int a = 0; a < 6; a++) {
-        wd[8 + 2 * a] = q[a][0] | (q[a][1] << 8) | (q[a][2] << 16) | ((uint32_t)q[a][3] << 24);
-        wd[9 + 2 * a] = q[a][4] | (q[a][5] << 8) | (q[a][6] << 16) | ((uint32_t)q[a][7] << 24);
-    }
-}
-
 // node words (quantise()), the next level's binary nodes and the leaf order
 __global__ __launch_bounds__(kThreads) void bvhd_write(TreeView tv, const Plan* __restrict__ plan, const unsigned long long* __restrict__ excl,
                                                        uint32_t count, uint32_t level_base, uint32_t tri_before, uint32_t node_cap,
@@ -538,15 +442,13 @@ __global__ __launch_bounds__(kThreads) void bvhd_write(TreeView tv, const Plan* 
     const Plan p = plan[w];
     const unsigned long long ex = excl[w];
     const uint32_t inner0 = (uint32_t)(ex >> 32), child_base = level_base + count + inner0, tri_base = tri_before + (uint32_t)ex;
-    DBox cb[8], nb;
-    box_empty(nb);
-    uint32_t occ = 0, imask = 0, leafmask = 0, rank = 0, off = 0;
+    Box cb[8], nb = Box::empty();
+    uint32_t imask = 0, leafmask = 0, rank = 0, off = 0;
     for (int s = 0; s < 8; s++) {
         const int32_t r = p.slot[s];
         if (r == kEmpty) continue;
-        occ |= 1u << s;
         cb[s] = tv.box(r);
-        box_grow(nb, cb[s]);
+        nb.grow(cb[s]);
         if (r >= 0) {
             imask |= 1u << s;
             const uint32_t at = inner0 + rank++;
@@ -557,20 +459,30 @@ __global__ __launch_bounds__(kThreads) void bvhd_write(TreeView tv, const Plan* 
             if (li < tv.n) order[li] = (uint32_t)keys[(uint32_t)~r];  // low word of the key: original triangle index
         }
     }
-    uint32_t wd[20];
-    quantise(nb, cb, occ, wd);
-    wd[3] |= imask << 24;
-    wd[4] = child_base;
-    wd[5] = tri_base;
-    wd[6] = leafmask;
-    wd[7] = 0;
+    uint32_t wd[kNodeWords];
+    quantise(nb, cb, imask | leafmask, wd);
+    node_set_topology(wd, imask, child_base, tri_base, leafmask);
     const uint32_t node = level_base + w;
     if (node >= node_cap) return;
-    uint4* dst = reinterpret_cast<uint4*>(nodes + (size_t)node * 20);
-    for (int i = 0; i < 5; i++) dst[i] = make_uint4(wd[4 * i], wd[4 * i + 1], wd[4 * i + 2], wd[4 * i + 3]);
+    uint4* dst = reinterpret_cast<uint4*>(node_at(nodes, node));
+    for (uint32_t i = 0; i < kNodeWords / 4; i++) dst[i] = make_uint4(wd[4 * i], wd[4 * i + 1], wd[4 * i + 2], wd[4 * i + 3]);
 }
 
 // ---- 8. leaf-order payload and the light list -----------------------------------------------------------------------------
+__device__ __forceinline__ void load_record(const float4* __restrict__ tris, uint32_t li, float r[kTriWords]) {
+    for (uint32_t i = 0; i < kTriWords / 4; i++) {
+        const float4 x = tris[(kTriWords / 4) * (size_t)li + i];
+        r[4 * i] = x.x;
+        r[4 * i + 1] = x.y;
+        r[4 * i + 2] = x.z;
+        r[4 * i + 3] = x.w;
+    }
+}
+
+__device__ __forceinline__ void store_record(float4* __restrict__ tris, uint32_t li, const float r[kTriWords]) {
+    for (uint32_t i = 0; i < kTriWords / 4; i++) tris[(kTriWords / 4) * (size_t)li + i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+}
+
 __global__ __launch_bounds__(kThreads) void bvhd_payload(const float* __restrict__ v, const float* __restrict__ albedo, const float* __restrict__ emission,
                                                          const uint32_t* __restrict__ order, uint32_t n, float4* __restrict__ tris,
                                                          float4* __restrict__ alb, float4* __restrict__ emi, uint32_t* __restrict__ leaf_pos,
@@ -588,10 +500,10 @@ __global__ __launch_bounds__(kThreads) void bvhd_payload(const float* __restrict
     }
     const float* em = emission + 3 * (size_t)t;
     const float* al = albedo + 3 * (size_t)t;
-    const uint32_t light = (em[0] > 0.0f || em[1] > 0.0f || em[2] > 0.0f) ? 1u : 0u;  // pack_leaf_range's word 10
-    tris[3 * (size_t)li] = make_float4(p[0], p[1], p[2], e1[0]);
-    tris[3 * (size_t)li + 1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
-    tris[3 * (size_t)li + 2] = make_float4(e2[2], __uint_as_float(t), __uint_as_float(light), 0.0f);
+    const uint32_t light = is_emissive(em) ? 1u : 0u;
+    float r[kTriWords];
+    pack_tri_record(p, e1, e2, t, light != 0u, r);
+    store_record(tris, li, r);
     alb[li] = make_float4(al[0], al[1], al[2], 0.0f);
     emi[li] = make_float4(em[0], em[1], em[2], 0.0f);
     light_flag[t] = light;
@@ -614,13 +526,14 @@ struct RefitTop {  // level j of the top = nodes [start[j], start[j + 1]), j < l
     uint32_t levels;
 };
 
-// triangle record of leaf position li: words 0-8 from the new vertices of triangle t = word 9 (edges formed in fp32 as in
-// bvhd_payload / set_mesh_impl), words 9-11 (index, light flag) kept.  Coalesced record traffic, gathered vertex reads
+// triangle record of leaf position li: packed again from the new vertices of its triangle t = word 9 (edges formed in fp32 as in
+// bvhd_payload / set_mesh_impl), index and light flag as they were.  Coalesced record traffic, gathered vertex reads
 __global__ __launch_bounds__(kThreads) void bvhr_tris(const float* __restrict__ v, uint32_t n, float4* __restrict__ tris) {
     const uint32_t li = blockIdx.x * kThreads + threadIdx.x;
     if (li >= n) return;
-    const float4 w2 = tris[3 * (size_t)li + 2];
-    const uint32_t t = __float_as_uint(w2.y);
+    const float4 last = tris[(kTriWords / 4) * (size_t)li + kTriIdWord / 4];
+    const uint32_t t = __float_as_uint(last.y), light = __float_as_uint(last.z);
+    static_assert(kTriIdWord % 4 == 1 && kTriLightWord == kTriIdWord + 1, "index and light flag are .y and .z of the record's last float4");
     if (t >= n) return;
     const float* p = v + 9 * (size_t)t;
     float x[9];
@@ -630,52 +543,45 @@ __global__ __launch_bounds__(kThreads) void bvhr_tris(const float* __restrict__ 
         e1[a] = x[3 + a] - x[a];
         e2[a] = x[6 + a] - x[a];
     }
-    tris[3 * (size_t)li] = make_float4(x[0], x[1], x[2], e1[0]);
-    tris[3 * (size_t)li + 1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
-    tris[3 * (size_t)li + 2] = make_float4(e2[2], w2.y, w2.z, w2.w);
+    float r[kTriWords];
+    pack_tri_record(x, e1, e2, t, light != 0u, r);
+    store_record(tris, li, r);
 }
 
-// padded box of the triangle at leaf position li, from its record: tri_box's expression (v0 + e1 = p0 + (p1 - p0))
-__device__ __forceinline__ DBox record_box(const float4* __restrict__ tris, uint32_t li, float pad) {
-    const float4 r0 = tris[3 * (size_t)li], r1 = tris[3 * (size_t)li + 1], r2 = tris[3 * (size_t)li + 2];
-    const float v0[3] = {r0.x, r0.y, r0.z}, e1[3] = {r0.w, r1.x, r1.y}, e2[3] = {r1.z, r1.w, r2.x};
-    DBox b;
-    for (int a = 0; a < 3; a++) {
-        const float p0 = v0[a], p1 = p0 + e1[a], p2 = p0 + e2[a];
-        b.lo[a] = fminf(p0, fminf(p1, p2)) - pad;
-        b.hi[a] = fmaxf(p0, fmaxf(p1, p2)) + pad;
-    }
-    return b;
+// padded box of the triangle at leaf position li, from its record
+__device__ __forceinline__ Box record_box(const float4* __restrict__ tris, uint32_t li, float pad) {
+    float r[kTriWords];
+    load_record(tris, li, r);
+    return tri_box(r, r + 3, r + 6, pad);
 }
 
 // node k: every slot's exact box (a leaf slot's padded triangle box, an inner slot's box as its child stored it one level deeper),
 // their union, the quantised frame and planes (words 0-3 with imask kept, words 8-19; words 4-7 untouched) and the node's exact
 // box for its parent.  Indices come from the node's own words and are checked before they are used
 __device__ __forceinline__ void refit_node(uint32_t* __restrict__ nodes, const float4* __restrict__ tris, uint32_t n, uint32_t n_nodes, float pad,
-                                           DBox* __restrict__ box, uint32_t k) {
-    uint4* nd = reinterpret_cast<uint4*>(nodes + (size_t)k * 20);
-    const uint32_t w3 = nd[0].w;
-    const uint4 topo = nd[1];  // child_base, tri_base, leafmask, 0
-    const uint32_t imask = w3 >> 24, leafmask = topo.z & 0xffu & ~imask;
-    DBox cb[8], nb;
-    box_empty(nb);
+                                           Box* __restrict__ box, uint32_t k) {
+    uint4* nd = reinterpret_cast<uint4*>(node_at(nodes, k));
+    const uint4 h0 = nd[0], h1 = nd[1];
+    uint32_t wd[kNodeWords] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+    const uint32_t imask = node_imask(wd), leafmask = node_leafmask(wd) & ~imask, child_base = node_child_base(wd), tri_base = node_tri_base(wd);
+    Box cb[8], nb = Box::empty();
     uint32_t rank = 0, off = 0;
     for (int s = 0; s < 8; s++) {
-        box_empty(cb[s]);
+        cb[s] = Box::empty();
         if ((imask >> s) & 1u) {
-            const uint32_t ch = topo.x + rank++;
+            const uint32_t ch = child_base + rank++;
             if (ch < n_nodes) cb[s] = box[ch];
         } else if ((leafmask >> s) & 1u) {
-            const uint32_t li = topo.y + off++;
+            const uint32_t li = tri_base + off++;
             if (li < n) cb[s] = record_box(tris, li, pad);
         } else {
             continue;
         }
-        box_grow(nb, cb[s]);
+        nb.grow(cb[s]);
     }
-    uint32_t wd[20];
     quantise(nb, cb, imask | leafmask, wd);
-    nd[0] = make_uint4(wd[0], wd[1], wd[2], wd[3] | (w3 & 0xff000000u));
+    node_set_topology(wd, imask, child_base, tri_base, leafmask);  // quantise() cleared the imask; words 4-7 are not stored
+    nd[0] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
     nd[2] = make_uint4(wd[8], wd[9], wd[10], wd[11]);
     nd[3] = make_uint4(wd[12], wd[13], wd[14], wd[15]);
     nd[4] = make_uint4(wd[16], wd[17], wd[18], wd[19]);
@@ -684,14 +590,14 @@ __device__ __forceinline__ void refit_node(uint32_t* __restrict__ nodes, const f
 
 // one level [k0, k1), one thread per node; the level below was finished by the previous launch
 __global__ __launch_bounds__(kThreads) void bvhr_level(uint32_t* __restrict__ nodes, const float4* __restrict__ tris, uint32_t n, uint32_t n_nodes,
-                                                       float pad, DBox* __restrict__ box, uint32_t k0, uint32_t k1) {
+                                                       float pad, Box* __restrict__ box, uint32_t k0, uint32_t k1) {
     const uint32_t k = k0 + blockIdx.x * kThreads + threadIdx.x;
     if (k < k1 && k < n_nodes) refit_node(nodes, tris, n, n_nodes, pad, box, k);
 }
 
 // the top levels, deepest first, by one workgroup (a barrier between levels, no other workgroup involved)
 __global__ __launch_bounds__(kRefitTopThreads) void bvhr_top(uint32_t* __restrict__ nodes, const float4* __restrict__ tris, uint32_t n, uint32_t n_nodes,
-                                                             float pad, DBox* __restrict__ box, RefitTop top) {
+                                                             float pad, Box* __restrict__ box, RefitTop top) {
     for (int j = (int)top.levels - 1; j >= 0; j--) {
         const uint32_t k1 = min(top.start[j + 1], n_nodes);
         for (uint32_t k = top.start[j] + threadIdx.x; k < k1; k += kRefitTopThreads) refit_node(nodes, tris, n, n_nodes, pad, box, k);
@@ -726,8 +632,8 @@ struct Scratch {
     unsigned long long* total;
     int2* child;
     uint2* range;
-    DBox* ibox;
-    DBox* tree;
+    Box* ibox;
+    Box* tree;
     int32_t* level[2];
     Plan* plan;
     unsigned long long* counts;
@@ -755,14 +661,14 @@ void carve(Bump& b, Scratch& s, size_t n) {
     s.total = b.take<unsigned long long>(1);
     s.child = b.take<int2>(m);
     s.range = b.take<uint2>(m);
-    s.ibox = b.take<DBox>(m);
-    s.tree = b.take<DBox>(2 * n);
+    s.ibox = b.take<Box>(m);
+    s.tree = b.take<Box>(2 * n);
     s.level[0] = b.take<int32_t>(m);
     s.level[1] = b.take<int32_t>(m);
     s.plan = b.take<Plan>(m);
     s.counts = b.take<unsigned long long>(m);
     s.excl = b.take<unsigned long long>(m);
-    s.nodes = b.take<uint32_t>(20 * m);
+    s.nodes = b.take<uint32_t>(kNodeWords * m);
     s.order = b.take<uint32_t>(n);
     s.leaf_pos = b.take<uint32_t>(n);
     s.flag = b.take<uint32_t>(n);
@@ -869,7 +775,7 @@ int build(Ctx* c, const float* verts, const float* albedo, const float* emission
             hipLaunchKernelGGL(bvhd_box_level, dim3(blocks_for(k1 - k0)), dim3(kThreads), 0, c->stream, s.tree, k0, k1);
         }
         if (j >= 0) hipLaunchKernelGGL(bvhd_box_top, dim3(1), dim3(kThreads), 0, c->stream, s.tree, n, j);
-        hipLaunchKernelGGL(bvhd_inner_boxes, dim3(blocks_for(n - 1)), dim3(kThreads), 0, c->stream, (const DBox*)s.tree, (const uint2*)s.range, n, s.ibox);
+        hipLaunchKernelGGL(bvhd_inner_boxes, dim3(blocks_for(n - 1)), dim3(kThreads), 0, c->stream, (const Box*)s.tree, (const uint2*)s.range, n, s.ibox);
     }
     BVHD_LAUNCH(c);
 
@@ -902,11 +808,11 @@ int build(Ctx* c, const float* verts, const float* albedo, const float* emission
     out->stack_need = depth + 1;  // at most one pending sibling group per level (bvh_build.cpp)
 
     // 8. the mesh's own arrays
-    if (!dalloc(out->nodes, (size_t)out->n_nodes * 5) || !dalloc(out->tris, (size_t)n * 3) || !dalloc(out->albedo, n) || !dalloc(out->emission, n))
+    if (!dalloc(out->nodes, (size_t)out->n_nodes * (kNodeWords / 4)) || !dalloc(out->tris, (size_t)n * (kTriWords / 4)) || !dalloc(out->albedo, n) || !dalloc(out->emission, n))
         return c->fail(RT_ERR_OOM, "mesh of %u triangles", n);
     out->cap_nodes = out->n_nodes;
     float4 *nodes = out->nodes.get(), *tris = out->tris.get(), *alb = out->albedo.get(), *emi = out->emission.get();
-    RT_HIP(c, hipMemcpyAsync(nodes, s.nodes, (size_t)out->n_nodes * 80, hipMemcpyDeviceToDevice, c->stream));
+    RT_HIP(c, hipMemcpyAsync(nodes, s.nodes, (size_t)out->n_nodes * kNodeWords * 4, hipMemcpyDeviceToDevice, c->stream));
     hipLaunchKernelGGL(bvhd_payload, dim3(blocks_for(n)), dim3(kThreads), 0, c->stream, verts, albedo, emission, (const uint32_t*)s.order, n, tris, alb, emi,
                        s.leaf_pos, s.flag);
     BVHD_LAUNCH(c);
@@ -931,7 +837,7 @@ size_t refit_scratch_bytes(uint32_t n_nodes) {
     Bump b;
     b.take<float>(kReduceBlocks);
     b.take<uint32_t>(kReduceBlocks);
-    b.take<DBox>(n_nodes);
+    b.take<Box>(n_nodes);
     return b.used;
 }
 
@@ -972,7 +878,7 @@ int refit_write(Ctx* c, const float* verts, uint32_t n, float pad, uint32_t n_no
     Bump bump{static_cast<char*>(scratch), 0};
     (void)bump.take<float>(kReduceBlocks);
     (void)bump.take<uint32_t>(kReduceBlocks);
-    DBox* box = bump.take<DBox>(n_nodes);
+    Box* box = bump.take<Box>(n_nodes);
     uint32_t* words = reinterpret_cast<uint32_t*>(nodes);
     hipLaunchKernelGGL(bvhr_tris, dim3(blocks_for(n)), dim3(kThreads), 0, c->stream, verts, n, tris);
     RefitTop top{};

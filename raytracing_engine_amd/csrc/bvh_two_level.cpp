@@ -7,22 +7,20 @@
 // (Round 2 cut the centroids' Morton order into equal runs: those chunk boxes overlap, a shadow ray entered 20 % more
 // nodes and traversal was 16-21 % slower than on the single SAH tree; profiles/r02_two_level_bvh.txt.)
 //
-// The two levels are FLATTENED into the one node array the traversal kernels read (layout: bvh_build.h): a top-level
+// The two levels are FLATTENED into the one node array the traversal kernels read (layout: bvh_node.h): a top-level
 // leaf (= a chunk) becomes an inner child slot whose node is the chunk's root, bottom-level nodes are copied with their
 // child / triangle bases relocated.  Frames cannot differ from the single-level build's (results do not depend on the
 // tree); what differs is build cost structure: rebuild_chunk() redoes one chunk's binned-SAH build
 // (1/chunks of the triangles), the top level over the chunk boxes and the flatten copy.
-#include <sched.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <system_error>
-#include <thread>
 
 #include "bvh_build.h"
+#include "bvh_node.h"
+#include "host_parallel.h"
 
 namespace rt {
 namespace {
@@ -30,36 +28,11 @@ namespace {
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
-int host_cpus() {
-    cpu_set_t set;
-    int hw = 1;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) hw = std::max(1, std::min(CPU_COUNT(&set), 32));
-    return hw;
-}
-
-// fn(t) for t in [0, parts) on up to `parts` threads; a thread that cannot be created runs on the caller
-template <typename F>
-void run_parts(uint32_t parts, F fn) {
-    std::vector<std::thread> pool;
-    uint32_t started = 1;
-    for (uint32_t t = 1; t < parts; t++) {
-        try {
-            pool.emplace_back(fn, t);
-            started++;
-        } catch (const std::system_error&) {
-            break;
-        }
-    }
-    fn(0u);
-    for (auto& th : pool) th.join();
-    for (uint32_t t = started; t < parts; t++) fn(t);
-}
-
 // One binned-SAH split of order[first, first + count) (16 bins per axis over the centroid bounds, cost = half-area x
 // count on either side): partitions the range and returns the size of the left part (1 .. count - 1).  Box unions,
 // counts and minima are order independent, so the result does not depend on the number of threads.
 constexpr int kCutBins = 16;
-uint32_t sah_split(std::vector<uint32_t>& order, uint32_t first, uint32_t count, const std::vector<float>& tb /* 6 per triangle */,
+uint32_t sah_split(std::vector<uint32_t>& order, uint32_t first, uint32_t count, const std::vector<Box>& tb /* unpadded, per triangle */,
                    const std::vector<float>& cen, int threads) {
     const uint32_t parts = count >= (1u << 16) ? (uint32_t)std::max(1, threads) : 1u;
     const uint32_t slice = (count + parts - 1) / parts;
@@ -69,7 +42,8 @@ uint32_t sah_split(std::vector<uint32_t>& order, uint32_t first, uint32_t count,
         uint32_t cnt[3][kCutBins];
     };
     std::vector<Acc> acc(parts);
-    run_parts(parts, [&](uint32_t t) {
+    parallel_for(parts, (int)parts, 1, [&](size_t part) {
+        const uint32_t t = (uint32_t)part;
         Acc& A = acc[t];
         for (int a = 0; a < 3; a++) {
             A.clo[a] = INFINITY;
@@ -98,7 +72,8 @@ uint32_t sah_split(std::vector<uint32_t>& order, uint32_t first, uint32_t count,
         const int b = (int)((cen[3 * (size_t)tri + a] - clo[a]) * kk[a]);
         return std::min(std::max(b, 0), kCutBins - 1);
     };
-    run_parts(parts, [&](uint32_t t) {
+    parallel_for(parts, (int)parts, 1, [&](size_t part) {
+        const uint32_t t = (uint32_t)part;
         Acc& A = acc[t];
         for (int a = 0; a < 3; a++)
             for (int b = 0; b < kCutBins; b++) {
@@ -111,14 +86,14 @@ uint32_t sah_split(std::vector<uint32_t>& order, uint32_t first, uint32_t count,
         const uint32_t i1 = std::min(count, (t + 1) * slice);
         for (uint32_t i = t * slice; i < i1; i++) {
             const uint32_t tri = order[first + i];
-            const float* bx = &tb[6 * (size_t)tri];
+            const Box& bx = tb[tri];
             for (int a = 0; a < 3; a++) {
                 if (!(kk[a] > 0.0f)) continue;
                 const int b = bin_of(tri, a);
                 A.cnt[a][b]++;
                 for (int k = 0; k < 3; k++) {
-                    A.lo[a][b][k] = std::min(A.lo[a][b][k], bx[k]);
-                    A.hi[a][b][k] = std::max(A.hi[a][b][k], bx[3 + k]);
+                    A.lo[a][b][k] = std::min(A.lo[a][b][k], bx.lo[k]);
+                    A.hi[a][b][k] = std::max(A.hi[a][b][k], bx.hi[k]);
                 }
             }
         }
@@ -199,16 +174,14 @@ uint32_t sah_split(std::vector<uint32_t>& order, uint32_t first, uint32_t count,
 }
 
 // conservative world-space box of a built BVH = the root node's quantisation frame [p, p + 255 * scale]
-void root_box(const BvhResult& b, float lo[3], float hi[3]) {
+Box root_box(const BvhResult& b) {
     const uint32_t* w = b.nodes.data();
+    Box r;
     for (int a = 0; a < 3; a++) {
-        float p, s;
-        std::memcpy(&p, &w[a], 4);
-        const uint32_t bits = ((w[3] >> (8 * a)) & 0xffu) << 23;
-        std::memcpy(&s, &bits, 4);
-        lo[a] = p;
-        hi[a] = p + 255.0f * s;
+        r.lo[a] = node_origin(w, a);
+        r.hi[a] = r.lo[a] + 255.0f * node_scale(w, a);
     }
+    return r;
 }
 
 bool build_one_chunk(const float* v0, const float* e1, const float* e2, const TwoLevelBvh& tl, uint32_t c, uint32_t max_depth, int max_threads, BvhResult* out) {
@@ -233,13 +206,12 @@ bool assemble(TwoLevelBvh* tl, uint32_t n, uint32_t max_depth, BvhResult* out) {
     // a chunk enters the top-level builder as a degenerate "triangle" whose bounding box is the chunk's box
     std::vector<float> bv0(3 * (size_t)chunks), be1(3 * (size_t)chunks), be2(3 * (size_t)chunks, 0.0f);
     for (uint32_t c = 0; c < chunks; c++) {
-        float lo[3], hi[3];
-        root_box(tl->blas[c], lo, hi);
+        const Box rb = root_box(tl->blas[c]);
         for (int a = 0; a < 3; a++) {
-            bv0[3 * (size_t)c + a] = lo[a];
-            // v0 + e1 must not fall short of hi after rounding
-            float e = hi[a] - lo[a];
-            while (lo[a] + e < hi[a]) e = std::nextafter(e, std::numeric_limits<float>::infinity());
+            bv0[3 * (size_t)c + a] = rb.lo[a];
+            // v0 + e1 must not fall short of hi after rounding (tri_box forms the corner as v0 + e1)
+            float e = rb.hi[a] - rb.lo[a];
+            while (rb.lo[a] + e < rb.hi[a]) e = std::nextafter(e, std::numeric_limits<float>::infinity());
             be1[3 * (size_t)c + a] = e;
         }
     }
@@ -267,12 +239,11 @@ bool assemble(TwoLevelBvh* tl, uint32_t n, uint32_t max_depth, BvhResult* out) {
             continue;
         }
         depth = std::max(depth, level[g]);
-        const uint32_t* w = &top.nodes[(size_t)place[g].index * 20];
-        const uint32_t imask = w[3] >> 24, leafmask = w[6] & 0xffu;
+        const uint32_t* w = node_at(top.nodes.data(), place[g].index);
         top_child_base[place[g].index] = (uint32_t)place.size();
         for (uint32_t s = 0; s < 8; s++) {
-            if ((imask >> s) & 1u) place.push_back(Item{0u, w[4] + (uint32_t)__builtin_popcount(imask & ((1u << s) - 1u))});
-            else if ((leafmask >> s) & 1u) place.push_back(Item{1u, top.order[w[5] + (uint32_t)__builtin_popcount(leafmask & ((1u << s) - 1u))]});
+            if ((node_imask(w) >> s) & 1u) place.push_back(Item{0u, node_inner_child(w, s)});
+            else if ((node_leafmask(w) >> s) & 1u) place.push_back(Item{1u, top.order[node_leaf_tri(w, s)]});
             else continue;
             level.push_back(level[g] + 1u);
         }
@@ -286,27 +257,22 @@ bool assemble(TwoLevelBvh* tl, uint32_t n, uint32_t max_depth, BvhResult* out) {
         n_tris += (uint32_t)tl->blas[c].order.size();
     }
     if (n_tris != n) return false;
-    out->nodes.assign((size_t)n_nodes * 20, 0u);
+    out->nodes.assign((size_t)n_nodes * kNodeWords, 0u);
     out->order.resize(n);
     auto copy_blas_node = [&](uint32_t c, uint32_t local, uint32_t global) {
-        const uint32_t* src = &tl->blas[c].nodes[(size_t)local * 20];
-        uint32_t* dst = &out->nodes[(size_t)global * 20];
-        std::memcpy(dst, src, 80);
-        dst[4] = rest_base[c] + src[4] - 1u;  // local child indices are >= 1 (the root is local node 0)
-        dst[5] = tri_off[c] + src[5];
+        const uint32_t* src = node_at(tl->blas[c].nodes.data(), local);
+        uint32_t* dst = node_at(out->nodes.data(), global);
+        std::memcpy(dst, src, kNodeWords * 4);
+        // local child indices are >= 1 (the root is local node 0)
+        node_relocate(dst, rest_base[c] + node_child_base(src) - 1u, tri_off[c] + node_tri_base(src));
     };
     for (size_t g = 0; g < place.size(); g++) {
         if (place[g].is_root) {
             copy_blas_node(place[g].index, 0u, (uint32_t)g);
         } else {
-            const uint32_t* src = &top.nodes[(size_t)place[g].index * 20];
-            uint32_t* dst = &out->nodes[g * 20];
-            std::memcpy(dst, src, 80);
-            const uint32_t imask = src[3] >> 24, leafmask = src[6] & 0xffu;
-            dst[3] = (src[3] & 0x00ffffffu) | ((imask | leafmask) << 24);  // chunk roots are inner children
-            dst[4] = top_child_base[place[g].index];
-            dst[5] = 0u;
-            dst[6] = 0u;
+            uint32_t* dst = node_at(out->nodes.data(), g);
+            std::memcpy(dst, node_at(top.nodes.data(), place[g].index), kNodeWords * 4);
+            node_leaves_to_inner(dst, top_child_base[place[g].index]);  // chunk roots are inner children
         }
     }
     for (uint32_t c = 0; c < chunks; c++) {
@@ -330,20 +296,22 @@ bool build_bvh_two_level(const float* v0, const float* e1, const float* e2, uint
     if (!v0 || !e1 || !e2 || !tl || !out || n == 0 || chunks == 0) return false;
     chunks = std::min(chunks, std::max(1u, n / 4u));  // on average at least four triangles per chunk
     auto t_cut = Clock::now();
-    std::vector<float> cen(3 * (size_t)n), tb(6 * (size_t)n);
-    const uint32_t pre_parts = n >= (1u << 16) ? (uint32_t)host_cpus() : 1u;
+    std::vector<float> cen(3 * (size_t)n);
+    std::vector<Box> tb(n);
+    const int cpus = host_threads();
+    const uint32_t pre_parts = n >= (1u << 16) ? (uint32_t)cpus : 1u;
     std::vector<float> part_max(pre_parts, 0.0f);
-    run_parts(pre_parts, [&](uint32_t w) {
-        const uint32_t slice = (n + pre_parts - 1) / pre_parts, i1 = std::min(n, (w + 1) * slice);
+    parallel_for(pre_parts, (int)pre_parts, 1, [&](size_t part) {
+        const uint32_t w = (uint32_t)part, slice = (n + pre_parts - 1) / pre_parts, i1 = std::min(n, (w + 1) * slice);
         float m = 0.0f;
-        for (uint32_t i = w * slice; i < i1; i++)
+        for (uint32_t i = w * slice; i < i1; i++) {
             for (int a = 0; a < 3; a++) {
                 const float p0 = v0[3 * (size_t)i + a], p1 = p0 + e1[3 * (size_t)i + a], p2 = p0 + e2[3 * (size_t)i + a];
                 cen[3 * (size_t)i + a] = p0 + (e1[3 * (size_t)i + a] + e2[3 * (size_t)i + a]) * (1.0f / 3.0f);
-                tb[6 * (size_t)i + a] = std::min(p0, std::min(p1, p2));
-                tb[6 * (size_t)i + 3 + a] = std::max(p0, std::max(p1, p2));
                 m = std::max(m, std::max(std::fabs(p0), std::max(std::fabs(p1), std::fabs(p2))));
             }
+            tb[i] = tri_box(&v0[3 * (size_t)i], &e1[3 * (size_t)i], &e2[3 * (size_t)i], 0.0f);  // the cut bins unpadded boxes
+        }
         part_max[w] = m;
     });
     float maxabs = 0.0f;
@@ -354,7 +322,6 @@ bool build_bvh_two_level(const float* v0, const float* e1, const float* e2, uint
     tl->sorted.resize(n);
     for (uint32_t i = 0; i < n; i++) tl->sorted[i] = i;
     std::vector<uint32_t> bounds{0u, n};  // leaf k = [bounds[k], bounds[k + 1])
-    const int cpus = host_cpus();
     while (bounds.size() - 1 < chunks) {
         const size_t leaves = bounds.size() - 1;
         std::vector<size_t> pick(leaves);
@@ -368,7 +335,7 @@ bool build_bvh_two_level(const float* v0, const float* e1, const float* e2, uint
         // few big leaves: one after the other, each binned by all threads; many leaves: side by side, one thread each
         const uint32_t side = (uint32_t)std::min<size_t>(take, (size_t)cpus);
         const int inner = std::max(1, cpus / (int)side);
-        run_parts(side, [&](uint32_t w) {
+        parallel_for(side, (int)side, 1, [&](size_t w) {
             for (size_t j = w; j < take; j += side) {
                 const uint32_t first = bounds[pick[j]], count = bounds[pick[j] + 1] - first;
                 mids[j] = first + sah_split(tl->sorted, first, count, tb, cen, inner);
@@ -381,8 +348,8 @@ bool build_bvh_two_level(const float* v0, const float* e1, const float* e2, uint
     tl->first = bounds;
     {  // a chunk lists its triangles in ascending index
         const uint32_t side = (uint32_t)std::min<uint32_t>(chunks, (uint32_t)cpus);
-        run_parts(side, [&](uint32_t w) {
-            for (uint32_t c = w; c < chunks; c += side) std::sort(tl->sorted.begin() + tl->first[c], tl->sorted.begin() + tl->first[c + 1]);
+        parallel_for(side, (int)side, 1, [&](size_t w) {
+            for (uint32_t c = (uint32_t)w; c < chunks; c += side) std::sort(tl->sorted.begin() + tl->first[c], tl->sorted.begin() + tl->first[c + 1]);
         });
     }
     tl->maxabs = std::max(maxabs, 1.0f);
@@ -393,29 +360,16 @@ bool build_bvh_two_level(const float* v0, const float* e1, const float* e2, uint
     tl->blas.assign(chunks, BvhResult{});
     std::vector<char> ok(chunks, 0);
     {  // chunks side by side, each built by one thread (its result does not depend on threads anyway)
-        const uint32_t workers = std::min<uint32_t>((uint32_t)host_cpus(), chunks);
-        std::vector<std::thread> pool;
-        auto run = [&](uint32_t w) {
-            for (uint32_t c = w; c < chunks; c += workers) {
+        const uint32_t workers = std::min<uint32_t>((uint32_t)cpus, chunks);
+        parallel_for(workers, (int)workers, 1, [&](size_t w) {
+            for (uint32_t c = (uint32_t)w; c < chunks; c += workers) {
                 try {
                     ok[c] = build_one_chunk(v0, e1, e2, *tl, c, max_depth, 1, &tl->blas[c]) ? 1 : 0;
                 } catch (...) {
                     ok[c] = 0;
                 }
             }
-        };
-        uint32_t started = 1;
-        for (uint32_t w = 1; w < workers; w++) {
-            try {
-                pool.emplace_back(run, w);
-                started++;
-            } catch (const std::system_error&) {
-                break;
-            }
-        }
-        run(0);
-        for (auto& th : pool) th.join();
-        for (uint32_t w = started; w < workers; w++) run(w);  // workers whose thread could not be created
+        });
     }
     for (uint32_t c = 0; c < chunks; c++)
         if (!ok[c]) return false;

@@ -16,7 +16,7 @@
 //   pt_trace<any>     shadow rays: any-hit traversal, unoccluded contributions added to the path
 //   pt_resolve        per pixel: samples summed in index order, divided by spp
 // Memory: path state is SoA of float4 (16 B per lane per array = widest coalesced access), BVH nodes
-// are 80-byte quantised records (bvh_build.h), triangles 48-byte records in leaf order.
+// are 80-byte quantised records (bvh_node.h), triangles 48-byte records in leaf order.
 #include "rt_device_math.h"
 #include "rt_internal.h"
 
@@ -186,7 +186,7 @@ struct TravCounters {
 // A traversal work item (Ylitie et al. 2017): either a node group  x = child_base,
 // y = hit bits of inner children in 31..24 (bit 24 + (slot ^ oct_inv): front to back) | the parent's imask in 7..0;
 // or a triangle group  x = tri_base, y = hit leaf slots in 7..0 | the node's leafmask in 15..8
-// (the triangle of leaf slot s is tri_base + popcount(leafmask below s), bvh_build.h).
+// (the triangle of leaf slot s is tri_base + popcount(leafmask below s), bvh_node.h).
 struct Group {
     uint32_t x, y;
 };

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bvh_build.h"
+#include "bvh_node.h"
 #include "mesh_registry.h"
 #include "rt_internal.h"
 
@@ -58,24 +59,14 @@ void publish_mesh_stats(PtData& pt) {
     s.ms_build_flatten = tl ? (float)tl->ms_flatten : 0.0f;
 }
 
-bool is_emissive(const float* emission, size_t t) { return emission[3 * t] > 0.0f || emission[3 * t + 1] > 0.0f || emission[3 * t + 2] > 0.0f; }
-
 // leaf-order records [li0, li1) of the device triangle / material arrays from the host copies; surf (may be NULL = all Lambert):
 // albedo.w per original triangle
 void pack_leaf_range(const rt::BvhResult& bvh, const float* v0, const float* e1, const float* e2, const float* albedo, const float* emission,
                      const float* surf, size_t li0, size_t li1, float* tris, float* alb, float* emi) {
     for (size_t li = li0; li < li1; li++) {
         const uint32_t t = bvh.order[li];
-        float* r = &tris[12 * (li - li0)];
-        r[0] = v0[3 * (size_t)t]; r[1] = v0[3 * (size_t)t + 1]; r[2] = v0[3 * (size_t)t + 2]; r[3] = e1[3 * (size_t)t];
-        r[4] = e1[3 * (size_t)t + 1]; r[5] = e1[3 * (size_t)t + 2]; r[6] = e2[3 * (size_t)t]; r[7] = e2[3 * (size_t)t + 1];
-        r[8] = e2[3 * (size_t)t + 2];
-        std::memcpy(&r[9], &t, 4);
-        // word 10: 1 = emissive.  pt_shade reads the record anyway (normal) and skips the 16-byte emission gather for the
-        // triangles that are not lights - all but a handful
-        const uint32_t is_light = is_emissive(emission, t) ? 1u : 0u;
-        std::memcpy(&r[10], &is_light, 4);
-        r[11] = 0.0f;
+        rt::pack_tri_record(&v0[3 * (size_t)t], &e1[3 * (size_t)t], &e2[3 * (size_t)t], t, rt::is_emissive(&emission[3 * (size_t)t]),
+                            &tris[rt::kTriWords * (li - li0)]);
         for (int a = 0; a < 3; a++) {
             alb[4 * (li - li0) + a] = albedo[3 * (size_t)t + a];
             emi[4 * (li - li0) + a] = emission[3 * (size_t)t + a];
@@ -93,7 +84,7 @@ std::vector<uint32_t> level_starts(const std::vector<uint32_t>& nodes, uint32_t 
     while (count) {
         if ((uint64_t)first + count > n_nodes) return {};
         uint64_t next = 0;
-        for (uint32_t k = first; k < first + count; k++) next += (uint32_t)__builtin_popcount(nodes[(size_t)k * 20 + 3] >> 24);
+        for (uint32_t k = first; k < first + count; k++) next += rt::node_inner_count(rt::node_at(nodes.data(), k));
         first += count;
         start.push_back(first);
         if (next > n_nodes) return {};
@@ -215,13 +206,13 @@ int build_mesh_host(Ctx* c, const float* verts, const float* albedo, const float
     m->build_ms = ms_since(t0);
 
     // leaf-order triangle records + materials; lights in ascending original index
-    std::vector<float> tris(12 * n), alb(4 * n), emi(4 * n);
+    std::vector<float> tris(rt::kTriWords * n), alb(4 * n), emi(4 * n);
     pack_leaf_range(bvh, v0.data(), e1.data(), e2.data(), albedo, emission, nullptr, 0, n, tris.data(), alb.data(), emi.data());
     std::vector<uint32_t> leaf_pos(n);
     for (size_t li = 0; li < n; li++) leaf_pos[bvh.order[li]] = (uint32_t)li;
     std::vector<uint32_t> lights, light_ids;
     for (size_t t = 0; t < n; t++)
-        if (is_emissive(emission, t)) {
+        if (rt::is_emissive(&emission[3 * t])) {
             lights.push_back(leaf_pos[t]);
             light_ids.push_back((uint32_t)t);
         }
@@ -353,7 +344,7 @@ int update_chunk_impl(Ctx* c, uint32_t chunk, const float* verts, uint32_t n_tri
     std::vector<float> tris, alb, emi;
     std::vector<uint32_t> leaf_of;
     try {
-        tris.resize(12 * (size_t)count);
+        tris.resize(rt::kTriWords * (size_t)count);
         alb.resize(4 * (size_t)count);
         emi.resize(4 * (size_t)count);
         pack_leaf_range(bvh, h.v0.data(), h.e1.data(), h.e2.data(), h.albedo.data(), h.emission.data(), h.surf.empty() ? nullptr : h.surf.data(), li0, li1,
@@ -528,9 +519,10 @@ int read_bvh_impl(Ctx* c, uint32_t* nodes_out, uint32_t node_capacity, uint32_t*
     if (int rc = rt::bind(c)) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
     if (nodes_out) RT_HIP(c, hipMemcpy(nodes_out, m.nodes.get(), (size_t)m.n_nodes * 80, hipMemcpyDeviceToHost));
-    // leaf order = word 9 of every 48-byte triangle record (the original index), whichever builder made the mesh
+    // leaf order = the original index in every triangle record, whichever builder made the mesh
     if (leaf_tris_out)
-        RT_HIP(c, hipMemcpy2D(leaf_tris_out, 4, reinterpret_cast<const char*>(m.tris.get()) + 36, 48, 4, m.n_tris, hipMemcpyDeviceToHost));
+        RT_HIP(c, hipMemcpy2D(leaf_tris_out, 4, reinterpret_cast<const char*>(m.tris.get()) + rt::kTriIdWord * 4, rt::kTriWords * 4, 4, m.n_tris,
+                              hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

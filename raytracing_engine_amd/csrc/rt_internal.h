@@ -146,7 +146,7 @@ enum {
 };
 
 struct PtScene {
-    const float4* nodes;     // 5 x float4 (80 B) per compressed 8-wide BVH node (bvh_build.h layout)
+    const float4* nodes;     // 5 x float4 (80 B) per compressed 8-wide BVH node (bvh_node.h layout)
     const float4* tris;      // 3 x float4 per triangle, leaf order: v0.xyz e1.x | e1.yz e2.xy | e2.z id emissive-flag -
     const float4* albedo;    // leaf order
     const float4* emission;  // leaf order
@@ -225,7 +225,7 @@ bool dalloc(DevPtr<T>& p, size_t count) {  // frees what p held first; false: ou
 // mesh hold the same record and treat it as read-only; whoever writes into it makes sure first that it is the only holder (detach_mesh,
 // DESIGN.md §6.12).  A context's frame-slot lanes read it through a plain pointer.
 struct DeviceMesh {
-    DevPtr<float4> nodes;     // cap_nodes x 80 B of which n_nodes are used, bvh_build.h layout
+    DevPtr<float4> nodes;     // cap_nodes x 80 B of which n_nodes are used, bvh_node.h layout
     DevPtr<float4> tris;      // leaf order, 48 B per triangle (PtScene::tris)
     DevPtr<float4> albedo;    // leaf order
     DevPtr<float4> emission;  // leaf order

@@ -1,4 +1,4 @@
-// bvh8_walk.cpp — TEST-ONLY host-side walk of the compressed 8-wide BVH (layout: csrc/bvh_build.h), written
+// bvh8_walk.cpp — TEST-ONLY host-side walk of the compressed 8-wide BVH (layout: csrc/bvh_node.h), written
 // from the layout and the traversal rules of DESIGN.md section 6.3 / 6.7 with scalar per-child code.  It
 // builds the tree with the product's own builder (csrc/bvh_build.cpp, deterministic) from the same
 // triangles, traces the same rays and writes, per ray, how many nodes it fetched and how many

@@ -47,7 +47,7 @@ def check_pt_dev(r, mesh, w, h, rot=(0, 0, 0, 1), pos=(0, 0, 0), **kw):
 
 
 def check_bvh(r, verts):
-    """Structural invariants of the current tree (layout: raytracing_engine_amd/csrc/bvh_build.h); returns its depth."""
+    """Structural invariants of the current tree (layout: raytracing_engine_amd/csrc/bvh_node.h); returns its depth."""
     f32 = np.float32
     verts = np.ascontiguousarray(verts, f32).reshape(-1, 9)
     n = len(verts)
