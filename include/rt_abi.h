@@ -382,7 +382,42 @@ int rt_render_pt_device(rt_ctx* ctx, const float rot[4], const float pos[3], con
 /* Path B frame into a frames-in-flight slot (see rt_frame_submit). */
 int rt_frame_submit_pt(rt_ctx* ctx, uint32_t slot, const float rot[4], const float pos[3], const rt_pt_params* params);
 int rt_get_pt_stats(rt_ctx* ctx, rt_pt_stats* stats);
-/* Test hook: trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
+/* Ray queries on device arrays: what does each of n caller-supplied rays hit in the current mesh?  Enqueued on the
+ * context's stream behind the work already there; no host synchronisation, and no allocation after the first query of a mesh or
+ * size class.  origins_dev / dirs_dev: n x 3 f32, tmax_dev: n f32 or NULL, all device memory of the context's device, only read.
+ * A triangle is hit when 0 < t < tmax[i] (strict; without tmax_dev the limit is +inf for closest hit and 0.999 for any hit, the
+ * path tracer's shadow segment).  any_hit = 0: t_out_dev[i] = distance along dirs[i] (in units of its length), tri_out_dev[i] =
+ * original triangle index (i32) of the closest hit, ties to the lower index; a miss is RT_RAY_MISS and +inf.  any_hit = 1:
+ * tri_out_dev[i] = 1 if something is hit, else 0; t_out_dev may be NULL and is not written.  A ray with a non-finite origin or
+ * direction component, a NaN tmax, or an origin component beyond 32 x max(1, largest |vertex coordinate| of the mesh) - the range
+ * over which the BVH's box padding covers the rounding of the ray/box test, the one rt_render_pt enforces for the camera - is not
+ * traced: tri_out = RT_RAY_INVALID, t_out = NaN (closest hit), and it is counted in rt_ray_query_stats.invalid_rays.  tmax = +inf
+ * is valid; tmax <= 0 and a zero direction miss everything.  Nothing beyond element n - 1 of an output is written.  The caller
+ * keeps all arrays alive until the stream has passed the call; lifetime rules against rt_set_mesh* are rt_render_pt_device's.
+ * Works on every mesh (host-built single- and two-level, device-built, refitted, with surfaces); reads the mesh only, so a
+ * shared mesh stays shared.  Errors, all before anything is enqueued or written: RT_ERR_INVALID (a NULL, host or other-device
+ * pointer, an allocation shorter than n rows, n above 2^30, tune_refill_min above 64, tune_blocks_per_cu above 8, tune_lds_stack
+ * above 78), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch).  n == 0: RT_OK, nothing is done. */
+typedef struct rt_ray_query_params {
+    uint32_t any_hit;            /* 0 closest hit, 1 occlusion */
+    uint32_t tune_refill_min;    /* as rt_pt_params (0 = default) */
+    uint32_t tune_blocks_per_cu; /* as rt_pt_params */
+    uint32_t tune_lds_stack;     /* as rt_pt_params */
+    uint32_t tune_max_blocks;    /* cap on persistent workgroups, 0 = none (small batches through many refills; tests) */
+} rt_ray_query_params;
+typedef struct rt_ray_query_stats {
+    uint64_t rays, invalid_rays; /* the last query with n > 0: rays asked, rays refused as invalid */
+    uint32_t stack_overflow;     /* must be 0 */
+    uint32_t launches;           /* kernel launches of that query */
+    float ms;                    /* HIP-event time of its launch */
+} rt_ray_query_stats;
+#define RT_RAY_MISS (-1)
+#define RT_RAY_INVALID (-2)
+int rt_default_ray_query_params(rt_ray_query_params* p);
+int rt_query_rays_device(rt_ctx* ctx, const void* origins_dev, const void* dirs_dev, const void* tmax_dev /* may be NULL */,
+                         uint32_t n, const rt_ray_query_params* params /* NULL = defaults */, void* t_out_dev, void* tri_out_dev);
+int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats); /* synchronises the stream; the last query */
+/* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */
 int rt_trace_rays(rt_ctx* ctx, const float* origins, const float* dirs, uint32_t n, int any_hit, float* t_out, int32_t* tri_out);

@@ -92,6 +92,20 @@ class PtStats(C.Structure):  # rt_pt_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RayQueryParams(C.Structure):  # rt_ray_query_params
+    _fields_ = [("any_hit", C.c_uint32), ("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32),
+                ("tune_max_blocks", C.c_uint32)]
+
+
+class RayQueryStats(C.Structure):  # rt_ray_query_stats
+    _fields_ = [("rays", C.c_uint64), ("invalid_rays", C.c_uint64), ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+RAY_MISS, RAY_INVALID = -1, -2  # RT_RAY_MISS, RT_RAY_INVALID
+
 assert C.sizeof(MutableData) == 656 and C.sizeof(Material) == 32 and C.sizeof(Object) == 16 and C.sizeof(Light) == 32
 
 # every symbol include/rt_abi.h declares: name -> (restype, argtypes)
@@ -144,6 +158,9 @@ PROTOTYPES = {
     "rt_frame_submit_pt": (C.c_int, [_vp, C.c_uint32, _fp, _fp, C.POINTER(PtParams)]),
     "rt_frame_wait": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "rt_frame_poll": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_int)]),
+    "rt_default_ray_query_params": (C.c_int, [C.POINTER(RayQueryParams)]),
+    "rt_query_rays_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(RayQueryParams), _vp, _vp]),
+    "rt_get_ray_query_stats": (C.c_int, [_vp, C.POINTER(RayQueryStats)]),
     "rt_trace_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32)]),
     "rt_trace_rays_counted": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32), _u32p]),
 }

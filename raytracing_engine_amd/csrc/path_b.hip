@@ -15,6 +15,7 @@
 //                     prefix-popcount compaction (one atomic per 1024-thread workgroup)
 //   pt_trace<any>     shadow rays: any-hit traversal, unoccluded contributions added to the path
 //   pt_resolve        per pixel: samples summed in index order, divided by spp
+//   pt_query_rays     rt_query_rays_device: the refilling loop of pt_trace on caller-supplied rays in device arrays (section 6.13)
 // Memory: path state is SoA of float4 (16 B per lane per array = widest coalesced access), BVH nodes
 // are 80-byte quantised records (bvh_node.h), triangles 48-byte records in leaf order.
 #include "rt_device_math.h"
@@ -306,8 +307,10 @@ __device__ __forceinline__ void build_perm_lut(uint8_t* lut) {
 
 // Test the next pending triangle of triangle group T.  is_any: what a hit means to this lane's ray - a compile-time constant where a
 // kernel traces one kind of ray, a per-lane flag in the loop that carries both.  Returns true when an any-hit ray found an occluder.
+// any_tmax: where an any-hit ray's segment ends - the constant of the shadow rays in the render kernels, a per-ray value in a ray query.
 template <bool COUNT>
-__device__ __forceinline__ bool tri_step(const float4* __restrict__ tris, TRay& r, Hit& best, Group& T, TravCounters& tc, bool is_any) {
+__device__ __forceinline__ bool tri_step(const float4* __restrict__ tris, TRay& r, Hit& best, Group& T, TravCounters& tc, bool is_any,
+                                         float any_tmax = kShadowTmax) {
     const uint32_t bit = (uint32_t)__builtin_ctz(T.y);  // lowest pending leaf slot (caller checked has_tris)
     T.y &= T.y - 1u;
     const uint32_t li = T.x + (uint32_t)__builtin_popcount((T.y >> 8) & ~(0xffffffffu << bit));  // rank of the slot among the node's leaves
@@ -316,7 +319,7 @@ __device__ __forceinline__ bool tri_step(const float4* __restrict__ tris, TRay& 
     if (COUNT) tc.tris++;
     float t;
     if (tri_test_flat(r.o, r.d, mk(a.x, a.y, a.z), mk(a.w, b.x, b.y), mk(b.z, b.w, c.x), t) && t > 0.0f) {
-        if (is_any) return t < kShadowTmax;
+        if (is_any) return t < any_tmax;
         const uint32_t id = __float_as_uint(c.y);
         if (t < best.t || (t == best.t && id < best.id)) {
             best.t = t;
@@ -348,7 +351,7 @@ __device__ __forceinline__ void start_ray(bool is_any, v3 o, v3 d, TRay& r, Hit&
 // register, with an and + compare wherever a branch needs it as a lane mask)
 template <bool COUNT, bool UNORDERED>
 __device__ __forceinline__ bool inline_round(const PtScene& sc, const uint8_t* perm_lut, TRay& r, Hit& best, Group& G, Group& T, TravStack& stk, TravCounters& tc,
-                                             bool alive, bool& occluded, bool is_any, int tris_per_round) {
+                                             bool alive, bool& occluded, bool is_any, int tris_per_round, float any_tmax = kShadowTmax) {
     // node phase
     if (alive && !has_tris(T)) {
         if (!has_nodes(G)) {
@@ -361,7 +364,7 @@ __device__ __forceinline__ bool inline_round(const PtScene& sc, const uint8_t* p
 #pragma unroll 1
     for (int it = 0; it < tris_per_round; it++) {
         if (alive && has_tris(T)) {
-            if (tri_step<COUNT>(sc.tris, r, best, T, tc, is_any)) {
+            if (tri_step<COUNT>(sc.tris, r, best, T, tc, is_any, any_tmax)) {
                 occluded = true;
                 alive = false;
             }
@@ -1775,6 +1778,91 @@ __global__ __launch_bounds__(256) void pt_trace_rays(const PtScene sc, const flo
     }
 }
 
+// ---- ray queries on device arrays (rt_query_rays_device) -----------------------
+// The persistent refilling loop of trace_queue_inline with another source and sink: the queue is implicit (entry i is ray i of the
+// caller's arrays), a retiring lane writes the caller's answer arrays.  Every ray is traced by start_ray / inline_round - node_step
+// and tri_step inside - exactly as in the render kernels and in the hook, so the answers are theirs bit for bit.  Differences:
+//   - a per-ray distance limit: r.tmax starts at it (boxes beyond it are culled from the start; a triangle inside a conservative
+//     box may still be tested and accepted beyond it, which only moves r.tmax to that hit's t - never below min(limit, best.t), so no
+//     hit nearer than the limit is lost) and the comparison at retire is the strict one: a closest hit at t >= limit is a miss;
+//   - validity is decided when the lane loads the ray: an invalid ray is answered on the spot and the lane stays idle.  A refill may
+//     therefore hand out 64 entries and leave no lane alive, and with few workgroups a stream may have no wave that started on it: a
+//     wave leaves only when it has found the last stream dry AND holds no live ray (the rule of RAYS_BOTH, not of the one-kind loops).
+template <bool ANY>
+__global__ __launch_bounds__(256, kInlineWaves) void pt_query_rays(const PtScene sc, const RayQuery q, uint32_t* __restrict__ head,
+                                                                   unsigned long long* __restrict__ stats, const StackCfg sk, uint32_t refill_min) {
+    extern __shared__ unsigned long long lds_stack[];  // sk.lds_cap x 256 entries
+    __shared__ uint8_t perm_lut[2048];
+    build_perm_lut(perm_lut);
+    TravStack stk = make_trav_stack(lds_stack, sk);
+
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const int tris_per_round = tris_per_round_of(refill_min);
+    refill_min &= 0xffu;
+    TravCounters tc{0, 0, 0};
+    TRay r = make_tray(mk(0.0f, 0.0f, 0.0f), mk(0.0f, 1.0f, 0.0f), 0.0f);
+    Hit best{0.0f, -1, 0u};
+    Group G{0u, 0u}, T{0u, 0u};
+    uint32_t ray = 0;      // index of this lane's ray
+    float limit = 0.0f;    // its distance limit
+    uint32_t invalid = 0;  // invalid rays this lane has met
+    bool has_ray = false, occluded = false, alive = false;
+    QueueCursor cur{q.n, head, home_stream(), 0u};
+    bool exhausted = cur.n == 0u;  // every stream has been found dry
+
+    for (;;) {
+        const unsigned long long idle = __ballot(!alive);
+        if (idle == ~0ull || (!exhausted && (uint32_t)__popcll(idle) >= refill_min)) {
+            if (!alive && has_ray) {  // the sink
+                if (ANY) {
+                    q.tri_out[ray] = occluded ? 1 : 0;
+                } else {
+                    const bool hit = best.li >= 0 && best.t < limit;
+                    q.t_out[ray] = hit ? best.t : __builtin_inff();
+                    q.tri_out[ray] = hit ? (int)best.id : RT_RAY_MISS;
+                }
+                has_ray = false;
+            }
+            if (!exhausted) {  // exactly what the idle lanes need, assigned by ballot + prefix popcount
+                const uint32_t want = (uint32_t)__popcll(idle);
+                const uint32_t base = cur.reserve(want, lane);
+                const uint32_t i = !alive ? stream_entry(cur.stream, base + (uint32_t)__popcll(idle & lt_mask)) : cur.n;  // >= n: nothing for this lane
+                if (!alive && i < cur.n) {  // the source
+                    const float* po = q.origins + (size_t)i * 3u;
+                    const float* pd = q.dirs + (size_t)i * 3u;
+                    const v3 o = mk(po[0], po[1], po[2]), d = mk(pd[0], pd[1], pd[2]);
+                    limit = q.tmax ? q.tmax[i] : ANY ? kShadowTmax : __builtin_inff();
+                    // (comparisons that are false for a NaN; +-inf origins fail the range test)
+                    const bool in_reach = __builtin_fabsf(o.x) <= q.reach && __builtin_fabsf(o.y) <= q.reach && __builtin_fabsf(o.z) <= q.reach;
+                    const bool d_finite = __builtin_fabsf(d.x) < __builtin_inff() && __builtin_fabsf(d.y) < __builtin_inff() && __builtin_fabsf(d.z) < __builtin_inff();
+                    if (!(in_reach && d_finite && limit == limit)) {  // not traced
+                        if (!ANY) q.t_out[i] = __builtin_nanf("");
+                        q.tri_out[i] = RT_RAY_INVALID;
+                        invalid++;
+                    } else if (!(limit > 0.0f)) {  // an empty interval: a miss without a walk
+                        if (!ANY) q.t_out[i] = __builtin_inff();
+                        q.tri_out[i] = ANY ? 0 : RT_RAY_MISS;
+                    } else {
+                        start_ray(ANY, o, d, r, best, G, T, stk);
+                        r.tmax = limit;
+                        ray = i;
+                        occluded = false;
+                        has_ray = true;
+                        alive = true;
+                    }
+                }
+                exhausted = cur.advance_if_dry(base + want);
+            }
+            if (__ballot(alive) == 0ull && exhausted) break;  // every answer of this wave is written (idle lanes retired above)
+        }
+        // (UNORDERED for any-hit rays, as in an all-shadow launch)
+        alive = inline_round<false, ANY>(sc, perm_lut, r, best, G, T, stk, tc, alive, occluded, ANY, tris_per_round, limit);
+    }
+    add_wave_total(&stats[RQ_STAT_INVALID], invalid, lane);
+    if (tc.overflow) atomicOr((unsigned int*)&stats[RQ_STAT_OVERFLOW], 1u);
+}
+
 // ---- surfaces (rt_set_mesh_surfaces, §6.11) -------------------------------------------------------
 // albedo.w of every leaf position from the surface words in original triangle order: word 9 of the triangle record names
 // the triangle, whichever builder wrote the records.  surf == nullptr: every triangle Lambert (0)
@@ -1893,6 +1981,17 @@ int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const 
     with_bool(counts != nullptr, [&](auto cnt) {
         hipLaunchKernelGGL(pt_trace_rays<decltype(cnt)::value>, dim3(grid), dim3(256), stack_lds_bytes(sk), c->stream, sc, origins, dirs, n, any_hit, t_out, tri_out,
                            counts, sk);
+    });
+    RT_HIP(c, hipGetLastError());
+    return RT_OK;
+}
+
+
+int launch_pt_query_rays(Ctx* c, const PtScene& sc, const RayQuery& q, bool any_hit, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                         const StackCfg& sk, uint32_t refill_min) {
+    if (!valid_stack_cfg(sk, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
+    with_bool(any_hit, [&](auto any) {
+        hipLaunchKernelGGL(pt_query_rays<decltype(any)::value>, dim3(grid), dim3(256), stack_lds_bytes(sk), c->stream, sc, q, head, stats, sk, refill_min);
     });
     RT_HIP(c, hipGetLastError());
     return RT_OK;

@@ -34,10 +34,32 @@ void pt_free_mesh(PtData& pt) {
     }
     pt.stats = rt_pt_stats{};
 }
+
+// a device allocation of `c`'s device that holds at least `bytes` bytes from p on
+int check_device_array(Ctx* c, const void* p, size_t bytes, const char* what) {
+    if (!p) return c->fail(RT_ERR_INVALID, "%s is NULL", what);
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return c->fail(RT_ERR_INVALID, "%s is not a device pointer", what);
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != c->device)
+        return c->fail(RT_ERR_INVALID, "%s is not device memory of device %d (memory type %d, device %d)", what, c->device, (int)a.type, a.device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return c->fail(RT_ERR_INVALID, "%s: allocation range unknown", what);
+    }
+    if (static_cast<const char*>(p) + bytes > static_cast<const char*>(base) + size)
+        return c->fail(RT_ERR_INVALID, "%s: the allocation holds fewer than the %zu bytes of %s", what, bytes, what);
+    return RT_OK;
+}
 }  // namespace rt
 
 namespace {
 
+using rt::check_device_array;
 using rt::pt_free_mesh;
 
 // The mesh part of rt_pt_stats, from the record (and the host side of a two-level mesh) the context renders
@@ -381,27 +403,6 @@ int update_chunk_impl(Ctx* c, uint32_t chunk, const float* verts, uint32_t n_tri
     set_tree_shape(m, bvh);
     m.build_ms = build_ms;
     publish_mesh_stats(pt);
-    return RT_OK;
-}
-
-// a device allocation of `c`'s device that holds at least `bytes` bytes from p on
-int check_device_array(Ctx* c, const void* p, size_t bytes, const char* what) {
-    if (!p) return c->fail(RT_ERR_INVALID, "%s is NULL", what);
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return c->fail(RT_ERR_INVALID, "%s is not a device pointer", what);
-    }
-    if (a.type != hipMemoryTypeDevice || a.device != c->device)
-        return c->fail(RT_ERR_INVALID, "%s is not device memory of device %d (memory type %d, device %d)", what, c->device, (int)a.type, a.device);
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
-        (void)hipGetLastError();
-        return c->fail(RT_ERR_INVALID, "%s: allocation range unknown", what);
-    }
-    if (static_cast<const char*>(p) + bytes > static_cast<const char*>(base) + size)
-        return c->fail(RT_ERR_INVALID, "%s: the allocation holds fewer than the %zu bytes of %s", what, bytes, what);
     return RT_OK;
 }
 

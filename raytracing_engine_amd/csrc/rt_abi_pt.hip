@@ -17,7 +17,9 @@ constexpr uint64_t kMaxPathsInFlight = 1ull << 25;  // 33.5 M paths = 4.3 GB of 
 constexpr uint32_t kMaxBounces = 15;
 constexpr uint32_t kDefaultPacketMode = rt::PACKET_INTERVAL_ONLY;
 constexpr uint32_t kDefaultTriMode = rt::TRI_MODE_INLINE;  // rt_pt_params.tune_tri_mode = 0
-constexpr float kCameraReach = 32.0f;  // camera |coordinate| limit in units of the mesh's largest |coordinate| (plan_frame)
+constexpr float kCameraReach = 32.0f;  // camera |coordinate| limit in units of the mesh's largest |coordinate| (plan_frame); ray-query origins too
+constexpr uint32_t kMaxQueryRays = 1u << 30;  // rt_query_rays_device: stream_entry() of a dry reservation stays below 2^32
+constexpr uint32_t kQueryRefillMin = 24;      // idle lanes per wave that trigger a refill in the query kernel (the render kernels' default)
 
 void free_wavefront(PtData& pt) {
     for (auto& mem : pt.wavefront) mem.reset();
@@ -410,12 +412,76 @@ int render_pt_common(Ctx* c, const float rot[4], const float pos[3], const rt_pt
     return sync ? read_frame_stats(c, tm, n) : RT_OK;
 }
 
+// rt_query_rays_device: everything that can refuse the call comes before the first enqueue
+int query_rays_impl(Ctx* c, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_ray_query_params* prm, void* t_out, void* tri_out) {
+    PtData& pt = c->pt;
+    rt_ray_query_params defaults{};
+    if (!prm) prm = &defaults;
+    const rt::DeviceMesh& mesh = pt.mesh();
+    if (!mesh.n_tris) return c->fail(RT_ERR_STATE, "rt_set_mesh has not been called");
+    if (n > kMaxQueryRays) return c->fail(RT_ERR_INVALID, "n %u is above 2^30", n);
+    if (prm->any_hit > 1u) return c->fail(RT_ERR_INVALID, "any_hit %u (0 or 1)", prm->any_hit);
+    if ((prm->tune_refill_min & 0xffu) > 64u || prm->tune_refill_min > 0xffffu) return c->fail(RT_ERR_INVALID, "tune_refill_min %u (low byte 0 .. 64)", prm->tune_refill_min);
+    if (prm->tune_blocks_per_cu > 8u) return c->fail(RT_ERR_INVALID, "tune_blocks_per_cu %u (0 .. 8)", prm->tune_blocks_per_cu);
+    if (prm->tune_lds_stack > 78u) return c->fail(RT_ERR_INVALID, "tune_lds_stack %u (0 .. 78)", prm->tune_lds_stack);
+    if (n == 0) return RT_OK;
+    if (int rc = rt::bind(c)) return rc;
+    const bool any_hit = prm->any_hit != 0u;
+    const size_t rows = n;
+    if (int rc = rt::check_device_array(c, origins, rows * 12, "origins_dev")) return rc;
+    if (int rc = rt::check_device_array(c, dirs, rows * 12, "dirs_dev")) return rc;
+    if (tmax)
+        if (int rc = rt::check_device_array(c, tmax, rows * 4, "tmax_dev")) return rc;
+    if (t_out || !any_hit)
+        if (int rc = rt::check_device_array(c, t_out, rows * 4, "t_out_dev")) return rc;
+    if (int rc = rt::check_device_array(c, tri_out, rows * 4, "tri_out_dev")) return rc;
+
+    if (!pt.d_query) {  // first query of this context
+        if (!dalloc(pt.d_query, rt::RQ_BLOCK_BYTES)) return c->fail(RT_ERR_OOM, "ray-query stream heads");
+        for (hipEvent_t& e : pt.ev_query)
+            if (!e) RT_HIP(c, hipEventCreate(&e));
+    }
+    rt::StackCfg sk{};
+    uint32_t grid = 0;
+    if (int rc = stack_config(c, prm->tune_lds_stack, prm->tune_blocks_per_cu, (uint64_t)n, &sk, &grid)) return rc;
+    grid = std::min<uint32_t>(grid, (n + 255u) / 256u);
+    if (prm->tune_max_blocks) grid = std::min<uint32_t>(grid, prm->tune_max_blocks);
+    const uint32_t refill_min = (prm->tune_refill_min & 0xffu ? prm->tune_refill_min & 0xffu : kQueryRefillMin) | (prm->tune_refill_min & 0xff00u);
+
+    rt::RayQuery q{};
+    q.origins = static_cast<const float*>(origins);
+    q.dirs = static_cast<const float*>(dirs);
+    q.tmax = static_cast<const float*>(tmax);
+    q.t_out = any_hit ? nullptr : static_cast<float*>(t_out);
+    q.tri_out = static_cast<int*>(tri_out);
+    q.n = n;
+    q.reach = kCameraReach * mesh.maxabs;
+    uint32_t* head = reinterpret_cast<uint32_t*>(pt.d_query.get());
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(pt.d_query.get() + (size_t)rt::RQ_HEAD_WORDS * 4);
+    rt::RoctxRange rr("rt.path_b.query_rays");
+    RT_HIP(c, hipMemsetAsync(pt.d_query.get(), 0, rt::RQ_BLOCK_BYTES, c->stream));
+    RT_HIP(c, hipEventRecord(pt.ev_query[0], c->stream));
+    if (int rc = rt::launch_pt_query_rays(c, scene_view(mesh), q, any_hit, head, stats, grid, sk, refill_min)) return rc;
+    RT_HIP(c, hipEventRecord(pt.ev_query[1], c->stream));
+    pt.query_stats = rt_ray_query_stats{};
+    pt.query_stats.rays = n;
+    pt.query_stats.launches = 1;
+    pt.query_pending = true;
+    return RT_OK;
+}
+
 }  // namespace
 
 namespace rt {
 void pt_free(Ctx* c) {
     free_wavefront(c->pt);
     pt_free_mesh(c->pt);
+    c->pt.d_query.reset();
+    for (hipEvent_t& e : c->pt.ev_query) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    c->pt.query_pending = false;
     c->pt.d_ctr.reset();
     c->pt.d_stats.reset();
     if (c->pt.ev_shaded) (void)hipEventDestroy(c->pt.ev_shaded);
@@ -469,6 +535,37 @@ int rt_get_pt_stats(rt_ctx* ctx, rt_pt_stats* stats) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !stats) return RT_ERR_INVALID;
     *stats = c->pt.stats;
+    return RT_OK;
+}
+
+int rt_default_ray_query_params(rt_ray_query_params* p) {
+    if (!p) return RT_ERR_INVALID;
+    *p = rt_ray_query_params{};
+    return RT_OK;
+}
+
+int rt_query_rays_device(rt_ctx* ctx, const void* origins_dev, const void* dirs_dev, const void* tmax_dev, uint32_t n, const rt_ray_query_params* params,
+                         void* t_out_dev, void* tri_out_dev) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    return query_rays_impl(c, origins_dev, dirs_dev, tmax_dev, n, params, t_out_dev, tri_out_dev);
+}
+
+int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    PtData& pt = c->pt;
+    if (pt.query_pending) {
+        if (int rc = rt::bind(c)) return rc;
+        RT_HIP(c, hipStreamSynchronize(c->stream));
+        unsigned long long st[rt::RQ_STAT_WORDS] = {};
+        RT_HIP(c, hipMemcpy(st, pt.d_query.get() + (size_t)rt::RQ_HEAD_WORDS * 4, sizeof st, hipMemcpyDeviceToHost));
+        pt.query_stats.invalid_rays = st[rt::RQ_STAT_INVALID];
+        pt.query_stats.stack_overflow = (uint32_t)st[rt::RQ_STAT_OVERFLOW];
+        RT_HIP(c, hipEventElapsedTime(&pt.query_stats.ms, pt.ev_query[0], pt.ev_query[1]));
+        pt.query_pending = false;
+    }
+    *stats = pt.query_stats;
     return RT_OK;
 }
 

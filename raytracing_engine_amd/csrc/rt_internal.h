@@ -193,6 +193,19 @@ struct PtFrame {
     float ray_eps;
 };
 
+// rt_query_rays_device: the rays of one query and where their answers go.  Ray i is queue entry i.
+struct RayQuery {
+    const float* origins;  // n x 3
+    const float* dirs;     // n x 3
+    const float* tmax;     // n, or nullptr: +inf (closest hit) / 0.999 (any hit)
+    float* t_out;          // n, closest hit only
+    int* tri_out;          // n
+    uint32_t n;
+    float reach;  // |origin component| limit: kCameraReach x the mesh's maxabs
+};
+// The query's device block (PtData::d_query), cleared before every launch: the PT_HEADS stream heads, then two 64-bit counters
+enum { RQ_STAT_INVALID = 0, RQ_STAT_OVERFLOW = 1, RQ_STAT_WORDS = 2, RQ_HEAD_WORDS = PT_HEADS * PT_HEAD_STRIDE, RQ_BLOCK_BYTES = RQ_HEAD_WORDS * 4 + RQ_STAT_WORDS * 8 };
+
 struct MeshHost {  // host side of a two-level mesh: what rt_update_mesh_chunk needs to rebuild one chunk
     TwoLevelBvh tl;
     std::vector<float> v0, e1, e2;          // original triangle order
@@ -264,6 +277,11 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     DevPtr<uint32_t> d_ctr;
     DevPtr<unsigned long long> d_stats;  // PT_STAT_WORDS words
     rt_pt_stats stats{};
+    // rt_query_rays_device: stream heads + counters (RQ_BLOCK_BYTES), allocated by the first query, freed with the context
+    DevPtr<char> d_query;
+    hipEvent_t ev_query[2] = {nullptr, nullptr};
+    rt_ray_query_stats query_stats{};
+    bool query_pending = false;  // a query has been enqueued whose counters and time rt_get_ray_query_stats has not read yet
 };
 
 struct Ctx {
@@ -359,7 +377,12 @@ int launch_pt_scatter_surfaces(Ctx* c, const float4* tris, const float* surf, fl
 int launch_pt_resolve(Ctx* c, const PtFrame& f, const PtState& st, float* acc, float* dst, int tile_major);
 int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const float* dirs, uint32_t n, int any_hit, float* t_out,
                          int* tri_out, uint32_t* counts, const StackCfg& sk, uint32_t grid);
+// persistent refilling query kernel on c->stream; head / stats: the two parts of PtData::d_query, cleared by the caller
+int launch_pt_query_rays(Ctx* c, const PtScene& sc, const RayQuery& q, bool any_hit, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                         const StackCfg& sk, uint32_t refill_min);
 void pt_free(Ctx* c);
+// rt_abi_mesh.hip: RT_OK when p is a device allocation of c's device that holds at least `bytes` bytes from p on, else RT_ERR_INVALID
+int check_device_array(Ctx* c, const void* p, size_t bytes, const char* what);
 void comm_free(Ctx* c);  // rt_abi_comm.hip
 
 // bvh_build_gpu.hip: path B mesh built on the GPU from device-resident triangles (rt_set_mesh_device), on c->stream.

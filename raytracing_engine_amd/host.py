@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Config, Light, Material, MutableData, Object, PtParams, PtStats, RtError, Stats
+from ._lib import Config, Light, Material, MutableData, Object, PtParams, PtStats, RayQueryParams, RayQueryStats, RtError, Stats
 
 # src/main.rs:343-364
 SPEED_MOVEMENT = 25.0
@@ -437,8 +437,71 @@ class Renderer:
         self._check(self._lib.rt_get_pt_stats(self._ctx, C.byref(s)))
         return s.as_dict()
 
+    RAY_MISS, RAY_INVALID = _lib.RAY_MISS, _lib.RAY_INVALID
+
+    def _device_i32(self, t, name, n):
+        """`t` must be a contiguous int32 torch tensor of n elements on this renderer's device; ValueError otherwise."""
+        import torch
+
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device or t.dim() != 1 or t.numel() != n:
+            raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+    def query_rays(self, origins, dirs, tmax=None, any_hit=False, out=None, sync=True, **tune):
+        """What do rays hit in the current mesh?  (rt_query_rays_device)  origins, dirs: float32 torch tensors on this
+        renderer's device, contiguous, (n, 3) or flat; tmax: (n,) or None.  A triangle is hit when 0 < t < tmax (default: +inf for the
+        closest hit, 0.999 for any hit).  any_hit=False: returns (t, tri) - float32 distances in units of |dir| (+inf on a miss) and int32
+        original triangle indices (RAY_MISS = -1); any_hit=True: returns int32 flags (1 = something is hit).  Invalid rays (a non-finite
+        component, an origin beyond 32 x the mesh's largest |coordinate|) get RAY_INVALID = -2 and t = NaN.  out: the tensors to fill -
+        (t, tri) resp. the flag tensor - instead of new ones.  sync=True: work torch has queued on its current stream is finished first
+        and the answers are complete on return; sync=False does neither: for callers that handed torch's stream to set_stream().
+        tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_ray_query_params."""
+        import torch
+
+        n = self._device_rows(origins, "origins", 3)
+        if self._device_rows(dirs, "dirs", 3) != n:
+            raise ValueError("origins and dirs disagree on the ray count")
+        if tmax is not None and (self._device_rows(tmax, "tmax", 1) != n or tmax.dim() != 1):
+            raise ValueError(f"tmax must have shape ({n},), got {tuple(tmax.shape)}")
+        p = RayQueryParams()
+        p.any_hit = int(bool(any_hit))
+        for k, v in tune.items():
+            if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
+                raise TypeError(f"query_rays() got an unexpected keyword argument {k!r}")
+            setattr(p, k, int(v))
+        if any_hit:
+            t, tri = None, out
+        else:
+            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+                raise ValueError("out must be the pair (t, tri) for a closest-hit query")
+            t, tri = out if out is not None else (None, None)
+        dev = origins.device
+        if tri is None:
+            tri = torch.empty(n, dtype=torch.int32, device=dev)
+        else:
+            self._device_i32(tri, "out tri", n)
+        if not any_hit:
+            if t is None:
+                t = torch.empty(n, dtype=torch.float32, device=dev)
+            elif self._device_rows(t, "out t", 1) != n or t.dim() != 1:
+                raise ValueError(f"out t must have shape ({n},), got {tuple(t.shape)}")
+        if sync:
+            torch.cuda.current_stream(self.device).synchronize()  # writers on torch's stream are done before the query reads
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None  # noqa: E731
+        self._check(self._lib.rt_query_rays_device(self._ctx, ptr(origins), ptr(dirs), ptr(tmax), n, C.byref(p), ptr(t), ptr(tri)))
+        if sync:
+            self.synchronize()
+        return tri if any_hit else (t, tri)
+
+    def ray_query_stats(self):
+        """rt_ray_query_stats of the last query as a dict (waits for it): rays, invalid_rays, stack_overflow, launches, ms."""
+        s = RayQueryStats()
+        self._check(self._lib.rt_get_ray_query_stats(self._ctx, C.byref(s)))
+        return s.as_dict()
+
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
-        """Test hook: closest hit (t, original triangle index) or occlusion flags for a ray batch;
+        """Test hook (query_rays is the product entry): closest hit (t, original triangle index) or occlusion flags for a ray batch;
         counted=True also returns an (n, 2) array of BVH nodes fetched / triangles tested per ray."""
         origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
