@@ -417,6 +417,42 @@ int rt_default_ray_query_params(rt_ray_query_params* p);
 int rt_query_rays_device(rt_ctx* ctx, const void* origins_dev, const void* dirs_dev, const void* tmax_dev /* may be NULL */,
                          uint32_t n, const rt_ray_query_params* params /* NULL = defaults */, void* t_out_dev, void* tri_out_dev);
 int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats); /* synchronises the stream; the last query */
+/* Closest-point queries on device arrays: which triangle of the current mesh is nearest to each of n caller-supplied
+ * points, how far away is it, and where on it?  Enqueued on the context's stream behind the work already there; no host
+ * synchronisation, and no allocation after the first query of a mesh or size class.  points_dev: n x 3 f32, rmax_dev: n f32 or NULL,
+ * device memory of the context's device, only read.  The answer for point i is the lexicographic minimum of (d2, original triangle
+ * index) over all triangles with d2 < rmax[i] * rmax[i] (strict; the product is formed in fp32; without rmax_dev the limit is +inf),
+ * d2 = the fp32 squared distance of csrc/point_tri.h; the limited answer is the unlimited one if its d2 is below the limit, else a
+ * miss.  dist_out_dev[i] = sqrt(d2), correctly rounded; tri_out_dev[i] = the original triangle index (i32); point_out_dev (n x 3 f32,
+ * may be NULL) = the nearest point of that triangle.  A miss (nothing within the limit) is RT_POINT_MISS, +inf and three NaNs.
+ * rmax = +inf is valid; !(rmax > 0) misses without a walk, and so does an rmax so small that its square underflows to 0 (rmax below
+ * 2^-75, about 2.6e-23: no d2 is below 0).  A point with a non-finite component, a NaN rmax, or a component beyond 32 x max(1, largest
+ * |vertex coordinate| of the mesh) - the reach of rt_query_rays_device - is not answered: tri_out = RT_POINT_INVALID, dist_out = NaN,
+ * point_out = NaNs, and it is counted in rt_point_query_stats.invalid_points.  Nothing beyond element n - 1 of an output is written.
+ * The caller keeps all arrays alive until the stream has passed the call; lifetime rules against rt_set_mesh* are
+ * rt_render_pt_device's.  Works on every mesh (host-built single- and two-level, device-built, refitted, with surfaces); reads the
+ * mesh only, so a shared mesh stays shared.  Errors, all before anything is enqueued or written: RT_ERR_INVALID (a NULL context; a
+ * NULL, host or other-device pointer, an allocation shorter than n rows, n above 2^30, count_traversal above 1, tune_refill_min above
+ * 64, tune_blocks_per_cu above 8, tune_lds_stack above 78), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch).  n == 0: RT_OK, nothing is
+ * done. */
+typedef struct rt_point_query_params {
+    uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_ray_query_params */
+    uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
+} rt_point_query_params;
+typedef struct rt_point_query_stats {
+    uint64_t points, invalid_points;     /* the last query with n > 0: points asked, points refused as invalid */
+    uint64_t nodes_visited, tris_tested; /* count_traversal = 1 only: node records fetched, triangles tested, over all points */
+    uint32_t stack_overflow;             /* must be 0 */
+    uint32_t launches;                   /* kernel launches of that query */
+    float ms;                            /* HIP-event time of its launch */
+} rt_point_query_stats;
+#define RT_POINT_MISS RT_RAY_MISS
+#define RT_POINT_INVALID RT_RAY_INVALID
+int rt_default_point_query_params(rt_point_query_params* p);
+int rt_query_points_device(rt_ctx* ctx, const void* points_dev, const void* rmax_dev /* may be NULL */, uint32_t n,
+                           const rt_point_query_params* params /* NULL = defaults */, void* dist_out_dev, void* tri_out_dev,
+                           void* point_out_dev /* may be NULL */);
+int rt_get_point_query_stats(rt_ctx* ctx, rt_point_query_stats* stats); /* synchronises the stream; the last query */
 /* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */

@@ -470,6 +470,88 @@ int query_rays_impl(Ctx* c, const void* origins, const void* dirs, const void* t
     return RT_OK;
 }
 
+// The stack of the closest-point walk: point_stack_need entries per lane (one pending sibling each - not stack_need's one group per
+// level), the first lds_cap of them in LDS (tune_lds_stack, default ten: where the nearest-first order keeps most walks), the rest in
+// the context's spill columns, which grow to this need once per mesh
+int point_stack_config(Ctx* c, uint32_t tune_lds, uint32_t tune_blocks, uint64_t n_points, rt::StackCfg* sk, uint32_t* grid) {
+    PtData& pt = c->pt;
+    const uint32_t need = rt::point_stack_need(pt.mesh().depth);
+    const uint32_t lds_cap = std::min<uint32_t>(need, tune_lds ? std::min<uint32_t>(tune_lds, 78u) : 10u);
+    const uint32_t fit = std::max<uint32_t>(1u, std::min<uint32_t>(8u, (160u * 1024u) / (2048u * lds_cap)));  // 2 KiB per entry per workgroup
+    const uint32_t by_load = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(3, (n_points + (uint64_t)c->n_cus * 1024 - 1) / ((uint64_t)c->n_cus * 1024)));
+    const uint32_t blocks_per_cu = tune_blocks ? std::min<uint32_t>(tune_blocks, fit) : std::min(fit, by_load);
+    *grid = (uint32_t)c->n_cus * blocks_per_cu;
+    sk->lds_cap = (int)lds_cap;
+    sk->spill_cap = (int)(need - lds_cap);
+    sk->spill_stride = (size_t)c->n_cus * 8u * 256u;  // covers every grid this function can return
+    const size_t words = std::max<size_t>(1, (size_t)sk->spill_cap) * sk->spill_stride;
+    if (words > pt.spill_words) {
+        RT_HIP(c, hipStreamSynchronize(c->stream));
+        pt.spill_words = 0;
+        if (!dalloc(pt.d_spill, words)) return c->fail(RT_ERR_OOM, "traversal spill stack (%zu words)", words);
+        pt.spill_words = words;
+    }
+    sk->spill = pt.d_spill.get();
+    return RT_OK;
+}
+
+// rt_query_points_device: everything that can refuse the call comes before the first enqueue
+int query_points_impl(Ctx* c, const void* points, const void* rmax, uint32_t n, const rt_point_query_params* prm, void* dist_out, void* tri_out, void* point_out) {
+    PtData& pt = c->pt;
+    rt_point_query_params defaults{};
+    if (!prm) prm = &defaults;
+    const rt::DeviceMesh& mesh = pt.mesh();
+    if (!mesh.n_tris) return c->fail(RT_ERR_STATE, "rt_set_mesh has not been called");
+    if (n > kMaxQueryRays) return c->fail(RT_ERR_INVALID, "n %u is above 2^30", n);
+    if (prm->count_traversal > 1u) return c->fail(RT_ERR_INVALID, "count_traversal %u (0 or 1)", prm->count_traversal);
+    if ((prm->tune_refill_min & 0xffu) > 64u || prm->tune_refill_min > 0xffffu) return c->fail(RT_ERR_INVALID, "tune_refill_min %u (low byte 0 .. 64)", prm->tune_refill_min);
+    if (prm->tune_blocks_per_cu > 8u) return c->fail(RT_ERR_INVALID, "tune_blocks_per_cu %u (0 .. 8)", prm->tune_blocks_per_cu);
+    if (prm->tune_lds_stack > 78u) return c->fail(RT_ERR_INVALID, "tune_lds_stack %u (0 .. 78)", prm->tune_lds_stack);
+    if (n == 0) return RT_OK;
+    if (int rc = rt::bind(c)) return rc;
+    const size_t rows = n;
+    if (int rc = rt::check_device_array(c, points, rows * 12, "points_dev")) return rc;
+    if (rmax)
+        if (int rc = rt::check_device_array(c, rmax, rows * 4, "rmax_dev")) return rc;
+    if (int rc = rt::check_device_array(c, dist_out, rows * 4, "dist_out_dev")) return rc;
+    if (int rc = rt::check_device_array(c, tri_out, rows * 4, "tri_out_dev")) return rc;
+    if (point_out)
+        if (int rc = rt::check_device_array(c, point_out, rows * 12, "point_out_dev")) return rc;
+
+    if (!pt.d_pquery) {  // first closest-point query of this context
+        if (!dalloc(pt.d_pquery, rt::PQ_BLOCK_BYTES)) return c->fail(RT_ERR_OOM, "point-query stream heads");
+        for (hipEvent_t& e : pt.ev_pquery)
+            if (!e) RT_HIP(c, hipEventCreate(&e));
+    }
+    rt::StackCfg sk{};
+    uint32_t grid = 0;
+    if (int rc = point_stack_config(c, prm->tune_lds_stack, prm->tune_blocks_per_cu, (uint64_t)n, &sk, &grid)) return rc;
+    grid = std::min<uint32_t>(grid, (n + 255u) / 256u);
+    if (prm->tune_max_blocks) grid = std::min<uint32_t>(grid, prm->tune_max_blocks);
+    const uint32_t refill_min = prm->tune_refill_min & 0xffu ? prm->tune_refill_min & 0xffu : kQueryRefillMin;  // (byte 1, the ray kernels' triangle tests per round, has no meaning here)
+
+    rt::PointQuery q{};
+    q.points = static_cast<const float*>(points);
+    q.rmax = static_cast<const float*>(rmax);
+    q.dist_out = static_cast<float*>(dist_out);
+    q.tri_out = static_cast<int*>(tri_out);
+    q.point_out = static_cast<float*>(point_out);
+    q.n = n;
+    q.reach = kCameraReach * mesh.maxabs;
+    uint32_t* head = reinterpret_cast<uint32_t*>(pt.d_pquery.get());
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(pt.d_pquery.get() + (size_t)rt::RQ_HEAD_WORDS * 4);
+    rt::RoctxRange rr("rt.path_b.query_points");
+    RT_HIP(c, hipMemsetAsync(pt.d_pquery.get(), 0, rt::PQ_BLOCK_BYTES, c->stream));
+    RT_HIP(c, hipEventRecord(pt.ev_pquery[0], c->stream));
+    if (int rc = rt::launch_pt_query_points(c, scene_view(mesh), q, prm->count_traversal != 0u, head, stats, grid, sk, refill_min)) return rc;
+    RT_HIP(c, hipEventRecord(pt.ev_pquery[1], c->stream));
+    pt.pquery_stats = rt_point_query_stats{};
+    pt.pquery_stats.points = n;
+    pt.pquery_stats.launches = 1;
+    pt.pquery_pending = true;
+    return RT_OK;
+}
+
 }  // namespace
 
 namespace rt {
@@ -482,6 +564,12 @@ void pt_free(Ctx* c) {
         e = nullptr;
     }
     c->pt.query_pending = false;
+    c->pt.d_pquery.reset();
+    for (hipEvent_t& e : c->pt.ev_pquery) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    c->pt.pquery_pending = false;
     c->pt.d_ctr.reset();
     c->pt.d_stats.reset();
     if (c->pt.ev_shaded) (void)hipEventDestroy(c->pt.ev_shaded);
@@ -566,6 +654,39 @@ int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats) {
         pt.query_pending = false;
     }
     *stats = pt.query_stats;
+    return RT_OK;
+}
+
+int rt_default_point_query_params(rt_point_query_params* p) {
+    if (!p) return RT_ERR_INVALID;
+    *p = rt_point_query_params{};
+    return RT_OK;
+}
+
+int rt_query_points_device(rt_ctx* ctx, const void* points_dev, const void* rmax_dev, uint32_t n, const rt_point_query_params* params, void* dist_out_dev,
+                           void* tri_out_dev, void* point_out_dev) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    return query_points_impl(c, points_dev, rmax_dev, n, params, dist_out_dev, tri_out_dev, point_out_dev);
+}
+
+int rt_get_point_query_stats(rt_ctx* ctx, rt_point_query_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    PtData& pt = c->pt;
+    if (pt.pquery_pending) {
+        if (int rc = rt::bind(c)) return rc;
+        RT_HIP(c, hipStreamSynchronize(c->stream));
+        unsigned long long st[rt::PQ_STAT_WORDS] = {};
+        RT_HIP(c, hipMemcpy(st, pt.d_pquery.get() + (size_t)rt::RQ_HEAD_WORDS * 4, sizeof st, hipMemcpyDeviceToHost));
+        pt.pquery_stats.invalid_points = st[rt::PQ_STAT_INVALID];
+        pt.pquery_stats.stack_overflow = (uint32_t)st[rt::PQ_STAT_OVERFLOW];
+        pt.pquery_stats.nodes_visited = st[rt::PQ_STAT_NODES];
+        pt.pquery_stats.tris_tested = st[rt::PQ_STAT_TRIS];
+        RT_HIP(c, hipEventElapsedTime(&pt.pquery_stats.ms, pt.ev_pquery[0], pt.ev_pquery[1]));
+        pt.pquery_pending = false;
+    }
+    *stats = pt.pquery_stats;
     return RT_OK;
 }
 

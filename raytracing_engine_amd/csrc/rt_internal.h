@@ -206,6 +206,24 @@ struct RayQuery {
 // The query's device block (PtData::d_query), cleared before every launch: the PT_HEADS stream heads, then two 64-bit counters
 enum { RQ_STAT_INVALID = 0, RQ_STAT_OVERFLOW = 1, RQ_STAT_WORDS = 2, RQ_HEAD_WORDS = PT_HEADS * PT_HEAD_STRIDE, RQ_BLOCK_BYTES = RQ_HEAD_WORDS * 4 + RQ_STAT_WORDS * 8 };
 
+// rt_query_points_device: the points of one query and where their answers go.  Point i is queue entry i.
+struct PointQuery {
+    const float* points;  // n x 3
+    const float* rmax;    // n, or nullptr: +inf
+    float* dist_out;      // n
+    int* tri_out;         // n
+    float* point_out;     // n x 3, or nullptr
+    uint32_t n;
+    float reach;  // |component| limit: kCameraReach x the mesh's maxabs
+};
+// Its device block (PtData::d_pquery), a sibling of the ray query's, cleared before every launch: the PT_HEADS stream heads, then four 64-bit counters
+enum { PQ_STAT_INVALID = 0, PQ_STAT_OVERFLOW = 1, PQ_STAT_NODES = 2, PQ_STAT_TRIS = 3, PQ_STAT_WORDS = 4, PQ_BLOCK_BYTES = RQ_HEAD_WORDS * 4 + PQ_STAT_WORDS * 8 };
+// Stack entries the nearest-first walk of pt_query_points can hold at once in a tree of `depth` levels of 8-wide nodes (root = 1): an
+// entry is one pending sibling, a node visit descends into one inner child and pushes at most seven, and the entries of one level
+// on the stack are always children of one node (they lie above every entry of the levels before them and are popped first), so at
+// most seven for each of the levels 2 .. depth.
+constexpr uint32_t point_stack_need(uint32_t depth) { return depth > 1u ? 7u * (depth - 1u) : 1u; }
+
 struct MeshHost {  // host side of a two-level mesh: what rt_update_mesh_chunk needs to rebuild one chunk
     TwoLevelBvh tl;
     std::vector<float> v0, e1, e2;          // original triangle order
@@ -282,6 +300,11 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     hipEvent_t ev_query[2] = {nullptr, nullptr};
     rt_ray_query_stats query_stats{};
     bool query_pending = false;  // a query has been enqueued whose counters and time rt_get_ray_query_stats has not read yet
+    // rt_query_points_device: the same for closest-point queries (PQ_BLOCK_BYTES)
+    DevPtr<char> d_pquery;
+    hipEvent_t ev_pquery[2] = {nullptr, nullptr};
+    rt_point_query_stats pquery_stats{};
+    bool pquery_pending = false;
 };
 
 struct Ctx {
@@ -380,6 +403,9 @@ int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const 
 // persistent refilling query kernel on c->stream; head / stats: the two parts of PtData::d_query, cleared by the caller
 int launch_pt_query_rays(Ctx* c, const PtScene& sc, const RayQuery& q, bool any_hit, uint32_t* head, unsigned long long* stats, uint32_t grid,
                          const StackCfg& sk, uint32_t refill_min);
+// the closest-point kernel, launched like launch_pt_query_rays; head / stats: the two parts of PtData::d_pquery
+int launch_pt_query_points(Ctx* c, const PtScene& sc, const PointQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                           const StackCfg& sk, uint32_t refill_min);
 void pt_free(Ctx* c);
 // rt_abi_mesh.hip: RT_OK when p is a device allocation of c's device that holds at least `bytes` bytes from p on, else RT_ERR_INVALID
 int check_device_array(Ctx* c, const void* p, size_t bytes, const char* what);

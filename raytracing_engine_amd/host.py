@@ -8,7 +8,8 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Config, Light, Material, MutableData, Object, PtParams, PtStats, RayQueryParams, RayQueryStats, RtError, Stats
+from ._lib import (Config, Light, Material, MutableData, Object, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
+                   RtError, Stats)
 
 # src/main.rs:343-364
 SPEED_MOVEMENT = 25.0
@@ -498,6 +499,63 @@ class Renderer:
         """rt_ray_query_stats of the last query as a dict (waits for it): rays, invalid_rays, stack_overflow, launches, ms."""
         s = RayQueryStats()
         self._check(self._lib.rt_get_ray_query_stats(self._ctx, C.byref(s)))
+        return s.as_dict()
+
+    POINT_MISS, POINT_INVALID = _lib.POINT_MISS, _lib.POINT_INVALID
+
+    def query_points(self, points, rmax=None, out=None, sync=True, want_points=True, count_traversal=False, **tune):
+        """Which triangle of the current mesh is nearest to each point, how far is it, and where on it?  (rt_query_points_device,
+        DESIGN.md §6.14.)  points: a float32 torch tensor on this renderer's device, contiguous, (n, 3) or flat; rmax: (n,) or None - only
+        triangles nearer than rmax count (strictly; default +inf).  Returns (dist, tri, point): float32 distances (+inf on a miss), int32
+        original triangle indices (POINT_MISS = -1) and the (n, 3) nearest points (NaN on a miss), or None in their place with
+        want_points=False.  Invalid points (a non-finite component, a NaN rmax, a component beyond 32 x the mesh's largest |coordinate|)
+        get POINT_INVALID = -2 and NaNs.  out: the tensors to fill - (dist, tri, point), or (dist, tri) with want_points=False - instead of
+        new ones.  sync=True: work torch has queued on its current stream is finished first and the answers are complete on return;
+        sync=False does neither: for callers that handed torch's stream to set_stream().  count_traversal=True: point_query_stats()
+        reports nodes_visited / tris_tested.  tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of
+        rt_point_query_params."""
+        import torch
+
+        n = self._device_rows(points, "points", 3)
+        if rmax is not None and (self._device_rows(rmax, "rmax", 1) != n or rmax.dim() != 1):
+            raise ValueError(f"rmax must have shape ({n},), got {tuple(rmax.shape)}")
+        p = PointQueryParams()
+        p.count_traversal = int(bool(count_traversal))
+        for k, v in tune.items():
+            if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
+                raise TypeError(f"query_points() got an unexpected keyword argument {k!r}")
+            setattr(p, k, int(v))
+        want = 3 if want_points else 2
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != want):
+            raise ValueError("out must be (dist, tri, point), or the pair (dist, tri) with want_points=False")
+        dist, tri, pt = (tuple(out) + (None,))[:3] if out is not None else (None, None, None)
+        dev = points.device
+        if dist is None:
+            dist = torch.empty(n, dtype=torch.float32, device=dev)
+        elif self._device_rows(dist, "out dist", 1) != n or dist.dim() != 1:
+            raise ValueError(f"out dist must have shape ({n},), got {tuple(dist.shape)}")
+        if tri is None:
+            tri = torch.empty(n, dtype=torch.int32, device=dev)
+        else:
+            self._device_i32(tri, "out tri", n)
+        if want_points:
+            if pt is None:
+                pt = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            elif self._device_rows(pt, "out point", 3) != n:
+                raise ValueError(f"out point must hold {n} rows of 3")
+        if sync:
+            torch.cuda.current_stream(self.device).synchronize()  # writers on torch's stream are done before the query reads
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None  # noqa: E731
+        self._check(self._lib.rt_query_points_device(self._ctx, ptr(points), ptr(rmax), n, C.byref(p), ptr(dist), ptr(tri), ptr(pt)))
+        if sync:
+            self.synchronize()
+        return dist, tri, pt
+
+    def point_query_stats(self):
+        """rt_point_query_stats of the last closest-point query as a dict (waits for it): points, invalid_points, nodes_visited,
+        tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
+        s = PointQueryStats()
+        self._check(self._lib.rt_get_point_query_stats(self._ctx, C.byref(s)))
         return s.as_dict()
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
