@@ -1,5 +1,6 @@
-// rt_abi_pt.hip — C-ABI entry points of path B's frames (wavefront path tracer over a triangle mesh + BVH) and the host-side
-// stage schedule.  No reference counterpart (include/rt_abi.h, "Path B").  The mesh's lifetime is in rt_abi_mesh.hip.
+// rt_abi_pt.hip — C-ABI entry points of path B's frames (wavefront path tracer over a triangle mesh + BVH), the host-side
+// stage schedule and the rt_trace_rays test hook.  No reference counterpart (include/rt_abi.h, "Path B").  The mesh's lifetime is
+// in rt_abi_mesh.hip, the queries on device arrays in rt_abi_query.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -9,7 +10,9 @@
 #include "rt_roctx.h"
 
 using rt::Ctx;
+using rt::kCameraReach;
 using rt::PtData;
+using rt::scene_view;
 
 namespace {
 
@@ -17,10 +20,6 @@ constexpr uint64_t kMaxPathsInFlight = 1ull << 25;  // 33.5 M paths = 4.3 GB of 
 constexpr uint32_t kMaxBounces = 15;
 constexpr uint32_t kDefaultPacketMode = rt::PACKET_INTERVAL_ONLY;
 constexpr uint32_t kDefaultTriMode = rt::TRI_MODE_INLINE;  // rt_pt_params.tune_tri_mode = 0
-constexpr float kCameraReach = 32.0f;  // camera |coordinate| limit in units of the mesh's largest |coordinate| (plan_frame); ray-query origins too
-constexpr uint32_t kMaxQueryRays = 1u << 30;  // rt_query_rays_device: stream_entry() of a dry reservation stays below 2^32
-constexpr uint32_t kQueryRefillMin = 24;      // idle lanes per wave that trigger a refill in the query kernel (the render kernels' default)
-
 void free_wavefront(PtData& pt) {
     for (auto& mem : pt.wavefront) mem.reset();
     pt.st = rt::PtState{};
@@ -56,51 +55,6 @@ int ensure_wavefront(Ctx* c, uint64_t n_paths, uint64_t n_slots) {
         pt.cap_slots = n_slots;
     }
     return RT_OK;
-}
-
-// Traversal stack + persistent grid.  The first lds_cap entries of every lane's stack live in LDS
-// (8-byte entries: 2 x lds_cap KiB per 256-thread workgroup, next to the kernel's 2 KiB octant table), which bounds residency at floor(160 KiB / that) workgroups
-// per CU, 8 at most (32 waves per CU); the rest of the builder's worst case spills to global memory.
-int stack_config(Ctx* c, uint32_t tune_lds, uint32_t tune_blocks, uint64_t n_paths, rt::StackCfg* sk, uint32_t* grid, uint32_t extra_lds_bytes = 0) {
-    PtData& pt = c->pt;
-    const uint32_t need = std::max<uint32_t>(pt.mesh().stack_need, 1u);
-    // default: up to ten entries in LDS - the whole stack of the 1 M-triangle tree (depth 9) - at seven workgroups per CU
-    // (measured 1 % ahead of eight entries at eight workgroups)
-    const uint32_t lds_cap = std::min<uint32_t>(need, tune_lds ? std::min<uint32_t>(tune_lds, 78u) : 10u);
-    const uint32_t fit = std::max<uint32_t>(1u, std::min<uint32_t>(8u, (160u * 1024u) / (2048u * lds_cap + 2048u + extra_lds_bytes)));  // 2 KiB per entry per workgroup + the 2 KiB octant table (+ the triangle pools)
-    // Few paths (a rank's small share of a frame): fewer resident waves.  Every lane of the grid takes a ray
-    // at once, so with ~2 rays per lane the rays in flight span half the frame instead of a compact window
-    // and the short launches are all ramp and tail; about four rays per lane and more measured best
-    // (1/8 of the headline frame: 2.87 -> 2.62 ms with 4 instead of 8 workgroups per CU).
-    const uint32_t by_load = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(3, (n_paths + (uint64_t)c->n_cus * 1024 - 1) / ((uint64_t)c->n_cus * 1024)));
-    const uint32_t blocks_per_cu = tune_blocks ? std::min<uint32_t>(tune_blocks, fit) : std::min(fit, by_load);
-    *grid = (uint32_t)c->n_cus * blocks_per_cu;
-    sk->lds_cap = (int)lds_cap;
-    sk->spill_cap = (int)(need - lds_cap);
-    sk->spill_stride = (size_t)c->n_cus * 8u * 256u;  // covers every grid this function can return
-    const size_t half = std::max<size_t>(1, (size_t)sk->spill_cap) * sk->spill_stride;
-    const size_t words = 2 * half;  // second half: the shadow kernel when it overlaps the next closest-hit kernel
-    if (words > pt.spill_words) {
-        RT_HIP(c, hipStreamSynchronize(c->stream));
-        pt.spill_words = 0;
-        if (!dalloc(pt.d_spill, words)) return c->fail(RT_ERR_OOM, "traversal spill stack (%zu words)", words);
-        pt.spill_words = words;
-    }
-    sk->spill = pt.d_spill.get();
-    pt.spill_half = half;
-    return RT_OK;
-}
-
-rt::PtScene scene_view(const rt::DeviceMesh& m) {
-    rt::PtScene s{};
-    s.nodes = m.nodes.get();
-    s.tris = m.tris.get();
-    s.albedo = m.albedo.get();
-    s.emission = m.emission.get();
-    s.lights = m.lights.get();
-    s.n_lights = m.n_lights;
-    s.n_tris = m.n_tris;
-    return s;
 }
 
 // The stages of a frame that per-stage timing tells apart, and where each one's time goes
@@ -152,6 +106,7 @@ struct FramePlan {  // what a frame's launches have in common: rt_pt_params deco
     uint32_t packet_mode = 0;
     uint32_t tri_mode = 0, tri_cfg = 0, refill_min = 0, sort_rays = 0;
     rt::StackCfg stack{};
+    size_t spill_half = 0;  // two-stream mode: where the shadow kernel's spill columns begin
     uint32_t grid_persistent = 0, grid_stride = 0;
     bool fused = false, overlap = false;  // how shadow(d) and closest(d + 1) share the machine (plan_frame)
 };
@@ -198,8 +153,11 @@ int plan_frame(Ctx* c, const float rot[4], const float pos[3], const rt_pt_param
     // low byte: idle lanes that trigger a refill (24; 8 with the software-pipelined refill, whose refill is a read from LDS); next byte (tuning): inner steps per round
     p->refill_min = (prm->tune_refill_min & 0xffu ? std::min<uint32_t>(prm->tune_refill_min & 0xffu, 64u) : p->tri_mode == rt::TRI_MODE_INLINE_PF ? 8u : 24u) |
                     (prm->tune_refill_min & 0xff00u);
-    if (int rc = stack_config(c, prm->tune_lds_stack, prm->tune_blocks_per_cu, p->n_slots * p->spp_batch, &p->stack, &p->grid_persistent, rt::pt_pool_lds_bytes(p->tri_mode)))
+    // (two halves of spill columns: the second for the shadow kernel when it overlaps the next closest-hit kernel)
+    if (int rc = rt::pt_stack_config(c, mesh.stack_need, 2048u + rt::pt_pool_lds_bytes(p->tri_mode), 2u, prm->tune_lds_stack, prm->tune_blocks_per_cu,
+                                     p->n_slots * p->spp_batch, &p->stack, &p->grid_persistent))
         return rc;
+    p->spill_half = rt::spill_half_words(p->stack);
     p->grid_stride = (uint32_t)c->n_cus * 2u;  // 1024-thread workgroups, grid-stride
     // camera rays through the packet kernel, which makes its own rays: no generate stage, no queue 0.  Its wave-uniform stack is a
     // fixed LDS array: a tree that may need more (a deep two-level tree) takes the per-lane kernel, whose stack is sized from stack_need
@@ -283,7 +241,7 @@ int enqueue_batch(Ctx* c, const FramePlan& p, const rt::PtScene& sc, const rt::P
         rt::StackCfg sk2 = p.stack;
         hipStream_t shadow_stream = c->stream;
         if (p.overlap) {
-            sk2.spill = p.stack.spill + pt.spill_half;
+            sk2.spill = p.stack.spill + p.spill_half;
             shadow_stream = c->aux_stream;
             RT_HIP(c, hipEventRecord(pt.ev_shaded, c->stream));
             RT_HIP(c, hipStreamWaitEvent(shadow_stream, pt.ev_shaded, 0));
@@ -412,80 +370,32 @@ int render_pt_common(Ctx* c, const float rot[4], const float pos[3], const rt_pt
     return sync ? read_frame_stats(c, tm, n) : RT_OK;
 }
 
-// rt_query_rays_device: everything that can refuse the call comes before the first enqueue
-int query_rays_impl(Ctx* c, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_ray_query_params* prm, void* t_out, void* tri_out) {
+}  // namespace
+
+namespace rt {
+// The first lds_cap entries of every lane's stack live in LDS (8-byte entries: 2 x lds_cap KiB per 256-thread workgroup, next to
+// fixed_lds_bytes: the ray kernels' 2 KiB octant table and triangle pools), which bounds residency at floor(160 KiB / that) workgroups
+// per CU, 8 at most (32 waves per CU); the rest of `need` spills to global memory.
+int pt_stack_config(Ctx* c, uint32_t need, uint32_t fixed_lds_bytes, uint32_t spill_halves, uint32_t tune_lds, uint32_t tune_blocks, uint64_t n_items,
+                    StackCfg* sk, uint32_t* grid) {
     PtData& pt = c->pt;
-    rt_ray_query_params defaults{};
-    if (!prm) prm = &defaults;
-    const rt::DeviceMesh& mesh = pt.mesh();
-    if (!mesh.n_tris) return c->fail(RT_ERR_STATE, "rt_set_mesh has not been called");
-    if (n > kMaxQueryRays) return c->fail(RT_ERR_INVALID, "n %u is above 2^30", n);
-    if (prm->any_hit > 1u) return c->fail(RT_ERR_INVALID, "any_hit %u (0 or 1)", prm->any_hit);
-    if ((prm->tune_refill_min & 0xffu) > 64u || prm->tune_refill_min > 0xffffu) return c->fail(RT_ERR_INVALID, "tune_refill_min %u (low byte 0 .. 64)", prm->tune_refill_min);
-    if (prm->tune_blocks_per_cu > 8u) return c->fail(RT_ERR_INVALID, "tune_blocks_per_cu %u (0 .. 8)", prm->tune_blocks_per_cu);
-    if (prm->tune_lds_stack > 78u) return c->fail(RT_ERR_INVALID, "tune_lds_stack %u (0 .. 78)", prm->tune_lds_stack);
-    if (n == 0) return RT_OK;
-    if (int rc = rt::bind(c)) return rc;
-    const bool any_hit = prm->any_hit != 0u;
-    const size_t rows = n;
-    if (int rc = rt::check_device_array(c, origins, rows * 12, "origins_dev")) return rc;
-    if (int rc = rt::check_device_array(c, dirs, rows * 12, "dirs_dev")) return rc;
-    if (tmax)
-        if (int rc = rt::check_device_array(c, tmax, rows * 4, "tmax_dev")) return rc;
-    if (t_out || !any_hit)
-        if (int rc = rt::check_device_array(c, t_out, rows * 4, "t_out_dev")) return rc;
-    if (int rc = rt::check_device_array(c, tri_out, rows * 4, "tri_out_dev")) return rc;
-
-    if (!pt.d_query) {  // first query of this context
-        if (!dalloc(pt.d_query, rt::RQ_BLOCK_BYTES)) return c->fail(RT_ERR_OOM, "ray-query stream heads");
-        for (hipEvent_t& e : pt.ev_query)
-            if (!e) RT_HIP(c, hipEventCreate(&e));
-    }
-    rt::StackCfg sk{};
-    uint32_t grid = 0;
-    if (int rc = stack_config(c, prm->tune_lds_stack, prm->tune_blocks_per_cu, (uint64_t)n, &sk, &grid)) return rc;
-    grid = std::min<uint32_t>(grid, (n + 255u) / 256u);
-    if (prm->tune_max_blocks) grid = std::min<uint32_t>(grid, prm->tune_max_blocks);
-    const uint32_t refill_min = (prm->tune_refill_min & 0xffu ? prm->tune_refill_min & 0xffu : kQueryRefillMin) | (prm->tune_refill_min & 0xff00u);
-
-    rt::RayQuery q{};
-    q.origins = static_cast<const float*>(origins);
-    q.dirs = static_cast<const float*>(dirs);
-    q.tmax = static_cast<const float*>(tmax);
-    q.t_out = any_hit ? nullptr : static_cast<float*>(t_out);
-    q.tri_out = static_cast<int*>(tri_out);
-    q.n = n;
-    q.reach = kCameraReach * mesh.maxabs;
-    uint32_t* head = reinterpret_cast<uint32_t*>(pt.d_query.get());
-    unsigned long long* stats = reinterpret_cast<unsigned long long*>(pt.d_query.get() + (size_t)rt::RQ_HEAD_WORDS * 4);
-    rt::RoctxRange rr("rt.path_b.query_rays");
-    RT_HIP(c, hipMemsetAsync(pt.d_query.get(), 0, rt::RQ_BLOCK_BYTES, c->stream));
-    RT_HIP(c, hipEventRecord(pt.ev_query[0], c->stream));
-    if (int rc = rt::launch_pt_query_rays(c, scene_view(mesh), q, any_hit, head, stats, grid, sk, refill_min)) return rc;
-    RT_HIP(c, hipEventRecord(pt.ev_query[1], c->stream));
-    pt.query_stats = rt_ray_query_stats{};
-    pt.query_stats.rays = n;
-    pt.query_stats.launches = 1;
-    pt.query_pending = true;
-    return RT_OK;
-}
-
-// The stack of the closest-point walk: point_stack_need entries per lane (one pending sibling each - not stack_need's one group per
-// level), the first lds_cap of them in LDS (tune_lds_stack, default ten: where the nearest-first order keeps most walks), the rest in
-// the context's spill columns, which grow to this need once per mesh
-int point_stack_config(Ctx* c, uint32_t tune_lds, uint32_t tune_blocks, uint64_t n_points, rt::StackCfg* sk, uint32_t* grid) {
-    PtData& pt = c->pt;
-    const uint32_t need = rt::point_stack_need(pt.mesh().depth);
+    need = std::max<uint32_t>(need, 1u);
+    // default: up to ten entries in LDS - the whole stack of the 1 M-triangle tree (depth 9) - at seven workgroups per CU
+    // (measured 1 % ahead of eight entries at eight workgroups)
     const uint32_t lds_cap = std::min<uint32_t>(need, tune_lds ? std::min<uint32_t>(tune_lds, 78u) : 10u);
-    const uint32_t fit = std::max<uint32_t>(1u, std::min<uint32_t>(8u, (160u * 1024u) / (2048u * lds_cap)));  // 2 KiB per entry per workgroup
-    const uint32_t by_load = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(3, (n_points + (uint64_t)c->n_cus * 1024 - 1) / ((uint64_t)c->n_cus * 1024)));
+    const uint32_t fit = std::max<uint32_t>(1u, std::min<uint32_t>(8u, (160u * 1024u) / (2048u * lds_cap + fixed_lds_bytes)));  // 2 KiB per entry per workgroup
+    // Few items (a rank's small share of a frame): fewer resident waves.  Every lane of the grid takes a ray
+    // at once, so with ~2 rays per lane the rays in flight span half the frame instead of a compact window
+    // and the short launches are all ramp and tail; about four rays per lane and more measured best
+    // (1/8 of the headline frame: 2.87 -> 2.62 ms with 4 instead of 8 workgroups per CU).
+    const uint32_t by_load = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(3, (n_items + (uint64_t)c->n_cus * 1024 - 1) / ((uint64_t)c->n_cus * 1024)));
     const uint32_t blocks_per_cu = tune_blocks ? std::min<uint32_t>(tune_blocks, fit) : std::min(fit, by_load);
     *grid = (uint32_t)c->n_cus * blocks_per_cu;
     sk->lds_cap = (int)lds_cap;
     sk->spill_cap = (int)(need - lds_cap);
     sk->spill_stride = (size_t)c->n_cus * 8u * 256u;  // covers every grid this function can return
-    const size_t words = std::max<size_t>(1, (size_t)sk->spill_cap) * sk->spill_stride;
-    if (words > pt.spill_words) {
+    const size_t words = spill_halves * spill_half_words(*sk);
+    if (words > pt.spill_words) {  // the columns grow to the largest need a mesh has met
         RT_HIP(c, hipStreamSynchronize(c->stream));
         pt.spill_words = 0;
         if (!dalloc(pt.d_spill, words)) return c->fail(RT_ERR_OOM, "traversal spill stack (%zu words)", words);
@@ -495,81 +405,10 @@ int point_stack_config(Ctx* c, uint32_t tune_lds, uint32_t tune_blocks, uint64_t
     return RT_OK;
 }
 
-// rt_query_points_device: everything that can refuse the call comes before the first enqueue
-int query_points_impl(Ctx* c, const void* points, const void* rmax, uint32_t n, const rt_point_query_params* prm, void* dist_out, void* tri_out, void* point_out) {
-    PtData& pt = c->pt;
-    rt_point_query_params defaults{};
-    if (!prm) prm = &defaults;
-    const rt::DeviceMesh& mesh = pt.mesh();
-    if (!mesh.n_tris) return c->fail(RT_ERR_STATE, "rt_set_mesh has not been called");
-    if (n > kMaxQueryRays) return c->fail(RT_ERR_INVALID, "n %u is above 2^30", n);
-    if (prm->count_traversal > 1u) return c->fail(RT_ERR_INVALID, "count_traversal %u (0 or 1)", prm->count_traversal);
-    if ((prm->tune_refill_min & 0xffu) > 64u || prm->tune_refill_min > 0xffffu) return c->fail(RT_ERR_INVALID, "tune_refill_min %u (low byte 0 .. 64)", prm->tune_refill_min);
-    if (prm->tune_blocks_per_cu > 8u) return c->fail(RT_ERR_INVALID, "tune_blocks_per_cu %u (0 .. 8)", prm->tune_blocks_per_cu);
-    if (prm->tune_lds_stack > 78u) return c->fail(RT_ERR_INVALID, "tune_lds_stack %u (0 .. 78)", prm->tune_lds_stack);
-    if (n == 0) return RT_OK;
-    if (int rc = rt::bind(c)) return rc;
-    const size_t rows = n;
-    if (int rc = rt::check_device_array(c, points, rows * 12, "points_dev")) return rc;
-    if (rmax)
-        if (int rc = rt::check_device_array(c, rmax, rows * 4, "rmax_dev")) return rc;
-    if (int rc = rt::check_device_array(c, dist_out, rows * 4, "dist_out_dev")) return rc;
-    if (int rc = rt::check_device_array(c, tri_out, rows * 4, "tri_out_dev")) return rc;
-    if (point_out)
-        if (int rc = rt::check_device_array(c, point_out, rows * 12, "point_out_dev")) return rc;
-
-    if (!pt.d_pquery) {  // first closest-point query of this context
-        if (!dalloc(pt.d_pquery, rt::PQ_BLOCK_BYTES)) return c->fail(RT_ERR_OOM, "point-query stream heads");
-        for (hipEvent_t& e : pt.ev_pquery)
-            if (!e) RT_HIP(c, hipEventCreate(&e));
-    }
-    rt::StackCfg sk{};
-    uint32_t grid = 0;
-    if (int rc = point_stack_config(c, prm->tune_lds_stack, prm->tune_blocks_per_cu, (uint64_t)n, &sk, &grid)) return rc;
-    grid = std::min<uint32_t>(grid, (n + 255u) / 256u);
-    if (prm->tune_max_blocks) grid = std::min<uint32_t>(grid, prm->tune_max_blocks);
-    const uint32_t refill_min = prm->tune_refill_min & 0xffu ? prm->tune_refill_min & 0xffu : kQueryRefillMin;  // (byte 1, the ray kernels' triangle tests per round, has no meaning here)
-
-    rt::PointQuery q{};
-    q.points = static_cast<const float*>(points);
-    q.rmax = static_cast<const float*>(rmax);
-    q.dist_out = static_cast<float*>(dist_out);
-    q.tri_out = static_cast<int*>(tri_out);
-    q.point_out = static_cast<float*>(point_out);
-    q.n = n;
-    q.reach = kCameraReach * mesh.maxabs;
-    uint32_t* head = reinterpret_cast<uint32_t*>(pt.d_pquery.get());
-    unsigned long long* stats = reinterpret_cast<unsigned long long*>(pt.d_pquery.get() + (size_t)rt::RQ_HEAD_WORDS * 4);
-    rt::RoctxRange rr("rt.path_b.query_points");
-    RT_HIP(c, hipMemsetAsync(pt.d_pquery.get(), 0, rt::PQ_BLOCK_BYTES, c->stream));
-    RT_HIP(c, hipEventRecord(pt.ev_pquery[0], c->stream));
-    if (int rc = rt::launch_pt_query_points(c, scene_view(mesh), q, prm->count_traversal != 0u, head, stats, grid, sk, refill_min)) return rc;
-    RT_HIP(c, hipEventRecord(pt.ev_pquery[1], c->stream));
-    pt.pquery_stats = rt_point_query_stats{};
-    pt.pquery_stats.points = n;
-    pt.pquery_stats.launches = 1;
-    pt.pquery_pending = true;
-    return RT_OK;
-}
-
-}  // namespace
-
-namespace rt {
 void pt_free(Ctx* c) {
     free_wavefront(c->pt);
     pt_free_mesh(c->pt);
-    c->pt.d_query.reset();
-    for (hipEvent_t& e : c->pt.ev_query) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    c->pt.query_pending = false;
-    c->pt.d_pquery.reset();
-    for (hipEvent_t& e : c->pt.ev_pquery) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    c->pt.pquery_pending = false;
+    query_free(c);
     c->pt.d_ctr.reset();
     c->pt.d_stats.reset();
     if (c->pt.ev_shaded) (void)hipEventDestroy(c->pt.ev_shaded);
@@ -626,70 +465,6 @@ int rt_get_pt_stats(rt_ctx* ctx, rt_pt_stats* stats) {
     return RT_OK;
 }
 
-int rt_default_ray_query_params(rt_ray_query_params* p) {
-    if (!p) return RT_ERR_INVALID;
-    *p = rt_ray_query_params{};
-    return RT_OK;
-}
-
-int rt_query_rays_device(rt_ctx* ctx, const void* origins_dev, const void* dirs_dev, const void* tmax_dev, uint32_t n, const rt_ray_query_params* params,
-                         void* t_out_dev, void* tri_out_dev) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c) return RT_ERR_INVALID;
-    return query_rays_impl(c, origins_dev, dirs_dev, tmax_dev, n, params, t_out_dev, tri_out_dev);
-}
-
-int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !stats) return RT_ERR_INVALID;
-    PtData& pt = c->pt;
-    if (pt.query_pending) {
-        if (int rc = rt::bind(c)) return rc;
-        RT_HIP(c, hipStreamSynchronize(c->stream));
-        unsigned long long st[rt::RQ_STAT_WORDS] = {};
-        RT_HIP(c, hipMemcpy(st, pt.d_query.get() + (size_t)rt::RQ_HEAD_WORDS * 4, sizeof st, hipMemcpyDeviceToHost));
-        pt.query_stats.invalid_rays = st[rt::RQ_STAT_INVALID];
-        pt.query_stats.stack_overflow = (uint32_t)st[rt::RQ_STAT_OVERFLOW];
-        RT_HIP(c, hipEventElapsedTime(&pt.query_stats.ms, pt.ev_query[0], pt.ev_query[1]));
-        pt.query_pending = false;
-    }
-    *stats = pt.query_stats;
-    return RT_OK;
-}
-
-int rt_default_point_query_params(rt_point_query_params* p) {
-    if (!p) return RT_ERR_INVALID;
-    *p = rt_point_query_params{};
-    return RT_OK;
-}
-
-int rt_query_points_device(rt_ctx* ctx, const void* points_dev, const void* rmax_dev, uint32_t n, const rt_point_query_params* params, void* dist_out_dev,
-                           void* tri_out_dev, void* point_out_dev) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c) return RT_ERR_INVALID;
-    return query_points_impl(c, points_dev, rmax_dev, n, params, dist_out_dev, tri_out_dev, point_out_dev);
-}
-
-int rt_get_point_query_stats(rt_ctx* ctx, rt_point_query_stats* stats) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !stats) return RT_ERR_INVALID;
-    PtData& pt = c->pt;
-    if (pt.pquery_pending) {
-        if (int rc = rt::bind(c)) return rc;
-        RT_HIP(c, hipStreamSynchronize(c->stream));
-        unsigned long long st[rt::PQ_STAT_WORDS] = {};
-        RT_HIP(c, hipMemcpy(st, pt.d_pquery.get() + (size_t)rt::RQ_HEAD_WORDS * 4, sizeof st, hipMemcpyDeviceToHost));
-        pt.pquery_stats.invalid_points = st[rt::PQ_STAT_INVALID];
-        pt.pquery_stats.stack_overflow = (uint32_t)st[rt::PQ_STAT_OVERFLOW];
-        pt.pquery_stats.nodes_visited = st[rt::PQ_STAT_NODES];
-        pt.pquery_stats.tris_tested = st[rt::PQ_STAT_TRIS];
-        RT_HIP(c, hipEventElapsedTime(&pt.pquery_stats.ms, pt.ev_pquery[0], pt.ev_pquery[1]));
-        pt.pquery_pending = false;
-    }
-    *stats = pt.pquery_stats;
-    return RT_OK;
-}
-
 int rt_trace_rays_counted(rt_ctx* ctx, const float* origins, const float* dirs, uint32_t n, int any_hit, float* t_out, int32_t* tri_out,
                           uint32_t* counts_out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
@@ -707,7 +482,7 @@ int rt_trace_rays_counted(rt_ctx* ctx, const float* origins, const float* dirs, 
     RT_HIP(c, hipMemcpy(d_d.get(), dirs, nb * 12, hipMemcpyHostToDevice));
     rt::StackCfg sk{};
     uint32_t grid = 0;
-    if (int rc = stack_config(c, 0, 0, (uint64_t)n, &sk, &grid)) return rc;
+    if (int rc = rt::pt_stack_config(c, c->pt.mesh().stack_need, 2048u, 2u, 0, 0, (uint64_t)n, &sk, &grid)) return rc;
     if (int rc = rt::launch_pt_trace_rays(c, scene_view(c->pt.mesh()), d_o.get(), d_d.get(), n, any_hit, d_t.get(), d_i.get(), d_c.get(), sk, std::min<uint32_t>(grid, (n + 255u) / 256u)))
         return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));  // the buffers are freed on return: nothing may still use them

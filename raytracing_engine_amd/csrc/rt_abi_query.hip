@@ -1,0 +1,195 @@
+// rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays and closest points (§6.14).
+// A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here.
+#include <algorithm>
+
+#include "rt_internal.h"
+#include "rt_roctx.h"
+
+using rt::Ctx;
+using rt::QueryState;
+
+namespace {
+
+constexpr uint32_t kMaxQueryItems = 1u << 30;  // stream_entry() of a dry reservation stays below 2^32
+constexpr uint32_t kQueryRefillMin = 24;       // idle lanes per wave that trigger a refill in the query kernels (the render kernels' default)
+
+// What both parameter structs are checked for, in the order the refusals have: `flag` is the kind's own switch (any_hit, count_traversal)
+template <class Params>
+int check_query_params(Ctx* c, uint32_t n, const Params& prm, uint32_t flag, const char* flag_name) {
+    if (!c->pt.mesh().n_tris) return c->fail(RT_ERR_STATE, "rt_set_mesh has not been called");
+    if (n > kMaxQueryItems) return c->fail(RT_ERR_INVALID, "n %u is above 2^30", n);
+    if (flag > 1u) return c->fail(RT_ERR_INVALID, "%s %u (0 or 1)", flag_name, flag);
+    if ((prm.tune_refill_min & 0xffu) > 64u || prm.tune_refill_min > 0xffffu) return c->fail(RT_ERR_INVALID, "tune_refill_min %u (low byte 0 .. 64)", prm.tune_refill_min);
+    if (prm.tune_blocks_per_cu > 8u) return c->fail(RT_ERR_INVALID, "tune_blocks_per_cu %u (0 .. 8)", prm.tune_blocks_per_cu);
+    if (prm.tune_lds_stack > 78u) return c->fail(RT_ERR_INVALID, "tune_lds_stack %u (0 .. 78)", prm.tune_lds_stack);
+    return RT_OK;
+}
+
+// After the kind's array checks.  What can still refuse comes first: the device block and the events (first query of the kind), the
+// stack of stack_need entries per lane.  Then the enqueue: clear the block, launch(head, stats, grid, stack, refill_min's low byte)
+// between the two events, remember that there is something to read
+template <class Params, class Launch>
+int enqueue_query(Ctx* c, QueryState& qs, uint32_t n, const Params& prm, uint32_t stack_need, const char* range, Launch&& launch) {
+    if (!qs.block) {
+        if (!dalloc(qs.block, rt::query_block_bytes(qs.n_counters))) return c->fail(RT_ERR_OOM, "%s stream heads", qs.name);
+        for (hipEvent_t& e : qs.ev)
+            if (!e) RT_HIP(c, hipEventCreate(&e));
+    }
+    rt::StackCfg sk{};
+    uint32_t grid = 0;
+    if (int rc = rt::pt_stack_config(c, stack_need, qs.fixed_lds_bytes, qs.spill_halves, prm.tune_lds_stack, prm.tune_blocks_per_cu, (uint64_t)n, &sk, &grid)) return rc;
+    grid = std::min<uint32_t>(grid, (n + 255u) / 256u);
+    if (prm.tune_max_blocks) grid = std::min<uint32_t>(grid, prm.tune_max_blocks);
+    const uint32_t refill_min = prm.tune_refill_min & 0xffu ? prm.tune_refill_min & 0xffu : kQueryRefillMin;
+    uint32_t* head = reinterpret_cast<uint32_t*>(qs.block.get());
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(qs.block.get() + rt::kQueryHeadBytes);
+    rt::RoctxRange rr(range);
+    RT_HIP(c, hipMemsetAsync(qs.block.get(), 0, rt::query_block_bytes(qs.n_counters), c->stream));
+    RT_HIP(c, hipEventRecord(qs.ev[0], c->stream));
+    if (int rc = launch(head, stats, grid, sk, refill_min)) return rc;
+    RT_HIP(c, hipEventRecord(qs.ev[1], c->stream));
+    qs.pending = true;
+    return RT_OK;
+}
+
+// The pending query's qs.n_counters counters and its time (waits for it)
+int read_query(Ctx* c, QueryState& qs, unsigned long long* counters, float* ms) {
+    if (int rc = rt::bind(c)) return rc;
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    RT_HIP(c, hipMemcpy(counters, qs.block.get() + rt::kQueryHeadBytes, qs.n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    RT_HIP(c, hipEventElapsedTime(ms, qs.ev[0], qs.ev[1]));
+    qs.pending = false;
+    return RT_OK;
+}
+
+}  // namespace
+
+namespace rt {
+void query_free(Ctx* c) {
+    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query}) {
+        qs->block.reset();
+        for (hipEvent_t& e : qs->ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        qs->pending = false;
+    }
+}
+}  // namespace rt
+
+extern "C" {
+
+int rt_default_ray_query_params(rt_ray_query_params* p) {
+    if (!p) return RT_ERR_INVALID;
+    *p = rt_ray_query_params{};
+    return RT_OK;
+}
+
+// Everything that can refuse a call comes before the first enqueue (in enqueue_query)
+int rt_query_rays_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_ray_query_params* prm, void* t_out, void* tri_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    rt_ray_query_params defaults{};
+    if (!prm) prm = &defaults;
+    if (int rc = check_query_params(c, n, *prm, prm->any_hit, "any_hit")) return rc;
+    if (n == 0) return RT_OK;
+    if (int rc = rt::bind(c)) return rc;
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    const bool any_hit = prm->any_hit != 0u;
+    if (int rc = rt::check_device_array(c, origins, (size_t)n * 12, "origins_dev")) return rc;
+    if (int rc = rt::check_device_array(c, dirs, (size_t)n * 12, "dirs_dev")) return rc;
+    if (tmax)
+        if (int rc = rt::check_device_array(c, tmax, (size_t)n * 4, "tmax_dev")) return rc;
+    if (t_out || !any_hit)
+        if (int rc = rt::check_device_array(c, t_out, (size_t)n * 4, "t_out_dev")) return rc;
+    if (int rc = rt::check_device_array(c, tri_out, (size_t)n * 4, "tri_out_dev")) return rc;
+    rt::RayQuery q{};
+    q.origins = static_cast<const float*>(origins);
+    q.dirs = static_cast<const float*>(dirs);
+    q.tmax = static_cast<const float*>(tmax);
+    q.t_out = any_hit ? nullptr : static_cast<float*>(t_out);
+    q.tri_out = static_cast<int*>(tri_out);
+    q.n = n;
+    q.reach = rt::kCameraReach * mesh.maxabs;
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_rays(c, rt::scene_view(mesh), q, any_hit, head, stats, grid, sk, refill_min | (prm->tune_refill_min & 0xff00u));  // byte 1: triangle tests per round
+    };
+    if (int rc = enqueue_query(c, c->pt.ray_query, n, *prm, mesh.stack_need, "rt.path_b.query_rays", launch)) return rc;
+    c->pt.ray_query_stats = rt_ray_query_stats{};
+    c->pt.ray_query_stats.rays = n;
+    c->pt.ray_query_stats.launches = 1;
+    return RT_OK;
+}
+
+int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    rt_ray_query_stats& s = c->pt.ray_query_stats;
+    if (c->pt.ray_query.pending) {
+        unsigned long long st[rt::RQ_STAT_WORDS] = {};
+        if (int rc = read_query(c, c->pt.ray_query, st, &s.ms)) return rc;
+        s.invalid_rays = st[rt::RQ_STAT_INVALID];
+        s.stack_overflow = (uint32_t)st[rt::RQ_STAT_OVERFLOW];
+    }
+    *stats = s;
+    return RT_OK;
+}
+
+int rt_default_point_query_params(rt_point_query_params* p) {
+    if (!p) return RT_ERR_INVALID;
+    *p = rt_point_query_params{};
+    return RT_OK;
+}
+
+int rt_query_points_device(rt_ctx* ctx, const void* points, const void* rmax, uint32_t n, const rt_point_query_params* prm, void* dist_out, void* tri_out, void* point_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    rt_point_query_params defaults{};
+    if (!prm) prm = &defaults;
+    if (int rc = check_query_params(c, n, *prm, prm->count_traversal, "count_traversal")) return rc;
+    if (n == 0) return RT_OK;
+    if (int rc = rt::bind(c)) return rc;
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, points, (size_t)n * 12, "points_dev")) return rc;
+    if (rmax)
+        if (int rc = rt::check_device_array(c, rmax, (size_t)n * 4, "rmax_dev")) return rc;
+    if (int rc = rt::check_device_array(c, dist_out, (size_t)n * 4, "dist_out_dev")) return rc;
+    if (int rc = rt::check_device_array(c, tri_out, (size_t)n * 4, "tri_out_dev")) return rc;
+    if (point_out)
+        if (int rc = rt::check_device_array(c, point_out, (size_t)n * 12, "point_out_dev")) return rc;
+    rt::PointQuery q{};
+    q.points = static_cast<const float*>(points);
+    q.rmax = static_cast<const float*>(rmax);
+    q.dist_out = static_cast<float*>(dist_out);
+    q.tri_out = static_cast<int*>(tri_out);
+    q.point_out = static_cast<float*>(point_out);
+    q.n = n;
+    q.reach = rt::kCameraReach * mesh.maxabs;
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_points(c, rt::scene_view(mesh), q, prm->count_traversal != 0u, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
+    };
+    // point_stack_need entries per lane: one pending sibling each, not stack_need's one group per level; the spill columns grow to it once per mesh
+    if (int rc = enqueue_query(c, c->pt.point_query, n, *prm, rt::point_stack_need(mesh.depth), "rt.path_b.query_points", launch)) return rc;
+    c->pt.point_query_stats = rt_point_query_stats{};
+    c->pt.point_query_stats.points = n;
+    c->pt.point_query_stats.launches = 1;
+    return RT_OK;
+}
+
+int rt_get_point_query_stats(rt_ctx* ctx, rt_point_query_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    rt_point_query_stats& s = c->pt.point_query_stats;
+    if (c->pt.point_query.pending) {
+        unsigned long long st[rt::PQ_STAT_WORDS] = {};
+        if (int rc = read_query(c, c->pt.point_query, st, &s.ms)) return rc;
+        s.invalid_points = st[rt::PQ_STAT_INVALID];
+        s.stack_overflow = (uint32_t)st[rt::PQ_STAT_OVERFLOW];
+        s.nodes_visited = st[rt::PQ_STAT_NODES];
+        s.tris_tested = st[rt::PQ_STAT_TRIS];
+    }
+    *stats = s;
+    return RT_OK;
+}
+
+}  // extern "C"

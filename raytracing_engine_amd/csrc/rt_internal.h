@@ -203,8 +203,8 @@ struct RayQuery {
     uint32_t n;
     float reach;  // |origin component| limit: kCameraReach x the mesh's maxabs
 };
-// The query's device block (PtData::d_query), cleared before every launch: the PT_HEADS stream heads, then two 64-bit counters
-enum { RQ_STAT_INVALID = 0, RQ_STAT_OVERFLOW = 1, RQ_STAT_WORDS = 2, RQ_HEAD_WORDS = PT_HEADS * PT_HEAD_STRIDE, RQ_BLOCK_BYTES = RQ_HEAD_WORDS * 4 + RQ_STAT_WORDS * 8 };
+// Counters of a ray query (QueryState's device block)
+enum { RQ_STAT_INVALID = 0, RQ_STAT_OVERFLOW = 1, RQ_STAT_WORDS = 2 };
 
 // rt_query_points_device: the points of one query and where their answers go.  Point i is queue entry i.
 struct PointQuery {
@@ -216,8 +216,8 @@ struct PointQuery {
     uint32_t n;
     float reach;  // |component| limit: kCameraReach x the mesh's maxabs
 };
-// Its device block (PtData::d_pquery), a sibling of the ray query's, cleared before every launch: the PT_HEADS stream heads, then four 64-bit counters
-enum { PQ_STAT_INVALID = 0, PQ_STAT_OVERFLOW = 1, PQ_STAT_NODES = 2, PQ_STAT_TRIS = 3, PQ_STAT_WORDS = 4, PQ_BLOCK_BYTES = RQ_HEAD_WORDS * 4 + PQ_STAT_WORDS * 8 };
+// Counters of a closest-point query
+enum { PQ_STAT_INVALID = 0, PQ_STAT_OVERFLOW = 1, PQ_STAT_NODES = 2, PQ_STAT_TRIS = 3, PQ_STAT_WORDS = 4 };
 // Stack entries the nearest-first walk of pt_query_points can hold at once in a tree of `depth` levels of 8-wide nodes (root = 1): an
 // entry is one pending sibling, a node visit descends into one inner child and pushes at most seven, and the entries of one level
 // on the stack are always children of one node (they lie above every entry of the levels before them and are popped first), so at
@@ -251,6 +251,21 @@ bool dalloc(DevPtr<T>& p, size_t count) {  // frees what p held first; false: ou
     return true;
 }
 
+// What a context keeps per query kind.  The device block is PT_HEADS stream heads (PT_HEAD_STRIDE words apart), then the kind's
+// 64-bit counters; it is cleared before every launch.  One block per kind: a query's counters stay until rt_get_*_query_stats reads
+// them, whatever the other kind does meanwhile.  Allocated by the kind's first query, freed with the context (rt_abi_query.hip).
+constexpr size_t kQueryHeadBytes = (size_t)PT_HEADS * PT_HEAD_STRIDE * sizeof(uint32_t);
+constexpr size_t query_block_bytes(uint32_t n_counters) { return kQueryHeadBytes + (size_t)n_counters * sizeof(unsigned long long); }
+struct QueryState {
+    QueryState(uint32_t k, const char* what, uint32_t lds, uint32_t halves) : n_counters(k), name(what), fixed_lds_bytes(lds), spill_halves(halves) {}
+    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS
+    const char* name;     // for messages
+    uint32_t fixed_lds_bytes, spill_halves;  // pt_stack_config's: the kernel's LDS beside the stacks, the sets of spill columns it is given
+    DevPtr<char> block;
+    hipEvent_t ev[2] = {nullptr, nullptr};  // around the launch
+    bool pending = false;  // a query has been enqueued whose counters and time rt_get_*_query_stats has not read yet
+};
+
 // A mesh resident on the device: the arrays the kernels read and what the host knows about them.  Made by the host build
 // (rt_abi_mesh.hip) or by build_bvh_device.  Contexts hold it through a shared pointer (PtData::own): contexts that were given the same host
 // mesh hold the same record and treat it as read-only; whoever writes into it makes sure first that it is the only holder (detach_mesh,
@@ -282,7 +297,7 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     DevPtr<char> d_refit;  // rt_refit_mesh_device scratch (refit_scratch_size), allocated by the first refit, freed with the mesh
     hipEvent_t ev_refit[2] = {nullptr, nullptr};
     DevPtr<unsigned long long> d_spill;
-    size_t spill_words = 0, spill_half = 0;
+    size_t spill_words = 0;
     hipEvent_t ev_shaded = nullptr, ev_shadowed = nullptr;  // ordering between the main and the auxiliary stream
     std::vector<hipEvent_t> ev_pool;  // profile_stages: timing events, created on this context's device, freed by pt_free
     // wavefront buffers, sized for cap_paths; st, d_queue and d_acc point into the allocations `wavefront` owns
@@ -295,16 +310,11 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     DevPtr<uint32_t> d_ctr;
     DevPtr<unsigned long long> d_stats;  // PT_STAT_WORDS words
     rt_pt_stats stats{};
-    // rt_query_rays_device: stream heads + counters (RQ_BLOCK_BYTES), allocated by the first query, freed with the context
-    DevPtr<char> d_query;
-    hipEvent_t ev_query[2] = {nullptr, nullptr};
-    rt_ray_query_stats query_stats{};
-    bool query_pending = false;  // a query has been enqueued whose counters and time rt_get_ray_query_stats has not read yet
-    // rt_query_points_device: the same for closest-point queries (PQ_BLOCK_BYTES)
-    DevPtr<char> d_pquery;
-    hipEvent_t ev_pquery[2] = {nullptr, nullptr};
-    rt_point_query_stats pquery_stats{};
-    bool pquery_pending = false;
+    // rt_query_rays_device / rt_query_points_device: what is in flight, and the statistics of the last query of each kind
+    // (rays: the 2 KiB octant table, two spill halves as the frames hold; points: no table, one set of columns)
+    QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u};
+    rt_ray_query_stats ray_query_stats{};
+    rt_point_query_stats point_query_stats{};
 };
 
 struct Ctx {
@@ -400,13 +410,32 @@ int launch_pt_scatter_surfaces(Ctx* c, const float4* tris, const float* surf, fl
 int launch_pt_resolve(Ctx* c, const PtFrame& f, const PtState& st, float* acc, float* dst, int tile_major);
 int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const float* dirs, uint32_t n, int any_hit, float* t_out,
                          int* tri_out, uint32_t* counts, const StackCfg& sk, uint32_t grid);
-// persistent refilling query kernel on c->stream; head / stats: the two parts of PtData::d_query, cleared by the caller
+// persistent refilling query kernels on c->stream; head / stats: the two parts of the kind's QueryState block, cleared by the caller
 int launch_pt_query_rays(Ctx* c, const PtScene& sc, const RayQuery& q, bool any_hit, uint32_t* head, unsigned long long* stats, uint32_t grid,
                          const StackCfg& sk, uint32_t refill_min);
-// the closest-point kernel, launched like launch_pt_query_rays; head / stats: the two parts of PtData::d_pquery
 int launch_pt_query_points(Ctx* c, const PtScene& sc, const PointQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                            const StackCfg& sk, uint32_t refill_min);
 void pt_free(Ctx* c);
+void query_free(Ctx* c);  // rt_abi_query.hip: both query kinds' device blocks and events
+
+// |coordinate| limit of a camera position, a query ray's origin and a query point in units of DeviceMesh::maxabs (plan_frame, rt_abi_pt.hip)
+constexpr float kCameraReach = 32.0f;
+inline PtScene scene_view(const DeviceMesh& m) {
+    PtScene s{};
+    s.nodes = m.nodes.get();
+    s.tris = m.tris.get();
+    s.albedo = m.albedo.get();
+    s.emission = m.emission.get();
+    s.lights = m.lights.get();
+    s.n_lights = m.n_lights;
+    s.n_tris = m.n_tris;
+    return s;
+}
+inline size_t spill_half_words(const StackCfg& sk) { return (sk.spill_cap > 1 ? (size_t)sk.spill_cap : 1) * sk.spill_stride; }
+// rt_abi_pt.hip: traversal stack + persistent grid of one launch over n_items rays or points.  need: worst-case entries per lane; fixed_lds_bytes:
+// a workgroup's LDS beside its stacks; spill_halves: sets of spill columns (spill_half_words each) that PtData::d_spill must hold at once.
+int pt_stack_config(Ctx* c, uint32_t need, uint32_t fixed_lds_bytes, uint32_t spill_halves, uint32_t tune_lds, uint32_t tune_blocks, uint64_t n_items,
+                    StackCfg* sk, uint32_t* grid);
 // rt_abi_mesh.hip: RT_OK when p is a device allocation of c's device that holds at least `bytes` bytes from p on, else RT_ERR_INVALID
 int check_device_array(Ctx* c, const void* p, size_t bytes, const char* what);
 void comm_free(Ctx* c);  // rt_abi_comm.hip

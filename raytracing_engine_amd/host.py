@@ -449,6 +449,35 @@ class Renderer:
         if t.dtype != torch.int32 or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device or t.dim() != 1 or t.numel() != n:
             raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
+    def _query_tune(self, params, tune, method):
+        """The tune_* keywords of `method` (query_rays / query_points) into its parameter struct; TypeError for any other keyword."""
+        for k, v in tune.items():
+            if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
+                raise TypeError(f"{method}() got an unexpected keyword argument {k!r}")
+            setattr(params, k, int(v))
+
+    def _query_out(self, t, name, n, dtype, dev, cols=1):
+        """The out tensor `name` of a query over n items: a new one (t is None), or t once it is what the query can fill."""
+        import torch
+
+        if t is None:
+            return torch.empty(n if cols == 1 else (n, cols), dtype=dtype, device=dev)
+        if dtype == torch.int32:
+            self._device_i32(t, name, n)
+        elif self._device_rows(t, name, cols) != n or (cols == 1 and t.dim() != 1):
+            raise ValueError(f"{name} must have shape ({n},), got {tuple(t.shape)}" if cols == 1 else f"{name} must hold {n} rows of {cols}")
+        return t
+
+    def _query_call(self, sync, fn, *args):
+        """The C call of a query between the two halves of `sync`: torch's current stream is finished before, ours after."""
+        import torch
+
+        if sync:
+            torch.cuda.current_stream(self.device).synchronize()  # writers on torch's stream are done before the query reads
+        self._check(fn(self._ctx, *(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args)))
+        if sync:
+            self.synchronize()
+
     def query_rays(self, origins, dirs, tmax=None, any_hit=False, out=None, sync=True, **tune):
         """What do rays hit in the current mesh?  (rt_query_rays_device)  origins, dirs: float32 torch tensors on this
         renderer's device, contiguous, (n, 3) or flat; tmax: (n,) or None.  A triangle is hit when 0 < t < tmax (default: +inf for the
@@ -467,32 +496,17 @@ class Renderer:
             raise ValueError(f"tmax must have shape ({n},), got {tuple(tmax.shape)}")
         p = RayQueryParams()
         p.any_hit = int(bool(any_hit))
-        for k, v in tune.items():
-            if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
-                raise TypeError(f"query_rays() got an unexpected keyword argument {k!r}")
-            setattr(p, k, int(v))
+        self._query_tune(p, tune, "query_rays")
         if any_hit:
             t, tri = None, out
         else:
             if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
                 raise ValueError("out must be the pair (t, tri) for a closest-hit query")
             t, tri = out if out is not None else (None, None)
-        dev = origins.device
-        if tri is None:
-            tri = torch.empty(n, dtype=torch.int32, device=dev)
-        else:
-            self._device_i32(tri, "out tri", n)
+        tri = self._query_out(tri, "out tri", n, torch.int32, origins.device)
         if not any_hit:
-            if t is None:
-                t = torch.empty(n, dtype=torch.float32, device=dev)
-            elif self._device_rows(t, "out t", 1) != n or t.dim() != 1:
-                raise ValueError(f"out t must have shape ({n},), got {tuple(t.shape)}")
-        if sync:
-            torch.cuda.current_stream(self.device).synchronize()  # writers on torch's stream are done before the query reads
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None  # noqa: E731
-        self._check(self._lib.rt_query_rays_device(self._ctx, ptr(origins), ptr(dirs), ptr(tmax), n, C.byref(p), ptr(t), ptr(tri)))
-        if sync:
-            self.synchronize()
+            t = self._query_out(t, "out t", n, torch.float32, origins.device)
+        self._query_call(sync, self._lib.rt_query_rays_device, origins, dirs, tmax, n, C.byref(p), t, tri)
         return tri if any_hit else (t, tri)
 
     def ray_query_stats(self):
@@ -521,34 +535,15 @@ class Renderer:
             raise ValueError(f"rmax must have shape ({n},), got {tuple(rmax.shape)}")
         p = PointQueryParams()
         p.count_traversal = int(bool(count_traversal))
-        for k, v in tune.items():
-            if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
-                raise TypeError(f"query_points() got an unexpected keyword argument {k!r}")
-            setattr(p, k, int(v))
-        want = 3 if want_points else 2
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != want):
+        self._query_tune(p, tune, "query_points")
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != (3 if want_points else 2)):
             raise ValueError("out must be (dist, tri, point), or the pair (dist, tri) with want_points=False")
         dist, tri, pt = (tuple(out) + (None,))[:3] if out is not None else (None, None, None)
-        dev = points.device
-        if dist is None:
-            dist = torch.empty(n, dtype=torch.float32, device=dev)
-        elif self._device_rows(dist, "out dist", 1) != n or dist.dim() != 1:
-            raise ValueError(f"out dist must have shape ({n},), got {tuple(dist.shape)}")
-        if tri is None:
-            tri = torch.empty(n, dtype=torch.int32, device=dev)
-        else:
-            self._device_i32(tri, "out tri", n)
+        dist = self._query_out(dist, "out dist", n, torch.float32, points.device)
+        tri = self._query_out(tri, "out tri", n, torch.int32, points.device)
         if want_points:
-            if pt is None:
-                pt = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            elif self._device_rows(pt, "out point", 3) != n:
-                raise ValueError(f"out point must hold {n} rows of 3")
-        if sync:
-            torch.cuda.current_stream(self.device).synchronize()  # writers on torch's stream are done before the query reads
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None  # noqa: E731
-        self._check(self._lib.rt_query_points_device(self._ctx, ptr(points), ptr(rmax), n, C.byref(p), ptr(dist), ptr(tri), ptr(pt)))
-        if sync:
-            self.synchronize()
+            pt = self._query_out(pt, "out point", n, torch.float32, points.device, cols=3)
+        self._query_call(sync, self._lib.rt_query_points_device, points, rmax, n, C.byref(p), dist, tri, pt)
         return dist, tri, pt
 
     def point_query_stats(self):

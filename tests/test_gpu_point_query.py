@@ -371,6 +371,67 @@ def test_errors_write_nothing(renderer):
     assert_answers(tuple(x.cpu().numpy() for x in got), b["ref"], slice(0, n))
 
 
+def test_ray_and_point_stats_do_not_mix(renderer):
+    """Each query kind keeps its own counters until somebody reads them: a ray query's survive a later point query, and the other way
+    round, and neither query's answers depend on what ran before it."""
+    b = set_soup(renderer)
+    parts = X.family("a")
+    o, d = np.concatenate([p["o"] for p in parts]).copy(), np.concatenate([p["d"] for p in parts])
+    assert len(o) == N
+    rng = np.random.default_rng(47)
+    bad_rays = rng.permutation(N)[:100]
+    o[bad_rays, np.arange(100) % 3] = np.array([np.nan, np.inf, -np.inf], f32)[np.arange(100) % 3]
+    p = b["p"].copy()
+    p[rng.permutation(N)[:300], 0] = np.nan
+    to, td, tp = tdev(o), tdev(d), tdev(p)
+
+    def rays():
+        t, tri = renderer.query_rays(to, td)
+        return t.cpu().numpy(), tri.cpu().numpy()
+
+    def points():
+        return tuple(x.cpu().numpy() for x in renderer.query_points(tp, count_traversal=True))
+
+    rays_alone, points_alone = rays(), points()
+    assert (rays_alone[1][bad_rays] == INVALID).all() and (rays_alone[1] == INVALID).sum() == 100 and (points_alone[1] == INVALID).sum() == 300
+    for first, second in ((rays, points), (points, rays)):
+        got = {first: first(), second: second()}
+        rs, ps = renderer.ray_query_stats(), renderer.point_query_stats()  # only now
+        assert (rs["invalid_rays"], rs["rays"]) == (100, N), rs
+        assert (ps["invalid_points"], ps["points"]) == (300, N) and ps["nodes_visited"] > 0, ps
+        assert rs["ms"] > 0 and ps["ms"] > 0
+        assert all(same_floats(x, y) for x, y in zip(got[rays], rays_alone)), first.__name__
+        assert all(same_floats(x, y) for x, y in zip(got[points], points_alone)), first.__name__
+        assert np.array_equal(got[rays][1], rays_alone[1]) and np.array_equal(got[points][1], points_alone[1])
+
+
+def test_queries_leave_two_stream_frames_alone(renderer):
+    """tune_no_overlap = 2: the shadow kernel runs beside the next closest-hit kernel on the second half of the spill columns - the one
+    path that reads where that half begins.  Queries that size the columns for themselves in between must not move the frame.  With the
+    default ten LDS entries this small tree never spills, so the same is asked of frames with one LDS entry, which do use both halves."""
+    b = set_soup(renderer)
+    renderer.resize(64, 64)
+    kw = dict(pos=(0, 1, 0), spp=2, bounces=2, seed=3, sky=(0.2, 0.2, 0.3), tune_no_overlap=2)
+    parts = X.family("a")
+    o, d = np.concatenate([p["o"] for p in parts]), np.concatenate([p["d"] for p in parts])
+
+    def frame(**more):
+        rgb = renderer.render_pt(**kw, **more)
+        st = renderer.pt_stats()
+        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+
+    before, before_spilling = frame(), frame(tune_lds_stack=1)
+    assert before[1][1] > 0 and before[1][2] > 0 and before[1][3] == 0
+    assert renderer.pt_stats()["bvh_depth"] > 1  # one LDS entry is not the whole stack
+    assert np.array_equal(before[0], before_spilling[0]) and before[1] == before_spilling[1]
+    assert_answers(query(renderer, b["p"], tune_lds_stack=1), b["ref"])
+    renderer.query_rays(tdev(o), tdev(d), tune_lds_stack=1)
+    assert renderer.ray_query_stats()["stack_overflow"] == 0
+    after, after_spilling = frame(), frame(tune_lds_stack=1)
+    assert np.array_equal(before[0], after[0]) and before[1] == after[1]
+    assert np.array_equal(before[0], after_spilling[0]) and before[1] == after_spilling[1]
+
+
 def test_rendering_and_sharing_are_undisturbed(renderer):
     b = set_soup(renderer)
     renderer.resize(64, 64)
