@@ -5,7 +5,7 @@
  * (IvoteSligte/raytracing_engine) has no triangles, BVH, RNG, spp or bounces, so
  * this oracle pins nothing against the reference — "parity unpinned by the reference".  It is the
  * executable form of the specification in DESIGN.md §6, which the HIP kernels in
- * raytracing_engine_amd/csrc/path_b.hip implement independently; the camera model is the
+ * raytracing_engine_amd/csrc/path_b.hip, pt_trace.hip and pt_packet.hip implement independently; the camera model is the
  * reference's (shaders/fragment.glsl:129-133, shaders/utilities.glsl:26-29).
  *
  * Results do not depend on the BVH (boxes are conservative, closest hit is the (t, index)

@@ -1,5 +1,5 @@
 // point_tri.h — the arithmetic of path B's closest-point query, defined once for the kernel (pt_query_points,
-// path_b.hip) and for the tests' reference (tests/native/point_query_ref.cpp).  Compiled by plain g++ and by hipcc; every function is
+// pt_point_query.hip) and for the tests' reference (tests/native/point_query_ref.cpp).  Compiled by plain g++ and by hipcc; every function is
 // host + device under hipcc.  fp32 only, after DESIGN.md §4: every fused multiply-add is an explicit __builtin_fmaf, dot() in §4's
 // order, correctly rounded / (and sqrt at the callers), no contraction (-ffp-contract=off on both sides).  The same operations in
 // the same order on both sides, so the two agree bit for bit.

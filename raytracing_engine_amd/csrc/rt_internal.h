@@ -155,11 +155,11 @@ struct PtScene {
     uint32_t n_tris;
 };
 
-constexpr uint32_t kPacketStackEntries = 40;  // pt_trace_packet's LDS stack of node groups (path_b.hip)
+constexpr uint32_t kPacketStackEntries = 40;  // pt_trace_packet's LDS stack of node groups (pt_packet.hip)
 // rt_pt_params.tune_no_packet: 0 = default, 1 = no packet kernel (camera rays through the per-lane kernel), then the packet kernel's node test:
 // per-ray slab tests of all eight children; interval test for the pass, per-ray tests of the children that pass; interval test only; the second without the best-hit cap
 enum { PACKET_DEFAULT = 0, PACKET_OFF = 1, PACKET_EXACT = 2, PACKET_INTERVAL = 3, PACKET_INTERVAL_ONLY = 4, PACKET_INTERVAL_NOCAP = 5 };
-enum { TRI_MODE_INLINE = 1, TRI_MODE_POOL = 2, TRI_MODE_DEFER = 3, TRI_MODE_INLINE_PF = 4 };  // rt_pt_params.tune_tri_mode, byte 0 (path_b.hip: TRI_INLINE, TRI_POOL)
+enum { TRI_MODE_INLINE = 1, TRI_MODE_POOL = 2, TRI_MODE_DEFER = 3, TRI_MODE_INLINE_PF = 4 };  // rt_pt_params.tune_tri_mode, byte 0 (pt_trace.hip: TRI_INLINE, TRI_POOL)
 
 struct StackCfg {  // per-lane traversal stack of 8-byte entries: lds_cap in LDS, then spill_cap in global memory
     unsigned long long* spill;  // spill_cap x spill_stride entries, entry-major
@@ -393,7 +393,8 @@ int launch_selftest_sqrt(Ctx* c, unsigned long long* mismatches_dev);
 int launch_detile(Ctx* c, const float* tiles, uint32_t n_ranks, uint32_t tiles_per_rank, float* rgb);
 int launch_to_rgba8(Ctx* c, const float* rgb, uint8_t* rgba, uint64_t n_pixels);
 
-// path_b.hip
+// path_b.hip (generate, shade, scatter_surfaces, resolve), pt_trace.hip (trace, trace_fused, pool_lds_bytes, trace_rays, query_rays), pt_packet.hip (trace_packet),
+// pt_point_query.hip (query_points): every unit ends with the launchers of its own kernels
 int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* queue, uint32_t* ctr);
 int launch_pt_trace(Ctx* c, hipStream_t stream, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,

@@ -120,7 +120,7 @@ int main(int argc, char** argv) {
                 a_[a] = s[a] * iv[a];
                 b_[a] = fmaf(p[a], iv[a], nv[a]);
             }
-            const float tlim = tmax;  // the box padding is the slack (see node_step in csrc/path_b.hip)
+            const float tlim = tmax;  // the box padding is the slack (see node_step in csrc/pt_traverse.h)
             uint32_t inner_hit = 0;   // bit (slot ^ oct_inv): inner child in `slot` was hit
             uint32_t leaf_hit = 0;    // bit slot: the leaf in `slot` was hit
             for (int slot = 0; slot < 8; slot++) {
@@ -133,7 +133,7 @@ int main(int argc, char** argv) {
                     tn = std::fmax(tn, t_near);
                     tf = std::fmin(tf, t_far);
                 }
-                if (std::signbit(tf - tn)) continue;  // the kernels collect sign bits of tf - tn (node_step in csrc/path_b.hip)
+                if (std::signbit(tf - tn)) continue;  // the kernels collect sign bits of tf - tn (node_step in csrc/pt_traverse.h)
                 if (inner) inner_hit |= 1u << ((uint32_t)slot ^ oct_inv);
                 else leaf_hit |= 1u << slot;
             }
