@@ -453,6 +453,55 @@ int rt_query_points_device(rt_ctx* ctx, const void* points_dev, const void* rmax
                            const rt_point_query_params* params /* NULL = defaults */, void* dist_out_dev, void* tri_out_dev,
                            void* point_out_dev /* may be NULL */);
 int rt_get_point_query_stats(rt_ctx* ctx, rt_point_query_stats* stats); /* synchronises the stream; the last query */
+/* Inside/outside queries on device arrays: on which side of the current mesh's surface does each of n caller-supplied
+ * points lie?  Enqueued on the context's stream behind the work already there; no host synchronisation, and no allocation after the
+ * first query of a mesh or size class.  points_dev: n x 3 f32, device memory of the context's device, only read.  For point i and each
+ * of three fixed directions D[k] (csrc/ray_parity.h) crossings(i, k) = the number of triangles that the ray / triangle test of
+ * rt_query_rays_device accepts with t > 0 for the ray from the point along D[k], without an upper limit; inside_out_dev[i] (i32) = the
+ * majority of the three parities crossings(i, k) & 1: 1 inside, 0 outside.  The answer is defined on every mesh as this parity of
+ * crossings and does not depend on the tree; it means "inside" on closed meshes (every edge shared by two triangles).  Three rays and
+ * not one because the triangle test is not watertight: a single ray through a shared edge or a vertex may count it twice or not at all.
+ * The third ray is walked only where the first two parities disagree (the majority is the same).  crossings_out_dev (n x 3 i32, may be
+ * NULL): all three rays are walked for every point and crossings_out_dev[3 i + k] = crossings(i, k); inside_out_dev is the same either
+ * way.  dist_inout_dev (n f32, may be NULL; read and written): entry i is read first - +inf: the point is not walked, inside_out =
+ * RT_POINT_MISS, the entry stays +inf, counted in skipped_points; NaN: not walked, inside_out = RT_POINT_INVALID, counted in
+ * invalid_points; anything else: the entry is negated when the point is inside (an unsigned distance becomes a signed one) and is left
+ * as it is when outside.  A point with a non-finite component or a component beyond 32 x max(1, largest |vertex coordinate| of the
+ * mesh) - the reach of rt_query_rays_device - is not walked: inside_out = RT_POINT_INVALID, its crossings_out and dist_inout entries
+ * are not written, and it is counted in invalid_points.  Nothing beyond element n - 1 of an output is written.  The caller keeps all
+ * arrays alive until the stream has passed the call; lifetime rules against rt_set_mesh* are rt_render_pt_device's.  Works on every
+ * mesh (host-built single- and two-level, device-built, refitted, with surfaces); reads the mesh only, so a shared mesh stays shared.
+ * Errors, all before anything is enqueued or written: RT_ERR_INVALID (a NULL context; a NULL (where not allowed), host or other-device
+ * pointer, an allocation shorter than n rows, n above 2^30, count_traversal above 1, tune_refill_min above 64, tune_blocks_per_cu above
+ * 8, tune_lds_stack above 78), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch).  n == 0: RT_OK, nothing is done.
+ * rt_query_signed_distance_device is exactly rt_query_points_device(points_dev, rmax_dev, n, point_params, sdist_out_dev, tri_out_dev,
+ * point_out_dev) followed by rt_query_sides_device(points_dev, n, side_params, inside_out_dev, NULL, sdist_out_dev): sdist_out_dev[i] =
+ * the distance to the nearest triangle, negative inside; with rmax_dev a narrow-band signed distance, the points beyond the band (+inf)
+ * cost no ray walk.  inside_out_dev may be NULL here.  Everything that can refuse either step - and the first-use allocations of
+ * both - comes before the first step is enqueued, so a refused call has written nothing.  rt_get_point_query_stats and
+ * rt_get_side_query_stats then report the two steps of this call. */
+typedef struct rt_side_query_params {
+    uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_ray_query_params */
+    uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
+} rt_side_query_params;
+typedef struct rt_side_query_stats {
+    uint64_t points, invalid_points;     /* the last query with n > 0: points asked, points answered RT_POINT_INVALID */
+    uint64_t skipped_points;             /* not walked because their dist_inout entry was +inf (answered RT_POINT_MISS) */
+    uint64_t walks;                      /* ray walks: 2 per walked point + third_walks, or 3 per walked point with crossings_out_dev */
+    uint64_t third_walks;                /* points whose first two parities disagreed: rare on closed meshes, a diagnostic for leaky or open ones */
+    uint64_t nodes_visited, tris_tested; /* count_traversal = 1 only: node records fetched, triangles tested, over all walks */
+    uint32_t stack_overflow;             /* must be 0 */
+    uint32_t launches;                   /* kernel launches of that query */
+    float ms;                            /* HIP-event time of its launch */
+} rt_side_query_stats;
+int rt_default_side_query_params(rt_side_query_params* p);
+int rt_query_sides_device(rt_ctx* ctx, const void* points_dev, uint32_t n, const rt_side_query_params* params /* NULL = defaults */,
+                          void* inside_out_dev, void* crossings_out_dev /* may be NULL */, void* dist_inout_dev /* may be NULL */);
+int rt_query_signed_distance_device(rt_ctx* ctx, const void* points_dev, const void* rmax_dev /* may be NULL */, uint32_t n,
+                                    const rt_point_query_params* point_params /* NULL = defaults */,
+                                    const rt_side_query_params* side_params /* NULL = defaults */, void* sdist_out_dev, void* tri_out_dev,
+                                    void* point_out_dev /* may be NULL */, void* inside_out_dev /* may be NULL */);
+int rt_get_side_query_stats(rt_ctx* ctx, rt_side_query_stats* stats); /* synchronises the stream; the last query */
 /* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */

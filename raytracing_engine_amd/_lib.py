@@ -122,6 +122,20 @@ class PointQueryStats(C.Structure):  # rt_point_query_stats
 
 POINT_MISS, POINT_INVALID = RAY_MISS, RAY_INVALID  # RT_POINT_MISS, RT_POINT_INVALID
 
+
+class SideQueryParams(C.Structure):  # rt_side_query_params
+    _fields_ = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
+                ("count_traversal", C.c_uint32)]
+
+
+class SideQueryStats(C.Structure):  # rt_side_query_stats
+    _fields_ = [("points", C.c_uint64), ("invalid_points", C.c_uint64), ("skipped_points", C.c_uint64), ("walks", C.c_uint64), ("third_walks", C.c_uint64),
+                ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64), ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 assert C.sizeof(MutableData) == 656 and C.sizeof(Material) == 32 and C.sizeof(Object) == 16 and C.sizeof(Light) == 32
 
 # every symbol include/rt_abi.h declares: name -> (restype, argtypes)
@@ -180,6 +194,10 @@ PROTOTYPES = {
     "rt_default_point_query_params": (C.c_int, [C.POINTER(PointQueryParams)]),
     "rt_query_points_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(PointQueryParams), _vp, _vp, _vp]),
     "rt_get_point_query_stats": (C.c_int, [_vp, C.POINTER(PointQueryStats)]),
+    "rt_default_side_query_params": (C.c_int, [C.POINTER(SideQueryParams)]),
+    "rt_query_sides_device": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(SideQueryParams), _vp, _vp, _vp]),
+    "rt_query_signed_distance_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(PointQueryParams), C.POINTER(SideQueryParams), _vp, _vp, _vp, _vp]),
+    "rt_get_side_query_stats": (C.c_int, [_vp, C.POINTER(SideQueryStats)]),
     "rt_trace_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32)]),
     "rt_trace_rays_counted": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32), _u32p]),
 }

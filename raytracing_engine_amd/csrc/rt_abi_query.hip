@@ -1,4 +1,5 @@
-// rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays and closest points (§6.14).
+// rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14) and
+// sides (§6.15).
 // A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here.
 #include <algorithm>
 
@@ -13,7 +14,7 @@ namespace {
 constexpr uint32_t kMaxQueryItems = 1u << 30;  // stream_entry() of a dry reservation stays below 2^32
 constexpr uint32_t kQueryRefillMin = 24;       // idle lanes per wave that trigger a refill in the query kernels (the render kernels' default)
 
-// What both parameter structs are checked for, in the order the refusals have: `flag` is the kind's own switch (any_hit, count_traversal)
+// What every parameter struct is checked for, in the order the refusals have: `flag` is the kind's own switch (any_hit, count_traversal)
 template <class Params>
 int check_query_params(Ctx* c, uint32_t n, const Params& prm, uint32_t flag, const char* flag_name) {
     if (!c->pt.mesh().n_tris) return c->fail(RT_ERR_STATE, "rt_set_mesh has not been called");
@@ -25,30 +26,116 @@ int check_query_params(Ctx* c, uint32_t n, const Params& prm, uint32_t flag, con
     return RT_OK;
 }
 
-// After the kind's array checks.  What can still refuse comes first: the device block and the events (first query of the kind), the
-// stack of stack_need entries per lane.  Then the enqueue: clear the block, launch(head, stats, grid, stack, refill_min's low byte)
-// between the two events, remember that there is something to read
-template <class Params, class Launch>
-int enqueue_query(Ctx* c, QueryState& qs, uint32_t n, const Params& prm, uint32_t stack_need, const char* range, Launch&& launch) {
+// A query that nothing can refuse any more: its stack, its persistent grid, its refill threshold
+struct QueryPlan {
+    rt::StackCfg sk;
+    uint32_t grid, refill_min;
+};
+
+// After the kind's array checks, what can still refuse: the device block and the events (first query of the kind), the stack of
+// stack_need entries per lane.  Enqueues nothing and writes nothing the caller can see.
+template <class Params>
+int prepare_query(Ctx* c, QueryState& qs, uint32_t n, const Params& prm, uint32_t stack_need, QueryPlan* plan) {
     if (!qs.block) {
         if (!dalloc(qs.block, rt::query_block_bytes(qs.n_counters))) return c->fail(RT_ERR_OOM, "%s stream heads", qs.name);
         for (hipEvent_t& e : qs.ev)
             if (!e) RT_HIP(c, hipEventCreate(&e));
     }
-    rt::StackCfg sk{};
-    uint32_t grid = 0;
-    if (int rc = rt::pt_stack_config(c, stack_need, qs.fixed_lds_bytes, qs.spill_halves, prm.tune_lds_stack, prm.tune_blocks_per_cu, (uint64_t)n, &sk, &grid)) return rc;
-    grid = std::min<uint32_t>(grid, (n + 255u) / 256u);
-    if (prm.tune_max_blocks) grid = std::min<uint32_t>(grid, prm.tune_max_blocks);
-    const uint32_t refill_min = prm.tune_refill_min & 0xffu ? prm.tune_refill_min & 0xffu : kQueryRefillMin;
+    plan->sk = rt::StackCfg{};
+    plan->grid = 0;
+    if (int rc = rt::pt_stack_config(c, stack_need, qs.fixed_lds_bytes, qs.spill_halves, prm.tune_lds_stack, prm.tune_blocks_per_cu, (uint64_t)n, &plan->sk, &plan->grid)) return rc;
+    plan->grid = std::min<uint32_t>(plan->grid, (n + 255u) / 256u);
+    if (prm.tune_max_blocks) plan->grid = std::min<uint32_t>(plan->grid, prm.tune_max_blocks);
+    plan->refill_min = prm.tune_refill_min & 0xffu ? prm.tune_refill_min & 0xffu : kQueryRefillMin;
+    return RT_OK;
+}
+
+// The enqueue: clear the block, launch(head, stats, grid, stack, refill_min's low byte) between the two events, remember that there
+// is something to read.  The spill columns are taken now: a plan made before another kind's plan grew them still launches on what is there.
+template <class Launch>
+int run_query(Ctx* c, QueryState& qs, QueryPlan plan, const char* range, Launch&& launch) {
+    plan.sk.spill = c->pt.d_spill.get();
     uint32_t* head = reinterpret_cast<uint32_t*>(qs.block.get());
     unsigned long long* stats = reinterpret_cast<unsigned long long*>(qs.block.get() + rt::kQueryHeadBytes);
     rt::RoctxRange rr(range);
     RT_HIP(c, hipMemsetAsync(qs.block.get(), 0, rt::query_block_bytes(qs.n_counters), c->stream));
     RT_HIP(c, hipEventRecord(qs.ev[0], c->stream));
-    if (int rc = launch(head, stats, grid, sk, refill_min)) return rc;
+    if (int rc = launch(head, stats, plan.grid, plan.sk, plan.refill_min)) return rc;
     RT_HIP(c, hipEventRecord(qs.ev[1], c->stream));
     qs.pending = true;
+    return RT_OK;
+}
+
+template <class Params, class Launch>
+int enqueue_query(Ctx* c, QueryState& qs, uint32_t n, const Params& prm, uint32_t stack_need, const char* range, Launch&& launch) {
+    QueryPlan plan{};
+    if (int rc = prepare_query(c, qs, n, prm, stack_need, &plan)) return rc;
+    return run_query(c, qs, plan, range, launch);
+}
+
+// ---- closest points: the array checks and the plan (everything that can refuse), then the enqueue ----
+int prepare_points(Ctx* c, const void* points, const void* rmax, uint32_t n, const rt_point_query_params& prm, void* dist_out, void* tri_out, void* point_out,
+                   rt::PointQuery* q, QueryPlan* plan) {
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, points, (size_t)n * 12, "points_dev")) return rc;
+    if (rmax)
+        if (int rc = rt::check_device_array(c, rmax, (size_t)n * 4, "rmax_dev")) return rc;
+    if (int rc = rt::check_device_array(c, dist_out, (size_t)n * 4, "dist_out_dev")) return rc;
+    if (int rc = rt::check_device_array(c, tri_out, (size_t)n * 4, "tri_out_dev")) return rc;
+    if (point_out)
+        if (int rc = rt::check_device_array(c, point_out, (size_t)n * 12, "point_out_dev")) return rc;
+    *q = rt::PointQuery{};
+    q->points = static_cast<const float*>(points);
+    q->rmax = static_cast<const float*>(rmax);
+    q->dist_out = static_cast<float*>(dist_out);
+    q->tri_out = static_cast<int*>(tri_out);
+    q->point_out = static_cast<float*>(point_out);
+    q->n = n;
+    q->reach = rt::kCameraReach * mesh.maxabs;
+    // point_stack_need entries per lane: one pending sibling each, not stack_need's one group per level; the spill columns grow to it once per mesh
+    return prepare_query(c, c->pt.point_query, n, prm, rt::point_stack_need(mesh.depth), plan);
+}
+
+int run_points(Ctx* c, const rt::PointQuery& q, const rt_point_query_params& prm, const QueryPlan& plan) {
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_points(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
+    };
+    if (int rc = run_query(c, c->pt.point_query, plan, "rt.path_b.query_points", launch)) return rc;
+    c->pt.point_query_stats = rt_point_query_stats{};
+    c->pt.point_query_stats.points = q.n;
+    c->pt.point_query_stats.launches = 1;
+    return RT_OK;
+}
+
+// ---- sides: the same two steps ----
+int prepare_sides(Ctx* c, const void* points, uint32_t n, const rt_side_query_params& prm, void* inside_out, bool need_inside, void* crossings_out, void* dist_inout,
+                  rt::SideQuery* q, QueryPlan* plan) {
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, points, (size_t)n * 12, "points_dev")) return rc;
+    if (inside_out || need_inside)
+        if (int rc = rt::check_device_array(c, inside_out, (size_t)n * 4, "inside_out_dev")) return rc;
+    if (crossings_out)
+        if (int rc = rt::check_device_array(c, crossings_out, (size_t)n * 12, "crossings_out_dev")) return rc;
+    if (dist_inout)
+        if (int rc = rt::check_device_array(c, dist_inout, (size_t)n * 4, "dist_inout_dev")) return rc;
+    *q = rt::SideQuery{};
+    q->points = static_cast<const float*>(points);
+    q->inside_out = static_cast<int*>(inside_out);
+    q->crossings_out = static_cast<int*>(crossings_out);
+    q->dist_inout = static_cast<float*>(dist_inout);
+    q->n = n;
+    q->reach = rt::kCameraReach * mesh.maxabs;
+    return prepare_query(c, c->pt.side_query, n, prm, mesh.stack_need, plan);  // a ray walk: one group per level
+}
+
+int run_sides(Ctx* c, const rt::SideQuery& q, const rt_side_query_params& prm, const QueryPlan& plan) {
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_sides(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
+    };
+    if (int rc = run_query(c, c->pt.side_query, plan, "rt.path_b.query_sides", launch)) return rc;
+    c->pt.side_query_stats = rt_side_query_stats{};
+    c->pt.side_query_stats.points = q.n;
+    c->pt.side_query_stats.launches = 1;
     return RT_OK;
 }
 
@@ -66,7 +153,7 @@ int read_query(Ctx* c, QueryState& qs, unsigned long long* counters, float* ms) 
 
 namespace rt {
 void query_free(Ctx* c) {
-    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query}) {
+    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query}) {
         qs->block.reset();
         for (hipEvent_t& e : qs->ev) {
             if (e) (void)hipEventDestroy(e);
@@ -149,31 +236,10 @@ int rt_query_points_device(rt_ctx* ctx, const void* points, const void* rmax, ui
     if (int rc = check_query_params(c, n, *prm, prm->count_traversal, "count_traversal")) return rc;
     if (n == 0) return RT_OK;
     if (int rc = rt::bind(c)) return rc;
-    const rt::DeviceMesh& mesh = c->pt.mesh();
-    if (int rc = rt::check_device_array(c, points, (size_t)n * 12, "points_dev")) return rc;
-    if (rmax)
-        if (int rc = rt::check_device_array(c, rmax, (size_t)n * 4, "rmax_dev")) return rc;
-    if (int rc = rt::check_device_array(c, dist_out, (size_t)n * 4, "dist_out_dev")) return rc;
-    if (int rc = rt::check_device_array(c, tri_out, (size_t)n * 4, "tri_out_dev")) return rc;
-    if (point_out)
-        if (int rc = rt::check_device_array(c, point_out, (size_t)n * 12, "point_out_dev")) return rc;
     rt::PointQuery q{};
-    q.points = static_cast<const float*>(points);
-    q.rmax = static_cast<const float*>(rmax);
-    q.dist_out = static_cast<float*>(dist_out);
-    q.tri_out = static_cast<int*>(tri_out);
-    q.point_out = static_cast<float*>(point_out);
-    q.n = n;
-    q.reach = rt::kCameraReach * mesh.maxabs;
-    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
-        return rt::launch_pt_query_points(c, rt::scene_view(mesh), q, prm->count_traversal != 0u, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
-    };
-    // point_stack_need entries per lane: one pending sibling each, not stack_need's one group per level; the spill columns grow to it once per mesh
-    if (int rc = enqueue_query(c, c->pt.point_query, n, *prm, rt::point_stack_need(mesh.depth), "rt.path_b.query_points", launch)) return rc;
-    c->pt.point_query_stats = rt_point_query_stats{};
-    c->pt.point_query_stats.points = n;
-    c->pt.point_query_stats.launches = 1;
-    return RT_OK;
+    QueryPlan plan{};
+    if (int rc = prepare_points(c, points, rmax, n, *prm, dist_out, tri_out, point_out, &q, &plan)) return rc;
+    return run_points(c, q, *prm, plan);
 }
 
 int rt_get_point_query_stats(rt_ctx* ctx, rt_point_query_stats* stats) {
@@ -187,6 +253,67 @@ int rt_get_point_query_stats(rt_ctx* ctx, rt_point_query_stats* stats) {
         s.stack_overflow = (uint32_t)st[rt::PQ_STAT_OVERFLOW];
         s.nodes_visited = st[rt::PQ_STAT_NODES];
         s.tris_tested = st[rt::PQ_STAT_TRIS];
+    }
+    *stats = s;
+    return RT_OK;
+}
+
+int rt_default_side_query_params(rt_side_query_params* p) {
+    if (!p) return RT_ERR_INVALID;
+    *p = rt_side_query_params{};
+    return RT_OK;
+}
+
+int rt_query_sides_device(rt_ctx* ctx, const void* points, uint32_t n, const rt_side_query_params* prm, void* inside_out, void* crossings_out, void* dist_inout) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    rt_side_query_params defaults{};
+    if (!prm) prm = &defaults;
+    if (int rc = check_query_params(c, n, *prm, prm->count_traversal, "count_traversal")) return rc;
+    if (n == 0) return RT_OK;
+    if (int rc = rt::bind(c)) return rc;
+    rt::SideQuery q{};
+    QueryPlan plan{};
+    if (int rc = prepare_sides(c, points, n, *prm, inside_out, true, crossings_out, dist_inout, &q, &plan)) return rc;
+    return run_sides(c, q, *prm, plan);
+}
+
+// rt_query_points_device, then rt_query_sides_device on its distances; both steps' refusals and first-use allocations before the first enqueue
+int rt_query_signed_distance_device(rt_ctx* ctx, const void* points, const void* rmax, uint32_t n, const rt_point_query_params* pprm, const rt_side_query_params* sprm,
+                                    void* sdist_out, void* tri_out, void* point_out, void* inside_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    rt_point_query_params pdefaults{};
+    rt_side_query_params sdefaults{};
+    if (!pprm) pprm = &pdefaults;
+    if (!sprm) sprm = &sdefaults;
+    if (int rc = check_query_params(c, n, *pprm, pprm->count_traversal, "count_traversal")) return rc;
+    if (int rc = check_query_params(c, n, *sprm, sprm->count_traversal, "count_traversal")) return rc;
+    if (n == 0) return RT_OK;
+    if (int rc = rt::bind(c)) return rc;
+    rt::PointQuery pq{};
+    rt::SideQuery sq{};
+    QueryPlan pplan{}, splan{};
+    if (int rc = prepare_points(c, points, rmax, n, *pprm, sdist_out, tri_out, point_out, &pq, &pplan)) return rc;
+    if (int rc = prepare_sides(c, points, n, *sprm, inside_out, false, nullptr, sdist_out, &sq, &splan)) return rc;
+    if (int rc = run_points(c, pq, *pprm, pplan)) return rc;
+    return run_sides(c, sq, *sprm, splan);
+}
+
+int rt_get_side_query_stats(rt_ctx* ctx, rt_side_query_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    rt_side_query_stats& s = c->pt.side_query_stats;
+    if (c->pt.side_query.pending) {
+        unsigned long long st[rt::SQ_STAT_WORDS] = {};
+        if (int rc = read_query(c, c->pt.side_query, st, &s.ms)) return rc;
+        s.invalid_points = st[rt::SQ_STAT_INVALID];
+        s.skipped_points = st[rt::SQ_STAT_SKIPPED];
+        s.walks = st[rt::SQ_STAT_WALKS];
+        s.third_walks = st[rt::SQ_STAT_THIRD];
+        s.stack_overflow = (uint32_t)st[rt::SQ_STAT_OVERFLOW];
+        s.nodes_visited = st[rt::SQ_STAT_NODES];
+        s.tris_tested = st[rt::SQ_STAT_TRIS];
     }
     *stats = s;
     return RT_OK;

@@ -224,6 +224,18 @@ enum { PQ_STAT_INVALID = 0, PQ_STAT_OVERFLOW = 1, PQ_STAT_NODES = 2, PQ_STAT_TRI
 // most seven for each of the levels 2 .. depth.
 constexpr uint32_t point_stack_need(uint32_t depth) { return depth > 1u ? 7u * (depth - 1u) : 1u; }
 
+// rt_query_sides_device: the points of one query and where their answers go.  Point i is queue entry i.
+struct SideQuery {
+    const float* points;  // n x 3
+    int* inside_out;      // n, or nullptr (rt_query_signed_distance_device without inside_out_dev)
+    int* crossings_out;   // n x 3, or nullptr: the third walk only where the first two parities disagree
+    float* dist_inout;    // n, or nullptr: +inf = not walked, NaN = invalid, else the sign is written into it
+    uint32_t n;
+    float reach;  // |component| limit: kCameraReach x the mesh's maxabs
+};
+// Counters of an inside/outside query
+enum { SQ_STAT_INVALID = 0, SQ_STAT_OVERFLOW = 1, SQ_STAT_NODES = 2, SQ_STAT_TRIS = 3, SQ_STAT_SKIPPED = 4, SQ_STAT_WALKS = 5, SQ_STAT_THIRD = 6, SQ_STAT_WORDS = 7 };
+
 struct MeshHost {  // host side of a two-level mesh: what rt_update_mesh_chunk needs to rebuild one chunk
     TwoLevelBvh tl;
     std::vector<float> v0, e1, e2;          // original triangle order
@@ -258,7 +270,7 @@ constexpr size_t kQueryHeadBytes = (size_t)PT_HEADS * PT_HEAD_STRIDE * sizeof(ui
 constexpr size_t query_block_bytes(uint32_t n_counters) { return kQueryHeadBytes + (size_t)n_counters * sizeof(unsigned long long); }
 struct QueryState {
     QueryState(uint32_t k, const char* what, uint32_t lds, uint32_t halves) : n_counters(k), name(what), fixed_lds_bytes(lds), spill_halves(halves) {}
-    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS
+    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS / SQ_STAT_WORDS
     const char* name;     // for messages
     uint32_t fixed_lds_bytes, spill_halves;  // pt_stack_config's: the kernel's LDS beside the stacks, the sets of spill columns it is given
     DevPtr<char> block;
@@ -310,11 +322,12 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     DevPtr<uint32_t> d_ctr;
     DevPtr<unsigned long long> d_stats;  // PT_STAT_WORDS words
     rt_pt_stats stats{};
-    // rt_query_rays_device / rt_query_points_device: what is in flight, and the statistics of the last query of each kind
-    // (rays: the 2 KiB octant table, two spill halves as the frames hold; points: no table, one set of columns)
-    QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u};
+    // rt_query_rays_device / rt_query_points_device / rt_query_sides_device: what is in flight, and the statistics of the last query of each kind
+    // (rays: the 2 KiB octant table, two spill halves as the frames hold; points and sides: no table, one set of columns)
+    QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u}, side_query{SQ_STAT_WORDS, "side-query", 0u, 1u};
     rt_ray_query_stats ray_query_stats{};
     rt_point_query_stats point_query_stats{};
+    rt_side_query_stats side_query_stats{};
 };
 
 struct Ctx {
@@ -394,7 +407,7 @@ int launch_detile(Ctx* c, const float* tiles, uint32_t n_ranks, uint32_t tiles_p
 int launch_to_rgba8(Ctx* c, const float* rgb, uint8_t* rgba, uint64_t n_pixels);
 
 // path_b.hip (generate, shade, scatter_surfaces, resolve), pt_trace.hip (trace, trace_fused, pool_lds_bytes, trace_rays, query_rays), pt_packet.hip (trace_packet),
-// pt_point_query.hip (query_points): every unit ends with the launchers of its own kernels
+// pt_point_query.hip (query_points), pt_side_query.hip (query_sides): every unit ends with the launchers of its own kernels
 int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* queue, uint32_t* ctr);
 int launch_pt_trace(Ctx* c, hipStream_t stream, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,
@@ -416,8 +429,10 @@ int launch_pt_query_rays(Ctx* c, const PtScene& sc, const RayQuery& q, bool any_
                          const StackCfg& sk, uint32_t refill_min);
 int launch_pt_query_points(Ctx* c, const PtScene& sc, const PointQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                            const StackCfg& sk, uint32_t refill_min);
+int launch_pt_query_sides(Ctx* c, const PtScene& sc, const SideQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                          const StackCfg& sk, uint32_t refill_min);  // q.crossings_out != nullptr: all three walks for every point
 void pt_free(Ctx* c);
-void query_free(Ctx* c);  // rt_abi_query.hip: both query kinds' device blocks and events
+void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block and events
 
 // |coordinate| limit of a camera position, a query ray's origin and a query point in units of DeviceMesh::maxabs (plan_frame, rt_abi_pt.hip)
 constexpr float kCameraReach = 32.0f;

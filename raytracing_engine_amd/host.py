@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (Config, Light, Material, MutableData, Object, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
-                   RtError, Stats)
+                   RtError, SideQueryParams, SideQueryStats, Stats)
 
 # src/main.rs:343-364
 SPEED_MOVEMENT = 25.0
@@ -450,7 +450,8 @@ class Renderer:
             raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
     def _query_tune(self, params, tune, method):
-        """The tune_* keywords of `method` (query_rays / query_points) into its parameter struct; TypeError for any other keyword."""
+        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance) into its parameter struct;
+        TypeError for any other keyword."""
         for k, v in tune.items():
             if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
                 raise TypeError(f"{method}() got an unexpected keyword argument {k!r}")
@@ -551,6 +552,71 @@ class Renderer:
         tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
         s = PointQueryStats()
         self._check(self._lib.rt_get_point_query_stats(self._ctx, C.byref(s)))
+        return s.as_dict()
+
+    def query_sides(self, points, out=None, sync=True, want_crossings=False, count_traversal=False, **tune):
+        """On which side of the current mesh's surface does each point lie?  (rt_query_sides_device)  points: a float32
+        torch tensor on this renderer's device, contiguous, (n, 3) or flat.  Returns int32 `inside` (1 inside, 0 outside): the majority of
+        the parities of the triangles crossed by three fixed rays from the point - defined on every mesh as that parity of crossings,
+        "inside" on closed meshes.  want_crossings=True: returns (inside, crossings) with the (n, 3) int32 crossing counts of the three
+        rays (all three are then walked for every point; inside is the same).  Invalid points (a non-finite component, a component beyond
+        32 x the mesh's largest |coordinate|) get POINT_INVALID = -2 and their crossings are not written.  out: the tensor(s) to fill -
+        inside, or (inside, crossings) - instead of new ones.  sync as for query_points.  count_traversal=True: side_query_stats()
+        reports nodes_visited / tris_tested.  tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of
+        rt_side_query_params."""
+        import torch
+
+        n = self._device_rows(points, "points", 3)
+        p = SideQueryParams()
+        p.count_traversal = int(bool(count_traversal))
+        self._query_tune(p, tune, "query_sides")
+        if want_crossings:
+            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+                raise ValueError("out must be the pair (inside, crossings) with want_crossings=True")
+            inside, crossings = out if out is not None else (None, None)
+        else:
+            if isinstance(out, (tuple, list)):
+                raise ValueError("out must be the inside tensor, or (inside, crossings) with want_crossings=True")
+            inside, crossings = out, None
+        inside = self._query_out(inside, "out inside", n, torch.int32, points.device)
+        if want_crossings:
+            if crossings is None:
+                crossings = torch.empty((n, 3), dtype=torch.int32, device=points.device)
+            else:
+                if not isinstance(crossings, torch.Tensor) or crossings.dim() != 2 or crossings.shape[1] != 3:
+                    raise ValueError(f"out crossings must have shape ({n}, 3)")
+                self._device_i32(crossings.view(-1) if crossings.is_contiguous() else crossings, "out crossings", 3 * n)
+        self._query_call(sync, self._lib.rt_query_sides_device, points, n, C.byref(p), inside, crossings, None)
+        return (inside, crossings) if want_crossings else inside
+
+    def query_signed_distance(self, points, rmax=None, out=None, sync=True, want_points=True, **tune):
+        """query_points followed by query_sides on its distances (rt_query_signed_distance_device): returns (sdist, tri,
+        point) as query_points returns (dist, tri, point), with sdist negative where the point is inside.  With rmax a narrow-band
+        signed distance: points beyond the band stay +inf / POINT_MISS and cost no ray walk.  out: (sdist, tri, point), or (sdist, tri)
+        with want_points=False.  tune applies to both steps; point_query_stats() and side_query_stats() report them."""
+        import torch
+
+        n = self._device_rows(points, "points", 3)
+        if rmax is not None and (self._device_rows(rmax, "rmax", 1) != n or rmax.dim() != 1):
+            raise ValueError(f"rmax must have shape ({n},), got {tuple(rmax.shape)}")
+        pp, sp = PointQueryParams(), SideQueryParams()
+        self._query_tune(pp, tune, "query_signed_distance")
+        self._query_tune(sp, tune, "query_signed_distance")
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != (3 if want_points else 2)):
+            raise ValueError("out must be (sdist, tri, point), or the pair (sdist, tri) with want_points=False")
+        dist, tri, pt = (tuple(out) + (None,))[:3] if out is not None else (None, None, None)
+        dist = self._query_out(dist, "out sdist", n, torch.float32, points.device)
+        tri = self._query_out(tri, "out tri", n, torch.int32, points.device)
+        if want_points:
+            pt = self._query_out(pt, "out point", n, torch.float32, points.device, cols=3)
+        self._query_call(sync, self._lib.rt_query_signed_distance_device, points, rmax, n, C.byref(pp), C.byref(sp), dist, tri, pt, None)
+        return dist, tri, pt
+
+    def side_query_stats(self):
+        """rt_side_query_stats of the last inside/outside query as a dict (waits for it): points, invalid_points, skipped_points, walks,
+        third_walks, nodes_visited, tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
+        s = SideQueryStats()
+        self._check(self._lib.rt_get_side_query_stats(self._ctx, C.byref(s)))
         return s.as_dict()
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):

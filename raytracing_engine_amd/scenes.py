@@ -156,6 +156,53 @@ def terrain_scene(grid=708, seed=1, light_emission=(6.0, 6.0, 6.0)):
     return verts, albedo, emission
 
 
+def planet_scene(n_tris=1000000, seed=1, radius=10.0, centre=(0.0, 20.0, 0.0), relief=0.12, light_emission=(6.0, 6.0, 6.0)):
+    """A CLOSED surface (terrain_scene is an open height field): a UV sphere of `stacks` x 2 `stacks` cells, stacks =
+    round(sqrt(n_tris / 4)), whose vertices are pushed along their directions by three octaves of hashed 3-D value noise (radius x
+    (1 +- relief)), so that the surface has hills and hollows at several scales and still bounds a volume: every edge is shared by
+    exactly two triangles, bit for bit (vertices are shared by index, the poles are single vertices), and all triangles are wound
+    outward.  4 stacks (stacks - 1) triangles: 1 000 000 gives stacks = 500 and 998 000.  The last triangle is emissive (the mesh
+    needs one light and stays closed).  Returns (verts[n,9], albedo[n,3], emission[n,3]) float32."""
+    f = np.float32
+    stacks = max(3, int(round((int(n_tris) / 4.0) ** 0.5)))
+    slices = 2 * stacks
+
+    def value_noise3(q, cells, stream):  # q in [-1, 1]^3
+        lat = _uniform(seed, stream, (cells + 1) ** 3).astype(np.float64).reshape(cells + 1, cells + 1, cells + 1)
+        t = (q + 1.0) * (0.5 * cells)
+        i = np.minimum(t.astype(np.int64), cells - 1)
+        fr = t - i
+        fr = fr * fr * (3 - 2 * fr)
+        out = 0.0
+        for dx in (0, 1):
+            for dy in (0, 1):
+                for dz in (0, 1):
+                    w = np.where(dx, fr[..., 0], 1 - fr[..., 0]) * np.where(dy, fr[..., 1], 1 - fr[..., 1]) * np.where(dz, fr[..., 2], 1 - fr[..., 2])
+                    out = out + w * lat[i[..., 0] + dx, i[..., 1] + dy, i[..., 2] + dz]
+        return out
+
+    th = np.pi * np.arange(1, stacks, dtype=np.float64) / stacks
+    ph = 2 * np.pi * np.arange(slices, dtype=np.float64) / slices
+    dirs = np.stack([np.sin(th)[:, None] * np.cos(ph)[None, :], np.cos(th)[:, None] * np.ones_like(ph)[None, :], np.sin(th)[:, None] * np.sin(ph)[None, :]], -1)
+    dirs = np.concatenate([dirs.reshape(-1, 3), [[0.0, 1.0, 0.0], [0.0, -1.0, 0.0]]])  # the rings, then the two poles
+    h = (4.0 * value_noise3(dirs, 3, 90) + 2.0 * value_noise3(dirs, 12, 91) + 1.0 * value_noise3(dirs, 48, 92)) / 7.0  # in [0, 1)
+    P = (np.asarray(centre, np.float64) + dirs * (radius * (1.0 + relief * (2.0 * h - 1.0)))[:, None]).astype(f)
+    ring = np.arange((stacks - 1) * slices).reshape(stacks - 1, slices)
+    north, south = (stacks - 1) * slices, (stacks - 1) * slices + 1
+    nxt = np.roll(ring, -1, axis=1)  # the vertex one slice on, wrapping
+    a, b, c, d = ring[:-1], ring[1:], nxt[:-1], nxt[1:]  # (i, j), (i + 1, j), (i, j + 1), (i + 1, j + 1)
+    idx = np.concatenate([np.stack([a, d, b], -1).reshape(-1, 3), np.stack([a, c, d], -1).reshape(-1, 3),
+                          np.stack([np.full(slices, north), nxt[0], ring[0]], -1), np.stack([np.full(slices, south), ring[-1], nxt[-1]], -1)])
+    verts = P[idx].reshape(-1, 9)
+    m = len(verts)
+    u = [_uniform(seed, 93 + k, m) for k in range(3)]
+    albedo = (np.stack(u, 1) * f(0.4) + f(0.4)).astype(f)
+    emission = np.zeros((m, 3), f)
+    albedo[m - 1] = 0.0
+    emission[m - 1] = np.asarray(light_emission, f)
+    return np.ascontiguousarray(verts, f), albedo, emission
+
+
 def sliver_stack_scene(n_layers=2048, n_targets=48, seed=1):
     """Adversarial scene for the traversal's leaf-hit buffers: n_layers parallel triangles stacked along the view axis (y in [4, 6]),
     every one covering the half x + z < 0 of the square x, z in [-8, 8].  A ray through the other half passes through every
