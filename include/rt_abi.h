@@ -502,6 +502,62 @@ int rt_query_signed_distance_device(rt_ctx* ctx, const void* points_dev, const v
                                     const rt_side_query_params* side_params /* NULL = defaults */, void* sdist_out_dev, void* tri_out_dev,
                                     void* point_out_dev /* may be NULL */, void* inside_out_dev /* may be NULL */);
 int rt_get_side_query_stats(rt_ctx* ctx, rt_side_query_stats* stats); /* synchronises the stream; the last query */
+/* All-hits ray queries on device arrays: EVERY triangle of the current mesh that each of n caller-supplied rays passes
+ * through, counted and listed, not only the nearest.  Enqueued on the context's stream behind the work already there; no host
+ * synchronisation, and no allocation after the first query of a size class.  Ray i is origins_dev[i], dirs_dev[i] (n x 3 f32) and
+ * tmax_dev[i] (n f32, or NULL: +inf), exactly as rt_query_rays_device takes them, device memory of the context's device, only read.
+ * hits(i) = the triangles that the ray / triangle test of rt_query_rays_device (csrc/ray_parity.h: ray_tri_t) accepts with
+ * 0 < t < tmax[i], strict at both ends.  The answer is defined without the tree and does not depend on it; for that a limit shortens
+ * the list and not the walk (a segment costs what its whole ray costs).
+ *   rt_count_ray_hits_device: count_out_dev[i] (n i32, may be NULL) = |hits(i)|; offsets_out_dev (n + 1 i64, may be NULL): [i] = the
+ * exclusive prefix sum of the counts, [n] = their total; at least one of the two is required.
+ *   rt_fill_ray_hits_device: the hits of ray i, sorted ascending by (t, original triangle index), into elements [offsets_in_dev[i],
+ * offsets_in_dev[i + 1]) of t_out_dev (f32) and tri_out_dev (i32), arrays of `capacity` elements; offsets_in_dev (n + 1 i64) is read
+ * on the stream.  A ray whose slice ends beyond the arrays (offsets[i + 1] > capacity) writes NOTHING; every other ray's slice is
+ * complete and sorted: what a too small capacity leaves out never depends on the tree.  The caller sees offsets[n] > capacity, grows
+ * the arrays and calls this step again.  The step is memory-safe against offsets that it did not make: ray i writes its hit number j
+ * only while 0 <= offsets[i] and offsets[i] + j < offsets[i + 1] <= capacity; a slice shorter than its ray's hits keeps the first of
+ * them in (t, index) order and the others are counted in slice_overflow, which is 0 whenever the offsets are the count step's for
+ * the same rays and mesh.  capacity == 0: t_out_dev / tri_out_dev may be NULL, nothing is written.
+ *   rt_list_ray_hits_device is exactly rt_count_ray_hits_device(..., count_out_dev, offsets_out_dev) followed by
+ * rt_fill_ray_hits_device(..., offsets_out_dev, capacity, t_out_dev, tri_out_dev); everything that can refuse either step - and the
+ * first-use allocations of both - comes before the first step is enqueued, so a refused call has written nothing.
+ * A ray with a non-finite origin or direction component, a NaN tmax, or an origin component beyond 32 x max(1, largest |vertex
+ * coordinate| of the mesh) - rt_query_rays_device's rule - is not walked: count_out = RT_RAY_INVALID, it adds 0 to the offsets, writes
+ * no hit, and is counted in invalid_rays.  tmax = +inf is valid; tmax <= 0 and a zero direction give count 0.  Nothing beyond element
+ * n - 1 of count_out_dev, n of offsets_out_dev and capacity - 1 of the hit arrays is written.  The caller keeps all arrays alive until
+ * the stream has passed the call; lifetime rules against rt_set_mesh* are rt_render_pt_device's.  Works on every mesh (host-built
+ * single- and two-level, device-built, refitted, with surfaces); reads the mesh only, so a shared mesh stays shared.  Errors, all
+ * before anything is enqueued or written: RT_ERR_INVALID (a NULL context; a NULL (where not allowed), host or other-device pointer,
+ * an allocation shorter than n / n + 1 / capacity rows, n above 2^30, capacity above 2^40, count_traversal above 1, tune_refill_min above 64,
+ * tune_blocks_per_cu above 8, tune_lds_stack above 78), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch: 8 bytes per ray for the scan,
+ * grown by size class).  n == 0: RT_OK, nothing is done. */
+typedef struct rt_hit_query_params {
+    uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_ray_query_params */
+    uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
+} rt_hit_query_params;
+typedef struct rt_hit_query_stats {
+    uint64_t rays, invalid_rays;         /* the last call with n > 0: rays asked, rays answered RT_RAY_INVALID */
+    uint64_t hits;                       /* sum of |hits(i)| over the valid rays */
+    uint64_t hits_written;               /* fill step: entries written into the hit arrays */
+    uint64_t incomplete_rays;            /* fill step: rays with hits whose slice did not fit (offsets[i + 1] > capacity): nothing written */
+    uint64_t slice_overflow;             /* fill step: hits beyond the length of their ray's slice; 0 with the count step's offsets */
+    uint64_t nodes_visited, tris_tested; /* count_traversal = 1 only: node records fetched, triangles tested, over all walks of the call */
+    uint32_t stack_overflow;             /* must be 0 */
+    uint32_t launches;                   /* kernel launches of that call: 1 per walk, 3 for the scan */
+    float ms;                            /* HIP-event time from the first to the last launch of the call */
+} rt_hit_query_stats;
+int rt_default_hit_query_params(rt_hit_query_params* p);
+int rt_count_ray_hits_device(rt_ctx* ctx, const void* origins_dev, const void* dirs_dev, const void* tmax_dev /* may be NULL */, uint32_t n,
+                             const rt_hit_query_params* params /* NULL = defaults */, void* count_out_dev /* may be NULL */,
+                             void* offsets_out_dev /* may be NULL */);
+int rt_fill_ray_hits_device(rt_ctx* ctx, const void* origins_dev, const void* dirs_dev, const void* tmax_dev /* may be NULL */, uint32_t n,
+                            const rt_hit_query_params* params /* NULL = defaults */, const void* offsets_in_dev, uint64_t capacity,
+                            void* t_out_dev, void* tri_out_dev);
+int rt_list_ray_hits_device(rt_ctx* ctx, const void* origins_dev, const void* dirs_dev, const void* tmax_dev /* may be NULL */, uint32_t n,
+                            const rt_hit_query_params* params /* NULL = defaults */, void* count_out_dev /* may be NULL */,
+                            void* offsets_out_dev, uint64_t capacity, void* t_out_dev, void* tri_out_dev);
+int rt_get_hit_query_stats(rt_ctx* ctx, rt_hit_query_stats* stats); /* synchronises the stream; the last call */
 /* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */

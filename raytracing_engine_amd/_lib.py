@@ -136,6 +136,20 @@ class SideQueryStats(C.Structure):  # rt_side_query_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class HitQueryParams(C.Structure):  # rt_hit_query_params
+    _fields_ = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
+                ("count_traversal", C.c_uint32)]
+
+
+class HitQueryStats(C.Structure):  # rt_hit_query_stats
+    _fields_ = [("rays", C.c_uint64), ("invalid_rays", C.c_uint64), ("hits", C.c_uint64), ("hits_written", C.c_uint64), ("incomplete_rays", C.c_uint64),
+                ("slice_overflow", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64), ("stack_overflow", C.c_uint32),
+                ("launches", C.c_uint32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 assert C.sizeof(MutableData) == 656 and C.sizeof(Material) == 32 and C.sizeof(Object) == 16 and C.sizeof(Light) == 32
 
 # every symbol include/rt_abi.h declares: name -> (restype, argtypes)
@@ -198,6 +212,11 @@ PROTOTYPES = {
     "rt_query_sides_device": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(SideQueryParams), _vp, _vp, _vp]),
     "rt_query_signed_distance_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(PointQueryParams), C.POINTER(SideQueryParams), _vp, _vp, _vp, _vp]),
     "rt_get_side_query_stats": (C.c_int, [_vp, C.POINTER(SideQueryStats)]),
+    "rt_default_hit_query_params": (C.c_int, [C.POINTER(HitQueryParams)]),
+    "rt_count_ray_hits_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(HitQueryParams), _vp, _vp]),
+    "rt_fill_ray_hits_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(HitQueryParams), _vp, C.c_uint64, _vp, _vp]),
+    "rt_list_ray_hits_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(HitQueryParams), _vp, _vp, C.c_uint64, _vp, _vp]),
+    "rt_get_hit_query_stats": (C.c_int, [_vp, C.POINTER(HitQueryStats)]),
     "rt_trace_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32)]),
     "rt_trace_rays_counted": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32), _u32p]),
 }

@@ -845,6 +845,12 @@ size_t refit_scratch_bytes(uint32_t n_nodes) {
 
 size_t refit_scratch_size(uint32_t n_nodes) { return refit_scratch_bytes(n_nodes); }
 
+// the build's own three-launch scan for callers outside this unit (the hit queries' offsets, rt_abi_query.hip)
+size_t scan_u64_sums_words(size_t count) { return (count + kScanTile - 1) / kScanTile + 1; }
+int scan_u64_device(Ctx* c, const unsigned long long* in, unsigned long long* out, size_t count, unsigned long long* sums, unsigned long long* total) {
+    return scan<unsigned long long>(c, in, out, count, sums, total);
+}
+
 int refit_measure(Ctx* c, const float* verts, uint32_t n, void* scratch, hipEvent_t begin, float* maxabs) {
     Bump bump{static_cast<char*>(scratch), 0};
     float* part_max = bump.take<float>(kReduceBlocks);

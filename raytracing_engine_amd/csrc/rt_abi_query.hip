@@ -1,5 +1,5 @@
-// rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14) and
-// sides (§6.15).
+// rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14),
+// sides (§6.15) and all hits (§6.16).
 // A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here.
 #include <algorithm>
 
@@ -52,16 +52,18 @@ int prepare_query(Ctx* c, QueryState& qs, uint32_t n, const Params& prm, uint32_
 
 // The enqueue: clear the block, launch(head, stats, grid, stack, refill_min's low byte) between the two events, remember that there
 // is something to read.  The spill columns are taken now: a plan made before another kind's plan grew them still launches on what is there.
+// A call of two walks (the hit kind's list) is first = true, last = false and then first = false, last = true: the second walk clears
+// the stream heads only - its counters are words the first did not touch - and the events enclose both.
 template <class Launch>
-int run_query(Ctx* c, QueryState& qs, QueryPlan plan, const char* range, Launch&& launch) {
+int run_query(Ctx* c, QueryState& qs, QueryPlan plan, const char* range, Launch&& launch, bool first = true, bool last = true) {
     plan.sk.spill = c->pt.d_spill.get();
     uint32_t* head = reinterpret_cast<uint32_t*>(qs.block.get());
     unsigned long long* stats = reinterpret_cast<unsigned long long*>(qs.block.get() + rt::kQueryHeadBytes);
     rt::RoctxRange rr(range);
-    RT_HIP(c, hipMemsetAsync(qs.block.get(), 0, rt::query_block_bytes(qs.n_counters), c->stream));
-    RT_HIP(c, hipEventRecord(qs.ev[0], c->stream));
+    RT_HIP(c, hipMemsetAsync(qs.block.get(), 0, first ? rt::query_block_bytes(qs.n_counters) : rt::kQueryHeadBytes, c->stream));
+    if (first) RT_HIP(c, hipEventRecord(qs.ev[0], c->stream));
     if (int rc = launch(head, stats, plan.grid, plan.sk, plan.refill_min)) return rc;
-    RT_HIP(c, hipEventRecord(qs.ev[1], c->stream));
+    if (last) RT_HIP(c, hipEventRecord(qs.ev[1], c->stream));
     qs.pending = true;
     return RT_OK;
 }
@@ -139,6 +141,112 @@ int run_sides(Ctx* c, const rt::SideQuery& q, const rt_side_query_params& prm, c
     return RT_OK;
 }
 
+// ---- all hits: the count step (walk, then the scan into offsets_out) and the fill step ----
+struct HitScan {  // where the scan's scratch lies in PtData::d_hit_scan
+    unsigned long long *counts, *sums, *total;
+};
+
+int prepare_hits(Ctx* c, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_hit_query_params& prm, rt::HitQuery* q, QueryPlan* plan) {
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, origins, (size_t)n * 12, "origins_dev")) return rc;
+    if (int rc = rt::check_device_array(c, dirs, (size_t)n * 12, "dirs_dev")) return rc;
+    if (tmax)
+        if (int rc = rt::check_device_array(c, tmax, (size_t)n * 4, "tmax_dev")) return rc;
+    *q = rt::HitQuery{};
+    q->origins = static_cast<const float*>(origins);
+    q->dirs = static_cast<const float*>(dirs);
+    q->tmax = static_cast<const float*>(tmax);
+    q->n = n;
+    q->reach = rt::kCameraReach * mesh.maxabs;
+    return prepare_query(c, c->pt.hit_query, n, prm, mesh.stack_need, plan);  // a ray walk: one group per level
+}
+
+// The count step's outputs and, with offsets_out, the scan's scratch: n + 1 counts, the tile sums, the total; by size class (powers of two)
+int prepare_count(Ctx* c, uint32_t n, void* count_out, void* offsets_out, HitScan* hs) {
+    if (!count_out && !offsets_out) return c->fail(RT_ERR_INVALID, "count_out_dev and offsets_out_dev are both NULL");
+    if (count_out)
+        if (int rc = rt::check_device_array(c, count_out, (size_t)n * 4, "count_out_dev")) return rc;
+    *hs = HitScan{};
+    if (!offsets_out) return RT_OK;
+    if (int rc = rt::check_device_array(c, offsets_out, ((size_t)n + 1) * 8, "offsets_out_dev")) return rc;
+    rt::PtData& pt = c->pt;
+    const size_t need = (size_t)n + 1 + rt::scan_u64_sums_words((size_t)n + 1) + 1;
+    if (need > pt.hit_scan_words) {
+        size_t words = 4096;
+        while (words < need) words *= 2;
+        RT_HIP(c, hipStreamSynchronize(c->stream));  // an earlier call may still be scanning in the old one
+        pt.hit_scan_words = 0;
+        if (!rt::dalloc(pt.d_hit_scan, words)) return c->fail(RT_ERR_OOM, "hit-query scan scratch (%zu words)", words);
+        pt.hit_scan_words = words;
+    }
+    hs->counts = pt.d_hit_scan.get();
+    hs->sums = hs->counts + (size_t)n + 1;
+    hs->total = hs->sums + rt::scan_u64_sums_words((size_t)n + 1);
+    return RT_OK;
+}
+
+int prepare_fill(Ctx* c, uint32_t n, const void* offsets, uint64_t capacity, void* t_out, void* tri_out, bool offsets_checked) {
+    if (capacity > (uint64_t)1 << 40) return c->fail(RT_ERR_INVALID, "capacity %llu is above 2^40", (unsigned long long)capacity);
+    if (!offsets_checked)
+        if (int rc = rt::check_device_array(c, offsets, ((size_t)n + 1) * 8, "offsets_in_dev")) return rc;
+    if (capacity || t_out)
+        if (int rc = rt::check_device_array(c, t_out, (size_t)capacity * 4, "t_out_dev")) return rc;
+    if (capacity || tri_out)
+        if (int rc = rt::check_device_array(c, tri_out, (size_t)capacity * 4, "tri_out_dev")) return rc;
+    return RT_OK;
+}
+
+void begin_hit_stats(Ctx* c, uint32_t n) {
+    c->pt.hit_query_stats = rt_hit_query_stats{};
+    c->pt.hit_query_stats.rays = n;
+    c->pt.hit_steps = 0;
+}
+
+int run_count(Ctx* c, rt::HitQuery q, const rt_hit_query_params& prm, const QueryPlan& plan, void* count_out, void* offsets_out, const HitScan& hs, bool last) {
+    q.count_out = static_cast<int*>(count_out);
+    q.count64 = hs.counts;
+    if (hs.counts) RT_HIP(c, hipMemsetAsync(hs.counts + q.n, 0, sizeof(unsigned long long), c->stream));  // entry n: offsets[n] = the total
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_hits(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, false, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
+    };
+    // the scan lies between the events too: it is part of the step
+    if (int rc = run_query(c, c->pt.hit_query, plan, "rt.path_b.count_ray_hits", launch, true, false)) return rc;
+    c->pt.hit_steps |= 1u;
+    c->pt.hit_query_stats.launches += 1;
+    if (hs.counts) {
+        if (int rc = rt::scan_u64_device(c, hs.counts, static_cast<unsigned long long*>(offsets_out), (size_t)q.n + 1, hs.sums, hs.total)) return rc;
+        c->pt.hit_query_stats.launches += 3;
+    }
+    if (last) RT_HIP(c, hipEventRecord(c->pt.hit_query.ev[1], c->stream));
+    return RT_OK;
+}
+
+int run_fill(Ctx* c, rt::HitQuery q, const rt_hit_query_params& prm, const QueryPlan& plan, const void* offsets, uint64_t capacity, void* t_out, void* tri_out, bool first) {
+    q.offsets = static_cast<const long long*>(offsets);
+    q.capacity = (long long)capacity;
+    q.t_out = static_cast<float*>(t_out);
+    q.tri_out = static_cast<int*>(tri_out);
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_hits(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, true, head, stats + rt::HQ_STEP_WORDS, grid, sk, refill_min);
+    };
+    if (int rc = run_query(c, c->pt.hit_query, plan, "rt.path_b.fill_ray_hits", launch, first, true)) return rc;
+    c->pt.hit_steps |= 2u;
+    c->pt.hit_query_stats.launches += 1;
+    return RT_OK;
+}
+
+// What the three entries share up to the kind's own arrays: context, defaults, parameter checks, n == 0 (returns 1: done, RT_OK)
+int enter_hits(Ctx* c, uint32_t n, const rt_hit_query_params*& prm, const rt_hit_query_params& defaults, int* done) {
+    *done = 0;
+    if (!prm) prm = &defaults;
+    if (int rc = check_query_params(c, n, *prm, prm->count_traversal, "count_traversal")) return rc;
+    if (n == 0) {
+        *done = 1;
+        return RT_OK;
+    }
+    return rt::bind(c);
+}
+
 // The pending query's qs.n_counters counters and its time (waits for it)
 int read_query(Ctx* c, QueryState& qs, unsigned long long* counters, float* ms) {
     if (int rc = rt::bind(c)) return rc;
@@ -153,7 +261,9 @@ int read_query(Ctx* c, QueryState& qs, unsigned long long* counters, float* ms) 
 
 namespace rt {
 void query_free(Ctx* c) {
-    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query}) {
+    c->pt.d_hit_scan.reset();
+    c->pt.hit_scan_words = 0;
+    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query}) {
         qs->block.reset();
         for (hipEvent_t& e : qs->ev) {
             if (e) (void)hipEventDestroy(e);
@@ -314,6 +424,88 @@ int rt_get_side_query_stats(rt_ctx* ctx, rt_side_query_stats* stats) {
         s.stack_overflow = (uint32_t)st[rt::SQ_STAT_OVERFLOW];
         s.nodes_visited = st[rt::SQ_STAT_NODES];
         s.tris_tested = st[rt::SQ_STAT_TRIS];
+    }
+    *stats = s;
+    return RT_OK;
+}
+
+int rt_default_hit_query_params(rt_hit_query_params* p) {
+    if (!p) return RT_ERR_INVALID;
+    *p = rt_hit_query_params{};
+    return RT_OK;
+}
+
+int rt_count_ray_hits_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_hit_query_params* prm, void* count_out,
+                             void* offsets_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_hit_query_params defaults{};
+    int done;
+    if (int rc = enter_hits(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
+    rt::HitQuery q{};
+    QueryPlan plan{};
+    HitScan hs{};
+    if (int rc = prepare_count(c, n, count_out, offsets_out, &hs)) return rc;
+    if (int rc = prepare_hits(c, origins, dirs, tmax, n, *prm, &q, &plan)) return rc;
+    begin_hit_stats(c, n);
+    return run_count(c, q, *prm, plan, count_out, offsets_out, hs, true);
+}
+
+int rt_fill_ray_hits_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_hit_query_params* prm, const void* offsets_in,
+                            uint64_t capacity, void* t_out, void* tri_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_hit_query_params defaults{};
+    int done;
+    if (int rc = enter_hits(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
+    rt::HitQuery q{};
+    QueryPlan plan{};
+    if (int rc = prepare_fill(c, n, offsets_in, capacity, t_out, tri_out, false)) return rc;
+    if (int rc = prepare_hits(c, origins, dirs, tmax, n, *prm, &q, &plan)) return rc;
+    begin_hit_stats(c, n);
+    return run_fill(c, q, *prm, plan, offsets_in, capacity, t_out, tri_out, true);
+}
+
+// rt_count_ray_hits_device, then rt_fill_ray_hits_device on its offsets; both steps' refusals and first-use allocations before the first enqueue
+int rt_list_ray_hits_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_hit_query_params* prm, void* count_out,
+                            void* offsets_out, uint64_t capacity, void* t_out, void* tri_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_hit_query_params defaults{};
+    int done;
+    if (int rc = enter_hits(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
+    rt::HitQuery q{};
+    QueryPlan plan{};
+    HitScan hs{};
+    if (!offsets_out) return c->fail(RT_ERR_INVALID, "offsets_out_dev is NULL");
+    if (int rc = prepare_count(c, n, count_out, offsets_out, &hs)) return rc;
+    if (int rc = prepare_fill(c, n, offsets_out, capacity, t_out, tri_out, true)) return rc;
+    if (int rc = prepare_hits(c, origins, dirs, tmax, n, *prm, &q, &plan)) return rc;  // one plan: the two walks are the same kind on the same rays
+    begin_hit_stats(c, n);
+    if (int rc = run_count(c, q, *prm, plan, count_out, offsets_out, hs, false)) return rc;
+    return run_fill(c, q, *prm, plan, offsets_out, capacity, t_out, tri_out, false);
+}
+
+int rt_get_hit_query_stats(rt_ctx* ctx, rt_hit_query_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    rt_hit_query_stats& s = c->pt.hit_query_stats;
+    if (c->pt.hit_query.pending) {
+        unsigned long long st[rt::HQ_STAT_WORDS] = {};
+        if (int rc = read_query(c, c->pt.hit_query, st, &s.ms)) return rc;
+        const unsigned long long *cs = st, *fs = st + rt::HQ_STEP_WORDS;  // the count step's words, the fill step's
+        const unsigned long long* any = (c->pt.hit_steps & 1u) ? cs : fs;  // both steps meet the same rays and the same hits
+        s.invalid_rays = any[rt::HQ_STAT_INVALID];
+        s.hits = any[rt::HQ_STAT_HITS];
+        s.hits_written = fs[rt::HQ_STAT_WRITTEN];
+        s.incomplete_rays = fs[rt::HQ_STAT_INCOMPLETE];
+        s.slice_overflow = fs[rt::HQ_STAT_SLICE_OVERFLOW];
+        s.nodes_visited = cs[rt::HQ_STAT_NODES] + fs[rt::HQ_STAT_NODES];
+        s.tris_tested = cs[rt::HQ_STAT_TRIS] + fs[rt::HQ_STAT_TRIS];
+        s.stack_overflow = (uint32_t)(cs[rt::HQ_STAT_OVERFLOW] | fs[rt::HQ_STAT_OVERFLOW]);
     }
     *stats = s;
     return RT_OK;

@@ -236,6 +236,27 @@ struct SideQuery {
 // Counters of an inside/outside query
 enum { SQ_STAT_INVALID = 0, SQ_STAT_OVERFLOW = 1, SQ_STAT_NODES = 2, SQ_STAT_TRIS = 3, SQ_STAT_SKIPPED = 4, SQ_STAT_WALKS = 5, SQ_STAT_THIRD = 6, SQ_STAT_WORDS = 7 };
 
+// rt_count_ray_hits_device / rt_fill_ray_hits_device: the rays of one step and where its answers go.  Ray i is queue entry i.
+struct HitQuery {
+    const float* origins;  // n x 3
+    const float* dirs;     // n x 3
+    const float* tmax;     // n, or nullptr: +inf
+    // the count step
+    int* count_out;               // n, or nullptr
+    unsigned long long* count64;  // n (the scan's input column: max(count, 0)), or nullptr
+    // the fill step
+    const long long* offsets;  // n + 1
+    long long capacity;        // elements of t_out / tri_out
+    float* t_out;
+    int* tri_out;
+    uint32_t n;
+    float reach;  // |origin component| limit: kCameraReach x the mesh's maxabs
+};
+// Counters of an all-hits query: one set per step (the fill step's HQ_STEP_WORDS words behind the count step's), so that the two
+// launches of rt_list_ray_hits_device report side by side
+enum { HQ_STAT_INVALID = 0, HQ_STAT_OVERFLOW = 1, HQ_STAT_NODES = 2, HQ_STAT_TRIS = 3, HQ_STAT_HITS = 4, HQ_STAT_WRITTEN = 5, HQ_STAT_INCOMPLETE = 6,
+       HQ_STAT_SLICE_OVERFLOW = 7, HQ_STEP_WORDS = 8, HQ_STAT_WORDS = 2 * HQ_STEP_WORDS };
+
 struct MeshHost {  // host side of a two-level mesh: what rt_update_mesh_chunk needs to rebuild one chunk
     TwoLevelBvh tl;
     std::vector<float> v0, e1, e2;          // original triangle order
@@ -270,7 +291,7 @@ constexpr size_t kQueryHeadBytes = (size_t)PT_HEADS * PT_HEAD_STRIDE * sizeof(ui
 constexpr size_t query_block_bytes(uint32_t n_counters) { return kQueryHeadBytes + (size_t)n_counters * sizeof(unsigned long long); }
 struct QueryState {
     QueryState(uint32_t k, const char* what, uint32_t lds, uint32_t halves) : n_counters(k), name(what), fixed_lds_bytes(lds), spill_halves(halves) {}
-    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS / SQ_STAT_WORDS
+    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS / SQ_STAT_WORDS / HQ_STAT_WORDS
     const char* name;     // for messages
     uint32_t fixed_lds_bytes, spill_halves;  // pt_stack_config's: the kernel's LDS beside the stacks, the sets of spill columns it is given
     DevPtr<char> block;
@@ -325,9 +346,15 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     // rt_query_rays_device / rt_query_points_device / rt_query_sides_device: what is in flight, and the statistics of the last query of each kind
     // (rays: the 2 KiB octant table, two spill halves as the frames hold; points and sides: no table, one set of columns)
     QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u}, side_query{SQ_STAT_WORDS, "side-query", 0u, 1u};
+    QueryState hit_query{HQ_STAT_WORDS, "hit-query", 0u, 1u};  // rt_count / fill / list_ray_hits_device: as sides
     rt_ray_query_stats ray_query_stats{};
     rt_point_query_stats point_query_stats{};
     rt_side_query_stats side_query_stats{};
+    rt_hit_query_stats hit_query_stats{};
+    uint32_t hit_steps = 0;  // bit 0: the pending hit query ran the count step, bit 1: the fill step
+    // the hit queries' scan: the 64-bit count column (n + 1), the scan's tile sums and its total; grows by size class, first use only
+    DevPtr<unsigned long long> d_hit_scan;
+    size_t hit_scan_words = 0;
 };
 
 struct Ctx {
@@ -407,7 +434,7 @@ int launch_detile(Ctx* c, const float* tiles, uint32_t n_ranks, uint32_t tiles_p
 int launch_to_rgba8(Ctx* c, const float* rgb, uint8_t* rgba, uint64_t n_pixels);
 
 // path_b.hip (generate, shade, scatter_surfaces, resolve), pt_trace.hip (trace, trace_fused, pool_lds_bytes, trace_rays, query_rays), pt_packet.hip (trace_packet),
-// pt_point_query.hip (query_points), pt_side_query.hip (query_sides): every unit ends with the launchers of its own kernels
+// pt_point_query.hip (query_points), pt_side_query.hip (query_sides), pt_hit_query.hip (query_hits): every unit ends with the launchers of its own kernels
 int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* queue, uint32_t* ctr);
 int launch_pt_trace(Ctx* c, hipStream_t stream, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,
@@ -431,6 +458,9 @@ int launch_pt_query_points(Ctx* c, const PtScene& sc, const PointQuery& q, bool 
                            const StackCfg& sk, uint32_t refill_min);
 int launch_pt_query_sides(Ctx* c, const PtScene& sc, const SideQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                           const StackCfg& sk, uint32_t refill_min);  // q.crossings_out != nullptr: all three walks for every point
+// fill = false: the count step (q.count_out / q.count64), true: the fill step (q.offsets, q.capacity, q.t_out, q.tri_out); stats: the step's own HQ_STEP_WORDS
+int launch_pt_query_hits(Ctx* c, const PtScene& sc, const HitQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                         const StackCfg& sk, uint32_t refill_min);
 void pt_free(Ctx* c);
 void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block and events
 
@@ -469,5 +499,10 @@ size_t refit_scratch_size(uint32_t n_nodes);  // exact node boxes (24 B per node
 int refit_measure(Ctx* c, const float* verts, uint32_t n, void* scratch, hipEvent_t begin, float* maxabs);
 int refit_write(Ctx* c, const float* verts, uint32_t n, float pad, uint32_t n_nodes, float4* nodes, float4* tris, const std::vector<uint32_t>& level_start,
                 void* scratch, hipEvent_t begin, hipEvent_t end, float* ms);
+
+// bvh_build_gpu.hip: the build's exclusive scan (three launches on c->stream, 4096-element tiles) of `count` 64-bit words: out[i] = in[0] + ..
+// + in[i - 1], *total = the sum of all.  sums: scan_u64_sums_words(count) words of scratch.  in and out are different arrays.
+size_t scan_u64_sums_words(size_t count);
+int scan_u64_device(Ctx* c, const unsigned long long* in, unsigned long long* out, size_t count, unsigned long long* sums, unsigned long long* total);
 
 }  // namespace rt

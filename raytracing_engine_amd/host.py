@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (Config, Light, Material, MutableData, Object, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
+from ._lib import (Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, Object, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
                    RtError, SideQueryParams, SideQueryStats, Stats)
 
 # src/main.rs:343-364
@@ -450,7 +450,7 @@ class Renderer:
             raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
     def _query_tune(self, params, tune, method):
-        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance) into its parameter struct;
+        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits) into its parameter struct;
         TypeError for any other keyword."""
         for k, v in tune.items():
             if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
@@ -617,6 +617,99 @@ class Renderer:
         third_walks, nodes_visited, tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
         s = SideQueryStats()
         self._check(self._lib.rt_get_side_query_stats(self._ctx, C.byref(s)))
+        return s.as_dict()
+
+    def _hit_rays(self, origins, dirs, tmax):
+        """The ray count of an all-hits query once its three inputs are what the library can read."""
+        n = self._device_rows(origins, "origins", 3)
+        if self._device_rows(dirs, "dirs", 3) != n:
+            raise ValueError("origins and dirs disagree on the ray count")
+        if tmax is not None and (self._device_rows(tmax, "tmax", 1) != n or tmax.dim() != 1):
+            raise ValueError(f"tmax must have shape ({n},), got {tuple(tmax.shape)}")
+        return n
+
+    def _device_i64(self, t, name, n):
+        """`t` must be a contiguous int64 torch tensor of n elements on this renderer's device; ValueError otherwise."""
+        import torch
+
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device or t.dim() != 1 or t.numel() != n:
+            raise ValueError(f"{name} must be a contiguous int64 tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+    def count_ray_hits(self, origins, dirs, tmax=None, out=None, sync=True, count_traversal=False, **tune):
+        """How many triangles of the current mesh does each ray pass through?  (rt_count_ray_hits_device)  origins, dirs,
+        tmax as for query_rays (tmax default: +inf).  Every triangle with 0 < t < tmax counts, not only the nearest.  Returns int32
+        counts; invalid rays (query_rays' rule) get RAY_INVALID = -2.  out: the tensor to fill instead of a new one.  sync as for
+        query_rays.  count_traversal=True: hit_query_stats() reports nodes_visited / tris_tested.  tune: tune_refill_min,
+        tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_hit_query_params."""
+        import torch
+
+        n = self._hit_rays(origins, dirs, tmax)
+        p = HitQueryParams()
+        p.count_traversal = int(bool(count_traversal))
+        self._query_tune(p, tune, "count_ray_hits")
+        counts = self._query_out(out, "out counts", n, torch.int32, origins.device)
+        self._query_call(sync, self._lib.rt_count_ray_hits_device, origins, dirs, tmax, n, C.byref(p), counts, None)
+        return counts
+
+    def list_ray_hits(self, origins, dirs, tmax=None, capacity=None, out=None, sync=True, **tune):
+        """Every triangle of the current mesh that each ray passes through.  (rt_list_ray_hits_device)  origins, dirs,
+        tmax as for count_ray_hits.  Returns (offsets, t, tri, counts): int64 offsets (n + 1; [n] = the number of hits of all rays), and
+        the hits of ray i in t[offsets[i]:offsets[i + 1]] (float32, units of |dir|) and tri[...] (int32 original triangle indices),
+        ascending by (t, tri); int32 counts as count_ray_hits returns them (invalid rays: RAY_INVALID, no hits).
+        capacity=k: one stream-ordered call, no host synchronisation beyond `sync`; t and tri hold k entries.  A ray whose slice ends
+        beyond k (offsets[i + 1] > k) has written nothing, every other ray's slice is complete; offsets are always the full sums, so
+        offsets[n] > k says: grow and call again.  capacity=None: the count step, ONE host synchronisation to read offsets[n], t and
+        tri allocated to exactly that, then the fill step (rt_count_ray_hits_device + rt_fill_ray_hits_device: two walks).
+        out: (offsets, t, tri, counts) to fill instead of new tensors, with a capacity only (t and tri of that many elements).
+        tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_hit_query_params; hit_query_stats() reports."""
+        import torch
+
+        n = self._hit_rays(origins, dirs, tmax)
+        p = HitQueryParams()
+        self._query_tune(p, tune, "list_ray_hits")
+        dev = origins.device
+        if capacity is None:
+            if out is not None:
+                raise ValueError("out needs a capacity: without one t and tri are allocated to the number of hits")
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            if n == 0:
+                offsets.zero_()
+                return offsets, torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), counts
+            self._query_call(sync, self._lib.rt_count_ray_hits_device, origins, dirs, tmax, n, C.byref(p), counts, offsets)
+            self.synchronize()  # the one host synchronisation: the total decides the allocation
+            total = int(offsets[n].item())
+            t = torch.empty(total, dtype=torch.float32, device=dev)
+            tri = torch.empty(total, dtype=torch.int32, device=dev)
+            self._query_call(sync, self._lib.rt_fill_ray_hits_device, origins, dirs, tmax, n, C.byref(p), offsets, total, t if total else None, tri if total else None)
+            return offsets, t, tri, counts
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError(f"capacity must be >= 0, got {capacity}")
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 4):
+            raise ValueError("out must be (offsets, t, tri, counts)")
+        offsets, t, tri, counts = out if out is not None else (None, None, None, None)
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        else:
+            self._device_i64(offsets, "out offsets", n + 1)
+        t = self._query_out(t, "out t", capacity, torch.float32, dev)
+        tri = self._query_out(tri, "out tri", capacity, torch.int32, dev)
+        counts = self._query_out(counts, "out counts", n, torch.int32, dev)
+        if n == 0:
+            offsets.zero_()
+            return offsets, t, tri, counts
+        self._query_call(sync, self._lib.rt_list_ray_hits_device, origins, dirs, tmax, n, C.byref(p), counts, offsets, capacity, t if capacity else None,
+                         tri if capacity else None)
+        return offsets, t, tri, counts
+
+    def hit_query_stats(self):
+        """rt_hit_query_stats of the last all-hits call as a dict (waits for it): rays, invalid_rays, hits, hits_written, incomplete_rays,
+        slice_overflow, nodes_visited, tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
+        s = HitQueryStats()
+        self._check(self._lib.rt_get_hit_query_stats(self._ctx, C.byref(s)))
         return s.as_dict()
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
