@@ -558,6 +558,66 @@ int rt_list_ray_hits_device(rt_ctx* ctx, const void* origins_dev, const void* di
                             const rt_hit_query_params* params /* NULL = defaults */, void* count_out_dev /* may be NULL */,
                             void* offsets_out_dev, uint64_t capacity, void* t_out_dev, void* tri_out_dev);
 int rt_get_hit_query_stats(rt_ctx* ctx, rt_hit_query_stats* stats); /* synchronises the stream; the last call */
+/* Neighbour queries on device arrays: EVERY triangle of the current mesh within a radius of each of n caller-supplied
+ * points, counted and listed, not only the nearest.  Enqueued on the context's stream behind the work already there; no host
+ * synchronisation, and no allocation after the first query of a size class.  Point i is points_dev[i] (n x 3 f32) with the radius
+ * rmax_dev[i] (n f32), or rmax_all for every point when rmax_dev is NULL (with rmax_dev given, rmax_all is ignored); device memory of
+ * the context's device, only read.  near(i) = the triangles with d2 < rmax[i] * rmax[i], strict and without a tolerance; the product is
+ * formed in fp32 and d2 is the fp32 squared distance of csrc/point_tri.h (closest_on_tri on the triangle record's own words), exactly as
+ * rt_query_points_device has them.  The answer is defined without the tree and does not depend on it.
+ *   rt_count_neighbors_device: count_out_dev[i] (n i32, may be NULL) = |near(i)|; offsets_out_dev (n + 1 i64, may be NULL): [i] = the
+ * exclusive prefix sum of the counts, [n] = their total; at least one of the two is required.
+ *   rt_fill_neighbors_device: the neighbours of point i, sorted ascending by (d2, original triangle index), into elements
+ * [offsets_in_dev[i], offsets_in_dev[i + 1]) of dist_out_dev (f32: sqrt(d2), correctly rounded, so non-decreasing along a slice) and
+ * tri_out_dev (i32), arrays of `capacity` elements; offsets_in_dev (n + 1 i64) is read on the stream.  Entry 0 of a slice is bit for bit
+ * what rt_query_points_device answers for the same point and rmax.  A point whose slice ends beyond the arrays (offsets[i + 1] >
+ * capacity) writes NOTHING; every other point's slice is complete and sorted: what a too small capacity leaves out never depends on the
+ * tree.  The caller sees offsets[n] > capacity, grows the arrays and calls this step again.  The step is memory-safe against offsets
+ * that it did not make: point i writes its entry number j only while 0 <= offsets[i] and offsets[i] + j < offsets[i + 1] <= capacity; a
+ * slice shorter than its point's list keeps the first entries in (d2, index) order and the others are counted in slice_overflow, which
+ * is 0 whenever the offsets are the count step's for the same points, radii and mesh.  capacity == 0: dist_out_dev / tri_out_dev may be
+ * NULL, nothing is written.
+ *   rt_list_neighbors_device is exactly rt_count_neighbors_device(..., count_out_dev, offsets_out_dev) followed by
+ * rt_fill_neighbors_device(..., offsets_out_dev, capacity, dist_out_dev, tri_out_dev); everything that can refuse either step - and
+ * the first-use allocations of both - comes before the first step is enqueued, so a refused call has written nothing.
+ * A point with a non-finite component, a NaN rmax, or a component beyond 32 x max(1, largest |vertex coordinate| of the mesh) -
+ * rt_query_points_device's rule - is not walked: count_out = RT_POINT_INVALID, it adds 0 to the offsets, writes no entry, and is counted
+ * in invalid_points.  !(rmax > 0), and an rmax so small that its square underflows to 0, give count 0 without a walk; rmax = +inf is
+ * valid and lists every triangle whose d2 is finite.  A list is built by insertion into its slice, O(k^2) for k entries: meant for
+ * lists of tens to a few hundred.  Nothing beyond element n - 1 of count_out_dev, n of offsets_out_dev and capacity - 1 of the entry
+ * arrays is written.  The caller keeps all arrays alive until the stream has passed the call; lifetime rules against rt_set_mesh* are
+ * rt_render_pt_device's.  Works on every mesh (host-built single- and two-level, device-built, refitted, with surfaces); reads the mesh
+ * only, so a shared mesh stays shared.  Errors, all before anything is enqueued or written: RT_ERR_INVALID (a NULL context; a NULL
+ * (where not allowed), host or other-device pointer, an allocation shorter than n / n + 1 / capacity rows, n above 2^30, capacity above
+ * 2^40, count_traversal above 1, tune_refill_min above 64, tune_blocks_per_cu above 8, tune_lds_stack above 78), RT_ERR_STATE (no
+ * mesh), RT_ERR_OOM (scratch: 8 bytes per point for the scan, shared with the all-hits queries, grown by size class).  n == 0: RT_OK,
+ * nothing is done. */
+typedef struct rt_neighbor_query_params {
+    uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_ray_query_params */
+    uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
+} rt_neighbor_query_params;
+typedef struct rt_neighbor_query_stats {
+    uint64_t points, invalid_points;     /* the last call with n > 0: points asked, points answered RT_POINT_INVALID */
+    uint64_t neighbors;                  /* sum of |near(i)| over the valid points */
+    uint64_t neighbors_written;          /* fill step: entries written into the entry arrays */
+    uint64_t incomplete_points;          /* fill step: points with neighbours whose slice did not fit (offsets[i + 1] > capacity): nothing written */
+    uint64_t slice_overflow;             /* fill step: neighbours beyond the length of their point's slice; 0 with the count step's offsets */
+    uint64_t nodes_visited, tris_tested; /* count_traversal = 1 only: node records fetched, triangles tested, over all walks of the call */
+    uint32_t stack_overflow;             /* must be 0 */
+    uint32_t launches;                   /* kernel launches of that call: 1 per walk, 3 for the scan */
+    float ms;                            /* HIP-event time from the first to the last launch of the call */
+} rt_neighbor_query_stats;
+int rt_default_neighbor_query_params(rt_neighbor_query_params* p);
+int rt_count_neighbors_device(rt_ctx* ctx, const void* points_dev, const void* rmax_dev /* may be NULL */, float rmax_all, uint32_t n,
+                              const rt_neighbor_query_params* params /* NULL = defaults */, void* count_out_dev /* may be NULL */,
+                              void* offsets_out_dev /* may be NULL */);
+int rt_fill_neighbors_device(rt_ctx* ctx, const void* points_dev, const void* rmax_dev /* may be NULL */, float rmax_all, uint32_t n,
+                             const rt_neighbor_query_params* params /* NULL = defaults */, const void* offsets_in_dev, uint64_t capacity,
+                             void* dist_out_dev, void* tri_out_dev);
+int rt_list_neighbors_device(rt_ctx* ctx, const void* points_dev, const void* rmax_dev /* may be NULL */, float rmax_all, uint32_t n,
+                             const rt_neighbor_query_params* params /* NULL = defaults */, void* count_out_dev /* may be NULL */,
+                             void* offsets_out_dev, uint64_t capacity, void* dist_out_dev, void* tri_out_dev);
+int rt_get_neighbor_query_stats(rt_ctx* ctx, rt_neighbor_query_stats* stats); /* synchronises the stream; the last call */
 /* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */

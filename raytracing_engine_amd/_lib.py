@@ -150,6 +150,20 @@ class HitQueryStats(C.Structure):  # rt_hit_query_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class NeighborQueryParams(C.Structure):  # rt_neighbor_query_params
+    _fields_ = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
+                ("count_traversal", C.c_uint32)]
+
+
+class NeighborQueryStats(C.Structure):  # rt_neighbor_query_stats
+    _fields_ = [("points", C.c_uint64), ("invalid_points", C.c_uint64), ("neighbors", C.c_uint64), ("neighbors_written", C.c_uint64),
+                ("incomplete_points", C.c_uint64), ("slice_overflow", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
+                ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 assert C.sizeof(MutableData) == 656 and C.sizeof(Material) == 32 and C.sizeof(Object) == 16 and C.sizeof(Light) == 32
 
 # every symbol include/rt_abi.h declares: name -> (restype, argtypes)
@@ -217,6 +231,11 @@ PROTOTYPES = {
     "rt_fill_ray_hits_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(HitQueryParams), _vp, C.c_uint64, _vp, _vp]),
     "rt_list_ray_hits_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(HitQueryParams), _vp, _vp, C.c_uint64, _vp, _vp]),
     "rt_get_hit_query_stats": (C.c_int, [_vp, C.POINTER(HitQueryStats)]),
+    "rt_default_neighbor_query_params": (C.c_int, [C.POINTER(NeighborQueryParams)]),
+    "rt_count_neighbors_device": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint32, C.POINTER(NeighborQueryParams), _vp, _vp]),
+    "rt_fill_neighbors_device": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint32, C.POINTER(NeighborQueryParams), _vp, C.c_uint64, _vp, _vp]),
+    "rt_list_neighbors_device": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint32, C.POINTER(NeighborQueryParams), _vp, _vp, C.c_uint64, _vp, _vp]),
+    "rt_get_neighbor_query_stats": (C.c_int, [_vp, C.POINTER(NeighborQueryStats)]),
     "rt_trace_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32)]),
     "rt_trace_rays_counted": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32), _u32p]),
 }

@@ -4,6 +4,7 @@
 // with the tests' CPU reference.  Nothing of frames, path state, shading, packets or the octant table is used here.
 #include "pt_launch.h"
 #include "pt_queue.h"
+#include "pt_slice.h"
 #include "ray_parity.h"
 
 namespace rt {
@@ -19,29 +20,6 @@ using namespace rtk;
 // box culled against the limit would take an accepted hit with it.  What a lane keeps between rounds is its ray, its limit, the
 // number of hits found so far and, in the fill step, where its slice starts and how many entries it may hold.
 constexpr int kHitWaves = 8;
-
-// Hit (t, id) into the slice ts / ids, which holds the min(found, room) smallest hits met so far in ascending (t, id) order: larger
-// entries move up by one; with the slice full its last entry falls off (or the new hit, if it is no smaller).  A lane reads back
-// only what it stored itself, so program order is all the ordering this needs.  Writes only elements below room.
-__device__ __forceinline__ void insert_hit(float* ts, int* ids, uint32_t room, uint32_t found, float t, int id) {
-    uint32_t j = found < room ? found : room;  // entries held
-    if (j == room) {
-        if (room == 0u) return;
-        const float tl = ts[room - 1u];
-        if (!(t < tl || (t == tl && id < ids[room - 1u]))) return;
-        j = room - 1u;
-    }
-    while (j > 0u) {
-        const float tp = ts[j - 1u];
-        const int ip = ids[j - 1u];
-        if (!(tp > t || (tp == t && ip > id))) break;
-        ts[j] = tp;
-        ids[j] = ip;
-        j--;
-    }
-    ts[j] = t;
-    ids[j] = id;
-}
 
 // cross_step's counterpart: fetch the record of the lowest pending leaf slot of T, test it, take a hit inside (0, limit)
 template <bool COUNT, bool FILL>

@@ -1,5 +1,5 @@
 // rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14),
-// sides (§6.15) and all hits (§6.16).
+// sides (§6.15), all hits (§6.16) and neighbours (§6.17).
 // A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here.
 #include <algorithm>
 
@@ -161,7 +161,7 @@ int prepare_hits(Ctx* c, const void* origins, const void* dirs, const void* tmax
     return prepare_query(c, c->pt.hit_query, n, prm, mesh.stack_need, plan);  // a ray walk: one group per level
 }
 
-// The count step's outputs and, with offsets_out, the scan's scratch: n + 1 counts, the tile sums, the total; by size class (powers of two)
+// The count step's outputs (hits and neighbours alike) and, with offsets_out, the scan's scratch: n + 1 counts, the tile sums, the total; by size class (powers of two)
 int prepare_count(Ctx* c, uint32_t n, void* count_out, void* offsets_out, HitScan* hs) {
     if (!count_out && !offsets_out) return c->fail(RT_ERR_INVALID, "count_out_dev and offsets_out_dev are both NULL");
     if (count_out)
@@ -185,12 +185,12 @@ int prepare_count(Ctx* c, uint32_t n, void* count_out, void* offsets_out, HitSca
     return RT_OK;
 }
 
-int prepare_fill(Ctx* c, uint32_t n, const void* offsets, uint64_t capacity, void* t_out, void* tri_out, bool offsets_checked) {
+int prepare_fill(Ctx* c, uint32_t n, const void* offsets, uint64_t capacity, void* t_out, void* tri_out, bool offsets_checked, const char* t_name = "t_out_dev") {
     if (capacity > (uint64_t)1 << 40) return c->fail(RT_ERR_INVALID, "capacity %llu is above 2^40", (unsigned long long)capacity);
     if (!offsets_checked)
         if (int rc = rt::check_device_array(c, offsets, ((size_t)n + 1) * 8, "offsets_in_dev")) return rc;
     if (capacity || t_out)
-        if (int rc = rt::check_device_array(c, t_out, (size_t)capacity * 4, "t_out_dev")) return rc;
+        if (int rc = rt::check_device_array(c, t_out, (size_t)capacity * 4, t_name)) return rc;
     if (capacity || tri_out)
         if (int rc = rt::check_device_array(c, tri_out, (size_t)capacity * 4, "tri_out_dev")) return rc;
     return RT_OK;
@@ -235,8 +235,9 @@ int run_fill(Ctx* c, rt::HitQuery q, const rt_hit_query_params& prm, const Query
     return RT_OK;
 }
 
-// What the three entries share up to the kind's own arrays: context, defaults, parameter checks, n == 0 (returns 1: done, RT_OK)
-int enter_hits(Ctx* c, uint32_t n, const rt_hit_query_params*& prm, const rt_hit_query_params& defaults, int* done) {
+// What the three entries of the hit kind and of the neighbour kind share up to the kind's own arrays: context, defaults, parameter checks, n == 0 (returns 1: done, RT_OK)
+template <class Params>
+int enter_listing(Ctx* c, uint32_t n, const Params*& prm, const Params& defaults, int* done) {
     *done = 0;
     if (!prm) prm = &defaults;
     if (int rc = check_query_params(c, n, *prm, prm->count_traversal, "count_traversal")) return rc;
@@ -245,6 +246,63 @@ int enter_hits(Ctx* c, uint32_t n, const rt_hit_query_params*& prm, const rt_hit
         return RT_OK;
     }
     return rt::bind(c);
+}
+
+// ---- neighbours: the hit kind's two steps on pt_query_points' inputs; the scan and its scratch are the hit kind's ----
+int prepare_neighbors(Ctx* c, const void* points, const void* rmax, float rmax_all, uint32_t n, const rt_neighbor_query_params& prm, rt::NeighborQuery* q, QueryPlan* plan) {
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, points, (size_t)n * 12, "points_dev")) return rc;
+    if (rmax)
+        if (int rc = rt::check_device_array(c, rmax, (size_t)n * 4, "rmax_dev")) return rc;
+    *q = rt::NeighborQuery{};
+    q->points = static_cast<const float*>(points);
+    q->rmax = static_cast<const float*>(rmax);
+    q->rmax_all = rmax_all;
+    q->n = n;
+    q->reach = rt::kCameraReach * mesh.maxabs;
+    // a group walk like the rays': one pending sibling group per level, so the spill columns are the ray kinds' 
+    return prepare_query(c, c->pt.neighbor_query, n, prm, mesh.stack_need, plan);
+}
+
+void begin_neighbor_stats(Ctx* c, uint32_t n) {
+    c->pt.neighbor_query_stats = rt_neighbor_query_stats{};
+    c->pt.neighbor_query_stats.points = n;
+    c->pt.neighbor_steps = 0;
+}
+
+int run_neighbor_count(Ctx* c, rt::NeighborQuery q, const rt_neighbor_query_params& prm, const QueryPlan& plan, void* count_out, void* offsets_out, const HitScan& hs,
+                       bool last) {
+    q.count_out = static_cast<int*>(count_out);
+    q.count64 = hs.counts;
+    if (hs.counts) RT_HIP(c, hipMemsetAsync(hs.counts + q.n, 0, sizeof(unsigned long long), c->stream));  // entry n: offsets[n] = the total
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_neighbors(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, false, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
+    };
+    // the scan lies between the events too: it is part of the step
+    if (int rc = run_query(c, c->pt.neighbor_query, plan, "rt.path_b.count_neighbors", launch, true, false)) return rc;
+    c->pt.neighbor_steps |= 1u;
+    c->pt.neighbor_query_stats.launches += 1;
+    if (hs.counts) {
+        if (int rc = rt::scan_u64_device(c, hs.counts, static_cast<unsigned long long*>(offsets_out), (size_t)q.n + 1, hs.sums, hs.total)) return rc;
+        c->pt.neighbor_query_stats.launches += 3;
+    }
+    if (last) RT_HIP(c, hipEventRecord(c->pt.neighbor_query.ev[1], c->stream));
+    return RT_OK;
+}
+
+int run_neighbor_fill(Ctx* c, rt::NeighborQuery q, const rt_neighbor_query_params& prm, const QueryPlan& plan, const void* offsets, uint64_t capacity, void* dist_out,
+                      void* tri_out, bool first) {
+    q.offsets = static_cast<const long long*>(offsets);
+    q.capacity = (long long)capacity;
+    q.dist_out = static_cast<float*>(dist_out);
+    q.tri_out = static_cast<int*>(tri_out);
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_neighbors(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, true, head, stats + rt::NQ_STEP_WORDS, grid, sk, refill_min);
+    };
+    if (int rc = run_query(c, c->pt.neighbor_query, plan, "rt.path_b.fill_neighbors", launch, first, true)) return rc;
+    c->pt.neighbor_steps |= 2u;
+    c->pt.neighbor_query_stats.launches += 1;
+    return RT_OK;
 }
 
 // The pending query's qs.n_counters counters and its time (waits for it)
@@ -263,7 +321,7 @@ namespace rt {
 void query_free(Ctx* c) {
     c->pt.d_hit_scan.reset();
     c->pt.hit_scan_words = 0;
-    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query}) {
+    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query, &c->pt.neighbor_query}) {
         qs->block.reset();
         for (hipEvent_t& e : qs->ev) {
             if (e) (void)hipEventDestroy(e);
@@ -441,7 +499,7 @@ int rt_count_ray_hits_device(rt_ctx* ctx, const void* origins, const void* dirs,
     if (!c) return RT_ERR_INVALID;
     const rt_hit_query_params defaults{};
     int done;
-    if (int rc = enter_hits(c, n, prm, defaults, &done)) return rc;
+    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
     if (done) return RT_OK;
     rt::HitQuery q{};
     QueryPlan plan{};
@@ -458,7 +516,7 @@ int rt_fill_ray_hits_device(rt_ctx* ctx, const void* origins, const void* dirs, 
     if (!c) return RT_ERR_INVALID;
     const rt_hit_query_params defaults{};
     int done;
-    if (int rc = enter_hits(c, n, prm, defaults, &done)) return rc;
+    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
     if (done) return RT_OK;
     rt::HitQuery q{};
     QueryPlan plan{};
@@ -475,7 +533,7 @@ int rt_list_ray_hits_device(rt_ctx* ctx, const void* origins, const void* dirs, 
     if (!c) return RT_ERR_INVALID;
     const rt_hit_query_params defaults{};
     int done;
-    if (int rc = enter_hits(c, n, prm, defaults, &done)) return rc;
+    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
     if (done) return RT_OK;
     rt::HitQuery q{};
     QueryPlan plan{};
@@ -506,6 +564,88 @@ int rt_get_hit_query_stats(rt_ctx* ctx, rt_hit_query_stats* stats) {
         s.nodes_visited = cs[rt::HQ_STAT_NODES] + fs[rt::HQ_STAT_NODES];
         s.tris_tested = cs[rt::HQ_STAT_TRIS] + fs[rt::HQ_STAT_TRIS];
         s.stack_overflow = (uint32_t)(cs[rt::HQ_STAT_OVERFLOW] | fs[rt::HQ_STAT_OVERFLOW]);
+    }
+    *stats = s;
+    return RT_OK;
+}
+
+int rt_default_neighbor_query_params(rt_neighbor_query_params* p) {
+    if (!p) return RT_ERR_INVALID;
+    *p = rt_neighbor_query_params{};
+    return RT_OK;
+}
+
+int rt_count_neighbors_device(rt_ctx* ctx, const void* points, const void* rmax, float rmax_all, uint32_t n, const rt_neighbor_query_params* prm, void* count_out,
+                              void* offsets_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_neighbor_query_params defaults{};
+    int done;
+    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
+    rt::NeighborQuery q{};
+    QueryPlan plan{};
+    HitScan hs{};
+    if (int rc = prepare_count(c, n, count_out, offsets_out, &hs)) return rc;
+    if (int rc = prepare_neighbors(c, points, rmax, rmax_all, n, *prm, &q, &plan)) return rc;
+    begin_neighbor_stats(c, n);
+    return run_neighbor_count(c, q, *prm, plan, count_out, offsets_out, hs, true);
+}
+
+int rt_fill_neighbors_device(rt_ctx* ctx, const void* points, const void* rmax, float rmax_all, uint32_t n, const rt_neighbor_query_params* prm, const void* offsets_in,
+                             uint64_t capacity, void* dist_out, void* tri_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_neighbor_query_params defaults{};
+    int done;
+    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
+    rt::NeighborQuery q{};
+    QueryPlan plan{};
+    if (int rc = prepare_fill(c, n, offsets_in, capacity, dist_out, tri_out, false, "dist_out_dev")) return rc;
+    if (int rc = prepare_neighbors(c, points, rmax, rmax_all, n, *prm, &q, &plan)) return rc;
+    begin_neighbor_stats(c, n);
+    return run_neighbor_fill(c, q, *prm, plan, offsets_in, capacity, dist_out, tri_out, true);
+}
+
+// rt_count_neighbors_device, then rt_fill_neighbors_device on its offsets; both steps' refusals and first-use allocations before the first enqueue
+int rt_list_neighbors_device(rt_ctx* ctx, const void* points, const void* rmax, float rmax_all, uint32_t n, const rt_neighbor_query_params* prm, void* count_out,
+                             void* offsets_out, uint64_t capacity, void* dist_out, void* tri_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_neighbor_query_params defaults{};
+    int done;
+    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
+    rt::NeighborQuery q{};
+    QueryPlan plan{};
+    HitScan hs{};
+    if (!offsets_out) return c->fail(RT_ERR_INVALID, "offsets_out_dev is NULL");
+    if (int rc = prepare_count(c, n, count_out, offsets_out, &hs)) return rc;
+    if (int rc = prepare_fill(c, n, offsets_out, capacity, dist_out, tri_out, true, "dist_out_dev")) return rc;
+    if (int rc = prepare_neighbors(c, points, rmax, rmax_all, n, *prm, &q, &plan)) return rc;  // one plan: the two walks are the same kind on the same points
+    begin_neighbor_stats(c, n);
+    if (int rc = run_neighbor_count(c, q, *prm, plan, count_out, offsets_out, hs, false)) return rc;
+    return run_neighbor_fill(c, q, *prm, plan, offsets_out, capacity, dist_out, tri_out, false);
+}
+
+int rt_get_neighbor_query_stats(rt_ctx* ctx, rt_neighbor_query_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    rt_neighbor_query_stats& s = c->pt.neighbor_query_stats;
+    if (c->pt.neighbor_query.pending) {
+        unsigned long long st[rt::NQ_STAT_WORDS] = {};
+        if (int rc = read_query(c, c->pt.neighbor_query, st, &s.ms)) return rc;
+        const unsigned long long *cs = st, *fs = st + rt::NQ_STEP_WORDS;  // the count step's words, the fill step's
+        const unsigned long long* any = (c->pt.neighbor_steps & 1u) ? cs : fs;  // both steps meet the same points and the same neighbours
+        s.invalid_points = any[rt::NQ_STAT_INVALID];
+        s.neighbors = any[rt::NQ_STAT_NEIGHBORS];
+        s.neighbors_written = fs[rt::NQ_STAT_WRITTEN];
+        s.incomplete_points = fs[rt::NQ_STAT_INCOMPLETE];
+        s.slice_overflow = fs[rt::NQ_STAT_SLICE_OVERFLOW];
+        s.nodes_visited = cs[rt::NQ_STAT_NODES] + fs[rt::NQ_STAT_NODES];
+        s.tris_tested = cs[rt::NQ_STAT_TRIS] + fs[rt::NQ_STAT_TRIS];
+        s.stack_overflow = (uint32_t)(cs[rt::NQ_STAT_OVERFLOW] | fs[rt::NQ_STAT_OVERFLOW]);
     }
     *stats = s;
     return RT_OK;

@@ -257,6 +257,26 @@ struct HitQuery {
 enum { HQ_STAT_INVALID = 0, HQ_STAT_OVERFLOW = 1, HQ_STAT_NODES = 2, HQ_STAT_TRIS = 3, HQ_STAT_HITS = 4, HQ_STAT_WRITTEN = 5, HQ_STAT_INCOMPLETE = 6,
        HQ_STAT_SLICE_OVERFLOW = 7, HQ_STEP_WORDS = 8, HQ_STAT_WORDS = 2 * HQ_STEP_WORDS };
 
+// rt_count_neighbors_device / rt_fill_neighbors_device: the points of one step and where its answers go.  Point i is queue entry i.
+struct NeighborQuery {
+    const float* points;  // n x 3
+    const float* rmax;    // n, or nullptr: rmax_all for every point
+    float rmax_all;
+    // the count step
+    int* count_out;               // n, or nullptr
+    unsigned long long* count64;  // n (the scan's input column: max(count, 0)), or nullptr
+    // the fill step
+    const long long* offsets;  // n + 1
+    long long capacity;        // elements of dist_out / tri_out
+    float* dist_out;
+    int* tri_out;
+    uint32_t n;
+    float reach;  // |component| limit: kCameraReach x the mesh's maxabs
+};
+// Counters of a neighbour query: one set per step, as the all-hits kind's
+enum { NQ_STAT_INVALID = 0, NQ_STAT_OVERFLOW = 1, NQ_STAT_NODES = 2, NQ_STAT_TRIS = 3, NQ_STAT_NEIGHBORS = 4, NQ_STAT_WRITTEN = 5, NQ_STAT_INCOMPLETE = 6,
+       NQ_STAT_SLICE_OVERFLOW = 7, NQ_STEP_WORDS = 8, NQ_STAT_WORDS = 2 * NQ_STEP_WORDS };
+
 struct MeshHost {  // host side of a two-level mesh: what rt_update_mesh_chunk needs to rebuild one chunk
     TwoLevelBvh tl;
     std::vector<float> v0, e1, e2;          // original triangle order
@@ -347,12 +367,15 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     // (rays: the 2 KiB octant table, two spill halves as the frames hold; points and sides: no table, one set of columns)
     QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u}, side_query{SQ_STAT_WORDS, "side-query", 0u, 1u};
     QueryState hit_query{HQ_STAT_WORDS, "hit-query", 0u, 1u};  // rt_count / fill / list_ray_hits_device: as sides
+    QueryState neighbor_query{NQ_STAT_WORDS, "neighbor-query", 0u, 1u};  // rt_count / fill / list_neighbors_device: a group walk, one group per level
     rt_ray_query_stats ray_query_stats{};
     rt_point_query_stats point_query_stats{};
     rt_side_query_stats side_query_stats{};
     rt_hit_query_stats hit_query_stats{};
-    uint32_t hit_steps = 0;  // bit 0: the pending hit query ran the count step, bit 1: the fill step
-    // the hit queries' scan: the 64-bit count column (n + 1), the scan's tile sums and its total; grows by size class, first use only
+    rt_neighbor_query_stats neighbor_query_stats{};
+    uint32_t hit_steps = 0;       // bit 0: the pending hit query ran the count step, bit 1: the fill step
+    uint32_t neighbor_steps = 0;  // the same of the pending neighbour query
+    // the hit and the neighbour queries' scan: the 64-bit count column (n + 1), the scan's tile sums and its total; grows by size class, first use only
     DevPtr<unsigned long long> d_hit_scan;
     size_t hit_scan_words = 0;
 };
@@ -434,7 +457,7 @@ int launch_detile(Ctx* c, const float* tiles, uint32_t n_ranks, uint32_t tiles_p
 int launch_to_rgba8(Ctx* c, const float* rgb, uint8_t* rgba, uint64_t n_pixels);
 
 // path_b.hip (generate, shade, scatter_surfaces, resolve), pt_trace.hip (trace, trace_fused, pool_lds_bytes, trace_rays, query_rays), pt_packet.hip (trace_packet),
-// pt_point_query.hip (query_points), pt_side_query.hip (query_sides), pt_hit_query.hip (query_hits): every unit ends with the launchers of its own kernels
+// pt_point_query.hip (query_points), pt_side_query.hip (query_sides), pt_hit_query.hip (query_hits), pt_neighbor_query.hip (query_neighbors): every unit ends with the launchers of its own kernels
 int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* queue, uint32_t* ctr);
 int launch_pt_trace(Ctx* c, hipStream_t stream, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,
@@ -461,6 +484,9 @@ int launch_pt_query_sides(Ctx* c, const PtScene& sc, const SideQuery& q, bool co
 // fill = false: the count step (q.count_out / q.count64), true: the fill step (q.offsets, q.capacity, q.t_out, q.tri_out); stats: the step's own HQ_STEP_WORDS
 int launch_pt_query_hits(Ctx* c, const PtScene& sc, const HitQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
                          const StackCfg& sk, uint32_t refill_min);
+// the same two steps of a neighbour query (q.dist_out in the place of q.t_out); stats: the step's own NQ_STEP_WORDS
+int launch_pt_query_neighbors(Ctx* c, const PtScene& sc, const NeighborQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                              const StackCfg& sk, uint32_t refill_min);
 void pt_free(Ctx* c);
 void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block and events
 

@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, Object, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
+from ._lib import (Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
                    RtError, SideQueryParams, SideQueryStats, Stats)
 
 # src/main.rs:343-364
@@ -450,7 +450,7 @@ class Renderer:
             raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
     def _query_tune(self, params, tune, method):
-        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits) into its parameter struct;
+        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors) into its parameter struct;
         TypeError for any other keyword."""
         for k, v in tune.items():
             if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
@@ -710,6 +710,99 @@ class Renderer:
         slice_overflow, nodes_visited, tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
         s = HitQueryStats()
         self._check(self._lib.rt_get_hit_query_stats(self._ctx, C.byref(s)))
+        return s.as_dict()
+
+    def _neighbor_points(self, points, rmax):
+        """(n, rmax tensor or None, rmax_all) of a neighbour query once its inputs are what the library can read."""
+        import torch
+
+        n = self._device_rows(points, "points", 3)
+        if isinstance(rmax, torch.Tensor):
+            if self._device_rows(rmax, "rmax", 1) != n or rmax.dim() != 1:
+                raise ValueError(f"rmax must have shape ({n},), got {tuple(rmax.shape)}")
+            return n, rmax, 0.0
+        if isinstance(rmax, bool) or not isinstance(rmax, (int, float, np.floating, np.integer)):
+            raise ValueError(f"rmax must be a float or a float32 tensor of shape ({n},), got {type(rmax).__name__}")
+        return n, None, float(rmax)
+
+    def count_neighbors(self, points, rmax, out=None, sync=True, count_traversal=False, **tune):
+        """How many triangles of the current mesh lie within rmax of each point?  (rt_count_neighbors_device)  points as
+        for query_points; rmax: a float for all points, or a float32 device tensor of n elements.  Every triangle with d2 < rmax * rmax
+        counts (strictly; d2 and the product in fp32, as query_points has them), not only the nearest.  Returns int32 counts; invalid
+        points (query_points' rule) get POINT_INVALID = -2.  out: the tensor to fill instead of a new one.  sync as for query_points.
+        count_traversal=True: neighbor_query_stats() reports nodes_visited / tris_tested.  tune: tune_refill_min, tune_blocks_per_cu,
+        tune_lds_stack, tune_max_blocks of rt_neighbor_query_params."""
+        import torch
+
+        n, rmax_t, rmax_all = self._neighbor_points(points, rmax)
+        p = NeighborQueryParams()
+        p.count_traversal = int(bool(count_traversal))
+        self._query_tune(p, tune, "count_neighbors")
+        counts = self._query_out(out, "out counts", n, torch.int32, points.device)
+        self._query_call(sync, self._lib.rt_count_neighbors_device, points, rmax_t, rmax_all, n, C.byref(p), counts, None)
+        return counts
+
+    def list_neighbors(self, points, rmax, capacity=None, out=None, sync=True, **tune):
+        """Every triangle of the current mesh within rmax of each point.  (rt_list_neighbors_device)  points, rmax as for
+        count_neighbors.  Returns (offsets, dist, tri, counts): int64 offsets (n + 1; [n] = the number of neighbours of all points), and
+        the neighbours of point i in dist[offsets[i]:offsets[i + 1]] (float32, non-decreasing) and tri[...] (int32 original triangle
+        indices), ascending by (d2, tri); entry 0 is query_points' answer.  int32 counts as count_neighbors returns them (invalid points:
+        POINT_INVALID, no entries).
+        capacity=k: one stream-ordered call, no host synchronisation beyond `sync`; dist and tri hold k entries.  A point whose slice
+        ends beyond k (offsets[i + 1] > k) has written nothing, every other point's slice is complete; offsets are always the full sums,
+        so offsets[n] > k says: grow and call again.  capacity=None: the count step, ONE host synchronisation to read offsets[n], dist
+        and tri allocated to exactly that, then the fill step (rt_count_neighbors_device + rt_fill_neighbors_device: two walks).
+        out: (offsets, dist, tri, counts) to fill instead of new tensors, with a capacity only (dist and tri of that many elements).
+        tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_neighbor_query_params; neighbor_query_stats()
+        reports."""
+        import torch
+
+        n, rmax_t, rmax_all = self._neighbor_points(points, rmax)
+        p = NeighborQueryParams()
+        self._query_tune(p, tune, "list_neighbors")
+        dev = points.device
+        if capacity is None:
+            if out is not None:
+                raise ValueError("out needs a capacity: without one dist and tri are allocated to the number of neighbours")
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            if n == 0:
+                offsets.zero_()
+                return offsets, torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), counts
+            self._query_call(sync, self._lib.rt_count_neighbors_device, points, rmax_t, rmax_all, n, C.byref(p), counts, offsets)
+            self.synchronize()  # the one host synchronisation: the total decides the allocation
+            total = int(offsets[n].item())
+            dist = torch.empty(total, dtype=torch.float32, device=dev)
+            tri = torch.empty(total, dtype=torch.int32, device=dev)
+            self._query_call(sync, self._lib.rt_fill_neighbors_device, points, rmax_t, rmax_all, n, C.byref(p), offsets, total, dist if total else None,
+                             tri if total else None)
+            return offsets, dist, tri, counts
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError(f"capacity must be >= 0, got {capacity}")
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 4):
+            raise ValueError("out must be (offsets, dist, tri, counts)")
+        offsets, dist, tri, counts = out if out is not None else (None, None, None, None)
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        else:
+            self._device_i64(offsets, "out offsets", n + 1)
+        dist = self._query_out(dist, "out dist", capacity, torch.float32, dev)
+        tri = self._query_out(tri, "out tri", capacity, torch.int32, dev)
+        counts = self._query_out(counts, "out counts", n, torch.int32, dev)
+        if n == 0:
+            offsets.zero_()
+            return offsets, dist, tri, counts
+        self._query_call(sync, self._lib.rt_list_neighbors_device, points, rmax_t, rmax_all, n, C.byref(p), counts, offsets, capacity, dist if capacity else None,
+                         tri if capacity else None)
+        return offsets, dist, tri, counts
+
+    def neighbor_query_stats(self):
+        """rt_neighbor_query_stats of the last neighbour call as a dict (waits for it): points, invalid_points, neighbors,
+        neighbors_written, incomplete_points, slice_overflow, nodes_visited, tris_tested (count_traversal=True only), stack_overflow,
+        launches, ms."""
+        s = NeighborQueryStats()
+        self._check(self._lib.rt_get_neighbor_query_stats(self._ctx, C.byref(s)))
         return s.as_dict()
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
