@@ -13,6 +13,7 @@ import pytest
 
 import oracle as O
 import raytracing_engine_amd as R
+from lbvh_exact import check_tree
 from raytracing_engine_amd import scenes
 
 pytestmark = pytest.mark.gpu
@@ -47,63 +48,14 @@ def check_pt_dev(r, mesh, w, h, rot=(0, 0, 0, 1), pos=(0, 0, 0), **kw):
 
 
 def check_bvh(r, verts):
-    """Structural invariants of the current tree (layout: raytracing_engine_amd/csrc/bvh_node.h); returns its depth."""
-    f32 = np.float32
-    verts = np.ascontiguousarray(verts, f32).reshape(-1, 9)
-    n = len(verts)
+    """Structural invariants of the current tree (layout: raytracing_engine_amd/csrc/bvh_node.h; the array part is
+    lbvh_exact.check_tree); returns its depth."""
+    verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 9)
     nodes, leaf = r.read_bvh()
     st = r.pt_stats()
-    nn = len(nodes)
-    assert nn == st["n_nodes"] >= 1 and len(leaf) == n == st["n_tris"]
-    assert np.array_equal(np.sort(leaf), np.arange(n, dtype=np.uint32)), "leaf order is not a permutation"
-    w3 = nodes[:, 3]
-    imask, leafmask = (w3 >> 24) & 0xFF, nodes[:, 6]
-    assert (nodes[:, 7] == 0).all() and (leafmask <= 0xFF).all() and ((leafmask & imask) == 0).all()
-    slots = np.arange(8, dtype=np.uint32)
-    inner = ((imask[:, None] >> slots) & 1).astype(bool)
-    leafs = ((leafmask[:, None] >> slots) & 1).astype(bool)
-    n_in, n_lf = inner.sum(1), leafs.sum(1)
-    child_base, tri_base = nodes[:, 4].astype(np.int64), nodes[:, 5].astype(np.int64)
-    # breadth-first order: the inner children of node k follow those of nodes 0..k-1, its leaf triangles likewise;
-    # with the counts below every node but the root is some node's child exactly once and every leaf position is used once
-    assert np.array_equal(child_base, 1 + np.concatenate([[0], np.cumsum(n_in)[:-1]])), "child indexing / breadth-first order"
-    assert np.array_equal(tri_base, np.concatenate([[0], np.cumsum(n_lf)[:-1]])), "leaf indexing"
-    assert n_in.sum() == nn - 1 and n_lf.sum() == n
-    q = np.ascontiguousarray(nodes[:, 8:20]).view(np.uint8).reshape(nn, 6, 8)
-    qlo, qhi = q[:, :3, :].transpose(0, 2, 1), q[:, 3:, :].transpose(0, 2, 1)  # (nodes, slot, axis)
-    empty = ~(inner | leafs)
-    assert (qlo[empty] == 255).all() and (qhi[empty] == 0).all(), "empty slot without an inverted box"
-    p = np.ascontiguousarray(nodes[:, :3]).view(f32)
-    scale = ((np.stack([(w3 >> (8 * a)) & 0xFF for a in range(3)], 1).astype(np.uint32)) << np.uint32(23)).view(f32)
-    lo = p[:, None, :] + qlo.astype(f32) * scale[:, None, :]  # fp32, as the kernels de-quantise
-    hi = p[:, None, :] + qhi.astype(f32) * scale[:, None, :]
-    assert lo.dtype == f32
-    v0 = verts[:, 0:3]
-    x1, x2 = v0 + (verts[:, 3:6] - v0), v0 + (verts[:, 6:9] - v0)
-    tmin, tmax = np.minimum(np.minimum(v0, x1), x2), np.maximum(np.maximum(v0, x1), x2)
-    rank_in = np.cumsum(inner, 1) - inner
-    rank_lf = np.cumsum(leafs, 1) - leafs
-    levels, first, count = [], 0, 1
-    while count:  # breadth-first numbering: every level is a contiguous index range
-        levels.append((first, first + count))
-        nxt = int(n_in[first:first + count].sum())
-        first, count = first + count, nxt
-    assert first == nn
-    depth = len(levels)
+    assert len(nodes) == st["n_nodes"] >= 1 and len(leaf) == len(verts) == st["n_tris"]
+    depth = check_tree(nodes, leaf, verts)
     assert depth == st["bvh_depth"] and depth <= st["stack_need"] - 1
-    sub_lo = np.full((nn, 3), np.inf, f32)
-    sub_hi = np.full((nn, 3), -np.inf, f32)
-    for a, b in reversed(levels):  # bottom-up: every slot's box holds every triangle below it
-        ks = slice(a, b)
-        li = np.where(leafs[ks], tri_base[ks, None] + rank_lf[ks], 0)
-        ch = np.where(inner[ks], child_base[ks, None] + rank_in[ks], 0)
-        tri = leaf[li]
-        slo = np.where(leafs[ks][..., None], tmin[tri], np.where(inner[ks][..., None], sub_lo[ch], np.inf)).astype(f32)
-        shi = np.where(leafs[ks][..., None], tmax[tri], np.where(inner[ks][..., None], sub_hi[ch], -np.inf)).astype(f32)
-        occ = ~empty[ks]
-        assert (lo[ks][occ] <= slo[occ]).all() and (hi[ks][occ] >= shi[occ]).all(), "a triangle lies outside a box on its root path"
-        sub_lo[ks] = slo.min(1)
-        sub_hi[ks] = shi.max(1)
     return depth
 
 
@@ -274,7 +226,7 @@ def test_structure_checker_accepts_the_host_tree(renderer):
     assert check_bvh(renderer, v) == renderer.pt_stats()["bvh_depth"]
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 7, 8, 9, 38, 700, 30000])
+@pytest.mark.parametrize("n", [1, 2, 3, 7, 8, 9, 38, 700, 30000, 4095, 4096, 4097, 8193, 65537])
 def test_device_tree_structure(renderer, n):
     rng = np.random.default_rng(n)
     v = (rng.uniform(-8, 8, size=(n, 1, 3)) + rng.uniform(-0.7, 0.7, size=(n, 3, 3))).astype(np.float32).reshape(n, 9)
