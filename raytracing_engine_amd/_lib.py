@@ -107,9 +107,12 @@ class RayQueryStats(C.Structure):  # rt_ray_query_stats
 RAY_MISS, RAY_INVALID = -1, -2  # RT_RAY_MISS, RT_RAY_INVALID
 
 
+_TUNE_AND_COUNT = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
+                   ("count_traversal", C.c_uint32)]  # rt_point / side / hit / neighbor_query_params alike
+
+
 class PointQueryParams(C.Structure):  # rt_point_query_params
-    _fields_ = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
-                ("count_traversal", C.c_uint32)]
+    _fields_ = _TUNE_AND_COUNT
 
 
 class PointQueryStats(C.Structure):  # rt_point_query_stats
@@ -124,8 +127,7 @@ POINT_MISS, POINT_INVALID = RAY_MISS, RAY_INVALID  # RT_POINT_MISS, RT_POINT_INV
 
 
 class SideQueryParams(C.Structure):  # rt_side_query_params
-    _fields_ = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
-                ("count_traversal", C.c_uint32)]
+    _fields_ = _TUNE_AND_COUNT
 
 
 class SideQueryStats(C.Structure):  # rt_side_query_stats
@@ -137,8 +139,7 @@ class SideQueryStats(C.Structure):  # rt_side_query_stats
 
 
 class HitQueryParams(C.Structure):  # rt_hit_query_params
-    _fields_ = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
-                ("count_traversal", C.c_uint32)]
+    _fields_ = _TUNE_AND_COUNT
 
 
 class HitQueryStats(C.Structure):  # rt_hit_query_stats
@@ -151,8 +152,7 @@ class HitQueryStats(C.Structure):  # rt_hit_query_stats
 
 
 class NeighborQueryParams(C.Structure):  # rt_neighbor_query_params
-    _fields_ = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
-                ("count_traversal", C.c_uint32)]
+    _fields_ = _TUNE_AND_COUNT
 
 
 class NeighborQueryStats(C.Structure):  # rt_neighbor_query_stats

@@ -33,7 +33,7 @@ __device__ __forceinline__ void hit_step(const float4* __restrict__ tris, const 
     if (COUNT) tc.tris++;
     float t;
     if (ray_tri_t(P3{r.o.x, r.o.y, r.o.z}, P3{r.d.x, r.d.y, r.d.z}, P3{a.x, a.y, a.z}, P3{a.w, b.x, b.y}, P3{b.z, b.w, c.x}, t) && t > 0.0f && t < limit) {
-        if (FILL) insert_hit(q.t_out + lo, q.tri_out + lo, room, found, t, (int)__float_as_uint(c.y));
+        if (FILL) insert_hit(q.key_out + lo, q.tri_out + lo, room, found, t, (int)__float_as_uint(c.y));
         found++;
     }
 }
@@ -88,28 +88,19 @@ __global__ __launch_bounds__(256, kHitWaves) void pt_query_hits(const PtScene sc
                     const bool in_reach = __builtin_fabsf(o.x) <= q.reach && __builtin_fabsf(o.y) <= q.reach && __builtin_fabsf(o.z) <= q.reach;
                     const bool d_finite = __builtin_fabsf(d.x) < __builtin_inff() && __builtin_fabsf(d.y) < __builtin_inff() && __builtin_fabsf(d.z) < __builtin_inff();
                     if (!(in_reach && d_finite && limit == limit)) {  // not walked
-                        if (!FILL) {
-                            if (q.count_out) q.count_out[i] = RT_RAY_INVALID;
-                            if (q.count64) q.count64[i] = 0ull;
-                        }
+                        if (!FILL) write_count(q.count_out, q.count64, i, RT_RAY_INVALID, 0ull);
                         invalid++;
                     } else if (!(limit > 0.0f)) {  // an empty interval: no hit, without a walk
-                        if (!FILL) {
-                            if (q.count_out) q.count_out[i] = 0;
-                            if (q.count64) q.count64[i] = 0ull;
-                        }
+                        if (!FILL) write_count(q.count_out, q.count64, i, 0, 0ull);
                     } else {
                         r = make_tray(o, d, __builtin_inff());
                         G = root_group();
                         T = Group{0u, 0u};
                         stk.sp = 0;
                         found = 0u;
-                        if (FILL) {  // the slice: written only if 0 <= lo <= hi <= capacity, and then only below hi - lo
-                            lo = q.offsets[i];
-                            const long long hi = q.offsets[(size_t)i + 1u];
-                            const long long span = hi > lo ? hi - lo : 0ll;
-                            len = span < 0xffffffffll ? (uint32_t)span : 0xffffffffu;
-                            room = (lo >= 0ll && hi <= q.capacity) ? len : 0u;
+                        if (FILL) {
+                            const Slice s = open_slice(q.offsets, i, q.capacity);
+                            lo = s.lo, len = s.len, room = s.room;
                         }
                         ray = i;
                         has_ray = true;
@@ -131,32 +122,15 @@ __global__ __launch_bounds__(256, kHitWaves) void pt_query_hits(const PtScene sc
         // triangle phase: one test
         if (alive && has_tris(T)) hit_step<COUNT, FILL>(sc.tris, r, limit, q, lo, room, found, T, tc);
     }
-    add_wave_total(&stats[HQ_STAT_INVALID], invalid, lane);
-    add_wave_total(&stats[HQ_STAT_HITS], hits, lane);
-    if (FILL) {
-        add_wave_total(&stats[HQ_STAT_WRITTEN], written, lane);
-        add_wave_total(&stats[HQ_STAT_INCOMPLETE], incomplete, lane);
-        add_wave_total(&stats[HQ_STAT_SLICE_OVERFLOW], beyond, lane);
-    }
-    if (COUNT) {
-        add_wave_total(&stats[HQ_STAT_NODES], tc.nodes, lane);
-        add_wave_total(&stats[HQ_STAT_TRIS], tc.tris, lane);
-    }
-    if (tc.overflow) atomicOr((unsigned int*)&stats[HQ_STAT_OVERFLOW], 1u);
+    add_listing_totals<COUNT, FILL>(stats, lane, invalid, hits, written, incomplete, beyond, tc);
 }
 
 // ---- launchers ------------------------------------------------------------------------------------
 int launch_pt_query_hits(Ctx* c, const PtScene& sc, const HitQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
                          const StackCfg& sk, uint32_t refill_min) {
-    if (!valid_stack_cfg(sk, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
-    with_bool(count, [&](auto cnt) {
-        with_bool(fill, [&](auto fl) {
-            hipLaunchKernelGGL((pt_query_hits<decltype(cnt)::value, decltype(fl)::value>), dim3(grid), dim3(256), stack_lds_bytes(sk), c->stream, sc, q, head, stats,
-                               sk, refill_min);
-        });
-    });
-    RT_HIP(c, hipGetLastError());
-    return RT_OK;
+    QueryKernel<HitQuery> kernel = nullptr;
+    with_bool(count, [&](auto cnt) { with_bool(fill, [&](auto fl) { kernel = pt_query_hits<decltype(cnt)::value, decltype(fl)::value>; }); });
+    return launch_query(c, kernel, sc, q, head, stats, grid, sk, refill_min);
 }
 
 }  // namespace rt

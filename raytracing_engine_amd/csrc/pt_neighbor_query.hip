@@ -72,7 +72,7 @@ __device__ __forceinline__ void neighbor_tri_step(const float4* __restrict__ tri
     if (COUNT) tc.tris++;
     const float d2 = closest_on_tri(p, P3{a.x, a.y, a.z}, P3{a.w, b.x, b.y}, P3{b.z, b.w, c.x}).d2;
     if (d2 < limit2) {
-        if (FILL) insert_hit(q.dist_out + lo, q.tri_out + lo, room, found, d2, (int)__float_as_uint(c.y));  // keyed by d2 until the sink
+        if (FILL) insert_hit(q.key_out + lo, q.tri_out + lo, room, found, d2, (int)__float_as_uint(c.y));  // keyed by d2 until the sink
         found++;
     }
 }
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256, kNeighborWaves) void pt_query_neighbors(const 
                 neighbors += found;
                 if (FILL) {
                     const uint32_t kept = found < room ? found : room;
-                    float* ds = q.dist_out + lo;
+                    float* ds = q.key_out + lo;
 #pragma unroll 1
                     for (uint32_t j = 0; j < kept; j++) ds[j] = sqrt_cr(ds[j]);  // d2 -> dist in place: the lane's own stores, program order
                     written += kept;
@@ -128,16 +128,10 @@ __global__ __launch_bounds__(256, kNeighborWaves) void pt_query_neighbors(const 
                     const float rmax = q.rmax ? q.rmax[i] : q.rmax_all;
                     const float l2 = point_limit2(rmax);
                     if (!(point_in_reach(np, q.reach) && rmax == rmax)) {  // not walked (comparisons that are false for a NaN)
-                        if (!FILL) {
-                            if (q.count_out) q.count_out[i] = RT_POINT_INVALID;
-                            if (q.count64) q.count64[i] = 0ull;
-                        }
+                        if (!FILL) write_count(q.count_out, q.count64, i, RT_POINT_INVALID, 0ull);
                         invalid++;
                     } else if (!(rmax > 0.0f) || !(l2 > 0.0f)) {  // nothing has d2 < limit2: no neighbour, without a walk
-                        if (!FILL) {
-                            if (q.count_out) q.count_out[i] = 0;
-                            if (q.count64) q.count64[i] = 0ull;
-                        }
+                        if (!FILL) write_count(q.count_out, q.count64, i, 0, 0ull);
                     } else {
                         p = np;
                         limit2 = l2;
@@ -145,12 +139,9 @@ __global__ __launch_bounds__(256, kNeighborWaves) void pt_query_neighbors(const 
                         T = Group{0u, 0u};
                         stk.sp = 0;
                         found = 0u;
-                        if (FILL) {  // the slice: written only if 0 <= lo <= hi <= capacity, and then only below hi - lo
-                            lo = q.offsets[i];
-                            const long long hi = q.offsets[(size_t)i + 1u];
-                            const long long span = hi > lo ? hi - lo : 0ll;
-                            len = span < 0xffffffffll ? (uint32_t)span : 0xffffffffu;
-                            room = (lo >= 0ll && hi <= q.capacity) ? len : 0u;
+                        if (FILL) {
+                            const Slice s = open_slice(q.offsets, i, q.capacity);
+                            lo = s.lo, len = s.len, room = s.room;
                         }
                         point = i;
                         has_point = true;
@@ -172,32 +163,15 @@ __global__ __launch_bounds__(256, kNeighborWaves) void pt_query_neighbors(const 
         // triangle phase: one test
         if (alive && has_tris(T)) neighbor_tri_step<COUNT, FILL>(sc.tris, p, limit2, q, lo, room, found, T, tc);
     }
-    add_wave_total(&stats[NQ_STAT_INVALID], invalid, lane);
-    add_wave_total(&stats[NQ_STAT_NEIGHBORS], neighbors, lane);
-    if (FILL) {
-        add_wave_total(&stats[NQ_STAT_WRITTEN], written, lane);
-        add_wave_total(&stats[NQ_STAT_INCOMPLETE], incomplete, lane);
-        add_wave_total(&stats[NQ_STAT_SLICE_OVERFLOW], beyond, lane);
-    }
-    if (COUNT) {
-        add_wave_total(&stats[NQ_STAT_NODES], tc.nodes, lane);
-        add_wave_total(&stats[NQ_STAT_TRIS], tc.tris, lane);
-    }
-    if (tc.overflow) atomicOr((unsigned int*)&stats[NQ_STAT_OVERFLOW], 1u);
+    add_listing_totals<COUNT, FILL>(stats, lane, invalid, neighbors, written, incomplete, beyond, tc);
 }
 
 // ---- launchers ------------------------------------------------------------------------------------
 int launch_pt_query_neighbors(Ctx* c, const PtScene& sc, const NeighborQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
                               const StackCfg& sk, uint32_t refill_min) {
-    if (!valid_stack_cfg(sk, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
-    with_bool(count, [&](auto cnt) {
-        with_bool(fill, [&](auto fl) {
-            hipLaunchKernelGGL((pt_query_neighbors<decltype(cnt)::value, decltype(fl)::value>), dim3(grid), dim3(256), stack_lds_bytes(sk), c->stream, sc, q, head,
-                               stats, sk, refill_min);
-        });
-    });
-    RT_HIP(c, hipGetLastError());
-    return RT_OK;
+    QueryKernel<NeighborQuery> kernel = nullptr;
+    with_bool(count, [&](auto cnt) { with_bool(fill, [&](auto fl) { kernel = pt_query_neighbors<decltype(cnt)::value, decltype(fl)::value>; }); });
+    return launch_query(c, kernel, sc, q, head, stats, grid, sk, refill_min);
 }
 
 }  // namespace rt

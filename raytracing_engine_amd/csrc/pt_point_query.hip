@@ -205,12 +205,9 @@ __global__ __launch_bounds__(256, kPointWaves) void pt_query_points(const PtScen
 // ---- launchers ------------------------------------------------------------------------------------
 int launch_pt_query_points(Ctx* c, const PtScene& sc, const PointQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                            const StackCfg& sk, uint32_t refill_min) {
-    if (!valid_stack_cfg(sk, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
-    with_bool(count, [&](auto cnt) {
-        hipLaunchKernelGGL(pt_query_points<decltype(cnt)::value>, dim3(grid), dim3(256), stack_lds_bytes(sk), c->stream, sc, q, head, stats, sk, refill_min);
-    });
-    RT_HIP(c, hipGetLastError());
-    return RT_OK;
+    QueryKernel<PointQuery> kernel = nullptr;
+    with_bool(count, [&](auto cnt) { kernel = pt_query_points<decltype(cnt)::value>; });
+    return launch_query(c, kernel, sc, q, head, stats, grid, sk, refill_min);
 }
 
 }  // namespace rt

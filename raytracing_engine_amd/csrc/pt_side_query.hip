@@ -145,15 +145,9 @@ __global__ __launch_bounds__(256, kSideWaves) void pt_query_sides(const PtScene 
 // ---- launchers ------------------------------------------------------------------------------------
 int launch_pt_query_sides(Ctx* c, const PtScene& sc, const SideQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                           const StackCfg& sk, uint32_t refill_min) {
-    if (!valid_stack_cfg(sk, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
-    with_bool(count, [&](auto cnt) {
-        with_bool(q.crossings_out != nullptr, [&](auto all) {
-            hipLaunchKernelGGL((pt_query_sides<decltype(cnt)::value, decltype(all)::value>), dim3(grid), dim3(256), stack_lds_bytes(sk), c->stream, sc, q, head, stats,
-                               sk, refill_min);
-        });
-    });
-    RT_HIP(c, hipGetLastError());
-    return RT_OK;
+    QueryKernel<SideQuery> kernel = nullptr;
+    with_bool(count, [&](auto cnt) { with_bool(q.crossings_out != nullptr, [&](auto all) { kernel = pt_query_sides<decltype(cnt)::value, decltype(all)::value>; }); });
+    return launch_query(c, kernel, sc, q, head, stats, grid, sk, refill_min);
 }
 
 }  // namespace rt

@@ -1,7 +1,10 @@
-// pt_slice.h — path B, device side: the sorted slice that a lane of a listing query keeps in global memory.  Used by the all-hits ray
-// queries (pt_hit_query.hip: keys are t) and by the neighbour queries (pt_neighbor_query.hip: keys are d2).
+// pt_slice.h — path B, device side: what the kernels of the listing queries share beside their loop - the sorted slice that a lane
+// keeps in global memory (insert_hit), where that slice lies (open_slice), the count step's answer for an item that is not walked
+// (write_count) and the wave totals (add_listing_totals).  Used by the all-hits ray queries (pt_hit_query.hip: keys are t) and by the
+// neighbour queries (pt_neighbor_query.hip: keys are d2).  Every function here left the kernels' object code as it was; the sink's
+// count and its written / incomplete / beyond accounting did not and stay in the kernels (profiles/refactor_listing.txt).
 #pragma once
-#include <cstdint>
+#include "pt_queue.h"
 
 namespace rt {
 
@@ -26,6 +29,45 @@ __device__ __forceinline__ void insert_hit(float* ts, int* ids, uint32_t room, u
     }
     ts[j] = t;
     ids[j] = id;
+}
+
+// The fill step: the slice of item i as the offsets give it - where it starts, its own length (saturated at 2^32 - 1), and the
+// entries it may hold: written only if 0 <= lo <= hi <= capacity, and then only below hi - lo (room 0: it does not fit, nothing is
+// written).  Returned by value: the same function filling three references changed the kernels' code (profiles/refactor_listing.txt).
+struct Slice {
+    long long lo;
+    uint32_t len, room;
+};
+__device__ __forceinline__ Slice open_slice(const long long* offsets, uint32_t i, long long capacity) {
+    const long long lo = offsets[i], hi = offsets[(size_t)i + 1u];
+    const long long span = hi > lo ? hi - lo : 0ll;
+    const uint32_t len = span < 0xffffffffll ? (uint32_t)span : 0xffffffffu;
+    return Slice{lo, len, (lo >= 0ll && hi <= capacity) ? len : 0u};
+}
+
+// The count step: the answer of an item that is not walked - the caller's 32-bit column and the scan's 64-bit one (max(count, 0));
+// either may be absent
+__device__ __forceinline__ void write_count(int* count_out, unsigned long long* count64, uint32_t i, int count, unsigned long long scanned) {
+    if (count_out) count_out[i] = count;
+    if (count64) count64[i] = scanned;
+}
+
+// A wave's totals into the step's LQ_STEP_WORDS counters, one atomic per word
+template <bool COUNT, bool FILL>
+__device__ __forceinline__ void add_listing_totals(unsigned long long* stats, uint32_t lane, uint32_t invalid, uint32_t found, uint32_t written, uint32_t incomplete,
+                                                   uint32_t beyond, const TravCounters& tc) {
+    add_wave_total(&stats[LQ_STAT_INVALID], invalid, lane);
+    add_wave_total(&stats[LQ_STAT_FOUND], found, lane);
+    if (FILL) {
+        add_wave_total(&stats[LQ_STAT_WRITTEN], written, lane);
+        add_wave_total(&stats[LQ_STAT_INCOMPLETE], incomplete, lane);
+        add_wave_total(&stats[LQ_STAT_SLICE_OVERFLOW], beyond, lane);
+    }
+    if (COUNT) {
+        add_wave_total(&stats[LQ_STAT_NODES], tc.nodes, lane);
+        add_wave_total(&stats[LQ_STAT_TRIS], tc.tris, lane);
+    }
+    if (tc.overflow) atomicOr((unsigned int*)&stats[LQ_STAT_OVERFLOW], 1u);
 }
 
 }  // namespace rt

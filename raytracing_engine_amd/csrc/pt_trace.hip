@@ -805,12 +805,9 @@ int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const 
 
 int launch_pt_query_rays(Ctx* c, const PtScene& sc, const RayQuery& q, bool any_hit, uint32_t* head, unsigned long long* stats, uint32_t grid,
                          const StackCfg& sk, uint32_t refill_min) {
-    if (!valid_stack_cfg(sk, grid)) return c->fail(RT_ERR_INVALID, "bad traversal stack configuration");
-    with_bool(any_hit, [&](auto any) {
-        hipLaunchKernelGGL(pt_query_rays<decltype(any)::value>, dim3(grid), dim3(256), stack_lds_bytes(sk), c->stream, sc, q, head, stats, sk, refill_min);
-    });
-    RT_HIP(c, hipGetLastError());
-    return RT_OK;
+    QueryKernel<RayQuery> kernel = nullptr;
+    with_bool(any_hit, [&](auto any) { kernel = pt_query_rays<decltype(any)::value>; });
+    return launch_query(c, kernel, sc, q, head, stats, grid, sk, refill_min);
 }
 
 }  // namespace rt

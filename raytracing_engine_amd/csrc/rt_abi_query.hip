@@ -1,6 +1,9 @@
 // rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14),
 // sides (§6.15), all hits (§6.16) and neighbours (§6.17).
-// A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here.
+// A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here: the
+// parameter checks and the prologue of an entry (enter_query), the plan and the enqueue (prepare_query, run_query), the read-back.
+// The listing kinds - all hits, neighbours - are a description each (HitKind, NeighborKind); their protocol of a count step, a fill
+// step or both in one call is listing_call, and their read-back is listing_stats.
 #include <algorithm>
 
 #include "rt_internal.h"
@@ -23,6 +26,33 @@ int check_query_params(Ctx* c, uint32_t n, const Params& prm, uint32_t flag, con
     if ((prm.tune_refill_min & 0xffu) > 64u || prm.tune_refill_min > 0xffffu) return c->fail(RT_ERR_INVALID, "tune_refill_min %u (low byte 0 .. 64)", prm.tune_refill_min);
     if (prm.tune_blocks_per_cu > 8u) return c->fail(RT_ERR_INVALID, "tune_blocks_per_cu %u (0 .. 8)", prm.tune_blocks_per_cu);
     if (prm.tune_lds_stack > 78u) return c->fail(RT_ERR_INVALID, "tune_lds_stack %u (0 .. 78)", prm.tune_lds_stack);
+    return RT_OK;
+}
+
+// The prologue of an entry, in two parts for the entry that takes two parameter structs.  use_params: the defaults for a NULL
+// struct, then check_query_params.  begin_query: n == 0 is *done (the caller returns RT_OK), else the context's device is bound.
+template <class Params>
+int use_params(Ctx* c, uint32_t n, const Params*& prm, const Params& defaults, uint32_t Params::*flag = &Params::count_traversal, const char* flag_name = "count_traversal") {
+    if (!prm) prm = &defaults;
+    return check_query_params(c, n, *prm, prm->*flag, flag_name);
+}
+
+int begin_query(Ctx* c, uint32_t n, int* done) {
+    *done = n == 0;
+    return *done ? RT_OK : rt::bind(c);
+}
+
+template <class Params>
+int enter_query(Ctx* c, uint32_t n, const Params*& prm, const Params& defaults, int* done, uint32_t Params::*flag = &Params::count_traversal,
+                const char* flag_name = "count_traversal") {
+    if (int rc = use_params(c, n, prm, defaults, flag, flag_name)) return rc;
+    return begin_query(c, n, done);
+}
+
+template <class Params>
+int default_params(Params* p) {
+    if (!p) return RT_ERR_INVALID;
+    *p = Params{};
     return RT_OK;
 }
 
@@ -52,7 +82,7 @@ int prepare_query(Ctx* c, QueryState& qs, uint32_t n, const Params& prm, uint32_
 
 // The enqueue: clear the block, launch(head, stats, grid, stack, refill_min's low byte) between the two events, remember that there
 // is something to read.  The spill columns are taken now: a plan made before another kind's plan grew them still launches on what is there.
-// A call of two walks (the hit kind's list) is first = true, last = false and then first = false, last = true: the second walk clears
+// A call of two walks (a listing kind's list) is first = true, last = false and then first = false, last = true: the second walk clears
 // the stream heads only - its counters are words the first did not touch - and the events enclose both.
 template <class Launch>
 int run_query(Ctx* c, QueryState& qs, QueryPlan plan, const char* range, Launch&& launch, bool first = true, bool last = true) {
@@ -141,167 +171,181 @@ int run_sides(Ctx* c, const rt::SideQuery& q, const rt_side_query_params& prm, c
     return RT_OK;
 }
 
-// ---- all hits: the count step (walk, then the scan into offsets_out) and the fill step ----
-struct HitScan {  // where the scan's scratch lies in PtData::d_hit_scan
+// ---- the listing kinds: all hits and neighbours.  The kinds' own array checks, then what they are to the shared protocol ----
+struct RaySource {
+    const void *origins, *dirs, *tmax;
+};
+struct PointSource {
+    const void *points, *rmax;
+    float rmax_all;
+};
+
+int prepare_hits(Ctx* c, const RaySource& src, uint32_t n, const rt_hit_query_params& prm, rt::HitQuery* q, QueryPlan* plan) {
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, src.origins, (size_t)n * 12, "origins_dev")) return rc;
+    if (int rc = rt::check_device_array(c, src.dirs, (size_t)n * 12, "dirs_dev")) return rc;
+    if (src.tmax)
+        if (int rc = rt::check_device_array(c, src.tmax, (size_t)n * 4, "tmax_dev")) return rc;
+    *q = rt::HitQuery{};
+    q->origins = static_cast<const float*>(src.origins);
+    q->dirs = static_cast<const float*>(src.dirs);
+    q->tmax = static_cast<const float*>(src.tmax);
+    q->n = n;
+    q->reach = rt::kCameraReach * mesh.maxabs;
+    return prepare_query(c, c->pt.hit_query.qs, n, prm, mesh.stack_need, plan);  // a ray walk: one group per level
+}
+
+// pt_query_points' inputs
+int prepare_neighbors(Ctx* c, const PointSource& src, uint32_t n, const rt_neighbor_query_params& prm, rt::NeighborQuery* q, QueryPlan* plan) {
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, src.points, (size_t)n * 12, "points_dev")) return rc;
+    if (src.rmax)
+        if (int rc = rt::check_device_array(c, src.rmax, (size_t)n * 4, "rmax_dev")) return rc;
+    *q = rt::NeighborQuery{};
+    q->points = static_cast<const float*>(src.points);
+    q->rmax = static_cast<const float*>(src.rmax);
+    q->rmax_all = src.rmax_all;
+    q->n = n;
+    q->reach = rt::kCameraReach * mesh.maxabs;
+    // a group walk like the rays': one pending sibling group per level, so the spill columns are the ray kinds' (DESIGN.md §6.17)
+    return prepare_query(c, c->pt.neighbor_query.qs, n, prm, mesh.stack_need, plan);
+}
+
+struct HitKind {
+    using Source = RaySource;
+    using Query = rt::HitQuery;
+    using Params = rt_hit_query_params;
+    using Stats = rt_hit_query_stats;
+    static constexpr auto prepare = prepare_hits;
+    static constexpr auto launch = rt::launch_pt_query_hits;
+    static constexpr auto state = &rt::PtData::hit_query;
+    static constexpr auto stats = &rt::PtData::hit_query_stats;
+    static constexpr const char *count_range = "rt.path_b.count_ray_hits", *fill_range = "rt.path_b.fill_ray_hits", *key_name = "t_out_dev";
+    static constexpr auto items = &Stats::rays, invalid = &Stats::invalid_rays, found = &Stats::hits, written = &Stats::hits_written, incomplete = &Stats::incomplete_rays;
+};
+struct NeighborKind {
+    using Source = PointSource;
+    using Query = rt::NeighborQuery;
+    using Params = rt_neighbor_query_params;
+    using Stats = rt_neighbor_query_stats;
+    static constexpr auto prepare = prepare_neighbors;
+    static constexpr auto launch = rt::launch_pt_query_neighbors;
+    static constexpr auto state = &rt::PtData::neighbor_query;
+    static constexpr auto stats = &rt::PtData::neighbor_query_stats;
+    static constexpr const char *count_range = "rt.path_b.count_neighbors", *fill_range = "rt.path_b.fill_neighbors", *key_name = "dist_out_dev";
+    static constexpr auto items = &Stats::points, invalid = &Stats::invalid_points, found = &Stats::neighbors, written = &Stats::neighbors_written,
+                          incomplete = &Stats::incomplete_points;
+};
+
+// ---- the listing protocol: the count step (walk, then the scan into offsets_out) and the fill step ----
+struct ListScan {  // where the scan's scratch lies in PtData::d_list_scan
     unsigned long long *counts, *sums, *total;
 };
 
-int prepare_hits(Ctx* c, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_hit_query_params& prm, rt::HitQuery* q, QueryPlan* plan) {
-    const rt::DeviceMesh& mesh = c->pt.mesh();
-    if (int rc = rt::check_device_array(c, origins, (size_t)n * 12, "origins_dev")) return rc;
-    if (int rc = rt::check_device_array(c, dirs, (size_t)n * 12, "dirs_dev")) return rc;
-    if (tmax)
-        if (int rc = rt::check_device_array(c, tmax, (size_t)n * 4, "tmax_dev")) return rc;
-    *q = rt::HitQuery{};
-    q->origins = static_cast<const float*>(origins);
-    q->dirs = static_cast<const float*>(dirs);
-    q->tmax = static_cast<const float*>(tmax);
-    q->n = n;
-    q->reach = rt::kCameraReach * mesh.maxabs;
-    return prepare_query(c, c->pt.hit_query, n, prm, mesh.stack_need, plan);  // a ray walk: one group per level
-}
-
-// The count step's outputs (hits and neighbours alike) and, with offsets_out, the scan's scratch: n + 1 counts, the tile sums, the total; by size class (powers of two)
-int prepare_count(Ctx* c, uint32_t n, void* count_out, void* offsets_out, HitScan* hs) {
+// The count step's outputs and, with offsets_out, the scan's scratch: n + 1 counts, the tile sums, the total; by size class (powers of two)
+int prepare_count(Ctx* c, uint32_t n, void* count_out, void* offsets_out, ListScan* ls) {
     if (!count_out && !offsets_out) return c->fail(RT_ERR_INVALID, "count_out_dev and offsets_out_dev are both NULL");
     if (count_out)
         if (int rc = rt::check_device_array(c, count_out, (size_t)n * 4, "count_out_dev")) return rc;
-    *hs = HitScan{};
+    *ls = ListScan{};
     if (!offsets_out) return RT_OK;
     if (int rc = rt::check_device_array(c, offsets_out, ((size_t)n + 1) * 8, "offsets_out_dev")) return rc;
     rt::PtData& pt = c->pt;
     const size_t need = (size_t)n + 1 + rt::scan_u64_sums_words((size_t)n + 1) + 1;
-    if (need > pt.hit_scan_words) {
+    if (need > pt.list_scan_words) {
         size_t words = 4096;
         while (words < need) words *= 2;
         RT_HIP(c, hipStreamSynchronize(c->stream));  // an earlier call may still be scanning in the old one
-        pt.hit_scan_words = 0;
-        if (!rt::dalloc(pt.d_hit_scan, words)) return c->fail(RT_ERR_OOM, "hit-query scan scratch (%zu words)", words);
-        pt.hit_scan_words = words;
+        pt.list_scan_words = 0;
+        if (!rt::dalloc(pt.d_list_scan, words)) return c->fail(RT_ERR_OOM, "hit-query scan scratch (%zu words)", words);
+        pt.list_scan_words = words;
     }
-    hs->counts = pt.d_hit_scan.get();
-    hs->sums = hs->counts + (size_t)n + 1;
-    hs->total = hs->sums + rt::scan_u64_sums_words((size_t)n + 1);
+    ls->counts = pt.d_list_scan.get();
+    ls->sums = ls->counts + (size_t)n + 1;
+    ls->total = ls->sums + rt::scan_u64_sums_words((size_t)n + 1);
     return RT_OK;
 }
 
-int prepare_fill(Ctx* c, uint32_t n, const void* offsets, uint64_t capacity, void* t_out, void* tri_out, bool offsets_checked, const char* t_name = "t_out_dev") {
+int prepare_fill(Ctx* c, uint32_t n, const void* offsets, uint64_t capacity, void* key_out, void* tri_out, bool offsets_checked, const char* key_name) {
     if (capacity > (uint64_t)1 << 40) return c->fail(RT_ERR_INVALID, "capacity %llu is above 2^40", (unsigned long long)capacity);
     if (!offsets_checked)
         if (int rc = rt::check_device_array(c, offsets, ((size_t)n + 1) * 8, "offsets_in_dev")) return rc;
-    if (capacity || t_out)
-        if (int rc = rt::check_device_array(c, t_out, (size_t)capacity * 4, t_name)) return rc;
+    if (capacity || key_out)
+        if (int rc = rt::check_device_array(c, key_out, (size_t)capacity * 4, key_name)) return rc;
     if (capacity || tri_out)
         if (int rc = rt::check_device_array(c, tri_out, (size_t)capacity * 4, "tri_out_dev")) return rc;
     return RT_OK;
 }
 
-void begin_hit_stats(Ctx* c, uint32_t n) {
-    c->pt.hit_query_stats = rt_hit_query_stats{};
-    c->pt.hit_query_stats.rays = n;
-    c->pt.hit_steps = 0;
-}
-
-int run_count(Ctx* c, rt::HitQuery q, const rt_hit_query_params& prm, const QueryPlan& plan, void* count_out, void* offsets_out, const HitScan& hs, bool last) {
+template <class K>
+int run_count(Ctx* c, typename K::Query q, const typename K::Params& prm, const QueryPlan& plan, void* count_out, void* offsets_out, const ListScan& ls, bool last) {
+    rt::ListingState& st = c->pt.*K::state;
     q.count_out = static_cast<int*>(count_out);
-    q.count64 = hs.counts;
-    if (hs.counts) RT_HIP(c, hipMemsetAsync(hs.counts + q.n, 0, sizeof(unsigned long long), c->stream));  // entry n: offsets[n] = the total
+    q.count64 = ls.counts;
+    if (ls.counts) RT_HIP(c, hipMemsetAsync(ls.counts + q.n, 0, sizeof(unsigned long long), c->stream));  // entry n: offsets[n] = the total
     const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
-        return rt::launch_pt_query_hits(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, false, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
+        return K::launch(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, false, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
     };
     // the scan lies between the events too: it is part of the step
-    if (int rc = run_query(c, c->pt.hit_query, plan, "rt.path_b.count_ray_hits", launch, true, false)) return rc;
-    c->pt.hit_steps |= 1u;
-    c->pt.hit_query_stats.launches += 1;
-    if (hs.counts) {
-        if (int rc = rt::scan_u64_device(c, hs.counts, static_cast<unsigned long long*>(offsets_out), (size_t)q.n + 1, hs.sums, hs.total)) return rc;
-        c->pt.hit_query_stats.launches += 3;
+    if (int rc = run_query(c, st.qs, plan, K::count_range, launch, true, false)) return rc;
+    st.steps |= 1u;
+    (c->pt.*K::stats).launches += 1;
+    if (ls.counts) {
+        if (int rc = rt::scan_u64_device(c, ls.counts, static_cast<unsigned long long*>(offsets_out), (size_t)q.n + 1, ls.sums, ls.total)) return rc;
+        (c->pt.*K::stats).launches += 3;
     }
-    if (last) RT_HIP(c, hipEventRecord(c->pt.hit_query.ev[1], c->stream));
+    if (last) RT_HIP(c, hipEventRecord(st.qs.ev[1], c->stream));
     return RT_OK;
 }
 
-int run_fill(Ctx* c, rt::HitQuery q, const rt_hit_query_params& prm, const QueryPlan& plan, const void* offsets, uint64_t capacity, void* t_out, void* tri_out, bool first) {
+template <class K>
+int run_fill(Ctx* c, typename K::Query q, const typename K::Params& prm, const QueryPlan& plan, const void* offsets, uint64_t capacity, void* key_out, void* tri_out,
+             bool first) {
+    rt::ListingState& st = c->pt.*K::state;
     q.offsets = static_cast<const long long*>(offsets);
     q.capacity = (long long)capacity;
-    q.t_out = static_cast<float*>(t_out);
+    q.key_out = static_cast<float*>(key_out);
     q.tri_out = static_cast<int*>(tri_out);
     const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
-        return rt::launch_pt_query_hits(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, true, head, stats + rt::HQ_STEP_WORDS, grid, sk, refill_min);
+        return K::launch(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, true, head, stats + rt::LQ_STEP_WORDS, grid, sk, refill_min);
     };
-    if (int rc = run_query(c, c->pt.hit_query, plan, "rt.path_b.fill_ray_hits", launch, first, true)) return rc;
-    c->pt.hit_steps |= 2u;
-    c->pt.hit_query_stats.launches += 1;
+    if (int rc = run_query(c, st.qs, plan, K::fill_range, launch, first, true)) return rc;
+    st.steps |= 2u;
+    (c->pt.*K::stats).launches += 1;
     return RT_OK;
 }
 
-// What the three entries of the hit kind and of the neighbour kind share up to the kind's own arrays: context, defaults, parameter checks, n == 0 (returns 1: done, RT_OK)
-template <class Params>
-int enter_listing(Ctx* c, uint32_t n, const Params*& prm, const Params& defaults, int* done) {
-    *done = 0;
-    if (!prm) prm = &defaults;
-    if (int rc = check_query_params(c, n, *prm, prm->count_traversal, "count_traversal")) return rc;
-    if (n == 0) {
-        *done = 1;
-        return RT_OK;
+// A call of a listing kind.  steps = 1: the count step (count_out, offsets_out), 2: the fill step on the caller's offsets, 3: the
+// list call - the count step, then the fill step on its offsets_out, one plan for the two walks (the same kind on the same items)
+// and one pair of events around both.  Both steps' refusals and first-use allocations come before the first enqueue.
+template <class K>
+int listing_call(rt_ctx* ctx, const typename K::Source& src, uint32_t n, const typename K::Params* prm, uint32_t steps, void* count_out, void* offsets_out,
+                 const void* offsets_in, uint64_t capacity, void* key_out, void* tri_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const typename K::Params defaults{};
+    int done;
+    if (int rc = enter_query(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
+    const bool count = steps & 1u, fill = steps & 2u;
+    typename K::Query q{};
+    QueryPlan plan{};
+    ListScan ls{};
+    if (count && fill) {
+        if (!offsets_out) return c->fail(RT_ERR_INVALID, "offsets_out_dev is NULL");
+        offsets_in = offsets_out;
     }
-    return rt::bind(c);
-}
-
-// ---- neighbours: the hit kind's two steps on pt_query_points' inputs; the scan and its scratch are the hit kind's ----
-int prepare_neighbors(Ctx* c, const void* points, const void* rmax, float rmax_all, uint32_t n, const rt_neighbor_query_params& prm, rt::NeighborQuery* q, QueryPlan* plan) {
-    const rt::DeviceMesh& mesh = c->pt.mesh();
-    if (int rc = rt::check_device_array(c, points, (size_t)n * 12, "points_dev")) return rc;
-    if (rmax)
-        if (int rc = rt::check_device_array(c, rmax, (size_t)n * 4, "rmax_dev")) return rc;
-    *q = rt::NeighborQuery{};
-    q->points = static_cast<const float*>(points);
-    q->rmax = static_cast<const float*>(rmax);
-    q->rmax_all = rmax_all;
-    q->n = n;
-    q->reach = rt::kCameraReach * mesh.maxabs;
-    // a group walk like the rays': one pending sibling group per level, so the spill columns are the ray kinds' (DESIGN.md §6.17)
-    return prepare_query(c, c->pt.neighbor_query, n, prm, mesh.stack_need, plan);
-}
-
-void begin_neighbor_stats(Ctx* c, uint32_t n) {
-    c->pt.neighbor_query_stats = rt_neighbor_query_stats{};
-    c->pt.neighbor_query_stats.points = n;
-    c->pt.neighbor_steps = 0;
-}
-
-int run_neighbor_count(Ctx* c, rt::NeighborQuery q, const rt_neighbor_query_params& prm, const QueryPlan& plan, void* count_out, void* offsets_out, const HitScan& hs,
-                       bool last) {
-    q.count_out = static_cast<int*>(count_out);
-    q.count64 = hs.counts;
-    if (hs.counts) RT_HIP(c, hipMemsetAsync(hs.counts + q.n, 0, sizeof(unsigned long long), c->stream));  // entry n: offsets[n] = the total
-    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
-        return rt::launch_pt_query_neighbors(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, false, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
-    };
-    // the scan lies between the events too: it is part of the step
-    if (int rc = run_query(c, c->pt.neighbor_query, plan, "rt.path_b.count_neighbors", launch, true, false)) return rc;
-    c->pt.neighbor_steps |= 1u;
-    c->pt.neighbor_query_stats.launches += 1;
-    if (hs.counts) {
-        if (int rc = rt::scan_u64_device(c, hs.counts, static_cast<unsigned long long*>(offsets_out), (size_t)q.n + 1, hs.sums, hs.total)) return rc;
-        c->pt.neighbor_query_stats.launches += 3;
-    }
-    if (last) RT_HIP(c, hipEventRecord(c->pt.neighbor_query.ev[1], c->stream));
-    return RT_OK;
-}
-
-int run_neighbor_fill(Ctx* c, rt::NeighborQuery q, const rt_neighbor_query_params& prm, const QueryPlan& plan, const void* offsets, uint64_t capacity, void* dist_out,
-                      void* tri_out, bool first) {
-    q.offsets = static_cast<const long long*>(offsets);
-    q.capacity = (long long)capacity;
-    q.dist_out = static_cast<float*>(dist_out);
-    q.tri_out = static_cast<int*>(tri_out);
-    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
-        return rt::launch_pt_query_neighbors(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, true, head, stats + rt::NQ_STEP_WORDS, grid, sk, refill_min);
-    };
-    if (int rc = run_query(c, c->pt.neighbor_query, plan, "rt.path_b.fill_neighbors", launch, first, true)) return rc;
-    c->pt.neighbor_steps |= 2u;
-    c->pt.neighbor_query_stats.launches += 1;
+    if (count)
+        if (int rc = prepare_count(c, n, count_out, offsets_out, &ls)) return rc;
+    if (fill)
+        if (int rc = prepare_fill(c, n, offsets_in, capacity, key_out, tri_out, count, K::key_name)) return rc;
+    if (int rc = K::prepare(c, src, n, *prm, &q, &plan)) return rc;
+    c->pt.*K::stats = typename K::Stats{};
+    (c->pt.*K::stats).*K::items = n;
+    (c->pt.*K::state).steps = 0;
+    if (count)
+        if (int rc = run_count<K>(c, q, *prm, plan, count_out, offsets_out, ls, !fill)) return rc;
+    if (fill) return run_fill<K>(c, q, *prm, plan, offsets_in, capacity, key_out, tri_out, !count);
     return RT_OK;
 }
 
@@ -315,13 +359,38 @@ int read_query(Ctx* c, QueryState& qs, unsigned long long* counters, float* ms) 
     return RT_OK;
 }
 
+// rt_get_*_query_stats of a listing kind: the two steps' counter words folded into the public struct
+template <class K>
+int listing_stats(rt_ctx* ctx, typename K::Stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    typename K::Stats& s = c->pt.*K::stats;
+    rt::ListingState& st = c->pt.*K::state;
+    if (st.qs.pending) {
+        unsigned long long w[rt::LQ_STAT_WORDS] = {};
+        if (int rc = read_query(c, st.qs, w, &s.ms)) return rc;
+        const unsigned long long *cs = w, *fs = w + rt::LQ_STEP_WORDS;  // the count step's words, the fill step's
+        const unsigned long long* any = (st.steps & 1u) ? cs : fs;      // both steps meet the same items and find the same
+        s.*K::invalid = any[rt::LQ_STAT_INVALID];
+        s.*K::found = any[rt::LQ_STAT_FOUND];
+        s.*K::written = fs[rt::LQ_STAT_WRITTEN];
+        s.*K::incomplete = fs[rt::LQ_STAT_INCOMPLETE];
+        s.slice_overflow = fs[rt::LQ_STAT_SLICE_OVERFLOW];
+        s.nodes_visited = cs[rt::LQ_STAT_NODES] + fs[rt::LQ_STAT_NODES];
+        s.tris_tested = cs[rt::LQ_STAT_TRIS] + fs[rt::LQ_STAT_TRIS];
+        s.stack_overflow = (uint32_t)(cs[rt::LQ_STAT_OVERFLOW] | fs[rt::LQ_STAT_OVERFLOW]);
+    }
+    *stats = s;
+    return RT_OK;
+}
+
 }  // namespace
 
 namespace rt {
 void query_free(Ctx* c) {
-    c->pt.d_hit_scan.reset();
-    c->pt.hit_scan_words = 0;
-    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query, &c->pt.neighbor_query}) {
+    c->pt.d_list_scan.reset();
+    c->pt.list_scan_words = 0;
+    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query.qs, &c->pt.neighbor_query.qs}) {
         qs->block.reset();
         for (hipEvent_t& e : qs->ev) {
             if (e) (void)hipEventDestroy(e);
@@ -334,21 +403,16 @@ void query_free(Ctx* c) {
 
 extern "C" {
 
-int rt_default_ray_query_params(rt_ray_query_params* p) {
-    if (!p) return RT_ERR_INVALID;
-    *p = rt_ray_query_params{};
-    return RT_OK;
-}
+int rt_default_ray_query_params(rt_ray_query_params* p) { return default_params(p); }
 
 // Everything that can refuse a call comes before the first enqueue (in enqueue_query)
 int rt_query_rays_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_ray_query_params* prm, void* t_out, void* tri_out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
-    rt_ray_query_params defaults{};
-    if (!prm) prm = &defaults;
-    if (int rc = check_query_params(c, n, *prm, prm->any_hit, "any_hit")) return rc;
-    if (n == 0) return RT_OK;
-    if (int rc = rt::bind(c)) return rc;
+    const rt_ray_query_params defaults{};
+    int done;
+    if (int rc = enter_query(c, n, prm, defaults, &done, &rt_ray_query_params::any_hit, "any_hit")) return rc;
+    if (done) return RT_OK;
     const rt::DeviceMesh& mesh = c->pt.mesh();
     const bool any_hit = prm->any_hit != 0u;
     if (int rc = rt::check_device_array(c, origins, (size_t)n * 12, "origins_dev")) return rc;
@@ -390,20 +454,15 @@ int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats) {
     return RT_OK;
 }
 
-int rt_default_point_query_params(rt_point_query_params* p) {
-    if (!p) return RT_ERR_INVALID;
-    *p = rt_point_query_params{};
-    return RT_OK;
-}
+int rt_default_point_query_params(rt_point_query_params* p) { return default_params(p); }
 
 int rt_query_points_device(rt_ctx* ctx, const void* points, const void* rmax, uint32_t n, const rt_point_query_params* prm, void* dist_out, void* tri_out, void* point_out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
-    rt_point_query_params defaults{};
-    if (!prm) prm = &defaults;
-    if (int rc = check_query_params(c, n, *prm, prm->count_traversal, "count_traversal")) return rc;
-    if (n == 0) return RT_OK;
-    if (int rc = rt::bind(c)) return rc;
+    const rt_point_query_params defaults{};
+    int done;
+    if (int rc = enter_query(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
     rt::PointQuery q{};
     QueryPlan plan{};
     if (int rc = prepare_points(c, points, rmax, n, *prm, dist_out, tri_out, point_out, &q, &plan)) return rc;
@@ -426,20 +485,15 @@ int rt_get_point_query_stats(rt_ctx* ctx, rt_point_query_stats* stats) {
     return RT_OK;
 }
 
-int rt_default_side_query_params(rt_side_query_params* p) {
-    if (!p) return RT_ERR_INVALID;
-    *p = rt_side_query_params{};
-    return RT_OK;
-}
+int rt_default_side_query_params(rt_side_query_params* p) { return default_params(p); }
 
 int rt_query_sides_device(rt_ctx* ctx, const void* points, uint32_t n, const rt_side_query_params* prm, void* inside_out, void* crossings_out, void* dist_inout) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
-    rt_side_query_params defaults{};
-    if (!prm) prm = &defaults;
-    if (int rc = check_query_params(c, n, *prm, prm->count_traversal, "count_traversal")) return rc;
-    if (n == 0) return RT_OK;
-    if (int rc = rt::bind(c)) return rc;
+    const rt_side_query_params defaults{};
+    int done;
+    if (int rc = enter_query(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
     rt::SideQuery q{};
     QueryPlan plan{};
     if (int rc = prepare_sides(c, points, n, *prm, inside_out, true, crossings_out, dist_inout, &q, &plan)) return rc;
@@ -451,14 +505,13 @@ int rt_query_signed_distance_device(rt_ctx* ctx, const void* points, const void*
                                     void* sdist_out, void* tri_out, void* point_out, void* inside_out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
-    rt_point_query_params pdefaults{};
-    rt_side_query_params sdefaults{};
-    if (!pprm) pprm = &pdefaults;
-    if (!sprm) sprm = &sdefaults;
-    if (int rc = check_query_params(c, n, *pprm, pprm->count_traversal, "count_traversal")) return rc;
-    if (int rc = check_query_params(c, n, *sprm, sprm->count_traversal, "count_traversal")) return rc;
-    if (n == 0) return RT_OK;
-    if (int rc = rt::bind(c)) return rc;
+    const rt_point_query_params pdefaults{};
+    const rt_side_query_params sdefaults{};
+    int done;
+    if (int rc = use_params(c, n, pprm, pdefaults)) return rc;
+    if (int rc = use_params(c, n, sprm, sdefaults)) return rc;
+    if (int rc = begin_query(c, n, &done)) return rc;
+    if (done) return RT_OK;
     rt::PointQuery pq{};
     rt::SideQuery sq{};
     QueryPlan pplan{}, splan{};
@@ -487,168 +540,42 @@ int rt_get_side_query_stats(rt_ctx* ctx, rt_side_query_stats* stats) {
     return RT_OK;
 }
 
-int rt_default_hit_query_params(rt_hit_query_params* p) {
-    if (!p) return RT_ERR_INVALID;
-    *p = rt_hit_query_params{};
-    return RT_OK;
-}
+int rt_default_hit_query_params(rt_hit_query_params* p) { return default_params(p); }
 
 int rt_count_ray_hits_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_hit_query_params* prm, void* count_out,
                              void* offsets_out) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c) return RT_ERR_INVALID;
-    const rt_hit_query_params defaults{};
-    int done;
-    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
-    if (done) return RT_OK;
-    rt::HitQuery q{};
-    QueryPlan plan{};
-    HitScan hs{};
-    if (int rc = prepare_count(c, n, count_out, offsets_out, &hs)) return rc;
-    if (int rc = prepare_hits(c, origins, dirs, tmax, n, *prm, &q, &plan)) return rc;
-    begin_hit_stats(c, n);
-    return run_count(c, q, *prm, plan, count_out, offsets_out, hs, true);
+    return listing_call<HitKind>(ctx, {origins, dirs, tmax}, n, prm, 1u, count_out, offsets_out, nullptr, 0, nullptr, nullptr);
 }
 
 int rt_fill_ray_hits_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_hit_query_params* prm, const void* offsets_in,
                             uint64_t capacity, void* t_out, void* tri_out) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c) return RT_ERR_INVALID;
-    const rt_hit_query_params defaults{};
-    int done;
-    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
-    if (done) return RT_OK;
-    rt::HitQuery q{};
-    QueryPlan plan{};
-    if (int rc = prepare_fill(c, n, offsets_in, capacity, t_out, tri_out, false)) return rc;
-    if (int rc = prepare_hits(c, origins, dirs, tmax, n, *prm, &q, &plan)) return rc;
-    begin_hit_stats(c, n);
-    return run_fill(c, q, *prm, plan, offsets_in, capacity, t_out, tri_out, true);
+    return listing_call<HitKind>(ctx, {origins, dirs, tmax}, n, prm, 2u, nullptr, nullptr, offsets_in, capacity, t_out, tri_out);
 }
 
-// rt_count_ray_hits_device, then rt_fill_ray_hits_device on its offsets; both steps' refusals and first-use allocations before the first enqueue
 int rt_list_ray_hits_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_hit_query_params* prm, void* count_out,
                             void* offsets_out, uint64_t capacity, void* t_out, void* tri_out) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c) return RT_ERR_INVALID;
-    const rt_hit_query_params defaults{};
-    int done;
-    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
-    if (done) return RT_OK;
-    rt::HitQuery q{};
-    QueryPlan plan{};
-    HitScan hs{};
-    if (!offsets_out) return c->fail(RT_ERR_INVALID, "offsets_out_dev is NULL");
-    if (int rc = prepare_count(c, n, count_out, offsets_out, &hs)) return rc;
-    if (int rc = prepare_fill(c, n, offsets_out, capacity, t_out, tri_out, true)) return rc;
-    if (int rc = prepare_hits(c, origins, dirs, tmax, n, *prm, &q, &plan)) return rc;  // one plan: the two walks are the same kind on the same rays
-    begin_hit_stats(c, n);
-    if (int rc = run_count(c, q, *prm, plan, count_out, offsets_out, hs, false)) return rc;
-    return run_fill(c, q, *prm, plan, offsets_out, capacity, t_out, tri_out, false);
+    return listing_call<HitKind>(ctx, {origins, dirs, tmax}, n, prm, 3u, count_out, offsets_out, nullptr, capacity, t_out, tri_out);
 }
 
-int rt_get_hit_query_stats(rt_ctx* ctx, rt_hit_query_stats* stats) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !stats) return RT_ERR_INVALID;
-    rt_hit_query_stats& s = c->pt.hit_query_stats;
-    if (c->pt.hit_query.pending) {
-        unsigned long long st[rt::HQ_STAT_WORDS] = {};
-        if (int rc = read_query(c, c->pt.hit_query, st, &s.ms)) return rc;
-        const unsigned long long *cs = st, *fs = st + rt::HQ_STEP_WORDS;  // the count step's words, the fill step's
-        const unsigned long long* any = (c->pt.hit_steps & 1u) ? cs : fs;  // both steps meet the same rays and the same hits
-        s.invalid_rays = any[rt::HQ_STAT_INVALID];
-        s.hits = any[rt::HQ_STAT_HITS];
-        s.hits_written = fs[rt::HQ_STAT_WRITTEN];
-        s.incomplete_rays = fs[rt::HQ_STAT_INCOMPLETE];
-        s.slice_overflow = fs[rt::HQ_STAT_SLICE_OVERFLOW];
-        s.nodes_visited = cs[rt::HQ_STAT_NODES] + fs[rt::HQ_STAT_NODES];
-        s.tris_tested = cs[rt::HQ_STAT_TRIS] + fs[rt::HQ_STAT_TRIS];
-        s.stack_overflow = (uint32_t)(cs[rt::HQ_STAT_OVERFLOW] | fs[rt::HQ_STAT_OVERFLOW]);
-    }
-    *stats = s;
-    return RT_OK;
-}
+int rt_get_hit_query_stats(rt_ctx* ctx, rt_hit_query_stats* stats) { return listing_stats<HitKind>(ctx, stats); }
 
-int rt_default_neighbor_query_params(rt_neighbor_query_params* p) {
-    if (!p) return RT_ERR_INVALID;
-    *p = rt_neighbor_query_params{};
-    return RT_OK;
-}
+int rt_default_neighbor_query_params(rt_neighbor_query_params* p) { return default_params(p); }
 
 int rt_count_neighbors_device(rt_ctx* ctx, const void* points, const void* rmax, float rmax_all, uint32_t n, const rt_neighbor_query_params* prm, void* count_out,
                               void* offsets_out) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c) return RT_ERR_INVALID;
-    const rt_neighbor_query_params defaults{};
-    int done;
-    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
-    if (done) return RT_OK;
-    rt::NeighborQuery q{};
-    QueryPlan plan{};
-    HitScan hs{};
-    if (int rc = prepare_count(c, n, count_out, offsets_out, &hs)) return rc;
-    if (int rc = prepare_neighbors(c, points, rmax, rmax_all, n, *prm, &q, &plan)) return rc;
-    begin_neighbor_stats(c, n);
-    return run_neighbor_count(c, q, *prm, plan, count_out, offsets_out, hs, true);
+    return listing_call<NeighborKind>(ctx, {points, rmax, rmax_all}, n, prm, 1u, count_out, offsets_out, nullptr, 0, nullptr, nullptr);
 }
 
 int rt_fill_neighbors_device(rt_ctx* ctx, const void* points, const void* rmax, float rmax_all, uint32_t n, const rt_neighbor_query_params* prm, const void* offsets_in,
                              uint64_t capacity, void* dist_out, void* tri_out) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c) return RT_ERR_INVALID;
-    const rt_neighbor_query_params defaults{};
-    int done;
-    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
-    if (done) return RT_OK;
-    rt::NeighborQuery q{};
-    QueryPlan plan{};
-    if (int rc = prepare_fill(c, n, offsets_in, capacity, dist_out, tri_out, false, "dist_out_dev")) return rc;
-    if (int rc = prepare_neighbors(c, points, rmax, rmax_all, n, *prm, &q, &plan)) return rc;
-    begin_neighbor_stats(c, n);
-    return run_neighbor_fill(c, q, *prm, plan, offsets_in, capacity, dist_out, tri_out, true);
+    return listing_call<NeighborKind>(ctx, {points, rmax, rmax_all}, n, prm, 2u, nullptr, nullptr, offsets_in, capacity, dist_out, tri_out);
 }
 
-// rt_count_neighbors_device, then rt_fill_neighbors_device on its offsets; both steps' refusals and first-use allocations before the first enqueue
 int rt_list_neighbors_device(rt_ctx* ctx, const void* points, const void* rmax, float rmax_all, uint32_t n, const rt_neighbor_query_params* prm, void* count_out,
                              void* offsets_out, uint64_t capacity, void* dist_out, void* tri_out) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c) return RT_ERR_INVALID;
-    const rt_neighbor_query_params defaults{};
-    int done;
-    if (int rc = enter_listing(c, n, prm, defaults, &done)) return rc;
-    if (done) return RT_OK;
-    rt::NeighborQuery q{};
-    QueryPlan plan{};
-    HitScan hs{};
-    if (!offsets_out) return c->fail(RT_ERR_INVALID, "offsets_out_dev is NULL");
-    if (int rc = prepare_count(c, n, count_out, offsets_out, &hs)) return rc;
-    if (int rc = prepare_fill(c, n, offsets_out, capacity, dist_out, tri_out, true, "dist_out_dev")) return rc;
-    if (int rc = prepare_neighbors(c, points, rmax, rmax_all, n, *prm, &q, &plan)) return rc;  // one plan: the two walks are the same kind on the same points
-    begin_neighbor_stats(c, n);
-    if (int rc = run_neighbor_count(c, q, *prm, plan, count_out, offsets_out, hs, false)) return rc;
-    return run_neighbor_fill(c, q, *prm, plan, offsets_out, capacity, dist_out, tri_out, false);
+    return listing_call<NeighborKind>(ctx, {points, rmax, rmax_all}, n, prm, 3u, count_out, offsets_out, nullptr, capacity, dist_out, tri_out);
 }
 
-int rt_get_neighbor_query_stats(rt_ctx* ctx, rt_neighbor_query_stats* stats) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !stats) return RT_ERR_INVALID;
-    rt_neighbor_query_stats& s = c->pt.neighbor_query_stats;
-    if (c->pt.neighbor_query.pending) {
-        unsigned long long st[rt::NQ_STAT_WORDS] = {};
-        if (int rc = read_query(c, c->pt.neighbor_query, st, &s.ms)) return rc;
-        const unsigned long long *cs = st, *fs = st + rt::NQ_STEP_WORDS;  // the count step's words, the fill step's
-        const unsigned long long* any = (c->pt.neighbor_steps & 1u) ? cs : fs;  // both steps meet the same points and the same neighbours
-        s.invalid_points = any[rt::NQ_STAT_INVALID];
-        s.neighbors = any[rt::NQ_STAT_NEIGHBORS];
-        s.neighbors_written = fs[rt::NQ_STAT_WRITTEN];
-        s.incomplete_points = fs[rt::NQ_STAT_INCOMPLETE];
-        s.slice_overflow = fs[rt::NQ_STAT_SLICE_OVERFLOW];
-        s.nodes_visited = cs[rt::NQ_STAT_NODES] + fs[rt::NQ_STAT_NODES];
-        s.tris_tested = cs[rt::NQ_STAT_TRIS] + fs[rt::NQ_STAT_TRIS];
-        s.stack_overflow = (uint32_t)(cs[rt::NQ_STAT_OVERFLOW] | fs[rt::NQ_STAT_OVERFLOW]);
-    }
-    *stats = s;
-    return RT_OK;
-}
+int rt_get_neighbor_query_stats(rt_ctx* ctx, rt_neighbor_query_stats* stats) { return listing_stats<NeighborKind>(ctx, stats); }
 
 }  // extern "C"

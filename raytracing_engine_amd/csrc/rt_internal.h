@@ -246,16 +246,12 @@ struct HitQuery {
     unsigned long long* count64;  // n (the scan's input column: max(count, 0)), or nullptr
     // the fill step
     const long long* offsets;  // n + 1
-    long long capacity;        // elements of t_out / tri_out
-    float* t_out;
+    long long capacity;        // elements of key_out / tri_out
+    float* key_out;            // t
     int* tri_out;
     uint32_t n;
     float reach;  // |origin component| limit: kCameraReach x the mesh's maxabs
 };
-// Counters of an all-hits query: one set per step (the fill step's HQ_STEP_WORDS words behind the count step's), so that the two
-// launches of rt_list_ray_hits_device report side by side
-enum { HQ_STAT_INVALID = 0, HQ_STAT_OVERFLOW = 1, HQ_STAT_NODES = 2, HQ_STAT_TRIS = 3, HQ_STAT_HITS = 4, HQ_STAT_WRITTEN = 5, HQ_STAT_INCOMPLETE = 6,
-       HQ_STAT_SLICE_OVERFLOW = 7, HQ_STEP_WORDS = 8, HQ_STAT_WORDS = 2 * HQ_STEP_WORDS };
 
 // rt_count_neighbors_device / rt_fill_neighbors_device: the points of one step and where its answers go.  Point i is queue entry i.
 struct NeighborQuery {
@@ -267,15 +263,16 @@ struct NeighborQuery {
     unsigned long long* count64;  // n (the scan's input column: max(count, 0)), or nullptr
     // the fill step
     const long long* offsets;  // n + 1
-    long long capacity;        // elements of dist_out / tri_out
-    float* dist_out;
+    long long capacity;        // elements of key_out / tri_out
+    float* key_out;            // dist (d2 until the lane retires)
     int* tri_out;
     uint32_t n;
     float reach;  // |component| limit: kCameraReach x the mesh's maxabs
 };
-// Counters of a neighbour query: one set per step, as the all-hits kind's
-enum { NQ_STAT_INVALID = 0, NQ_STAT_OVERFLOW = 1, NQ_STAT_NODES = 2, NQ_STAT_TRIS = 3, NQ_STAT_NEIGHBORS = 4, NQ_STAT_WRITTEN = 5, NQ_STAT_INCOMPLETE = 6,
-       NQ_STAT_SLICE_OVERFLOW = 7, NQ_STEP_WORDS = 8, NQ_STAT_WORDS = 2 * NQ_STEP_WORDS };
+// Counters of a listing query (all hits, neighbours): one set per step (the fill step's LQ_STEP_WORDS words behind the count step's),
+// so that the two launches of a list call report side by side.  FOUND: hits / neighbours met.
+enum { LQ_STAT_INVALID = 0, LQ_STAT_OVERFLOW = 1, LQ_STAT_NODES = 2, LQ_STAT_TRIS = 3, LQ_STAT_FOUND = 4, LQ_STAT_WRITTEN = 5, LQ_STAT_INCOMPLETE = 6,
+       LQ_STAT_SLICE_OVERFLOW = 7, LQ_STEP_WORDS = 8, LQ_STAT_WORDS = 2 * LQ_STEP_WORDS };
 
 struct MeshHost {  // host side of a two-level mesh: what rt_update_mesh_chunk needs to rebuild one chunk
     TwoLevelBvh tl;
@@ -306,17 +303,23 @@ bool dalloc(DevPtr<T>& p, size_t count) {  // frees what p held first; false: ou
 
 // What a context keeps per query kind.  The device block is PT_HEADS stream heads (PT_HEAD_STRIDE words apart), then the kind's
 // 64-bit counters; it is cleared before every launch.  One block per kind: a query's counters stay until rt_get_*_query_stats reads
-// them, whatever the other kind does meanwhile.  Allocated by the kind's first query, freed with the context (rt_abi_query.hip).
+// them, whatever the other kinds do meanwhile.  Allocated by the kind's first query, freed with the context (rt_abi_query.hip).
 constexpr size_t kQueryHeadBytes = (size_t)PT_HEADS * PT_HEAD_STRIDE * sizeof(uint32_t);
 constexpr size_t query_block_bytes(uint32_t n_counters) { return kQueryHeadBytes + (size_t)n_counters * sizeof(unsigned long long); }
 struct QueryState {
     QueryState(uint32_t k, const char* what, uint32_t lds, uint32_t halves) : n_counters(k), name(what), fixed_lds_bytes(lds), spill_halves(halves) {}
-    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS / SQ_STAT_WORDS / HQ_STAT_WORDS
+    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS / SQ_STAT_WORDS / LQ_STAT_WORDS
     const char* name;     // for messages
     uint32_t fixed_lds_bytes, spill_halves;  // pt_stack_config's: the kernel's LDS beside the stacks, the sets of spill columns it is given
     DevPtr<char> block;
     hipEvent_t ev[2] = {nullptr, nullptr};  // around the launch
     bool pending = false;  // a query has been enqueued whose counters and time rt_get_*_query_stats has not read yet
+};
+// A listing kind's QueryState (no LDS beside the stacks, one set of spill columns: one group per level) and its pending call's steps
+struct ListingState {
+    explicit ListingState(const char* what) : qs(LQ_STAT_WORDS, what, 0u, 1u) {}
+    QueryState qs;
+    uint32_t steps = 0;  // bit 0: the count step ran, bit 1: the fill step
 };
 
 // A mesh resident on the device: the arrays the kernels read and what the host knows about them.  Made by the host build
@@ -363,21 +366,18 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     DevPtr<uint32_t> d_ctr;
     DevPtr<unsigned long long> d_stats;  // PT_STAT_WORDS words
     rt_pt_stats stats{};
-    // rt_query_rays_device / rt_query_points_device / rt_query_sides_device: what is in flight, and the statistics of the last query of each kind
-    // (rays: the 2 KiB octant table, two spill halves as the frames hold; points and sides: no table, one set of columns)
+    // the five query kinds (rays, closest points, sides, all hits, neighbours): what is in flight, and the statistics of the last query of each kind
+    // (rays: the 2 KiB octant table, two spill halves as the frames hold; the others: no table, one set of columns)
     QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u}, side_query{SQ_STAT_WORDS, "side-query", 0u, 1u};
-    QueryState hit_query{HQ_STAT_WORDS, "hit-query", 0u, 1u};  // rt_count / fill / list_ray_hits_device: as sides
-    QueryState neighbor_query{NQ_STAT_WORDS, "neighbor-query", 0u, 1u};  // rt_count / fill / list_neighbors_device: a group walk, one group per level
+    ListingState hit_query{"hit-query"}, neighbor_query{"neighbor-query"};  // rt_count / fill / list_ray_hits_device, rt_count / fill / list_neighbors_device
     rt_ray_query_stats ray_query_stats{};
     rt_point_query_stats point_query_stats{};
     rt_side_query_stats side_query_stats{};
     rt_hit_query_stats hit_query_stats{};
     rt_neighbor_query_stats neighbor_query_stats{};
-    uint32_t hit_steps = 0;       // bit 0: the pending hit query ran the count step, bit 1: the fill step
-    uint32_t neighbor_steps = 0;  // the same of the pending neighbour query
-    // the hit and the neighbour queries' scan: the 64-bit count column (n + 1), the scan's tile sums and its total; grows by size class, first use only
-    DevPtr<unsigned long long> d_hit_scan;
-    size_t hit_scan_words = 0;
+    // the listing kinds' scan: the 64-bit count column (n + 1), the scan's tile sums and its total; grows by size class, first use only
+    DevPtr<unsigned long long> d_list_scan;
+    size_t list_scan_words = 0;
 };
 
 struct Ctx {
@@ -481,10 +481,10 @@ int launch_pt_query_points(Ctx* c, const PtScene& sc, const PointQuery& q, bool 
                            const StackCfg& sk, uint32_t refill_min);
 int launch_pt_query_sides(Ctx* c, const PtScene& sc, const SideQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                           const StackCfg& sk, uint32_t refill_min);  // q.crossings_out != nullptr: all three walks for every point
-// fill = false: the count step (q.count_out / q.count64), true: the fill step (q.offsets, q.capacity, q.t_out, q.tri_out); stats: the step's own HQ_STEP_WORDS
+// fill = false: the count step (q.count_out / q.count64), true: the fill step (q.offsets, q.capacity, q.key_out, q.tri_out); stats: the step's own LQ_STEP_WORDS
 int launch_pt_query_hits(Ctx* c, const PtScene& sc, const HitQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
                          const StackCfg& sk, uint32_t refill_min);
-// the same two steps of a neighbour query (q.dist_out in the place of q.t_out); stats: the step's own NQ_STEP_WORDS
+// the same two steps of a neighbour query
 int launch_pt_query_neighbors(Ctx* c, const PtScene& sc, const NeighborQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
                               const StackCfg& sk, uint32_t refill_min);
 void pt_free(Ctx* c);

@@ -440,14 +440,23 @@ class Renderer:
 
     RAY_MISS, RAY_INVALID = _lib.RAY_MISS, _lib.RAY_INVALID
 
-    def _device_i32(self, t, name, n):
-        """`t` must be a contiguous int32 torch tensor of n elements on this renderer's device; ValueError otherwise."""
+    def _device_ints(self, t, name, n, kind):
+        """`t` must be a contiguous torch tensor of n elements of the integer type `kind` on this renderer's device; ValueError otherwise."""
         import torch
 
+        dtype = getattr(torch, kind)
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device or t.dim() != 1 or t.numel() != n:
-            raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if t.dtype != dtype or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device or t.dim() != 1 or t.numel() != n:
+            raise ValueError(f"{name} must be a contiguous {kind} tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+    def _device_i32(self, t, name, n):
+        """_device_ints for int32."""
+        self._device_ints(t, name, n, "int32")
+
+    def _device_i64(self, t, name, n):
+        """_device_ints for int64."""
+        self._device_ints(t, name, n, "int64")
 
     def _query_tune(self, params, tune, method):
         """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors) into its parameter struct;
@@ -463,8 +472,8 @@ class Renderer:
 
         if t is None:
             return torch.empty(n if cols == 1 else (n, cols), dtype=dtype, device=dev)
-        if dtype == torch.int32:
-            self._device_i32(t, name, n)
+        if dtype in (torch.int32, torch.int64):
+            (self._device_i32 if dtype == torch.int32 else self._device_i64)(t, name, n)
         elif self._device_rows(t, name, cols) != n or (cols == 1 and t.dim() != 1):
             raise ValueError(f"{name} must have shape ({n},), got {tuple(t.shape)}" if cols == 1 else f"{name} must hold {n} rows of {cols}")
         return t
@@ -479,6 +488,40 @@ class Renderer:
         if sync:
             self.synchronize()
 
+    def _query_stats(self, stats, name):
+        """The C struct `stats` filled by the library's `name` (waits for the kind's pending query), as a dict."""
+        self._check(getattr(self._lib, name)(self._ctx, C.byref(stats)))
+        return stats.as_dict()
+
+    def _ray_rows(self, origins, dirs, tmax):
+        """The ray count of a ray or all-hits query once its three inputs are what the library can read."""
+        n = self._device_rows(origins, "origins", 3)
+        if self._device_rows(dirs, "dirs", 3) != n:
+            raise ValueError("origins and dirs disagree on the ray count")
+        if tmax is not None and (self._device_rows(tmax, "tmax", 1) != n or tmax.dim() != 1):
+            raise ValueError(f"tmax must have shape ({n},), got {tuple(tmax.shape)}")
+        return n
+
+    def _point_rows(self, points, rmax):
+        """The point count of a query on points once points and the rmax tensor (or None) are what the library can read."""
+        n = self._device_rows(points, "points", 3)
+        if rmax is not None and (self._device_rows(rmax, "rmax", 1) != n or rmax.dim() != 1):
+            raise ValueError(f"rmax must have shape ({n},), got {tuple(rmax.shape)}")
+        return n
+
+    def _point_out(self, out, first, n, dev, want_points):
+        """The (dist, tri, point) tensors of query_points / query_signed_distance: new ones, or those of `out`.  first: dist's name."""
+        import torch
+
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != (3 if want_points else 2)):
+            raise ValueError(f"out must be ({first}, tri, point), or the pair ({first}, tri) with want_points=False")
+        dist, tri, pt = (tuple(out) + (None,))[:3] if out is not None else (None, None, None)
+        dist = self._query_out(dist, f"out {first}", n, torch.float32, dev)
+        tri = self._query_out(tri, "out tri", n, torch.int32, dev)
+        if want_points:
+            pt = self._query_out(pt, "out point", n, torch.float32, dev, cols=3)
+        return dist, tri, pt
+
     def query_rays(self, origins, dirs, tmax=None, any_hit=False, out=None, sync=True, **tune):
         """What do rays hit in the current mesh?  (rt_query_rays_device)  origins, dirs: float32 torch tensors on this
         renderer's device, contiguous, (n, 3) or flat; tmax: (n,) or None.  A triangle is hit when 0 < t < tmax (default: +inf for the
@@ -490,11 +533,7 @@ class Renderer:
         tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_ray_query_params."""
         import torch
 
-        n = self._device_rows(origins, "origins", 3)
-        if self._device_rows(dirs, "dirs", 3) != n:
-            raise ValueError("origins and dirs disagree on the ray count")
-        if tmax is not None and (self._device_rows(tmax, "tmax", 1) != n or tmax.dim() != 1):
-            raise ValueError(f"tmax must have shape ({n},), got {tuple(tmax.shape)}")
+        n = self._ray_rows(origins, dirs, tmax)
         p = RayQueryParams()
         p.any_hit = int(bool(any_hit))
         self._query_tune(p, tune, "query_rays")
@@ -512,9 +551,7 @@ class Renderer:
 
     def ray_query_stats(self):
         """rt_ray_query_stats of the last query as a dict (waits for it): rays, invalid_rays, stack_overflow, launches, ms."""
-        s = RayQueryStats()
-        self._check(self._lib.rt_get_ray_query_stats(self._ctx, C.byref(s)))
-        return s.as_dict()
+        return self._query_stats(RayQueryStats(), "rt_get_ray_query_stats")
 
     POINT_MISS, POINT_INVALID = _lib.POINT_MISS, _lib.POINT_INVALID
 
@@ -529,30 +566,18 @@ class Renderer:
         sync=False does neither: for callers that handed torch's stream to set_stream().  count_traversal=True: point_query_stats()
         reports nodes_visited / tris_tested.  tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of
         rt_point_query_params."""
-        import torch
-
-        n = self._device_rows(points, "points", 3)
-        if rmax is not None and (self._device_rows(rmax, "rmax", 1) != n or rmax.dim() != 1):
-            raise ValueError(f"rmax must have shape ({n},), got {tuple(rmax.shape)}")
+        n = self._point_rows(points, rmax)
         p = PointQueryParams()
         p.count_traversal = int(bool(count_traversal))
         self._query_tune(p, tune, "query_points")
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != (3 if want_points else 2)):
-            raise ValueError("out must be (dist, tri, point), or the pair (dist, tri) with want_points=False")
-        dist, tri, pt = (tuple(out) + (None,))[:3] if out is not None else (None, None, None)
-        dist = self._query_out(dist, "out dist", n, torch.float32, points.device)
-        tri = self._query_out(tri, "out tri", n, torch.int32, points.device)
-        if want_points:
-            pt = self._query_out(pt, "out point", n, torch.float32, points.device, cols=3)
+        dist, tri, pt = self._point_out(out, "dist", n, points.device, want_points)
         self._query_call(sync, self._lib.rt_query_points_device, points, rmax, n, C.byref(p), dist, tri, pt)
         return dist, tri, pt
 
     def point_query_stats(self):
         """rt_point_query_stats of the last closest-point query as a dict (waits for it): points, invalid_points, nodes_visited,
         tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
-        s = PointQueryStats()
-        self._check(self._lib.rt_get_point_query_stats(self._ctx, C.byref(s)))
-        return s.as_dict()
+        return self._query_stats(PointQueryStats(), "rt_get_point_query_stats")
 
     def query_sides(self, points, out=None, sync=True, want_crossings=False, count_traversal=False, **tune):
         """On which side of the current mesh's surface does each point lie?  (rt_query_sides_device)  points: a float32
@@ -594,48 +619,74 @@ class Renderer:
         point) as query_points returns (dist, tri, point), with sdist negative where the point is inside.  With rmax a narrow-band
         signed distance: points beyond the band stay +inf / POINT_MISS and cost no ray walk.  out: (sdist, tri, point), or (sdist, tri)
         with want_points=False.  tune applies to both steps; point_query_stats() and side_query_stats() report them."""
-        import torch
-
-        n = self._device_rows(points, "points", 3)
-        if rmax is not None and (self._device_rows(rmax, "rmax", 1) != n or rmax.dim() != 1):
-            raise ValueError(f"rmax must have shape ({n},), got {tuple(rmax.shape)}")
+        n = self._point_rows(points, rmax)
         pp, sp = PointQueryParams(), SideQueryParams()
         self._query_tune(pp, tune, "query_signed_distance")
         self._query_tune(sp, tune, "query_signed_distance")
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != (3 if want_points else 2)):
-            raise ValueError("out must be (sdist, tri, point), or the pair (sdist, tri) with want_points=False")
-        dist, tri, pt = (tuple(out) + (None,))[:3] if out is not None else (None, None, None)
-        dist = self._query_out(dist, "out sdist", n, torch.float32, points.device)
-        tri = self._query_out(tri, "out tri", n, torch.int32, points.device)
-        if want_points:
-            pt = self._query_out(pt, "out point", n, torch.float32, points.device, cols=3)
+        dist, tri, pt = self._point_out(out, "sdist", n, points.device, want_points)
         self._query_call(sync, self._lib.rt_query_signed_distance_device, points, rmax, n, C.byref(pp), C.byref(sp), dist, tri, pt, None)
         return dist, tri, pt
 
     def side_query_stats(self):
         """rt_side_query_stats of the last inside/outside query as a dict (waits for it): points, invalid_points, skipped_points, walks,
         third_walks, nodes_visited, tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
-        s = SideQueryStats()
-        self._check(self._lib.rt_get_side_query_stats(self._ctx, C.byref(s)))
-        return s.as_dict()
+        return self._query_stats(SideQueryStats(), "rt_get_side_query_stats")
 
-    def _hit_rays(self, origins, dirs, tmax):
-        """The ray count of an all-hits query once its three inputs are what the library can read."""
-        n = self._device_rows(origins, "origins", 3)
-        if self._device_rows(dirs, "dirs", 3) != n:
-            raise ValueError("origins and dirs disagree on the ray count")
-        if tmax is not None and (self._device_rows(tmax, "tmax", 1) != n or tmax.dim() != 1):
-            raise ValueError(f"tmax must have shape ({n},), got {tuple(tmax.shape)}")
-        return n
+    # A listing kind: the stem of the library's rt_{count,fill,list}_<stem>_device and of count_<stem> / list_<stem> here, its
+    # parameter struct, the key's name, what it lists
+    _RAY_HITS = ("ray_hits", HitQueryParams, "t", "hits")
+    _NEIGHBORS = ("neighbors", NeighborQueryParams, "dist", "neighbours")
 
-    def _device_i64(self, t, name, n):
-        """`t` must be a contiguous int64 torch tensor of n elements on this renderer's device; ValueError otherwise."""
+    def _count_listing(self, kind, src, n, dev, out, sync, count_traversal, tune):
+        """count_ray_hits / count_neighbors on the checked source arguments `src` of n items."""
         import torch
 
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
-        if t.dtype != torch.int64 or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device or t.dim() != 1 or t.numel() != n:
-            raise ValueError(f"{name} must be a contiguous int64 tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        stem, params = kind[:2]
+        p = params()
+        p.count_traversal = int(bool(count_traversal))
+        self._query_tune(p, tune, f"count_{stem}")
+        counts = self._query_out(out, "out counts", n, torch.int32, dev)
+        self._query_call(sync, getattr(self._lib, f"rt_count_{stem}_device"), *src, n, C.byref(p), counts, None)
+        return counts
+
+    def _list_listing(self, kind, src, n, dev, capacity, out, sync, tune):
+        """list_ray_hits / list_neighbors on the checked source arguments `src` of n items: (offsets, key, tri, counts)."""
+        import torch
+
+        stem, params, key, what = kind
+        p = params()
+        self._query_tune(p, tune, f"list_{stem}")
+        if capacity is None:
+            if out is not None:
+                raise ValueError(f"out needs a capacity: without one {key} and tri are allocated to the number of {what}")
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            if n == 0:
+                offsets.zero_()
+                return offsets, torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), counts
+            self._query_call(sync, getattr(self._lib, f"rt_count_{stem}_device"), *src, n, C.byref(p), counts, offsets)
+            self.synchronize()  # the one host synchronisation: the total decides the allocation
+            total = int(offsets[n].item())
+            keys = torch.empty(total, dtype=torch.float32, device=dev)
+            tri = torch.empty(total, dtype=torch.int32, device=dev)
+            self._query_call(sync, getattr(self._lib, f"rt_fill_{stem}_device"), *src, n, C.byref(p), offsets, total, keys if total else None, tri if total else None)
+            return offsets, keys, tri, counts
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError(f"capacity must be >= 0, got {capacity}")
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 4):
+            raise ValueError(f"out must be (offsets, {key}, tri, counts)")
+        offsets, keys, tri, counts = out if out is not None else (None, None, None, None)
+        offsets = self._query_out(offsets, "out offsets", n + 1, torch.int64, dev)
+        keys = self._query_out(keys, f"out {key}", capacity, torch.float32, dev)
+        tri = self._query_out(tri, "out tri", capacity, torch.int32, dev)
+        counts = self._query_out(counts, "out counts", n, torch.int32, dev)
+        if n == 0:
+            offsets.zero_()
+            return offsets, keys, tri, counts
+        self._query_call(sync, getattr(self._lib, f"rt_list_{stem}_device"), *src, n, C.byref(p), counts, offsets, capacity, keys if capacity else None,
+                         tri if capacity else None)
+        return offsets, keys, tri, counts
 
     def count_ray_hits(self, origins, dirs, tmax=None, out=None, sync=True, count_traversal=False, **tune):
         """How many triangles of the current mesh does each ray pass through?  (rt_count_ray_hits_device)  origins, dirs,
@@ -643,15 +694,8 @@ class Renderer:
         counts; invalid rays (query_rays' rule) get RAY_INVALID = -2.  out: the tensor to fill instead of a new one.  sync as for
         query_rays.  count_traversal=True: hit_query_stats() reports nodes_visited / tris_tested.  tune: tune_refill_min,
         tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_hit_query_params."""
-        import torch
-
-        n = self._hit_rays(origins, dirs, tmax)
-        p = HitQueryParams()
-        p.count_traversal = int(bool(count_traversal))
-        self._query_tune(p, tune, "count_ray_hits")
-        counts = self._query_out(out, "out counts", n, torch.int32, origins.device)
-        self._query_call(sync, self._lib.rt_count_ray_hits_device, origins, dirs, tmax, n, C.byref(p), counts, None)
-        return counts
+        n = self._ray_rows(origins, dirs, tmax)
+        return self._count_listing(self._RAY_HITS, (origins, dirs, tmax), n, origins.device, out, sync, count_traversal, tune)
 
     def list_ray_hits(self, origins, dirs, tmax=None, capacity=None, out=None, sync=True, **tune):
         """Every triangle of the current mesh that each ray passes through.  (rt_list_ray_hits_device)  origins, dirs,
@@ -664,63 +708,21 @@ class Renderer:
         tri allocated to exactly that, then the fill step (rt_count_ray_hits_device + rt_fill_ray_hits_device: two walks).
         out: (offsets, t, tri, counts) to fill instead of new tensors, with a capacity only (t and tri of that many elements).
         tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_hit_query_params; hit_query_stats() reports."""
-        import torch
-
-        n = self._hit_rays(origins, dirs, tmax)
-        p = HitQueryParams()
-        self._query_tune(p, tune, "list_ray_hits")
-        dev = origins.device
-        if capacity is None:
-            if out is not None:
-                raise ValueError("out needs a capacity: without one t and tri are allocated to the number of hits")
-            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-            counts = torch.empty(n, dtype=torch.int32, device=dev)
-            if n == 0:
-                offsets.zero_()
-                return offsets, torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), counts
-            self._query_call(sync, self._lib.rt_count_ray_hits_device, origins, dirs, tmax, n, C.byref(p), counts, offsets)
-            self.synchronize()  # the one host synchronisation: the total decides the allocation
-            total = int(offsets[n].item())
-            t = torch.empty(total, dtype=torch.float32, device=dev)
-            tri = torch.empty(total, dtype=torch.int32, device=dev)
-            self._query_call(sync, self._lib.rt_fill_ray_hits_device, origins, dirs, tmax, n, C.byref(p), offsets, total, t if total else None, tri if total else None)
-            return offsets, t, tri, counts
-        capacity = int(capacity)
-        if capacity < 0:
-            raise ValueError(f"capacity must be >= 0, got {capacity}")
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 4):
-            raise ValueError("out must be (offsets, t, tri, counts)")
-        offsets, t, tri, counts = out if out is not None else (None, None, None, None)
-        if offsets is None:
-            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        else:
-            self._device_i64(offsets, "out offsets", n + 1)
-        t = self._query_out(t, "out t", capacity, torch.float32, dev)
-        tri = self._query_out(tri, "out tri", capacity, torch.int32, dev)
-        counts = self._query_out(counts, "out counts", n, torch.int32, dev)
-        if n == 0:
-            offsets.zero_()
-            return offsets, t, tri, counts
-        self._query_call(sync, self._lib.rt_list_ray_hits_device, origins, dirs, tmax, n, C.byref(p), counts, offsets, capacity, t if capacity else None,
-                         tri if capacity else None)
-        return offsets, t, tri, counts
+        n = self._ray_rows(origins, dirs, tmax)
+        return self._list_listing(self._RAY_HITS, (origins, dirs, tmax), n, origins.device, capacity, out, sync, tune)
 
     def hit_query_stats(self):
         """rt_hit_query_stats of the last all-hits call as a dict (waits for it): rays, invalid_rays, hits, hits_written, incomplete_rays,
         slice_overflow, nodes_visited, tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
-        s = HitQueryStats()
-        self._check(self._lib.rt_get_hit_query_stats(self._ctx, C.byref(s)))
-        return s.as_dict()
+        return self._query_stats(HitQueryStats(), "rt_get_hit_query_stats")
 
     def _neighbor_points(self, points, rmax):
         """(n, rmax tensor or None, rmax_all) of a neighbour query once its inputs are what the library can read."""
         import torch
 
-        n = self._device_rows(points, "points", 3)
         if isinstance(rmax, torch.Tensor):
-            if self._device_rows(rmax, "rmax", 1) != n or rmax.dim() != 1:
-                raise ValueError(f"rmax must have shape ({n},), got {tuple(rmax.shape)}")
-            return n, rmax, 0.0
+            return self._point_rows(points, rmax), rmax, 0.0
+        n = self._point_rows(points, None)
         if isinstance(rmax, bool) or not isinstance(rmax, (int, float, np.floating, np.integer)):
             raise ValueError(f"rmax must be a float or a float32 tensor of shape ({n},), got {type(rmax).__name__}")
         return n, None, float(rmax)
@@ -732,15 +734,8 @@ class Renderer:
         points (query_points' rule) get POINT_INVALID = -2.  out: the tensor to fill instead of a new one.  sync as for query_points.
         count_traversal=True: neighbor_query_stats() reports nodes_visited / tris_tested.  tune: tune_refill_min, tune_blocks_per_cu,
         tune_lds_stack, tune_max_blocks of rt_neighbor_query_params."""
-        import torch
-
         n, rmax_t, rmax_all = self._neighbor_points(points, rmax)
-        p = NeighborQueryParams()
-        p.count_traversal = int(bool(count_traversal))
-        self._query_tune(p, tune, "count_neighbors")
-        counts = self._query_out(out, "out counts", n, torch.int32, points.device)
-        self._query_call(sync, self._lib.rt_count_neighbors_device, points, rmax_t, rmax_all, n, C.byref(p), counts, None)
-        return counts
+        return self._count_listing(self._NEIGHBORS, (points, rmax_t, rmax_all), n, points.device, out, sync, count_traversal, tune)
 
     def list_neighbors(self, points, rmax, capacity=None, out=None, sync=True, **tune):
         """Every triangle of the current mesh within rmax of each point.  (rt_list_neighbors_device)  points, rmax as for
@@ -755,55 +750,14 @@ class Renderer:
         out: (offsets, dist, tri, counts) to fill instead of new tensors, with a capacity only (dist and tri of that many elements).
         tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_neighbor_query_params; neighbor_query_stats()
         reports."""
-        import torch
-
         n, rmax_t, rmax_all = self._neighbor_points(points, rmax)
-        p = NeighborQueryParams()
-        self._query_tune(p, tune, "list_neighbors")
-        dev = points.device
-        if capacity is None:
-            if out is not None:
-                raise ValueError("out needs a capacity: without one dist and tri are allocated to the number of neighbours")
-            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-            counts = torch.empty(n, dtype=torch.int32, device=dev)
-            if n == 0:
-                offsets.zero_()
-                return offsets, torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), counts
-            self._query_call(sync, self._lib.rt_count_neighbors_device, points, rmax_t, rmax_all, n, C.byref(p), counts, offsets)
-            self.synchronize()  # the one host synchronisation: the total decides the allocation
-            total = int(offsets[n].item())
-            dist = torch.empty(total, dtype=torch.float32, device=dev)
-            tri = torch.empty(total, dtype=torch.int32, device=dev)
-            self._query_call(sync, self._lib.rt_fill_neighbors_device, points, rmax_t, rmax_all, n, C.byref(p), offsets, total, dist if total else None,
-                             tri if total else None)
-            return offsets, dist, tri, counts
-        capacity = int(capacity)
-        if capacity < 0:
-            raise ValueError(f"capacity must be >= 0, got {capacity}")
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 4):
-            raise ValueError("out must be (offsets, dist, tri, counts)")
-        offsets, dist, tri, counts = out if out is not None else (None, None, None, None)
-        if offsets is None:
-            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        else:
-            self._device_i64(offsets, "out offsets", n + 1)
-        dist = self._query_out(dist, "out dist", capacity, torch.float32, dev)
-        tri = self._query_out(tri, "out tri", capacity, torch.int32, dev)
-        counts = self._query_out(counts, "out counts", n, torch.int32, dev)
-        if n == 0:
-            offsets.zero_()
-            return offsets, dist, tri, counts
-        self._query_call(sync, self._lib.rt_list_neighbors_device, points, rmax_t, rmax_all, n, C.byref(p), counts, offsets, capacity, dist if capacity else None,
-                         tri if capacity else None)
-        return offsets, dist, tri, counts
+        return self._list_listing(self._NEIGHBORS, (points, rmax_t, rmax_all), n, points.device, capacity, out, sync, tune)
 
     def neighbor_query_stats(self):
         """rt_neighbor_query_stats of the last neighbour call as a dict (waits for it): points, invalid_points, neighbors,
         neighbors_written, incomplete_points, slice_overflow, nodes_visited, tris_tested (count_traversal=True only), stack_overflow,
         launches, ms."""
-        s = NeighborQueryStats()
-        self._check(self._lib.rt_get_neighbor_query_stats(self._ctx, C.byref(s)))
-        return s.as_dict()
+        return self._query_stats(NeighborQueryStats(), "rt_get_neighbor_query_stats")
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
         """Test hook (query_rays is the product entry): closest hit (t, original triangle index) or occlusion flags for a ray batch;
