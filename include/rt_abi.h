@@ -453,6 +453,25 @@ int rt_query_points_device(rt_ctx* ctx, const void* points_dev, const void* rmax
                            const rt_point_query_params* params /* NULL = defaults */, void* dist_out_dev, void* tri_out_dev,
                            void* point_out_dev /* may be NULL */);
 int rt_get_point_query_stats(rt_ctx* ctx, rt_point_query_stats* stats); /* synchronises the stream; the last query */
+/* Hit attributes: rt_query_rays_device (closest hit) and rt_query_points_device that also say where in the winning
+ * triangle the hit or the nearest point lies and which way that triangle faces.  t_out / tri_out resp. dist_out / tri_out / point_out
+ * come from the same walk under the same validity and limit rules and are bit for bit the plain functions' answers; parameters,
+ * stream order, lifetime rules, meshes and statistics (rt_get_ray_query_stats / rt_get_point_query_stats) are theirs as well.
+ * uv_out_dev (n x 2 f32, may be NULL) = (u, v): the point is v0 + u (v1 - v0) + v (v2 - v0) of the caller's vertices of triangle tri_out,
+ * i.e. the weights of v0, v1, v2 are (1 - u - v, u, v).  For a ray u = U / det, v = V / det of the ray / triangle test that accepted the
+ * triangle (csrc/hit_attr.h): u >= 0, v >= 0 (-0.0 can occur), u + v <= 1 + 2^-22.  For a point they are the parameters of the nearest
+ * point as csrc/point_tri.h finds them (u + v <= 1 + 2^-24), of which point_out is the evaluation.  normal_out_dev (n x 3 f32, may be
+ * NULL) = the unit geometric normal (v1 - v0) x (v2 - v0) / |..| in the caller's winding, never turned towards the ray or the point; three
+ * zeros for a triangle without area (or one whose squared doubled area underflows or overflows in fp32).  On a miss - a hit cut off by
+ * its limit included - and for an invalid ray or point uv is two NaNs and normal three NaNs.  With both arrays NULL the call is the plain
+ * query.  Errors, all before anything is enqueued or written: those of the plain functions, the same checks on the two arrays, and
+ * RT_ERR_INVALID for params->any_hit = 1 (an occlusion has no winner).  Nothing beyond row n - 1 of an output is written. */
+int rt_query_rays_attr_device(rt_ctx* ctx, const void* origins_dev, const void* dirs_dev, const void* tmax_dev /* may be NULL */, uint32_t n,
+                              const rt_ray_query_params* params /* NULL = defaults */, void* t_out_dev, void* tri_out_dev,
+                              void* uv_out_dev /* n x 2 f32, may be NULL */, void* normal_out_dev /* n x 3 f32, may be NULL */);
+int rt_query_points_attr_device(rt_ctx* ctx, const void* points_dev, const void* rmax_dev /* may be NULL */, uint32_t n,
+                                const rt_point_query_params* params /* NULL = defaults */, void* dist_out_dev, void* tri_out_dev,
+                                void* point_out_dev /* may be NULL */, void* uv_out_dev /* may be NULL */, void* normal_out_dev /* may be NULL */);
 /* Inside/outside queries on device arrays: on which side of the current mesh's surface does each of n caller-supplied
  * points lie?  Enqueued on the context's stream behind the work already there; no host synchronisation, and no allocation after the
  * first query of a mesh or size class.  points_dev: n x 3 f32, device memory of the context's device, only read.  For point i and each

@@ -222,6 +222,8 @@ PROTOTYPES = {
     "rt_default_point_query_params": (C.c_int, [C.POINTER(PointQueryParams)]),
     "rt_query_points_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(PointQueryParams), _vp, _vp, _vp]),
     "rt_get_point_query_stats": (C.c_int, [_vp, C.POINTER(PointQueryStats)]),
+    "rt_query_rays_attr_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(RayQueryParams), _vp, _vp, _vp, _vp]),
+    "rt_query_points_attr_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(PointQueryParams), _vp, _vp, _vp, _vp, _vp]),
     "rt_default_side_query_params": (C.c_int, [C.POINTER(SideQueryParams)]),
     "rt_query_sides_device": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(SideQueryParams), _vp, _vp, _vp]),
     "rt_query_signed_distance_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(PointQueryParams), C.POINTER(SideQueryParams), _vp, _vp, _vp, _vp]),

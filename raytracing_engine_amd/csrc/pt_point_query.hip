@@ -2,6 +2,7 @@
 // loop of pt_query_rays (pt_trace.hip) over pt_queue.h's streams around a nearest-first walk of the BVH8: of pt_traverse.h only the
 // stack and ubyte_f32 are used, the arithmetic that decides an answer is point_tri.h's.  Nothing of rays, frames, path state,
 // shading or packets is used here.
+#include "hit_attr.h"
 #include "point_tri.h"
 #include "pt_launch.h"
 #include "pt_queue.h"
@@ -96,8 +97,15 @@ __device__ __forceinline__ void point_node_step(const PtScene& sc, P3 p, uint32_
     cur = child_base + (uint32_t)__builtin_popcount(imask & ~(0xffffffffu << smin));
 }
 
-template <bool COUNT>
-__global__ __launch_bounds__(256, kPointWaves) void pt_query_points(const PtScene sc, const PointQuery q, uint32_t* __restrict__ head,
+// Hit attributes (ATTR, rt_query_points_attr_device): the sink writes the (u, v) it forms for point_out anyway and
+// hit_attr.h's normal of the record it fetched for them.  The sink stands before the source: p, best and point are the retiring
+// point's.  The attribute arrays come in an argument block of their own (PointAttrQuery), so the plain instantiations keep theirs and
+// are the code of a kernel without ATTR (profiles/hit_attributes.txt).
+template <bool ATTR>
+using PointQueryOf = std::conditional_t<ATTR, PointAttrQuery, PointQuery>;
+
+template <bool COUNT, bool ATTR>
+__global__ __launch_bounds__(256, kPointWaves) void pt_query_points(const PtScene sc, const PointQueryOf<ATTR> q, uint32_t* __restrict__ head,
                                                                     unsigned long long* __restrict__ stats, const StackCfg sk, uint32_t refill_min) {
     extern __shared__ unsigned long long lds_stack[];  // sk.lds_cap x 256 entries
     TravStack stk = make_trav_stack(lds_stack, sk);
@@ -123,7 +131,9 @@ __global__ __launch_bounds__(256, kPointWaves) void pt_query_points(const PtScen
                 const bool hit = best.li >= 0 && best.d2 < limit2;
                 q.dist_out[point] = hit ? sqrt_cr(best.d2) : __builtin_inff();
                 q.tri_out[point] = hit ? (int)best.id : RT_POINT_MISS;
-                if (q.point_out) {
+                bool want_record = q.point_out != nullptr;
+                if constexpr (ATTR) want_record = q.point_out || q.uv_out || q.normal_out;
+                if (want_record) {
                     P3 c{nan, nan, nan};
                     if (hit) {  // (u, v) once more from the record: the same function on the same words, the same bits
                         const float4* tp = sc.tris + (size_t)best.li * 3;
@@ -131,11 +141,16 @@ __global__ __launch_bounds__(256, kPointWaves) void pt_query_points(const PtScen
                         const P3 v0{ta.x, ta.y, ta.z}, e1{ta.w, tb.x, tb.y}, e2{tb.z, tb.w, tcw.x};
                         const ClosestTri ct = closest_on_tri(p, v0, e1, e2);
                         c = tri_point(v0, e1, e2, ct.u, ct.v);
+                        if constexpr (ATTR) write_attr(q.uv_out, q.normal_out, point, ct.u, ct.v, unit_normal(e1, e2));
+                    } else if constexpr (ATTR) {
+                        write_no_attr(q.uv_out, q.normal_out, point);
                     }
-                    float* po = q.point_out + (size_t)point * 3u;
-                    po[0] = c.x;
-                    po[1] = c.y;
-                    po[2] = c.z;
+                    if (!ATTR || q.point_out) {  // (without ATTR the record was fetched for nothing else)
+                        float* po = q.point_out + (size_t)point * 3u;
+                        po[0] = c.x;
+                        po[1] = c.y;
+                        po[2] = c.z;
+                    }
                 }
                 has_point = false;
             }
@@ -174,6 +189,9 @@ __global__ __launch_bounds__(256, kPointWaves) void pt_query_points(const PtScen
                         po[1] = nan;
                         po[2] = nan;
                     }
+                    if constexpr (ATTR) {
+                        if (miss) write_no_attr(q.uv_out, q.normal_out, i);
+                    }
                 }
                 exhausted = qc.advance_if_dry(base + want);
             }
@@ -206,7 +224,14 @@ __global__ __launch_bounds__(256, kPointWaves) void pt_query_points(const PtScen
 int launch_pt_query_points(Ctx* c, const PtScene& sc, const PointQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                            const StackCfg& sk, uint32_t refill_min) {
     QueryKernel<PointQuery> kernel = nullptr;
-    with_bool(count, [&](auto cnt) { kernel = pt_query_points<decltype(cnt)::value>; });
+    with_bool(count, [&](auto cnt) { kernel = pt_query_points<decltype(cnt)::value, false>; });
+    return launch_query(c, kernel, sc, q, head, stats, grid, sk, refill_min);
+}
+
+int launch_pt_query_points_attr(Ctx* c, const PtScene& sc, const PointAttrQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                                const StackCfg& sk, uint32_t refill_min) {
+    QueryKernel<PointAttrQuery> kernel = nullptr;
+    with_bool(count, [&](auto cnt) { kernel = pt_query_points<decltype(cnt)::value, true>; });
     return launch_query(c, kernel, sc, q, head, stats, grid, sk, refill_min);
 }
 

@@ -6,6 +6,7 @@
 // Why the hook and the ray queries are here and not beside the point queries: they share instantiations of inline_round with the
 // render kernels, and what the compiler makes of a shared function depends on the callers it sees in the unit (constant arguments
 // are propagated into it before it is inlined).  In a unit of their own two of them compile to other code (profiles/split_path_b.txt).
+#include "hit_attr.h"
 #include "pt_launch.h"
 #include "pt_queue.h"
 
@@ -676,9 +677,18 @@ __global__ __launch_bounds__(256) void pt_trace_rays(const PtScene sc, const flo
 //   - validity is decided when the lane loads the ray: an invalid ray is answered on the spot and the lane stays idle.  A refill may
 //     therefore hand out 64 entries and leave no lane alive, and with few workgroups a stream may have no wave that started on it: a
 //     wave leaves only when it has found the last stream dry AND holds no live ray (the rule of RAYS_BOTH, not of the one-kind loops).
-template <bool ANY>
-__global__ __launch_bounds__(256, kInlineWaves) void pt_query_rays(const PtScene sc, const RayQuery q, uint32_t* __restrict__ head,
+// Hit attributes (ATTR, rt_query_rays_attr_device): the sink of a lane that retires a ray with a winner fetches
+// the 48-byte record at best.li once more and evaluates hit_attr.h on the lane's own r.o, r.d - the values the accepting tri_step used,
+// so u, v, det are its u, v, det bit for bit.  tri_step carries nothing new: it and the rounds are the plain kernels'.
+// The sink stands before the source: r, best, limit and ray are still the retiring ray's.  The attribute arrays come in an argument
+// block of their own (RayAttrQuery), so the plain instantiations keep theirs and are the code of a kernel without ATTR (profiles/hit_attributes.txt).
+template <bool ATTR>
+using RayQueryOf = std::conditional_t<ATTR, RayAttrQuery, RayQuery>;
+
+template <bool ANY, bool ATTR>
+__global__ __launch_bounds__(256, kInlineWaves) void pt_query_rays(const PtScene sc, const RayQueryOf<ATTR> q, uint32_t* __restrict__ head,
                                                                    unsigned long long* __restrict__ stats, const StackCfg sk, uint32_t refill_min) {
+    static_assert(!(ANY && ATTR), "an occlusion query has no winner");
     extern __shared__ unsigned long long lds_stack[];  // sk.lds_cap x 256 entries
     __shared__ uint8_t perm_lut[2048];
     build_perm_lut(perm_lut);
@@ -709,6 +719,17 @@ __global__ __launch_bounds__(256, kInlineWaves) void pt_query_rays(const PtScene
                     const bool hit = best.li >= 0 && best.t < limit;
                     q.t_out[ray] = hit ? best.t : __builtin_inff();
                     q.tri_out[ray] = hit ? (int)best.id : RT_RAY_MISS;
+                    if constexpr (ATTR) {
+                        if (hit) {
+                            const float4* tp = sc.tris + (size_t)best.li * 3;
+                            const float4 ta = tp[0], tb = tp[1], tcw = tp[2];
+                            const P3 e1{ta.w, tb.x, tb.y}, e2{tb.z, tb.w, tcw.x};
+                            const Bary b = ray_bary(P3{r.o.x, r.o.y, r.o.z}, P3{r.d.x, r.d.y, r.d.z}, P3{ta.x, ta.y, ta.z}, e1, e2);
+                            write_attr(q.uv_out, q.normal_out, ray, b.u, b.v, unit_normal(e1, e2));
+                        } else {
+                            write_no_attr(q.uv_out, q.normal_out, ray);  // a miss, or a hit that its limit cuts off
+                        }
+                    }
                 }
                 has_ray = false;
             }
@@ -728,9 +749,11 @@ __global__ __launch_bounds__(256, kInlineWaves) void pt_query_rays(const PtScene
                         if (!ANY) q.t_out[i] = __builtin_nanf("");
                         q.tri_out[i] = RT_RAY_INVALID;
                         invalid++;
+                        if constexpr (ATTR) write_no_attr(q.uv_out, q.normal_out, i);
                     } else if (!(limit > 0.0f)) {  // an empty interval: a miss without a walk
                         if (!ANY) q.t_out[i] = __builtin_inff();
                         q.tri_out[i] = ANY ? 0 : RT_RAY_MISS;
+                        if constexpr (ATTR) write_no_attr(q.uv_out, q.normal_out, i);
                     } else {
                         start_ray(ANY, o, d, r, best, G, T, stk);
                         r.tmax = limit;
@@ -806,7 +829,13 @@ int launch_pt_trace_rays(Ctx* c, const PtScene& sc, const float* origins, const 
 int launch_pt_query_rays(Ctx* c, const PtScene& sc, const RayQuery& q, bool any_hit, uint32_t* head, unsigned long long* stats, uint32_t grid,
                          const StackCfg& sk, uint32_t refill_min) {
     QueryKernel<RayQuery> kernel = nullptr;
-    with_bool(any_hit, [&](auto any) { kernel = pt_query_rays<decltype(any)::value>; });
+    with_bool(any_hit, [&](auto any) { kernel = pt_query_rays<decltype(any)::value, false>; });
+    return launch_query(c, kernel, sc, q, head, stats, grid, sk, refill_min);
+}
+
+int launch_pt_query_rays_attr(Ctx* c, const PtScene& sc, const RayAttrQuery& q, uint32_t* head, unsigned long long* stats, uint32_t grid, const StackCfg& sk,
+                              uint32_t refill_min) {
+    const QueryKernel<RayAttrQuery> kernel = pt_query_rays<false, true>;
     return launch_query(c, kernel, sc, q, head, stats, grid, sk, refill_min);
 }
 

@@ -1,5 +1,5 @@
 // rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14),
-// sides (§6.15), all hits (§6.16) and neighbours (§6.17).
+// sides (§6.15), all hits (§6.16), neighbours (§6.17) and the attribute variants of the first two (§6.18).
 // A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here: the
 // parameter checks and the prologue of an entry (enter_query), the plan and the enqueue (prepare_query, run_query), the read-back.
 // The listing kinds - all hits, neighbours - are a description each (HitKind, NeighborKind); their protocol of a count step, a fill
@@ -105,9 +105,56 @@ int enqueue_query(Ctx* c, QueryState& qs, uint32_t n, const Params& prm, uint32_
     return run_query(c, qs, plan, range, launch);
 }
 
+// ---- rays: rt_query_rays_device and, with attr, rt_query_rays_attr_device ----
+// Everything that can refuse a call comes before the first enqueue (in enqueue_query)
+int query_rays(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_ray_query_params* prm, void* t_out, void* tri_out, bool attr,
+               void* uv_out, void* normal_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_ray_query_params defaults{};
+    int done;
+    if (int rc = enter_query(c, n, prm, defaults, &done, &rt_ray_query_params::any_hit, "any_hit")) return rc;
+    if (done) return RT_OK;
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    const bool any_hit = prm->any_hit != 0u;
+    if (attr && any_hit) return c->fail(RT_ERR_INVALID, "any_hit 1 with an attribute query: an occlusion has no winner");
+    if (int rc = rt::check_device_array(c, origins, (size_t)n * 12, "origins_dev")) return rc;
+    if (int rc = rt::check_device_array(c, dirs, (size_t)n * 12, "dirs_dev")) return rc;
+    if (tmax)
+        if (int rc = rt::check_device_array(c, tmax, (size_t)n * 4, "tmax_dev")) return rc;
+    if (t_out || !any_hit)
+        if (int rc = rt::check_device_array(c, t_out, (size_t)n * 4, "t_out_dev")) return rc;
+    if (int rc = rt::check_device_array(c, tri_out, (size_t)n * 4, "tri_out_dev")) return rc;
+    if (uv_out)
+        if (int rc = rt::check_device_array(c, uv_out, (size_t)n * 8, "uv_out_dev")) return rc;
+    if (normal_out)
+        if (int rc = rt::check_device_array(c, normal_out, (size_t)n * 12, "normal_out_dev")) return rc;
+    rt::RayAttrQuery q{};
+    q.origins = static_cast<const float*>(origins);
+    q.dirs = static_cast<const float*>(dirs);
+    q.tmax = static_cast<const float*>(tmax);
+    q.t_out = any_hit ? nullptr : static_cast<float*>(t_out);
+    q.tri_out = static_cast<int*>(tri_out);
+    q.n = n;
+    q.reach = rt::kCameraReach * mesh.maxabs;
+    q.uv_out = static_cast<float*>(uv_out);
+    q.normal_out = static_cast<float*>(normal_out);
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        const uint32_t refill = refill_min | (prm->tune_refill_min & 0xff00u);  // byte 1: triangle tests per round
+        if (uv_out || normal_out) return rt::launch_pt_query_rays_attr(c, rt::scene_view(mesh), q, head, stats, grid, sk, refill);
+        return rt::launch_pt_query_rays(c, rt::scene_view(mesh), q, any_hit, head, stats, grid, sk, refill);  // without attribute arrays: the plain query
+    };
+    if (int rc = enqueue_query(c, c->pt.ray_query, n, *prm, mesh.stack_need, "rt.path_b.query_rays", launch)) return rc;
+    c->pt.ray_query_stats = rt_ray_query_stats{};
+    c->pt.ray_query_stats.rays = n;
+    c->pt.ray_query_stats.launches = 1;
+    return RT_OK;
+}
+
 // ---- closest points: the array checks and the plan (everything that can refuse), then the enqueue ----
+// (uv_out, normal_out: rt_query_points_attr_device's, NULL from every other entry)
 int prepare_points(Ctx* c, const void* points, const void* rmax, uint32_t n, const rt_point_query_params& prm, void* dist_out, void* tri_out, void* point_out,
-                   rt::PointQuery* q, QueryPlan* plan) {
+                   void* uv_out, void* normal_out, rt::PointAttrQuery* q, QueryPlan* plan) {
     const rt::DeviceMesh& mesh = c->pt.mesh();
     if (int rc = rt::check_device_array(c, points, (size_t)n * 12, "points_dev")) return rc;
     if (rmax)
@@ -116,20 +163,27 @@ int prepare_points(Ctx* c, const void* points, const void* rmax, uint32_t n, con
     if (int rc = rt::check_device_array(c, tri_out, (size_t)n * 4, "tri_out_dev")) return rc;
     if (point_out)
         if (int rc = rt::check_device_array(c, point_out, (size_t)n * 12, "point_out_dev")) return rc;
-    *q = rt::PointQuery{};
+    if (uv_out)
+        if (int rc = rt::check_device_array(c, uv_out, (size_t)n * 8, "uv_out_dev")) return rc;
+    if (normal_out)
+        if (int rc = rt::check_device_array(c, normal_out, (size_t)n * 12, "normal_out_dev")) return rc;
+    *q = rt::PointAttrQuery{};
     q->points = static_cast<const float*>(points);
     q->rmax = static_cast<const float*>(rmax);
     q->dist_out = static_cast<float*>(dist_out);
     q->tri_out = static_cast<int*>(tri_out);
     q->point_out = static_cast<float*>(point_out);
+    q->uv_out = static_cast<float*>(uv_out);
+    q->normal_out = static_cast<float*>(normal_out);
     q->n = n;
     q->reach = rt::kCameraReach * mesh.maxabs;
     // point_stack_need entries per lane: one pending sibling each, not stack_need's one group per level; the spill columns grow to it once per mesh
     return prepare_query(c, c->pt.point_query, n, prm, rt::point_stack_need(mesh.depth), plan);
 }
 
-int run_points(Ctx* c, const rt::PointQuery& q, const rt_point_query_params& prm, const QueryPlan& plan) {
+int run_points(Ctx* c, const rt::PointAttrQuery& q, const rt_point_query_params& prm, const QueryPlan& plan) {
     const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        if (q.uv_out || q.normal_out) return rt::launch_pt_query_points_attr(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, head, stats, grid, sk, refill_min);
         return rt::launch_pt_query_points(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
     };
     if (int rc = run_query(c, c->pt.point_query, plan, "rt.path_b.query_points", launch)) return rc;
@@ -405,39 +459,13 @@ extern "C" {
 
 int rt_default_ray_query_params(rt_ray_query_params* p) { return default_params(p); }
 
-// Everything that can refuse a call comes before the first enqueue (in enqueue_query)
 int rt_query_rays_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_ray_query_params* prm, void* t_out, void* tri_out) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c) return RT_ERR_INVALID;
-    const rt_ray_query_params defaults{};
-    int done;
-    if (int rc = enter_query(c, n, prm, defaults, &done, &rt_ray_query_params::any_hit, "any_hit")) return rc;
-    if (done) return RT_OK;
-    const rt::DeviceMesh& mesh = c->pt.mesh();
-    const bool any_hit = prm->any_hit != 0u;
-    if (int rc = rt::check_device_array(c, origins, (size_t)n * 12, "origins_dev")) return rc;
-    if (int rc = rt::check_device_array(c, dirs, (size_t)n * 12, "dirs_dev")) return rc;
-    if (tmax)
-        if (int rc = rt::check_device_array(c, tmax, (size_t)n * 4, "tmax_dev")) return rc;
-    if (t_out || !any_hit)
-        if (int rc = rt::check_device_array(c, t_out, (size_t)n * 4, "t_out_dev")) return rc;
-    if (int rc = rt::check_device_array(c, tri_out, (size_t)n * 4, "tri_out_dev")) return rc;
-    rt::RayQuery q{};
-    q.origins = static_cast<const float*>(origins);
-    q.dirs = static_cast<const float*>(dirs);
-    q.tmax = static_cast<const float*>(tmax);
-    q.t_out = any_hit ? nullptr : static_cast<float*>(t_out);
-    q.tri_out = static_cast<int*>(tri_out);
-    q.n = n;
-    q.reach = rt::kCameraReach * mesh.maxabs;
-    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
-        return rt::launch_pt_query_rays(c, rt::scene_view(mesh), q, any_hit, head, stats, grid, sk, refill_min | (prm->tune_refill_min & 0xff00u));  // byte 1: triangle tests per round
-    };
-    if (int rc = enqueue_query(c, c->pt.ray_query, n, *prm, mesh.stack_need, "rt.path_b.query_rays", launch)) return rc;
-    c->pt.ray_query_stats = rt_ray_query_stats{};
-    c->pt.ray_query_stats.rays = n;
-    c->pt.ray_query_stats.launches = 1;
-    return RT_OK;
+    return query_rays(ctx, origins, dirs, tmax, n, prm, t_out, tri_out, false, nullptr, nullptr);
+}
+
+int rt_query_rays_attr_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* tmax, uint32_t n, const rt_ray_query_params* prm, void* t_out, void* tri_out,
+                              void* uv_out, void* normal_out) {
+    return query_rays(ctx, origins, dirs, tmax, n, prm, t_out, tri_out, true, uv_out, normal_out);
 }
 
 int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats) {
@@ -457,15 +485,20 @@ int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats) {
 int rt_default_point_query_params(rt_point_query_params* p) { return default_params(p); }
 
 int rt_query_points_device(rt_ctx* ctx, const void* points, const void* rmax, uint32_t n, const rt_point_query_params* prm, void* dist_out, void* tri_out, void* point_out) {
+    return rt_query_points_attr_device(ctx, points, rmax, n, prm, dist_out, tri_out, point_out, nullptr, nullptr);
+}
+
+int rt_query_points_attr_device(rt_ctx* ctx, const void* points, const void* rmax, uint32_t n, const rt_point_query_params* prm, void* dist_out, void* tri_out,
+                                void* point_out, void* uv_out, void* normal_out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
     const rt_point_query_params defaults{};
     int done;
     if (int rc = enter_query(c, n, prm, defaults, &done)) return rc;
     if (done) return RT_OK;
-    rt::PointQuery q{};
+    rt::PointAttrQuery q{};
     QueryPlan plan{};
-    if (int rc = prepare_points(c, points, rmax, n, *prm, dist_out, tri_out, point_out, &q, &plan)) return rc;
+    if (int rc = prepare_points(c, points, rmax, n, *prm, dist_out, tri_out, point_out, uv_out, normal_out, &q, &plan)) return rc;
     return run_points(c, q, *prm, plan);
 }
 
@@ -512,10 +545,10 @@ int rt_query_signed_distance_device(rt_ctx* ctx, const void* points, const void*
     if (int rc = use_params(c, n, sprm, sdefaults)) return rc;
     if (int rc = begin_query(c, n, &done)) return rc;
     if (done) return RT_OK;
-    rt::PointQuery pq{};
+    rt::PointAttrQuery pq{};
     rt::SideQuery sq{};
     QueryPlan pplan{}, splan{};
-    if (int rc = prepare_points(c, points, rmax, n, *pprm, sdist_out, tri_out, point_out, &pq, &pplan)) return rc;
+    if (int rc = prepare_points(c, points, rmax, n, *pprm, sdist_out, tri_out, point_out, nullptr, nullptr, &pq, &pplan)) return rc;
     if (int rc = prepare_sides(c, points, n, *sprm, inside_out, false, nullptr, sdist_out, &sq, &splan)) return rc;
     if (int rc = run_points(c, pq, *pprm, pplan)) return rc;
     return run_sides(c, sq, *sprm, splan);

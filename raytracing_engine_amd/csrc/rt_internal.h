@@ -203,6 +203,12 @@ struct RayQuery {
     uint32_t n;
     float reach;  // |origin component| limit: kCameraReach x the mesh's maxabs
 };
+// rt_query_rays_attr_device: the same rays and answers, and where the winner's attributes go.  A struct of its own:
+// the plain kernels keep their argument block.
+struct RayAttrQuery : RayQuery {
+    float* uv_out;      // n x 2, or nullptr
+    float* normal_out;  // n x 3, or nullptr
+};
 // Counters of a ray query (QueryState's device block)
 enum { RQ_STAT_INVALID = 0, RQ_STAT_OVERFLOW = 1, RQ_STAT_WORDS = 2 };
 
@@ -215,6 +221,11 @@ struct PointQuery {
     float* point_out;     // n x 3, or nullptr
     uint32_t n;
     float reach;  // |component| limit: kCameraReach x the mesh's maxabs
+};
+// rt_query_points_attr_device
+struct PointAttrQuery : PointQuery {
+    float* uv_out;      // n x 2, or nullptr
+    float* normal_out;  // n x 3, or nullptr
 };
 // Counters of a closest-point query
 enum { PQ_STAT_INVALID = 0, PQ_STAT_OVERFLOW = 1, PQ_STAT_NODES = 2, PQ_STAT_TRIS = 3, PQ_STAT_WORDS = 4 };
@@ -479,6 +490,11 @@ int launch_pt_query_rays(Ctx* c, const PtScene& sc, const RayQuery& q, bool any_
                          const StackCfg& sk, uint32_t refill_min);
 int launch_pt_query_points(Ctx* c, const PtScene& sc, const PointQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                            const StackCfg& sk, uint32_t refill_min);
+// the ATTR instantiations (closest hit only; q.uv_out / q.normal_out, either may be nullptr)
+int launch_pt_query_rays_attr(Ctx* c, const PtScene& sc, const RayAttrQuery& q, uint32_t* head, unsigned long long* stats, uint32_t grid, const StackCfg& sk,
+                              uint32_t refill_min);
+int launch_pt_query_points_attr(Ctx* c, const PtScene& sc, const PointAttrQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                                const StackCfg& sk, uint32_t refill_min);
 int launch_pt_query_sides(Ctx* c, const PtScene& sc, const SideQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                           const StackCfg& sk, uint32_t refill_min);  // q.crossings_out != nullptr: all three walks for every point
 // fill = false: the count step (q.count_out / q.count64), true: the fill step (q.offsets, q.capacity, q.key_out, q.tri_out); stats: the step's own LQ_STEP_WORDS

@@ -522,7 +522,7 @@ class Renderer:
             pt = self._query_out(pt, "out point", n, torch.float32, dev, cols=3)
         return dist, tri, pt
 
-    def query_rays(self, origins, dirs, tmax=None, any_hit=False, out=None, sync=True, **tune):
+    def query_rays(self, origins, dirs, tmax=None, any_hit=False, out=None, sync=True, attributes=False, **tune):
         """What do rays hit in the current mesh?  (rt_query_rays_device)  origins, dirs: float32 torch tensors on this
         renderer's device, contiguous, (n, 3) or flat; tmax: (n,) or None.  A triangle is hit when 0 < t < tmax (default: +inf for the
         closest hit, 0.999 for any hit).  any_hit=False: returns (t, tri) - float32 distances in units of |dir| (+inf on a miss) and int32
@@ -530,22 +530,34 @@ class Renderer:
         component, an origin beyond 32 x the mesh's largest |coordinate|) get RAY_INVALID = -2 and t = NaN.  out: the tensors to fill -
         (t, tri) resp. the flag tensor - instead of new ones.  sync=True: work torch has queued on its current stream is finished first
         and the answers are complete on return; sync=False does neither: for callers that handed torch's stream to set_stream().
+        attributes=True (rt_query_rays_attr_device, §6.18; closest hit only): returns (t, tri, uv, normal) - the same t and tri, the (n, 2)
+        barycentrics (u, v) of the hit in its triangle (vertex weights (1 - u - v, u, v): interpolate()) and the (n, 3) unit geometric
+        normal in the caller's winding; NaNs where tri < 0.  out must then be the 4-tuple.
         tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_ray_query_params."""
         import torch
 
+        if attributes and any_hit:
+            raise ValueError("attributes=True needs a closest-hit query: an occlusion has no winning triangle")
         n = self._ray_rows(origins, dirs, tmax)
         p = RayQueryParams()
         p.any_hit = int(bool(any_hit))
         self._query_tune(p, tune, "query_rays")
+        uv = normal = None
         if any_hit:
             t, tri = None, out
         else:
-            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-                raise ValueError("out must be the pair (t, tri) for a closest-hit query")
-            t, tri = out if out is not None else (None, None)
+            k = 4 if attributes else 2
+            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != k):
+                raise ValueError("out must be (t, tri, uv, normal) with attributes=True" if attributes else "out must be the pair (t, tri) for a closest-hit query")
+            t, tri, uv, normal = (tuple(out) + (None, None))[:4] if out is not None else (None,) * 4
         tri = self._query_out(tri, "out tri", n, torch.int32, origins.device)
         if not any_hit:
             t = self._query_out(t, "out t", n, torch.float32, origins.device)
+        if attributes:
+            uv = self._query_out(uv, "out uv", n, torch.float32, origins.device, cols=2)
+            normal = self._query_out(normal, "out normal", n, torch.float32, origins.device, cols=3)
+            self._query_call(sync, self._lib.rt_query_rays_attr_device, origins, dirs, tmax, n, C.byref(p), t, tri, uv, normal)
+            return t, tri, uv, normal
         self._query_call(sync, self._lib.rt_query_rays_device, origins, dirs, tmax, n, C.byref(p), t, tri)
         return tri if any_hit else (t, tri)
 
@@ -555,7 +567,7 @@ class Renderer:
 
     POINT_MISS, POINT_INVALID = _lib.POINT_MISS, _lib.POINT_INVALID
 
-    def query_points(self, points, rmax=None, out=None, sync=True, want_points=True, count_traversal=False, **tune):
+    def query_points(self, points, rmax=None, out=None, sync=True, want_points=True, count_traversal=False, attributes=False, **tune):
         """Which triangle of the current mesh is nearest to each point, how far is it, and where on it?  (rt_query_points_device,
         DESIGN.md §6.14.)  points: a float32 torch tensor on this renderer's device, contiguous, (n, 3) or flat; rmax: (n,) or None - only
         triangles nearer than rmax count (strictly; default +inf).  Returns (dist, tri, point): float32 distances (+inf on a miss), int32
@@ -564,15 +576,47 @@ class Renderer:
         get POINT_INVALID = -2 and NaNs.  out: the tensors to fill - (dist, tri, point), or (dist, tri) with want_points=False - instead of
         new ones.  sync=True: work torch has queued on its current stream is finished first and the answers are complete on return;
         sync=False does neither: for callers that handed torch's stream to set_stream().  count_traversal=True: point_query_stats()
-        reports nodes_visited / tris_tested.  tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of
+        reports nodes_visited / tris_tested.  attributes=True (rt_query_points_attr_device, §6.18): returns (dist, tri, point, uv, normal) -
+        the same three, the (n, 2) barycentrics (u, v) of the nearest point in its triangle (vertex weights (1 - u - v, u, v):
+        interpolate()) and the (n, 3) unit geometric normal in the caller's winding (zeros for a triangle without area); NaNs where
+        tri < 0.  out then ends with (uv, normal).  tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of
         rt_point_query_params."""
+        import torch
+
         n = self._point_rows(points, rmax)
         p = PointQueryParams()
         p.count_traversal = int(bool(count_traversal))
         self._query_tune(p, tune, "query_points")
-        dist, tri, pt = self._point_out(out, "dist", n, points.device, want_points)
-        self._query_call(sync, self._lib.rt_query_points_device, points, rmax, n, C.byref(p), dist, tri, pt)
-        return dist, tri, pt
+        if not attributes:
+            dist, tri, pt = self._point_out(out, "dist", n, points.device, want_points)
+            self._query_call(sync, self._lib.rt_query_points_device, points, rmax, n, C.byref(p), dist, tri, pt)
+            return dist, tri, pt
+        k = 3 if want_points else 2
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != k + 2):
+            raise ValueError("out must be (dist, tri, point, uv, normal) with attributes=True, or (dist, tri, uv, normal) with want_points=False")
+        dist, tri, pt = self._point_out(None if out is None else tuple(out)[:k], "dist", n, points.device, want_points)
+        uv, normal = tuple(out)[k:] if out is not None else (None, None)
+        uv = self._query_out(uv, "out uv", n, torch.float32, points.device, cols=2)
+        normal = self._query_out(normal, "out normal", n, torch.float32, points.device, cols=3)
+        self._query_call(sync, self._lib.rt_query_points_attr_device, points, rmax, n, C.byref(p), dist, tri, pt, uv, normal)
+        return dist, tri, pt, uv, normal
+
+    @staticmethod
+    def interpolate(tri, uv, vertex_attr):
+        """Per-vertex data at the hits of query_rays / query_points(attributes=True).  tri: (n,) integer triangle indices, uv: (n, 2),
+        vertex_attr: (n_tris, 3, C) in the caller's original triangle order.  Returns (n, C): (1 - u - v) a0 + u a1 + v a2 of triangle
+        tri's three rows; NaN where tri < 0.  Plain torch on whatever device the tensors are on (CPU tensors included)."""
+        import torch
+
+        if vertex_attr.dim() != 3 or vertex_attr.shape[1] != 3:
+            raise ValueError(f"vertex_attr must have shape (n_tris, 3, C), got {tuple(vertex_attr.shape)}")
+        if uv.dim() != 2 or uv.shape[1] != 2 or tri.dim() != 1 or tri.shape[0] != uv.shape[0]:
+            raise ValueError(f"tri must have shape (n,) and uv (n, 2), got {tuple(tri.shape)} and {tuple(uv.shape)}")
+        hit = tri >= 0
+        a = vertex_attr[torch.where(hit, tri, torch.zeros_like(tri)).long()]  # (n, 3, C)
+        u, v = uv[:, 0:1].to(a.dtype), uv[:, 1:2].to(a.dtype)
+        val = (1 - u - v) * a[:, 0] + u * a[:, 1] + v * a[:, 2]
+        return torch.where(hit[:, None], val, torch.full_like(val, float("nan")))
 
     def point_query_stats(self):
         """rt_point_query_stats of the last closest-point query as a dict (waits for it): points, invalid_points, nodes_visited,

@@ -6,6 +6,9 @@ tree's Makefile lists (SRCS) is compiled to gfx950 assembly with that tree's own
 functions are compared by mangled name, wherever in a tree they are defined: the text between a function's label and its .Lfunc_end
 line with two normalisations - ';' comments removed, and the function's number dropped from its local labels (.LBB<f>_<n>), which
 counts the functions of a unit - and a kernel's .amdhsa_kernel block as it is.  Nothing else in the assembly is looked at.
+A function that is on one side only is then looked for on the other side under another name - a kernel whose template gained a
+parameter keeps its code but not its mangled name: same body, same kernel block once the function's own name is taken out of both.
+Such pairs are listed as "identical under another name"; they do not count as differences, what stays unpaired does.
 Exit status 0: every function is on both sides exactly once, with the same body and the same kernel block."""
 import re
 import sys
@@ -38,6 +41,12 @@ def tree_functions(tree, workdir):
     return found, twice
 
 
+def nameless(name, entry):
+    """A function's body and kernel block with its own name taken out."""
+    _, body, block = entry
+    return tuple(l.replace(name, "@") for l in body), tuple(l.replace(name, "@") for l in block)
+
+
 def first_difference(a, b):
     for i, (x, y) in enumerate(zip(a, b)):
         if x != y:
@@ -58,13 +67,28 @@ def main(tree_a, tree_b):
             differ.append("%s (%s): .amdhsa_kernel block, %s" % (name, where, first_difference(block_a, block_b)))
         else:
             same.append((name, where))
+    n_a, n_b = len(fa), len(fb)
+    # renamed: a function of A that B lacks and a function of B that A lacks, with the same code (each used once)
+    left = {}
+    for n in sorted(set(fb) - set(fa)):
+        left.setdefault(nameless(n, fb[n]), []).append(n)
+    renamed = []
+    for n in sorted(set(fa) - set(fb)):
+        twins = left.get(nameless(n, fa[n]))
+        if twins:
+            renamed.append((n, twins.pop(0)))
+    for na, nb in renamed:
+        del fa[na], fb[nb]
     only = ["%s: only in %s (%s)" % (n, t, f[n][0]) for t, f, g in ((tree_a, fa, fb), (tree_b, fb, fa)) for n in sorted(set(f) - set(g))]
     twice = ["%s: in %s and %s of %s" % (n, u1, u2, t) for t, tw in ((tree_a, twice_a), (tree_b, twice_b)) for n, u1, u2 in tw]
 
-    print("A = %s: %d functions;  B = %s: %d functions" % (tree_a, len(fa), tree_b, len(fb)))
+    print("A = %s: %d functions;  B = %s: %d functions" % (tree_a, n_a, tree_b, n_b))
     print("identical (body and kernel block): %d" % len(same))
     for where in sorted(set(w for _, w in same)):
         print("    %-40s %d" % (where, sum(1 for _, w in same if w == where)))
+    print("identical under another name: %d" % len(renamed))
+    for na, nb in renamed:
+        print("    %s\n        -> %s" % (na, nb))
     for title, rows in (("differ", differ), ("on one side only", only), ("defined in more than one unit", twice)):
         print("%s: %d" % (title, len(rows)))
         for row in rows:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate of the closest-point queries on device arrays (rt_query_points_device) on 1 M-triangle scenes.
 
-    python tools/point_query.py [--points 8388608] [--repeats 20] [--warmup 3] [--out profiles/point_queries.txt]
+    python tools/point_query.py [--points 8388608] [--repeats 20] [--warmup 3] [--attributes] [--out profiles/point_queries.txt]
 
 Scenes: the 1 M-triangle soup and the 1 M-triangle terrain (raytracing_engine_amd/scenes.py).  Point distributions per scene, made
 on the device from fixed seeds: UNIFORM in the mesh's bounding box; NEAR, within 1e-3 M of the surface (a uniform point of a uniformly
@@ -10,7 +10,9 @@ origin of the coordinates (log-uniform), where the first boxes of the walk all l
 
 Time = rt_point_query_stats.ms (HIP events around the launch of pt_query_points), median of --repeats after --warmup, with
 tune_refill_min swept over 8, 24 and 48 (24 is the default).  Nodes and triangles per query come from one more run with
-count_traversal = 1, outside the timed ones.  There is no bar and no parent to compare with: the capability is new."""
+count_traversal = 1, outside the timed ones.  There is no bar and no parent to compare with: the capability is new.
+--attributes: every batch once more through rt_query_points_attr_device (barycentrics and normals) at
+refill_min 24, in the same process under the same protocol; its tri must be the plain query's."""
 import argparse
 import os
 import statistics
@@ -56,6 +58,7 @@ def main():
     ap.add_argument("--points", type=int, default=1 << 23)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--attributes", action="store_true", help="every batch with barycentrics and normals too")
     ap.add_argument("--out", default="")
     ap.add_argument("--commit", default="", help="what to name as the commit (default: git rev-parse of this checkout)")
     a = ap.parse_args()
@@ -70,10 +73,12 @@ def main():
             commit += " + uncommitted changes"
     except (OSError, subprocess.CalledProcessError):
         commit = a.commit or "unknown (not a git checkout)"
-    lines = [f"# tools/point_query.py --points {a.points} --repeats {a.repeats} --warmup {a.warmup}   ({torch.cuda.get_device_name(0)})",
+    lines = [f"# tools/point_query.py --points {a.points} --repeats {a.repeats} --warmup {a.warmup}{' --attributes' if a.attributes else ''}   ({torch.cuda.get_device_name(0)})",
              f"# commit {commit}",
              "# ms = rt_point_query_stats.ms (HIP events around the launch of pt_query_points), median of the repeats; Mpoints/s = points / that",
              "# nodes, tris = node records fetched and triangles tested per query (one run with count_traversal = 1, not timed)"]
+    if a.attributes:
+        lines.append("# '24 + attr' = the same batch through rt_query_points_attr_device (barycentrics and normals, DESIGN.md section 6.18), refill_min 24")
     r = R.Renderer(0)
     dev = torch.device("cuda", 0)
     for name, make in scene_list():
@@ -86,10 +91,10 @@ def main():
             r.query_points(p, want_points=False, count_traversal=True)
             c = r.point_query_stats()
             ref = None
-            for refill in (8, 24, 48):
+            for refill, attr in [(v, False) for v in (8, 24, 48)] + ([(24, True)] if a.attributes else []):
                 ms = []
                 for k in range(a.warmup + a.repeats):
-                    dist, tri, _ = r.query_points(p, want_points=False, tune_refill_min=refill)
+                    dist, tri = r.query_points(p, want_points=False, tune_refill_min=refill, attributes=attr)[:2]
                     st = r.point_query_stats()
                     if k >= a.warmup:
                         ms.append(st["ms"])
@@ -100,7 +105,7 @@ def main():
                 elif not torch.equal(ref, tri):
                     raise SystemExit(f"{name} {label} refill_min {refill}: answers differ from the first setting's")
                 med = statistics.median(ms)
-                lines.append(f"{label:8} {refill:10d} {med:9.3f} {min(ms):9.3f} {max(ms):9.3f} {a.points / med * 1e-3:10.1f} "
+                lines.append(f"{label:8} {str(refill) + (' + attr' if attr else ''):>10} {med:9.3f} {min(ms):9.3f} {max(ms):9.3f} {a.points / med * 1e-3:10.1f} "
                              f"{c['nodes_visited'] / a.points:8.2f} {c['tris_tested'] / a.points:8.2f}")
                 print(lines[-1], flush=True)
     text = "\n".join(lines) + "\n"

@@ -2,7 +2,7 @@
 """Rate of the ray queries on device arrays (rt_query_rays_device) on 1 M-triangle scenes, against the kernel of the rt_trace_rays
 test hook on the same rays.
 
-    python tools/ray_query.py [--rays 8388608] [--repeats 20] [--warmup 3] [--sweep] [--baseline DIR] [--out profiles/ray_queries.txt]
+    python tools/ray_query.py [--rays 8388608] [--repeats 20] [--warmup 3] [--sweep] [--attributes] [--baseline DIR] [--out profiles/ray_queries.txt]
     python tools/ray_query.py --hook [--rays N]      # the hook on the same batches, nothing else: the run to put under
                                                      # rocprofv3 --kernel-trace --stats --output-format csv -d DIR
 
@@ -15,7 +15,8 @@ The query's time is rt_ray_query_stats.ms (HIP events around its launch), median
 includes four allocations and four synchronous copies and is not the comparison: its KERNEL time comes from a rocprofv3 kernel trace
 of the --hook run, a separate process, handed over with --baseline DIR (dispatches of pt_trace_rays in order; the --hook run
 prints the order).  Both processes make the batches with the same code from the same seeds; the fan's hits come from the hook in
-both."""
+both.  --attributes: every closest-hit batch once more through rt_query_rays_attr_device (barycentrics and normals, DESIGN.md
+section 6.18), in the same process under the same protocol; its t and tri must be the plain query's."""
 import argparse
 import csv
 import glob
@@ -154,6 +155,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sweep", action="store_true", help="tune_refill_min 8, 24, 48 beside the default")
+    ap.add_argument("--attributes", action="store_true", help="the closest-hit batches with barycentrics and normals too")
     ap.add_argument("--baseline", default="", help="directory of the rocprofv3 kernel trace of a --hook run")
     ap.add_argument("--hook", action="store_true")
     ap.add_argument("--out", default="")
@@ -174,7 +176,7 @@ def main():
             commit += " + uncommitted changes"
     except (OSError, subprocess.CalledProcessError):
         commit = a.commit or "unknown (not a git checkout)"
-    lines = [f"# tools/ray_query.py --rays {a.rays} --repeats {a.repeats} --warmup {a.warmup}{' --sweep' if a.sweep else ''}   ({torch.cuda.get_device_name(0)})",
+    lines = [f"# tools/ray_query.py --rays {a.rays} --repeats {a.repeats} --warmup {a.warmup}{' --sweep' if a.sweep else ''}{' --attributes' if a.attributes else ''}   ({torch.cuda.get_device_name(0)})",
              f"# commit {commit}",
              "# query ms = rt_ray_query_stats.ms (HIP events around the launch of pt_query_rays), median of the repeats; Mrays/s = rays / that",
              "# hook kernel ms = pt_trace_rays in a rocprofv3 kernel trace of `tools/ray_query.py --hook` (a separate process, the same batches),"
@@ -194,7 +196,7 @@ def main():
             tseg = td * float(SEGMENT)
             for kind, dirs, any_hit in (("closest", td, False), ("any", tseg, True)):
                 ref = None
-                for sname, kw in settings:
+                for sname, kw in settings + ([("attributes", dict(attributes=True))] if a.attributes and not any_hit else []):
                     ms = []
                     for k in range(a.warmup + a.repeats):
                         got = r.query_rays(to, dirs, any_hit=any_hit, **kw)
