@@ -235,7 +235,31 @@ int rt_frame_poll(rt_ctx* ctx, uint32_t slot, int* ready);
  * deterministic sample and direct lighting (shaders/utilities.glsl:16-19, fragment.glsl:123-126
  * list reflection etc. as TODO).  The camera model (rot/pos/ratio, rt_resize) and the framebuffer
  * partition are shared with path A.  Specification: DESIGN.md §6.
+ *
+ * THE COORDINATE AND DIRECTION DOMAIN of every path B render and query entry (rt_render_pt, rt_render_pt_device,
+ * rt_frame_submit_pt, every rt_query_*, rt_count_*, rt_fill_* and rt_list_* below); derivation: DESIGN.md §6.3,
+ * measurements: §6.19.
+ *   mesh        max(1, M) <= 2^RT_PT_MAX_COORD_LOG2, M = the largest |vertex coordinate|.  One limit for all entries.  Beyond it
+ *               these entries return RT_ERR_INVALID before anything is enqueued or written; the message names M and the limit.
+ *               rt_set_mesh*, rt_refit_mesh_device, rt_update_mesh_chunk and rt_read_bvh take every finite mesh.
+ *   positions   camera position, ray origins and query points within the reach 32 x max(1, M) on every axis (the camera is refused
+ *               beyond it, a ray or a point is answered as invalid).
+ *   directions  query directions are only checked for being finite.  The answers hold - no intermediate overflows, and t means what
+ *               the entry says - for direction components of magnitude <= 1 (a unit vector; an occlusion segment as long as the
+ *               reach allows is rescaled by the caller).  Components below 1e-20 in magnitude count as 1e-20 in the ray/box test
+ *               only, which is conservative.  Longer directions work while |component| x M^2 stays below 2^110.
+ *   scale       within this domain all answers are covariant: a problem with every length (vertices, origins, points, tmax, rmax,
+ *               ray_eps, camera position) multiplied by 2^k gives bit for bit the same indices, counts, sides, barycentrics, unit
+ *               normals and frames, and t, dist, signed distances and closest points multiplied by 2^k - as long as the smallest
+ *               feature (a triangle's edges and altitudes, the distance from a shaded point to a light sample, ray_eps, a query
+ *               point's distance from the surface where it is not zero) stays above 2^RT_PT_MIN_FEATURE_LOG2.  Smaller features
+ *               are legitimate and never refused: there products of three and four lengths go subnormal, answers keep their
+ *               contracts' meaning but lose covariance and precision, a normal may be the zero vector (§6.18), and a light
+ *               sample closer than about 2^-37 contributes nothing.  A frame of a finite mesh with the camera in reach and a
+ *               finite ray_eps has no non-finite pixel at any scale down to zero.
  * ------------------------------------------------------------------------------------------------ */
+#define RT_PT_MAX_COORD_LOG2 20     /* max(1, M) <= 2^20 = 1 048 576 */
+#define RT_PT_MIN_FEATURE_LOG2 (-24) /* documentation only: nothing is refused on the small side */
 typedef struct rt_pt_params {
     uint32_t spp;      /* samples per pixel (any value >= 1) */
     uint32_t bounces;  /* indirect bounces after the camera ray (0..15) */
@@ -375,7 +399,9 @@ int rt_read_bvh(rt_ctx* ctx, uint32_t* nodes_out, uint32_t node_capacity, uint32
 /* Synchronous path-traced frame of the current view (rt_resize) into host memory.
  * Every |pos| component must be <= 32 x max(1, largest |vertex coordinate| of the mesh): that is the range
  * over which the BVH's conservative box padding covers the fp32 rounding of the ray/box test (beyond it the
- * frame could depend on the tree); RT_ERR_INVALID otherwise. */
+ * frame could depend on the tree); RT_ERR_INVALID otherwise.  RT_ERR_INVALID too for a mesh beyond
+ * 2^RT_PT_MAX_COORD_LOG2 (the domain above; the same for the two entries below).  A refused call has
+ * enqueued and written nothing: the frame the context held before still reads back (rt_read_rgba8). */
 int rt_render_pt(rt_ctx* ctx, const float rot[4], const float pos[3], const rt_pt_params* params, float* rgb_out);
 /* Asynchronous device-side variant, same output layouts as rt_render_device. */
 int rt_render_pt_device(rt_ctx* ctx, const float rot[4], const float pos[3], const rt_pt_params* params, void* rgb_dev, int tile_major);
@@ -397,7 +423,9 @@ int rt_get_pt_stats(rt_ctx* ctx, rt_pt_stats* stats);
  * Works on every mesh (host-built single- and two-level, device-built, refitted, with surfaces); reads the mesh only, so a
  * shared mesh stays shared.  Errors, all before anything is enqueued or written: RT_ERR_INVALID (a NULL, host or other-device
  * pointer, an allocation shorter than n rows, n above 2^30, tune_refill_min above 64, tune_blocks_per_cu above 8, tune_lds_stack
- * above 78), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch).  n == 0: RT_OK, nothing is done. */
+ * above 78, a mesh beyond 2^RT_PT_MAX_COORD_LOG2 - the domain at the head of this section, which also says for which direction
+ * magnitudes the answers hold; the same refusal in every query entry below), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch).
+ * n == 0: RT_OK, nothing is done. */
 typedef struct rt_ray_query_params {
     uint32_t any_hit;            /* 0 closest hit, 1 occlusion */
     uint32_t tune_refill_min;    /* as rt_pt_params (0 = default) */
@@ -433,8 +461,8 @@ int rt_get_ray_query_stats(rt_ctx* ctx, rt_ray_query_stats* stats); /* synchroni
  * rt_render_pt_device's.  Works on every mesh (host-built single- and two-level, device-built, refitted, with surfaces); reads the
  * mesh only, so a shared mesh stays shared.  Errors, all before anything is enqueued or written: RT_ERR_INVALID (a NULL context; a
  * NULL, host or other-device pointer, an allocation shorter than n rows, n above 2^30, count_traversal above 1, tune_refill_min above
- * 64, tune_blocks_per_cu above 8, tune_lds_stack above 78), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch).  n == 0: RT_OK, nothing is
- * done. */
+ * 64, tune_blocks_per_cu above 8, tune_lds_stack above 78, a mesh beyond 2^RT_PT_MAX_COORD_LOG2 (the domain at the head of this
+ * section)), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch).  n == 0: RT_OK, nothing is done. */
 typedef struct rt_point_query_params {
     uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_ray_query_params */
     uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
@@ -492,7 +520,8 @@ int rt_query_points_attr_device(rt_ctx* ctx, const void* points_dev, const void*
  * mesh (host-built single- and two-level, device-built, refitted, with surfaces); reads the mesh only, so a shared mesh stays shared.
  * Errors, all before anything is enqueued or written: RT_ERR_INVALID (a NULL context; a NULL (where not allowed), host or other-device
  * pointer, an allocation shorter than n rows, n above 2^30, count_traversal above 1, tune_refill_min above 64, tune_blocks_per_cu above
- * 8, tune_lds_stack above 78), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch).  n == 0: RT_OK, nothing is done.
+ * 8, tune_lds_stack above 78, a mesh beyond 2^RT_PT_MAX_COORD_LOG2 (the domain at the head of this section)), RT_ERR_STATE (no
+ * mesh), RT_ERR_OOM (scratch).  n == 0: RT_OK, nothing is done.
  * rt_query_signed_distance_device is exactly rt_query_points_device(points_dev, rmax_dev, n, point_params, sdist_out_dev, tri_out_dev,
  * point_out_dev) followed by rt_query_sides_device(points_dev, n, side_params, inside_out_dev, NULL, sdist_out_dev): sdist_out_dev[i] =
  * the distance to the nearest triangle, negative inside; with rmax_dev a narrow-band signed distance, the points beyond the band (+inf)
@@ -549,8 +578,9 @@ int rt_get_side_query_stats(rt_ctx* ctx, rt_side_query_stats* stats); /* synchro
  * single- and two-level, device-built, refitted, with surfaces); reads the mesh only, so a shared mesh stays shared.  Errors, all
  * before anything is enqueued or written: RT_ERR_INVALID (a NULL context; a NULL (where not allowed), host or other-device pointer,
  * an allocation shorter than n / n + 1 / capacity rows, n above 2^30, capacity above 2^40, count_traversal above 1, tune_refill_min above 64,
- * tune_blocks_per_cu above 8, tune_lds_stack above 78), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch: 8 bytes per ray for the scan,
- * grown by size class).  n == 0: RT_OK, nothing is done. */
+ * tune_blocks_per_cu above 8, tune_lds_stack above 78, a mesh beyond 2^RT_PT_MAX_COORD_LOG2 (the domain at the head of this
+ * section)), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch: 8 bytes per ray for the scan, grown by size class).  n == 0: RT_OK,
+ * nothing is done. */
 typedef struct rt_hit_query_params {
     uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_ray_query_params */
     uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
@@ -608,9 +638,9 @@ int rt_get_hit_query_stats(rt_ctx* ctx, rt_hit_query_stats* stats); /* synchroni
  * rt_render_pt_device's.  Works on every mesh (host-built single- and two-level, device-built, refitted, with surfaces); reads the mesh
  * only, so a shared mesh stays shared.  Errors, all before anything is enqueued or written: RT_ERR_INVALID (a NULL context; a NULL
  * (where not allowed), host or other-device pointer, an allocation shorter than n / n + 1 / capacity rows, n above 2^30, capacity above
- * 2^40, count_traversal above 1, tune_refill_min above 64, tune_blocks_per_cu above 8, tune_lds_stack above 78), RT_ERR_STATE (no
- * mesh), RT_ERR_OOM (scratch: 8 bytes per point for the scan, shared with the all-hits queries, grown by size class).  n == 0: RT_OK,
- * nothing is done. */
+ * 2^40, count_traversal above 1, tune_refill_min above 64, tune_blocks_per_cu above 8, tune_lds_stack above 78, a mesh beyond
+ * 2^RT_PT_MAX_COORD_LOG2 (the domain at the head of this section)), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch: 8 bytes per point
+ * for the scan, shared with the all-hits queries, grown by size class).  n == 0: RT_OK, nothing is done. */
 typedef struct rt_neighbor_query_params {
     uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_ray_query_params */
     uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */

@@ -375,9 +375,10 @@ static void trace_path(const orb_scene* s, const orb_params* p, uint32_t px, uin
             float d2 = dot(wi, wi);
             v3 nl = cross(le1, le2); /* |nl| = 2 * area */
             float cs = dot(n, wi), cl = fabsf(dot(nl, wi));
-            if (cs > 0.0f && cl > 0.0f && d2 > 0.0f) {
+            float d4 = d2 * d2; /* underflows to 0 for a light closer than about 2^-37 (d2 > 0 still): no sample, not a division by 0 */
+            if (cs > 0.0f && cl > 0.0f && d4 > 0.0f) {
                 /* cos_s cos_l / d^2 * area * n_lights / pi, with the normalisations folded in */
-                float w = ((cs * cl) * ((float)s->n_lights * 0.15915494f)) / (d2 * d2);
+                float w = ((cs * cl) * ((float)s->n_lights * 0.15915494f)) / d4;
                 const float* le = s->emission + 3 * lt;
                 float cr = ((Tr * alb[0]) * le[0]) * w, cg = ((Tg * alb[1]) * le[1]) * w, cb = ((Tb * alb[2]) * le[2]) * w;
                 ct->shadow_rays++;

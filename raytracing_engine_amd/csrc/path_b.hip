@@ -294,8 +294,9 @@ __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, 
                         const float d2 = dot(wi, wi);
                         const v3 nl = cross(le1, le2);
                         const float cs = dot(nrm, wi), cl = __builtin_fabsf(dot(nl, wi));
-                        if (cs > 0.0f && cl > 0.0f && d2 > 0.0f) {
-                            const float w = ((cs * cl) * ((float)sc.n_lights * 0.15915494f)) / (d2 * d2);
+                        const float d4 = d2 * d2;  // underflows to 0 for a light closer than about 2^-37 (d2 > 0 still): no sample, not a division by 0
+                        if (cs > 0.0f && cl > 0.0f && d4 > 0.0f) {
+                            const float w = ((cs * cl) * ((float)sc.n_lights * 0.15915494f)) / d4;
                             const float4 le = sc.emission[lt];
                             shadow = true;
                             so = make_float4(po.x, po.y, po.z, __uint_as_float(pid));

@@ -124,6 +124,7 @@ int plan_frame(Ctx* c, const float rot[4], const float pos[3], const rt_pt_param
     if (!mesh.n_tris) return c->fail(RT_ERR_STATE, "rt_set_mesh has not been called");
     if (!c->width) return c->fail(RT_ERR_STATE, "rt_resize has not been called");
     if (prm->spp == 0 || prm->bounces > kMaxBounces) return c->fail(RT_ERR_INVALID, "spp %u / bounces %u out of range", prm->spp, prm->bounces);
+    if (int rc = rt::check_mesh_domain(c, mesh)) return rc;
     {
         // The slab test's rounding error is about 2^-22 * (|origin| + |plane|) in position space and the boxes are
         // padded by 2e-5 * M (M = largest |vertex coordinate|, at least 1): the invariant "results do not depend on
@@ -325,12 +326,15 @@ int read_frame_stats(Ctx* c, const StageTimer& tm, const FrameCounts& n) {
     return RT_OK;
 }
 
-int render_pt_common(Ctx* c, const float rot[4], const float pos[3], const rt_pt_params* prm, float* dst_dev, int tile_major, bool sync) {
+// clear_bytes: dst_dev is zeroed first (rt_render_pt's frame: the tiles of other ranks stay black) - after every refusal of plan_frame,
+// so that a refused call has enqueued nothing and the frame that was there still reads back
+int render_pt_common(Ctx* c, const float rot[4], const float pos[3], const rt_pt_params* prm, float* dst_dev, int tile_major, bool sync, size_t clear_bytes = 0) {
     if (!c) return RT_ERR_INVALID;
     PtData& pt = c->pt;
     StageTimer tm{c, c->cfg.profile_stages != 0, pt.ev_pool, {}, 0};
     FramePlan plan;
     if (int rc = plan_frame(c, rot, pos, prm, tm.on, &plan)) return rc;
+    if (clear_bytes) RT_HIP(c, hipMemsetAsync(dst_dev, 0, clear_bytes, c->stream));
     if (plan.n_slots == 0) return RT_OK;
 
     rt::PtFrame f{};  // per batch only spp_batch, n_paths and sample0 change
@@ -445,9 +449,9 @@ int rt_render_pt(rt_ctx* ctx, const float rot[4], const float pos[3], const rt_p
     if (!c) return RT_ERR_INVALID;
     if (!c->width) return c->fail(RT_ERR_STATE, "rt_resize has not been called");
     if (int rc = rt::bind(c)) return rc;
-    RT_HIP(c, hipMemsetAsync(c->d_rgb, 0, (size_t)c->width * c->height * 3 * sizeof(float), c->stream));
-    if (int rc = render_pt_common(c, rot, pos, params, c->d_rgb, 0, true)) return rc;
-    if (rgb_out) RT_HIP(c, hipMemcpy(rgb_out, c->d_rgb, (size_t)c->width * c->height * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    const size_t bytes = (size_t)c->width * c->height * 3 * sizeof(float);
+    if (int rc = render_pt_common(c, rot, pos, params, c->d_rgb, 0, true, bytes)) return rc;
+    if (rgb_out) RT_HIP(c, hipMemcpy(rgb_out, c->d_rgb, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

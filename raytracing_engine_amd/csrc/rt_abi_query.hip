@@ -21,6 +21,7 @@ constexpr uint32_t kQueryRefillMin = 24;       // idle lanes per wave that trigg
 template <class Params>
 int check_query_params(Ctx* c, uint32_t n, const Params& prm, uint32_t flag, const char* flag_name) {
     if (!c->pt.mesh().n_tris) return c->fail(RT_ERR_STATE, "rt_set_mesh has not been called");
+    if (int rc = rt::check_mesh_domain(c, c->pt.mesh())) return rc;
     if (n > kMaxQueryItems) return c->fail(RT_ERR_INVALID, "n %u is above 2^30", n);
     if (flag > 1u) return c->fail(RT_ERR_INVALID, "%s %u (0 or 1)", flag_name, flag);
     if ((prm.tune_refill_min & 0xffu) > 64u || prm.tune_refill_min > 0xffffu) return c->fail(RT_ERR_INVALID, "tune_refill_min %u (low byte 0 .. 64)", prm.tune_refill_min);

@@ -508,6 +508,16 @@ void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block a
 
 // |coordinate| limit of a camera position, a query ray's origin and a query point in units of DeviceMesh::maxabs (plan_frame, rt_abi_pt.hip)
 constexpr float kCameraReach = 32.0f;
+// Largest DeviceMesh::maxabs that path B renders and queries: 2^RT_PT_MAX_COORD_LOG2.  Up to it no intermediate of a path B operation
+// overflows (DESIGN.md sections 6.3 and 6.19); rt_set_mesh*, the refit, a chunk update and rt_read_bvh take every finite mesh.
+constexpr float kMaxCoord = (float)(1u << RT_PT_MAX_COORD_LOG2);
+// The refusal of a render or a query on a mesh beyond it: one host comparison, before anything is enqueued or written
+inline int check_mesh_domain(Ctx* c, const DeviceMesh& mesh) {
+    if (!(mesh.maxabs <= kMaxCoord))
+        return c->fail(RT_ERR_INVALID, "the mesh's largest |coordinate| %g is above the limit %g (2^%u) of path B's renders and queries: beyond it fp32 intermediates overflow",
+                       (double)mesh.maxabs, (double)kMaxCoord, (unsigned)RT_PT_MAX_COORD_LOG2);
+    return RT_OK;
+}
 inline PtScene scene_view(const DeviceMesh& m) {
     PtScene s{};
     s.nodes = m.nodes.get();

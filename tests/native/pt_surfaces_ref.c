@@ -181,8 +181,9 @@ static void trace_path(const prs_scene* ps, const orb_params* p, uint32_t px, ui
             const float d2 = dot(wi, wi);
             const v3 nl = cross(le1, le2);
             const float cs = dot(n, wi), cl = fabsf(dot(nl, wi));
-            if (cs > 0.0f && cl > 0.0f && d2 > 0.0f) {
-                const float wt = ((cs * cl) * ((float)ps->n_lights * 0.15915494f)) / (d2 * d2);
+            const float d4 = d2 * d2; /* oracle_b.c: 0 for a light closer than about 2^-37 */
+            if (cs > 0.0f && cl > 0.0f && d4 > 0.0f) {
+                const float wt = ((cs * cl) * ((float)ps->n_lights * 0.15915494f)) / d4;
                 const float* le = ps->emission + 3 * (size_t)lt;
                 float c3[3];
                 for (int j = 0; j < 3; j++) c3[j] = ((T[j] * alb[j]) * le[j]) * wt;
