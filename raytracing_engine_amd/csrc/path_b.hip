@@ -122,16 +122,20 @@ __device__ __forceinline__ uint32_t block_append_sorted(bool want, uint32_t key,
     static_assert(BINS % 64u == 0u && BINS <= kSortBins, "whole waves of bins");
     uint32_t* hist = lds;               // BINS
     uint32_t* wsum = lds + kSortBins;   // 16 wave sums of the scan + 1 base
-    for (uint32_t i = threadIdx.x; i < BINS; i += blockDim.x) hist[i] = 0;
+    // The thread index as a value the compiler cannot follow: what this function derives from it (lane masks of the scan, LDS
+    // addresses) is then made where it is used, not kept in registers through the caller's loop, which seldom comes here.
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    for (uint32_t i = tid; i < BINS; i += blockDim.x) hist[i] = 0;
     __syncthreads();
     uint32_t rank = 0;
     if (want) rank = atomicAdd(&hist[key], 1u);
     __syncthreads();
     // exclusive scan of the BINS counts by the first BINS threads (wave scan + wave sums)
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
     uint32_t v = 0, incl = 0;
-    if (threadIdx.x < BINS) {
-        v = hist[threadIdx.x];
+    if (tid < BINS) {
+        v = hist[tid];
         incl = v;
         for (int off = 1; off < 64; off <<= 1) {
             const uint32_t t = __shfl_up(incl, off);
@@ -140,7 +144,7 @@ __device__ __forceinline__ uint32_t block_append_sorted(bool want, uint32_t key,
         if (lane == 63) wsum[wave] = incl;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (tid == 0) {
         uint32_t total = 0;
         for (uint32_t w = 0; w < BINS / 64u; w++) {
             const uint32_t c = wsum[w];
@@ -150,7 +154,7 @@ __device__ __forceinline__ uint32_t block_append_sorted(bool want, uint32_t key,
         wsum[16] = total ? atomicAdd(counter, total) : 0u;
     }
     __syncthreads();
-    if (threadIdx.x < BINS) hist[threadIdx.x] = wsum[wave] + incl - v;  // bin start inside the workgroup's range
+    if (tid < BINS) hist[tid] = wsum[wave] + incl - v;  // bin start inside the workgroup's range
     __syncthreads();
     const uint32_t idx = want ? wsum[16] + hist[key] + rank : 0u;
     __syncthreads();  // lds is reused by the next append
@@ -212,16 +216,49 @@ __global__ __launch_bounds__(kAppendThreads) void pt_generate(const PtFrame f, P
 // ---- shade ----------------------------------------------------------------------------------------
 // SURF = false: every triangle is a Lambert reflector or a light (§6.4).  SURF = true: also mirror and glass triangles
 // (§6.11, albedo.w != 0); thr.w = 1 marks a path whose last vertex was one of them, so the light it hits next is counted.
-template <bool SURF>
+//
+// The stage is bound by memory latency, so an item waits for memory three times, once per true dependency, and every load of a
+// level is issued before the first wait of that level:
+//   1. queue[i] -> pid                       (not behind the packet kernel: there the items are the path ids)
+//   2. hit / ray_d / ray_o / thr / rad of the path
+//   3. the whole record of the hit triangle (the emissive flag arrives with it) and its albedo, as one batch
+// emission[li] of the hit triangle stays behind the flag: only the rare path that ends on a light reads it.
+// The sampled light, TAB = true (at most kShadeLightTable lights, the launcher decides): every workgroup copies lights[k], the
+// record and the emission of each light into LDS once, before its first item, and the sample reads them there - no wait on
+// memory.  TAB = false: lights[kk] needs the path id alone and is loaded with level 2; the light's record and emission are one
+// more batch inside the estimation (64 VGPRs do not reach to start it before the hit triangle has arrived).  Both ways the
+// sample runs the same operations on the same values.
+constexpr uint32_t kShadeLightTable = 32;  // lights held in LDS: four float4 each (2 KiB)
+// An empty statement that reads and writes x in a vector register: the load that produces x cannot move below it.
+__device__ __forceinline__ void keep_here(float& x) { asm volatile("" : "+v"(x)); }
+// The light of a path's next-event estimation at this depth: lights[min(floor(u N_L), N_L - 1)], from the path id alone.
+__device__ __forceinline__ uint32_t light_pick(const PtScene& sc, const PtFrame& f, uint32_t pid, uint32_t depth) {
+    const uint32_t slot = pid / f.spp_batch, s = f.sample0 + (pid - slot * f.spp_batch);
+    uint32_t px, py, lx, ly, k;
+    slot_pixel(f, slot, px, py, lx, ly, k);
+    const uint32_t kk = (uint32_t)(rnd(path_key(py * f.width + px, s, f.seed), depth, 2) * (float)sc.n_lights);
+    return kk > sc.n_lights - 1 ? sc.n_lights - 1 : kk;
+}
+template <bool SURF, bool TAB>
 __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, const PtFrame f, PtState st, const uint32_t* __restrict__ queue,
                                                            const uint32_t* __restrict__ count_ptr, uint32_t depth, uint32_t* __restrict__ next_queue,
                                                            uint32_t* __restrict__ next_ctr, uint32_t sort_rays) {
     __shared__ uint32_t lds[kSortBins + 40];
+    __shared__ float4 light_tab[kShadeLightTable * 4];  // per light: the three float4 of its record, then emission.xyz with lights[k] in w
     // queue == nullptr (depth 0 behind the packet kernel, which has no generate stage and no queue): the items are the
     // path ids themselves; origin = camera, throughput 1, radiance 0 are known and not read from the path state
     const bool direct = queue == nullptr;
     const uint32_t n = direct ? f.n_paths : *count_ptr;
     const uint32_t stride = gridDim.x * kAppendThreads;
+    if (TAB) {
+        if (threadIdx.x < sc.n_lights * 4u) {
+            const uint32_t lt = sc.lights[threadIdx.x >> 2], j = threadIdx.x & 3u;
+            float4 v = j < 3u ? sc.tris[(size_t)lt * 3 + j] : sc.emission[lt];
+            if (j == 3u) v.w = __uint_as_float(lt);
+            light_tab[threadIdx.x] = v;
+        }
+        __syncthreads();
+    }
     // grid-stride over whole workgroups: the trip count is workgroup-uniform (barriers in block_append)
     for (uint32_t base = blockIdx.x * kAppendThreads; base < n; base += stride) {
         const uint32_t i = base + threadIdx.x;
@@ -229,37 +266,48 @@ __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, 
         uint32_t pid = 0;
         float4 so = {}, sd = {}, scn = {};
         bool item = i < n;
-        if (item && direct) {
-            uint32_t px, py, lx, ly, k;
-            item = slot_pixel(f, i / f.spp_batch, px, py, lx, ly, k);
-        }
+        uint32_t px = 0, py = 0, lx, ly, k;
+        if (item && direct) item = slot_pixel(f, i / f.spp_batch, px, py, lx, ly, k);
         if (item) {
             pid = direct ? i : queue[i];
+            // ---- level 2: everything that hangs on pid alone
             const float2 hrec = st.hit[pid];
-            const int li = __float_as_int(hrec.y);
+            uint32_t lt = 0;
+            if (!TAB) lt = sc.lights[light_pick(sc, f, pid, depth)];
             const float4 rd = st.ray_d[pid];
             const float4 ro = direct ? make_float4(f.cam.pos[0], f.cam.pos[1], f.cam.pos[2], 0.0f) : st.ray_o[pid];
             const float4 T = direct ? make_float4(1.0f, 1.0f, 1.0f, 0.0f) : st.thr[pid];
-            const v3 o = mk(ro.x, ro.y, ro.z), d = mk(rd.x, rd.y, rd.z);
             float4 L = direct ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : st.rad[pid];
-            if (direct) st.rad[pid] = L;  // the shadow stage and pt_resolve read it; the branches below overwrite it where they add light
+            // ---- level 3: the hit triangle's record and albedo in one batch (a path that left the scene reads triangle 0 and
+            // ignores it)
+            const int li = __float_as_int(hrec.y);
+            const size_t lr = li < 0 ? 0 : (size_t)li;
+            float4 ta = sc.tris[lr * 3 + 0], tb = sc.tris[lr * 3 + 1], tc = sc.tris[lr * 3 + 2];
+            float4 alb = sc.albedo[lr];
+            // left alone, the compiler sinks these loads into the branches below, the flag word first and the rest behind its wait
+            keep_here(tc.z), keep_here(ta.w), keep_here(tb.x), keep_here(tb.y), keep_here(tb.z), keep_here(tb.w), keep_here(tc.x);
+            keep_here(alb.x), keep_here(alb.y), keep_here(alb.z);
+            if (SURF) keep_here(alb.w);
+            const v3 o = mk(ro.x, ro.y, ro.z), d = mk(rd.x, rd.y, rd.z);
+            // depth 0 behind the packet kernel: rad[pid] is stored once per path - zero (the shadow stage and pt_resolve read
+            // it), the sky term or the emission term
             if (li < 0) {  // left the scene
                 L.x = __builtin_fmaf(T.x, f.sky[0], L.x);
                 L.y = __builtin_fmaf(T.y, f.sky[1], L.y);
                 L.z = __builtin_fmaf(T.z, f.sky[2], L.z);
                 st.rad[pid] = L;
             } else {
-                const float4 ta = sc.tris[(size_t)li * 3 + 0], tb = sc.tris[(size_t)li * 3 + 1], tc = sc.tris[(size_t)li * 3 + 2];
                 if (__float_as_uint(tc.z) != 0u) {  // emissive (flag in the triangle record); lights are seen directly only by camera rays
-                    if (depth == 0 || (SURF && T.w != 0.0f)) {  // and by rays that leave a mirror or glass vertex
+                    const bool seen = depth == 0 || (SURF && T.w != 0.0f);  // and by rays that leave a mirror or glass vertex
+                    if (seen) {
                         const float4 em = sc.emission[li];
                         L.x = __builtin_fmaf(T.x, em.x, L.x);
                         L.y = __builtin_fmaf(T.y, em.y, L.y);
                         L.z = __builtin_fmaf(T.z, em.z, L.z);
-                        st.rad[pid] = L;
                     }
+                    if (seen || direct) st.rad[pid] = L;
                 } else {
-                    const float4 alb = sc.albedo[li];
+                    if (direct) st.rad[pid] = L;
                     v3 nrm = normalize(cross(mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x)));
                     const bool flipped = dot(nrm, d) > 0.0f;
                     if (flipped) nrm = -nrm;
@@ -267,7 +315,6 @@ __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, 
                     const v3 po = fma3(nrm, f.ray_eps, pt);
                     // path id -> rng key
                     const uint32_t slot = pid / f.spp_batch, s = f.sample0 + (pid - slot * f.spp_batch);
-                    uint32_t px, py, lx, ly, k;
                     slot_pixel(f, slot, px, py, lx, ly, k);
                     const uint32_t key = path_key(py * f.width + px, s, f.seed);
                     const bool delta = SURF && alb.w != 0.0f;  // mirror or glass: no next-event estimation; on as a bounce ray or the path ends
@@ -281,12 +328,19 @@ __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, 
                         st.thr[pid] = make_float4(T.x * alb.x, T.y * alb.y, T.z * alb.z, 1.0f);
                     }
                     if (!delta && sc.n_lights > 0) {  // next-event estimation
-                        uint32_t kk = (uint32_t)(rnd(key, depth, 2) * (float)sc.n_lights);
-                        if (kk > sc.n_lights - 1) kk = sc.n_lights - 1;
-                        const uint32_t lt = sc.lights[kk];
+                        float4 la, lb, lc, le;
+                        if (TAB) {
+                            uint32_t kk = (uint32_t)(rnd(key, depth, 2) * (float)sc.n_lights);
+                            if (kk > sc.n_lights - 1) kk = sc.n_lights - 1;
+                            la = light_tab[kk * 4u + 0u], lb = light_tab[kk * 4u + 1u], lc = light_tab[kk * 4u + 2u];
+                            le = light_tab[kk * 4u + 3u];
+                        } else {  // the record and the emission in one batch: the registers do not reach to start it before the hit triangle is there
+                            la = sc.tris[(size_t)lt * 3 + 0], lb = sc.tris[(size_t)lt * 3 + 1], lc = sc.tris[(size_t)lt * 3 + 2];
+                            le = sc.emission[lt];
+                            keep_here(le.x), keep_here(le.y), keep_here(le.z);
+                        }
                         const float su = __builtin_sqrtf(rnd(key, depth, 3)), u2 = rnd(key, depth, 4);
                         const float b1 = su * (1.0f - u2), b2 = su * u2;
-                        const float4 la = sc.tris[(size_t)lt * 3 + 0], lb = sc.tris[(size_t)lt * 3 + 1], lc = sc.tris[(size_t)lt * 3 + 2];
                         const v3 lv0 = mk(la.x, la.y, la.z), le1 = mk(la.w, lb.x, lb.y), le2 = mk(lb.z, lb.w, lc.x);
                         const v3 q = mk(__builtin_fmaf(le2.x, b2, __builtin_fmaf(le1.x, b1, lv0.x)), __builtin_fmaf(le2.y, b2, __builtin_fmaf(le1.y, b1, lv0.y)),
                                         __builtin_fmaf(le2.z, b2, __builtin_fmaf(le1.z, b1, lv0.z)));
@@ -297,7 +351,6 @@ __global__ __launch_bounds__(kAppendThreads, 8) void pt_shade(const PtScene sc, 
                         const float d4 = d2 * d2;  // underflows to 0 for a light closer than about 2^-37 (d2 > 0 still): no sample, not a division by 0
                         if (cs > 0.0f && cl > 0.0f && d4 > 0.0f) {
                             const float w = ((cs * cl) * ((float)sc.n_lights * 0.15915494f)) / d4;
-                            const float4 le = sc.emission[lt];
                             shadow = true;
                             so = make_float4(po.x, po.y, po.z, __uint_as_float(pid));
                             sd = make_float4(wi.x, wi.y, wi.z, 0.0f);
@@ -397,12 +450,9 @@ int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* qu
 
 int launch_pt_shade(Ctx* c, const PtScene& sc, const PtFrame& f, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr,
                     uint32_t depth, uint32_t* next_queue, uint32_t* next_ctr, uint32_t grid, uint32_t sort_rays, bool surfaces) {
-    if (surfaces)
-        hipLaunchKernelGGL(pt_shade<true>, dim3(grid), dim3(kAppendThreads), 0, c->stream, sc, f, st, queue, count_ptr, depth, next_queue, next_ctr,
-                           sort_rays);
-    else
-        hipLaunchKernelGGL(pt_shade<false>, dim3(grid), dim3(kAppendThreads), 0, c->stream, sc, f, st, queue, count_ptr, depth, next_queue, next_ctr,
-                           sort_rays);
+    const bool tab = sc.n_lights <= kShadeLightTable;
+    auto kernel = surfaces ? (tab ? pt_shade<true, true> : pt_shade<true, false>) : (tab ? pt_shade<false, true> : pt_shade<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kAppendThreads), 0, c->stream, sc, f, st, queue, count_ptr, depth, next_queue, next_ctr, sort_rays);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
