@@ -32,6 +32,65 @@ def test_rng_is_a_counter_hash():
     assert O.pt_rand(123, 3, 2, 5, 77) == np.float32(expect)
 
 
+# ---- independence of the generator's dimensions (spec §6.2) -------------------------------------------------------------------------
+# A path tracer's answer is an integral over the unit cube of all (depth, dim): two coordinates that are correlated bias it, and every
+# parity test passes, because the kernels share the generator bit for bit.  2^16 points (256 pixels x 256 samples) per stream.
+RNG_SEED, RNG_SIDE = 20261019, 256
+CHI2_MAX = 255 + 5 * math.sqrt(510)  # 16 x 16 bins: 255 degrees of freedom, five sigma = 368
+RNG_DEPTHS = 5
+
+
+@pytest.fixture(scope="module")
+def rng_streams():
+    """{(depth, dim, seed): (256 pixels, 256 samples) float64} from O.pt_rand: every dim at depths 0..4, and depth 0 at the next seed."""
+    from itertools import repeat
+
+    pix, smp = (x.ravel().tolist() for x in np.meshgrid(np.arange(RNG_SIDE), np.arange(RNG_SIDE), indexing="ij"))
+    keys = [(d, k, RNG_SEED) for d in range(RNG_DEPTHS) for k in range(8)] + [(0, k, RNG_SEED + 1) for k in range(8)]
+    return {(d, k, s): np.array(list(map(O.pt_rand, pix, smp, repeat(d), repeat(k), repeat(s)))).reshape(RNG_SIDE, RNG_SIDE) for d, k, s in keys}
+
+
+def chi2_16x16(x, y):
+    x, y = np.ravel(x), np.ravel(y)
+    counts = np.bincount((x * 16).astype(np.int64) * 16 + (y * 16).astype(np.int64), minlength=256)
+    expect = len(x) / 256.0
+    return float(((counts - expect) ** 2).sum() / expect)
+
+
+def test_rng_dimensions_are_pairwise_independent(rng_streams):
+    s = rng_streams
+    pairs = {f"dims {i},{j} at depth 0": (s[0, i, RNG_SEED], s[0, j, RNG_SEED]) for i in range(8) for j in range(i + 1, 8)}
+    for k in range(8):
+        x = s[0, k, RNG_SEED]
+        for d in range(RNG_DEPTHS - 1):
+            pairs[f"dim {k} at depths {d},{d + 1}"] = (s[d, k, RNG_SEED], s[d + 1, k, RNG_SEED])
+        pairs[f"dim {k} at samples s,s+1"] = (x[:, :-1], x[:, 1:])
+        pairs[f"dim {k} at pixels p,p+1"] = (x[:-1], x[1:])
+        pairs[f"dim {k} at seeds S,S+1"] = (x, s[0, k, RNG_SEED + 1])
+    assert len(pairs) == 28 + 8 * (RNG_DEPTHS - 1 + 3)
+    chi = {name: chi2_16x16(*xy) for name, xy in pairs.items()}
+    worst = max(chi, key=chi.get)
+    print(f"{len(chi)} pairs: chi^2 from {min(chi.values()):.0f} to {chi[worst]:.0f} ({worst}), mean {np.mean(list(chi.values())):.0f}; limit {CHI2_MAX:.0f}")
+    assert not {n: c for n, c in chi.items() if c > CHI2_MAX}
+    band = 5 * math.sqrt(510 / len(chi))  # the mean of 84 such values: 255 +- 12.3; neither correlated nor too even (a lattice would be)
+    assert abs(np.mean(list(chi.values())) - 255) <= band
+    x = s[0, 5, RNG_SEED]  # power: a stream against a shifted copy of itself, and against a copy blended 1 : 9 with an independent one
+    assert chi2_16x16(x, (x + 0.03) % 1.0) > 10 * CHI2_MAX
+    assert chi2_16x16(x, np.where(s[0, 2, RNG_SEED] < 0.1, x, s[0, 6, RNG_SEED])) > CHI2_MAX
+
+
+def test_rng_streams_have_no_serial_correlation(rng_streams):
+    """Lag-1 correlation of every stream in pixel-major order and in sample-major order: |r| sqrt(n) <= 5."""
+    worst = 0.0
+    for key, x in rng_streams.items():
+        assert x.min() >= 0.0 and x.max() < 1.0 and abs(x.mean() - 0.5) * math.sqrt(12 * x.size) <= 5.0, key
+        for flat in (x.ravel(), x.T.ravel()):
+            r = np.corrcoef(flat[:-1], flat[1:])[0, 1]
+            worst = max(worst, abs(r) * math.sqrt(flat.size - 1))
+            assert abs(r) * math.sqrt(flat.size - 1) <= 5.0, (key, r)
+    print(f"worst |r| sqrt(n) = {worst:.2f}")
+
+
 def test_sincos_polynomial():
     us = np.linspace(0, 1, 4001, endpoint=False, dtype=np.float32)
     sc = np.array([O.sincos_2pi(float(u)) for u in us])
