@@ -242,8 +242,8 @@ int rt_frame_poll(rt_ctx* ctx, uint32_t slot, int* ready);
  *   mesh        max(1, M) <= 2^RT_PT_MAX_COORD_LOG2, M = the largest |vertex coordinate|.  One limit for all entries.  Beyond it
  *               these entries return RT_ERR_INVALID before anything is enqueued or written; the message names M and the limit.
  *               rt_set_mesh*, rt_refit_mesh_device, rt_update_mesh_chunk and rt_read_bvh take every finite mesh.
- *   positions   camera position, ray origins and query points within the reach 32 x max(1, M) on every axis (the camera is refused
- *               beyond it, a ray or a point is answered as invalid).
+ *   positions   camera position, ray origins, query points and the vertices of query triangles (rt_*_overlaps_device) within the reach
+ *               32 x max(1, M) on every axis (the camera is refused beyond it, a ray, a point or a triangle is answered as invalid).
  *   directions  query directions are only checked for being finite.  The answers hold - no intermediate overflows, and t means what
  *               the entry says - for direction components of magnitude <= 1 (a unit vector; an occlusion segment as long as the
  *               reach allows is rescaled by the caller).  Components below 1e-20 in magnitude count as 1e-20 in the ray/box test
@@ -667,6 +667,70 @@ int rt_list_neighbors_device(rt_ctx* ctx, const void* points_dev, const void* rm
                              const rt_neighbor_query_params* params /* NULL = defaults */, void* count_out_dev /* may be NULL */,
                              void* offsets_out_dev, uint64_t capacity, void* dist_out_dev, void* tri_out_dev);
 int rt_get_neighbor_query_stats(rt_ctx* ctx, rt_neighbor_query_stats* stats); /* synchronises the stream; the last call */
+/* Overlap queries on device arrays: EVERY triangle of the current mesh that each of n caller-supplied triangles
+ * intersects, counted and listed with the edges that pierce.  Enqueued on the context's stream behind the work already there; no host
+ * synchronisation, and no allocation after the first query of a size class.  Query triangle i is tris_dev[i] (n x 9 f32: the vertices
+ * A0, A1, A2, rt_set_mesh's vertex layout), device memory of the context's device, only read.  The arithmetic is csrc/tri_overlap.h,
+ * fp32 only.  With F1 = A1 - A0, F2 = A2 - A0, Q = the box of the three vertices, and for mesh triangle T its record's v0, e1, e2 and
+ * B = the box of v0, fl(v0 + e1), fl(v0 + e2):  cand(i, T) = Q and B overlap (closed, on all three axes);
+ * seg(o, d, w0, g1, g2) = the ray / triangle test of rt_query_rays_device (csrc/ray_parity.h: ray_tri_t) accepts with 0 < t < 1, strict
+ * at both ends;  mask(i, T) = bit 0: seg(A0, A1 - A0, v0, e1, e2), bit 1: seg(A1, A2 - A1, v0, e1, e2), bit 2: seg(A2, A0 - A2, v0, e1,
+ * e2), bit 3: seg(v0, e1, A0, F1, F2), bit 4: seg(fl(v0 + e1), e2 - e1, A0, F1, F2), bit 5: seg(v0, e2, A0, F1, F2) - bits 0-2: an edge
+ * of the query triangle pierces T, bits 3-5: an edge of T pierces the query triangle.  overlaps(i) = the triangles with cand and
+ * mask != 0.  The answer is defined without the tree and does not depend on it.  In exact arithmetic two triangles that are not
+ * coplanar intersect exactly when an edge of one pierces the other; coplanar pairs (det == 0) are never reported; the test is not
+ * watertight (passes near an edge or a vertex inherit §6.3's leaks); pairs that share a vertex or an edge get whatever the arithmetic
+ * gives, deterministically; a query triangle without area still answers as its three segments through bits 0-2, which are, given
+ * cand, exactly membership in hits() of rt_count_ray_hits_device for the ray (o, d, tmax = 1).
+ *   rt_count_overlaps_device: count_out_dev[i] (n i32, may be NULL) = |overlaps(i)|; offsets_out_dev (n + 1 i64, may be NULL): [i] = the
+ * exclusive prefix sum of the counts, [n] = their total; at least one of the two is required.
+ *   rt_fill_overlaps_device: the overlaps of triangle i, sorted ascending by original triangle index, into elements [offsets_in_dev[i],
+ * offsets_in_dev[i + 1]) of tri_out_dev (i32) and edges_out_dev (i32: the mask), arrays of `capacity` elements; offsets_in_dev (n + 1
+ * i64) is read on the stream.  A triangle whose slice ends beyond the arrays (offsets[i + 1] > capacity) writes NOTHING; every other
+ * triangle's slice is complete and sorted: what a too small capacity leaves out never depends on the tree.  The caller sees
+ * offsets[n] > capacity, grows the arrays and calls this step again.  The step is memory-safe against offsets that it did not make:
+ * triangle i writes its entry number j only while 0 <= offsets[i] and offsets[i] + j < offsets[i + 1] <= capacity; a slice shorter
+ * than its triangle's list keeps the entries with the lowest indices and the others are counted in slice_overflow, which is 0
+ * whenever the offsets are the count step's for the same triangles and mesh.  capacity == 0: tri_out_dev / edges_out_dev may be NULL,
+ * nothing is written.
+ *   rt_list_overlaps_device is exactly rt_count_overlaps_device(..., count_out_dev, offsets_out_dev) followed by
+ * rt_fill_overlaps_device(..., offsets_out_dev, capacity, tri_out_dev, edges_out_dev); everything that can refuse either step - and
+ * the first-use allocations of both - comes before the first step is enqueued, so a refused call has written nothing.
+ * A query triangle with a non-finite coordinate, or a coordinate beyond 32 x max(1, largest |vertex coordinate| of the mesh), is not
+ * walked: count_out = RT_RAY_INVALID, it adds 0 to the offsets, writes no entry, and is counted in invalid_triangles.  A list is built
+ * by insertion into its slice, O(k^2) for k entries: meant for lists of tens to a few hundred.  Nothing beyond element n - 1 of
+ * count_out_dev, n of offsets_out_dev and capacity - 1 of the entry arrays is written.  The caller keeps all arrays alive until the
+ * stream has passed the call; lifetime rules against rt_set_mesh* are rt_render_pt_device's.  Works on every mesh (host-built single-
+ * and two-level, device-built, refitted, with surfaces); reads the mesh only, so a shared mesh stays shared.  Errors, all before
+ * anything is enqueued or written: RT_ERR_INVALID (a NULL context; a NULL (where not allowed), host or other-device pointer, an
+ * allocation shorter than n / n + 1 / capacity rows, n above 2^30, capacity above 2^40, count_traversal above 1, tune_refill_min above
+ * 64, tune_blocks_per_cu above 8, tune_lds_stack above 78, a mesh beyond 2^RT_PT_MAX_COORD_LOG2 (the domain at the head of this
+ * section)), RT_ERR_STATE (no mesh), RT_ERR_OOM (scratch: 8 bytes per triangle for the scan, shared with the other listing queries,
+ * grown by size class).  n == 0: RT_OK, nothing is done. */
+typedef struct rt_overlap_query_params {
+    uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_ray_query_params */
+    uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
+} rt_overlap_query_params;
+typedef struct rt_overlap_query_stats {
+    uint64_t triangles, invalid_triangles; /* the last call with n > 0: triangles asked, triangles answered RT_RAY_INVALID */
+    uint64_t overlaps;                     /* sum of |overlaps(i)| over the valid triangles */
+    uint64_t overlaps_written;             /* fill step: entries written into the entry arrays */
+    uint64_t incomplete_triangles;         /* fill step: triangles with overlaps whose slice did not fit (offsets[i + 1] > capacity): nothing written */
+    uint64_t slice_overflow;               /* fill step: overlaps beyond the length of their triangle's slice; 0 with the count step's offsets */
+    uint64_t nodes_visited, tris_tested;   /* count_traversal = 1 only: node records fetched, triangle records fetched, over all walks of the call */
+    uint32_t stack_overflow;               /* must be 0 */
+    uint32_t launches;                     /* kernel launches of that call: 1 per walk, 3 for the scan */
+    float ms;                              /* HIP-event time from the first to the last launch of the call */
+} rt_overlap_query_stats;
+int rt_default_overlap_query_params(rt_overlap_query_params* p);
+int rt_count_overlaps_device(rt_ctx* ctx, const void* tris_dev, uint32_t n, const rt_overlap_query_params* params /* NULL = defaults */,
+                             void* count_out_dev /* may be NULL */, void* offsets_out_dev /* may be NULL */);
+int rt_fill_overlaps_device(rt_ctx* ctx, const void* tris_dev, uint32_t n, const rt_overlap_query_params* params /* NULL = defaults */,
+                            const void* offsets_in_dev, uint64_t capacity, void* tri_out_dev, void* edges_out_dev);
+int rt_list_overlaps_device(rt_ctx* ctx, const void* tris_dev, uint32_t n, const rt_overlap_query_params* params /* NULL = defaults */,
+                            void* count_out_dev /* may be NULL */, void* offsets_out_dev, uint64_t capacity, void* tri_out_dev,
+                            void* edges_out_dev);
+int rt_get_overlap_query_stats(rt_ctx* ctx, rt_overlap_query_stats* stats); /* synchronises the stream; the last call */
 /* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */

@@ -108,7 +108,7 @@ RAY_MISS, RAY_INVALID = -1, -2  # RT_RAY_MISS, RT_RAY_INVALID
 
 
 _TUNE_AND_COUNT = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
-                   ("count_traversal", C.c_uint32)]  # rt_point / side / hit / neighbor_query_params alike
+                   ("count_traversal", C.c_uint32)]  # rt_point / side / hit / neighbor / overlap_query_params alike
 
 
 class PointQueryParams(C.Structure):  # rt_point_query_params
@@ -158,6 +158,19 @@ class NeighborQueryParams(C.Structure):  # rt_neighbor_query_params
 class NeighborQueryStats(C.Structure):  # rt_neighbor_query_stats
     _fields_ = [("points", C.c_uint64), ("invalid_points", C.c_uint64), ("neighbors", C.c_uint64), ("neighbors_written", C.c_uint64),
                 ("incomplete_points", C.c_uint64), ("slice_overflow", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
+                ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class OverlapQueryParams(C.Structure):  # rt_overlap_query_params
+    _fields_ = _TUNE_AND_COUNT
+
+
+class OverlapQueryStats(C.Structure):  # rt_overlap_query_stats
+    _fields_ = [("triangles", C.c_uint64), ("invalid_triangles", C.c_uint64), ("overlaps", C.c_uint64), ("overlaps_written", C.c_uint64),
+                ("incomplete_triangles", C.c_uint64), ("slice_overflow", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
                 ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
 
     def as_dict(self):
@@ -238,6 +251,11 @@ PROTOTYPES = {
     "rt_fill_neighbors_device": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint32, C.POINTER(NeighborQueryParams), _vp, C.c_uint64, _vp, _vp]),
     "rt_list_neighbors_device": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint32, C.POINTER(NeighborQueryParams), _vp, _vp, C.c_uint64, _vp, _vp]),
     "rt_get_neighbor_query_stats": (C.c_int, [_vp, C.POINTER(NeighborQueryStats)]),
+    "rt_default_overlap_query_params": (C.c_int, [C.POINTER(OverlapQueryParams)]),
+    "rt_count_overlaps_device": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(OverlapQueryParams), _vp, _vp]),
+    "rt_fill_overlaps_device": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(OverlapQueryParams), _vp, C.c_uint64, _vp, _vp]),
+    "rt_list_overlaps_device": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(OverlapQueryParams), _vp, _vp, C.c_uint64, _vp, _vp]),
+    "rt_get_overlap_query_stats": (C.c_int, [_vp, C.POINTER(OverlapQueryStats)]),
     "rt_trace_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32)]),
     "rt_trace_rays_counted": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32), _u32p]),
 }

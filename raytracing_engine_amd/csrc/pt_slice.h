@@ -1,7 +1,8 @@
 // pt_slice.h — path B, device side: what the kernels of the listing queries share beside their loop - the sorted slice that a lane
 // keeps in global memory (insert_hit), where that slice lies (open_slice), the count step's answer for an item that is not walked
 // (write_count) and the wave totals (add_listing_totals).  Used by the all-hits ray queries (pt_hit_query.hip: keys are t) and by the
-// neighbour queries (pt_neighbor_query.hip: keys are d2).  Every function here left the kernels' object code as it was; the sink's
+// neighbour queries (pt_neighbor_query.hip: keys are d2); the overlap queries (pt_overlap_query.hip) keep (index, mask) pairs with
+// insert_pair and share the rest.  Every function here left the kernels' object code as it was; the sink's
 // count and its written / incomplete / beyond accounting did not and stay in the kernels (profiles/refactor_listing.txt).
 #pragma once
 #include "pt_queue.h"
@@ -68,6 +69,27 @@ __device__ __forceinline__ void add_listing_totals(unsigned long long* stats, ui
         add_wave_total(&stats[LQ_STAT_TRIS], tc.tris, lane);
     }
     if (tc.overflow) atomicOr((unsigned int*)&stats[LQ_STAT_OVERFLOW], 1u);
+}
+
+// The overlap queries' slice (pt_overlap_query.hip): pairs (id, word) in ascending id order, ids distinct.  insert_hit's protocol
+// with the id as the only key: the slice holds the min(found, room) smallest ids met so far, larger entries move up by one, with
+// the slice full its last entry falls off (or the new pair, if its id is no smaller).  Writes only elements below room.
+__device__ __forceinline__ void insert_pair(int* ids, int* words, uint32_t room, uint32_t found, int id, int word) {
+    uint32_t j = found < room ? found : room;  // entries held
+    if (j == room) {
+        if (room == 0u) return;
+        if (!(id < ids[room - 1u])) return;
+        j = room - 1u;
+    }
+    while (j > 0u) {
+        const int ip = ids[j - 1u];
+        if (!(ip > id)) break;
+        ids[j] = ip;
+        words[j] = words[j - 1u];
+        j--;
+    }
+    ids[j] = id;
+    words[j] = word;
 }
 
 }  // namespace rt

@@ -1,8 +1,8 @@
 // rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14),
-// sides (§6.15), all hits (§6.16), neighbours (§6.17) and the attribute variants of the first two (§6.18).
+// sides (§6.15), all hits (§6.16), neighbours (§6.17), the attribute variants of the first two (§6.18) and overlaps (§6.20).
 // A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here: the
 // parameter checks and the prologue of an entry (enter_query), the plan and the enqueue (prepare_query, run_query), the read-back.
-// The listing kinds - all hits, neighbours - are a description each (HitKind, NeighborKind); their protocol of a count step, a fill
+// The listing kinds - all hits, neighbours, overlaps - are a description each (HitKind, NeighborKind, OverlapKind); their protocol of a count step, a fill
 // step or both in one call is listing_call, and their read-back is listing_stats.
 #include <algorithm>
 
@@ -226,13 +226,16 @@ int run_sides(Ctx* c, const rt::SideQuery& q, const rt_side_query_params& prm, c
     return RT_OK;
 }
 
-// ---- the listing kinds: all hits and neighbours.  The kinds' own array checks, then what they are to the shared protocol ----
+// ---- the listing kinds: all hits, neighbours and overlaps.  The kinds' own array checks, then what they are to the shared protocol ----
 struct RaySource {
     const void *origins, *dirs, *tmax;
 };
 struct PointSource {
     const void *points, *rmax;
     float rmax_all;
+};
+struct TriSource {
+    const void* tris;
 };
 
 int prepare_hits(Ctx* c, const RaySource& src, uint32_t n, const rt_hit_query_params& prm, rt::HitQuery* q, QueryPlan* plan) {
@@ -266,6 +269,20 @@ int prepare_neighbors(Ctx* c, const PointSource& src, uint32_t n, const rt_neigh
     return prepare_query(c, c->pt.neighbor_query.qs, n, prm, mesh.stack_need, plan);
 }
 
+// the caller's triangles: nine floats each
+int prepare_overlaps(Ctx* c, const TriSource& src, uint32_t n, const rt_overlap_query_params& prm, rt::OverlapQuery* q, QueryPlan* plan) {
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, src.tris, (size_t)n * 36, "tris_dev")) return rc;
+    *q = rt::OverlapQuery{};
+    q->tris = static_cast<const float*>(src.tris);
+    q->n = n;
+    q->reach = rt::kCameraReach * mesh.maxabs;
+    // a group walk like the neighbours': one pending sibling group per level
+    if (int rc = prepare_query(c, c->pt.overlap_query.qs, n, prm, mesh.stack_need, plan)) return rc;
+    plan->grid = std::min<uint32_t>(plan->grid, (uint32_t)c->n_cus * (uint32_t)rt::kOverlapWaves);  // what the kernel's register budget keeps resident
+    return RT_OK;
+}
+
 struct HitKind {
     using Source = RaySource;
     using Query = rt::HitQuery;
@@ -290,6 +307,20 @@ struct NeighborKind {
     static constexpr const char *count_range = "rt.path_b.count_neighbors", *fill_range = "rt.path_b.fill_neighbors", *key_name = "dist_out_dev";
     static constexpr auto items = &Stats::points, invalid = &Stats::invalid_points, found = &Stats::neighbors, written = &Stats::neighbors_written,
                           incomplete = &Stats::incomplete_points;
+};
+
+struct OverlapKind {  // the second entry array holds the edge masks (i32), keyed "edges_out_dev"
+    using Source = TriSource;
+    using Query = rt::OverlapQuery;
+    using Params = rt_overlap_query_params;
+    using Stats = rt_overlap_query_stats;
+    static constexpr auto prepare = prepare_overlaps;
+    static constexpr auto launch = rt::launch_pt_query_overlaps;
+    static constexpr auto state = &rt::PtData::overlap_query;
+    static constexpr auto stats = &rt::PtData::overlap_query_stats;
+    static constexpr const char *count_range = "rt.path_b.count_overlaps", *fill_range = "rt.path_b.fill_overlaps", *key_name = "edges_out_dev";
+    static constexpr auto items = &Stats::triangles, invalid = &Stats::invalid_triangles, found = &Stats::overlaps, written = &Stats::overlaps_written,
+                          incomplete = &Stats::incomplete_triangles;
 };
 
 // ---- the listing protocol: the count step (walk, then the scan into offsets_out) and the fill step ----
@@ -359,7 +390,7 @@ int run_fill(Ctx* c, typename K::Query q, const typename K::Params& prm, const Q
     rt::ListingState& st = c->pt.*K::state;
     q.offsets = static_cast<const long long*>(offsets);
     q.capacity = (long long)capacity;
-    q.key_out = static_cast<float*>(key_out);
+    q.key_out = static_cast<decltype(q.key_out)>(key_out);  // f32 keys, or the overlaps' i32 masks: four bytes an entry either way
     q.tri_out = static_cast<int*>(tri_out);
     const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
         return K::launch(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, true, head, stats + rt::LQ_STEP_WORDS, grid, sk, refill_min);
@@ -445,7 +476,8 @@ namespace rt {
 void query_free(Ctx* c) {
     c->pt.d_list_scan.reset();
     c->pt.list_scan_words = 0;
-    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query.qs, &c->pt.neighbor_query.qs}) {
+    for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query.qs, &c->pt.neighbor_query.qs,
+                           &c->pt.overlap_query.qs}) {
         qs->block.reset();
         for (hipEvent_t& e : qs->ev) {
             if (e) (void)hipEventDestroy(e);
@@ -611,5 +643,23 @@ int rt_list_neighbors_device(rt_ctx* ctx, const void* points, const void* rmax, 
 }
 
 int rt_get_neighbor_query_stats(rt_ctx* ctx, rt_neighbor_query_stats* stats) { return listing_stats<NeighborKind>(ctx, stats); }
+
+int rt_default_overlap_query_params(rt_overlap_query_params* p) { return default_params(p); }
+
+int rt_count_overlaps_device(rt_ctx* ctx, const void* tris, uint32_t n, const rt_overlap_query_params* prm, void* count_out, void* offsets_out) {
+    return listing_call<OverlapKind>(ctx, {tris}, n, prm, 1u, count_out, offsets_out, nullptr, 0, nullptr, nullptr);
+}
+
+int rt_fill_overlaps_device(rt_ctx* ctx, const void* tris, uint32_t n, const rt_overlap_query_params* prm, const void* offsets_in, uint64_t capacity, void* tri_out,
+                            void* edges_out) {
+    return listing_call<OverlapKind>(ctx, {tris}, n, prm, 2u, nullptr, nullptr, offsets_in, capacity, edges_out, tri_out);
+}
+
+int rt_list_overlaps_device(rt_ctx* ctx, const void* tris, uint32_t n, const rt_overlap_query_params* prm, void* count_out, void* offsets_out, uint64_t capacity,
+                            void* tri_out, void* edges_out) {
+    return listing_call<OverlapKind>(ctx, {tris}, n, prm, 3u, count_out, offsets_out, nullptr, capacity, edges_out, tri_out);
+}
+
+int rt_get_overlap_query_stats(rt_ctx* ctx, rt_overlap_query_stats* stats) { return listing_stats<OverlapKind>(ctx, stats); }
 
 }  // extern "C"

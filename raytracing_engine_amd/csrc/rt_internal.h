@@ -280,7 +280,24 @@ struct NeighborQuery {
     uint32_t n;
     float reach;  // |component| limit: kCameraReach x the mesh's maxabs
 };
-// Counters of a listing query (all hits, neighbours): one set per step (the fill step's LQ_STEP_WORDS words behind the count step's),
+// rt_count_overlaps_device / rt_fill_overlaps_device: the query triangles of one step and where its answers go.  Triangle i is queue entry i.
+struct OverlapQuery {
+    const float* tris;  // n x 9: the three vertices, rt_set_mesh's layout
+    // the count step
+    int* count_out;               // n, or nullptr
+    unsigned long long* count64;  // n (the scan's input column: max(count, 0)), or nullptr
+    // the fill step
+    const long long* offsets;  // n + 1
+    long long capacity;        // elements of key_out / tri_out
+    int* key_out;              // the edge mask of each listed triangle
+    int* tri_out;
+    uint32_t n;
+    float reach;  // |coordinate| limit: kCameraReach x the mesh's maxabs
+};
+// Waves per SIMD pt_query_overlaps is bounded to, = its workgroups per CU: at the neighbours' 8 (64 VGPRs) the six segment tests spill
+// 9 - 23 registers to scratch, at 6 (75 - 79 VGPRs) nothing does (profiles/overlap_queries.txt); the host caps the persistent grid to it.
+constexpr int kOverlapWaves = 6;
+// Counters of a listing query (all hits, neighbours, overlaps): one set per step (the fill step's LQ_STEP_WORDS words behind the count step's),
 // so that the two launches of a list call report side by side.  FOUND: hits / neighbours met.
 enum { LQ_STAT_INVALID = 0, LQ_STAT_OVERFLOW = 1, LQ_STAT_NODES = 2, LQ_STAT_TRIS = 3, LQ_STAT_FOUND = 4, LQ_STAT_WRITTEN = 5, LQ_STAT_INCOMPLETE = 6,
        LQ_STAT_SLICE_OVERFLOW = 7, LQ_STEP_WORDS = 8, LQ_STAT_WORDS = 2 * LQ_STEP_WORDS };
@@ -377,15 +394,17 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     DevPtr<uint32_t> d_ctr;
     DevPtr<unsigned long long> d_stats;  // PT_STAT_WORDS words
     rt_pt_stats stats{};
-    // the five query kinds (rays, closest points, sides, all hits, neighbours): what is in flight, and the statistics of the last query of each kind
+    // the six query kinds (rays, closest points, sides, all hits, neighbours, overlaps): what is in flight, and the statistics of the last query of each kind
     // (rays: the 2 KiB octant table, two spill halves as the frames hold; the others: no table, one set of columns)
     QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u}, side_query{SQ_STAT_WORDS, "side-query", 0u, 1u};
     ListingState hit_query{"hit-query"}, neighbor_query{"neighbor-query"};  // rt_count / fill / list_ray_hits_device, rt_count / fill / list_neighbors_device
+    ListingState overlap_query{"overlap-query"};                            // rt_count / fill / list_overlaps_device
     rt_ray_query_stats ray_query_stats{};
     rt_point_query_stats point_query_stats{};
     rt_side_query_stats side_query_stats{};
     rt_hit_query_stats hit_query_stats{};
     rt_neighbor_query_stats neighbor_query_stats{};
+    rt_overlap_query_stats overlap_query_stats{};
     // the listing kinds' scan: the 64-bit count column (n + 1), the scan's tile sums and its total; grows by size class, first use only
     DevPtr<unsigned long long> d_list_scan;
     size_t list_scan_words = 0;
@@ -468,7 +487,7 @@ int launch_detile(Ctx* c, const float* tiles, uint32_t n_ranks, uint32_t tiles_p
 int launch_to_rgba8(Ctx* c, const float* rgb, uint8_t* rgba, uint64_t n_pixels);
 
 // path_b.hip (generate, shade, scatter_surfaces, resolve), pt_trace.hip (trace, trace_fused, pool_lds_bytes, trace_rays, query_rays), pt_packet.hip (trace_packet),
-// pt_point_query.hip (query_points), pt_side_query.hip (query_sides), pt_hit_query.hip (query_hits), pt_neighbor_query.hip (query_neighbors): every unit ends with the launchers of its own kernels
+// pt_point_query.hip (query_points), pt_side_query.hip (query_sides), pt_hit_query.hip (query_hits), pt_neighbor_query.hip (query_neighbors), pt_overlap_query.hip (query_overlaps): every unit ends with the launchers of its own kernels
 int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* queue, uint32_t* ctr);
 int launch_pt_trace(Ctx* c, hipStream_t stream, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,
@@ -503,6 +522,9 @@ int launch_pt_query_hits(Ctx* c, const PtScene& sc, const HitQuery& q, bool coun
 // the same two steps of a neighbour query
 int launch_pt_query_neighbors(Ctx* c, const PtScene& sc, const NeighborQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
                               const StackCfg& sk, uint32_t refill_min);
+// the same two steps of an overlap query (pt_overlap_query.hip)
+int launch_pt_query_overlaps(Ctx* c, const PtScene& sc, const OverlapQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                             const StackCfg& sk, uint32_t refill_min);
 void pt_free(Ctx* c);
 void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block and events
 

@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
+from ._lib import (Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, OverlapQueryParams, OverlapQueryStats, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
                    RtError, SideQueryParams, SideQueryStats, Stats)
 
 # src/main.rs:343-364
@@ -459,7 +459,7 @@ class Renderer:
         self._device_ints(t, name, n, "int64")
 
     def _query_tune(self, params, tune, method):
-        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors) into its parameter struct;
+        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors / count_overlaps / list_overlaps) into its parameter struct;
         TypeError for any other keyword."""
         for k, v in tune.items():
             if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
@@ -677,12 +677,13 @@ class Renderer:
         return self._query_stats(SideQueryStats(), "rt_get_side_query_stats")
 
     # A listing kind: the stem of the library's rt_{count,fill,list}_<stem>_device and of count_<stem> / list_<stem> here, its
-    # parameter struct, the key's name, what it lists
+    # parameter struct, the key's name, what it lists; the overlaps' "key" is the int32 edge mask, and it comes behind tri
     _RAY_HITS = ("ray_hits", HitQueryParams, "t", "hits")
     _NEIGHBORS = ("neighbors", NeighborQueryParams, "dist", "neighbours")
+    _OVERLAPS = ("overlaps", OverlapQueryParams, "edges", "overlaps")
 
     def _count_listing(self, kind, src, n, dev, out, sync, count_traversal, tune):
-        """count_ray_hits / count_neighbors on the checked source arguments `src` of n items."""
+        """count_ray_hits / count_neighbors / count_overlaps on the checked source arguments `src` of n items."""
         import torch
 
         stem, params = kind[:2]
@@ -694,10 +695,14 @@ class Renderer:
         return counts
 
     def _list_listing(self, kind, src, n, dev, capacity, out, sync, tune):
-        """list_ray_hits / list_neighbors on the checked source arguments `src` of n items: (offsets, key, tri, counts)."""
+        """list_ray_hits / list_neighbors on the checked source arguments `src` of n items: (offsets, key, tri, counts); list_overlaps:
+        (offsets, tri, edges, counts), the order of the library's arguments too."""
         import torch
 
         stem, params, key, what = kind
+        tri_first = kind is self._OVERLAPS
+        key_dtype = torch.int32 if tri_first else torch.float32
+        order = (lambda k, t: (t, k)) if tri_first else (lambda k, t: (k, t))  # (key, tri) as the caller and the library have them
         p = params()
         self._query_tune(p, tune, f"list_{stem}")
         if capacity is None:
@@ -707,30 +712,31 @@ class Renderer:
             counts = torch.empty(n, dtype=torch.int32, device=dev)
             if n == 0:
                 offsets.zero_()
-                return offsets, torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), counts
+                return (offsets,) + order(torch.empty(0, dtype=key_dtype, device=dev), torch.empty(0, dtype=torch.int32, device=dev)) + (counts,)
             self._query_call(sync, getattr(self._lib, f"rt_count_{stem}_device"), *src, n, C.byref(p), counts, offsets)
             self.synchronize()  # the one host synchronisation: the total decides the allocation
             total = int(offsets[n].item())
-            keys = torch.empty(total, dtype=torch.float32, device=dev)
+            keys = torch.empty(total, dtype=key_dtype, device=dev)
             tri = torch.empty(total, dtype=torch.int32, device=dev)
-            self._query_call(sync, getattr(self._lib, f"rt_fill_{stem}_device"), *src, n, C.byref(p), offsets, total, keys if total else None, tri if total else None)
-            return offsets, keys, tri, counts
+            self._query_call(sync, getattr(self._lib, f"rt_fill_{stem}_device"), *src, n, C.byref(p), offsets, total, *order(keys if total else None, tri if total else None))
+            return (offsets,) + order(keys, tri) + (counts,)
         capacity = int(capacity)
         if capacity < 0:
             raise ValueError(f"capacity must be >= 0, got {capacity}")
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 4):
-            raise ValueError(f"out must be (offsets, {key}, tri, counts)")
+            raise ValueError("out must be (offsets, tri, edges, counts)" if tri_first else f"out must be (offsets, {key}, tri, counts)")
         offsets, keys, tri, counts = out if out is not None else (None, None, None, None)
+        keys, tri = order(keys, tri)  # (its own inverse)
         offsets = self._query_out(offsets, "out offsets", n + 1, torch.int64, dev)
-        keys = self._query_out(keys, f"out {key}", capacity, torch.float32, dev)
+        keys = self._query_out(keys, f"out {key}", capacity, key_dtype, dev)
         tri = self._query_out(tri, "out tri", capacity, torch.int32, dev)
         counts = self._query_out(counts, "out counts", n, torch.int32, dev)
         if n == 0:
             offsets.zero_()
-            return offsets, keys, tri, counts
-        self._query_call(sync, getattr(self._lib, f"rt_list_{stem}_device"), *src, n, C.byref(p), counts, offsets, capacity, keys if capacity else None,
-                         tri if capacity else None)
-        return offsets, keys, tri, counts
+            return (offsets,) + order(keys, tri) + (counts,)
+        self._query_call(sync, getattr(self._lib, f"rt_list_{stem}_device"), *src, n, C.byref(p), counts, offsets, capacity,
+                         *order(keys if capacity else None, tri if capacity else None))
+        return (offsets,) + order(keys, tri) + (counts,)
 
     def count_ray_hits(self, origins, dirs, tmax=None, out=None, sync=True, count_traversal=False, **tune):
         """How many triangles of the current mesh does each ray pass through?  (rt_count_ray_hits_device)  origins, dirs,
@@ -802,6 +808,41 @@ class Renderer:
         neighbors_written, incomplete_points, slice_overflow, nodes_visited, tris_tested (count_traversal=True only), stack_overflow,
         launches, ms."""
         return self._query_stats(NeighborQueryStats(), "rt_get_neighbor_query_stats")
+
+    def count_overlaps(self, tris, out=None, sync=True, count_traversal=False, **tune):
+        """How many triangles of the current mesh does each query triangle intersect?  (rt_count_overlaps_device)
+        tris: a float32 torch tensor on this renderer's device, contiguous, (n, 9), (n, 3, 3) or flat: the three vertices of each
+        query triangle.  A mesh triangle counts when its box meets the query triangle's and an edge of one pierces the other (fp32,
+        csrc/tri_overlap.h; coplanar pairs never count, the test is not watertight).  Returns int32 counts; invalid triangles (a
+        non-finite coordinate, one beyond 32 x the mesh's largest |coordinate|) get RAY_INVALID = -2.  out: the tensor to fill instead
+        of a new one.  sync as for query_rays.  count_traversal=True: overlap_query_stats() reports nodes_visited / tris_tested.  tune:
+        tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_overlap_query_params."""
+        flat, n = self._tri_rows(tris)
+        return self._count_listing(self._OVERLAPS, (flat,), n, tris.device, out, sync, count_traversal, tune)
+
+    def list_overlaps(self, tris, capacity=None, out=None, sync=True, **tune):
+        """Every triangle of the current mesh that each query triangle intersects.  (rt_list_overlaps_device)  tris as
+        for count_overlaps.  Returns (offsets, tri, edges, counts): int64 offsets (n + 1; [n] = the number of overlaps of all query
+        triangles), and the overlaps of query triangle i in tri[offsets[i]:offsets[i + 1]] (int32 original triangle indices, ascending)
+        and edges[...] (int32 masks: bits 0-2 = the query triangle's edges A0A1, A1A2, A2A0 that pierce the mesh triangle, bits 3-5 =
+        the mesh triangle's edges v0v1, v1v2, v0v2 that pierce the query triangle); int32 counts as count_overlaps returns them.
+        capacity, out (then (offsets, tri, edges, counts)), sync and tune as for list_neighbors; overlap_query_stats() reports."""
+        flat, n = self._tri_rows(tris)
+        return self._list_listing(self._OVERLAPS, (flat,), n, tris.device, capacity, out, sync, tune)
+
+    def _tri_rows(self, tris):
+        """(the tensor the library reads, n) of the query triangles `tris`: (n, 9), (n, 3, 3) or flat."""
+        import torch
+
+        if isinstance(tris, torch.Tensor) and tris.dim() == 3 and tuple(tris.shape[1:]) == (3, 3) and tris.is_contiguous():
+            tris = tris.view(-1, 9)
+        return tris, self._device_rows(tris, "tris", 9)
+
+    def overlap_query_stats(self):
+        """rt_overlap_query_stats of the last overlap call as a dict (waits for it): triangles, invalid_triangles, overlaps,
+        overlaps_written, incomplete_triangles, slice_overflow, nodes_visited, tris_tested (count_traversal=True only; records fetched),
+        stack_overflow, launches, ms."""
+        return self._query_stats(OverlapQueryStats(), "rt_get_overlap_query_stats")
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
         """Test hook (query_rays is the product entry): closest hit (t, original triangle index) or occlusion flags for a ray batch;
