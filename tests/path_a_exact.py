@@ -1,0 +1,482 @@
+"""Closed-form float64 sphere geometry that path A's depth pyramid and shading are held to, with none of the march loops.
+
+Test helper (imported by tests/test_path_a_exact_host.py and tests/test_gpu_path_a_exact.py); not a conftest, no fixtures.
+numpy float64 only: nothing from `oracle`, nothing from librt_amd at module level.  Written from the specification (include/rt_abi.h,
+oracle/oracle.h, DESIGN.md sections 4-5), not from oracle_a.c / path_a.hip, which mirror each other line by line and would share any
+misreading.  It covers the reference as shipped: march algorithm 3, no repeat(), no mirror or transmission chains, 1 spp, jitter 0.
+There is no stepping loop over a ray anywhere in this file: the scene is at most 8 spheres, so what the marches approximate has a
+closed form, and what they leave open (WHERE a march samples) is held in an interval.
+
+DEPTH, depth_bands(frame, i).  Texel (gx, gy) of level i looks along u = normalize(rotate(rot, ((2gx+1) isx - 1) ratio_x, 1,
+((2gy+1) isy - 1) ratio_y)), isx, isy = 2^(count-1-i) / view, starts at o = pos + len0 u with len0 = 1 at level 0 and the frame's OWN
+parent texel (gx>>1, gy>>1) above, and marches the relative distance t >= 0 with f(t) = min_k |o + t u - c_k| - r_k against the cone
+radius rho(t) = (t + 1) tau, tau = sqrt2 * 8 * isx (x only; relative t, both as the reference has them).  The cached distances of
+algorithm 3 are lower bounds of a 1-Lipschitz function and a cached value at or below the radius is refreshed, hence exact, so:
+    the march stops at the first SAMPLED s with f(s) <= rho(s), it never steps across a surface (f >= 0 on [0, s)), and returns
+    max(len0 + g(s), 0),  g(s) = s + max(f(s), 0) - rho(s);   otherwise it runs out at a relative length >= render_dist.
+Where it samples is not decided here.  Per sphere {t : f_k <= rho} is one quadratic, (1 - tau^2) t^2 + 2 (oc.u - tau (r + tau)) t
++ |oc|^2 - (r + tau)^2 <= 0; the feasible set F is the union of those touch sets cut at the first surface crossing a (the usual
+ray/sphere root; 0 when o is inside a sphere) and at render_dist.  The band is [len0 + min_F g, len0 + max_F g], clamped at 0: g is
+sampled at N_SAMPLE points of every interval of F and widened by its Lipschitz constant (2 + tau) times half the spacing, and cut by
+two closed forms that hold on any interval I of sphere k: g >= s - rho(s) (linear) and g <= s - rho(s) + max(f_k(s), 0) (convex, so
+its maximum is at an end of I).  A texel is right when
+    it reports a hit (< render_dist) and lies in the band;  or it reports a miss (>= render_dist) and either lies in the band or the
+    centre line crosses no surface before render_dist AND the value is >= len0 + render_dist (a march that ran out);
+so an empty F forces a miss, a crossed surface forbids one, and a grazing ray whose cone touches while its centre line misses may
+report either.  In every tested scene a texel whose parent missed stays a miss (`far_bad` counts the others); the tests assert that too.
+
+COLOUR, shade_bands(frame).  Pixel (px, py) with own finest-level depth d < render_dist: step through ((px + 0.5) 2 / view - 1) ratio,
+P = pos + d step, nearest sphere by strict '<' (first wins), then DESIGN.md section 5's formula in float64: cam_fall, normal,
+normal_fall, per light light_dir, light_dist, light_fall, diffuse, reflect, pow (0 for a base <= 0).  Where the two smallest SDFs at P
+differ by less than AMBIGUOUS the pixel is ambiguous and left out.  The shadow factor is not marched.  The shadow march walks
+o' = P + light_dir along light_dir over t in [0, end), end = light_dist (THE CAP: every sampled value is min(end, f), which a reader
+of the formula alone gets wrong for a light nearer than 1 to open space), always samples t = 0, exactly, and steps by at most
+f + ray_radius.  So with m* = min of f over the segment (per sphere the closest approach clamped to the segment) and f0 = f(0):
+    min(end, f0) <= ray_radius                                            soft = 0    (the first sample already stops it)
+    the segment crosses a surface at some a <= end - 2 ray_radius         soft = 0    (a sample lands in [a, a + ray_radius], f <= ray_radius)
+    otherwise   soft in [lo, hi],  hi = min(1, end, max(f0, 0)),  lo = min(m*, end, 1) if m* > ray_radius else 0.
+RGB is monotone in every soft, so the pixel lies between RGB(lo) and RGB(hi) component-wise; it is PINNED when that interval is
+narrower than PINNED_WIDTH (every light blocked, or its minimum attained at t = 0, or >= end or 1).
+
+THE CONSTANTS are measured on the CPU against oracle A, never on a GPU frame:  python tests/path_a_exact.py  renders every frame of
+the two test files (FRAMES and GPU_ONLY_FRAMES below) with the oracle and prints, with no tolerance at all, the largest distance of an
+oracle texel / pixel outside its band.  Measured by that command:
+    depth, relative to 1 + depth:  3.109e-07  (room_turned 200 x 120; about 160 texels of all frames leave their band at all, by fp32 rounding)
+    rgb:                           5.471e-06  (random_8_8 96 x 64: shine 30, eight lights)
+Constants = four times the measurement, to cover powf and the fp32 position the kernels shade at:
+    EPS_DEPTH = 1.244e-06      EPS_RGB = 2.188e-05   (under the project's 1e-4 bar for RGB)
+A roll by one texel, a depth moved by one cone radius, a wrong parent, swapped materials, a dropped light or exchanged fall-offs move
+a frame by 1e-2 and more (tests/test_path_a_exact_host.py shows each rejected), so the margin costs no power.
+Shares of the hit pixels, same command: ambiguous 0 - 0.37 %; pinned 57 - 100 % in the open scenes and 24 - 49 % in the room; median
+width of the room's RGB intervals 0.0004 - 0.045.
+"""
+import sys
+
+import numpy as np
+
+SQRT2_8 = float(np.float32(1.4142135)) * 8.0  # compute.glsl:75 as the fp32 code holds it
+N_SAMPLE = 33
+AMBIGUOUS = 1e-3
+PINNED_WIDTH = 1e-6
+# python tests/path_a_exact.py  (see the module docstring)
+EPS_DEPTH = 1.244e-06
+EPS_RGB = 2.188e-05
+
+
+# ---- inputs --------------------------------------------------------------------------------------------------------------------
+def level_count(width):
+    """floor(log2(width / 8)) + 1, at least 1, at most 9."""
+    q = int(width) // 8
+    return min(max(q.bit_length(), 1), 9)
+
+
+def level_dims(width, height, count, level):
+    """(w, h) of pyramid level `level`: ceil(res * 2^level / (4 << count)) * 8."""
+    den = 4 << count
+    return -(-(width << level) // den) * 8, -(-(height << level) // den) * 8
+
+
+def parse_scene(raw):
+    """The 656-byte scene -> float64 arrays of the live objects, their materials (material i belongs to object i) and lights."""
+    raw = bytes(raw)
+    assert len(raw) == 656
+    n_mat, n_obj, n_light, _ = np.frombuffer(raw, np.uint32, 4)
+    mats = np.frombuffer(raw, np.float32, 64, 16).reshape(8, 8).astype(np.float64)
+    objs = np.frombuffer(raw, np.float32, 32, 16 + 256).reshape(8, 4).astype(np.float64)
+    lights = np.frombuffer(raw, np.float32, 64, 16 + 256 + 128).reshape(8, 8).astype(np.float64)
+    n_obj, n_light = int(n_obj), int(n_light)
+    return dict(c=objs[:n_obj, :3], r=objs[:n_obj, 3], color=mats[:n_obj, :3], shine=mats[:n_obj, 5], ambient=mats[:n_obj, 6],
+                lpos=lights[:n_light, :3], lcol=lights[:n_light, 4:7])
+
+
+class Frame:
+    """Everything the two band functions read: the scene, the view, the config scalars, and the frame's own levels and RGB."""
+
+    def __init__(self, scene, width, height, rot=(0, 0, 0, 1), pos=(0, 0, 0), ratio=None, render_dist=1000.0, cam_fall_off=0.01,
+                 light_fall_off=0.01, ray_radius=0.01, levels=None, rgb=None):
+        self.scene = parse_scene(scene)
+        self.w, self.h = int(width), int(height)
+        f32 = np.float32
+        if ratio is None:
+            ratio = (1.0, f32(1.0) * f32(height) / f32(width))
+        self.ratio = np.asarray(ratio, np.float32).astype(np.float64)
+        self.rot = np.asarray(rot, np.float32).astype(np.float64)
+        self.pos = np.asarray(pos, np.float32).astype(np.float64)
+        self.render_dist, self.cam_fall_off, self.light_fall_off, self.ray_radius = (float(f32(v)) for v in (render_dist, cam_fall_off, light_fall_off, ray_radius))
+        self.count = level_count(self.w)
+        self.levels = None if levels is None else [np.asarray(lv, np.float64) for lv in levels]
+        self.rgb = None if rgb is None else np.asarray(rgb, np.float64)
+        if self.levels is not None:
+            assert [lv.shape[::-1] for lv in self.levels] == [level_dims(self.w, self.h, self.count, i) for i in range(self.count)]
+
+    def on_screen(self, i):
+        """Texels of level i with a descendant inside the frame: the others are padding nothing reads."""
+        w, h = level_dims(self.w, self.h, self.count, i)
+        s = self.count - 1 - i
+        gy, gx = np.mgrid[0:h, 0:w]
+        return ((gx << s) < self.w) & ((gy << s) < self.h)
+
+
+def rotate(q, v):
+    """utilities.glsl:26-29: t = cross(q.xyz, v) + q.w v; v + 2 cross(q.xyz, t)."""
+    t = np.cross(q[:3], v) + q[3] * v
+    return v + 2.0 * np.cross(q[:3], t)
+
+
+def rays(fr, nx, ny):
+    """Unit directions through the normalised coordinates (nx, ny): normalize(rotate(rot, (nx ratio_x, 1, ny ratio_y)))."""
+    v = np.stack([nx * fr.ratio[0], np.ones_like(nx), ny * fr.ratio[1]], -1)
+    d = rotate(fr.rot, v)
+    return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+# ---- depth ---------------------------------------------------------------------------------------------------------------------
+def _touch_intervals(A, B, Cq):
+    """{t : A t^2 + 2 B t + Cq <= 0} as two intervals (lo, hi)[..., 2]; an empty one has lo > hi."""
+    inf = np.inf
+    D = B * B - A * Cq
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sq = np.sqrt(np.maximum(D, 0.0))
+        r1, r2 = (-B - sq) / A, (-B + sq) / A
+        lin = -Cq / (2.0 * B)
+    lo = np.full(A.shape + (2,), inf)
+    hi = np.full(A.shape + (2,), -inf)
+    pos, neg, zero = (A > 0) & (D >= 0), A < 0, A == 0
+    lo[..., 0] = np.where(pos, r1, lo[..., 0])
+    hi[..., 0] = np.where(pos, r2, hi[..., 0])
+    # A < 0: everything when there is no real root, otherwise outside the roots (r2 <= r1 there, dividing by a negative A)
+    every = neg & (D < 0)
+    out = neg & (D >= 0)
+    lo[..., 0] = np.where(every | out, -inf, lo[..., 0])
+    hi[..., 0] = np.where(every, inf, np.where(out, r2, hi[..., 0]))
+    lo[..., 1] = np.where(out, r1, lo[..., 1])
+    hi[..., 1] = np.where(out, inf, hi[..., 1])
+    # A == 0: 2 B t + Cq <= 0
+    zl = zero & (B > 0)
+    zg = zero & (B < 0)
+    ze = zero & (B == 0) & (Cq <= 0)
+    lo[..., 0] = np.where(zl | ze, -inf, np.where(zg, lin, lo[..., 0]))
+    hi[..., 0] = np.where(zl, lin, np.where(zg | ze, inf, hi[..., 0]))
+    return lo, hi
+
+
+def depth_bands(fr, i, texels=None, chunk=4096):
+    """depth_bands_chunk over blocks of `chunk` texels (bounds the working set)."""
+    w, h = level_dims(fr.w, fr.h, fr.count, i)
+    gy, gx = (a.ravel() for a in np.mgrid[0:h, 0:w]) if texels is None else texels
+    parts = [depth_bands_chunk(fr, i, (gy[k:k + chunk], gx[k:k + chunk])) for k in range(0, max(len(gy), 1), chunk)]
+    return {key: (np.concatenate([p[key] for p in parts]) if key != "tau" else parts[0]["tau"]) for key in parts[0]}
+
+
+def depth_bands_chunk(fr, i, texels):
+    """Bands of level i of fr (which carries its own levels).  texels: (gy, gx) index arrays.
+    Returns a dict of flat arrays over those texels: lo, hi (nan where F is empty), empty (F empty), crossed (the centre line crosses a
+    surface before render_dist), len0."""
+    gy, gx = texels
+    pw = float(1 << (fr.count - 1 - i))
+    isx, isy = pw / fr.w, pw / fr.h
+    tau = SQRT2_8 * isx
+    u = rays(fr, (2.0 * gx + 1.0) * isx - 1.0, (2.0 * gy + 1.0) * isy - 1.0)
+    len0 = np.ones(len(gx)) if i == 0 else fr.levels[i - 1][gy >> 1, gx >> 1]
+    o = fr.pos + len0[:, None] * u
+    c, r = fr.scene["c"], fr.scene["r"]
+    RD = fr.render_dist
+    oc = o[:, None, :] - c[None]                    # (T, n, 3)
+    b = (oc * u[:, None, :]).sum(-1)                # (T, n)
+    cc = (oc * oc).sum(-1)
+
+    # first surface crossing of the centre line
+    disc = b * b - (cc - r * r)
+    with np.errstate(invalid="ignore"):
+        root = -b - np.sqrt(np.maximum(disc, 0.0))
+    a_k = np.where(cc <= r * r, 0.0, np.where((disc >= 0) & (root >= 0), root, np.inf))
+    a = a_k.min(1)
+    cut = np.minimum(a, RD)
+
+    lo_k, hi_k = _touch_intervals(np.full_like(b, 1.0 - tau * tau), b - tau * (r + tau), cc - (r + tau) ** 2)
+    lo_k = np.maximum(lo_k, 0.0)
+    hi_k = np.minimum(hi_k, cut[:, None, None])
+
+    def f_at(idx, s):  # min_k |o + s u - c_k| - r_k for texels idx at relative distances s (len(idx), m)
+        p = oc[idx][:, None, :, :] + s[:, :, None, None] * u[idx][:, None, None, :]
+        return (np.sqrt((p * p).sum(-1)) - r).min(-1)
+
+    gmin = np.full(len(gx), np.inf)
+    gmax = np.full(len(gx), -np.inf)
+    frac = np.linspace(0.0, 1.0, N_SAMPLE)
+    for k in range(len(r)):
+        for j in range(2):
+            idx = np.nonzero(lo_k[:, k, j] <= hi_k[:, k, j])[0]
+            if not len(idx):
+                continue
+            l, hgh = lo_k[idx, k, j], hi_k[idx, k, j]
+            s = l[:, None] + (hgh - l)[:, None] * frac
+            g = s + np.maximum(f_at(idx, s), 0.0) - (s + 1.0) * tau
+            slack = (2.0 + tau) * (hgh - l) / (2.0 * (N_SAMPLE - 1))
+            # closed forms on this interval: g >= s - rho(s); g <= s - rho(s) + max(f_k(s), 0), convex
+            ends = np.stack([l, hgh], 1)
+            pk = oc[idx, k][:, None, :] + ends[:, :, None] * u[idx][:, None, :]
+            fk = np.sqrt((pk * pk).sum(-1)) - r[k]
+            lin = ends - (ends + 1.0) * tau
+            g_lo = np.maximum(g.min(1) - slack, lin.min(1))
+            g_hi = np.minimum(g.max(1) + slack, (lin + np.maximum(fk, 0.0)).max(1))
+            np.minimum.at(gmin, idx, g_lo)
+            np.maximum.at(gmax, idx, g_hi)
+    empty = ~np.isfinite(gmin)
+    with np.errstate(invalid="ignore"):
+        lo = np.where(empty, np.nan, np.maximum(len0 + gmin, 0.0))
+        hi = np.where(empty, np.nan, np.maximum(len0 + gmax, 0.0))
+    return dict(lo=lo, hi=hi, empty=empty, crossed=a < RD, len0=len0, gy=gy, gx=gx, tau=tau)
+
+
+def check_depth(fr, i, eps=None, texels=None, bands=None):
+    """Level i of fr against its bands, over the on-screen texels (or `texels`).  Returns dict(n, bad, excursion, far_bad, hits):
+    bad = texels that break a rule by more than eps (1 + depth); excursion = the largest distance outside a band relative to
+    1 + depth (inf for a rule with no distance: a forbidden or a forced miss); far_bad = texels whose parent missed and that do not."""
+    eps = EPS_DEPTH if eps is None else eps
+    if texels is None:
+        gy, gx = np.nonzero(fr.on_screen(i))
+    else:
+        gy, gx = texels
+    bd = bands if bands is not None else depth_bands(fr, i, (gy, gx))
+    v = fr.levels[i][gy, gx]
+    RD = fr.render_dist
+    with np.errstate(invalid="ignore"):
+        out = np.maximum(np.maximum(bd["lo"] - v, v - bd["hi"]), 0.0) / (1.0 + v)  # nan where F is empty
+    in_band = ~bd["empty"] & (out <= eps)
+    miss = v >= RD
+    # a march that ran out left the loop at a relative fp32 length >= render_dist; the one rounding of len0 + length is monotone
+    ran_out = miss & ~bd["crossed"] & (v >= (bd["len0"] + RD) * (1.0 - 2.0 ** -23))
+    ok = np.where(miss, in_band | ran_out, in_band)
+    exc = np.where(ok, 0.0, np.where(np.isfinite(out), out, np.inf))
+    far = bd["len0"] >= RD
+    return dict(n=len(v), bad=int(np.count_nonzero(~ok)), excursion=float(exc.max()) if len(v) else 0.0,
+                far_bad=int(np.count_nonzero(far & ~miss)), hits=int(np.count_nonzero(~miss)))
+
+
+def sample_texels(fr, i, limit=100_000, n=20_000, seed=1):
+    """The on-screen texels of level i, or a fixed-seed sample of n of them when there are more than `limit`."""
+    gy, gx = np.nonzero(fr.on_screen(i))
+    if len(gy) > limit:
+        pick = np.sort(np.random.default_rng(seed + i).choice(len(gy), n, replace=False))
+        gy, gx = gy[pick], gx[pick]
+    return gy, gx
+
+
+# ---- colour --------------------------------------------------------------------------------------------------------------------
+def _segment_min(o, d, end, c, r):
+    """min over t in [0, end] and spheres of |o + t d - c_k| - r_k for unit d: per sphere the closest approach clamped to the segment.
+    Also the first t in [0, end] with f <= 0 (inf when there is none).  o, d (P, 3); end (P,)."""
+    oc = o[:, None, :] - c[None]
+    b = (oc * d[:, None, :]).sum(-1)
+    cc = (oc * oc).sum(-1)
+    t = np.clip(-b, 0.0, end[:, None])
+    p = oc + t[..., None] * d[:, None, :]
+    m = (np.sqrt((p * p).sum(-1)) - r).min(1)
+    disc = b * b - (cc - r * r)
+    with np.errstate(invalid="ignore"):
+        root = -b - np.sqrt(np.maximum(disc, 0.0))
+    a = np.where(cc <= r * r, 0.0, np.where((disc >= 0) & (root >= 0), root, np.inf)).min(1)
+    f0 = (np.sqrt(cc) - r).min(1)
+    return m, np.where(a <= end, a, np.inf), f0
+
+
+def shade_bands(fr, pixels=None):
+    """RGB intervals of the pixels whose own finest-level depth is < render_dist.  Returns dict(py, px: the hit pixels; lo, hi (n, 3);
+    ambiguous, pinned (n,) bool; width (n,) = the largest component of hi - lo)."""
+    sc = fr.scene
+    depth = fr.levels[-1][:fr.h, :fr.w]
+    if pixels is None:
+        py, px = np.nonzero(depth < fr.render_dist)
+    else:
+        py, px = pixels
+        keep = depth[py, px] < fr.render_dist
+        py, px = py[keep], px[keep]
+    d = depth[py, px]
+    step = rays(fr, (px + 0.5) * 2.0 / fr.w - 1.0, (py + 0.5) * 2.0 / fr.h - 1.0)
+    P = fr.pos + d[:, None] * step
+    sdf = np.linalg.norm(P[:, None, :] - sc["c"][None], axis=-1) - sc["r"]
+    best = sdf.argmin(1)  # strict '<', first wins
+    if sdf.shape[1] > 1:
+        two = np.partition(sdf, 1, axis=1)
+        ambiguous = (two[:, 1] - two[:, 0]) < AMBIGUOUS
+    else:
+        ambiguous = np.zeros(len(d), bool)
+    cam_dist = np.linalg.norm(P - fr.pos, axis=-1)
+    cam_fall = np.maximum(fr.cam_fall_off * (cam_dist * cam_dist + 1.0), 1.0)
+    normal = P - sc["c"][best]
+    normal /= np.linalg.norm(normal, axis=-1, keepdims=True)
+    cam_dir = -step
+    normal_fall = np.maximum((normal * cam_dir).sum(-1), 0.0)
+    color, shine, ambient = sc["color"][best], sc["shine"][best], sc["ambient"][best]
+    rr = fr.ray_radius
+    lo = np.zeros((len(d), 3))
+    hi = np.zeros((len(d), 3))
+    for lp, lc in zip(sc["lpos"], sc["lcol"]):
+        to = lp - P
+        light_dist = np.linalg.norm(to, axis=-1)
+        light_dir = to / light_dist[:, None]
+        light_fall = np.maximum(fr.light_fall_off * light_dist * light_dist, 1.0)
+        diffuse = np.maximum((normal * light_dir).sum(-1), 0.0)
+        inc = -light_dir
+        refl = inc - 2.0 * (normal * inc).sum(-1)[:, None] * normal
+        base = (refl * cam_dir).sum(-1)
+        with np.errstate(invalid="ignore"):
+            spec = np.where(base > 0, np.maximum(diffuse * np.power(np.maximum(base, 0.0), shine), 0.0), 0.0)
+        s = np.maximum(diffuse + spec, 0.0)
+        end = light_dist
+        m, a, f0 = _segment_min(P + light_dir, light_dir, end, sc["c"], sc["r"])
+        blocked = (np.minimum(end, f0) <= rr) | (a <= end - 2.0 * rr)
+        s_hi = np.where(blocked, 0.0, np.minimum(np.minimum(1.0, end), np.maximum(f0, 0.0)))
+        s_lo = np.where(blocked | (m <= rr), 0.0, np.minimum(np.minimum(m, end), 1.0))
+        for soft, acc in ((s_lo, lo), (s_hi, hi)):
+            direct = (s[:, None] * lc[None] / light_fall[:, None]) * soft[:, None]
+            acc += (ambient[:, None] + direct) / cam_fall[:, None] * normal_fall[:, None] * color
+    lo, hi = np.minimum(lo, hi), np.maximum(lo, hi)
+    width = (hi - lo).max(1) if len(d) else np.zeros(0)
+    return dict(py=py, px=px, lo=lo, hi=hi, ambiguous=ambiguous, pinned=~ambiguous & (width < PINNED_WIDTH), width=width)
+
+
+def check_rgb(fr, eps=None, bands=None):
+    """fr.rgb against its intervals.  Returns dict(hits, bad, excursion, ambiguous, pinned (shares of the hit pixels), median_width,
+    miss_nonblack (miss pixels that are not exactly black))."""
+    eps = EPS_RGB if eps is None else eps
+    sb = bands if bands is not None else shade_bands(fr)
+    got = fr.rgb[sb["py"], sb["px"]]
+    keep = ~sb["ambiguous"]
+    out = np.maximum(np.maximum(sb["lo"] - got, got - sb["hi"]), 0.0).max(1) if len(got) else np.zeros(0)
+    out = np.where(np.isfinite(out), out, np.inf)[keep]
+    n = len(got)
+    missed = fr.levels[-1][:fr.h, :fr.w] >= fr.render_dist
+    return dict(hits=n, bad=int(np.count_nonzero(out > eps)), excursion=float(out.max()) if len(out) else 0.0,
+                ambiguous=float(np.count_nonzero(sb["ambiguous"])) / max(n, 1), pinned=float(np.count_nonzero(sb["pinned"])) / max(n, 1),
+                median_width=float(np.median(sb["width"][keep])) if keep.any() else 0.0,
+                miss_nonblack=int(np.count_nonzero(fr.rgb[missed])))
+
+
+def check_frame(fr, eps_depth=None, eps_rgb=None, limit=100_000):
+    """Every level and the RGB of fr.  Returns (list of check_depth results, check_rgb result)."""
+    depth = [check_depth(fr, i, eps_depth, sample_texels(fr, i, limit)) for i in range(fr.count)]
+    return depth, check_rgb(fr, eps_rgb)
+
+
+# ---- the cases both test files run ---------------------------------------------------------------------------------------------
+def _pack_scene(spheres, mats, lights):
+    """The 656-byte scene image: spheres [(x, y, z, r)], mats [(r, g, b, shine, ambient)], lights [((x, y, z), (r, g, b))]."""
+    head = np.array([len(mats), len(spheres), len(lights), 0], np.uint32)
+    m = np.zeros((8, 8), np.float32)
+    o = np.zeros((8, 4), np.float32)
+    li = np.zeros((8, 8), np.float32)
+    for k, (r, g, b, shine, ambient) in enumerate(mats):
+        m[k, :7] = (r, g, b, 1.0, 1.0, shine, ambient)
+    for k, s in enumerate(spheres):
+        o[k] = s
+    for k, (p, c) in enumerate(lights):
+        li[k, :3], li[k, 4:7] = p, c
+    return head.tobytes() + m.tobytes() + o.tobytes() + li.tobytes()
+
+
+def startup_scene():
+    """The reference's start-up scene (src/main.rs:524-591)."""
+    return _pack_scene([(5, 5, -1, 3), (5, 4, 10, 6), (-3, 3, -3, 1), (4, -1, 0, 2)],
+                       [(0.2, 0.2, 1.0, 1, 0.05), (0.1, 1.0, 0.1, 10, 0.05), (1.0, 1.0, 0.1, 1, 0.05), (1.0, 0.1, 0.1, 1, 0.05)],
+                       [((-1, 0, -3), (0.1, 0.5, 0.6)), ((8, -5, 10), (1.2, 0.2, 0.3))])
+
+
+def room_scene():
+    """The eight-sphere room of BASELINE.json configs[0]/[1]: five wall spheres of radius 50, three balls, one light."""
+    return _pack_scene([(-56, 10, 0, 50), (56, 10, 0, 50), (0, 10, -56, 50), (0, 10, 56, 50), (0, 72, 0, 50), (-2.5, 14, -4, 2), (2.5, 11, -3, 3), (0, 8, -5, 1)],
+                       [(0.75, 0.15, 0.15, 1, 0.05), (0.15, 0.75, 0.15, 1, 0.05), (0.75, 0.75, 0.75, 1, 0.05), (0.75, 0.75, 0.75, 1, 0.05),
+                        (0.75, 0.75, 0.75, 1, 0.05), (0.9, 0.9, 0.2, 10, 0.05), (0.2, 0.4, 0.9, 30, 0.05), (0.9, 0.5, 0.2, 4, 0.05)],
+                       [((0, 10, 5), (1.0, 1.0, 1.0))])
+
+
+def random_scene(n_obj, n_light):
+    """Drawn as tests/test_gpu_path_a.py::test_object_and_light_counts draws its scenes."""
+    rng = np.random.default_rng(n_obj * 16 + n_light)
+    spheres = [(rng.uniform(-8, 8), rng.uniform(6, 25), rng.uniform(-6, 6), rng.uniform(0.5, 3)) for _ in range(n_obj)]
+    mats = [(*rng.uniform(0.1, 1, 3), float(rng.choice([1, 2, 10, 30])), 0.05) for _ in range(n_obj)]
+    lights = [(tuple(rng.uniform(-10, 10, 3)), tuple(rng.uniform(0.1, 1.5, 3))) for _ in range(n_light)]
+    return _pack_scene(spheres, mats, lights)
+
+
+def camera_quat(yaw, pitch):
+    """Rz(-yaw) * Rx(pitch) as [x, y, z, w], fp32 (src/main.rs:402-404)."""
+    hz, hx = np.float32(-yaw) * np.float32(0.5), np.float32(pitch) * np.float32(0.5)
+    zs, zc, xs, xc = np.sin(hz), np.cos(hz), np.sin(hx), np.cos(hx)
+    return np.array([zc * xs, zs * xs, zs * xc, zc * xc], np.float32)
+
+
+TURNED = dict(rot=camera_quat(0.6, -0.2), pos=(1.0, -2.0, 0.5))
+OTHER_CONFIG = dict(render_dist=40.0, cam_fall_off=0.02, light_fall_off=0.005, ray_radius=0.02)
+SMALL, MID, PADDED = (17, 9), (96, 64), (200, 120)  # tau = 0.67 at the finest level of two; four levels; five levels padded to multiples of 8
+# name -> (scene, view keywords, config keywords, kind, sizes); kind "open" and "room" carry the caps on the pinned share.
+# The caps below are conditions on (scene, view, size), asserted for every frame listed here; a frame that misses one is not listed.
+# The room seen straight on misses the width cap below 200 x 120 (median width 0.056 at 17 x 9, where 3.3 % of its pixels are ambiguous
+# as well, and 0.059 at 96 x 64: the cone radius lifts P off the walls and every shadow segment ends one unit past the light, next to
+# the ceiling), so it runs at 200 x 120 (and 512 x 288 on the GPU) and the turned room carries the small sizes.
+CASES = {
+    "startup": (startup_scene(), {}, {}, "open", [(12, 10), SMALL, MID, PADDED]),
+    "startup_turned": (startup_scene(), TURNED, {}, "open", [SMALL, MID, PADDED]),
+    "room": (room_scene(), {}, {}, "room", [PADDED]),
+    "room_turned": (room_scene(), TURNED, {}, "room", [SMALL, MID, PADDED]),
+    "random_5_2": (random_scene(5, 2), {}, {}, "open", [MID, PADDED]),
+    "random_8_8": (random_scene(8, 8), {}, {}, "open", [MID, PADDED]),
+    # inside a sphere, off its centre (at the centre the normal is 0 / 0, outside the arithmetic contract)
+    "inside": (_pack_scene([(0.5, 1.0, -0.25, 5)], [(1, 1, 1, 1, 0.05)], [((0, 1, 0), (1, 1, 1))]), {}, {}, None, [SMALL, MID]),
+    "all_miss": (_pack_scene([(0, -50, 0, 1)], [(1, 1, 1, 1, 0.05)], [((0, 1, 0), (1, 1, 1))]), {}, {}, None, [MID]),
+    "config": (startup_scene(), {}, OTHER_CONFIG, None, [MID, PADDED]),
+    "ratio": (startup_scene(), dict(ratio=(0.7, 0.9)), {}, None, [MID, PADDED]),
+}
+FRAMES = [(name, w, h) for name, case in CASES.items() for w, h in case[4]]
+GPU_ONLY_FRAMES = [("startup", 512, 288), ("room", 512, 288)]  # 7 levels, tau = 0.022: the tight bands; sampled above 100 000 texels a level
+CAP_AMBIGUOUS = 0.01
+CAP_PINNED = {"open": 0.50, "room": 0.20}
+CAP_ROOM_MEDIAN_WIDTH = 0.05
+
+
+def check_caps(name, rgb):
+    """The caps as assertions on a check_rgb result of case `name`."""
+    kind = CASES[name][3]
+    assert rgb["ambiguous"] <= CAP_AMBIGUOUS, rgb
+    if kind:
+        assert rgb["pinned"] >= CAP_PINNED[kind], rgb
+    if kind == "room":
+        assert rgb["median_width"] <= CAP_ROOM_MEDIAN_WIDTH, rgb
+
+
+# ---- measurement ---------------------------------------------------------------------------------------------------------------
+def oracle_frame(name, w, h):
+    """The case rendered by oracle A (CPU)."""
+    import oracle as O
+
+    scene, view, conf = CASES[name][:3]
+    cfg = O.default_config()
+    for k, v in conf.items():
+        setattr(cfg, k, v)
+    ref = O.render_a(O.scene_from_bytes(scene), w, h, cfg=cfg, **view)
+    fr = Frame(scene, w, h, levels=ref["levels"], rgb=ref["rgb"], **view, **conf)
+    fr.name = name
+    return fr
+
+
+def measure(out=sys.stdout):
+    """Largest excursions of oracle A's frames from the bands, every frame of both test files, with no tolerance."""
+    worst_d = worst_c = 0.0
+    for name, w, h in FRAMES + GPU_ONLY_FRAMES:
+        depth, rgb = check_frame(oracle_frame(name, w, h), 0.0, 0.0)
+        ed = max(x["excursion"] for x in depth)
+        worst_d, worst_c = max(worst_d, ed), max(worst_c, rgb["excursion"])
+        print(f"{name:15s} {w:4d}x{h:<4d} depth: {sum(x['bad'] for x in depth):5d} of {sum(x['n'] for x in depth):6d} outside, worst {ed:.3g}, "
+              f"parent missed and child hit {sum(x['far_bad'] for x in depth)} | rgb: {rgb['bad']:5d} of {rgb['hits']:6d} outside, worst {rgb['excursion']:.3g}, "
+              f"ambiguous {100 * rgb['ambiguous']:.2f} %, pinned {100 * rgb['pinned']:.1f} %, median width {rgb['median_width']:.3g}", file=out)
+    print(f"largest depth excursion / (1 + depth) = {worst_d:.4g}  -> EPS_DEPTH = {4 * worst_d:.4g}", file=out)
+    print(f"largest rgb excursion = {worst_c:.4g}  -> EPS_RGB = {4 * worst_c:.4g}", file=out)
+    return worst_d, worst_c
+
+
+if __name__ == "__main__":
+    import os
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    measure()

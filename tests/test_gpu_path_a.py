@@ -3,6 +3,7 @@
 Bar: pyramid levels (depth) bit-exact vs oracle A; RGB within 1e-4 max-abs (north_star tolerance;
 powf in the specular term is the only operation that is not bit-defined).  The oracle is pinned
 by tests/test_oracle_a.py, not by the reference ("parity unpinned by the reference").
+What oracle and kernels could both get wrong is held to closed-form sphere geometry in tests/test_gpu_path_a_exact.py.
 """
 import ctypes as C
 import os
