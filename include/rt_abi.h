@@ -19,7 +19,7 @@
  *     submit + fence  src/main.rs:909-927                          rt_render / rt_render_spp /
  *                                                                  rt_render_device
  *   swapchain *_UNORM colour attachment  src/main.rs:471-486       rt_read_rgba8
- *   (none: the reference cannot read a pyramid level back)         rt_read_level  [test hook]
+ *   (none: the reference cannot read a pyramid level back)         rt_read_level / rt_read_level_image  [test hooks]
  *   FPS println  src/main.rs:719,730                               rt_get_stats
  *   swapchain images + one fence per image: wait the image's fence,
  *     record, submit after the previous frame, present
@@ -167,7 +167,9 @@ int rt_set_stream(rt_ctx* ctx, void* hip_stream);
  * Synchronous: results are complete on return. */
 int rt_render(rt_ctx* ctx, const float rot[4], const float pos[3], float* rgb_out, float* depth_out);
 /* spp = n*n stratified sub-pixel centres (n = 1,2,3,..), each sample one full frame, averaged
- * in sample order; spp = 1 is rt_render. */
+ * in sample order, ((s0 + s1) + s2) + ... then / spp; spp = 1 is rt_render.  Sample s has the stratum i = s % n in x and
+ * j = s / n in y and adds the fp32 offset ((2i + 1) / n - 1) / width resp. ((2j + 1) / n - 1) / height to the normalised
+ * coordinates of every level texel and of the pixel, before the ratio is applied (n = 1: exactly 0). */
 int rt_render_spp(rt_ctx* ctx, const float rot[4], const float pos[3], uint32_t spp, float* rgb_out);
 /* Asynchronous device-side variant: rgb_dev is a device pointer receiving either the full frame
  * (tile_major = 0: width*height*3 f32) or only this rank's tiles packed tile-major
@@ -199,6 +201,11 @@ int rt_comm_destroy(rt_ctx* ctx);
 
 /* Test hook: copy pyramid level `level` of the last frame to host. */
 int rt_read_level(rt_ctx* ctx, uint32_t level, float* out, uint32_t* w, uint32_t* h);
+/* Test hook: the same for any image of the last enqueued sample batch.  A multi-sample frame is rendered in batches of up to 16
+ * samples (one sample per batch with fuse_levels = 1), each level holding one image per sample of the batch; image = 0 .. the
+ * batch's last image (RT_ERR_INVALID beyond it), *sample = the sample index that image belongs to (the batch's first sample +
+ * image).  rt_read_level is this call with the last image, which holds the frame's last sample. */
+int rt_read_level_image(rt_ctx* ctx, uint32_t level, uint32_t image, float* out, uint32_t* w, uint32_t* h, uint32_t* sample);
 /* Last frame as a *_UNORM swapchain would hold it (src/main.rs:471-486): linear, clamped,
  * round-to-nearest, alpha = 255 (never written by fragment.glsl:138,159). width*height*4 bytes. */
 int rt_read_rgba8(rt_ctx* ctx, uint8_t* rgba_out);

@@ -208,6 +208,7 @@ PROTOTYPES = {
     "rt_gather_tiles": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
     "rt_comm_destroy": (C.c_int, [_vp]),
     "rt_read_level": (C.c_int, [_vp, C.c_uint32, _fp, _u32p, _u32p]),
+    "rt_read_level_image": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _fp, _u32p, _u32p, _u32p]),
     "rt_read_rgba8": (C.c_int, [_vp, C.POINTER(C.c_uint8)]),
     "rt_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "rt_default_pt_params": (C.c_int, [C.POINTER(PtParams)]),

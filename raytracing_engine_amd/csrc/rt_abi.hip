@@ -48,6 +48,7 @@ void free_frame(Ctx* c) {
     c->d_rgba8 = nullptr;
     c->level_batch = 0;
     c->last_image = 0;
+    c->last_sample0 = 0;
     c->frame_valid = false;
 }
 
@@ -208,6 +209,7 @@ int enqueue_samples(Ctx* c, const float rot[4], const float pos[3], uint32_t s0,
     if (rc) return rc;
     if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++], c->stream));
     c->last_image = nb - 1u;
+    c->last_sample0 = s0;
     return RT_OK;
 }
 
@@ -567,20 +569,28 @@ int rt_synchronize(rt_ctx* ctx) {
     return RT_OK;
 }
 
-int rt_read_level(rt_ctx* ctx, uint32_t level, float* out, uint32_t* w, uint32_t* h) {
+int rt_read_level_image(rt_ctx* ctx, uint32_t level, uint32_t image, float* out, uint32_t* w, uint32_t* h, uint32_t* sample) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
     if (!c->frame_valid) return c->fail(RT_ERR_STATE, "no frame rendered yet");
     if (level >= c->level_count) return c->fail(RT_ERR_INVALID, "level %u >= %u", level, c->level_count);
+    if (image > c->last_image || image >= c->level_batch) return c->fail(RT_ERR_INVALID, "image %u > %u, the last of the batch", image, c->last_image);
     if (int rc = rt::bind(c)) return rc;
     if (w) *w = c->dims[level][0];
     if (h) *h = c->dims[level][1];
+    if (sample) *sample = c->last_sample0 + image;
     if (out) {
         RT_HIP(c, hipStreamSynchronize(c->stream));
-        RT_HIP(c, hipMemcpy(out, c->d_level[level] + (size_t)c->last_image * c->dims[level][0] * c->dims[level][1], (size_t)c->dims[level][0] * c->dims[level][1] * sizeof(float),
+        RT_HIP(c, hipMemcpy(out, c->d_level[level] + (size_t)image * c->dims[level][0] * c->dims[level][1], (size_t)c->dims[level][0] * c->dims[level][1] * sizeof(float),
                             hipMemcpyDeviceToHost));
     }
     return RT_OK;
+}
+
+int rt_read_level(rt_ctx* ctx, uint32_t level, float* out, uint32_t* w, uint32_t* h) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    return rt_read_level_image(ctx, level, c->last_image, out, w, h, nullptr);
 }
 
 int rt_read_rgba8(rt_ctx* ctx, uint8_t* rgba_out) {

@@ -428,6 +428,7 @@ struct Ctx {
     float* d_level[RT_MAX_LEVELS] = {};  // level i: level_batch images of dims[i], one per sample of a batch
     uint32_t level_batch = 0;            // images allocated per level
     uint32_t last_image = 0;             // image of the batch that holds the last sample rendered
+    uint32_t last_sample0 = 0;           // sample index of image 0 of that batch (rt_read_level_image)
     float* d_rgb = nullptr;         // full frame, f32 x 3
     uint8_t* d_rgba8 = nullptr;     // rt_read_rgba8 staging, width*height*4, allocated on first use, freed with the frame
     uint64_t* d_counters = nullptr;  // 4 x 1024 slots: hit pixels, secondary hits shaded, mirror rays, transmitted rays; summed on the host

@@ -238,12 +238,18 @@ class Renderer:
     def comm_destroy(self):
         self._check(self._lib.rt_comm_destroy(self._ctx))
 
-    def read_level(self, level):
+    def read_level(self, level, image=None):
+        """Test hook: pyramid level `level` of the last sample rendered, or, with `image`, (that level of image `image` of the
+        last sample batch, the sample index it belongs to) (rt_read_level_image)."""
         w, h = C.c_uint32(), C.c_uint32()
         self._check(self._lib.rt_read_level(self._ctx, level, None, C.byref(w), C.byref(h)))
         out = np.empty((h.value, w.value), np.float32)
-        self._check(self._lib.rt_read_level(self._ctx, level, _fptr(out), C.byref(w), C.byref(h)))
-        return out
+        if image is None:
+            self._check(self._lib.rt_read_level(self._ctx, level, _fptr(out), C.byref(w), C.byref(h)))
+            return out
+        sample = C.c_uint32()
+        self._check(self._lib.rt_read_level_image(self._ctx, level, int(image), _fptr(out), C.byref(w), C.byref(h), C.byref(sample)))
+        return out, int(sample.value)
 
     def read_rgba8(self):
         out = np.empty((self.height, self.width, 4), np.uint8)

@@ -3,7 +3,8 @@
 Test helper (imported by tests/test_path_a_exact_host.py and tests/test_gpu_path_a_exact.py); not a conftest, no fixtures.
 numpy float64 only: nothing from `oracle`, nothing from librt_amd at module level.  Written from the specification (include/rt_abi.h,
 oracle/oracle.h, DESIGN.md sections 4-5), not from oracle_a.c / path_a.hip, which mirror each other line by line and would share any
-misreading.  It covers the reference as shipped: march algorithm 3, no repeat(), no mirror or transmission chains, 1 spp, jitter 0.
+misreading.  It covers the reference as shipped (march algorithm 3, 1 spp, jitter 0), multi-sample frames (every sample a full frame
+with its own jitter, averaged in sample order) and march algorithm 1; no repeat(), no mirror or transmission chains, no algorithm 2.
 There is no stepping loop over a ray anywhere in this file: the scene is at most 8 spheres, so what the marches approximate has a
 closed form, and what they leave open (WHERE a march samples) is held in an interval.
 
@@ -25,6 +26,20 @@ its maximum is at an end of I).  A texel is right when
 so an empty F forces a miss, a crossed surface forbids one, and a grazing ray whose cone touches while its centre line misses may
 report either.  In every tested scene a texel whose parent missed stays a miss (`far_bad` counts the others); the tests assert that too.
 
+ALGORITHM 1 (Frame(march_algorithm=1); oracle.h, rt_abi.h: every SDF every step, the radius taken AFTER the step).  The march samples
+s_0 = 0, s_{j+1} = s_j + f(s_j), so it never crosses a surface either, stops at the first sampled s with f(s) <= (s + f(s) + 1) tau and
+returns max(len0 + g1(s), 0), g1(s) = (s + f(s)) (1 - tau) - tau.  For tau < 1 the stop condition is f(s) <= (s + 1) tau', tau' = tau /
+(1 - tau): the touch sets are the same quadratic with tau' for tau, cut the same way, g1 has the Lipschitz constant 2 (1 - tau), and the
+two closed forms are g1 with 0 and with max(f_k, 0) for f.  For tau >= 1 (level 0 of 17 x 9) f(0) (1 - tau) <= 0 <= tau: the first sample
+stops the march and the band is the one point len0 + f(0) (1 - tau) - tau, clamped at 0.  The miss rules are the same; so is the colour,
+which only reads the finest level.  A camera inside a sphere is not covered under algorithm 1.
+
+SAMPLES.  Sample s of spp = n x n adds the fp32 offset sample_jitter(s, spp, w, h) = ((2i + 1) / n - 1) / view, i = s % n in x and s // n
+in y, to the normalised coordinates of every level's texels and of the pixel, BEFORE the ratio (rays()).  check_samples(frames, rgb):
+every level of every sample in the bands of its own jitter; per pixel the average lies in [sum lo_s, sum hi_s] / spp, a sample that
+missed adding exactly 0; a pixel is left out when one of its hit samples is ambiguous, pinned when all of them are, and exactly black
+when every sample missed.
+
 COLOUR, shade_bands(frame).  Pixel (px, py) with own finest-level depth d < render_dist: step through ((px + 0.5) 2 / view - 1) ratio,
 P = pos + d step, nearest sphere by strict '<' (first wins), then DESIGN.md section 5's formula in float64: cam_fall, normal,
 normal_fall, per light light_dir, light_dist, light_fall, diffuse, reflect, pow (0 for a base <= 0).  Where the two smallest SDFs at P
@@ -39,16 +54,21 @@ RGB is monotone in every soft, so the pixel lies between RGB(lo) and RGB(hi) com
 narrower than PINNED_WIDTH (every light blocked, or its minimum attained at t = 0, or >= end or 1).
 
 THE CONSTANTS are measured on the CPU against oracle A, never on a GPU frame:  python tests/path_a_exact.py  renders every frame of
-the two test files (FRAMES and GPU_ONLY_FRAMES below) with the oracle and prints, with no tolerance at all, the largest distance of an
-oracle texel / pixel outside its band.  Measured by that command:
-    depth, relative to 1 + depth:  3.109e-07  (room_turned 200 x 120; about 160 texels of all frames leave their band at all, by fp32 rounding)
-    rgb:                           5.471e-06  (random_8_8 96 x 64: shine 30, eight lights)
+the two test files (FRAMES, ALG1_FRAMES, SAMPLE_FRAMES and the GPU_ONLY lists below; multi-sample frames per sample and averaged) with
+the oracle and prints, with no tolerance at all, the largest distance of an oracle texel / pixel outside its band.  Measured by that command:
+    depth, relative to 1 + depth:  5.922e-07  (room_turned 96 x 64, algorithm 1, finest level: its bands are narrow next to a wall of radius
+                                               50, where the fp32 |p - c| - r is a few ulps of 50 off; algorithm 3 alone: 3.109e-07, room_turned
+                                               200 x 120; jittered samples: 2.57e-07)
+    rgb:                           9.342e-06  (random_8_8 96 x 64 under algorithm 1: shine 30, eight lights; algorithm 3: 5.471e-06; one
+                                               jittered sample: 6.73e-06, same scene; an averaged frame: 2.48e-06)
 Constants = four times the measurement, to cover powf and the fp32 position the kernels shade at:
-    EPS_DEPTH = 1.244e-06      EPS_RGB = 2.188e-05   (under the project's 1e-4 bar for RGB)
+    EPS_DEPTH = 2.369e-06      EPS_RGB = 3.737e-05   (under the project's 1e-5 / 1e-4 bars)
 A roll by one texel, a depth moved by one cone radius, a wrong parent, swapped materials, a dropped light or exchanged fall-offs move
 a frame by 1e-2 and more (tests/test_path_a_exact_host.py shows each rejected), so the margin costs no power.
 Shares of the hit pixels, same command: ambiguous 0 - 0.37 %; pinned 57 - 100 % in the open scenes and 24 - 49 % in the room; median
-width of the room's RGB intervals 0.0004 - 0.045.
+width of the room's RGB intervals 0.0004 - 0.045.  Averaged frames (4, 9, 16 spp; shares of the pixels some sample hit): ambiguous
+0 - 0.68 % (17 x 9) and <= 0.38 % elsewhere, every hit sample pinned 53 - 94 % (open) and 24 - 33 % (rooms), room median width 0.012 - 0.0451.
+Algorithm 1: ambiguous <= 0.37 %, pinned 55 - 100 % / 25 - 31 %, room median width 0.017 - 0.047.
 """
 import sys
 
@@ -59,8 +79,8 @@ N_SAMPLE = 33
 AMBIGUOUS = 1e-3
 PINNED_WIDTH = 1e-6
 # python tests/path_a_exact.py  (see the module docstring)
-EPS_DEPTH = 1.244e-06
-EPS_RGB = 2.188e-05
+EPS_DEPTH = 2.369e-06
+EPS_RGB = 3.737e-05
 
 
 # ---- inputs --------------------------------------------------------------------------------------------------------------------
@@ -93,8 +113,11 @@ class Frame:
     """Everything the two band functions read: the scene, the view, the config scalars, and the frame's own levels and RGB."""
 
     def __init__(self, scene, width, height, rot=(0, 0, 0, 1), pos=(0, 0, 0), ratio=None, render_dist=1000.0, cam_fall_off=0.01,
-                 light_fall_off=0.01, ray_radius=0.01, levels=None, rgb=None):
+                 light_fall_off=0.01, ray_radius=0.01, levels=None, rgb=None, jitter=(0, 0), march_algorithm=3):
         self.scene = parse_scene(scene)
+        self.jitter = np.asarray(jitter, np.float32).astype(np.float64)  # added to the normalised coordinates, before the ratio
+        assert march_algorithm in (1, 3)
+        self.alg = int(march_algorithm)
         self.w, self.h = int(width), int(height)
         f32 = np.float32
         if ratio is None:
@@ -123,8 +146,19 @@ def rotate(q, v):
     return v + 2.0 * np.cross(q[:3], t)
 
 
+def sample_jitter(s, spp, width, height):
+    """The offset of sample s of spp = n x n stratified samples (include/rt_abi.h at rt_render_spp):
+    ((2i + 1) / n - 1) / view with i = s % n for x and s // n for y, every operation in fp32; the fp32 pair."""
+    n = int(round(spp ** 0.5))
+    assert n * n == spp and 0 <= s < spp
+    f32 = np.float32
+    return np.array([(f32(2 * (s % n) + 1) / f32(n) - f32(1)) / f32(width), (f32(2 * (s // n) + 1) / f32(n) - f32(1)) / f32(height)], np.float32)
+
+
 def rays(fr, nx, ny):
-    """Unit directions through the normalised coordinates (nx, ny): normalize(rotate(rot, (nx ratio_x, 1, ny ratio_y)))."""
+    """Unit directions through the normalised coordinates (nx, ny), to which the sample's jitter is added first:
+    normalize(rotate(rot, ((nx + jx) ratio_x, 1, (ny + jy) ratio_y)))."""
+    nx, ny = nx + fr.jitter[0], ny + fr.jitter[1]
     v = np.stack([nx * fr.ratio[0], np.ones_like(nx), ny * fr.ratio[1]], -1)
     d = rotate(fr.rot, v)
     return d / np.linalg.norm(d, axis=-1, keepdims=True)
@@ -193,13 +227,32 @@ def depth_bands_chunk(fr, i, texels):
     a = a_k.min(1)
     cut = np.minimum(a, RD)
 
-    lo_k, hi_k = _touch_intervals(np.full_like(b, 1.0 - tau * tau), b - tau * (r + tau), cc - (r + tau) ** 2)
+    if fr.alg == 1 and tau >= 1.0:
+        # f(0) (1 - tau) <= 0 <= tau: the first sample stops the march, the band is one point
+        f0 = (np.sqrt(cc) - r).min(1)
+        assert (f0 >= 0.0).all(), "algorithm 1 from inside a sphere is not covered"
+        point = np.maximum(len0 + f0 * (1.0 - tau) - tau, 0.0)
+        return dict(lo=point, hi=point.copy(), empty=np.zeros(len(gx), bool), crossed=a < RD, len0=len0, gy=gy, gx=gx, tau=tau)
+    # the radius factor of the touch sets {f_k <= (t + 1) tq}; algorithm 1 stops on f (1 - tau) <= (s + 1) tau
+    tq = tau if fr.alg == 3 else tau / (1.0 - tau)
+    lo_k, hi_k = _touch_intervals(np.full_like(b, 1.0 - tq * tq), b - tq * (r + tq), cc - (r + tq) ** 2)
     lo_k = np.maximum(lo_k, 0.0)
     hi_k = np.minimum(hi_k, cut[:, None, None])
 
     def f_at(idx, s):  # min_k |o + s u - c_k| - r_k for texels idx at relative distances s (len(idx), m)
         p = oc[idx][:, None, :, :] + s[:, :, None, None] * u[idx][:, None, None, :]
         return (np.sqrt((p * p).sum(-1)) - r).min(-1)
+
+    if fr.alg == 3:
+        lipschitz = 2.0 + tau
+
+        def g_of(s, f):  # what a march that stops at s returns, relative to len0
+            return s + np.maximum(f, 0.0) - (s + 1.0) * tau
+    else:
+        lipschitz = 2.0 * (1.0 - tau)
+
+        def g_of(s, f):  # f >= 0 on F, the march never crosses a surface: the clamp only takes the rounding at the cut
+            return (s + np.maximum(f, 0.0)) * (1.0 - tau) - tau
 
     gmin = np.full(len(gx), np.inf)
     gmax = np.full(len(gx), -np.inf)
@@ -211,15 +264,14 @@ def depth_bands_chunk(fr, i, texels):
                 continue
             l, hgh = lo_k[idx, k, j], hi_k[idx, k, j]
             s = l[:, None] + (hgh - l)[:, None] * frac
-            g = s + np.maximum(f_at(idx, s), 0.0) - (s + 1.0) * tau
-            slack = (2.0 + tau) * (hgh - l) / (2.0 * (N_SAMPLE - 1))
-            # closed forms on this interval: g >= s - rho(s); g <= s - rho(s) + max(f_k(s), 0), convex
+            g = g_of(s, f_at(idx, s))
+            slack = lipschitz * (hgh - l) / (2.0 * (N_SAMPLE - 1))
+            # closed forms on this interval: g >= g with f = 0 (linear, rising); g <= g with max(f_k, 0) for f (convex in s)
             ends = np.stack([l, hgh], 1)
             pk = oc[idx, k][:, None, :] + ends[:, :, None] * u[idx][:, None, :]
             fk = np.sqrt((pk * pk).sum(-1)) - r[k]
-            lin = ends - (ends + 1.0) * tau
-            g_lo = np.maximum(g.min(1) - slack, lin.min(1))
-            g_hi = np.minimum(g.max(1) + slack, (lin + np.maximum(fk, 0.0)).max(1))
+            g_lo = np.maximum(g.min(1) - slack, g_of(ends, 0.0).min(1))
+            g_hi = np.minimum(g.max(1) + slack, g_of(ends, np.maximum(fk, 0.0)).max(1))
             np.minimum.at(gmin, idx, g_lo)
             np.maximum.at(gmax, idx, g_hi)
     empty = ~np.isfinite(gmin)
@@ -360,6 +412,53 @@ def check_frame(fr, eps_depth=None, eps_rgb=None, limit=100_000):
     return depth, check_rgb(fr, eps_rgb)
 
 
+def sample_bands(frames):
+    """Intervals of the average of the per-sample frames (each with its own jitter and levels): per pixel [sum lo_s, sum hi_s] / spp,
+    a sample that missed adding exactly 0.  Returns dict(lo, hi (h, w, 3); hit (a sample hit), ambiguous (a hit sample is
+    ambiguous), pinned (every hit sample is pinned) (h, w) bool; sample_hits = the (pixel, sample) pairs that hit)."""
+    h, w, n = frames[0].h, frames[0].w, len(frames)
+    lo, hi = np.zeros((h, w, 3)), np.zeros((h, w, 3))
+    hit, ambiguous, pinned = np.zeros((h, w), bool), np.zeros((h, w), bool), np.ones((h, w), bool)
+    sample_hits = 0
+    for fr in frames:
+        assert (fr.w, fr.h) == (w, h)
+        sb = shade_bands(fr)
+        py, px = sb["py"], sb["px"]  # every pixel at most once
+        lo[py, px] += sb["lo"]
+        hi[py, px] += sb["hi"]
+        hit[py, px] = True
+        ambiguous[py, px] |= sb["ambiguous"]
+        pinned[py, px] &= sb["pinned"]
+        sample_hits += len(py)
+    return dict(lo=lo / n, hi=hi / n, hit=hit, ambiguous=ambiguous, pinned=pinned & hit, sample_hits=sample_hits)
+
+
+def check_samples_rgb(frames, rgb, eps=None, bands=None):
+    """The averaged frame `rgb` against sample_bands(frames).  check_rgb's keys, the shares being of the pixels some sample hit
+    (ambiguous pixels are left out of bad / excursion / median_width), and sample_hits."""
+    eps = EPS_RGB if eps is None else eps
+    sb = bands if bands is not None else sample_bands(frames)
+    rgb = np.asarray(rgb, np.float64)
+    hit, keep = sb["hit"], sb["hit"] & ~sb["ambiguous"]
+    out = np.maximum(np.maximum(sb["lo"] - rgb, rgb - sb["hi"]), 0.0).max(-1)
+    out = np.where(np.isfinite(out), out, np.inf)[keep]
+    n = int(np.count_nonzero(hit))
+    width = (sb["hi"] - sb["lo"]).max(-1)
+    return dict(hits=n, bad=int(np.count_nonzero(out > eps)), excursion=float(out.max()) if len(out) else 0.0,
+                ambiguous=float(np.count_nonzero(sb["ambiguous"])) / max(n, 1), pinned=float(np.count_nonzero(sb["pinned"])) / max(n, 1),
+                median_width=float(np.median(width[keep])) if keep.any() else 0.0, miss_nonblack=int(np.count_nonzero(rgb[~hit])),
+                sample_hits=sb["sample_hits"])
+
+
+def check_samples(frames, rgb, eps_depth=None, eps_rgb=None, limit=100_000):
+    """A multi-sample frame: `frames` are the per-sample Frames (own jitter, own levels), `rgb` their average as rendered.  Every
+    level of every sample against its bands, and the average against the averaged intervals.  Returns check_samples_rgb's dict (so
+    check_caps applies) with depth = [sample][level] check_depth results."""
+    res = check_samples_rgb(frames, rgb, eps_rgb)
+    res["depth"] = [[check_depth(fr, i, eps_depth, sample_texels(fr, i, limit)) for i in range(fr.count)] for fr in frames]
+    return res
+
+
 # ---- the cases both test files run ---------------------------------------------------------------------------------------------
 def _pack_scene(spheres, mats, lights):
     """The 656-byte scene image: spheres [(x, y, z, r)], mats [(r, g, b, shine, ambient)], lights [((x, y, z), (r, g, b))]."""
@@ -430,6 +529,15 @@ CASES = {
 }
 FRAMES = [(name, w, h) for name, case in CASES.items() for w, h in case[4]]
 GPU_ONLY_FRAMES = [("startup", 512, 288), ("room", 512, 288)]  # 7 levels, tau = 0.022: the tight bands; sampled above 100 000 texels a level
+# (name, w, h, spp): spp = n x n stratified samples, each a full frame with its own jitter; the caps are asserted on the averaged frame.
+# 4 = one SP batch; 9 = a batch that is no multiple of four; 16 = four SP rounds.  Sizes follow FRAMES (the room only at 200 x 120).
+SAMPLE_FRAMES = [(name, w, h, spp) for spp in (4, 9) for name, w, h in
+                 [("startup",) + SMALL, ("startup",) + MID, ("startup_turned",) + PADDED, ("room_turned",) + MID, ("random_8_8",) + MID,
+                  ("room",) + PADDED, ("ratio",) + PADDED]] + [("startup",) + MID + (16,), ("room_turned",) + MID + (16,)]
+GPU_ONLY_SAMPLE_FRAMES = [("startup", 512, 288, 4)]
+# march algorithm 1 at 1 spp (17 x 9: tau = 1.33 at level 0, the one-point band); no camera inside a sphere
+ALG1_FRAMES = [("startup",) + SMALL, ("startup",) + MID, ("startup_turned",) + PADDED, ("room_turned",) + MID, ("room",) + PADDED,
+               ("random_8_8",) + MID, ("random_5_2",) + PADDED, ("all_miss",) + MID, ("config",) + MID]
 CAP_AMBIGUOUS = 0.01
 CAP_PINNED = {"open": 0.50, "room": 0.20}
 CAP_ROOM_MEDIAN_WIDTH = 0.05
@@ -446,30 +554,59 @@ def check_caps(name, rgb):
 
 
 # ---- measurement ---------------------------------------------------------------------------------------------------------------
-def oracle_frame(name, w, h):
-    """The case rendered by oracle A (CPU)."""
+def oracle_frame(name, w, h, jitter=(0, 0), march_algorithm=3):
+    """The case rendered by oracle A (CPU), at one sample's jitter and with one of the march algorithms."""
     import oracle as O
 
     scene, view, conf = CASES[name][:3]
     cfg = O.default_config()
     for k, v in conf.items():
         setattr(cfg, k, v)
-    ref = O.render_a(O.scene_from_bytes(scene), w, h, cfg=cfg, **view)
-    fr = Frame(scene, w, h, levels=ref["levels"], rgb=ref["rgb"], **view, **conf)
+    cfg.march_algorithm = march_algorithm
+    ref = O.render_a(O.scene_from_bytes(scene), w, h, cfg=cfg, jitter=jitter, **view)
+    fr = Frame(scene, w, h, levels=ref["levels"], rgb=ref["rgb"], jitter=jitter, march_algorithm=march_algorithm, **view, **conf)
     fr.name = name
     return fr
+
+
+def average(rgbs):
+    """fp32 frames added in index order, ((s0 + s1) + s2) + ..., then divided by their number."""
+    acc = np.asarray(rgbs[0], np.float32)
+    for f in rgbs[1:]:
+        acc = acc + np.asarray(f, np.float32)
+    return acc / np.float32(len(rgbs))
+
+
+def oracle_samples(name, w, h, spp):
+    """The spp per-sample frames of the case by oracle A, and their average."""
+    frames = [oracle_frame(name, w, h, jitter=sample_jitter(s, spp, w, h)) for s in range(spp)]
+    return frames, average([fr.rgb for fr in frames])
 
 
 def measure(out=sys.stdout):
     """Largest excursions of oracle A's frames from the bands, every frame of both test files, with no tolerance."""
     worst_d = worst_c = 0.0
-    for name, w, h in FRAMES + GPU_ONLY_FRAMES:
-        depth, rgb = check_frame(oracle_frame(name, w, h), 0.0, 0.0)
+
+    def line(label, depth, rgb):
+        nonlocal worst_d, worst_c
         ed = max(x["excursion"] for x in depth)
         worst_d, worst_c = max(worst_d, ed), max(worst_c, rgb["excursion"])
-        print(f"{name:15s} {w:4d}x{h:<4d} depth: {sum(x['bad'] for x in depth):5d} of {sum(x['n'] for x in depth):6d} outside, worst {ed:.3g}, "
+        print(f"{label:28s} depth: {sum(x['bad'] for x in depth):5d} of {sum(x['n'] for x in depth):6d} outside, worst {ed:.3g}, "
               f"parent missed and child hit {sum(x['far_bad'] for x in depth)} | rgb: {rgb['bad']:5d} of {rgb['hits']:6d} outside, worst {rgb['excursion']:.3g}, "
               f"ambiguous {100 * rgb['ambiguous']:.2f} %, pinned {100 * rgb['pinned']:.1f} %, median width {rgb['median_width']:.3g}", file=out)
+
+    for name, w, h in FRAMES + GPU_ONLY_FRAMES:
+        line(f"{name} {w}x{h}", *check_frame(oracle_frame(name, w, h), 0.0, 0.0))
+    for name, w, h in ALG1_FRAMES:
+        line(f"{name} {w}x{h} alg 1", *check_frame(oracle_frame(name, w, h, march_algorithm=1), 0.0, 0.0))
+    for name, w, h, spp in SAMPLE_FRAMES + GPU_ONLY_SAMPLE_FRAMES:
+        frames, rgb = oracle_samples(name, w, h, spp)
+        per_sample = [check_rgb(fr, 0.0) for fr in frames]
+        res = check_samples(frames, rgb, 0.0, 0.0)
+        worst_c = max(worst_c, max(x["excursion"] for x in per_sample))
+        print(f"{name} {w}x{h} {spp} spp: largest rgb excursion of one sample {max(x['excursion'] for x in per_sample):.3g}, of all samples' "
+              f"depth {max(x['excursion'] for lv in res['depth'] for x in lv):.3g}; averaged:", file=out)
+        line("", [x for lv in res["depth"] for x in lv], res)
     print(f"largest depth excursion / (1 + depth) = {worst_d:.4g}  -> EPS_DEPTH = {4 * worst_d:.4g}", file=out)
     print(f"largest rgb excursion = {worst_c:.4g}  -> EPS_RGB = {4 * worst_c:.4g}", file=out)
     return worst_d, worst_c

@@ -6,6 +6,14 @@ cap of the shadow term) passes there.  Here every level of the depth pyramid lie
 in its RGB interval (EPS_DEPTH / EPS_RGB were measured on the CPU, never on a GPU frame), misses are exactly black, and the caps that
 keep the intervals meaningful hold; both launch schedules, padded levels, a non-default config and ratio.  What the bands decide and
 what they leave open (grazing rays, penumbrae), and the power of the check: tests/test_path_a_exact_host.py, DESIGN.md section 3.
+
+Multi-sample frames are what the benchmark renders: batched level launches (grid.y = sample, the jitter recomputed in the kernel) and
+the SP shade kernel (four lanes per pixel) for batches of a multiple of four.  Every image of the batch is read back
+(rt_read_level_image), mapped to its sample by the index the hook reports, and held to the bands of that sample's jitter; the
+averaged frame to the averaged intervals; 4 (SP), 9 (in-thread loop) and 16 spp (four SP rounds).  March algorithm 1 against its own
+bands.  Without any band: the batched schedule and the one-sample-per-launch schedule give the same frame bit for bit at 4, 9, 16,
+25 (16 SP + 9 continuing the sum) and 36 spp (16 + 16 + 4), at widths that are no multiple of 4 or 64; SP with tile-major output and
+a partition de-tiles to the single frame; a frame slot at 16 spp delivers the synchronous frame.
 """
 import numpy as np
 import pytest
@@ -15,21 +23,41 @@ import path_a_exact as X
 pytestmark = pytest.mark.gpu
 
 
-def gpu_frame(r, name, w, h, fused):
+def setup(r, name, w, h, fused=0, march_algorithm=0):
+    """Config, scene and size of case `name` on the renderer -> (scene, view, conf, rot, pos).  The caller resets the config."""
     scene, view, conf = X.CASES[name][:3]
     cfg = r.default_config()
     for k, v in conf.items():
         setattr(cfg, k, v)
     cfg.fuse_levels = int(fused)
+    cfg.march_algorithm = int(march_algorithm)
     r.set_config(cfg)
     r.set_scene(scene)
     r.resize(w, h, view.get("ratio"))
-    rgb, depth = r.render(view.get("rot", (0, 0, 0, 1)), view.get("pos", (0, 0, 0)), want_depth=True)
+    return scene, view, conf, view.get("rot", (0, 0, 0, 1)), view.get("pos", (0, 0, 0))
+
+
+def gpu_frame(r, name, w, h, fused, march_algorithm=0):
+    scene, view, conf, rot, pos = setup(r, name, w, h, fused, march_algorithm)
+    rgb, depth = r.render(rot, pos, want_depth=True)
     levels = [r.read_level(i) for i in range(len(r.level_info()))]
     assert np.array_equal(depth, levels[-1])
-    fr = X.Frame(scene, w, h, levels=levels, rgb=rgb, **view, **conf)
+    fr = X.Frame(scene, w, h, levels=levels, rgb=rgb, march_algorithm=march_algorithm or 3, **view, **conf)
     fr.hit_pixels = r.stats()["hit_pixels"]
     return fr
+
+
+def read_batch(r, n_images):
+    """{sample index: [levels]} of the last batch's images, each mapped through the sample index the hook reports."""
+    out = {}
+    for image in range(n_images):
+        levels = []
+        for i in range(len(r.level_info())):
+            lv, sample = r.read_level(i, image)
+            levels.append(lv)
+            assert sample == r.read_level(0, image)[1]
+        out[sample] = levels
+    return out
 
 
 @pytest.mark.parametrize("fused", [0, 1])
@@ -52,3 +80,163 @@ def test_frames_lie_inside_every_band(renderer, name, w, h, fused):
     else:
         assert rgb["hits"] > 0.05 * w * h
         assert fr.hit_pixels == rgb["hits"]
+
+
+@pytest.mark.parametrize("name,w,h", X.ALG1_FRAMES)
+def test_algorithm_1_frames_lie_inside_every_band(renderer, name, w, h):
+    """March algorithm 1 (every SDF every step, radius after the step) against its own closed-form bands; per-level schedule
+    (the sketched algorithms have no fused launch)."""
+    try:
+        fr = gpu_frame(renderer, name, w, h, 0, march_algorithm=1)
+    finally:
+        renderer.set_config(renderer.default_config())
+    depth, rgb = X.check_frame(fr)
+    for i, lv in enumerate(depth):
+        print(f"level {i}: {lv}")
+        assert lv["bad"] == 0 and lv["far_bad"] == 0, (i, lv)
+    print(rgb)
+    assert rgb["bad"] == 0 and rgb["miss_nonblack"] == 0, rgb
+    X.check_caps(name, rgb)
+    if name == "all_miss":
+        assert rgb["hits"] == 0 and not fr.rgb.any() and all(lv["hits"] == 0 for lv in depth[1:])
+    else:
+        assert rgb["hits"] > 0.05 * w * h
+        assert fr.hit_pixels == rgb["hits"]
+
+
+# ---- multi-sample frames: the batched level launches and the SP shade kernel -------------------------------------------------------
+@pytest.mark.parametrize("name,w,h,spp", X.SAMPLE_FRAMES + X.GPU_ONLY_SAMPLE_FRAMES)
+def test_multi_sample_frames_lie_inside_every_band(renderer, name, w, h, spp):
+    """Per-level schedule, one batch (spp <= 16): every image of the batch is read back, mapped to its sample through the index the
+    hook reports, and held to the bands of that sample's jitter; the averaged frame to the averaged intervals."""
+    try:
+        scene, view, conf, rot, pos = setup(renderer, name, w, h)
+        rgb = renderer.render(rot, pos, spp=spp)
+        hit_pixels = renderer.stats()["hit_pixels"]
+        batch = read_batch(renderer, spp)
+    finally:
+        renderer.set_config(renderer.default_config())
+    assert sorted(batch) == list(range(spp))
+    frames = [X.Frame(scene, w, h, levels=batch[s], jitter=X.sample_jitter(s, spp, w, h), **view, **conf) for s in range(spp)]
+    res = X.check_samples(frames, rgb)
+    for s, levels in enumerate(res["depth"]):
+        for i, lv in enumerate(levels):
+            assert lv["bad"] == 0 and lv["far_bad"] == 0, (s, i, lv)
+    print({k: v for k, v in res.items() if k != "depth"})
+    assert res["bad"] == 0 and res["miss_nonblack"] == 0, res
+    X.check_caps(name, res)
+    assert res["hits"] > 0.05 * w * h
+    assert hit_pixels == res["sample_hits"]
+
+
+@pytest.mark.parametrize("name,w,h,spp", X.SAMPLE_FRAMES)
+def test_the_last_sample_of_a_fused_multi_sample_frame_lies_inside_its_bands(renderer, name, w, h, spp):
+    """fuse_levels = 1 renders one sample per launch, so only the last sample's levels can be read: image 0 = sample spp - 1."""
+    try:
+        scene, view, conf, rot, pos = setup(renderer, name, w, h, fused=1)
+        renderer.render(rot, pos, spp=spp)
+        batch = read_batch(renderer, 1)
+    finally:
+        renderer.set_config(renderer.default_config())
+    assert list(batch) == [spp - 1]
+    fr = X.Frame(scene, w, h, levels=batch[spp - 1], jitter=X.sample_jitter(spp - 1, spp, w, h), **view, **conf)
+    for i in range(fr.count):
+        lv = X.check_depth(fr, i)
+        assert lv["bad"] == 0 and lv["far_bad"] == 0, (i, lv)
+
+
+def test_the_hook_reads_the_images_of_the_last_batch_only(renderer):
+    import raytracing_engine_amd as R
+
+    try:
+        scene, view, conf, rot, pos = setup(renderer, "startup", 70, 66)
+        renderer.render(rot, pos, spp=25)  # batches of 16 and 9
+        top = len(renderer.level_info()) - 1
+        assert [renderer.read_level(top, k)[1] for k in range(9)] == list(range(16, 25))
+        assert np.array_equal(renderer.read_level(top), renderer.read_level(top, 8)[0])
+        for bad in (9, 15, 16, 2 ** 32 - 1):
+            with pytest.raises(R.RtError) as e:
+                renderer.read_level(top, bad)
+            assert e.value.code == -1
+        renderer.render(rot, pos, spp=4)
+        assert [renderer.read_level(0, k)[1] for k in range(4)] == [0, 1, 2, 3]
+        with pytest.raises(R.RtError):
+            renderer.read_level(0, 4)  # allocated (the pyramid keeps 16 images) but not of the last batch
+        setup(renderer, "startup", 70, 66, fused=1)
+        renderer.render(rot, pos, spp=9)
+        assert renderer.read_level(top, 0)[1] == 8
+        with pytest.raises(R.RtError):
+            renderer.read_level(top, 1)
+    finally:
+        renderer.set_config(renderer.default_config())
+
+
+# ---- the two schedules give the same frame, bit for bit --------------------------------------------------------------------------
+@pytest.mark.parametrize("spp", [4, 9, 16, 25, 36])
+@pytest.mark.parametrize("w,h", [(17, 9), (70, 66), (200, 120)])
+@pytest.mark.parametrize("name", ["startup", "room"])
+def test_batched_and_one_sample_per_launch_frames_are_bit_identical(renderer, name, w, h, spp):
+    """the per-level schedule renders batches of up to 16 samples (the SP shade kernel when the batch is a
+    multiple of four: 4, 16, the 16 of 25, 16 + 16 + 4 of 36; the in-thread loop for 9 and the 9 of 25, continuing the running
+    sum), the fused schedule one sample per launch and never SP.  Both state ((s0 + s1) + s2) + ..., / spp, so the frames are equal
+    bit for bit, and so is the last sample's finest level on the texels inside the frame (the fused launch writes no others)."""
+    try:
+        scene, view, conf, rot, pos = setup(renderer, name, w, h, fused=0)
+        batched = renderer.render(rot, pos, spp=spp)
+        top = len(renderer.level_info()) - 1
+        last = spp - 1 - (spp - 1) // 16 * 16  # image of the last batch that holds sample spp - 1
+        level, sample = renderer.read_level(top, last)
+        hits = renderer.stats()["hit_pixels"]
+        setup(renderer, name, w, h, fused=1)
+        single = renderer.render(rot, pos, spp=spp)
+        level1, sample1 = renderer.read_level(top, 0)
+        hits1 = renderer.stats()["hit_pixels"]
+    finally:
+        renderer.set_config(renderer.default_config())
+    assert sample == sample1 == spp - 1
+    assert np.array_equal(level[:h, :w], level1[:h, :w])
+    diff = np.flatnonzero((batched != single).any(-1))
+    assert not len(diff), (len(diff), np.abs(batched - single).max())
+    assert hits == hits1 and batched.any()
+
+
+# ---- SP with partitions and frame slots ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("spp", [4, 25])
+@pytest.mark.parametrize("n_ranks", [2, 3])
+@pytest.mark.parametrize("name,w,h", [("room", 200, 120), ("startup", 200, 120), ("room", 70, 66), ("startup", 70, 66)])
+def test_tile_major_multi_sample_partitions_unite_to_the_single_frame(renderer, name, w, h, n_ranks, spp):
+    """The SP shade kernel (4 spp; the batch of 16 in 25 spp) with tile-major output and a partition: every rank renders only its
+    64 x 64 tiles, de-tiled they are the single-context frame bit for bit."""
+    import torch
+
+    try:
+        scene, view, conf, rot, pos = setup(renderer, name, w, h)
+        renderer.set_partition(0, 1)
+        full = renderer.render(rot, pos, spp=spp)
+        tx, ty, _ = renderer.tile_info()
+        tiles_per_rank = -(-(tx * ty) // n_ranks)
+        gathered = torch.zeros((n_ranks, tiles_per_rank, 64, 64, 3), dtype=torch.float32, device="cuda")
+        for rank in range(n_ranks):
+            renderer.set_partition(rank, n_ranks)
+            renderer.render_device(rot, pos, spp, gathered[rank].data_ptr(), tile_major=True)
+            renderer.synchronize()
+        out = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        renderer.detile_device(gathered.data_ptr(), n_ranks, tiles_per_rank, out.data_ptr())
+        renderer.synchronize()
+    finally:
+        renderer.set_partition(0, 1)
+        renderer.set_config(renderer.default_config())
+    assert full.any() and np.array_equal(out.cpu().numpy(), full)
+
+
+def test_a_frame_slot_at_16_spp_delivers_the_synchronous_frame(renderer):
+    try:
+        scene, view, conf, rot, pos = setup(renderer, "room", 200, 120)
+        want = renderer.render(rot, pos, spp=16)
+        renderer.frames_configure(1, renderer.FRAME_F32)
+        renderer.frame_submit(0, rot, pos, spp=16)
+        got = renderer.frame_wait(0)
+    finally:
+        renderer.resize(64, 64)  # releases the slot
+        renderer.set_config(renderer.default_config())
+    assert want.any() and np.array_equal(got, want)
