@@ -738,6 +738,45 @@ int rt_list_overlaps_device(rt_ctx* ctx, const void* tris_dev, uint32_t n, const
                             void* count_out_dev /* may be NULL */, void* offsets_out_dev, uint64_t capacity, void* tri_out_dev,
                             void* edges_out_dev);
 int rt_get_overlap_query_stats(rt_ctx* ctx, rt_overlap_query_stats* stats); /* synchronises the stream; the last call */
+/* Overlap segments on device arrays: WHERE each pair of an overlap list intersects - one segment per entry of the
+ * list that rt_list_overlaps_device / rt_fill_overlaps_device wrote for the same n query triangles and the same mesh.  Enqueued on the
+ * context's stream behind the work already there (a list call, a refit), no host synchronisation, and no allocation after the first
+ * call of a size class.  tris_dev (n x 9 f32), offsets_dev (n + 1 i64) and tri_dev (capacity i32) are the list call's arrays, device
+ * memory of the context's device, only read; offsets_dev[n] is read on the stream.  The arithmetic is csrc/tri_section.h, fp32 only,
+ * on the resident record words v0, e1, e2 of mesh triangle T = tri_dev[k] and the vertices of the query triangle i that owns entry k
+ * (offsets[i] <= k < offsets[i + 1]):  m = cand(i, T) ? mask(i, T) : 0, recomputed - the stored masks are not an input, and on a list
+ * the library wrote m is the stored mask;  for each set bit b, with (o, d, ...) the arguments of that bit's seg() above and t_b the t
+ * of its ray / triangle test, P_b = (fma(t_b, d.x, o.x), fma(t_b, d.y, o.y), fma(t_b, d.z, o.z));  one bit set: both endpoints are P_b
+ * (a touch);  two or more: the pair b < c of set bits with the largest fp32 |P_c - P_b|^2, ties to the first pair in lexicographic
+ * (b, c) order, the segment is (P_b, P_c) in that order.  seg_out_dev[k] (capacity x 6 f32) = the two endpoints; ends_out_dev[k]
+ * (capacity i32, may be NULL) = b | (c << 3), c = b for a touch: the edge each endpoint lies on (bits as in the mask).  In exact
+ * arithmetic this is the intersection segment of two triangles that are not coplanar; it inherits the list's caveats (coplanar pairs
+ * are never listed, the test is not watertight, pairs that share an edge or a vertex get what the arithmetic gives).
+ *   Entries k < min(offsets[n], capacity) are visited, nothing else is read or written.  An entry of a slice that ends beyond the
+ * capacity (offsets[i + 1] > capacity: the list call wrote nothing there) is left untouched and counted in skipped_incomplete.  The
+ * call is memory-safe against arrays it did not make: an entry that no slice owns (offsets that do not ascend), with tri_dev[k]
+ * outside [0, triangles of the mesh), with an invalid query triangle (rt_count_overlaps_device's rule) or with m == 0 gets six NaNs
+ * and ends = -1 and is counted in bad_entries; 0 on a list the library wrote for these triangles and this mesh.
+ *   Works on every mesh (host-built single- and two-level, device-built, refitted, updated by chunk, with surfaces).  The records are
+ * in leaf order, so every call first writes the map original index -> leaf position (4 bytes per mesh triangle) into scratch of the
+ * context's own, from the records themselves: nothing to invalidate, and the mesh is only read, so a shared mesh stays shared.
+ * Errors, all before anything is enqueued or written: RT_ERR_INVALID (a NULL context; a NULL, host or other-device tris_dev,
+ * offsets_dev, tri_dev or seg_out_dev, a host or other-device ends_out_dev, an allocation shorter than n / n + 1 / capacity rows, n
+ * above 2^30, capacity above 2^40, a mesh beyond 2^RT_PT_MAX_COORD_LOG2), RT_ERR_STATE (no mesh), RT_ERR_OOM (the scratch, grown by
+ * size class).  n == 0 or capacity == 0: RT_OK, nothing is done. */
+typedef struct rt_overlap_segment_stats {
+    uint64_t entries;            /* the last call with n > 0 and capacity > 0: entries visited, min(offsets[n], capacity) */
+    uint64_t segments;           /* entries with two or more bits: a segment between two different edges */
+    uint64_t touches;            /* entries with one bit: the same point twice */
+    uint64_t skipped_incomplete; /* entries of slices that end beyond the capacity: untouched */
+    uint64_t bad_entries;        /* entries answered with NaNs; entries = segments + touches + skipped_incomplete + bad_entries */
+    uint32_t launches;           /* kernel launches of that call: the map and the segments */
+    float ms;                    /* HIP-event time from the first to the last launch of the call */
+} rt_overlap_segment_stats;
+int rt_overlap_segments_device(rt_ctx* ctx, const void* tris_dev, uint32_t n, const void* offsets_dev /* n + 1 int64 */, uint64_t capacity,
+                               const void* tri_dev /* int32 */, void* seg_out_dev /* capacity x 6 f32 */,
+                               void* ends_out_dev /* capacity int32, may be NULL */);
+int rt_get_overlap_segment_stats(rt_ctx* ctx, rt_overlap_segment_stats* stats); /* synchronises the stream; the last call */
 /* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */

@@ -177,6 +177,14 @@ class OverlapQueryStats(C.Structure):  # rt_overlap_query_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class OverlapSegmentStats(C.Structure):  # rt_overlap_segment_stats
+    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("touches", C.c_uint64), ("skipped_incomplete", C.c_uint64), ("bad_entries", C.c_uint64),
+                ("launches", C.c_uint32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 assert C.sizeof(MutableData) == 656 and C.sizeof(Material) == 32 and C.sizeof(Object) == 16 and C.sizeof(Light) == 32
 
 # every symbol include/rt_abi.h declares: name -> (restype, argtypes)
@@ -257,6 +265,8 @@ PROTOTYPES = {
     "rt_fill_overlaps_device": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(OverlapQueryParams), _vp, C.c_uint64, _vp, _vp]),
     "rt_list_overlaps_device": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(OverlapQueryParams), _vp, _vp, C.c_uint64, _vp, _vp]),
     "rt_get_overlap_query_stats": (C.c_int, [_vp, C.POINTER(OverlapQueryStats)]),
+    "rt_overlap_segments_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "rt_get_overlap_segment_stats": (C.c_int, [_vp, C.POINTER(OverlapSegmentStats)]),
     "rt_trace_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32)]),
     "rt_trace_rays_counted": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32), _u32p]),
 }

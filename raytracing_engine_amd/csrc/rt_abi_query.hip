@@ -1,5 +1,6 @@
 // rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14),
-// sides (§6.15), all hits (§6.16), neighbours (§6.17), the attribute variants of the first two (§6.18) and overlaps (§6.20).
+// sides (§6.15), all hits (§6.16), neighbours (§6.17), the attribute variants of the first two (§6.18), overlaps (§6.20) and their
+// segments (§6.21: a flat kernel over a list, with a prologue and an enqueue of its own at the end of this file).
 // A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here: the
 // parameter checks and the prologue of an entry (enter_query), the plan and the enqueue (prepare_query, run_query), the read-back.
 // The listing kinds - all hits, neighbours, overlaps - are a description each (HitKind, NeighborKind, OverlapKind); their protocol of a count step, a fill
@@ -476,8 +477,10 @@ namespace rt {
 void query_free(Ctx* c) {
     c->pt.d_list_scan.reset();
     c->pt.list_scan_words = 0;
+    c->pt.d_tri_inverse.reset();
+    c->pt.tri_inverse_words = 0;
     for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query.qs, &c->pt.neighbor_query.qs,
-                           &c->pt.overlap_query.qs}) {
+                           &c->pt.overlap_query.qs, &c->pt.segment_query}) {
         qs->block.reset();
         for (hipEvent_t& e : qs->ev) {
             if (e) (void)hipEventDestroy(e);
@@ -661,5 +664,77 @@ int rt_list_overlaps_device(rt_ctx* ctx, const void* tris, uint32_t n, const rt_
 }
 
 int rt_get_overlap_query_stats(rt_ctx* ctx, rt_overlap_query_stats* stats) { return listing_stats<OverlapKind>(ctx, stats); }
+
+// ---- overlap segments: every refusal and the first-use allocations, then the map, then one lane per entry ----
+int rt_overlap_segments_device(rt_ctx* ctx, const void* tris, uint32_t n, const void* offsets, uint64_t capacity, const void* tri, void* seg_out, void* ends_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    rt::PtData& pt = c->pt;
+    const rt::DeviceMesh& mesh = pt.mesh();
+    if (!mesh.n_tris) return c->fail(RT_ERR_STATE, "rt_set_mesh has not been called");
+    if (int rc = rt::check_mesh_domain(c, mesh)) return rc;
+    if (n > kMaxQueryItems) return c->fail(RT_ERR_INVALID, "n %u is above 2^30", n);
+    if (capacity > (uint64_t)1 << 40) return c->fail(RT_ERR_INVALID, "capacity %llu is above 2^40", (unsigned long long)capacity);
+    if (n == 0 || capacity == 0) return RT_OK;
+    if (int rc = rt::bind(c)) return rc;
+    if (int rc = rt::check_device_array(c, tris, (size_t)n * 36, "tris_dev")) return rc;
+    if (int rc = rt::check_device_array(c, offsets, ((size_t)n + 1) * 8, "offsets_dev")) return rc;
+    if (int rc = rt::check_device_array(c, tri, (size_t)capacity * 4, "tri_dev")) return rc;
+    if (int rc = rt::check_device_array(c, seg_out, (size_t)capacity * 24, "seg_out_dev")) return rc;
+    if (ends_out)
+        if (int rc = rt::check_device_array(c, ends_out, (size_t)capacity * 4, "ends_out_dev")) return rc;
+    QueryState& qs = pt.segment_query;
+    if (!qs.block) {
+        if (!dalloc(qs.block, rt::query_block_bytes(qs.n_counters))) return c->fail(RT_ERR_OOM, "%s counters", qs.name);
+        for (hipEvent_t& e : qs.ev)
+            if (!e) RT_HIP(c, hipEventCreate(&e));
+    }
+    if (mesh.n_tris > pt.tri_inverse_words) {  // by size class (powers of two)
+        size_t words = 4096;
+        while (words < mesh.n_tris) words *= 2;
+        RT_HIP(c, hipStreamSynchronize(c->stream));  // an earlier call may still be reading the old one
+        pt.tri_inverse_words = 0;
+        if (!rt::dalloc(pt.d_tri_inverse, words)) return c->fail(RT_ERR_OOM, "overlap-segments index map (%zu words)", words);
+        pt.tri_inverse_words = words;
+    }
+    rt::SegmentQuery q{};
+    q.tris = static_cast<const float*>(tris);
+    q.offsets = static_cast<const long long*>(offsets);
+    q.tri = static_cast<const int*>(tri);
+    q.capacity = (long long)capacity;
+    q.seg_out = static_cast<float*>(seg_out);
+    q.ends_out = static_cast<int*>(ends_out);
+    q.n = n;
+    q.reach = rt::kCameraReach * mesh.maxabs;
+    // nothing can refuse any more
+    rt::RoctxRange rr("rt.path_b.overlap_segments");
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(qs.block.get() + rt::kQueryHeadBytes);
+    RT_HIP(c, hipMemsetAsync(stats, 0, qs.n_counters * sizeof(unsigned long long), c->stream));
+    RT_HIP(c, hipEventRecord(qs.ev[0], c->stream));
+    if (int rc = rt::launch_pt_tri_inverse(c, rt::scene_view(mesh), pt.d_tri_inverse.get())) return rc;
+    if (int rc = rt::launch_pt_overlap_segments(c, rt::scene_view(mesh), q, pt.d_tri_inverse.get(), stats)) return rc;
+    RT_HIP(c, hipEventRecord(qs.ev[1], c->stream));
+    qs.pending = true;
+    pt.segment_stats = rt_overlap_segment_stats{};
+    pt.segment_stats.launches = 2;
+    return RT_OK;
+}
+
+int rt_get_overlap_segment_stats(rt_ctx* ctx, rt_overlap_segment_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    rt_overlap_segment_stats& s = c->pt.segment_stats;
+    if (c->pt.segment_query.pending) {
+        unsigned long long st[rt::SG_STAT_WORDS] = {};
+        if (int rc = read_query(c, c->pt.segment_query, st, &s.ms)) return rc;
+        s.entries = st[rt::SG_STAT_ENTRIES];
+        s.touches = st[rt::SG_STAT_TOUCHES];
+        s.skipped_incomplete = st[rt::SG_STAT_SKIPPED];
+        s.bad_entries = st[rt::SG_STAT_BAD];
+        s.segments = s.entries - s.touches - s.skipped_incomplete - s.bad_entries;  // every entry is one of the four
+    }
+    *stats = s;
+    return RT_OK;
+}
 
 }  // extern "C"

@@ -297,6 +297,19 @@ struct OverlapQuery {
 // Waves per SIMD pt_query_overlaps is bounded to, = its workgroups per CU: at the neighbours' 8 (64 VGPRs) the six segment tests spill
 // 9 - 23 registers to scratch, at 6 (75 - 79 VGPRs) nothing does (profiles/overlap_queries.txt); the host caps the persistent grid to it.
 constexpr int kOverlapWaves = 6;
+// rt_overlap_segments_device: an overlap list and where the segment of each of its entries goes.  Entry k is lane k.
+struct SegmentQuery {
+    const float* tris;         // n x 9: the query triangles the list was made for
+    const long long* offsets;  // n + 1: the list's slices; offsets[n] is read on the device
+    const int* tri;            // capacity: the listed mesh triangles, original indices
+    long long capacity;        // elements of tri, ends_out; rows of seg_out
+    float* seg_out;            // capacity x 6
+    int* ends_out;             // capacity, or nullptr
+    uint32_t n;
+    float reach;  // |coordinate| limit: kCameraReach x the mesh's maxabs
+};
+// Counters of a segment call (TOUCHES, SKIPPED, BAD in this order: one thread each adds them); segments = entries - the other three
+enum { SG_STAT_ENTRIES = 0, SG_STAT_TOUCHES = 1, SG_STAT_SKIPPED = 2, SG_STAT_BAD = 3, SG_STAT_WORDS = 4 };
 // Counters of a listing query (all hits, neighbours, overlaps): one set per step (the fill step's LQ_STEP_WORDS words behind the count step's),
 // so that the two launches of a list call report side by side.  FOUND: hits / neighbours met.
 enum { LQ_STAT_INVALID = 0, LQ_STAT_OVERFLOW = 1, LQ_STAT_NODES = 2, LQ_STAT_TRIS = 3, LQ_STAT_FOUND = 4, LQ_STAT_WRITTEN = 5, LQ_STAT_INCOMPLETE = 6,
@@ -399,12 +412,18 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u}, side_query{SQ_STAT_WORDS, "side-query", 0u, 1u};
     ListingState hit_query{"hit-query"}, neighbor_query{"neighbor-query"};  // rt_count / fill / list_ray_hits_device, rt_count / fill / list_neighbors_device
     ListingState overlap_query{"overlap-query"};                            // rt_count / fill / list_overlaps_device
+    QueryState segment_query{SG_STAT_WORDS, "overlap-segments", 0u, 0u};    // rt_overlap_segments_device: a flat kernel, no stack (the block's stream heads stay unused)
     rt_ray_query_stats ray_query_stats{};
     rt_point_query_stats point_query_stats{};
     rt_side_query_stats side_query_stats{};
     rt_hit_query_stats hit_query_stats{};
     rt_neighbor_query_stats neighbor_query_stats{};
     rt_overlap_query_stats overlap_query_stats{};
+    rt_overlap_segment_stats segment_stats{};
+    // rt_overlap_segments_device: original triangle index -> leaf position of the current mesh, rewritten by every call; the context's own
+    // (a DeviceMesh is shared read-only, §6.12); grows by size class, first use only
+    DevPtr<uint32_t> d_tri_inverse;
+    size_t tri_inverse_words = 0;
     // the listing kinds' scan: the 64-bit count column (n + 1), the scan's tile sums and its total; grows by size class, first use only
     DevPtr<unsigned long long> d_list_scan;
     size_t list_scan_words = 0;
@@ -526,6 +545,9 @@ int launch_pt_query_neighbors(Ctx* c, const PtScene& sc, const NeighborQuery& q,
 // the same two steps of an overlap query (pt_overlap_query.hip)
 int launch_pt_query_overlaps(Ctx* c, const PtScene& sc, const OverlapQuery& q, bool count, bool fill, uint32_t* head, unsigned long long* stats, uint32_t grid,
                              const StackCfg& sk, uint32_t refill_min);
+// pt_overlap_segments.hip: inv[original index] = leaf position over the mesh's records; one lane per entry of an overlap list (stats: SG_STAT_WORDS words)
+int launch_pt_tri_inverse(Ctx* c, const PtScene& sc, uint32_t* inv);
+int launch_pt_overlap_segments(Ctx* c, const PtScene& sc, const SegmentQuery& q, const uint32_t* inv, unsigned long long* stats);
 void pt_free(Ctx* c);
 void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block and events
 

@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, OverlapQueryParams, OverlapQueryStats, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
+from ._lib import (Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, OverlapQueryParams, OverlapQueryStats, OverlapSegmentStats, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
                    RtError, SideQueryParams, SideQueryStats, Stats)
 
 # src/main.rs:343-364
@@ -849,6 +849,47 @@ class Renderer:
         overlaps_written, incomplete_triangles, slice_overflow, nodes_visited, tris_tested (count_traversal=True only; records fetched),
         stack_overflow, launches, ms."""
         return self._query_stats(OverlapQueryStats(), "rt_get_overlap_query_stats")
+
+    def overlap_segments(self, tris, offsets, tri, capacity=None, out=None, sync=True, want_ends=False):
+        """Where does each listed pair intersect?  (rt_overlap_segments_device)  tris as for list_overlaps; offsets
+        (int64, n + 1) and tri (int32) are the tensors list_overlaps returned for them on the current mesh.  Returns seg, a float32
+        tensor of shape (capacity, 2, 3): entry k holds the two endpoints of the segment in which query triangle i (offsets[i] <= k <
+        offsets[i + 1]) and mesh triangle tri[k] intersect, computed on the device from the resident records in the arithmetic that
+        produced the edge mask (csrc/tri_section.h).  An entry with one bit in its mask is a touch: the same point twice.
+        want_ends=True: returns (seg, ends); ends[k] (int32) = b | (c << 3), the mask bits of the edges the first and the second
+        endpoint lie on (c = b for a touch).  capacity=None means len(tri); tri must hold at least capacity elements.  Entries
+        from min(offsets[n], capacity) on, and those of a slice that ends beyond the capacity, are left as they are; an entry that
+        is not the library's (no owner, an index outside the mesh, no bit set) gets NaNs and ends = -1.  out: the tensor seg - or
+        (seg, ends) with want_ends - to fill instead of new ones.  sync as for query_rays; overlap_segment_stats() reports."""
+        import torch
+
+        flat, n = self._tri_rows(tris)
+        self._device_i64(offsets, "offsets", n + 1)
+        if not isinstance(tri, torch.Tensor) or tri.dim() != 1:
+            raise ValueError(f"tri must be a torch tensor of one dimension, got {type(tri).__name__}")
+        capacity = tri.numel() if capacity is None else int(capacity)
+        if capacity < 0:
+            raise ValueError(f"capacity must be >= 0, got {capacity}")
+        if tri.numel() < capacity:
+            raise ValueError(f"tri must hold at least capacity = {capacity} elements, got {tri.numel()}")
+        self._device_i32(tri, "tri", tri.numel())
+        if out is not None and want_ends and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError("out must be (seg, ends) with want_ends=True")
+        seg, ends = (out if want_ends else (out, None)) if out is not None else (None, None)
+        if isinstance(seg, torch.Tensor) and seg.dim() == 3 and tuple(seg.shape[1:]) == (2, 3) and seg.is_contiguous():
+            seg = seg.view(-1, 6)
+        seg = self._query_out(seg, "out seg", capacity, torch.float32, tris.device, cols=6)
+        if want_ends:
+            ends = self._query_out(ends, "out ends", capacity, torch.int32, tris.device)
+        if n and capacity:
+            self._query_call(sync, self._lib.rt_overlap_segments_device, flat, n, offsets, capacity, tri, seg, ends)
+        seg = seg.view(capacity, 2, 3)
+        return (seg, ends) if want_ends else seg
+
+    def overlap_segment_stats(self):
+        """rt_overlap_segment_stats of the last overlap_segments call as a dict (waits for it): entries, segments, touches,
+        skipped_incomplete, bad_entries, launches, ms."""
+        return self._query_stats(OverlapSegmentStats(), "rt_get_overlap_segment_stats")
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
         """Test hook (query_rays is the product entry): closest hit (t, original triangle index) or occlusion flags for a ray batch;
