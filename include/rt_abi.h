@@ -777,6 +777,43 @@ int rt_overlap_segments_device(rt_ctx* ctx, const void* tris_dev, uint32_t n, co
                                const void* tri_dev /* int32 */, void* seg_out_dev /* capacity x 6 f32 */,
                                void* ends_out_dev /* capacity int32, may be NULL */);
 int rt_get_overlap_segment_stats(rt_ctx* ctx, rt_overlap_segment_stats* stats); /* synchronises the stream; the last call */
+/* Clearance queries on device arrays: how far is each of n caller-supplied triangles from the current mesh, which
+ * mesh triangle is nearest, and where are the two nearest points?  Enqueued on the context's stream behind the work already there;
+ * no host synchronisation, and no allocation after the first query of a mesh or size class.  tris_dev: n x 9 f32 (the three vertices,
+ * rt_set_mesh's layout), rmax_dev: n f32 or NULL, device memory of the context's device, only read.  The arithmetic is
+ * csrc/tri_dist.h, fp32 only, on the resident record words v0, e1, e2 of each mesh triangle T and the vertices A0, A1, A2 of query
+ * triangle i, F1 = A1 - A0, F2 = A2 - A0:  a pair's d2 is the smallest d2 = |a - c|^2 (fp32) of up to twenty-one candidates, with
+ * a = A0 + uq F1 + vq F2 and c = v0 + um e1 + vm e2 points of the two closed triangles, the earlier candidate winning a tie - where
+ * one of the six segment tests of rt_list_overlaps_device accepts (cand and its mask bit), the point at t on that edge and the point
+ * at (u / det, v / det) in the pierced triangle: for triangles that intersect, the pierce point twice and d2 = 0 or a rounding of it;
+ * each corner of one triangle against the other (csrc/point_tri.h's closest_on_tri); each edge of one against each edge of the other
+ * (the closest points of two clamped segments).  A test only proposes its pair: what counts is the d2 the pair evaluates to, so a
+ * query triangle without area (a segment, a point), whose tests decide on rounding noise, is answered as well.  The answer for triangle i is the
+ * lexicographic minimum of (d2, original triangle index) over all mesh triangles with d2 < rmax[i] * rmax[i] (strict; the product is
+ * formed in fp32; without rmax_dev the limit is +inf).  tri_out_dev[i] = the original triangle index (i32); dist_out_dev[i] =
+ * sqrt(d2), correctly rounded; point_query_out_dev / point_mesh_out_dev (n x 3 f32 each, either may be NULL) = a and c.  A miss
+ * (nothing within the limit) is RT_POINT_MISS, +inf and NaNs; !(rmax > 0) and an rmax whose square underflows to 0 miss without a
+ * walk.  A triangle with a non-finite coordinate, a NaN rmax, or a coordinate beyond 32 x max(1, largest |vertex coordinate| of the
+ * mesh) is not answered: tri_out = RT_RAY_INVALID, NaNs, counted in invalid_triangles.  Coplanar pairs that overlap are not "cut"
+ * (the overlap test refuses them): their distance is the candidates', which is 0 or a rounding of it.  Nothing beyond element n - 1
+ * of an output is written.  Lifetime rules, meshes (every kind; the mesh is only read, a shared mesh stays shared) and errors are
+ * rt_query_points_device's, all before anything is enqueued or written.  n == 0: RT_OK, nothing is done. */
+typedef struct rt_clearance_query_params {
+    uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_point_query_params */
+    uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
+} rt_clearance_query_params;
+typedef struct rt_clearance_query_stats {
+    uint64_t queries, invalid_triangles; /* the last query with n > 0: triangles asked, triangles answered RT_RAY_INVALID */
+    uint64_t nodes_visited, tris_tested; /* count_traversal = 1 only: node records fetched, triangle records fetched, over all queries */
+    uint32_t stack_overflow;             /* must be 0 */
+    float ms;                            /* HIP-event time of its launch */
+} rt_clearance_query_stats;
+int rt_default_clearance_query_params(rt_clearance_query_params* p);
+int rt_query_clearance_device(rt_ctx* ctx, const void* tris_dev, const void* rmax_dev /* may be NULL */, uint32_t n,
+                              const rt_clearance_query_params* params /* NULL = defaults */, void* tri_out_dev /* i32 n */,
+                              void* dist_out_dev /* f32 n */, void* point_query_out_dev /* f32 3n, may be NULL */,
+                              void* point_mesh_out_dev /* f32 3n, may be NULL */);
+int rt_get_clearance_query_stats(rt_ctx* ctx, rt_clearance_query_stats* stats); /* synchronises the stream; the last query */
 /* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */

@@ -185,6 +185,18 @@ class OverlapSegmentStats(C.Structure):  # rt_overlap_segment_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ClearanceQueryParams(C.Structure):  # rt_clearance_query_params
+    _fields_ = _TUNE_AND_COUNT
+
+
+class ClearanceQueryStats(C.Structure):  # rt_clearance_query_stats
+    _fields_ = [("queries", C.c_uint64), ("invalid_triangles", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
+                ("stack_overflow", C.c_uint32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 assert C.sizeof(MutableData) == 656 and C.sizeof(Material) == 32 and C.sizeof(Object) == 16 and C.sizeof(Light) == 32
 
 # every symbol include/rt_abi.h declares: name -> (restype, argtypes)
@@ -267,6 +279,9 @@ PROTOTYPES = {
     "rt_get_overlap_query_stats": (C.c_int, [_vp, C.POINTER(OverlapQueryStats)]),
     "rt_overlap_segments_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
     "rt_get_overlap_segment_stats": (C.c_int, [_vp, C.POINTER(OverlapSegmentStats)]),
+    "rt_default_clearance_query_params": (C.c_int, [C.POINTER(ClearanceQueryParams)]),
+    "rt_query_clearance_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(ClearanceQueryParams), _vp, _vp, _vp, _vp]),
+    "rt_get_clearance_query_stats": (C.c_int, [_vp, C.POINTER(ClearanceQueryStats)]),
     "rt_trace_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32)]),
     "rt_trace_rays_counted": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32), _u32p]),
 }

@@ -1,6 +1,6 @@
 // rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14),
 // sides (§6.15), all hits (§6.16), neighbours (§6.17), the attribute variants of the first two (§6.18), overlaps (§6.20) and their
-// segments (§6.21: a flat kernel over a list, with a prologue and an enqueue of its own at the end of this file).
+// segments (§6.21: a flat kernel over a list, with a prologue and an enqueue of its own at the end of this file), clearance (§6.22).
 // A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here: the
 // parameter checks and the prologue of an entry (enter_query), the plan and the enqueue (prepare_query, run_query), the read-back.
 // The listing kinds - all hits, neighbours, overlaps - are a description each (HitKind, NeighborKind, OverlapKind); their protocol of a count step, a fill
@@ -480,7 +480,7 @@ void query_free(Ctx* c) {
     c->pt.d_tri_inverse.reset();
     c->pt.tri_inverse_words = 0;
     for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query.qs, &c->pt.neighbor_query.qs,
-                           &c->pt.overlap_query.qs, &c->pt.segment_query}) {
+                           &c->pt.overlap_query.qs, &c->pt.segment_query, &c->pt.clearance_query}) {
         qs->block.reset();
         for (hipEvent_t& e : qs->ev) {
             if (e) (void)hipEventDestroy(e);
@@ -717,6 +717,65 @@ int rt_overlap_segments_device(rt_ctx* ctx, const void* tris, uint32_t n, const 
     qs.pending = true;
     pt.segment_stats = rt_overlap_segment_stats{};
     pt.segment_stats.launches = 2;
+    return RT_OK;
+}
+
+// ---- clearance: the single-answer kinds' path - enter_query, the array checks, prepare_query, run_query ----
+int rt_default_clearance_query_params(rt_clearance_query_params* p) { return default_params(p); }
+
+int rt_query_clearance_device(rt_ctx* ctx, const void* tris, const void* rmax, uint32_t n, const rt_clearance_query_params* prm, void* tri_out, void* dist_out,
+                              void* point_query_out, void* point_mesh_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_clearance_query_params defaults{};
+    int done;
+    if (int rc = enter_query(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, tris, (size_t)n * 36, "tris_dev")) return rc;
+    if (rmax)
+        if (int rc = rt::check_device_array(c, rmax, (size_t)n * 4, "rmax_dev")) return rc;
+    if (int rc = rt::check_device_array(c, tri_out, (size_t)n * 4, "tri_out_dev")) return rc;
+    if (int rc = rt::check_device_array(c, dist_out, (size_t)n * 4, "dist_out_dev")) return rc;
+    if (point_query_out)
+        if (int rc = rt::check_device_array(c, point_query_out, (size_t)n * 12, "point_query_out_dev")) return rc;
+    if (point_mesh_out)
+        if (int rc = rt::check_device_array(c, point_mesh_out, (size_t)n * 12, "point_mesh_out_dev")) return rc;
+    rt::ClearanceQuery q{};
+    q.tris = static_cast<const float*>(tris);
+    q.rmax = static_cast<const float*>(rmax);
+    q.tri_out = static_cast<int*>(tri_out);
+    q.dist_out = static_cast<float*>(dist_out);
+    q.point_query_out = static_cast<float*>(point_query_out);
+    q.point_mesh_out = static_cast<float*>(point_mesh_out);
+    q.n = n;
+    q.reach = rt::kCameraReach * mesh.maxabs;
+    QueryPlan plan{};
+    // the points' walk: point_stack_need entries per lane; the grid is what the kernel's register budget keeps resident
+    if (int rc = prepare_query(c, c->pt.clearance_query, n, *prm, rt::point_stack_need(mesh.depth), &plan)) return rc;
+    plan.grid = std::min<uint32_t>(plan.grid, (uint32_t)c->n_cus * (uint32_t)rt::kClearanceWaves);
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_clearance(c, rt::scene_view(mesh), q, prm->count_traversal != 0u, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
+    };
+    if (int rc = run_query(c, c->pt.clearance_query, plan, "rt.path_b.query_clearance", launch)) return rc;
+    c->pt.clearance_query_stats = rt_clearance_query_stats{};
+    c->pt.clearance_query_stats.queries = n;
+    return RT_OK;
+}
+
+int rt_get_clearance_query_stats(rt_ctx* ctx, rt_clearance_query_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    rt_clearance_query_stats& s = c->pt.clearance_query_stats;
+    if (c->pt.clearance_query.pending) {
+        unsigned long long st[rt::CQ_STAT_WORDS] = {};
+        if (int rc = read_query(c, c->pt.clearance_query, st, &s.ms)) return rc;
+        s.invalid_triangles = st[rt::CQ_STAT_INVALID];
+        s.stack_overflow = (uint32_t)st[rt::CQ_STAT_OVERFLOW];
+        s.nodes_visited = st[rt::CQ_STAT_NODES];
+        s.tris_tested = st[rt::CQ_STAT_TRIS];
+    }
+    *stats = s;
     return RT_OK;
 }
 

@@ -310,6 +310,22 @@ struct SegmentQuery {
 };
 // Counters of a segment call (TOUCHES, SKIPPED, BAD in this order: one thread each adds them); segments = entries - the other three
 enum { SG_STAT_ENTRIES = 0, SG_STAT_TOUCHES = 1, SG_STAT_SKIPPED = 2, SG_STAT_BAD = 3, SG_STAT_WORDS = 4 };
+// rt_query_clearance_device: the query triangles of one query and where their answers go.  Triangle i is queue entry i.
+struct ClearanceQuery {
+    const float* tris;       // n x 9: the three vertices, rt_set_mesh's layout
+    const float* rmax;       // n, or nullptr: +inf
+    int* tri_out;            // n
+    float* dist_out;         // n
+    float* point_query_out;  // n x 3, or nullptr: the nearest point on the query triangle
+    float* point_mesh_out;   // n x 3, or nullptr: the nearest point on the mesh triangle
+    uint32_t n;
+    float reach;  // |coordinate| limit: kCameraReach x the mesh's maxabs
+};
+// Counters of a clearance query
+enum { CQ_STAT_INVALID = 0, CQ_STAT_OVERFLOW = 1, CQ_STAT_NODES = 2, CQ_STAT_TRIS = 3, CQ_STAT_WORDS = 4 };
+// Waves per SIMD pt_query_clearance is bounded to, = its workgroups per CU (the compiler's figures: DESIGN.md §6.22); the host caps the
+// persistent grid to it.
+constexpr int kClearanceWaves = 4;
 // Counters of a listing query (all hits, neighbours, overlaps): one set per step (the fill step's LQ_STEP_WORDS words behind the count step's),
 // so that the two launches of a list call report side by side.  FOUND: hits / neighbours met.
 enum { LQ_STAT_INVALID = 0, LQ_STAT_OVERFLOW = 1, LQ_STAT_NODES = 2, LQ_STAT_TRIS = 3, LQ_STAT_FOUND = 4, LQ_STAT_WRITTEN = 5, LQ_STAT_INCOMPLETE = 6,
@@ -413,6 +429,7 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     ListingState hit_query{"hit-query"}, neighbor_query{"neighbor-query"};  // rt_count / fill / list_ray_hits_device, rt_count / fill / list_neighbors_device
     ListingState overlap_query{"overlap-query"};                            // rt_count / fill / list_overlaps_device
     QueryState segment_query{SG_STAT_WORDS, "overlap-segments", 0u, 0u};    // rt_overlap_segments_device: a flat kernel, no stack (the block's stream heads stay unused)
+    QueryState clearance_query{CQ_STAT_WORDS, "clearance-query", 0u, 1u};   // rt_query_clearance_device: the points' walk, one set of columns
     rt_ray_query_stats ray_query_stats{};
     rt_point_query_stats point_query_stats{};
     rt_side_query_stats side_query_stats{};
@@ -420,6 +437,7 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     rt_neighbor_query_stats neighbor_query_stats{};
     rt_overlap_query_stats overlap_query_stats{};
     rt_overlap_segment_stats segment_stats{};
+    rt_clearance_query_stats clearance_query_stats{};
     // rt_overlap_segments_device: original triangle index -> leaf position of the current mesh, rewritten by every call; the context's own
     // (a DeviceMesh is shared read-only, §6.12); grows by size class, first use only
     DevPtr<uint32_t> d_tri_inverse;
@@ -548,6 +566,9 @@ int launch_pt_query_overlaps(Ctx* c, const PtScene& sc, const OverlapQuery& q, b
 // pt_overlap_segments.hip: inv[original index] = leaf position over the mesh's records; one lane per entry of an overlap list (stats: SG_STAT_WORDS words)
 int launch_pt_tri_inverse(Ctx* c, const PtScene& sc, uint32_t* inv);
 int launch_pt_overlap_segments(Ctx* c, const PtScene& sc, const SegmentQuery& q, const uint32_t* inv, unsigned long long* stats);
+// pt_clearance_query.hip: the persistent refilling clearance kernel (stats: CQ_STAT_WORDS words)
+int launch_pt_query_clearance(Ctx* c, const PtScene& sc, const ClearanceQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
+                              const StackCfg& sk, uint32_t refill_min);
 void pt_free(Ctx* c);
 void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block and events
 

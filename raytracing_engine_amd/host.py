@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, OverlapQueryParams, OverlapQueryStats, OverlapSegmentStats, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
+from ._lib import (ClearanceQueryParams, ClearanceQueryStats, Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, OverlapQueryParams, OverlapQueryStats, OverlapSegmentStats, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
                    RtError, SideQueryParams, SideQueryStats, Stats)
 
 # src/main.rs:343-364
@@ -465,7 +465,7 @@ class Renderer:
         self._device_ints(t, name, n, "int64")
 
     def _query_tune(self, params, tune, method):
-        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors / count_overlaps / list_overlaps) into its parameter struct;
+        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors / count_overlaps / list_overlaps / query_clearance) into its parameter struct;
         TypeError for any other keyword."""
         for k, v in tune.items():
             if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
@@ -890,6 +890,41 @@ class Renderer:
         """rt_overlap_segment_stats of the last overlap_segments call as a dict (waits for it): entries, segments, touches,
         skipped_incomplete, bad_entries, launches, ms."""
         return self._query_stats(OverlapSegmentStats(), "rt_get_overlap_segment_stats")
+
+    def query_clearance(self, tris, rmax=None, out=None, sync=True, want_points=True, count_traversal=False, **tune):
+        """How far is each query triangle from the current mesh, which mesh triangle is nearest, and where are the two nearest points?
+        (rt_query_clearance_device)  tris as for count_overlaps: a float32 torch tensor on this renderer's device,
+        contiguous, (n, 9), (n, 3, 3) or flat; rmax: (n,) or None - only mesh triangles nearer than rmax count (strictly; default +inf).
+        Returns (dist, tri, point_query, point_mesh): float32 distances (+inf on a miss; 0 or a rounding of it where the triangles
+        intersect), int32 original triangle indices (POINT_MISS = -1), and the (n, 3) nearest points on the query triangle and on mesh
+        triangle tri (NaN on a miss), or None in their place with want_points=False.  Invalid triangles (a non-finite coordinate, a
+        NaN rmax, a coordinate beyond 32 x the mesh's largest |coordinate|) get RAY_INVALID = -2 and NaNs.  out: the tensors to fill -
+        (dist, tri, point_query, point_mesh), or (dist, tri) with want_points=False - instead of new ones.  sync as for query_rays.
+        count_traversal=True: clearance_query_stats() reports nodes_visited / tris_tested.  tune: tune_refill_min, tune_blocks_per_cu,
+        tune_lds_stack, tune_max_blocks of rt_clearance_query_params."""
+        import torch
+
+        flat, n = self._tri_rows(tris)
+        if rmax is not None and (self._device_rows(rmax, "rmax", 1) != n or rmax.dim() != 1):
+            raise ValueError(f"rmax must have shape ({n},), got {tuple(rmax.shape)}")
+        p = ClearanceQueryParams()
+        p.count_traversal = int(bool(count_traversal))
+        self._query_tune(p, tune, "query_clearance")
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != (4 if want_points else 2)):
+            raise ValueError("out must be (dist, tri, point_query, point_mesh), or the pair (dist, tri) with want_points=False")
+        dist, tri, pq, pm = (tuple(out) + (None, None))[:4] if out is not None else (None,) * 4
+        dist = self._query_out(dist, "out dist", n, torch.float32, tris.device)
+        tri = self._query_out(tri, "out tri", n, torch.int32, tris.device)
+        if want_points:
+            pq = self._query_out(pq, "out point_query", n, torch.float32, tris.device, cols=3)
+            pm = self._query_out(pm, "out point_mesh", n, torch.float32, tris.device, cols=3)
+        self._query_call(sync, self._lib.rt_query_clearance_device, flat, rmax, n, C.byref(p), tri, dist, pq, pm)
+        return dist, tri, pq, pm
+
+    def clearance_query_stats(self):
+        """rt_clearance_query_stats of the last clearance query as a dict (waits for it): queries, invalid_triangles, nodes_visited,
+        tris_tested (count_traversal=True only; records fetched), stack_overflow, ms."""
+        return self._query_stats(ClearanceQueryStats(), "rt_get_clearance_query_stats")
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
         """Test hook (query_rays is the product entry): closest hit (t, original triangle index) or occlusion flags for a ray batch;
