@@ -1,5 +1,6 @@
 // pt_packet.hip — path B: the packet kernels for camera rays, pt_trace_packet (per-ray slab tests of all eight children) and
-// pt_trace_packet_ia (interval test for the pass first), with the generate stage fused (stage map: path_b.hip).  A whole wave walks
+// pt_trace_packet_ia (interval test for the pass first) and pt_trace_packet_wide (the interval test alone, two or four rays per lane: the
+// default), with the generate stage fused (stage map: path_b.hip).  A whole wave walks
 // the tree together, so nothing of the per-lane node step or queue is used: from pt_traverse.h only the triangle tests, safe_inv,
 // octant_inv and Hit; the camera ray is pt_camera.h's.
 #include "pt_camera.h"
@@ -377,6 +378,170 @@ __global__ __launch_bounds__(256) void pt_trace_packet_ia(const PtScene sc, cons
     packet_finish<COUNT>(st, stats, pid, lane, alive, best, n_nodes, n_tris, overflow);
 }
 
+// ---- packet trace, interval form, R rays per lane ------------------------------------------------------
+// pt_trace_packet_ia<COUNT, PURE = true, FARCAP = true> with R consecutive 64-path groups in one wave: wave w walks the tree once for
+// paths [w * 64R, (w + 1) * 64R), lane l holds paths base + l + 64r (r < R) - with the Morton slots at 4 spp an 8x4 (R = 2) or 8x8
+// (R = 4) pixel block, for other sample counts whatever the numbering gives; nothing below depends on it.  Neighbouring 4x4 blocks
+// walk almost the same nodes (a block is far narrower than a bottom-level box), so the node step - header, plane decode, interval
+// test, ds_bpermute, ballot, VGPR stack: all as above - is paid once for R x 64 rays: the interval test works on the pass's range
+// of 1 / d whatever the number of rays, reduced over a lane's R rays first and then across the wave.  Only the triangle test grows
+// with R: the record is loaded once, tri_inside_mask and the division run once per ray index, each with its own lane mask, its own
+// best hit and its own wave-uniform way out.  A pass takes the rays of ONE direction octant among all R x 64; the others wait for a
+// later pass.  Per ray the kernel keeps the direction and the best hit (6 VGPRs); 1 / d is needed for the range only and is
+// recomputed at the head of each pass.  Every ray tests a superset of the triangles its own walk would reach, with its own
+// arithmetic, so its (t, id)-minimal hit - and the frame - is unchanged.
+template <bool COUNT, int R>
+__global__ __launch_bounds__(256) void pt_trace_packet_wide(const PtScene sc, const PtFrame f, PtState st, unsigned long long* __restrict__ stats) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t pid0 = (blockIdx.x * 4u + wv) * (64u * (uint32_t)R) + lane;  // path of ray index r: pid0 + 64 r
+
+    v3 o = mk(0.0f, 0.0f, 0.0f), d[R];
+    Hit best[R];
+    uint32_t ray_bits = 0;  // nibble r: 7 - octant of ray r, bit 3 = the path exists
+    unsigned long long remaining[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        PacketRays pr;
+        const bool alive = packet_camera_ray(f, st, pid0 + 64u * (uint32_t)r, pr);
+        o = pr.o;
+        d[r] = pr.d;
+        best[r] = Hit{__builtin_inff(), -1, 0xffffffffu};
+        ray_bits |= (pr.oct_inv | (alive ? 8u : 0u)) << (4 * r);
+        remaining[r] = __ballot(alive);
+    }
+
+    // lane 8c + k: plane k of child c
+    const uint32_t p_child = lane >> 3, pk = lane & 7u, p_axis = pk & 3u;
+    const bool p_plane = p_axis != 3u, p_far = pk >= 4u;
+    const float o_ax = p_axis == 0u ? o.x : p_axis == 1u ? o.y : o.z;
+    uint32_t n_nodes = 0, n_tris = 0, overflow = 0;  // wave-uniform
+
+    for (;;) {
+        // the pass's octant: that of the first ray still waiting
+        uint32_t oct = 8u;
+#pragma unroll
+        for (int r = R - 1; r >= 0; r--)
+            if (remaining[r]) oct = ((uint32_t)__builtin_amdgcn_readlane((int)ray_bits, (int)__builtin_ctzll(remaining[r])) >> (4 * r)) & 7u;
+        if (oct == 8u) break;
+        unsigned long long act_mask[R];  // wave-uniform, one per ray index
+        const float inf = __builtin_inff();
+        // the pass's range of |1 / d| per axis: over the lane's own rays first, then across the wave
+        float ax0 = inf, ay0 = inf, az0 = inf, ax1 = 0.0f, ay1 = 0.0f, az1 = 0.0f;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const bool act = ((ray_bits >> (4 * r)) & 15u) == (oct | 8u);
+            act_mask[r] = __ballot(act);
+            remaining[r] &= ~act_mask[r];
+            const v3 inv = safe_inv(d[r]);
+            const float ax = __builtin_fabsf(inv.x), ay = __builtin_fabsf(inv.y), az = __builtin_fabsf(inv.z);
+            ax0 = fmin_(ax0, act ? ax : inf), ax1 = fmax_(ax1, act ? ax : 0.0f);
+            ay0 = fmin_(ay0, act ? ay : inf), ay1 = fmax_(ay1, act ? ay : 0.0f);
+            az0 = fmin_(az0, act ? az : inf), az1 = fmax_(az1, act ? az : 0.0f);
+        }
+        const float ix0 = wave_reduce_nonneg<false>(ax0), ix1 = wave_reduce_nonneg<true>(ax1);
+        const float iy0 = wave_reduce_nonneg<false>(ay0), iy1 = wave_reduce_nonneg<true>(ay1);
+        const float iz0 = wave_reduce_nonneg<false>(az0), iz1 = wave_reduce_nonneg<true>(az1);
+        // from here to the triangle loop: pt_trace_packet_ia's pass, PURE and FARCAP (the comments are there)
+        const float i_sign = ((oct >> (2u - (p_axis < 2u ? p_axis : 2u))) & 1u) != 0u ? 1.0f : -1.0f;
+        const float imin = i_sign * (p_axis == 0u ? ix0 : p_axis == 1u ? iy0 : iz0), imax = i_sign * (p_axis == 0u ? ix1 : p_axis == 1u ? iy1 : iz1);
+        const float ia_a = p_plane ? (p_far ? -imin : imin) : 0.0f, ia_b = p_plane ? (p_far ? -imax : imax) : 0.0f;
+        float ia_m = p_plane ? (__builtin_fabsf(o_ax) * fmax_(__builtin_fabsf(imin), __builtin_fabsf(imax))) * 0x1p-22f : (pk == 3u ? 0.0f : inf);
+        const bool dir_pos = p_plane && ((oct >> (2u - p_axis)) & 1u) != 0u;
+        const uint32_t q_off = p_plane ? 32u + (p_far == dir_pos ? 24u : 0u) + p_axis * 8u + p_child : 32u + p_child;
+        const uint32_t v_slot = lane < 8u ? lane ^ oct : lane & 7u;
+        const uint32_t v_addr = lane < 16u ? v_slot * 32u : 0u;
+        const uint32_t v_sh = lane < 8u ? 31u - v_slot : lane < 16u ? 31u - lane : 0u;
+        const uint32_t s_sh = 23u - 8u * (p_axis < 2u ? p_axis : 2u);
+        const float w_x = p_axis == 0u ? 1.0f : 0.0f, w_y = p_axis == 1u ? 1.0f : 0.0f, w_z = p_axis >= 2u ? 1.0f : 0.0f;
+
+        int stx = 0, sty = 0;  // entry 0 = (0, 0): the end marker
+        uint32_t sp = 1, sp_max = 0;
+        uint32_t gx = 0u, gy = 0x80000000u;  // the root group
+        for (;;) {
+        do {
+            const uint32_t lz = (uint32_t)__builtin_clz(gy);
+            const uint32_t hits = gy;
+            gy &= ~(0x80000000u >> lz);
+            if (gy > 0x00ffffffu) {  // remaining siblings
+                uint32_t m0_saved;
+                asm("s_mov_b32 %2, m0\n\ts_mov_b32 m0, %5\n\tv_writelane_b32 %0, %3, m0\n\tv_writelane_b32 %1, %4, m0\n\ts_mov_b32 m0, %2"
+                    : "+v"(stx), "+v"(sty), "=&s"(m0_saved)
+                    : "s"(gx), "s"(gy), "s"(sp));
+                sp++;
+                sp_max = sp_max > sp ? sp_max : sp;
+            }
+            const uint32_t slot = (7u - lz) ^ oct;
+            const uint32_t node = gx + (uint32_t)__builtin_popcount(hits & ((1u << slot) - 1u));
+            const uint32_t* __restrict__ nd = reinterpret_cast<const uint32_t*>(sc.nodes) + (size_t)uniform(node) * 20u;
+            if (COUNT) n_nodes++;
+            const uint32_t q = reinterpret_cast<const uint8_t*>(nd)[q_off];  // issued ahead of the header's wait
+            u32x8 hdr;
+            asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(hdr) : "s"(nd) : "memory");
+            const float px_ = __uint_as_float(hdr[0]), py_ = __uint_as_float(hdr[1]), pz_ = __uint_as_float(hdr[2]);
+            const uint32_t w3 = hdr[3], child_base = hdr[4], tri_base = hdr[5], leafmask = hdr[6] & 0xffu;
+            const uint32_t imask = w3 >> 24;
+            const float ps = __uint_as_float((w3 << s_sh) & 0x7f800000u);
+            const float pp = __builtin_fmaf(w_z, pz_, __builtin_fmaf(w_y, py_, w_x * px_));
+            const float plane = __builtin_fmaf((float)q, ps, pp);
+            const float u = plane - o_ax;
+            const float lo = fmin_(u * ia_a, u * ia_b);
+            float qm = __builtin_fmaf(__builtin_fabsf(lo), -0x1p-21f, lo - ia_m);
+            RT_DPP_MAX(qm, "quad_perm:[1,0,3,2]");
+            RT_DPP_MAX(qm, "quad_perm:[2,3,0,1]");
+            float gap;
+            asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf" : "=v"(gap) : "v"(qm));
+            const float gap_c = __int_as_float(__builtin_amdgcn_ds_bpermute((int)v_addr, __float_as_int(gap)));
+            const uint32_t masks = imask | (leafmask << 8);
+            const uint32_t verdict = (uint32_t)__builtin_amdgcn_ballot_w64(gap_c <= 0.0f) & (uint32_t)__builtin_amdgcn_ballot_w64((int)(masks << v_sh) < 0);
+            const uint32_t any = verdict >> 8, inner_hits = verdict << 24;
+            unsigned long long improved = 0ull;  // wave-uniform: lanes one of whose best hits moved at this node
+            for (uint32_t lh = any & leafmask; lh; lh &= lh - 1u) {  // the single triangles of the leaf slots that are entered
+                const uint32_t c = (uint32_t)__builtin_ctz(lh);
+                const uint32_t li = tri_base + (uint32_t)__builtin_popcount(leafmask & ((1u << c) - 1u));
+                const float* __restrict__ tp = reinterpret_cast<const float*>(sc.tris) + (size_t)li * 12u;  // wave-uniform address
+                if (COUNT) n_tris++;
+                const v3 v0 = mk(tp[0], tp[1], tp[2]), e1 = mk(tp[3], tp[4], tp[5]), e2 = mk(tp[6], tp[7], tp[8]);
+                const uint32_t id = __float_as_uint(tp[9]);
+#pragma unroll
+                for (int r = 0; r < R; r++) {  // one record, every ray index with its own mask and its own way out
+                    float det;
+                    v3 qvec;
+                    const unsigned long long inside = tri_inside_mask(o, d[r], v0, e1, e2, act_mask[r], det, qvec);
+                    if (inside == 0ull) continue;
+                    const float t = dot(e2, qvec) / det;
+                    const unsigned long long closer = __builtin_amdgcn_ballot_w64(t < best[r].t) | (__builtin_amdgcn_ballot_w64(t == best[r].t) & __builtin_amdgcn_ballot_w64(id < best[r].id));
+                    const unsigned long long take = inside & __builtin_amdgcn_ballot_w64(t > 0.0f) & closer;
+                    improved |= take;
+                    const bool mine = __builtin_amdgcn_inverse_ballot_w64(take);
+                    best[r].t = mine ? t : best[r].t;
+                    best[r].li = mine ? (int)li : best[r].li;
+                    best[r].id = mine ? id : best[r].id;
+                }
+            }
+            if (improved != 0ull) {  // the cap: the farthest best hit of the pass's rays
+                float far = 0.0f;
+#pragma unroll
+                for (int r = 0; r < R; r++) far = fmax_(far, __builtin_amdgcn_inverse_ballot_w64(act_mask[r]) ? best[r].t : 0.0f);
+                const float maxbest = wave_reduce_nonneg<true>(far);
+                if (pk == 7u) ia_m = maxbest;
+            }
+            gx = child_base;
+            gy = inner_hits | imask;
+        } while (gy > 0x00ffffffu);
+            // no child entered: on with the newest pending group
+            sp--;
+            gx = (uint32_t)__builtin_amdgcn_readlane(stx, (int)sp);
+            gy = (uint32_t)__builtin_amdgcn_readlane(sty, (int)sp);
+            if (gy == 0u) break;
+        }
+        if (sp_max > 63u) overflow = 1;
+    }
+#pragma unroll
+    for (int r = 1; r < R; r++)
+        if ((ray_bits >> (4 * r)) & 8u) st.hit[pid0 + 64u * (uint32_t)r] = make_float2(best[r].t, __int_as_float(best[r].li));
+    packet_finish<COUNT>(st, stats, pid0, lane, (ray_bits & 8u) != 0u, best[0], n_nodes, n_tris, overflow);  // one walk: counted once
+}
+
 // ---- launchers ------------------------------------------------------------------------------------
 // (PURE, FARCAP) of pt_trace_packet_ia for a tune_no_packet mode other than PACKET_EXACT, as compile-time constants
 template <class F>
@@ -387,9 +552,15 @@ static void with_interval_cfg(uint32_t mode, F&& f) {
 }
 
 int launch_pt_trace_packet(Ctx* c, const PtScene& sc, const PtFrame& f, const PtState& st, unsigned long long* stats, bool count, uint32_t mode) {
-    const dim3 g((f.n_paths + 255u) / 256u), b(256);
+    const uint32_t rays_per_lane = mode == PACKET_WIDE_2 ? 2u : mode == PACKET_WIDE_4 ? 4u : 1u;
+    const uint32_t per_block = 256u * rays_per_lane;
+    const dim3 g((f.n_paths + per_block - 1u) / per_block), b(256);
     with_bool(count, [&](auto cnt) {
-        if (mode == PACKET_EXACT) {
+        if (mode == PACKET_WIDE_2) {
+            hipLaunchKernelGGL((pt_trace_packet_wide<decltype(cnt)::value, 2>), g, b, 0, c->stream, sc, f, st, stats);
+        } else if (mode == PACKET_WIDE_4) {
+            hipLaunchKernelGGL((pt_trace_packet_wide<decltype(cnt)::value, 4>), g, b, 0, c->stream, sc, f, st, stats);
+        } else if (mode == PACKET_EXACT) {
             hipLaunchKernelGGL(pt_trace_packet<decltype(cnt)::value>, g, b, 0, c->stream, sc, f, st, stats);
         } else {
             with_interval_cfg(mode, [&](auto pure, auto farcap) {

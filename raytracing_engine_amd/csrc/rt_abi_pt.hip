@@ -18,7 +18,9 @@ namespace {
 
 constexpr uint64_t kMaxPathsInFlight = 1ull << 25;  // 33.5 M paths = 4.3 GB of wavefront state
 constexpr uint32_t kMaxBounces = 15;
-constexpr uint32_t kDefaultPacketMode = rt::PACKET_INTERVAL_ONLY;
+// chosen on the headline scene among the interval-only walk with 1, 2 and 4 rays per lane (profiles/packet_wide.txt): 2 and 4 both beat 1
+// by the gain gate; 4 over 2 is inside the run-to-run spread with three frame lanes and costs the context scenes 6 % (2: under 1 %)
+constexpr uint32_t kDefaultPacketMode = rt::PACKET_WIDE_2;
 constexpr uint32_t kDefaultTriMode = rt::TRI_MODE_INLINE;  // rt_pt_params.tune_tri_mode = 0
 void free_wavefront(PtData& pt) {
     for (auto& mem : pt.wavefront) mem.reset();

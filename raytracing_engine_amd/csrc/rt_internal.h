@@ -158,7 +158,8 @@ struct PtScene {
 constexpr uint32_t kPacketStackEntries = 40;  // pt_trace_packet's LDS stack of node groups (pt_packet.hip)
 // rt_pt_params.tune_no_packet: 0 = default, 1 = no packet kernel (camera rays through the per-lane kernel), then the packet kernel's node test:
 // per-ray slab tests of all eight children; interval test for the pass, per-ray tests of the children that pass; interval test only; the second without the best-hit cap
-enum { PACKET_DEFAULT = 0, PACKET_OFF = 1, PACKET_EXACT = 2, PACKET_INTERVAL = 3, PACKET_INTERVAL_ONLY = 4, PACKET_INTERVAL_NOCAP = 5 };
+// 6 / 7: the interval test only, with 2 / 4 rays per lane: one tree walk per 128 / 256 camera rays (pt_trace_packet_wide)
+enum { PACKET_DEFAULT = 0, PACKET_OFF = 1, PACKET_EXACT = 2, PACKET_INTERVAL = 3, PACKET_INTERVAL_ONLY = 4, PACKET_INTERVAL_NOCAP = 5, PACKET_WIDE_2 = 6, PACKET_WIDE_4 = 7 };
 enum { TRI_MODE_INLINE = 1, TRI_MODE_POOL = 2, TRI_MODE_DEFER = 3, TRI_MODE_INLINE_PF = 4 };  // rt_pt_params.tune_tri_mode, byte 0 (pt_trace.hip: TRI_INLINE, TRI_POOL)
 
 struct StackCfg {  // per-lane traversal stack of 8-byte entries: lds_cap in LDS, then spill_cap in global memory
