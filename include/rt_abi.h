@@ -815,6 +815,41 @@ int rt_query_clearance_device(rt_ctx* ctx, const void* tris_dev, const void* rma
                               void* dist_out_dev /* f32 n */, void* point_query_out_dev /* f32 3n, may be NULL */,
                               void* point_mesh_out_dev /* f32 3n, may be NULL */);
 int rt_get_clearance_query_stats(rt_ctx* ctx, rt_clearance_query_stats* stats); /* synchronises the stream; the last query */
+/* k-nearest queries on device arrays: the k triangles of the current mesh nearest to each of n caller-supplied
+ * points, sorted, as rectangular n x k outputs from one walk.  Enqueued on the context's stream behind the work already there; no
+ * host synchronisation, and no allocation after the first query of a mesh or size class.  points_dev: n x 3 f32, rmax_dev: n f32 or
+ * NULL, device memory of the context's device, only read.  With limit2 = rmax[i] * rmax[i] (one fp32 product; +inf without
+ * rmax_dev), near(i) is rt_list_neighbors_device's list: every triangle with d2 < limit2 (strictly), d2 = the fp32 squared distance
+ * of csrc/point_tri.h on the resident record, sorted ascending by (d2, original triangle index).  Row i is the first
+ * count = min(k, |near(i)|) entries of that list: dist_out_dev[i * k + j] = sqrt(d2), correctly rounded, tri_out_dev[i * k + j] =
+ * the original triangle index (i32); an exact tie at the cut keeps the lower index; only triangles with a finite d2 appear.  k = 1 is
+ * bit for bit rt_query_points_device's (dist, tri); every row is a prefix of rt_list_neighbors_device's slice for the same rmax.
+ * Entries at and beyond count are +inf and RT_POINT_MISS (k above the number of triangles is valid: its rows are short).
+ * count_out_dev (n i32, may be NULL) = count.  !(rmax > 0) and an rmax whose square underflows to 0 give count 0 without a walk.  A
+ * point with a non-finite component, a NaN rmax, or a component beyond 32 x max(1, largest |vertex coordinate| of the mesh) is not
+ * answered: count = RT_POINT_INVALID, its whole row NaN and RT_POINT_INVALID, counted in invalid_points.  Every element of rows
+ * 0 .. n - 1 is written, nothing outside them; rows are addressed with 64 bits (n x k reaches 2^40).  Lifetime rules, meshes (every
+ * kind; the mesh is only read, a shared mesh stays shared) and errors are rt_query_points_device's, and RT_ERR_INVALID also for
+ * k == 0, k above RT_KNN_MAX_K and an output allocation shorter than n x k elements - all before anything is enqueued or written.
+ * n == 0: RT_OK, nothing is done. */
+#define RT_KNN_MAX_K 1024u
+typedef struct rt_knn_query_params {
+    uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_point_query_params */
+    uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
+} rt_knn_query_params;
+typedef struct rt_knn_query_stats {
+    uint64_t points, invalid_points;     /* the last query with n > 0: points asked, points answered RT_POINT_INVALID */
+    uint64_t neighbors;                  /* entries listed over all rows: the sum of max(count, 0) */
+    uint64_t nodes_visited, tris_tested; /* count_traversal = 1 only: node records fetched, triangles tested, over all points */
+    uint32_t stack_overflow;             /* must be 0 */
+    uint32_t launches;                   /* kernel launches of that query */
+    float ms;                            /* HIP-event time of its launch */
+} rt_knn_query_stats;
+int rt_default_knn_query_params(rt_knn_query_params* p);
+int rt_query_knn_device(rt_ctx* ctx, const void* points_dev, const void* rmax_dev /* may be NULL */, uint32_t n, uint32_t k,
+                        const rt_knn_query_params* params /* NULL = defaults */, void* dist_out_dev /* n x k f32 */,
+                        void* tri_out_dev /* n x k i32 */, void* count_out_dev /* n i32, may be NULL */);
+int rt_get_knn_query_stats(rt_ctx* ctx, rt_knn_query_stats* stats); /* synchronises the stream; the last query */
 /* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */

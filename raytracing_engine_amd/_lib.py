@@ -124,6 +124,7 @@ class PointQueryStats(C.Structure):  # rt_point_query_stats
 
 
 POINT_MISS, POINT_INVALID = RAY_MISS, RAY_INVALID  # RT_POINT_MISS, RT_POINT_INVALID
+KNN_MAX_K = 1024  # RT_KNN_MAX_K
 
 
 class SideQueryParams(C.Structure):  # rt_side_query_params
@@ -192,6 +193,18 @@ class ClearanceQueryParams(C.Structure):  # rt_clearance_query_params
 class ClearanceQueryStats(C.Structure):  # rt_clearance_query_stats
     _fields_ = [("queries", C.c_uint64), ("invalid_triangles", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
                 ("stack_overflow", C.c_uint32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class KnnQueryParams(C.Structure):  # rt_knn_query_params
+    _fields_ = _TUNE_AND_COUNT
+
+
+class KnnQueryStats(C.Structure):  # rt_knn_query_stats
+    _fields_ = [("points", C.c_uint64), ("invalid_points", C.c_uint64), ("neighbors", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
+                ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -282,6 +295,9 @@ PROTOTYPES = {
     "rt_default_clearance_query_params": (C.c_int, [C.POINTER(ClearanceQueryParams)]),
     "rt_query_clearance_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(ClearanceQueryParams), _vp, _vp, _vp, _vp]),
     "rt_get_clearance_query_stats": (C.c_int, [_vp, C.POINTER(ClearanceQueryStats)]),
+    "rt_default_knn_query_params": (C.c_int, [C.POINTER(KnnQueryParams)]),
+    "rt_query_knn_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(KnnQueryParams), _vp, _vp, _vp]),
+    "rt_get_knn_query_stats": (C.c_int, [_vp, C.POINTER(KnnQueryStats)]),
     "rt_trace_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32)]),
     "rt_trace_rays_counted": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32), _u32p]),
 }

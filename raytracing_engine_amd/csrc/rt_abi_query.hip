@@ -1,6 +1,7 @@
 // rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14),
 // sides (§6.15), all hits (§6.16), neighbours (§6.17), the attribute variants of the first two (§6.18), overlaps (§6.20) and their
-// segments (§6.21: a flat kernel over a list, with a prologue and an enqueue of its own at the end of this file), clearance (§6.22).
+// segments (§6.21: a flat kernel over a list, with a prologue and an enqueue of its own at the end of this file), clearance (§6.22),
+// k nearest (§6.23).
 // A kind is a parameter struct, its array checks, a launcher and its counters; what the kinds share is written once here: the
 // parameter checks and the prologue of an entry (enter_query), the plan and the enqueue (prepare_query, run_query), the read-back.
 // The listing kinds - all hits, neighbours, overlaps - are a description each (HitKind, NeighborKind, OverlapKind); their protocol of a count step, a fill
@@ -480,7 +481,7 @@ void query_free(Ctx* c) {
     c->pt.d_tri_inverse.reset();
     c->pt.tri_inverse_words = 0;
     for (QueryState* qs : {&c->pt.ray_query, &c->pt.point_query, &c->pt.side_query, &c->pt.hit_query.qs, &c->pt.neighbor_query.qs,
-                           &c->pt.overlap_query.qs, &c->pt.segment_query, &c->pt.clearance_query}) {
+                           &c->pt.overlap_query.qs, &c->pt.segment_query, &c->pt.clearance_query, &c->pt.knn_query}) {
         qs->block.reset();
         for (hipEvent_t& e : qs->ev) {
             if (e) (void)hipEventDestroy(e);
@@ -774,6 +775,64 @@ int rt_get_clearance_query_stats(rt_ctx* ctx, rt_clearance_query_stats* stats) {
         s.stack_overflow = (uint32_t)st[rt::CQ_STAT_OVERFLOW];
         s.nodes_visited = st[rt::CQ_STAT_NODES];
         s.tris_tested = st[rt::CQ_STAT_TRIS];
+    }
+    *stats = s;
+    return RT_OK;
+}
+
+// ---- k nearest: the single-answer kinds' path with rows of k - the parameter checks, k, the array checks, prepare_query, run_query ----
+int rt_default_knn_query_params(rt_knn_query_params* p) { return default_params(p); }
+
+int rt_query_knn_device(rt_ctx* ctx, const void* points, const void* rmax, uint32_t n, uint32_t k, const rt_knn_query_params* prm, void* dist_out, void* tri_out,
+                        void* count_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_knn_query_params defaults{};
+    int done;
+    if (int rc = use_params(c, n, prm, defaults)) return rc;
+    if (k == 0u || k > RT_KNN_MAX_K) return c->fail(RT_ERR_INVALID, "k %u (1 .. %u)", k, RT_KNN_MAX_K);
+    if (int rc = begin_query(c, n, &done)) return rc;
+    if (done) return RT_OK;
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = rt::check_device_array(c, points, (size_t)n * 12, "points_dev")) return rc;
+    if (rmax)
+        if (int rc = rt::check_device_array(c, rmax, (size_t)n * 4, "rmax_dev")) return rc;
+    if (int rc = rt::check_device_array(c, dist_out, (size_t)n * k * 4, "dist_out_dev")) return rc;
+    if (int rc = rt::check_device_array(c, tri_out, (size_t)n * k * 4, "tri_out_dev")) return rc;
+    if (count_out)
+        if (int rc = rt::check_device_array(c, count_out, (size_t)n * 4, "count_out_dev")) return rc;
+    rt::KnnQuery q{};
+    q.points = static_cast<const float*>(points);
+    q.rmax = static_cast<const float*>(rmax);
+    q.dist_out = static_cast<float*>(dist_out);
+    q.tri_out = static_cast<int*>(tri_out);
+    q.count_out = static_cast<int*>(count_out);
+    q.n = n;
+    q.k = k;
+    q.reach = rt::kCameraReach * mesh.maxabs;
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_knn(c, rt::scene_view(mesh), q, prm->count_traversal != 0u, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
+    };
+    // the points' walk: point_stack_need entries per lane, so the spill columns grow no further than the point query grows them
+    if (int rc = enqueue_query(c, c->pt.knn_query, n, *prm, rt::point_stack_need(mesh.depth), "rt.path_b.query_knn", launch)) return rc;
+    c->pt.knn_query_stats = rt_knn_query_stats{};
+    c->pt.knn_query_stats.points = n;
+    c->pt.knn_query_stats.launches = 1;
+    return RT_OK;
+}
+
+int rt_get_knn_query_stats(rt_ctx* ctx, rt_knn_query_stats* stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !stats) return RT_ERR_INVALID;
+    rt_knn_query_stats& s = c->pt.knn_query_stats;
+    if (c->pt.knn_query.pending) {
+        unsigned long long st[rt::KQ_STAT_WORDS] = {};
+        if (int rc = read_query(c, c->pt.knn_query, st, &s.ms)) return rc;
+        s.invalid_points = st[rt::KQ_STAT_INVALID];
+        s.neighbors = st[rt::KQ_STAT_NEIGHBORS];
+        s.stack_overflow = (uint32_t)st[rt::KQ_STAT_OVERFLOW];
+        s.nodes_visited = st[rt::KQ_STAT_NODES];
+        s.tris_tested = st[rt::KQ_STAT_TRIS];
     }
     *stats = s;
     return RT_OK;

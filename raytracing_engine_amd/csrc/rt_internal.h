@@ -327,6 +327,19 @@ enum { CQ_STAT_INVALID = 0, CQ_STAT_OVERFLOW = 1, CQ_STAT_NODES = 2, CQ_STAT_TRI
 // Waves per SIMD pt_query_clearance is bounded to, = its workgroups per CU (the compiler's figures: DESIGN.md §6.22); the host caps the
 // persistent grid to it.
 constexpr int kClearanceWaves = 4;
+// rt_query_knn_device: the points of one query and where their rows go.  Point i is queue entry i; its row is
+// elements i * k .. i * k + k - 1 of dist_out and tri_out (64-bit addressing: n x k reaches 2^40).
+struct KnnQuery {
+    const float* points;  // n x 3
+    const float* rmax;    // n, or nullptr: +inf
+    float* dist_out;      // n x k (d2 until the lane retires)
+    int* tri_out;         // n x k
+    int* count_out;       // n, or nullptr
+    uint32_t n, k;
+    float reach;  // |component| limit: kCameraReach x the mesh's maxabs
+};
+// Counters of a k-nearest query
+enum { KQ_STAT_INVALID = 0, KQ_STAT_OVERFLOW = 1, KQ_STAT_NODES = 2, KQ_STAT_TRIS = 3, KQ_STAT_NEIGHBORS = 4, KQ_STAT_WORDS = 5 };
 // Counters of a listing query (all hits, neighbours, overlaps): one set per step (the fill step's LQ_STEP_WORDS words behind the count step's),
 // so that the two launches of a list call report side by side.  FOUND: hits / neighbours met.
 enum { LQ_STAT_INVALID = 0, LQ_STAT_OVERFLOW = 1, LQ_STAT_NODES = 2, LQ_STAT_TRIS = 3, LQ_STAT_FOUND = 4, LQ_STAT_WRITTEN = 5, LQ_STAT_INCOMPLETE = 6,
@@ -366,7 +379,7 @@ constexpr size_t kQueryHeadBytes = (size_t)PT_HEADS * PT_HEAD_STRIDE * sizeof(ui
 constexpr size_t query_block_bytes(uint32_t n_counters) { return kQueryHeadBytes + (size_t)n_counters * sizeof(unsigned long long); }
 struct QueryState {
     QueryState(uint32_t k, const char* what, uint32_t lds, uint32_t halves) : n_counters(k), name(what), fixed_lds_bytes(lds), spill_halves(halves) {}
-    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS / SQ_STAT_WORDS / LQ_STAT_WORDS
+    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS / SQ_STAT_WORDS / LQ_STAT_WORDS / SG_STAT_WORDS / CQ_STAT_WORDS / KQ_STAT_WORDS
     const char* name;     // for messages
     uint32_t fixed_lds_bytes, spill_halves;  // pt_stack_config's: the kernel's LDS beside the stacks, the sets of spill columns it is given
     DevPtr<char> block;
@@ -431,6 +444,8 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     ListingState overlap_query{"overlap-query"};                            // rt_count / fill / list_overlaps_device
     QueryState segment_query{SG_STAT_WORDS, "overlap-segments", 0u, 0u};    // rt_overlap_segments_device: a flat kernel, no stack (the block's stream heads stay unused)
     QueryState clearance_query{CQ_STAT_WORDS, "clearance-query", 0u, 1u};   // rt_query_clearance_device: the points' walk, one set of columns
+    QueryState knn_query{KQ_STAT_WORDS, "knn-query", 0u, 1u};               // rt_query_knn_device: the points' walk, one set of columns
+    rt_knn_query_stats knn_query_stats{};
     rt_ray_query_stats ray_query_stats{};
     rt_point_query_stats point_query_stats{};
     rt_side_query_stats side_query_stats{};
@@ -526,7 +541,7 @@ int launch_detile(Ctx* c, const float* tiles, uint32_t n_ranks, uint32_t tiles_p
 int launch_to_rgba8(Ctx* c, const float* rgb, uint8_t* rgba, uint64_t n_pixels);
 
 // path_b.hip (generate, shade, scatter_surfaces, resolve), pt_trace.hip (trace, trace_fused, pool_lds_bytes, trace_rays, query_rays), pt_packet.hip (trace_packet),
-// pt_point_query.hip (query_points), pt_side_query.hip (query_sides), pt_hit_query.hip (query_hits), pt_neighbor_query.hip (query_neighbors), pt_overlap_query.hip (query_overlaps): every unit ends with the launchers of its own kernels
+// pt_point_query.hip (query_points), pt_side_query.hip (query_sides), pt_hit_query.hip (query_hits), pt_neighbor_query.hip (query_neighbors), pt_overlap_query.hip (query_overlaps), pt_knn_query.hip (query_knn): every unit ends with the launchers of its own kernels
 int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* queue, uint32_t* ctr);
 int launch_pt_trace(Ctx* c, hipStream_t stream, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,
@@ -570,6 +585,9 @@ int launch_pt_overlap_segments(Ctx* c, const PtScene& sc, const SegmentQuery& q,
 // pt_clearance_query.hip: the persistent refilling clearance kernel (stats: CQ_STAT_WORDS words)
 int launch_pt_query_clearance(Ctx* c, const PtScene& sc, const ClearanceQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid,
                               const StackCfg& sk, uint32_t refill_min);
+// pt_knn_query.hip: the persistent refilling k-nearest kernel (stats: KQ_STAT_WORDS words)
+int launch_pt_query_knn(Ctx* c, const PtScene& sc, const KnnQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid, const StackCfg& sk,
+                        uint32_t refill_min);
 void pt_free(Ctx* c);
 void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block and events
 

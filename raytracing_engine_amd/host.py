@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (ClearanceQueryParams, ClearanceQueryStats, Config, HitQueryParams, HitQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, OverlapQueryParams, OverlapQueryStats, OverlapSegmentStats, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
+from ._lib import (ClearanceQueryParams, ClearanceQueryStats, Config, HitQueryParams, HitQueryStats, KnnQueryParams, KnnQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, OverlapQueryParams, OverlapQueryStats, OverlapSegmentStats, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
                    RtError, SideQueryParams, SideQueryStats, Stats)
 
 # src/main.rs:343-364
@@ -460,12 +460,20 @@ class Renderer:
         """_device_ints for int32."""
         self._device_ints(t, name, n, "int32")
 
+    def _device_i32_rows(self, t, name, n, cols):
+        """`t` must be a contiguous int32 torch tensor of shape (n, cols) on this renderer's device; ValueError otherwise."""
+        import torch
+
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device
+                or tuple(t.shape) != (n, cols)):
+            raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({n}, {cols}) on cuda:{self.device}")
+
     def _device_i64(self, t, name, n):
         """_device_ints for int64."""
         self._device_ints(t, name, n, "int64")
 
     def _query_tune(self, params, tune, method):
-        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors / count_overlaps / list_overlaps / query_clearance) into its parameter struct;
+        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors / count_overlaps / list_overlaps / query_clearance / query_knn) into its parameter struct;
         TypeError for any other keyword."""
         for k, v in tune.items():
             if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
@@ -925,6 +933,55 @@ class Renderer:
         """rt_clearance_query_stats of the last clearance query as a dict (waits for it): queries, invalid_triangles, nodes_visited,
         tris_tested (count_traversal=True only; records fetched), stack_overflow, ms."""
         return self._query_stats(ClearanceQueryStats(), "rt_get_clearance_query_stats")
+
+    KNN_MAX_K = _lib.KNN_MAX_K
+
+    def query_knn(self, points, k, rmax=None, out=None, sync=True, count_traversal=False, **tune):
+        """The k triangles of the current mesh nearest to each point, sorted.  (rt_query_knn_device)  points as for
+        query_points; k: 1 .. KNN_MAX_K = 1024 (it may exceed the number of triangles: rows are then short); rmax: None (+inf), a float
+        for all points - it becomes a filled device tensor - or a float32 device tensor of n elements: only triangles nearer than rmax
+        count (strictly).  Returns (dist, tri, counts): (n, k) float32 distances and (n, k) int32 original triangle indices, row i
+        ascending by (d2, tri) - the first min(k, its length) entries of list_neighbors' slice for the same rmax, entry 0 query_points'
+        answer - and (n,) int32 counts, the entries that are neighbours; those behind them are +inf and POINT_MISS = -1.  Invalid points
+        (query_points' rule) get counts POINT_INVALID = -2 and a row of NaN and POINT_INVALID.  out: (dist, tri, counts) to fill instead
+        of new tensors.  sync as for query_points.  count_traversal=True: knn_query_stats() reports nodes_visited / tris_tested.  tune:
+        tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of rt_knn_query_params."""
+        import torch
+
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"k must be an integer, got {type(k).__name__}")
+        k = int(k)
+        if not 1 <= k <= self.KNN_MAX_K:
+            raise ValueError(f"k must be 1 .. {self.KNN_MAX_K}, got {k}")
+        if rmax is None or isinstance(rmax, torch.Tensor):
+            n = self._point_rows(points, rmax)
+        else:
+            n = self._point_rows(points, None)
+            if isinstance(rmax, bool) or not isinstance(rmax, (int, float, np.floating, np.integer)):
+                raise ValueError(f"rmax must be None, a float or a float32 tensor of shape ({n},), got {type(rmax).__name__}")
+            rmax = torch.full((n,), float(rmax), dtype=torch.float32, device=points.device)
+        p = KnnQueryParams()
+        p.count_traversal = int(bool(count_traversal))
+        self._query_tune(p, tune, "query_knn")
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
+            raise ValueError("out must be (dist, tri, counts)")
+        dist, tri, counts = out if out is not None else (None, None, None)
+        if dist is None:
+            dist = torch.empty((n, k), dtype=torch.float32, device=points.device)
+        elif not isinstance(dist, torch.Tensor) or dist.dim() != 2 or tuple(dist.shape) != (n, k) or self._device_rows(dist, "out dist", k) != n:
+            raise ValueError(f"out dist must be a contiguous float32 tensor of shape ({n}, {k}) on cuda:{self.device}")
+        if tri is None:
+            tri = torch.empty((n, k), dtype=torch.int32, device=points.device)
+        else:
+            self._device_i32_rows(tri, "out tri", n, k)
+        counts = self._query_out(counts, "out counts", n, torch.int32, points.device)
+        self._query_call(sync, self._lib.rt_query_knn_device, points, rmax, n, k, C.byref(p), dist, tri, counts)
+        return dist, tri, counts
+
+    def knn_query_stats(self):
+        """rt_knn_query_stats of the last k-nearest query as a dict (waits for it): points, invalid_points, neighbors (the sum of the
+        counts that are not negative), nodes_visited, tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
+        return self._query_stats(KnnQueryStats(), "rt_get_knn_query_stats")
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
         """Test hook (query_rays is the product entry): closest hit (t, original triangle index) or occlusion flags for a ray batch;
