@@ -34,13 +34,12 @@ A swapped (ub, vb), barycentrics applied to the neighbouring triangle and a norm
 triangle or of a unit vector, thousands of units: tests/test_hit_attr_host.py shows that the contract rejects them.
 """
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 import ray_exact as RX  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,50 +51,29 @@ f32 = np.float32
 
 
 # ---- the native reference ------------------------------------------------------------------------------------------------------
-_BUILT = {}
 
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/hit_attr_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="hit_attr_ref_")
-        exe = os.path.join(where, "hit_attr_ref_asan" if sanitized else "hit_attr_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off"] + flags + [os.path.join(ROOT, "tests", "native", "hit_attr_ref.cpp"), "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("hit_attr_ref", (), sanitized, where)
 
 
 def reference(verts, o, d, tmax=None, tris=None, sanitized=False):
     """The native reference on mesh `verts` and rays (o, d).  Returns dict(t, tri, ub, vb, uvd (n, 3): u, v, det as the test forms
     them, normal (n, 3)[, tri_normals (len(tris), 3): the unit normals of the triangles `tris`, NaN rows for negative indices])."""
-    exe = build_reference(sanitized)
     o = np.ascontiguousarray(o, f32).reshape(-1, 3)
     d = np.ascontiguousarray(d, f32).reshape(-1, 3)
     n = len(o)
-    with tempfile.TemporaryDirectory(prefix="hit_attr_") as tmp:
-        np.ascontiguousarray(verts, f32).tofile(os.path.join(tmp, "mesh"))
-        np.ascontiguousarray(np.concatenate([o, d], 1), f32).tofile(os.path.join(tmp, "rays"))
-        cmd = [exe, os.path.join(tmp, "mesh"), os.path.join(tmp, "rays"), os.path.join(tmp, "out"), "-"]
-        if tmax is not None:
-            np.ascontiguousarray(tmax, f32).tofile(os.path.join(tmp, "tmax"))
-            cmd[4] = os.path.join(tmp, "tmax")
-        if tris is not None:
-            np.ascontiguousarray(tris, np.int32).tofile(os.path.join(tmp, "tris"))
-            cmd.append(os.path.join(tmp, "tris"))
-        run = subprocess.run(cmd, capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"hit_attr_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(tmp, "out"), np.uint8)
-    assert int(raw[:8].view(np.uint64)[0]) == n
-    out, at = {}, 8
-    for key, dt, width in (("t", f32, 1), ("tri", np.int32, 1), ("ub", f32, 1), ("vb", f32, 1), ("uvd", f32, 3), ("normal", f32, 3)):
-        out[key] = raw[at:at + 4 * n * width].view(dt).copy()
-        at += 4 * n * width
-    out["uvd"], out["normal"] = out["uvd"].reshape(n, 3), out["normal"].reshape(n, 3)
+    inputs = dict(mesh=np.asarray(verts, f32), rays=np.concatenate([o, d], 1).astype(f32, copy=False), out=NR.OUT, tmax=None if tmax is None else np.asarray(tmax, f32))
     if tris is not None:
-        out["tri_normals"] = raw[at:].view(f32).copy().reshape(-1, 3)
-        assert len(out["tri_normals"]) == len(np.asarray(tris).ravel())
+        inputs["tris"] = np.asarray(tris, np.int32)
+    m = 0 if tris is None else inputs["tris"].size
+    head, out = NR.unpack(NR.run(build_reference(sanitized), inputs), 1, (("t", f32, n), ("tri", np.int32, n), ("ub", f32, n), ("vb", f32, n), ("uvd", f32, 3 * n),
+                                                                           ("normal", f32, 3 * n), ("tri_normals", f32, 3 * m)))
+    assert head[0] == n
+    out["uvd"], out["normal"], out["tri_normals"] = out["uvd"].reshape(n, 3), out["normal"].reshape(n, 3), out["tri_normals"].reshape(m, 3)
+    if tris is None:
+        del out["tri_normals"]
     return out
 
 

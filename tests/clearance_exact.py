@@ -34,13 +34,12 @@ THE QUERY FAMILIES (fixed seeds; a part has at most 2 000 mesh triangles and 600
 """
 import functools
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 import overlap_exact as OX  # noqa: E402
 import point_exact as PX  # noqa: E402
 
@@ -255,63 +254,32 @@ def exact_answer(ex, withhold_nearest=False):
 
 
 # ---- the native reference ------------------------------------------------------------------------------------------------------
-_BUILT = {}
 
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/clearance_query_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="clearance_query_ref_")
-        exe = os.path.join(where, "clearance_query_ref_asan" if sanitized else "clearance_query_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-pthread"] + flags +
-                       [os.path.join(ROOT, "tests", "native", "clearance_query_ref.cpp"), os.path.join(ROOT, "raytracing_engine_amd", "csrc", "bvh_build.cpp"),
-                        "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("clearance_query_ref", [NR.BVH_BUILD], sanitized, where, flags=("-pthread",))
 
 
 def reference(verts, q, rmax=None, pairs=None, sanitized=False, nopad=False):
     """The native reference on mesh `verts` and query triangles q (n, 9).  Returns dict(brute=..., walk=..., nodes, tris (uint32 per
     query), nodes_total, tris_total[, pair_d2]); brute and walk are dicts of tri, cand (int32: the winning candidate of tri_dist, 0 .. 5 a pierce), d2, uq, vq, um, vm, dist (float32), pq
     and pm (n, 3)."""
-    exe = build_reference(sanitized)
     q = np.ascontiguousarray(q, f32).reshape(-1, 9)
     n = len(q)
-    with tempfile.TemporaryDirectory(prefix="clearance_query_") as d:
-        np.ascontiguousarray(verts, f32).tofile(os.path.join(d, "mesh"))
-        q.tofile(os.path.join(d, "queries"))
-        cmd = [exe, os.path.join(d, "mesh"), os.path.join(d, "queries"), os.path.join(d, "out"), "-", "-"]
-        if rmax is not None:
-            np.ascontiguousarray(rmax, f32).tofile(os.path.join(d, "rmax"))
-            cmd[4] = os.path.join(d, "rmax")
-        if pairs is not None:
-            np.ascontiguousarray(pairs, np.int32).tofile(os.path.join(d, "pairs"))
-            cmd[5] = os.path.join(d, "pairs")
-        if nopad:
-            cmd.append("nopad")
-        run = subprocess.run(cmd, capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"clearance_query_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(d, "out"), np.uint8)
-    head = raw[:24].view(np.uint64)
-    assert int(head[0]) == n
-    out = dict(nodes_total=int(head[1]), tris_total=int(head[2]))
-    at = 24
-    for key in ("nodes", "tris"):
-        out[key] = raw[at:at + 4 * n].view(np.uint32).copy()
-        at += 4 * n
+    inputs = dict(mesh=np.asarray(verts, f32), queries=q, out=NR.OUT, rmax=None if rmax is None else np.asarray(rmax, f32),
+                  pairs=None if pairs is None else np.asarray(pairs, np.int32))
+    if nopad:
+        inputs["mode"] = "nopad"
+    fields = [("nodes", np.uint32, n), ("tris", np.uint32, n)] + [(f"{name}.{key}", dt, n * width) for name in ("brute", "walk") for key, dt, width in COLUMNS]
+    head, flat = NR.unpack(NR.run(build_reference(sanitized), inputs), 3, fields + [("pair_d2", f32, 0 if pairs is None else inputs["pairs"].size // 2)])
+    assert head[0] == n
+    out = dict(nodes_total=head[1], tris_total=head[2], nodes=flat["nodes"], tris=flat["tris"])
     for name in ("brute", "walk"):
-        col = {}
-        for key, dt, width in COLUMNS:
-            col[key] = raw[at:at + 4 * n * width].view(dt).copy()
-            at += 4 * n * width
-        col["pq"], col["pm"] = col["pq"].reshape(n, 3), col["pm"].reshape(n, 3)
-        out[name] = col
+        out[name] = {key: flat[f"{name}.{key}"] for key, _, _ in COLUMNS}
+        out[name]["pq"], out[name]["pm"] = out[name]["pq"].reshape(n, 3), out[name]["pm"].reshape(n, 3)
     if pairs is not None:
-        out["pair_d2"] = raw[at:].view(f32).copy()
-    else:
-        assert at == len(raw)
+        out["pair_d2"] = flat["pair_d2"]
     return out
 
 

@@ -15,13 +15,12 @@ duplicates(): every triangle twice, so that every t comes twice and the index de
 """
 import functools
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 import ray_exact as RX  # noqa: E402
 import sign_exact as SX  # noqa: E402
 
@@ -30,49 +29,24 @@ f32 = np.float32
 INF = f32(np.inf)
 INVALID = -2
 
-_BUILT = {}
-
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/hit_query_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="hit_query_ref_")
-        exe = os.path.join(where, "hit_query_ref_asan" if sanitized else "hit_query_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-pthread"] + flags +
-                       [os.path.join(ROOT, "tests", "native", "hit_query_ref.cpp"), os.path.join(ROOT, "raytracing_engine_amd", "csrc", "bvh_build.cpp"),
-                        "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("hit_query_ref", [NR.BVH_BUILD], sanitized, where, flags=("-pthread",))
 
 
 def reference(verts, o, d, tmax=None, sanitized=False):
     """The native reference on mesh `verts` and rays (o, d, tmax; None: +inf): dict(count (n,) with INVALID = -2, walk_count (n,), same
     (n,) - the walk's sorted list is the brute force's -, offsets (n + 1,) int64, t, tri (hits,), hits, nodes, tris, invalid)."""
-    exe = build_reference(sanitized)
     o = np.ascontiguousarray(o, f32).reshape(-1, 3)
     d = np.ascontiguousarray(d, f32).reshape(-1, 3)
     n = len(o)
     tmax = np.full(n, INF, f32) if tmax is None else np.ascontiguousarray(tmax, f32).reshape(n)
-    with tempfile.TemporaryDirectory(prefix="hit_query_") as tmp:
-        np.ascontiguousarray(verts, f32).tofile(os.path.join(tmp, "mesh"))
-        np.ascontiguousarray(np.concatenate([o, d, tmax[:, None]], 1), f32).tofile(os.path.join(tmp, "rays"))
-        run = subprocess.run([exe, os.path.join(tmp, "mesh"), os.path.join(tmp, "rays"), os.path.join(tmp, "out")], capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"hit_query_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(tmp, "out"), np.uint8)
-    head = raw[:40].view(np.uint64)
-    assert int(head[0]) == n
-    hits = int(head[1])
-    out = dict(hits=hits, nodes=int(head[2]), tris=int(head[3]), invalid=int(head[4]))
-    at = 40
-    for key, dt, count in (("count", np.int32, n), ("walk_count", np.int32, n), ("same", np.int32, n), ("offsets", np.int64, n + 1), ("t", f32, hits),
-                           ("tri", np.int32, hits)):
-        size = count * np.dtype(dt).itemsize
-        out[key] = raw[at:at + size].view(dt).copy()
-        at += size
-    assert at == len(raw)
-    return out
+    raw = NR.run(build_reference(sanitized), dict(mesh=np.asarray(verts, f32), rays=np.concatenate([o, d, tmax[:, None]], 1).astype(f32, copy=False)))
+    head, out = NR.unpack(raw, 5, lambda h: (("count", np.int32, n), ("walk_count", np.int32, n), ("same", np.int32, n), ("offsets", np.int64, n + 1), ("t", f32, h[1]),
+                                             ("tri", np.int32, h[1])))
+    assert head[0] == n
+    return dict(out, hits=head[1], nodes=head[2], tris=head[3], invalid=head[4])
 
 
 def rows(ref, sel):
@@ -85,11 +59,7 @@ def rows(ref, sel):
     return dict(count=count, offsets=offsets, t=ref["t"][take], tri=ref["tri"][take], hits=int(lens.sum()), invalid=int((count == INVALID).sum()))
 
 
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype == f32:
-        return b.dtype == f32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    return a.shape == b.shape and np.array_equal(a, b)
+same_bits = NR.same_bits
 
 
 def first_hits(ref):

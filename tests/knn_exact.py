@@ -19,13 +19,12 @@ no triangle that is not listed (and lies more than the band inside rmax) has D b
 every triangle with D < rmax - Kp unit; none with D > rmax + Kp unit is listed."""
 import functools
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 import neighbor_exact as NX  # noqa: E402
 import point_exact as PX  # noqa: E402
 
@@ -38,20 +37,10 @@ BIG_K = 1024  # RT_KNN_MAX_K
 BIG_POINTS = 8
 N_FAMILY = NX.N_FAMILY
 
-_BUILT = {}
-
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/knn_query_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="knn_query_ref_")
-        exe = os.path.join(where, "knn_query_ref_asan" if sanitized else "knn_query_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-pthread"] + flags +
-                       [os.path.join(ROOT, "tests", "native", "knn_query_ref.cpp"), os.path.join(ROOT, "raytracing_engine_amd", "csrc", "bvh_build.cpp"),
-                        "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("knn_query_ref", [NR.BVH_BUILD], sanitized, where, flags=("-pthread",))
 
 
 def reference(verts, p, k, rmax=None, sanitized=False):
@@ -60,33 +49,17 @@ def reference(verts, p, k, rmax=None, sanitized=False):
     INVALID for an invalid point), d2, dist (float32), tri (int32): the brute force's rows, k[i] entries each, padded with +inf / MISS
     (an invalid point's row: NaN / INVALID); walk_count, walk_d2, walk_tri: the tree walk's; nodes, tris (uint32 per point): what the walk
     fetched and tested; neighbors, walk_neighbors, nodes_total, tris_total, invalid: the sums."""
-    exe = build_reference(sanitized)
     p = np.ascontiguousarray(p, f32).reshape(-1, 3)
     n = len(p)
-    rmax = np.ascontiguousarray(np.broadcast_to(np.asarray(INF if rmax is None else rmax, f32), (n,)), f32)
+    rmax = np.broadcast_to(np.asarray(INF if rmax is None else rmax, f32), (n,))
     k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, np.uint32), (n,)), np.uint32)
-    with tempfile.TemporaryDirectory(prefix="knn_query_") as d:
-        np.ascontiguousarray(verts, f32).tofile(os.path.join(d, "mesh"))
-        p.tofile(os.path.join(d, "points"))
-        rmax.tofile(os.path.join(d, "rmax"))
-        k.tofile(os.path.join(d, "k"))
-        run = subprocess.run([exe] + [os.path.join(d, x) for x in ("mesh", "points", "rmax", "k", "out")], capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"knn_query_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(d, "out"), np.uint8)
-    head = raw[:56].view(np.uint64)
-    assert int(head[0]) == n and int(head[1]) == int(k.sum(dtype=np.uint64))
-    e = int(head[1])
-    out = dict(k=k, starts=np.concatenate([[0], np.cumsum(k.astype(np.int64))]), neighbors=int(head[2]), walk_neighbors=int(head[3]), nodes_total=int(head[4]),
-               tris_total=int(head[5]), invalid=int(head[6]))
-    at = 56
-    for key, dt, count in (("count", np.int32, n), ("walk_count", np.int32, n), ("nodes", np.uint32, n), ("tris", np.uint32, n), ("d2", f32, e), ("dist", f32, e),
-                           ("tri", np.int32, e), ("walk_d2", f32, e), ("walk_tri", np.int32, e)):
-        size = count * np.dtype(dt).itemsize
-        out[key] = raw[at:at + size].view(dt).copy()
-        at += size
-    assert at == len(raw)
-    return out
+    e = int(k.sum(dtype=np.uint64))
+    raw = NR.run(build_reference(sanitized), dict(mesh=np.asarray(verts, f32), points=p, rmax=rmax, k=k))
+    head, out = NR.unpack(raw, 7, (("count", np.int32, n), ("walk_count", np.int32, n), ("nodes", np.uint32, n), ("tris", np.uint32, n), ("d2", f32, e), ("dist", f32, e),
+                                   ("tri", np.int32, e), ("walk_d2", f32, e), ("walk_tri", np.int32, e)))
+    assert head[:2] == (n, e)
+    return dict(out, k=k, starts=np.concatenate([[0], np.cumsum(k.astype(np.int64))]), neighbors=head[2], walk_neighbors=head[3], nodes_total=head[4],
+                tris_total=head[5], invalid=head[6])
 
 
 same_bits = NX.same_bits

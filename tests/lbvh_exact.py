@@ -11,9 +11,7 @@ THE SIZES are the smallest triangle counts at which a mechanism of csrc/bvh_buil
 constant), THE FAMILIES the meshes whose keys stress the sort, the tie breaks and the quantiser (FAMILIES); all seeded."""
 import functools
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -21,6 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from raytracing_engine_amd import scenes  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 
 f32 = np.float32
 NODE_WORDS = 20
@@ -46,55 +47,25 @@ SIZES = (
 FAMILY_SIZES = (K_SORT_TILE + 1, 16 * K_SORT_TILE + 1)
 SANITIZED_MAX = 2 * K_TOP_LEVEL_NODES + 2  # the sanitized reference runs on every case of at most this many triangles
 
-_BUILT = {}
-
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/lbvh_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="lbvh_ref_")
-        exe = os.path.join(where, "lbvh_ref_asan" if sanitized else "lbvh_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"] + flags +
-                       [os.path.join(ROOT, "tests", "native", "lbvh_ref.cpp"), "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
-
-
-def _run(exe, args, out_path):
-    run = subprocess.run([exe] + args + [out_path], capture_output=True, text=True)
-    if run.returncode != 0 or not run.stdout.startswith("OK"):
-        raise RuntimeError(f"lbvh_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-    with open(out_path, "rb") as f:
-        return f.read()
+    return NR.build("lbvh_ref", (), sanitized, where, flags=("-Wall", "-Wextra", "-Werror"))
 
 
 def _parse(raw):
-    buf = np.frombuffer(raw, np.uint8)
-    head = buf[:48].view(np.uint64)
-    n, nn, depth, n_levels, n_keys, n_bin = (int(x) for x in head)
-    maxabs, pad = buf[48:56].view(f32)
-    out = dict(n=n, n_nodes=nn, depth=depth, maxabs=f32(maxabs), pad=f32(pad), raw=raw)
-    at = 56
-    for key, dt, count in (("keys", np.uint64, n_keys), ("nodes", np.uint32, nn * NODE_WORDS), ("leaf", np.uint32, n), ("level_start", np.uint32, n_levels),
-                           ("binary", np.uint32, 3 * n_bin)):
-        size = count * np.dtype(dt).itemsize
-        out[key] = buf[at:at + size].view(dt).copy()
-        at += size
-    assert at == len(buf)
-    out["nodes"] = out["nodes"].reshape(nn, NODE_WORDS)
-    out["binary"] = out["binary"].reshape(n_bin, 3)
-    return out
+    head, out = NR.unpack(raw, 6, lambda h: (("scale", f32, 2), ("keys", np.uint64, h[4]), ("nodes", np.uint32, h[1] * NODE_WORDS), ("leaf", np.uint32, h[0]),
+                                             ("level_start", np.uint32, h[3]), ("binary", np.uint32, 3 * h[5])))
+    n, nn, depth = head[:3]
+    maxabs, pad = out.pop("scale")
+    return dict(out, n=n, n_nodes=nn, depth=depth, maxabs=f32(maxabs), pad=f32(pad), raw=raw, nodes=out["nodes"].reshape(nn, NODE_WORDS), binary=out["binary"].reshape(head[5], 3))
 
 
 def reference(verts, sanitized=False):
     """The reference build of mesh `verts` (n x 9).  Returns a dict: n, n_nodes, depth, maxabs (M), pad, keys (uint64, sorted), nodes
     (uint32, n_nodes x 20), leaf (uint32), level_start (uint32, depth + 1), binary (uint32, (n - 1) x 3: first, last and split position of
     every internal node of the radix tree, in preorder) and raw, the program's output file."""
-    exe = build_reference(sanitized)
-    with tempfile.TemporaryDirectory(prefix="lbvh_") as d:
-        np.ascontiguousarray(verts, f32).reshape(-1, 9).tofile(os.path.join(d, "mesh"))
-        return _parse(_run(exe, ["build", os.path.join(d, "mesh")], os.path.join(d, "out")))
+    return _parse(NR.run(build_reference(sanitized), dict(mode="build", mesh=np.asarray(verts, f32))))
 
 
 def topology_of(nodes):
@@ -108,12 +79,7 @@ def topology_of(nodes):
 def reference_refit(nodes, leaf, verts, sanitized=False):
     """The reference refit of the tree (nodes, leaf), as rt_read_bvh returned it BEFORE the refit, to the vertices `verts`: only the
     topology (topology_of) reaches the program.  Returns reference()'s dict without keys, level starts and the binary tree."""
-    exe = build_reference(sanitized)
-    with tempfile.TemporaryDirectory(prefix="lbvh_") as d:
-        topology_of(nodes).tofile(os.path.join(d, "topo"))
-        np.ascontiguousarray(leaf, np.uint32).tofile(os.path.join(d, "leaf"))
-        np.ascontiguousarray(verts, f32).reshape(-1, 9).tofile(os.path.join(d, "mesh"))
-        return _parse(_run(exe, ["refit", os.path.join(d, "topo"), os.path.join(d, "leaf"), os.path.join(d, "mesh")], os.path.join(d, "out")))
+    return _parse(NR.run(build_reference(sanitized), dict(mode="refit", topo=topology_of(nodes), leaf=np.asarray(leaf, np.uint32), mesh=np.asarray(verts, f32))))
 
 
 # ---- the structure check (the array part of test_gpu_device_bvh.check_bvh) ------------------------------------------------------------

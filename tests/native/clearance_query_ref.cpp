@@ -21,28 +21,15 @@
 #include <limits>
 #include <vector>
 
-#include "../../raytracing_engine_amd/csrc/bvh_build.h"
 #include "../../raytracing_engine_amd/csrc/tri_dist.h"
+#define REF_IO_TREE
+#include "ref_io.h"
 
 namespace {
 
-template <class T>
-bool read_all(const char* path, std::vector<T>& out) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long bytes = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    out.resize(bytes > 0 ? (size_t)bytes / sizeof(T) : 0);
-    const bool ok = bytes >= 0 && (size_t)bytes % sizeof(T) == 0 && std::fread(out.data(), sizeof(T), out.size(), f) == out.size();
-    std::fclose(f);
-    return ok;
-}
-
-template <class T>
-bool write_all(FILE* f, const std::vector<T>& v) {
-    return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-}
+using ref::fail;
+using ref::read_all;
+using ref::write_all;
 
 struct Mesh {
     std::vector<float> v0, e1, e2;  // original order, edges formed in fp32 as rt_abi_mesh.hip forms them
@@ -127,26 +114,16 @@ int main(int argc, char** argv) {
         std::fputs("usage: clearance_query_ref <mesh> <queries> <out> [rmax | -] [pairs | -] [nopad]\n", stderr);
         return 2;
     }
-    std::vector<float> raw, qs, rmax;
-    if (!read_all(argv[1], raw) || raw.empty() || raw.size() % 9) { std::fputs("cannot read the mesh\n", stderr); return 1; }
-    if (!read_all(argv[2], qs) || qs.size() % 9) { std::fputs("cannot read the queries\n", stderr); return 1; }
+    std::vector<float> qs, rmax;
+    if (!read_all(argv[2], qs) || qs.size() % 9) return fail("cannot read the queries");
     const size_t n = qs.size() / 9;
-    if (argc > 4 && std::strcmp(argv[4], "-") != 0 && (!read_all(argv[4], rmax) || rmax.size() != n)) { std::fputs("cannot read rmax\n", stderr); return 1; }
+    if (argc > 4 && std::strcmp(argv[4], "-") != 0 && (!read_all(argv[4], rmax) || rmax.size() != n)) return fail("cannot read rmax");
     const bool nopad = argc > 6 && std::strcmp(argv[6], "nopad") == 0;
     Mesh m;
-    m.n = raw.size() / 9;
-    m.v0.resize(3 * m.n);
-    m.e1.resize(3 * m.n);
-    m.e2.resize(3 * m.n);
-    for (size_t i = 0; i < m.n; i++)
-        for (int a = 0; a < 3; a++) {
-            m.v0[3 * i + a] = raw[9 * i + a];
-            m.e1[3 * i + a] = raw[9 * i + 3 + a] - raw[9 * i + a];
-            m.e2[3 * i + a] = raw[9 * i + 6 + a] - raw[9 * i + a];
-        }
     rt::BvhResult b;
-    if (!rt::build_bvh(m.v0.data(), m.e1.data(), m.e2.data(), (uint32_t)m.n, rt::kBvhMaxDepth, &b)) { std::fputs("build failed\n", stderr); return 1; }
-    const float reach = 32.0f * b.maxabs;
+    float reach;
+    if (!ref::load_mesh(argv[1], m.v0, m.e1, m.e2, m.n)) return fail("cannot read the mesh");
+    if (!ref::build_tree(m.v0, m.e1, m.e2, m.n, b, reach)) return fail("build failed");
 
     Column brute(n), walked(n);
     std::vector<uint32_t> nodes(n), tris(n);
@@ -170,7 +147,7 @@ int main(int argc, char** argv) {
         walked.set(i, m, A, w, limit2, invalid);
     }
     FILE* f = std::fopen(argv[3], "wb");
-    if (!f) { std::fputs("cannot write the answers\n", stderr); return 1; }
+    if (!f) return fail("cannot write the answers");
     const uint64_t head[3] = {(uint64_t)n, total_nodes, total_tris};
     bool ok = std::fwrite(head, 8, 3, f) == 3 && write_all(f, nodes) && write_all(f, tris) && brute.write(f) && walked.write(f);
     if (argc > 5 && std::strcmp(argv[5], "-") != 0) {
@@ -185,7 +162,7 @@ int main(int argc, char** argv) {
         }
     }
     std::fclose(f);
-    if (!ok) { std::fputs("short write\n", stderr); return 1; }
+    if (!ok) return fail("short write");
     std::printf("OK queries=%zu tris=%zu depth=%u nodes/query=%.2f records/query=%.2f\n", n, m.n, b.depth, n ? (double)total_nodes / n : 0.0,
                 n ? (double)total_tris / n : 0.0);
     return 0;

@@ -20,21 +20,13 @@
 
 #include "../../raytracing_engine_amd/csrc/hit_attr.h"
 #include "../../raytracing_engine_amd/csrc/ray_parity.h"
+#include "ref_io.h"
 
 namespace {
 
-template <class T>
-bool read_all(const char* path, std::vector<T>& out) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long bytes = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    out.resize(bytes > 0 ? (size_t)bytes / sizeof(T) : 0);
-    const bool ok = bytes >= 0 && (size_t)bytes % sizeof(T) == 0 && std::fread(out.data(), sizeof(T), out.size(), f) == out.size();
-    std::fclose(f);
-    return ok;
-}
+using ref::fail;
+using ref::read_all;
+using ref::write_all;
 
 struct Mesh {
     std::vector<float> v0, e1, e2;  // original order, edges formed in fp32 as rt_abi_mesh.hip forms them
@@ -44,9 +36,6 @@ struct Mesh {
 
 bool finite3(rt::P3 a) { return std::fabs(a.x) < INFINITY && std::fabs(a.y) < INFINITY && std::fabs(a.z) < INFINITY; }
 
-template <class T>
-bool put(FILE* f, const std::vector<T>& v) { return std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
-
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -55,24 +44,14 @@ int main(int argc, char** argv) {
         return 2;
     }
     std::vector<float> raw, rays, tmax;
-    if (!read_all(argv[1], raw) || raw.empty() || raw.size() % 9) { std::fputs("cannot read the mesh\n", stderr); return 1; }
-    if (!read_all(argv[2], rays) || rays.size() % 6) { std::fputs("cannot read the rays\n", stderr); return 1; }
+    if (!read_all(argv[2], rays) || rays.size() % 6) return fail("cannot read the rays");
     const size_t n = rays.size() / 6;
-    if (argc > 4 && std::strcmp(argv[4], "-") != 0 && (!read_all(argv[4], tmax) || tmax.size() != n)) { std::fputs("cannot read tmax\n", stderr); return 1; }
+    if (argc > 4 && std::strcmp(argv[4], "-") != 0 && (!read_all(argv[4], tmax) || tmax.size() != n)) return fail("cannot read tmax");
     Mesh m;
-    m.n = raw.size() / 9;
-    m.v0.resize(3 * m.n);
-    m.e1.resize(3 * m.n);
-    m.e2.resize(3 * m.n);
-    float maxabs = 1.0f;
-    for (size_t i = 0; i < m.n; i++)
-        for (int a = 0; a < 3; a++) {
-            m.v0[3 * i + a] = raw[9 * i + a];
-            m.e1[3 * i + a] = raw[9 * i + 3 + a] - raw[9 * i + a];
-            m.e2[3 * i + a] = raw[9 * i + 6 + a] - raw[9 * i + a];
-            for (int k = 0; k < 3; k++) maxabs = std::fmax(maxabs, std::fabs(raw[9 * i + 3 * k + a]));
-        }
-    const float reach = 32.0f * maxabs;
+    if (!ref::load_mesh(argv[1], m.v0, m.e1, m.e2, m.n, &raw)) return fail("cannot read the mesh");
+    float maxabs = 1.0f;  // over the vertices as given
+    for (float x : raw) maxabs = std::fmax(maxabs, std::fabs(x));
+    const float reach = ref::reach_of(maxabs);
     const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
 
     std::vector<float> t_out(n), ub(n), vb(n), uvd(3 * n), nrm(3 * n);
@@ -90,7 +69,7 @@ int main(int argc, char** argv) {
                 const rt::P3 v0 = m.at(m.v0, k), e1 = m.at(m.e1, k), e2 = m.at(m.e2, k);
                 float t = 0.0f;
                 const bool line = rt::ray_tri_t(o, d, v0, e1, e2, t);
-                if (line != rt::ray_uvdet_accepted(rt::ray_tri_uvdet(o, d, v0, e1, e2))) { std::fputs("hit_attr.h and ray_parity.h disagree on a pair\n", stderr); return 1; }
+                if (line != rt::ray_uvdet_accepted(rt::ray_tri_uvdet(o, d, v0, e1, e2))) return fail("hit_attr.h and ray_parity.h disagree on a pair");
                 if (line && t > 0.0f && (t < best_t || (t == best_t && k < best_id))) {
                     best_t = t;
                     best_id = k;
@@ -119,9 +98,9 @@ int main(int argc, char** argv) {
         rt::write_attr(nullptr, nrm.data(), i, 0.0f, 0.0f, nn);
     }
     FILE* f = std::fopen(argv[3], "wb");
-    if (!f) { std::fputs("cannot write the answers\n", stderr); return 1; }
+    if (!f) return fail("cannot write the answers");
     const uint64_t head = (uint64_t)n;
-    bool ok = std::fwrite(&head, 8, 1, f) == 1 && put(f, t_out) && put(f, tri_out) && put(f, ub) && put(f, vb) && put(f, uvd) && put(f, nrm);
+    bool ok = std::fwrite(&head, 8, 1, f) == 1 && write_all(f, t_out) && write_all(f, tri_out) && write_all(f, ub) && write_all(f, vb) && write_all(f, uvd) && write_all(f, nrm);
     size_t n_tris = 0;
     if (argc > 5) {
         std::vector<int32_t> tris;
@@ -137,7 +116,7 @@ int main(int argc, char** argv) {
         }
     }
     std::fclose(f);
-    if (!ok) { std::fputs("short write or a bad triangle index\n", stderr); return 1; }
+    if (!ok) return fail("short write or a bad triangle index");
     std::printf("OK rays=%zu tris=%zu hits=%zu normals=%zu\n", n, m.n, hits, n_tris);
     return 0;
 }

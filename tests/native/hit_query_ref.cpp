@@ -23,23 +23,14 @@
 #include <utility>
 #include <vector>
 
-#include "../../raytracing_engine_amd/csrc/bvh_build.h"
 #include "../../raytracing_engine_amd/csrc/ray_parity.h"
+#define REF_IO_TREE
+#include "ref_io.h"
 
 namespace {
 
-template <class T>
-bool read_all(const char* path, std::vector<T>& out) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long bytes = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    out.resize(bytes > 0 ? (size_t)bytes / sizeof(T) : 0);
-    const bool ok = bytes >= 0 && (size_t)bytes % sizeof(T) == 0 && std::fread(out.data(), sizeof(T), out.size(), f) == out.size();
-    std::fclose(f);
-    return ok;
-}
+using ref::fail;
+using ref::read_all;
 
 struct Mesh {
     std::vector<float> v0, e1, e2;  // original order, edges formed in fp32 as rt_abi_mesh.hip forms them
@@ -125,24 +116,14 @@ int main(int argc, char** argv) {
         std::fputs("usage: hit_query_ref <mesh> <rays> <out>\n", stderr);
         return 2;
     }
-    std::vector<float> raw, rays;
-    if (!read_all(argv[1], raw) || raw.empty() || raw.size() % 9) { std::fputs("cannot read the mesh\n", stderr); return 1; }
-    if (!read_all(argv[2], rays) || rays.size() % 7) { std::fputs("cannot read the rays\n", stderr); return 1; }
+    std::vector<float> rays;
+    if (!read_all(argv[2], rays) || rays.size() % 7) return fail("cannot read the rays");
     const size_t n = rays.size() / 7;
     Mesh m;
-    m.n = raw.size() / 9;
-    m.v0.resize(3 * m.n);
-    m.e1.resize(3 * m.n);
-    m.e2.resize(3 * m.n);
-    for (size_t i = 0; i < m.n; i++)
-        for (int a = 0; a < 3; a++) {
-            m.v0[3 * i + a] = raw[9 * i + a];
-            m.e1[3 * i + a] = raw[9 * i + 3 + a] - raw[9 * i + a];
-            m.e2[3 * i + a] = raw[9 * i + 6 + a] - raw[9 * i + a];
-        }
     rt::BvhResult b;
-    if (!rt::build_bvh(m.v0.data(), m.e1.data(), m.e2.data(), (uint32_t)m.n, rt::kBvhMaxDepth, &b)) { std::fputs("build failed\n", stderr); return 1; }
-    const float reach = 32.0f * b.maxabs;
+    float reach;
+    if (!ref::load_mesh(argv[1], m.v0, m.e1, m.e2, m.n)) return fail("cannot read the mesh");
+    if (!ref::build_tree(m.v0, m.e1, m.e2, m.n, b, reach)) return fail("build failed");
 
     std::vector<int32_t> count(n), wcount(n), same(n), tri_out;
     std::vector<int64_t> offsets(n + 1);
@@ -185,13 +166,13 @@ int main(int argc, char** argv) {
     offsets[n] = (int64_t)t_out.size();
     const size_t hits = t_out.size();
     FILE* f = std::fopen(argv[3], "wb");
-    if (!f) { std::fputs("cannot write the answers\n", stderr); return 1; }
+    if (!f) return fail("cannot write the answers");
     const uint64_t head[5] = {(uint64_t)n, (uint64_t)hits, walk.nodes, walk.tris, invalid};
     const auto put = [f](const void* p, size_t size, size_t items) { return items == 0 || std::fwrite(p, size, items, f) == items; };  // (an empty vector's data() may be null)
     const bool ok = put(head, 8, 5) && put(count.data(), 4, n) && put(wcount.data(), 4, n) && put(same.data(), 4, n) && put(offsets.data(), 8, n + 1) &&
                     put(t_out.data(), 4, hits) && put(tri_out.data(), 4, hits);
     std::fclose(f);
-    if (!ok) { std::fputs("short write\n", stderr); return 1; }
+    if (!ok) return fail("short write");
     std::printf("OK rays=%zu tris=%zu depth=%u hits=%zu invalid=%llu nodes/ray=%.2f tris/ray=%.2f\n", n, m.n, b.depth, hits, (unsigned long long)invalid,
                 n ? (double)walk.nodes / (double)n : 0.0, n ? (double)walk.tris / (double)n : 0.0);
     return 0;

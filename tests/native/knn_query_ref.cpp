@@ -28,28 +28,15 @@
 #include <utility>
 #include <vector>
 
-#include "../../raytracing_engine_amd/csrc/bvh_build.h"
 #include "../../raytracing_engine_amd/csrc/point_tri.h"
+#define REF_IO_TREE
+#include "ref_io.h"
 
 namespace {
 
-template <class T>
-bool read_all(const char* path, std::vector<T>& out) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long bytes = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    out.resize(bytes > 0 ? (size_t)bytes / sizeof(T) : 0);
-    const bool ok = bytes >= 0 && (size_t)bytes % sizeof(T) == 0 && std::fread(out.data(), sizeof(T), out.size(), f) == out.size();
-    std::fclose(f);
-    return ok;
-}
-
-template <class T>
-bool write_all(FILE* f, const std::vector<T>& v) {
-    return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-}
+using ref::fail;
+using ref::read_all;
+using ref::write_all;
 
 struct Mesh {
     std::vector<float> v0, e1, e2;  // original order, edges formed in fp32 as rt_abi_mesh.hip forms them
@@ -127,29 +114,19 @@ int main(int argc, char** argv) {
         std::fputs("usage: knn_query_ref <mesh> <points> <rmax> <k> <out>\n", stderr);
         return 2;
     }
-    std::vector<float> raw, pts, rmax;
+    std::vector<float> pts, rmax;
     std::vector<uint32_t> ks;
-    if (!read_all(argv[1], raw) || raw.empty() || raw.size() % 9) { std::fputs("cannot read the mesh\n", stderr); return 1; }
-    if (!read_all(argv[2], pts) || pts.size() % 3) { std::fputs("cannot read the points\n", stderr); return 1; }
+    if (!read_all(argv[2], pts) || pts.size() % 3) return fail("cannot read the points");
     const size_t n = pts.size() / 3;
-    if (!read_all(argv[3], rmax) || rmax.size() != n) { std::fputs("cannot read rmax\n", stderr); return 1; }
-    if (!read_all(argv[4], ks) || ks.size() != n) { std::fputs("cannot read k\n", stderr); return 1; }
+    if (!read_all(argv[3], rmax) || rmax.size() != n) return fail("cannot read rmax");
+    if (!read_all(argv[4], ks) || ks.size() != n) return fail("cannot read k");
     for (uint32_t k : ks)
-        if (k == 0 || k > 1024) { std::fputs("k must be 1 .. 1024\n", stderr); return 1; }
+        if (k == 0 || k > 1024) return fail("k must be 1 .. 1024");
     Mesh m;
-    m.n = raw.size() / 9;
-    m.v0.resize(3 * m.n);
-    m.e1.resize(3 * m.n);
-    m.e2.resize(3 * m.n);
-    for (size_t i = 0; i < m.n; i++)
-        for (int a = 0; a < 3; a++) {
-            m.v0[3 * i + a] = raw[9 * i + a];
-            m.e1[3 * i + a] = raw[9 * i + 3 + a] - raw[9 * i + a];
-            m.e2[3 * i + a] = raw[9 * i + 6 + a] - raw[9 * i + a];
-        }
     rt::BvhResult b;
-    if (!rt::build_bvh(m.v0.data(), m.e1.data(), m.e2.data(), (uint32_t)m.n, rt::kBvhMaxDepth, &b)) { std::fputs("build failed\n", stderr); return 1; }
-    const float reach = 32.0f * b.maxabs;
+    float reach;
+    if (!ref::load_mesh(argv[1], m.v0, m.e1, m.e2, m.n)) return fail("cannot read the mesh");
+    if (!ref::build_tree(m.v0, m.e1, m.e2, m.n, b, reach)) return fail("build failed");
     const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
 
     std::vector<int32_t> count(n), walk_count(n), tri_a, tri_b;
@@ -200,12 +177,12 @@ int main(int argc, char** argv) {
         }
     }
     FILE* f = std::fopen(argv[5], "wb");
-    if (!f) { std::fputs("cannot write the answers\n", stderr); return 1; }
+    if (!f) return fail("cannot write the answers");
     const uint64_t head[7] = {(uint64_t)n, (uint64_t)tri_a.size(), found_a, found_b, total_nodes, total_tris, invalid_points};
     const bool ok = std::fwrite(head, 8, 7, f) == 7 && write_all(f, count) && write_all(f, walk_count) && write_all(f, nodes) && write_all(f, tris) &&
                     write_all(f, d2_a) && write_all(f, dist_a) && write_all(f, tri_a) && write_all(f, d2_b) && write_all(f, tri_b);
     std::fclose(f);
-    if (!ok) { std::fputs("short write\n", stderr); return 1; }
+    if (!ok) return fail("short write");
     std::printf("OK points=%zu tris=%zu depth=%u neighbours/point=%.2f nodes/point=%.2f tris/point=%.2f\n", n, m.n, b.depth, n ? (double)found_a / n : 0.0,
                 n ? (double)total_nodes / n : 0.0, n ? (double)total_tris / n : 0.0);
     return 0;

@@ -21,28 +21,15 @@
 #include <utility>
 #include <vector>
 
-#include "../../raytracing_engine_amd/csrc/bvh_build.h"
 #include "../../raytracing_engine_amd/csrc/tri_overlap.h"
+#define REF_IO_TREE
+#include "ref_io.h"
 
 namespace {
 
-template <class T>
-bool read_all(const char* path, std::vector<T>& out) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long bytes = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    out.resize(bytes > 0 ? (size_t)bytes / sizeof(T) : 0);
-    const bool ok = bytes >= 0 && (size_t)bytes % sizeof(T) == 0 && std::fread(out.data(), sizeof(T), out.size(), f) == out.size();
-    std::fclose(f);
-    return ok;
-}
-
-template <class T>
-bool write_all(FILE* f, const std::vector<T>& v) {
-    return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-}
+using ref::fail;
+using ref::read_all;
+using ref::write_all;
 
 struct Mesh {
     std::vector<float> v0, e1, e2;  // original order, edges formed in fp32 as rt_abi_mesh.hip forms them
@@ -83,24 +70,14 @@ int main(int argc, char** argv) {
         std::fputs("usage: overlap_query_ref <mesh> <queries> <out>\n", stderr);
         return 2;
     }
-    std::vector<float> raw, qs;
-    if (!read_all(argv[1], raw) || raw.empty() || raw.size() % 9) { std::fputs("cannot read the mesh\n", stderr); return 1; }
-    if (!read_all(argv[2], qs) || qs.size() % 9) { std::fputs("cannot read the queries\n", stderr); return 1; }
+    std::vector<float> qs;
+    if (!read_all(argv[2], qs) || qs.size() % 9) return fail("cannot read the queries");
     const size_t n = qs.size() / 9;
     Mesh m;
-    m.n = raw.size() / 9;
-    m.v0.resize(3 * m.n);
-    m.e1.resize(3 * m.n);
-    m.e2.resize(3 * m.n);
-    for (size_t i = 0; i < m.n; i++)
-        for (int a = 0; a < 3; a++) {
-            m.v0[3 * i + a] = raw[9 * i + a];
-            m.e1[3 * i + a] = raw[9 * i + 3 + a] - raw[9 * i + a];
-            m.e2[3 * i + a] = raw[9 * i + 6 + a] - raw[9 * i + a];
-        }
     rt::BvhResult b;
-    if (!rt::build_bvh(m.v0.data(), m.e1.data(), m.e2.data(), (uint32_t)m.n, rt::kBvhMaxDepth, &b)) { std::fputs("build failed\n", stderr); return 1; }
-    const float reach = 32.0f * b.maxabs;
+    float reach;
+    if (!ref::load_mesh(argv[1], m.v0, m.e1, m.e2, m.n)) return fail("cannot read the mesh");
+    if (!ref::build_tree(m.v0, m.e1, m.e2, m.n, b, reach)) return fail("build failed");
 
     std::vector<int32_t> count(n), walk_count(n), tri_a, mask_a, tri_b, mask_b, pair_q, pair_t, pair_m;
     std::vector<uint32_t> nodes(n), tris(n);
@@ -144,13 +121,13 @@ int main(int argc, char** argv) {
     }
     offsets[n] = (int64_t)tri_a.size();
     FILE* f = std::fopen(argv[3], "wb");
-    if (!f) { std::fputs("cannot write the answers\n", stderr); return 1; }
+    if (!f) return fail("cannot write the answers");
     const uint64_t head[7] = {(uint64_t)n, (uint64_t)tri_a.size(), (uint64_t)tri_b.size(), total_nodes, total_tris, invalid_queries, (uint64_t)pair_q.size()};
     const bool ok = std::fwrite(head, 8, 7, f) == 7 && write_all(f, count) && write_all(f, walk_count) && write_all(f, nodes) && write_all(f, tris) &&
                     write_all(f, offsets) && write_all(f, tri_a) && write_all(f, mask_a) && write_all(f, tri_b) && write_all(f, mask_b) && write_all(f, pair_q) &&
                     write_all(f, pair_t) && write_all(f, pair_m);
     std::fclose(f);
-    if (!ok) { std::fputs("short write\n", stderr); return 1; }
+    if (!ok) return fail("short write");
     std::printf("OK queries=%zu tris=%zu depth=%u overlaps/query=%.2f nodes/query=%.2f records/query=%.2f\n", n, m.n, b.depth, n ? (double)tri_a.size() / n : 0.0,
                 n ? (double)total_nodes / n : 0.0, n ? (double)total_tris / n : 0.0);
     return 0;

@@ -16,26 +16,13 @@
 #include <vector>
 
 #include "../../raytracing_engine_amd/csrc/tri_section.h"
+#include "ref_io.h"
 
 namespace {
 
-template <class T>
-bool read_all(const char* path, std::vector<T>& out) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long bytes = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    out.resize(bytes > 0 ? (size_t)bytes / sizeof(T) : 0);
-    const bool ok = bytes >= 0 && (size_t)bytes % sizeof(T) == 0 && std::fread(out.data(), sizeof(T), out.size(), f) == out.size();
-    std::fclose(f);
-    return ok;
-}
-
-template <class T>
-bool write_all(FILE* f, const std::vector<T>& v) {
-    return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-}
+using ref::fail;
+using ref::read_all;
+using ref::write_all;
 
 struct Mesh {
     std::vector<float> v0, e1, e2;  // original order, edges formed in fp32 as rt_abi_mesh.hip forms them
@@ -54,26 +41,17 @@ int main(int argc, char** argv) {
         std::fputs("usage: overlap_segment_ref <mesh> <queries> <out> [<pairs>]\n", stderr);
         return 2;
     }
-    std::vector<float> raw, qs;
+    std::vector<float> qs;
     std::vector<int32_t> pairs;
-    if (!read_all(argv[1], raw) || raw.empty() || raw.size() % 9) { std::fputs("cannot read the mesh\n", stderr); return 1; }
-    if (!read_all(argv[2], qs) || qs.size() % 9) { std::fputs("cannot read the queries\n", stderr); return 1; }
-    if (argc == 5 && (!read_all(argv[4], pairs) || pairs.size() % 2)) { std::fputs("cannot read the pairs\n", stderr); return 1; }
+    if (!read_all(argv[2], qs) || qs.size() % 9) return fail("cannot read the queries");
+    if (argc == 5 && (!read_all(argv[4], pairs) || pairs.size() % 2)) return fail("cannot read the pairs");
     const size_t n = qs.size() / 9;
     Mesh m;
-    m.n = raw.size() / 9;
-    m.v0.resize(3 * m.n);
-    m.e1.resize(3 * m.n);
-    m.e2.resize(3 * m.n);
+    if (!ref::load_mesh(argv[1], m.v0, m.e1, m.e2, m.n)) return fail("cannot read the mesh");
     float maxabs = 1.0f;  // max(1, largest |coordinate| of v0, fl(v0 + e1), fl(v0 + e2)): build_bvh's maxabs (csrc/bvh_build.cpp)
-    for (size_t i = 0; i < m.n; i++)
-        for (int a = 0; a < 3; a++) {
-            const float p0 = m.v0[3 * i + a] = raw[9 * i + a];
-            const float f1 = m.e1[3 * i + a] = raw[9 * i + 3 + a] - raw[9 * i + a];
-            const float f2 = m.e2[3 * i + a] = raw[9 * i + 6 + a] - raw[9 * i + a];
-            maxabs = std::fmax(maxabs, std::fmax(std::fabs(p0), std::fmax(std::fabs(p0 + f1), std::fabs(p0 + f2))));
-        }
-    const float reach = 32.0f * maxabs;
+    for (size_t i = 0; i < 3 * m.n; i++)
+        maxabs = std::fmax(maxabs, std::fmax(std::fabs(m.v0[i]), std::fmax(std::fabs(m.v0[i] + m.e1[i]), std::fabs(m.v0[i] + m.e2[i]))));
+    const float reach = ref::reach_of(maxabs);
 
     const auto query = [&](size_t i) {
         const float* p = &qs[9 * i];
@@ -117,12 +95,12 @@ int main(int argc, char** argv) {
         push_segment(pair_seg, s);
     }
     FILE* f = std::fopen(argv[3], "wb");
-    if (!f) { std::fputs("cannot write the answers\n", stderr); return 1; }
+    if (!f) return fail("cannot write the answers");
     const uint64_t head[4] = {(uint64_t)n, (uint64_t)tri.size(), invalid_queries, (uint64_t)pair_mask.size()};
     const bool ok = std::fwrite(head, 8, 4, f) == 4 && write_all(f, count) && write_all(f, offsets) && write_all(f, tri) && write_all(f, mask) && write_all(f, seg) &&
                     write_all(f, ends) && write_all(f, d2) && write_all(f, pair_mask) && write_all(f, pair_seg) && write_all(f, pair_ends);
     std::fclose(f);
-    if (!ok) { std::fputs("short write\n", stderr); return 1; }
+    if (!ok) return fail("short write");
     std::printf("OK queries=%zu tris=%zu entries=%zu pairs=%zu\n", n, m.n, tri.size(), pair_mask.size());
     return 0;
 }

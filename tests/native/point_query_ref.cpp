@@ -19,23 +19,14 @@
 #include <limits>
 #include <vector>
 
-#include "../../raytracing_engine_amd/csrc/bvh_build.h"
 #include "../../raytracing_engine_amd/csrc/point_tri.h"
+#define REF_IO_TREE
+#include "ref_io.h"
 
 namespace {
 
-template <class T>
-bool read_all(const char* path, std::vector<T>& out) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long bytes = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    out.resize(bytes > 0 ? (size_t)bytes / sizeof(T) : 0);
-    const bool ok = bytes >= 0 && (size_t)bytes % sizeof(T) == 0 && std::fread(out.data(), sizeof(T), out.size(), f) == out.size();
-    std::fclose(f);
-    return ok;
-}
+using ref::fail;
+using ref::read_all;
 
 struct Mesh {
     std::vector<float> v0, e1, e2;  // original order, edges formed in fp32 as rt_abi_mesh.hip forms them
@@ -114,25 +105,15 @@ int main(int argc, char** argv) {
         std::fputs("usage: point_query_ref <mesh> <points> <out> [rmax | -] [pairs]\n", stderr);
         return 2;
     }
-    std::vector<float> raw, pts, rmax;
-    if (!read_all(argv[1], raw) || raw.empty() || raw.size() % 9) { std::fputs("cannot read the mesh\n", stderr); return 1; }
-    if (!read_all(argv[2], pts) || pts.size() % 3) { std::fputs("cannot read the points\n", stderr); return 1; }
+    std::vector<float> pts, rmax;
+    if (!read_all(argv[2], pts) || pts.size() % 3) return fail("cannot read the points");
     const size_t n = pts.size() / 3;
-    if (argc > 4 && std::strcmp(argv[4], "-") != 0 && (!read_all(argv[4], rmax) || rmax.size() != n)) { std::fputs("cannot read rmax\n", stderr); return 1; }
+    if (argc > 4 && std::strcmp(argv[4], "-") != 0 && (!read_all(argv[4], rmax) || rmax.size() != n)) return fail("cannot read rmax");
     Mesh m;
-    m.n = raw.size() / 9;
-    m.v0.resize(3 * m.n);
-    m.e1.resize(3 * m.n);
-    m.e2.resize(3 * m.n);
-    for (size_t i = 0; i < m.n; i++)
-        for (int a = 0; a < 3; a++) {
-            m.v0[3 * i + a] = raw[9 * i + a];
-            m.e1[3 * i + a] = raw[9 * i + 3 + a] - raw[9 * i + a];
-            m.e2[3 * i + a] = raw[9 * i + 6 + a] - raw[9 * i + a];
-        }
     rt::BvhResult b;
-    if (!rt::build_bvh(m.v0.data(), m.e1.data(), m.e2.data(), (uint32_t)m.n, rt::kBvhMaxDepth, &b)) { std::fputs("build failed\n", stderr); return 1; }
-    const float reach = 32.0f * b.maxabs;
+    float reach;
+    if (!ref::load_mesh(argv[1], m.v0, m.e1, m.e2, m.n)) return fail("cannot read the mesh");
+    if (!ref::build_tree(m.v0, m.e1, m.e2, m.n, b, reach)) return fail("build failed");
 
     Column brute(n), walked(n);
     Walk walk{m, b};
@@ -151,7 +132,7 @@ int main(int argc, char** argv) {
         walked.set(i, m, p, w, limit2, invalid);
     }
     FILE* f = std::fopen(argv[3], "wb");
-    if (!f) { std::fputs("cannot write the answers\n", stderr); return 1; }
+    if (!f) return fail("cannot write the answers");
     const uint64_t head[3] = {(uint64_t)n, walk.nodes, walk.tris};
     bool ok = std::fwrite(head, 8, 3, f) == 3 && brute.write(f) && walked.write(f);
     if (argc > 5) {
@@ -165,7 +146,7 @@ int main(int argc, char** argv) {
         }
     }
     std::fclose(f);
-    if (!ok) { std::fputs("short write\n", stderr); return 1; }
+    if (!ok) return fail("short write");
     std::printf("OK points=%zu tris=%zu depth=%u nodes/point=%.2f tris/point=%.2f\n", n, m.n, b.depth, n ? (double)walk.nodes / n : 0.0, n ? (double)walk.tris / n : 0.0);
     return 0;
 }

@@ -50,6 +50,8 @@
 #include <vector>
 #include <atomic>
 
+#include "ref_io.h"
+
 struct V { double x, y, z; };
 static inline V operator+(V a, V b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
 static inline V operator-(V a, V b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
@@ -179,19 +181,6 @@ static void path(const std::vector<Tri>& tris, const Params& P, int px, int py, 
     }
 }
 
-static std::vector<double> read_doubles(const char* name) {
-    std::vector<double> v;
-    FILE* f = std::fopen(name, "rb");
-    if (!f) return v;
-    std::fseek(f, 0, SEEK_END);
-    const long size = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    v.resize(size > 0 ? (size_t)size / 8 : 0);
-    if (!v.empty() && std::fread(v.data(), 8, v.size(), f) != v.size()) v.clear();
-    std::fclose(f);
-    return v;
-}
-
 struct Moments { double mean[3], se[3], sd[3]; };
 
 /* the pixels [x0, x1) x [y0, y1): sums[(b * pixels + p) * 6 + (k | 3 + k)] = sum and sum of squares of unit (b, p), channel k */
@@ -240,7 +229,8 @@ static Moments reduce(const std::vector<double>& sums, const Params& P, int x0, 
 
 int main(int argc, char** argv) {
     if (argc < 4) { std::fprintf(stderr, "usage: pt_transport_ref SCENE PARAMS OUT [threads]\n"); return 2; }
-    const std::vector<double> sc = read_doubles(argv[1]), pr = read_doubles(argv[2]);
+    std::vector<double> sc, pr;
+    if (!ref::read_all(argv[1], sc) || !ref::read_all(argv[2], pr)) { std::fprintf(stderr, "bad input files\n"); return 2; }
     int threads = argc > 4 ? std::atoi(argv[4]) : 16;
     if (threads < 1) threads = 1;
     if (sc.empty() || sc.size() % 17 != 0 || pr.size() != 24) { std::fprintf(stderr, "bad input files\n"); return 2; }

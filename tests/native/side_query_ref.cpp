@@ -24,23 +24,14 @@
 #include <limits>
 #include <vector>
 
-#include "../../raytracing_engine_amd/csrc/bvh_build.h"
 #include "../../raytracing_engine_amd/csrc/ray_parity.h"
+#define REF_IO_TREE
+#include "ref_io.h"
 
 namespace {
 
-template <class T>
-bool read_all(const char* path, std::vector<T>& out) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long bytes = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    out.resize(bytes > 0 ? (size_t)bytes / sizeof(T) : 0);
-    const bool ok = bytes >= 0 && (size_t)bytes % sizeof(T) == 0 && std::fread(out.data(), sizeof(T), out.size(), f) == out.size();
-    std::fclose(f);
-    return ok;
-}
+using ref::fail;
+using ref::read_all;
 
 struct Mesh {
     std::vector<float> v0, e1, e2;  // original order, edges formed in fp32 as rt_abi_mesh.hip forms them
@@ -126,25 +117,15 @@ int main(int argc, char** argv) {
         std::fputs("usage: side_query_ref <mesh> <points> <out> [rays]\n", stderr);
         return 2;
     }
-    std::vector<float> raw, pts, rays;
-    if (!read_all(argv[1], raw) || raw.empty() || raw.size() % 9) { std::fputs("cannot read the mesh\n", stderr); return 1; }
-    if (!read_all(argv[2], pts) || pts.size() % 3) { std::fputs("cannot read the points\n", stderr); return 1; }
-    if (argc > 4 && (!read_all(argv[4], rays) || rays.size() % 6)) { std::fputs("cannot read the rays\n", stderr); return 1; }
+    std::vector<float> pts, rays;
+    if (!read_all(argv[2], pts) || pts.size() % 3) return fail("cannot read the points");
+    if (argc > 4 && (!read_all(argv[4], rays) || rays.size() % 6)) return fail("cannot read the rays");
     const size_t n = pts.size() / 3, n_rays = rays.size() / 6;
     Mesh m;
-    m.n = raw.size() / 9;
-    m.v0.resize(3 * m.n);
-    m.e1.resize(3 * m.n);
-    m.e2.resize(3 * m.n);
-    for (size_t i = 0; i < m.n; i++)
-        for (int a = 0; a < 3; a++) {
-            m.v0[3 * i + a] = raw[9 * i + a];
-            m.e1[3 * i + a] = raw[9 * i + 3 + a] - raw[9 * i + a];
-            m.e2[3 * i + a] = raw[9 * i + 6 + a] - raw[9 * i + a];
-        }
     rt::BvhResult b;
-    if (!rt::build_bvh(m.v0.data(), m.e1.data(), m.e2.data(), (uint32_t)m.n, rt::kBvhMaxDepth, &b)) { std::fputs("build failed\n", stderr); return 1; }
-    const float reach = 32.0f * b.maxabs;
+    float reach;
+    if (!ref::load_mesh(argv[1], m.v0, m.e1, m.e2, m.n)) return fail("cannot read the mesh");
+    if (!ref::build_tree(m.v0, m.e1, m.e2, m.n, b, reach)) return fail("build failed");
 
     std::vector<int32_t> inside(n), third(n), cb(3 * n), cw(3 * n), ctri(3 * n, -1), rtri(n_rays, -1);
     std::vector<float> ct(3 * n, std::numeric_limits<float>::infinity()), rtt(n_rays, std::numeric_limits<float>::infinity());
@@ -176,13 +157,13 @@ int main(int argc, char** argv) {
         rtri[r] = best.tri;
     }
     FILE* f = std::fopen(argv[3], "wb");
-    if (!f) { std::fputs("cannot write the answers\n", stderr); return 1; }
+    if (!f) return fail("cannot write the answers");
     const uint64_t head[5] = {(uint64_t)n, walk.nodes, walk.tris, thirds, (uint64_t)n_rays};
     const bool ok = std::fwrite(head, 8, 5, f) == 5 && std::fwrite(inside.data(), 4, n, f) == n && std::fwrite(third.data(), 4, n, f) == n &&
                     std::fwrite(cb.data(), 4, 3 * n, f) == 3 * n && std::fwrite(cw.data(), 4, 3 * n, f) == 3 * n && std::fwrite(ct.data(), 4, 3 * n, f) == 3 * n &&
                     std::fwrite(ctri.data(), 4, 3 * n, f) == 3 * n && std::fwrite(rtt.data(), 4, n_rays, f) == n_rays && std::fwrite(rtri.data(), 4, n_rays, f) == n_rays;
     std::fclose(f);
-    if (!ok) { std::fputs("short write\n", stderr); return 1; }
+    if (!ok) return fail("short write");
     std::printf("OK points=%zu tris=%zu depth=%u third=%llu nodes/walk=%.2f tris/walk=%.2f\n", n, m.n, b.depth, (unsigned long long)thirds,
                 n ? (double)walk.nodes / (3.0 * n) : 0.0, n ? (double)walk.tris / (3.0 * n) : 0.0);
     return 0;

@@ -17,13 +17,12 @@ THE CONTRACT in float64, with point_exact's Kp = 16 and unit: every triangle wit
 D > rmax + Kp unit is, and each listed dist is within Kp unit of its triangle's D."""
 import functools
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 import point_exact as PX  # noqa: E402
 
 ROOT = PX.ROOT
@@ -37,20 +36,10 @@ INF_POINTS = 8
 LONGEST = 256  # the longest list outside the +inf block (asserted on the CPU: test_neighbor_query_host.py)
 N_FAMILY = 600
 
-_BUILT = {}
-
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/neighbor_query_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="neighbor_query_ref_")
-        exe = os.path.join(where, "neighbor_query_ref_asan" if sanitized else "neighbor_query_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-pthread"] + flags +
-                       [os.path.join(ROOT, "tests", "native", "neighbor_query_ref.cpp"), os.path.join(ROOT, "raytracing_engine_amd", "csrc", "bvh_build.cpp"),
-                        "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("neighbor_query_ref", [NR.BVH_BUILD], sanitized, where, flags=("-pthread",))
 
 
 def reference(verts, p, rmax, sanitized=False):
@@ -58,37 +47,16 @@ def reference(verts, p, rmax, sanitized=False):
     INVALID for an invalid point), offsets (int64, n + 1), d2, dist (float32), tri (int32): the brute-force lists; walk_count, walk_d2,
     walk_tri: the tree walk's; nodes, tris (uint32 per point): what the walk fetched and tested; neighbors, walk_neighbors, nodes_total,
     tris_total, invalid: the sums."""
-    exe = build_reference(sanitized)
     p = np.ascontiguousarray(p, f32).reshape(-1, 3)
     n = len(p)
-    rmax = np.ascontiguousarray(np.broadcast_to(np.asarray(rmax, f32), (n,)), f32)
-    with tempfile.TemporaryDirectory(prefix="neighbor_query_") as d:
-        np.ascontiguousarray(verts, f32).tofile(os.path.join(d, "mesh"))
-        p.tofile(os.path.join(d, "points"))
-        rmax.tofile(os.path.join(d, "rmax"))
-        run = subprocess.run([exe, os.path.join(d, "mesh"), os.path.join(d, "points"), os.path.join(d, "rmax"), os.path.join(d, "out")], capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"neighbor_query_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(d, "out"), np.uint8)
-    head = raw[:48].view(np.uint64)
-    assert int(head[0]) == n
-    na, nb = int(head[1]), int(head[2])
-    out = dict(neighbors=na, walk_neighbors=nb, nodes_total=int(head[3]), tris_total=int(head[4]), invalid=int(head[5]))
-    at = 48
-    for key, dt, count in (("count", np.int32, n), ("walk_count", np.int32, n), ("nodes", np.uint32, n), ("tris", np.uint32, n), ("offsets", np.int64, n + 1),
-                           ("d2", f32, na), ("dist", f32, na), ("tri", np.int32, na), ("walk_d2", f32, nb), ("walk_tri", np.int32, nb)):
-        size = count * np.dtype(dt).itemsize
-        out[key] = raw[at:at + size].view(dt).copy()
-        at += size
-    assert at == len(raw)
-    return out
+    raw = NR.run(build_reference(sanitized), dict(mesh=np.asarray(verts, f32), points=p, rmax=np.broadcast_to(np.asarray(rmax, f32), (n,))))
+    head, out = NR.unpack(raw, 6, lambda h: (("count", np.int32, n), ("walk_count", np.int32, n), ("nodes", np.uint32, n), ("tris", np.uint32, n), ("offsets", np.int64, n + 1),
+                                             ("d2", f32, h[1]), ("dist", f32, h[1]), ("tri", np.int32, h[1]), ("walk_d2", f32, h[2]), ("walk_tri", np.int32, h[2])))
+    assert head[0] == n
+    return dict(out, neighbors=head[1], walk_neighbors=head[2], nodes_total=head[3], tris_total=head[4], invalid=head[5])
 
 
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype == f32:
-        return b.dtype == f32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    return a.shape == b.shape and np.array_equal(a, b)
+same_bits = NR.same_bits
 
 
 def walk_is_brute(ref):

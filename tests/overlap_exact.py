@@ -25,13 +25,12 @@ set; low < -M: it must be clear; a float64 det == 0 decides nothing.
 """
 import functools
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 import point_exact as PX  # noqa: E402
 
 RX = PX.RX
@@ -46,20 +45,10 @@ _SEED = {k: 500 + i for i, k in enumerate(FAMILIES)}
 ALL_MESHES = ("soup", "soup_small", "soup_far", "terrain", "grid", "needle")
 SOUP_CUT = 256
 
-_BUILT = {}
-
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/overlap_query_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="overlap_query_ref_")
-        exe = os.path.join(where, "overlap_query_ref_asan" if sanitized else "overlap_query_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-pthread"] + flags +
-                       [os.path.join(ROOT, "tests", "native", "overlap_query_ref.cpp"), os.path.join(ROOT, "raytracing_engine_amd", "csrc", "bvh_build.cpp"),
-                        "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("overlap_query_ref", [NR.BVH_BUILD], sanitized, where, flags=("-pthread",))
 
 
 def reference(verts, q, sanitized=False):
@@ -67,29 +56,14 @@ def reference(verts, q, sanitized=False):
     offsets (int64, n + 1), tri, edges (int32): the brute-force lists; walk_count, walk_tri, walk_edges: the tree walk's; nodes, tris
     (uint32 per query): what the walk fetched; overlaps, walk_overlaps, nodes_total, tris_total, invalid: the sums; pair_q, pair_t,
     pair_mask: every pair with cand (mask 0 included)."""
-    exe = build_reference(sanitized)
     q = np.ascontiguousarray(q, f32).reshape(-1, 9)
     n = len(q)
-    with tempfile.TemporaryDirectory(prefix="overlap_query_") as d:
-        np.ascontiguousarray(verts, f32).tofile(os.path.join(d, "mesh"))
-        q.tofile(os.path.join(d, "queries"))
-        run = subprocess.run([exe, os.path.join(d, "mesh"), os.path.join(d, "queries"), os.path.join(d, "out")], capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"overlap_query_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(d, "out"), np.uint8)
-    head = raw[:56].view(np.uint64)
-    assert int(head[0]) == n
-    na, nb, npairs = int(head[1]), int(head[2]), int(head[6])
-    out = dict(overlaps=na, walk_overlaps=nb, nodes_total=int(head[3]), tris_total=int(head[4]), invalid=int(head[5]))
-    at = 56
-    for key, dt, count in (("count", np.int32, n), ("walk_count", np.int32, n), ("nodes", np.uint32, n), ("tris", np.uint32, n), ("offsets", np.int64, n + 1),
-                           ("tri", np.int32, na), ("edges", np.int32, na), ("walk_tri", np.int32, nb), ("walk_edges", np.int32, nb),
-                           ("pair_q", np.int32, npairs), ("pair_t", np.int32, npairs), ("pair_mask", np.int32, npairs)):
-        size = count * np.dtype(dt).itemsize
-        out[key] = raw[at:at + size].view(dt).copy()
-        at += size
-    assert at == len(raw)
-    return out
+    raw = NR.run(build_reference(sanitized), dict(mesh=np.asarray(verts, f32), queries=q))
+    head, out = NR.unpack(raw, 7, lambda h: (("count", np.int32, n), ("walk_count", np.int32, n), ("nodes", np.uint32, n), ("tris", np.uint32, n), ("offsets", np.int64, n + 1),
+                                             ("tri", np.int32, h[1]), ("edges", np.int32, h[1]), ("walk_tri", np.int32, h[2]), ("walk_edges", np.int32, h[2]),
+                                             ("pair_q", np.int32, h[6]), ("pair_t", np.int32, h[6]), ("pair_mask", np.int32, h[6])))
+    assert head[0] == n
+    return dict(out, overlaps=head[1], walk_overlaps=head[2], nodes_total=head[3], tris_total=head[4], invalid=head[5])
 
 
 def walk_is_brute(ref):

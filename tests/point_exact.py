@@ -26,13 +26,12 @@ margin costs no power: test_point_query_host.py demonstrates it on float64 answe
 nearest triangle withheld.
 """
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 import ray_exact as RX  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,55 +155,31 @@ def closest_point64(em, p, tri):
 
 
 # ---- the native reference ------------------------------------------------------------------------------------------------------
-_BUILT = {}
 
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/point_query_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="point_query_ref_")
-        exe = os.path.join(where, "point_query_ref_asan" if sanitized else "point_query_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-pthread"] + flags +
-                       [os.path.join(ROOT, "tests", "native", "point_query_ref.cpp"), os.path.join(ROOT, "raytracing_engine_amd", "csrc", "bvh_build.cpp"),
-                        "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("point_query_ref", [NR.BVH_BUILD], sanitized, where, flags=("-pthread",))
 
 
 def reference(verts, p, rmax=None, pairs=None, sanitized=False):
     """The native reference on mesh `verts` and points p.  Returns dict(brute=..., walk=..., nodes, tris[, pair_d2]); brute and
     walk are dicts of tri (int32), d2, u, v, dist (float32) and c (n, 3)."""
-    exe = build_reference(sanitized)
     p = np.ascontiguousarray(p, f32).reshape(-1, 3)
     n = len(p)
-    with tempfile.TemporaryDirectory(prefix="point_query_") as d:
-        np.ascontiguousarray(verts, f32).tofile(os.path.join(d, "mesh"))
-        p.tofile(os.path.join(d, "points"))
-        cmd = [exe, os.path.join(d, "mesh"), os.path.join(d, "points"), os.path.join(d, "out"), "-"]
-        if rmax is not None:
-            np.ascontiguousarray(rmax, f32).tofile(os.path.join(d, "rmax"))
-            cmd[4] = os.path.join(d, "rmax")
-        if pairs is not None:
-            np.ascontiguousarray(pairs, np.int32).tofile(os.path.join(d, "pairs"))
-            cmd.append(os.path.join(d, "pairs"))
-        run = subprocess.run(cmd, capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"point_query_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(d, "out"), np.uint8)
-    head = raw[:24].view(np.uint64)
-    assert int(head[0]) == n
-    out = dict(nodes=int(head[1]), tris=int(head[2]))
-    at = 24
-    for name in ("brute", "walk"):
-        col = {}
-        for key, dt, width in (("tri", np.int32, 1), ("d2", f32, 1), ("u", f32, 1), ("v", f32, 1), ("dist", f32, 1), ("c", f32, 3)):
-            col[key] = raw[at:at + 4 * n * width].view(dt).copy()
-            at += 4 * n * width
-        col["c"] = col["c"].reshape(n, 3)
-        out[name] = col
+    inputs = dict(mesh=np.asarray(verts, f32), points=p, out=NR.OUT, rmax=None if rmax is None else np.asarray(rmax, f32))
     if pairs is not None:
-        out["pair_d2"] = raw[at:].view(f32).copy()
+        inputs["pairs"] = np.asarray(pairs, np.int32)
+    column = (("tri", np.int32, n), ("d2", f32, n), ("u", f32, n), ("v", f32, n), ("dist", f32, n), ("c", f32, 3 * n))
+    fields = [(f"{name}.{key}", dt, count) for name in ("brute", "walk") for key, dt, count in column]
+    head, flat = NR.unpack(NR.run(build_reference(sanitized), inputs), 3, fields + [("pair_d2", f32, 0 if pairs is None else inputs["pairs"].size // 2)])
+    assert head[0] == n
+    out = dict(nodes=head[1], tris=head[2], brute={}, walk={})
+    for name in ("brute", "walk"):
+        out[name] = {key: flat[f"{name}.{key}"] for key, _, _ in column}
+        out[name]["c"] = out[name]["c"].reshape(n, 3)
+    if pairs is not None:
+        out["pair_d2"] = flat["pair_d2"]
     return out
 
 

@@ -33,6 +33,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import attr_exact as AX  # noqa: E402
 import hit_exact as HX  # noqa: E402
+import native_ref as NR  # noqa: E402
 import neighbor_exact as NX  # noqa: E402
 import point_exact as PX  # noqa: E402
 import ray_exact as RX  # noqa: E402
@@ -94,14 +95,7 @@ def scaled_problem(k, scale=None, check=True, **q):
     return out
 
 
-def bits_equal(a, b):
-    """Bit-equal arrays of one dtype and shape (NaN equals the same NaN, -0.0 is not 0.0)."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    if a.dtype == f32:
-        return bool(np.array_equal(a.view(np.uint32), b.view(np.uint32)))
-    return bool(np.array_equal(a, b))
+bits_equal = functools.partial(NR.same_bits, same_dtype=True)  # bit-equal arrays of one dtype and shape (NaN equals the same NaN, -0.0 is not 0.0)
 
 
 def transformed(answers, k):

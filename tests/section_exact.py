@@ -26,13 +26,12 @@ S = the largest |coordinate| among A0, A1, A2, v0, fl(v0 + e1), fl(v0 + e2).
 """
 import functools
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 import overlap_exact as OX  # noqa: E402
 
 ROOT = OX.ROOT
@@ -43,18 +42,10 @@ CHECKED_FAMILIES = ("a", "b", "c", "d")
 COVERED_FAMILIES = ("a", "c", "d")
 PAIRS = [(b, c) for b in range(6) for c in range(b + 1, 6)]  # the order of the native program's d2 columns
 
-_BUILT = {}
-
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/overlap_segment_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="overlap_segment_ref_")
-        exe = os.path.join(where, "overlap_segment_ref_asan" if sanitized else "overlap_segment_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off"] + flags + [os.path.join(ROOT, "tests", "native", "overlap_segment_ref.cpp"), "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("overlap_segment_ref", (), sanitized, where)
 
 
 def reference(verts, q, pairs=None, sanitized=False):
@@ -62,33 +53,18 @@ def reference(verts, q, pairs=None, sanitized=False):
     offsets (int64, n + 1), tri, mask, ends (int32 per entry of the brute-force list), seg (entries, 2, 3) float32, d2 (entries, 15)
     float32 (PAIRS order, NaN where a bit of the pair is clear), entries, invalid; with pairs ((k, 2) int32: query, triangle):
     pair_mask, pair_seg, pair_ends of those pairs, listed or not."""
-    exe = build_reference(sanitized)
     q = np.ascontiguousarray(q, f32).reshape(-1, 9)
     n = len(q)
-    with tempfile.TemporaryDirectory(prefix="overlap_segment_") as d:
-        np.ascontiguousarray(verts, f32).tofile(os.path.join(d, "mesh"))
-        q.tofile(os.path.join(d, "queries"))
-        cmd = [exe, os.path.join(d, "mesh"), os.path.join(d, "queries"), os.path.join(d, "out")]
-        if pairs is not None:
-            np.ascontiguousarray(pairs, np.int32).reshape(-1, 2).tofile(os.path.join(d, "pairs"))
-            cmd.append(os.path.join(d, "pairs"))
-        run = subprocess.run(cmd, capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"overlap_segment_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(d, "out"), np.uint8)
-    head = raw[:32].view(np.uint64)
-    assert int(head[0]) == n
-    k, npairs = int(head[1]), int(head[3])
-    out = dict(entries=k, invalid=int(head[2]))
-    at = 32
-    for key, dt, count in (("count", np.int32, n), ("offsets", np.int64, n + 1), ("tri", np.int32, k), ("mask", np.int32, k), ("seg", f32, 6 * k), ("ends", np.int32, k),
-                           ("d2", f32, 15 * k), ("pair_mask", np.int32, npairs), ("pair_seg", f32, 6 * npairs), ("pair_ends", np.int32, npairs)):
-        size = count * np.dtype(dt).itemsize
-        out[key] = raw[at:at + size].view(dt).copy()
-        at += size
-    assert at == len(raw)
+    inputs = dict(mesh=np.asarray(verts, f32), queries=q, out=NR.OUT)
+    if pairs is not None:
+        inputs["pairs"] = np.asarray(pairs, np.int32).reshape(-1, 2)
+    head, out = NR.unpack(NR.run(build_reference(sanitized), inputs), 4,
+                          lambda h: (("count", np.int32, n), ("offsets", np.int64, n + 1), ("tri", np.int32, h[1]), ("mask", np.int32, h[1]), ("seg", f32, 6 * h[1]),
+                                     ("ends", np.int32, h[1]), ("d2", f32, 15 * h[1]), ("pair_mask", np.int32, h[3]), ("pair_seg", f32, 6 * h[3]), ("pair_ends", np.int32, h[3])))
+    assert head[0] == n
+    k, npairs = head[1], head[3]
     out["seg"], out["d2"], out["pair_seg"] = out["seg"].reshape(k, 2, 3), out["d2"].reshape(k, 15), out["pair_seg"].reshape(npairs, 2, 3)
-    return out
+    return dict(out, entries=k, invalid=head[2])
 
 
 @functools.lru_cache(maxsize=None)

@@ -22,13 +22,12 @@ majority to be wrong for none.
 """
 import functools
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 import point_exact as PX  # noqa: E402
 import ray_exact as RX  # noqa: E402
 
@@ -205,52 +204,28 @@ def family(name, verts, n, seed=0):
 
 
 # ---- the native reference ------------------------------------------------------------------------------------------------------
-_BUILT = {}
 
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/side_query_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="side_query_ref_")
-        exe = os.path.join(where, "side_query_ref_asan" if sanitized else "side_query_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-pthread"] + flags +
-                       [os.path.join(ROOT, "tests", "native", "side_query_ref.cpp"), os.path.join(ROOT, "raytracing_engine_amd", "csrc", "bvh_build.cpp"),
-                        "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("side_query_ref", [NR.BVH_BUILD], sanitized, where, flags=("-pthread",))
 
 
 def reference(verts, p, rays=None, sanitized=False):
     """The native reference on mesh `verts` and points p: dict(inside (n,), third (n,), brute, walk (n, 3) crossings, t, tri (n, 3)
     closest accepted triangle along D[k], nodes, tris, thirds[, ray_t, ray_tri for rays = (origins, dirs)])."""
-    exe = build_reference(sanitized)
     p = np.ascontiguousarray(p, f32).reshape(-1, 3)
     n = len(p)
-    with tempfile.TemporaryDirectory(prefix="side_query_") as d:
-        np.ascontiguousarray(verts, f32).tofile(os.path.join(d, "mesh"))
-        p.tofile(os.path.join(d, "points"))
-        cmd = [exe, os.path.join(d, "mesh"), os.path.join(d, "points"), os.path.join(d, "out")]
-        if rays is not None:
-            np.ascontiguousarray(np.concatenate([np.asarray(rays[0], f32).reshape(-1, 3), np.asarray(rays[1], f32).reshape(-1, 3)], 1), f32).tofile(os.path.join(d, "rays"))
-            cmd.append(os.path.join(d, "rays"))
-        run = subprocess.run(cmd, capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"side_query_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(d, "out"), np.uint8)
-    head = raw[:40].view(np.uint64)
-    assert int(head[0]) == n
-    m = int(head[4])
-    out = dict(nodes=int(head[1]), tris=int(head[2]), thirds=int(head[3]))
-    at = 40
-    for key, dt, count in (("inside", np.int32, n), ("third", np.int32, n), ("brute", np.int32, 3 * n), ("walk", np.int32, 3 * n), ("t", f32, 3 * n),
-                           ("tri", np.int32, 3 * n), ("ray_t", f32, m), ("ray_tri", np.int32, m)):
-        out[key] = raw[at:at + 4 * count].view(dt).copy()
-        at += 4 * count
-    assert at == len(raw)
+    inputs = dict(mesh=np.asarray(verts, f32), points=p, out=NR.OUT)
+    if rays is not None:
+        inputs["rays"] = np.concatenate([np.asarray(rays[0], f32).reshape(-1, 3), np.asarray(rays[1], f32).reshape(-1, 3)], 1).astype(f32, copy=False)
+    head, out = NR.unpack(NR.run(build_reference(sanitized), inputs), 5,
+                          lambda h: (("inside", np.int32, n), ("third", np.int32, n), ("brute", np.int32, 3 * n), ("walk", np.int32, 3 * n), ("t", f32, 3 * n),
+                                     ("tri", np.int32, 3 * n), ("ray_t", f32, h[4]), ("ray_tri", np.int32, h[4])))
+    assert head[0] == n
     for key in ("brute", "walk", "t", "tri"):
         out[key] = out[key].reshape(n, 3)
-    return out
+    return dict(out, nodes=head[1], tris=head[2], thirds=head[3])
 
 
 # ---- one case per mesh: the points of every family and their reference, computed once and shared ---------------------------------

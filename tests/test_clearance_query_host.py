@@ -5,66 +5,43 @@ equals its brute force bit for bit on every family, on still and on moved vertic
 argument: no GPU needed); the brute force satisfies the float64 contract of tests/clearance_exact.py with the committed Kc; and that
 contract rejects wrong answers.  The kernel itself is tested on the GPU (tests/test_gpu_clearance_query.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_boundary as AB
 import clearance_exact as CX
 import raytracing_engine_amd as R
-from raytracing_engine_amd import _lib
 
 PX, OX = CX.PX, CX.OX
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = ("rt_default_clearance_query_params", "rt_query_clearance_device", "rt_get_clearance_query_stats")
+V = C.c_void_p(16)
+KIND = AB.Kind(functions=FUNCTIONS, methods=("query_clearance", "clearance_query_stats"), params="ClearanceQueryParams", stats="ClearanceQueryStats",
+               params_c="rt_clearance_query_params", stats_c="rt_clearance_query_stats", params_fields=["tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks", "count_traversal"],
+               stats_fields=frozenset(["ms", "nodes_visited", "tris_tested", "invalid_triangles", "stack_overflow", "queries"]),
+               default="rt_default_clearance_query_params",
+               null_calls=(("rt_query_clearance_device", (None, None, 0, None, None, None, None, None)),
+                           ("rt_query_clearance_device", (V, None, 1, C.byref(R.ClearanceQueryParams()), V, V, V, V)),
+                           ("rt_get_clearance_query_stats", (C.byref(R.ClearanceQueryStats()),)), ("rt_default_clearance_query_params", ())))
 f32 = np.float32
 
 
 # ---- the boundary --------------------------------------------------------------------------------------------------------------
 def test_the_functions_are_exported_and_bound():
-    lib = R.load()
-    for name in FUNCTIONS:
-        assert hasattr(lib, name), name
-        assert name in _lib.PROTOTYPES, name
-    assert lib.rt_abi_version() == 4  # additions only
-    assert callable(R.Renderer.query_clearance) and callable(R.Renderer.clearance_query_stats)
+    AB.exports(KIND)
 
 
 def test_a_null_context_is_refused():
-    lib = R.load()
-    p = R.ClearanceQueryParams()
-    assert lib.rt_query_clearance_device(None, None, None, 0, None, None, None, None, None) == -1  # RT_ERR_INVALID: nothing touched
-    assert lib.rt_query_clearance_device(None, C.c_void_p(16), None, 1, C.byref(p), C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), C.c_void_p(16)) == -1
-    assert lib.rt_get_clearance_query_stats(None, C.byref(R.ClearanceQueryStats())) == -1
-    assert lib.rt_default_clearance_query_params(None) == -1
+    AB.null_context(KIND)
 
 
 def test_struct_layouts_match_the_header(tmp_path):
     """sizeof/offsetof as gcc computes them from include/rt_abi.h vs the ctypes mirrors."""
-    pf = [n for n, _ in R.ClearanceQueryParams._fields_]
-    sf = [n for n, _ in R.ClearanceQueryStats._fields_]
-    prog = tmp_path / "layout.c"
-    prog.write_text("#include <stdio.h>\n#include <stddef.h>\n#include \"rt_abi.h\"\nint main(void) {\n"
-                    "    printf(\"%zu %zu\\n\", sizeof(rt_clearance_query_params), sizeof(rt_clearance_query_stats));\n"
-                    + "".join(f"    printf(\"%zu\\n\", offsetof(rt_clearance_query_params, {n}));\n" for n in pf)
-                    + "".join(f"    printf(\"%zu\\n\", offsetof(rt_clearance_query_stats, {n}));\n" for n in sf)
-                    + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[:2] == [C.sizeof(R.ClearanceQueryParams), C.sizeof(R.ClearanceQueryStats)]
-    assert out[2:2 + len(pf)] == [getattr(R.ClearanceQueryParams, n).offset for n in pf]
-    assert out[2 + len(pf):] == [getattr(R.ClearanceQueryStats, n).offset for n in sf]
-    assert pf == ["tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks", "count_traversal"]
-    assert sorted(sf) == sorted(["ms", "nodes_visited", "tris_tested", "invalid_triangles", "stack_overflow", "queries"])
+    AB.struct_layout(KIND, tmp_path)
 
 
 def test_default_params_are_zeros():
-    lib = R.load()
-    p = R.ClearanceQueryParams(7, 7, 7, 7, 7)
-    assert lib.rt_default_clearance_query_params(C.byref(p)) == 0
-    assert bytes(p) == bytes(C.sizeof(R.ClearanceQueryParams))
+    AB.default_params(KIND)
 
 
 def test_the_wrapper_checks_its_tensors_before_the_library():
@@ -84,22 +61,7 @@ def test_the_wrapper_compares_lengths_and_shapes():
     """The refusals past the device check (a renderer that takes CPU tensors for its device's): query_points' refusals."""
     torch = pytest.importorskip("torch")
 
-    class OnCpu(R.Renderer):
-        def _device_rows(self, t, name, width):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(name)
-            if t.dim() == 2 and t.shape[1] == width:
-                return t.shape[0]
-            if t.dim() == 1 and t.numel() % width == 0:
-                return t.numel() // width
-            raise ValueError(name)
-
-        def _device_i32(self, t, name, n):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n:
-                raise ValueError(name)
-
-    r = OnCpu.__new__(OnCpu)
-    r._lib, r._ctx, r.device = None, None, 0
+    r = AB.cpu_renderer()
     q = torch.zeros(4, 3, 3)
     d, t, a, c = torch.zeros(4), torch.zeros(4, dtype=torch.int32), torch.zeros(4, 3), torch.zeros(4, 3)
     with pytest.raises(ValueError, match="tris"):

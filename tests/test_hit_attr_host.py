@@ -11,6 +11,7 @@ import functools
 import numpy as np
 import pytest
 
+import abi_boundary as AB
 import attr_exact as AX
 import point_exact as PX
 import ray_exact as RX
@@ -20,25 +21,22 @@ from test_ray_contract import family_data as oracle_data  # the oracle's brute-f
 
 f32 = np.float32
 FUNCTIONS = ("rt_query_rays_attr_device", "rt_query_points_attr_device")
+V = C.c_void_p(16)
+KIND = AB.Kind(functions=FUNCTIONS,  # no structs of its own: the ray and point queries' parameters
+               null_calls=(("rt_query_rays_attr_device", (None, None, None, 0, None, None, None, None, None)),
+                           ("rt_query_rays_attr_device", (V, V, None, 1, C.byref(R.RayQueryParams()), V, V, V, V)),
+                           ("rt_query_points_attr_device", (None, None, 0, None, None, None, None, None, None)),
+                           ("rt_query_points_attr_device", (V, None, 1, C.byref(R.PointQueryParams()), V, V, V, V, V))))
 
 
 # ---- the boundary --------------------------------------------------------------------------------------------------------------
 def test_the_functions_are_exported_and_bound():
-    lib = R.load()
-    for name in FUNCTIONS:
-        assert hasattr(lib, name), name
-        assert name in _lib.PROTOTYPES, name
+    AB.exports(KIND)
     assert len(_lib.PROTOTYPES["rt_query_rays_attr_device"][1]) == 10 and len(_lib.PROTOTYPES["rt_query_points_attr_device"][1]) == 10
-    assert lib.rt_abi_version() == 4  # additions only
 
 
 def test_a_null_context_is_refused():
-    lib = R.load()
-    p16 = C.c_void_p(16)
-    assert lib.rt_query_rays_attr_device(None, None, None, None, 0, None, None, None, None, None) == -1  # RT_ERR_INVALID: nothing touched
-    assert lib.rt_query_rays_attr_device(None, p16, p16, None, 1, C.byref(R.RayQueryParams()), p16, p16, p16, p16) == -1
-    assert lib.rt_query_points_attr_device(None, None, None, 0, None, None, None, None, None, None) == -1
-    assert lib.rt_query_points_attr_device(None, p16, None, 1, C.byref(R.PointQueryParams()), p16, p16, p16, p16, p16) == -1
+    AB.null_context(KIND)
 
 
 def test_the_wrapper_refuses_before_the_library_is_called():
@@ -64,22 +62,7 @@ def test_the_wrapper_checks_the_arity_and_shapes_of_out():
     """The refusals past the device check (a renderer that takes CPU tensors for its device's, as in test_point_query_host.py)."""
     torch = pytest.importorskip("torch")
 
-    class OnCpu(R.Renderer):
-        def _device_rows(self, t, name, width):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(name)
-            if t.dim() == 2 and t.shape[1] == width:
-                return t.shape[0]
-            if t.dim() == 1 and t.numel() % width == 0:
-                return t.numel() // width
-            raise ValueError(name)
-
-        def _device_i32(self, t, name, n):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n:
-                raise ValueError(name)
-
-    r = OnCpu.__new__(OnCpu)
-    r._lib, r._ctx, r.device = None, None, 0
+    r = AB.cpu_renderer()
     o = torch.zeros(4, 3)
     t, tri, c, uv, nrm = torch.zeros(4), torch.zeros(4, dtype=torch.int32), torch.zeros(4, 3), torch.zeros(4, 2), torch.zeros(4, 3)
     for bad in ((t, tri), (t, tri, uv), (t, tri, uv, nrm, nrm), t):

@@ -8,72 +8,47 @@ closest-point reference's answer; ties come lower index first and a cut inside a
 contract holds and rejects a withheld k-th neighbour; the walk prunes.  The kernel itself is tested on the GPU
 (tests/test_gpu_knn_query.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_boundary as AB
 import knn_exact as KX
 import neighbor_exact as NX
 import point_exact as PX
 import raytracing_engine_amd as R
 from raytracing_engine_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = ("rt_default_knn_query_params", "rt_query_knn_device", "rt_get_knn_query_stats")
+V = C.c_void_p(16)
+KIND = AB.Kind(functions=FUNCTIONS, methods=("query_knn", "knn_query_stats"), params="KnnQueryParams", stats="KnnQueryStats",
+               params_c="rt_knn_query_params", stats_c="rt_knn_query_stats", params_fields=["tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks", "count_traversal"],
+               stats_fields=["points", "invalid_points", "neighbors", "nodes_visited", "tris_tested", "stack_overflow", "launches", "ms"],
+               constants={"RT_KNN_MAX_K": _lib.KNN_MAX_K}, default="rt_default_knn_query_params",
+               null_calls=(("rt_query_knn_device", (None, None, 0, 1, None, None, None, None)),
+                           ("rt_query_knn_device", (V, V, 1, 8, C.byref(R.KnnQueryParams()), V, V, V)),
+                           ("rt_get_knn_query_stats", (C.byref(R.KnnQueryStats()),)), ("rt_default_knn_query_params", ())))
 f32 = np.float32
 INF = NX.INF
 
 
 # ---- the boundary --------------------------------------------------------------------------------------------------------------
 def test_the_functions_are_exported_and_bound():
-    lib = R.load()
-    for name in FUNCTIONS:
-        assert hasattr(lib, name), name
-        assert name in _lib.PROTOTYPES, name
-    assert lib.rt_abi_version() == 4  # additions only
-    for method in ("query_knn", "knn_query_stats"):
-        assert callable(getattr(R.Renderer, method))
-    assert R.KnnQueryParams is _lib.KnnQueryParams and R.KnnQueryStats is _lib.KnnQueryStats
+    AB.exports(KIND)
     assert R.Renderer.KNN_MAX_K == _lib.KNN_MAX_K == KX.BIG_K == 1024
 
 
 def test_a_null_context_is_refused():
-    lib = R.load()
-    p = R.KnnQueryParams()
-    v = C.c_void_p(16)
-    assert lib.rt_query_knn_device(None, None, None, 0, 1, None, None, None, None) == -1  # RT_ERR_INVALID: nothing touched
-    assert lib.rt_query_knn_device(None, v, v, 1, 8, C.byref(p), v, v, v) == -1
-    assert lib.rt_get_knn_query_stats(None, C.byref(R.KnnQueryStats())) == -1
-    assert lib.rt_default_knn_query_params(None) == -1
+    AB.null_context(KIND)
 
 
 def test_struct_layouts_match_the_header(tmp_path):
     """sizeof/offsetof as gcc computes them from include/rt_abi.h vs the ctypes mirrors."""
-    pf = [n for n, _ in R.KnnQueryParams._fields_]
-    sf = [n for n, _ in R.KnnQueryStats._fields_]
-    prog = tmp_path / "layout.c"
-    prog.write_text("#include <stdio.h>\n#include <stddef.h>\n#include \"rt_abi.h\"\nint main(void) {\n"
-                    "    printf(\"%zu %zu %d %u\\n\", sizeof(rt_knn_query_params), sizeof(rt_knn_query_stats), RT_ABI_VERSION, RT_KNN_MAX_K);\n"
-                    + "".join(f"    printf(\"%zu\\n\", offsetof(rt_knn_query_params, {n}));\n" for n in pf)
-                    + "".join(f"    printf(\"%zu\\n\", offsetof(rt_knn_query_stats, {n}));\n" for n in sf)
-                    + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[:4] == [C.sizeof(R.KnnQueryParams), C.sizeof(R.KnnQueryStats), 4, _lib.KNN_MAX_K]
-    assert out[4:4 + len(pf)] == [getattr(R.KnnQueryParams, n).offset for n in pf]
-    assert out[4 + len(pf):] == [getattr(R.KnnQueryStats, n).offset for n in sf]
-    assert pf == ["tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks", "count_traversal"]
-    assert sf == ["points", "invalid_points", "neighbors", "nodes_visited", "tris_tested", "stack_overflow", "launches", "ms"]
+    AB.struct_layout(KIND, tmp_path)
 
 
 def test_default_params_are_zeros():
-    lib = R.load()
-    p = R.KnnQueryParams(7, 7, 7, 7, 7)
-    assert lib.rt_default_knn_query_params(C.byref(p)) == 0
-    assert bytes(p) == bytes(C.sizeof(R.KnnQueryParams))
+    AB.default_params(KIND)
 
 
 def test_the_wrapper_checks_its_tensors_before_the_library():
@@ -93,26 +68,7 @@ def test_the_wrapper_refuses_k_shapes_and_types():
     """The refusals past the device check (a renderer that takes CPU tensors for its device's)."""
     torch = pytest.importorskip("torch")
 
-    class OnCpu(R.Renderer):
-        def _device_rows(self, t, name, width):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(name)
-            if t.dim() == 2 and t.shape[1] == width:
-                return t.shape[0]
-            if t.dim() == 1 and t.numel() % width == 0:
-                return t.numel() // width
-            raise ValueError(name)
-
-        def _device_i32(self, t, name, n):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n:
-                raise ValueError(name)
-
-        def _device_i32_rows(self, t, name, n, cols):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (n, cols):
-                raise ValueError(name)
-
-    r = OnCpu.__new__(OnCpu)
-    r._lib, r._ctx, r.device = None, None, 0
+    r = AB.cpu_renderer()
     p = torch.zeros(4, 3)
     for bad_k in (0, 1025, -1, 2 ** 32, 1.0, "8", None, True):
         with pytest.raises(ValueError, match="k must"):

@@ -7,75 +7,47 @@ tests/neighbor_exact.py (tree independence: no GPU needed); entry 0 is the close
 unlimited one cut strictly below the limit; ties come lower index first; the float64 contract holds and rejects a withheld neighbour.
 The kernel itself is tested on the GPU (tests/test_gpu_neighbor_query.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_boundary as AB
 import neighbor_exact as NX
 import point_exact as PX
 import raytracing_engine_amd as R
-from raytracing_engine_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = ("rt_default_neighbor_query_params", "rt_count_neighbors_device", "rt_fill_neighbors_device", "rt_list_neighbors_device", "rt_get_neighbor_query_stats")
+V = C.c_void_p(16)
+P = C.byref(R.NeighborQueryParams())
+KIND = AB.Kind(functions=FUNCTIONS, methods=("count_neighbors", "list_neighbors", "neighbor_query_stats"), params="NeighborQueryParams", stats="NeighborQueryStats",
+               params_c="rt_neighbor_query_params", stats_c="rt_neighbor_query_stats", params_fields=["tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks", "count_traversal"],
+               stats_fields=["points", "invalid_points", "neighbors", "neighbors_written", "incomplete_points", "slice_overflow", "nodes_visited", "tris_tested",
+                             "stack_overflow", "launches", "ms"],
+               default="rt_default_neighbor_query_params",
+               null_calls=(("rt_count_neighbors_device", (None, None, 1.0, 0, None, None, None)), ("rt_count_neighbors_device", (V, V, 1.0, 1, P, V, V)),
+                           ("rt_fill_neighbors_device", (None, None, 1.0, 0, None, None, 0, None, None)), ("rt_fill_neighbors_device", (V, V, 1.0, 1, P, V, 1, V, V)),
+                           ("rt_list_neighbors_device", (None, None, 1.0, 0, None, None, None, 0, None, None)), ("rt_list_neighbors_device", (V, V, 1.0, 1, P, V, V, 1, V, V)),
+                           ("rt_get_neighbor_query_stats", (C.byref(R.NeighborQueryStats()),)), ("rt_default_neighbor_query_params", ())))
 f32 = np.float32
 INF = NX.INF
 
 
 # ---- the boundary --------------------------------------------------------------------------------------------------------------
 def test_the_functions_are_exported_and_bound():
-    lib = R.load()
-    for name in FUNCTIONS:
-        assert hasattr(lib, name), name
-        assert name in _lib.PROTOTYPES, name
-    assert lib.rt_abi_version() == 4  # additions only
-    for method in ("count_neighbors", "list_neighbors", "neighbor_query_stats"):
-        assert callable(getattr(R.Renderer, method))
-    assert R.NeighborQueryParams is _lib.NeighborQueryParams and R.NeighborQueryStats is _lib.NeighborQueryStats
+    AB.exports(KIND)
 
 
 def test_a_null_context_is_refused():
-    lib = R.load()
-    p = R.NeighborQueryParams()
-    v = C.c_void_p(16)
-    assert lib.rt_count_neighbors_device(None, None, None, 1.0, 0, None, None, None) == -1  # RT_ERR_INVALID: nothing touched
-    assert lib.rt_count_neighbors_device(None, v, v, 1.0, 1, C.byref(p), v, v) == -1
-    assert lib.rt_fill_neighbors_device(None, None, None, 1.0, 0, None, None, 0, None, None) == -1
-    assert lib.rt_fill_neighbors_device(None, v, v, 1.0, 1, C.byref(p), v, 1, v, v) == -1
-    assert lib.rt_list_neighbors_device(None, None, None, 1.0, 0, None, None, None, 0, None, None) == -1
-    assert lib.rt_list_neighbors_device(None, v, v, 1.0, 1, C.byref(p), v, v, 1, v, v) == -1
-    assert lib.rt_get_neighbor_query_stats(None, C.byref(R.NeighborQueryStats())) == -1
-    assert lib.rt_default_neighbor_query_params(None) == -1
+    AB.null_context(KIND)
 
 
 def test_struct_layouts_match_the_header(tmp_path):
     """sizeof/offsetof as gcc computes them from include/rt_abi.h vs the ctypes mirrors."""
-    pf = [n for n, _ in R.NeighborQueryParams._fields_]
-    sf = [n for n, _ in R.NeighborQueryStats._fields_]
-    prog = tmp_path / "layout.c"
-    prog.write_text("#include <stdio.h>\n#include <stddef.h>\n#include \"rt_abi.h\"\nint main(void) {\n"
-                    "    printf(\"%zu %zu %d\\n\", sizeof(rt_neighbor_query_params), sizeof(rt_neighbor_query_stats), RT_ABI_VERSION);\n"
-                    + "".join(f"    printf(\"%zu\\n\", offsetof(rt_neighbor_query_params, {n}));\n" for n in pf)
-                    + "".join(f"    printf(\"%zu\\n\", offsetof(rt_neighbor_query_stats, {n}));\n" for n in sf)
-                    + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[:3] == [C.sizeof(R.NeighborQueryParams), C.sizeof(R.NeighborQueryStats), 4]
-    assert out[3:3 + len(pf)] == [getattr(R.NeighborQueryParams, n).offset for n in pf]
-    assert out[3 + len(pf):] == [getattr(R.NeighborQueryStats, n).offset for n in sf]
-    assert pf == ["tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks", "count_traversal"]
-    assert sf == ["points", "invalid_points", "neighbors", "neighbors_written", "incomplete_points", "slice_overflow", "nodes_visited", "tris_tested",
-                  "stack_overflow", "launches", "ms"]
+    AB.struct_layout(KIND, tmp_path)
 
 
 def test_default_params_are_zeros():
-    lib = R.load()
-    p = R.NeighborQueryParams(7, 7, 7, 7, 7)
-    assert lib.rt_default_neighbor_query_params(C.byref(p)) == 0
-    assert bytes(p) == bytes(C.sizeof(R.NeighborQueryParams))
+    AB.default_params(KIND)
 
 
 def test_the_wrappers_check_their_tensors_before_the_library():
@@ -96,26 +68,7 @@ def test_the_wrappers_compare_lengths_and_shapes():
     """The refusals past the device check (a renderer that takes CPU tensors for its device's)."""
     torch = pytest.importorskip("torch")
 
-    class OnCpu(R.Renderer):
-        def _device_rows(self, t, name, width):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(name)
-            if t.dim() == 2 and t.shape[1] == width:
-                return t.shape[0]
-            if t.dim() == 1 and t.numel() % width == 0:
-                return t.numel() // width
-            raise ValueError(name)
-
-        def _device_i32(self, t, name, n):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n:
-                raise ValueError(name)
-
-        def _device_i64(self, t, name, n):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != n:
-                raise ValueError(name)
-
-    r = OnCpu.__new__(OnCpu)
-    r._lib, r._ctx, r.device = None, None, 0
+    r = AB.cpu_renderer()
     p = torch.zeros(4, 3)
     cnt, off = torch.zeros(4, dtype=torch.int32), torch.zeros(5, dtype=torch.int64)
     dist, tri = torch.zeros(8), torch.zeros(8, dtype=torch.int32)

@@ -3,56 +3,36 @@ wrapper's argument checks, and the native reference of tests/section_exact.py (c
 to answers computed by hand, to the list reference of tests/overlap_exact.py, to its own selection rule, to the float64 interval method
 and to covariance under scale.  The kernel is compared with this reference bit for bit in tests/test_gpu_overlap_segments.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_boundary as AB
 import overlap_exact as OX
 import raytracing_engine_amd as R
 import section_exact as SX
-from raytracing_engine_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 STATS = ["entries", "segments", "touches", "skipped_incomplete", "bad_entries", "launches", "ms"]
+V = C.c_void_p(16)
+KIND = AB.Kind(functions=("rt_overlap_segments_device", "rt_get_overlap_segment_stats"), methods=("overlap_segments", "overlap_segment_stats"),
+               stats="OverlapSegmentStats", stats_c="rt_overlap_segment_stats", stats_fields=STATS,  # no parameter struct
+               null_calls=(("rt_overlap_segments_device", (None, 0, None, 0, None, None, None)), ("rt_overlap_segments_device", (V, 1, V, 1, V, V, V)),
+                           ("rt_get_overlap_segment_stats", (C.byref(R.OverlapSegmentStats()),))))
 
 
 # ---- the boundary --------------------------------------------------------------------------------------------------------------
 def test_the_functions_are_exported_and_bound():
-    lib = R.load()
-    for name in ("rt_overlap_segments_device", "rt_get_overlap_segment_stats"):
-        assert hasattr(lib, name), name
-        assert name in _lib.PROTOTYPES, name
-    assert lib.rt_abi_version() == 4  # additions only
-    for method in ("overlap_segments", "overlap_segment_stats"):
-        assert callable(getattr(R.Renderer, method))
-    assert R.OverlapSegmentStats is _lib.OverlapSegmentStats
+    AB.exports(KIND)
 
 
 def test_a_null_context_is_refused():
-    lib = R.load()
-    v = C.c_void_p(16)
-    assert lib.rt_overlap_segments_device(None, None, 0, None, 0, None, None, None) == -1  # RT_ERR_INVALID: nothing touched
-    assert lib.rt_overlap_segments_device(None, v, 1, v, 1, v, v, v) == -1
-    assert lib.rt_get_overlap_segment_stats(None, C.byref(R.OverlapSegmentStats())) == -1
+    AB.null_context(KIND)
 
 
 def test_the_stats_layout_matches_the_header(tmp_path):
     """sizeof/offsetof as gcc computes them from include/rt_abi.h vs the ctypes mirror."""
-    sf = [n for n, _ in R.OverlapSegmentStats._fields_]
-    prog = tmp_path / "layout.c"
-    prog.write_text("#include <stdio.h>\n#include <stddef.h>\n#include \"rt_abi.h\"\nint main(void) {\n"
-                    "    printf(\"%zu %d\\n\", sizeof(rt_overlap_segment_stats), RT_ABI_VERSION);\n"
-                    + "".join(f"    printf(\"%zu\\n\", offsetof(rt_overlap_segment_stats, {n}));\n" for n in sf)
-                    + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[:2] == [C.sizeof(R.OverlapSegmentStats), 4]
-    assert out[2:] == [getattr(R.OverlapSegmentStats, n).offset for n in sf]
-    assert sf == STATS
+    AB.struct_layout(KIND, tmp_path)
 
 
 def test_the_wrapper_checks_its_tensors_before_the_library():
@@ -70,22 +50,7 @@ def test_the_wrapper_compares_lengths_and_shapes():
     """The refusals past the device check (a renderer that takes CPU tensors for its device's)."""
     torch = pytest.importorskip("torch")
 
-    class OnCpu(R.Renderer):
-        def _device_rows(self, t, name, width):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(name)
-            if t.dim() == 2 and t.shape[1] == width:
-                return t.shape[0]
-            if t.dim() == 1 and t.numel() % width == 0:
-                return t.numel() // width
-            raise ValueError(name)
-
-        def _device_ints(self, t, name, n, kind):
-            if not isinstance(t, torch.Tensor) or t.dtype != getattr(torch, kind) or t.dim() != 1 or t.numel() != n:
-                raise ValueError(name)
-
-    r = OnCpu.__new__(OnCpu)
-    r._lib, r._ctx, r.device = None, None, 0
+    r = AB.cpu_renderer()
     q, off, tri = torch.zeros(4, 9), torch.zeros(5, dtype=torch.int64), torch.zeros(8, dtype=torch.int32)
     with pytest.raises(ValueError, match="tris"):
         r.overlap_segments(torch.zeros(4, 8), off, tri)

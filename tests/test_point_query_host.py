@@ -6,65 +6,43 @@ tests/point_exact.py with the committed Kp; and that contract rejects wrong answ
 (tests/test_gpu_point_query.py)."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_boundary as AB
 import point_exact as PX
 import raytracing_engine_amd as R
 from raytracing_engine_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = ("rt_default_point_query_params", "rt_query_points_device", "rt_get_point_query_stats")
+V = C.c_void_p(16)
+KIND = AB.Kind(functions=FUNCTIONS, params="PointQueryParams", stats="PointQueryStats", params_c="rt_point_query_params", stats_c="rt_point_query_stats",
+               params_fields=["tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks", "count_traversal"], stats_fields=["points", "invalid_points", "nodes_visited", "tris_tested", "stack_overflow", "launches", "ms"],
+               constants={"RT_POINT_MISS": _lib.POINT_MISS, "RT_POINT_INVALID": _lib.POINT_INVALID}, default="rt_default_point_query_params",
+               null_calls=(("rt_query_points_device", (None, None, 0, None, None, None, None)),
+                           ("rt_query_points_device", (V, None, 1, C.byref(R.PointQueryParams()), V, V, V)),
+                           ("rt_get_point_query_stats", (C.byref(R.PointQueryStats()),)), ("rt_default_point_query_params", ())))
 N = 4000
 
 
 # ---- the boundary --------------------------------------------------------------------------------------------------------------
 def test_the_functions_are_exported_and_bound():
-    lib = R.load()
-    for name in FUNCTIONS:
-        assert hasattr(lib, name), name
-        assert name in _lib.PROTOTYPES, name
-    assert lib.rt_abi_version() == 4  # additions only
+    AB.exports(KIND)
 
 
 def test_a_null_context_is_refused():
-    lib = R.load()
-    p = R.PointQueryParams()
-    assert lib.rt_query_points_device(None, None, None, 0, None, None, None, None) == -1  # RT_ERR_INVALID: nothing touched
-    assert lib.rt_query_points_device(None, C.c_void_p(16), None, 1, C.byref(p), C.c_void_p(16), C.c_void_p(16), C.c_void_p(16)) == -1
-    assert lib.rt_get_point_query_stats(None, C.byref(R.PointQueryStats())) == -1
-    assert lib.rt_default_point_query_params(None) == -1
+    AB.null_context(KIND)
 
 
 def test_struct_layouts_match_the_header(tmp_path):
     """sizeof/offsetof as gcc computes them from include/rt_abi.h vs the ctypes mirrors."""
-    pf = [n for n, _ in R.PointQueryParams._fields_]
-    sf = [n for n, _ in R.PointQueryStats._fields_]
-    prog = tmp_path / "layout.c"
-    prog.write_text("#include <stdio.h>\n#include <stddef.h>\n#include \"rt_abi.h\"\nint main(void) {\n"
-                    "    printf(\"%zu %zu %d %d\\n\", sizeof(rt_point_query_params), sizeof(rt_point_query_stats), RT_POINT_MISS, RT_POINT_INVALID);\n"
-                    + "".join(f"    printf(\"%zu\\n\", offsetof(rt_point_query_params, {n}));\n" for n in pf)
-                    + "".join(f"    printf(\"%zu\\n\", offsetof(rt_point_query_stats, {n}));\n" for n in sf)
-                    + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[:4] == [C.sizeof(R.PointQueryParams), C.sizeof(R.PointQueryStats), _lib.POINT_MISS, _lib.POINT_INVALID]
-    assert out[4:4 + len(pf)] == [getattr(R.PointQueryParams, n).offset for n in pf]
-    assert out[4 + len(pf):] == [getattr(R.PointQueryStats, n).offset for n in sf]
-    assert pf == ["tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks", "count_traversal"]
-    assert sf == ["points", "invalid_points", "nodes_visited", "tris_tested", "stack_overflow", "launches", "ms"]
+    AB.struct_layout(KIND, tmp_path)
     assert (R.Renderer.POINT_MISS, R.Renderer.POINT_INVALID) == (-1, -2)
 
 
 def test_default_params_are_zeros():
-    lib = R.load()
-    p = R.PointQueryParams(7, 7, 7, 7, 7)
-    assert lib.rt_default_point_query_params(C.byref(p)) == 0
-    assert bytes(p) == bytes(C.sizeof(R.PointQueryParams))
+    AB.default_params(KIND)
 
 
 def test_the_wrapper_checks_its_tensors_before_the_library():
@@ -84,22 +62,7 @@ def test_the_wrapper_compares_lengths_and_shapes():
     """The refusals past the device check (a renderer that takes CPU tensors for its device's)."""
     torch = pytest.importorskip("torch")
 
-    class OnCpu(R.Renderer):
-        def _device_rows(self, t, name, width):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(name)
-            if t.dim() == 2 and t.shape[1] == width:
-                return t.shape[0]
-            if t.dim() == 1 and t.numel() % width == 0:
-                return t.numel() // width
-            raise ValueError(name)
-
-        def _device_i32(self, t, name, n):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n:
-                raise ValueError(name)
-
-    r = OnCpu.__new__(OnCpu)
-    r._lib, r._ctx, r.device = None, None, 0
+    r = AB.cpu_renderer()
     p = torch.zeros(4, 3)
     d, t, c = torch.zeros(4), torch.zeros(4, dtype=torch.int32), torch.zeros(4, 3)
     with pytest.raises(ValueError, match="points"):

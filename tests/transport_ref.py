@@ -20,12 +20,14 @@ variance where there are lights and the same where there are none, and the devia
 """
 import math
 import os
-import subprocess
-import tempfile
+import sys
 
 import numpy as np
 
 from raytracing_engine_amd import scenes
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import native_ref as NR  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -41,26 +43,16 @@ FRAME_REL_SE = 5e-4
 CELL_REL_SE = 2.5e-3
 BRIGHT = 0.1  # a cell is bright if its mean exceeds this fraction of the frame mean; dimmer ones are held to the scale BRIGHT * frame mean
 
-_BUILT = {}
-
 
 def build_reference(sanitized=False, where=None):
     """Compiles tests/native/pt_transport_ref.cpp (once per process and flavour); returns the program's path."""
-    if sanitized not in _BUILT:
-        where = where or tempfile.mkdtemp(prefix="pt_transport_ref_")
-        exe = os.path.join(where, "pt_transport_ref_asan" if sanitized else "pt_transport_ref")
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra"] + flags +
-                       [os.path.join(ROOT, "tests", "native", "pt_transport_ref.cpp"), "-o", exe], check=True)
-        _BUILT[sanitized] = exe
-    return _BUILT[sanitized]
+    return NR.build("pt_transport_ref", (), sanitized, where, flags=("-pthread", "-Wall", "-Wextra"))
 
 
 def reference(mesh, kind=None, ior=None, *, bounces, seed, batches, spp, pos=(0, 0, 0), rot=(0, 0, 0, 1), ratio=None, sky=(0, 0, 0),
               ray_eps=1e-3, width=WIDTH, height=HEIGHT, cells=(CELLS, CELLS), only_depth=-1, threads=16, sanitized=False):
     """The native reference on mesh = (verts, albedo, emission): `batches` x `spp` paths per pixel.  dict(paths, mean, se, sd
     (cells_y, cells_x, 3), frame_mean, frame_se, frame_sd (3,), by_depth (bounces + 2, 3): the frame mean by gathering vertex)."""
-    exe = build_reference(sanitized)
     v = np.asarray(mesh[0], np.float64).reshape(-1, 9)
     n = len(v)
     kind = np.zeros(n) if kind is None else np.asarray(kind, np.float64)
@@ -70,13 +62,7 @@ def reference(mesh, kind=None, ior=None, *, bounces, seed, batches, spp, pos=(0,
         ratio = (1.0, height / width)
     params = np.array([width, height, cells[1], cells[0], bounces, seed, batches, spp, *ratio, *rot, *pos, *sky, ray_eps, only_depth, 0, 0], np.float64)
     assert rows.shape == (n, 17) and params.shape == (24,)
-    with tempfile.TemporaryDirectory(prefix="pt_transport_") as tmp:
-        rows.tofile(os.path.join(tmp, "scene"))
-        params.tofile(os.path.join(tmp, "params"))
-        run = subprocess.run([exe, os.path.join(tmp, "scene"), os.path.join(tmp, "params"), os.path.join(tmp, "out"), str(threads)], capture_output=True, text=True)
-        if run.returncode != 0 or not run.stdout.startswith("OK"):
-            raise RuntimeError(f"pt_transport_ref failed ({run.returncode}): {run.stdout}{run.stderr}")
-        raw = np.fromfile(os.path.join(tmp, "out"), np.float64)
+    raw = np.frombuffer(NR.run(build_reference(sanitized), dict(scene=rows, params=params, out=NR.OUT, threads=str(threads))), np.float64).copy()
     cy, cx, depths = int(raw[1]), int(raw[2]), int(raw[3])
     assert (cy, cx) == tuple(cells) and depths == bounces + 2 and len(raw) == 4 + 9 * cy * cx + 9 + 3 * depths
     assert raw[0] == width * height * batches * spp
