@@ -1,8 +1,8 @@
 // bvh_node.h — the compressed 8-wide BVH node and the leaf-order triangle record of path B, defined once for everything that
 // produces or rewrites them: the host builder (bvh_build.cpp), the two-level flatten (bvh_two_level.cpp), the mesh upload
 // (rt_abi_mesh.hip) and the GPU build and refit (bvh_build_gpu.hip).  Compiled by plain g++ and by hipcc: standard library
-// only, and every function is host + device under hipcc.  The traversal kernels (pt_traverse.h, pt_packet.hip, pt_point_query.hip) decode nodes in hand-scheduled
-// code of their own; the tests' decoders (tests/native/bvh_check.cpp, bvh8_walk.cpp) are independent on purpose.
+// only, and every function is host + device under hipcc.  The traversal kernels decode nodes in hand-scheduled code of their own (pt_traverse.h: node_step for the
+// ray walks, NodeRec / fetch_node for the other query walks; pt_packet.hip; point_node_step of pt_point_query.hip); the tests' decoders (tests/native/bvh_check.cpp, bvh8_walk.cpp) are independent on purpose.
 //
 // Node = 80 bytes = 5 x 16-byte fetches for 8 children (20 little-endian words):
 //   w0..w2  p.xyz (f32)        origin of the node's quantisation frame (= box minimum)

@@ -1,7 +1,7 @@
 // pt_queue.h — path B, device side: a device-resident queue of PT_HEADS interleaved streams (rt_internal.h) as a persistent wave
 // sees it: where a stream's entries lie, which stream a wave starts on, the cursor that reserves entries with one atomic per refill
-// and moves on when a stream is dry.  Used by the per-lane trace kernels and the ray queries (pt_trace.hip) and by the point, side, all-hits and
-// neighbour queries (pt_point_query.hip, pt_side_query.hip, pt_hit_query.hip, pt_neighbor_query.hip); the queries' queue is implicit.  The atomics here are aggregated by hand: see the Makefile for the flag that keeps them as written.
+// and moves on when a stream is dry.  Used by the per-lane trace kernels and the ray queries (pt_trace.hip), by the shared query loop
+// (pt_query_loop.h: six of the eight query kinds), the closest-point and the all-hits queries (pt_point_query.hip, pt_hit_query.hip); pt_overlap_segments.hip uses add_wave_total.  The queries' queue is implicit.  The atomics here are aggregated by hand: see the Makefile for the flag that keeps them as written.
 #pragma once
 #include "pt_traverse.h"
 

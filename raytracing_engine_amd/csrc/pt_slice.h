@@ -1,9 +1,9 @@
-// pt_slice.h — path B, device side: what the kernels of the listing queries share beside their loop - the sorted slice that a lane
-// keeps in global memory (insert_hit), where that slice lies (open_slice), the count step's answer for an item that is not walked
-// (write_count) and the wave totals (add_listing_totals).  Used by the all-hits ray queries (pt_hit_query.hip: keys are t) and by the
-// neighbour queries (pt_neighbor_query.hip: keys are d2); the overlap queries (pt_overlap_query.hip) keep (index, mask) pairs with
-// insert_pair and share the rest.  Every function here left the kernels' object code as it was; the sink's
-// count and its written / incomplete / beyond accounting did not and stay in the kernels (profiles/refactor_listing.txt).
+// pt_slice.h — path B, device side: what the kernels of the listing queries share beside their loop and their walk - the sorted
+// slice that a lane keeps in global memory (insert_hit), where that slice lies (open_slice), the lane's slice record with the
+// sink's accounting (ListSlice), the count step's answer (write_count) and the wave totals (add_listing_totals).  Used by the
+// all-hits ray queries (pt_hit_query.hip: keys are t; its kernel keeps the record's fields and the sink's arithmetic as its own
+// text), by the neighbour queries (pt_neighbor_query.hip: keys are d2) and by the overlap queries (pt_overlap_query.hip: (index,
+// mask) pairs with insert_pair); the k-nearest queries (pt_knn_query.hip) use insert_hit on their rows.
 #pragma once
 #include "pt_queue.h"
 
@@ -46,12 +46,38 @@ __device__ __forceinline__ Slice open_slice(const long long* offsets, uint32_t i
     return Slice{lo, len, (lo >= 0ll && hi <= capacity) ? len : 0u};
 }
 
-// The count step: the answer of an item that is not walked - the caller's 32-bit column and the scan's 64-bit one (max(count, 0));
+// The count step: the answer of an item whose count is known - the caller's 32-bit column and the scan's 64-bit one (max(count, 0));
 // either may be absent
 __device__ __forceinline__ void write_count(int* count_out, unsigned long long* count64, uint32_t i, int count, unsigned long long scanned) {
     if (count_out) count_out[i] = count;
     if (count64) count64[i] = scanned;
 }
+
+// What a listing lane holds of its list beside the walk: the slice of the item under way and the lane's totals.
+struct ListSlice {
+    long long lo = 0;    // FILL: where the slice starts
+    uint32_t room = 0;   // FILL: entries it may hold (0: it does not fit, nothing is written)
+    uint32_t len = 0;    // FILL: its own length
+    uint32_t found = 0;  // the item's entries so far
+    uint32_t invalid = 0, total = 0, written = 0, incomplete = 0, beyond = 0;  // what this lane has met
+    // on admission, FILL: open_slice's answer
+    __device__ __forceinline__ void open(const long long* offsets, uint32_t i, long long capacity) {
+        const Slice s = open_slice(offsets, i, capacity);
+        lo = s.lo, len = s.len, room = s.room;
+    }
+    // The sink: the item's entries into the totals; returns how many of them the slice holds.
+    template <bool FILL>
+    __device__ __forceinline__ uint32_t close() {
+        const uint32_t kept = found < room ? found : room;
+        total += found;
+        if (FILL) {
+            written += kept;
+            incomplete += (found != 0u && room != len) ? 1u : 0u;
+            beyond += found > len ? found - len : 0u;
+        }
+        return kept;
+    }
+};
 
 // A wave's totals into the step's LQ_STEP_WORDS counters, one atomic per word
 template <bool COUNT, bool FILL>
@@ -69,6 +95,10 @@ __device__ __forceinline__ void add_listing_totals(unsigned long long* stats, ui
         add_wave_total(&stats[LQ_STAT_TRIS], tc.tris, lane);
     }
     if (tc.overflow) atomicOr((unsigned int*)&stats[LQ_STAT_OVERFLOW], 1u);
+}
+template <bool COUNT, bool FILL>
+__device__ __forceinline__ void add_listing_totals(unsigned long long* stats, uint32_t lane, const ListSlice& sl, const TravCounters& tc) {
+    add_listing_totals<COUNT, FILL>(stats, lane, sl.invalid, sl.total, sl.written, sl.incomplete, sl.beyond, tc);
 }
 
 // The overlap queries' slice (pt_overlap_query.hip): pairs (id, word) in ascending id order, ids distinct.  insert_hit's protocol

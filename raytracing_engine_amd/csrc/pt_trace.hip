@@ -8,7 +8,7 @@
 // are propagated into it before it is inlined).  In a unit of their own two of them compile to other code (profiles/split_path_b.txt).
 #include "hit_attr.h"
 #include "pt_launch.h"
-#include "pt_queue.h"
+#include "pt_query_loop.h"
 
 namespace rt {
 using namespace rtk;
@@ -668,7 +668,7 @@ __global__ __launch_bounds__(256) void pt_trace_rays(const PtScene sc, const flo
 }
 
 // ---- ray queries on device arrays (rt_query_rays_device) -----------------------
-// The persistent refilling loop of trace_queue_inline with another source and sink: the queue is implicit (entry i is ray i of the
+// A lane of the query kernels' refilling loop (pt_query_loop.h): the queue is implicit (entry i is ray i of the
 // caller's arrays), a retiring lane writes the caller's answer arrays.  Every ray is traced by start_ray / inline_round - node_step
 // and tri_step inside - exactly as in the render kernels and in the hook, so the answers are theirs bit for bit.  Differences:
 //   - a per-ray distance limit: r.tmax starts at it (boxes beyond it are culled from the start; a triangle inside a conservative
@@ -680,10 +680,79 @@ __global__ __launch_bounds__(256) void pt_trace_rays(const PtScene sc, const flo
 // Hit attributes (ATTR, rt_query_rays_attr_device): the sink of a lane that retires a ray with a winner fetches
 // the 48-byte record at best.li once more and evaluates hit_attr.h on the lane's own r.o, r.d - the values the accepting tri_step used,
 // so u, v, det are its u, v, det bit for bit.  tri_step carries nothing new: it and the rounds are the plain kernels'.
-// The sink stands before the source: r, best, limit and ray are still the retiring ray's.  The attribute arrays come in an argument
+// The attribute arrays come in an argument
 // block of their own (RayAttrQuery), so the plain instantiations keep theirs and are the code of a kernel without ATTR (profiles/hit_attributes.txt).
 template <bool ATTR>
 using RayQueryOf = std::conditional_t<ATTR, RayAttrQuery, RayQuery>;
+
+template <bool ANY, bool ATTR>
+struct RayLane {
+    const PtScene& sc;
+    const RayQueryOf<ATTR>& q;
+    const uint8_t* perm_lut;
+    int tris_per_round;  // byte 1 of tune_refill_min
+    TravStack stk;
+    TravCounters tc{0, 0, 0};
+    TRay r = make_tray(mk(0.0f, 0.0f, 0.0f), mk(0.0f, 1.0f, 0.0f), 0.0f);
+    Hit best{0.0f, -1, 0u};
+    Group G{0u, 0u}, T{0u, 0u};
+    uint32_t ray = 0;      // index of this lane's ray
+    float limit = 0.0f;    // its distance limit
+    uint32_t invalid = 0;  // invalid rays this lane has met
+    bool occluded = false;
+
+    __device__ __forceinline__ void retire() {
+        if (ANY) {
+            q.tri_out[ray] = occluded ? 1 : 0;
+            return;
+        }
+        const bool hit = best.li >= 0 && best.t < limit;
+        q.t_out[ray] = hit ? best.t : __builtin_inff();
+        q.tri_out[ray] = hit ? (int)best.id : RT_RAY_MISS;
+        if constexpr (ATTR) {
+            if (hit) {
+                const float4* tp = sc.tris + (size_t)best.li * 3;
+                const float4 ta = tp[0], tb = tp[1], tcw = tp[2];
+                const P3 e1{ta.w, tb.x, tb.y}, e2{tb.z, tb.w, tcw.x};
+                const Bary b = ray_bary(P3{r.o.x, r.o.y, r.o.z}, P3{r.d.x, r.d.y, r.d.z}, P3{ta.x, ta.y, ta.z}, e1, e2);
+                write_attr(q.uv_out, q.normal_out, ray, b.u, b.v, unit_normal(e1, e2));
+            } else {
+                write_no_attr(q.uv_out, q.normal_out, ray);  // a miss, or a hit that its limit cuts off
+            }
+        }
+    }
+
+    __device__ __forceinline__ bool admit(uint32_t i) {
+        const float* po = q.origins + (size_t)i * 3u;
+        const float* pd = q.dirs + (size_t)i * 3u;
+        const v3 o = mk(po[0], po[1], po[2]), d = mk(pd[0], pd[1], pd[2]);
+        limit = q.tmax ? q.tmax[i] : ANY ? kShadowTmax : __builtin_inff();
+        // (comparisons that are false for a NaN; +-inf origins fail the range test)
+        const bool in_reach = __builtin_fabsf(o.x) <= q.reach && __builtin_fabsf(o.y) <= q.reach && __builtin_fabsf(o.z) <= q.reach;
+        const bool d_finite = __builtin_fabsf(d.x) < __builtin_inff() && __builtin_fabsf(d.y) < __builtin_inff() && __builtin_fabsf(d.z) < __builtin_inff();
+        if (!(in_reach && d_finite && limit == limit)) {  // not traced
+            if (!ANY) q.t_out[i] = __builtin_nanf("");
+            q.tri_out[i] = RT_RAY_INVALID;
+            invalid++;
+        } else if (!(limit > 0.0f)) {  // an empty interval: a miss without a walk
+            if (!ANY) q.t_out[i] = __builtin_inff();
+            q.tri_out[i] = ANY ? 0 : RT_RAY_MISS;
+        } else {
+            start_ray(ANY, o, d, r, best, G, T, stk);
+            r.tmax = limit;
+            ray = i;
+            occluded = false;
+            return true;
+        }
+        if constexpr (ATTR) write_no_attr(q.uv_out, q.normal_out, i);
+        return false;
+    }
+
+    // (UNORDERED for any-hit rays, as in an all-shadow launch)
+    __device__ __forceinline__ bool step(bool alive) {
+        return inline_round<false, ANY>(sc, perm_lut, r, best, G, T, stk, tc, alive, occluded, ANY, tris_per_round, limit);
+    }
+};
 
 template <bool ANY, bool ATTR>
 __global__ __launch_bounds__(256, kInlineWaves) void pt_query_rays(const PtScene sc, const RayQueryOf<ATTR> q, uint32_t* __restrict__ head,
@@ -692,86 +761,11 @@ __global__ __launch_bounds__(256, kInlineWaves) void pt_query_rays(const PtScene
     extern __shared__ unsigned long long lds_stack[];  // sk.lds_cap x 256 entries
     __shared__ uint8_t perm_lut[2048];
     build_perm_lut(perm_lut);
-    TravStack stk = make_trav_stack(lds_stack, sk);
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const int tris_per_round = tris_per_round_of(refill_min);
-    refill_min &= 0xffu;
-    TravCounters tc{0, 0, 0};
-    TRay r = make_tray(mk(0.0f, 0.0f, 0.0f), mk(0.0f, 1.0f, 0.0f), 0.0f);
-    Hit best{0.0f, -1, 0u};
-    Group G{0u, 0u}, T{0u, 0u};
-    uint32_t ray = 0;      // index of this lane's ray
-    float limit = 0.0f;    // its distance limit
-    uint32_t invalid = 0;  // invalid rays this lane has met
-    bool has_ray = false, occluded = false, alive = false;
-    QueueCursor cur{q.n, head, home_stream(), 0u};
-    bool exhausted = cur.n == 0u;  // every stream has been found dry
-
-    for (;;) {
-        const unsigned long long idle = __ballot(!alive);
-        if (idle == ~0ull || (!exhausted && (uint32_t)__popcll(idle) >= refill_min)) {
-            if (!alive && has_ray) {  // the sink
-                if (ANY) {
-                    q.tri_out[ray] = occluded ? 1 : 0;
-                } else {
-                    const bool hit = best.li >= 0 && best.t < limit;
-                    q.t_out[ray] = hit ? best.t : __builtin_inff();
-                    q.tri_out[ray] = hit ? (int)best.id : RT_RAY_MISS;
-                    if constexpr (ATTR) {
-                        if (hit) {
-                            const float4* tp = sc.tris + (size_t)best.li * 3;
-                            const float4 ta = tp[0], tb = tp[1], tcw = tp[2];
-                            const P3 e1{ta.w, tb.x, tb.y}, e2{tb.z, tb.w, tcw.x};
-                            const Bary b = ray_bary(P3{r.o.x, r.o.y, r.o.z}, P3{r.d.x, r.d.y, r.d.z}, P3{ta.x, ta.y, ta.z}, e1, e2);
-                            write_attr(q.uv_out, q.normal_out, ray, b.u, b.v, unit_normal(e1, e2));
-                        } else {
-                            write_no_attr(q.uv_out, q.normal_out, ray);  // a miss, or a hit that its limit cuts off
-                        }
-                    }
-                }
-                has_ray = false;
-            }
-            if (!exhausted) {  // exactly what the idle lanes need, assigned by ballot + prefix popcount
-                const uint32_t want = (uint32_t)__popcll(idle);
-                const uint32_t base = cur.reserve(want, lane);
-                const uint32_t i = !alive ? stream_entry(cur.stream, base + (uint32_t)__popcll(idle & lt_mask)) : cur.n;  // >= n: nothing for this lane
-                if (!alive && i < cur.n) {  // the source
-                    const float* po = q.origins + (size_t)i * 3u;
-                    const float* pd = q.dirs + (size_t)i * 3u;
-                    const v3 o = mk(po[0], po[1], po[2]), d = mk(pd[0], pd[1], pd[2]);
-                    limit = q.tmax ? q.tmax[i] : ANY ? kShadowTmax : __builtin_inff();
-                    // (comparisons that are false for a NaN; +-inf origins fail the range test)
-                    const bool in_reach = __builtin_fabsf(o.x) <= q.reach && __builtin_fabsf(o.y) <= q.reach && __builtin_fabsf(o.z) <= q.reach;
-                    const bool d_finite = __builtin_fabsf(d.x) < __builtin_inff() && __builtin_fabsf(d.y) < __builtin_inff() && __builtin_fabsf(d.z) < __builtin_inff();
-                    if (!(in_reach && d_finite && limit == limit)) {  // not traced
-                        if (!ANY) q.t_out[i] = __builtin_nanf("");
-                        q.tri_out[i] = RT_RAY_INVALID;
-                        invalid++;
-                        if constexpr (ATTR) write_no_attr(q.uv_out, q.normal_out, i);
-                    } else if (!(limit > 0.0f)) {  // an empty interval: a miss without a walk
-                        if (!ANY) q.t_out[i] = __builtin_inff();
-                        q.tri_out[i] = ANY ? 0 : RT_RAY_MISS;
-                        if constexpr (ATTR) write_no_attr(q.uv_out, q.normal_out, i);
-                    } else {
-                        start_ray(ANY, o, d, r, best, G, T, stk);
-                        r.tmax = limit;
-                        ray = i;
-                        occluded = false;
-                        has_ray = true;
-                        alive = true;
-                    }
-                }
-                exhausted = cur.advance_if_dry(base + want);
-            }
-            if (__ballot(alive) == 0ull && exhausted) break;  // every answer of this wave is written (idle lanes retired above)
-        }
-        // (UNORDERED for any-hit rays, as in an all-shadow launch)
-        alive = inline_round<false, ANY>(sc, perm_lut, r, best, G, T, stk, tc, alive, occluded, ANY, tris_per_round, limit);
-    }
-    add_wave_total(&stats[RQ_STAT_INVALID], invalid, lane);
-    if (tc.overflow) atomicOr((unsigned int*)&stats[RQ_STAT_OVERFLOW], 1u);
+    RayLane<ANY, ATTR> lane{sc, q, perm_lut, tris_per_round_of(refill_min), make_trav_stack(lds_stack, sk)};
+    const uint32_t lane_id = threadIdx.x & 63u;
+    RT_QUERY_LOOP(lane, q.n, head, refill_min & 0xffu, lane_id);
+    add_wave_total(&stats[RQ_STAT_INVALID], lane.invalid, lane_id);
+    if (lane.tc.overflow) atomicOr((unsigned int*)&stats[RQ_STAT_OVERFLOW], 1u);
 }
 
 // ---- launchers ------------------------------------------------------------------------------------

@@ -1,8 +1,8 @@
 // pt_traverse.h — path B, device side: what one lane needs to walk the compressed 8-wide BVH (bvh_node.h) with a ray.  The ray /
 // triangle tests, the ray in traversal form, the work items (node and triangle groups), the per-lane stack, the node step, the
 // triangle step and the round that the persistent loops repeat.  Used by the per-lane trace kernels, the test hook
-// and the ray queries (pt_trace.hip), for the triangle tests and the ray set-up by the packet kernels (pt_packet.hip), for the stack
-// by the point queries (pt_point_query.hip).
+// and the ray queries (pt_trace.hip), for the triangle tests and the ray set-up by the packet kernels (pt_packet.hip), for the stack,
+// the work items and the unpacked node record (NodeRec) by the other query kernels (pt_query_loop.h and the pt_*_query.hip units).
 // Only __device__ __forceinline__ functions, structs and constants: every unit that includes this compiles its own copy into its
 // kernels, and the Makefile gives all of them the same flags so that the copies are the same code.
 #pragma once
@@ -155,6 +155,30 @@ struct TravStack {
 
 __device__ __forceinline__ float ubyte_f32(uint32_t w, int byte) {  // v_cvt_f32_ubyteN
     return (float)((w >> (8 * byte)) & 0xffu);
+}
+
+// An 80-byte node record (bvh_node.h) fetched and unpacked once, for the walks of the queries (pt_query_loop.h and the kernels around
+// it): five 16-byte loads, the origin, the three scales from their exponent bytes, the masks, the bases and the twelve plane words.
+// node_step below keeps its own hand-scheduled decode: the render kernels are compiled from it.
+struct NodeRec {
+    float ox, oy, oz, sx, sy, sz;
+    uint32_t imask, leafmask, child_base, tri_base;
+    uint32_t lx[2], ly[2], lz[2], hx[2], hy[2], hz[2];
+    // node index of the inner child in slot s, leaf-order index of the triangle in leaf slot s: the slot's rank under its mask
+    __device__ __forceinline__ uint32_t child(uint32_t s) const { return child_base + (uint32_t)__builtin_popcount(imask & ~(0xffffffffu << s)); }
+    __device__ __forceinline__ uint32_t leaf_tri(uint32_t s) const { return tri_base + (uint32_t)__builtin_popcount(leafmask & ~(0xffffffffu << s)); }
+};
+__device__ __forceinline__ float plane_q(const uint32_t (&w)[2], int slot) { return ubyte_f32(w[slot >> 2], slot & 3); }  // a plane's byte, exact
+template <bool COUNT>
+__device__ __forceinline__ NodeRec fetch_node(const float4* __restrict__ nodes, uint32_t index, TravCounters& tc) {
+    const float4* nd = nodes + (size_t)index * 5;
+    const float4 n0 = nd[0], n1 = nd[1], n2 = nd[2], n3 = nd[3], n4 = nd[4];
+    if (COUNT) tc.nodes++;
+    const uint32_t w3 = __float_as_uint(n0.w);
+    return NodeRec{n0.x, n0.y, n0.z, __uint_as_float((w3 & 0xffu) << 23), __uint_as_float(((w3 >> 8) & 0xffu) << 23), __uint_as_float(((w3 >> 16) & 0xffu) << 23),
+                   w3 >> 24, __float_as_uint(n1.z) & 0xffu, __float_as_uint(n1.x), __float_as_uint(n1.y),
+                   {__float_as_uint(n2.x), __float_as_uint(n2.y)}, {__float_as_uint(n2.z), __float_as_uint(n2.w)}, {__float_as_uint(n3.x), __float_as_uint(n3.y)},
+                   {__float_as_uint(n3.z), __float_as_uint(n3.w)}, {__float_as_uint(n4.x), __float_as_uint(n4.y)}, {__float_as_uint(n4.z), __float_as_uint(n4.w)}};
 }
 
 // Visit the nearest pending inner child of node group G: fetch its 80-byte record (five 16-byte

@@ -437,7 +437,7 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     DevPtr<uint32_t> d_ctr;
     DevPtr<unsigned long long> d_stats;  // PT_STAT_WORDS words
     rt_pt_stats stats{};
-    // the six query kinds (rays, closest points, sides, all hits, neighbours, overlaps): what is in flight, and the statistics of the last query of each kind
+    // the query kinds (rays, closest points, sides, all hits, neighbours, overlaps, overlap segments, clearance, k-nearest): what is in flight, and the statistics of the last query of each kind
     // (rays: the 2 KiB octant table, two spill halves as the frames hold; the others: no table, one set of columns)
     QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u}, side_query{SQ_STAT_WORDS, "side-query", 0u, 1u};
     ListingState hit_query{"hit-query"}, neighbor_query{"neighbor-query"};  // rt_count / fill / list_ray_hits_device, rt_count / fill / list_neighbors_device

@@ -127,11 +127,13 @@ def set_batch(renderer):
 TUNINGS = [dict(tune_max_blocks=1, tune_refill_min=1), dict(tune_max_blocks=1, tune_refill_min=24), dict(tune_max_blocks=1, tune_refill_min=64)]
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1000])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1000, 1023, 1024, 1025])
 def test_batch_edges_and_refill(renderer, n):
     """One workgroup (tune_max_blocks = 1) has 4 waves for the 16 streams: every stream is reached only by waves moving on from a dry
-    one, and with 1 000 points every lane refills."""
+    one, and with 1 000 points every lane refills.  16 streams of 64 entries: 1 023 / 1 024 / 1 025 are the first sizes at which a wave's home stream is dry
+    while others are not."""
     b = set_batch(renderer)
+    assert n <= len(b["p"])
     for kw in TUNINGS:
         inside, crossings = sides(renderer, b["p"][:n], want_crossings=True, **kw)
         assert np.array_equal(inside, b["ref"]["inside"][:n]) and np.array_equal(crossings, b["ref"]["brute"][:n]), (n, kw)
