@@ -5,53 +5,29 @@ arithmetic of csrc/tri_dist.h without a tree), which the kernel must match bit f
 contract, which its answers must satisfy on their own.  The first tests run every family on its own meshes; the others use one batch:
 the 600 query triangles of soup_batch() against the 2 000-triangle soup.  A distance limit needs no tolerance: the answer is defined as
 the (d2, index)-minimal triangle, so "hit when d2 < rmax * rmax" is decided by the reference's own d2."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
 import clearance_exact as CX
-import ray_exact as X
 import raytracing_engine_amd as R
+from gpu_query import RT_ERR_INVALID, RT_ERR_STATE, assert_untouched, bad_params, bad_pointers, dev, pt_frame, ptr, same_floats, sentinel, still_sentinel, tdev
+from gpu_query import set_mesh_px_surface as set_mesh
 
 pytestmark = pytest.mark.gpu
 
 PX, OX = CX.PX, CX.OX
 f32 = np.float32
 INF = f32(np.inf)
-RT_ERR_INVALID, RT_ERR_STATE = -1, -4
 MISS, INVALID = -1, -2
 N = 600
-
-
-def dev():
-    import torch
-
-    return torch.device("cuda", 0)
-
-
-def tdev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
 
 
 def query(renderer, q, rmax=None, **kw):
     """Numpy in, numpy out, through device tensors: (dist, tri, point_query, point_mesh)."""
     got = renderer.query_clearance(tdev(q), None if rmax is None else tdev(rmax), **kw)
     return tuple(None if x is None else x.cpu().numpy() for x in got)
-
-
-def same_floats(a, b):
-    """Bit-equal, NaN for NaN (whatever its payload)."""
-    a, b = np.asarray(a, f32).ravel(), np.asarray(b, f32).ravel()
-    nan = np.isnan(a)
-    return a.shape == b.shape and np.array_equal(nan, np.isnan(b)) and np.array_equal(a[~nan].view(np.uint32), b[~nan].view(np.uint32))
-
-
-def set_mesh(renderer, verts, **kw):
-    renderer.set_mesh(verts, *PX.surface(verts), **kw)
 
 
 def assert_answers(got, ref, sel=slice(None), what=None):
@@ -235,13 +211,11 @@ def test_bounds_and_out_tensors(renderer):
     for n in (1, 65, N):
         q, rm = tdev(b["q"][:n]), tdev(np.full(n, INF, f32))
         q0, rm0 = q.clone(), rm.clone()
-        d_buf = torch.full((n + 64,), -7.0, dtype=torch.float32, device=dev())
-        t_buf = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
-        a_buf = torch.full((n + 64, 3), -7.0, dtype=torch.float32, device=dev())
-        c_buf = torch.full((n + 64, 3), -7.0, dtype=torch.float32, device=dev())
+        d_buf, t_buf = sentinel(n, torch.float32, 64), sentinel(n, torch.int32, 64)
+        a_buf, c_buf = sentinel(n, torch.float32, 64, cols=3), sentinel(n, torch.float32, 64, cols=3)
         dist, tri, pq, pm = renderer.query_clearance(q.view(n, 3, 3), rm, out=(d_buf[:n], t_buf[:n], a_buf[:n], c_buf[:n]))
         assert dist.data_ptr() == d_buf.data_ptr() and tri.data_ptr() == t_buf.data_ptr() and pq.data_ptr() == a_buf.data_ptr() and pm.data_ptr() == c_buf.data_ptr()
-        assert (d_buf[n:] == -7.0).all() and (t_buf[n:] == -7).all() and (a_buf[n:] == -7.0).all() and (c_buf[n:] == -7.0).all()
+        assert still_sentinel(d_buf, 0, n) and still_sentinel(t_buf, 0, n) and still_sentinel(a_buf, 0, n) and still_sentinel(c_buf, 0, n)
         assert_answers(tuple(x.cpu().numpy() for x in (dist, tri, pq, pm)), b["ref"], slice(0, n))
         for x, x0 in ((q, q0), (rm, rm0)):
             assert torch.equal(x.view(torch.int32), x0.view(torch.int32))
@@ -249,10 +223,10 @@ def test_bounds_and_out_tensors(renderer):
         d_buf.fill_(-7.0)
         t_buf.fill_(-7)
         dist, tri, none_q, none_m = renderer.query_clearance(q, out=(d_buf[:n], t_buf[:n]), want_points=False)
-        assert none_q is None and none_m is None and (d_buf[n:] == -7.0).all() and (t_buf[n:] == -7).all()
+        assert none_q is None and none_m is None and still_sentinel(d_buf, 0, n) and still_sentinel(t_buf, 0, n)
         assert_answers((dist.cpu().numpy(), tri.cpu().numpy(), None, None), b["ref"], slice(0, n))
         # each point output NULL in turn, through the library
-        lib, ptr = R.load(), (lambda x: C.c_void_p(x.data_ptr()))
+        lib = R.load()
         for keep_query in (True, False):
             for buf in (d_buf, t_buf, a_buf, c_buf):
                 buf.fill_(-7)
@@ -261,7 +235,7 @@ def test_bounds_and_out_tensors(renderer):
                                                  None if keep_query else ptr(c_buf)) == 0
             renderer.synchronize()
             kept, left = (a_buf, c_buf) if keep_query else (c_buf, a_buf)
-            assert (left == -7.0).all() and (kept[n:] == -7.0).all() and (d_buf[n:] == -7.0).all() and (t_buf[n:] == -7).all()
+            assert still_sentinel(left) and still_sentinel(kept, 0, n) and still_sentinel(d_buf, 0, n) and still_sentinel(t_buf, 0, n)
             assert_answers((d_buf[:n].cpu().numpy(), t_buf[:n].cpu().numpy(), a_buf[:n].cpu().numpy() if keep_query else None,
                             None if keep_query else c_buf[:n].cpu().numpy()), b["ref"], slice(0, n))
     with pytest.raises(ValueError):
@@ -284,10 +258,7 @@ def test_stream_order_behind_a_refit(renderer):
     ref = cm["ref"]["brute"]
     assert not np.array_equal(ref["dist"], CX.reference(v, cm["q"])["brute"]["dist"])  # the unmoved mesh answers otherwise
     ref_d, ref_t, ref_q, ref_m = tdev(ref["dist"]).view(torch.int32), tdev(ref["tri"]), tdev(ref["pq"]).view(torch.int32), tdev(ref["pm"]).view(torch.int32)
-    dist = torch.full((n,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    pq = torch.full((n, 3), -7.0, dtype=torch.float32, device=dev())
-    pm = torch.full((n, 3), -7.0, dtype=torch.float32, device=dev())
+    dist, tri, pq, pm = sentinel(n, torch.float32), sentinel(n, torch.int32), sentinel(n, torch.float32, cols=3), sentinel(n, torch.float32, cols=3)
     torch.cuda.synchronize()
     s = torch.cuda.Stream(device=dev())
     renderer.set_stream(s.cuda_stream)
@@ -303,16 +274,6 @@ def test_stream_order_behind_a_refit(renderer):
         renderer.set_stream(None)
 
 
-def _segment_end(ptr):
-    """End address of the device allocation (caching-allocator segment) that holds `ptr`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= ptr < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
-
-
 def test_errors_write_nothing(renderer):
     import torch
 
@@ -320,11 +281,7 @@ def test_errors_write_nothing(renderer):
     b = set_soup(renderer)
     n = 500
     q = tdev(b["q"][:n])
-    dist = torch.full((n,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    pq = torch.full((n, 3), -7.0, dtype=torch.float32, device=dev())
-    pm = torch.full((n, 3), -7.0, dtype=torch.float32, device=dev())
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+    dist, tri, pq, pm = sentinel(n, torch.float32), sentinel(n, torch.int32), sentinel(n, torch.float32, cols=3), sentinel(n, torch.float32, cols=3)
     good = (ptr(q), None, n, None, ptr(tri), ptr(dist), ptr(pq), ptr(pm))
     fresh = R.Renderer(0)
     try:
@@ -332,12 +289,8 @@ def test_errors_write_nothing(renderer):
     finally:
         fresh.close()
     ctx = renderer._ctx
-    host = np.zeros((n, 9), f32)
-    hp = C.c_void_p(host.ctypes.data)
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
-    end = _segment_end(big.data_ptr())
-    short9, short3, short1 = C.c_void_p(end - 36 * (n - 1)), C.c_void_p(end - 12 * (n - 1)), C.c_void_p(end - 4 * (n - 1))  # n - 1 rows from here
-    P = R.ClearanceQueryParams
+    bp = bad_pointers(n, short9=36, short3=12, short1=4)  # n - 1 rows from the short ones
+    hp, big, short9, short3, short1 = bp.hp, bp.big, bp.short9, bp.short3, bp.short1
 
     def with_arg(k, value):
         args = list(good)
@@ -347,17 +300,14 @@ def test_errors_write_nothing(renderer):
     calls = [with_arg(0, None), with_arg(4, None), with_arg(5, None),  # NULL where a pointer is due
              with_arg(0, hp), with_arg(1, hp), with_arg(4, hp), with_arg(5, hp), with_arg(6, hp), with_arg(7, hp),  # host memory
              with_arg(0, short9), with_arg(1, short1), with_arg(4, short1), with_arg(5, short1), with_arg(6, short3), with_arg(7, short3),  # too short
-             with_arg(2, (1 << 30) + 1),
-             with_arg(3, C.byref(P(tune_refill_min=65))), with_arg(3, C.byref(P(tune_blocks_per_cu=9))), with_arg(3, C.byref(P(tune_lds_stack=79))),
-             with_arg(3, C.byref(P(count_traversal=2)))]
+             with_arg(2, (1 << 30) + 1)] + [with_arg(3, prm) for prm in bad_params(R.ClearanceQueryParams)]
     for k, args in enumerate(calls):
         assert lib.rt_query_clearance_device(ctx, *args) == RT_ERR_INVALID, k
-        renderer.synchronize()
-        assert (dist == -7.0).all() and (tri == -7).all() and (pq == -7.0).all() and (pm == -7.0).all() and (big == 0).all(), k
+        assert_untouched(renderer, (dist, tri, pq, pm), big, k)
     assert lib.rt_query_clearance_device(ctx, *with_arg(2, 0)) == 0  # n = 0 is accepted, and does nothing
     assert lib.rt_query_clearance_device(ctx, None, None, 0, None, None, None, None, None) == 0
     renderer.synchronize()
-    assert (dist == -7.0).all() and (tri == -7).all() and (pq == -7.0).all() and (pm == -7.0).all()
+    assert still_sentinel(dist) and still_sentinel(tri) and still_sentinel(pq) and still_sentinel(pm)
     e = renderer.query_clearance(q[:0])
     assert all(len(x) == 0 for x in e)
     # a mesh beyond the domain is refused too, and the context still answers afterwards
@@ -365,7 +315,7 @@ def test_errors_write_nothing(renderer):
     set_mesh(renderer, far)
     assert lib.rt_query_clearance_device(ctx, *good) == RT_ERR_INVALID
     renderer.synchronize()
-    assert (dist == -7.0).all() and (tri == -7).all()
+    assert still_sentinel(dist) and still_sentinel(tri)
     set_mesh(renderer, b["v"])
     got = renderer.query_clearance(q, out=(dist, tri, pq, pm))
     assert_answers(tuple(x.cpu().numpy() for x in got), b["ref"], slice(0, n))
@@ -378,9 +328,7 @@ def test_rendering_and_sharing_are_undisturbed(renderer):
     kw = dict(pos=(0, 1, 0), spp=2, bounces=2, seed=3, sky=(0.2, 0.2, 0.3))
 
     def frame(r):
-        rgb = r.render_pt(**kw)
-        st = r.pt_stats()
-        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+        return pt_frame(r, **kw)
 
     before = frame(renderer)
     assert before[1][1] > 0 and before[1][2] > 0

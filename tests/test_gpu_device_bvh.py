@@ -13,6 +13,7 @@ import pytest
 
 import oracle as O
 import raytracing_engine_amd as R
+from gpu_query import ptr
 from lbvh_exact import check_tree
 from raytracing_engine_amd import scenes
 
@@ -277,7 +278,6 @@ def test_errors_leave_the_previous_mesh(renderer):
     n = len(mesh[0])
     host = np.zeros((n, 9), np.float32)
     ctx = renderer._ctx
-    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     assert lib.rt_set_mesh_device(ctx, None, ptr(a), ptr(e), n) == RT_ERR_INVALID
     assert lib.rt_set_mesh_device(ctx, ptr(v), None, ptr(e), n) == RT_ERR_INVALID
     assert lib.rt_set_mesh_device(ctx, ptr(v), ptr(a), None, n) == RT_ERR_INVALID

@@ -17,13 +17,12 @@ import ray_exact as X
 import raytracing_engine_amd as R
 import test_gpu_point_query as TP
 import test_gpu_ray_query as TR
-from test_gpu_point_query import dev, same_floats, tdev  # same_floats: bit-equal, NaN for NaN
+from gpu_query import RT_ERR_INVALID, bad_pointers, busy_stream, pt_frame, ptr, same_floats, sentinel, still_sentinel, tdev  # same_floats: bit-equal, NaN for NaN
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 INF = f32(np.inf)
-RT_ERR_INVALID = -1
 MISS, INVALID = -1, -2
 N = 4000
 NS = [1, 63, 64, 65, 255, 256, 257, 4000]
@@ -250,7 +249,6 @@ def test_each_attribute_array_may_be_null_and_nothing_else_is_written(renderer):
     import torch
 
     lib = R.load()
-    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
     TR.set_soup(renderer)
     m = mixed_rays()
     for n in (1, 65, N):
@@ -258,23 +256,21 @@ def test_each_attribute_array_may_be_null_and_nothing_else_is_written(renderer):
         o, d, tm = tdev(m["o"][sel]), tdev(m["d"][sel]), tdev(m["tmax"][sel])
         o0, d0, tm0 = o.clone(), d.clone(), tm.clone()
         for want_uv, want_n in ((True, True), (True, False), (False, True), (False, False)):
-            t = torch.full((n + 64,), -7.0, dtype=torch.float32, device=dev())
-            tri = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
-            uv = torch.full((n + 64, 2), -7.0, dtype=torch.float32, device=dev())
-            nrm = torch.full((n + 64, 3), -7.0, dtype=torch.float32, device=dev())
+            t, tri = sentinel(n, torch.float32, 64), sentinel(n, torch.int32, 64)
+            uv, nrm = sentinel(n, torch.float32, 64, cols=2), sentinel(n, torch.float32, 64, cols=3)
             assert lib.rt_query_rays_attr_device(renderer._ctx, ptr(o), ptr(d), ptr(tm), n, None, ptr(t), ptr(tri), ptr(uv if want_uv else None), ptr(nrm if want_n else None)) == 0
             renderer.synchronize()
             ref = m["ref"]
             assert np.array_equal(tri[:n].cpu().numpy(), ref["tri"][sel]) and same_floats(t[:n].cpu().numpy(), ref["t"][sel]), (n, want_uv, want_n)
-            assert (t[n:] == -7.0).all() and (tri[n:] == -7).all() and (uv[n:] == -7.0).all() and (nrm[n:] == -7.0).all()
+            assert still_sentinel(t, 0, n) and still_sentinel(tri, 0, n) and still_sentinel(uv, 0, n) and still_sentinel(nrm, 0, n)
             if want_uv:
                 assert same_floats(uv[:n, 0].cpu().numpy(), ref["ub"][sel]) and same_floats(uv[:n, 1].cpu().numpy(), ref["vb"][sel])
             else:
-                assert (uv == -7.0).all()
+                assert still_sentinel(uv)
             if want_n:
                 assert same_floats(nrm[:n].cpu().numpy(), ref["normal"][sel])
             else:
-                assert (nrm == -7.0).all()
+                assert still_sentinel(nrm)
         for x, x0 in ((o, o0), (d, d0), (tm, tm0)):
             assert torch.equal(x.view(torch.int32), x0.view(torch.int32))
     # points
@@ -285,23 +281,20 @@ def test_each_attribute_array_may_be_null_and_nothing_else_is_written(renderer):
     p, rm = tdev(mp["p"][sel]), tdev(mp["rmax"][sel])
     p0, rm0 = p.clone(), rm.clone()
     for want_c, want_uv, want_n in ((True, True, True), (False, True, False), (False, False, True), (True, False, False), (False, False, False)):
-        dist = torch.full((n + 64,), -7.0, dtype=torch.float32, device=dev())
-        tri = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
-        c = torch.full((n + 64, 3), -7.0, dtype=torch.float32, device=dev())
-        uv = torch.full((n + 64, 2), -7.0, dtype=torch.float32, device=dev())
-        nrm = torch.full((n + 64, 3), -7.0, dtype=torch.float32, device=dev())
+        dist, tri, c = sentinel(n, torch.float32, 64), sentinel(n, torch.int32, 64), sentinel(n, torch.float32, 64, cols=3)
+        uv, nrm = sentinel(n, torch.float32, 64, cols=2), sentinel(n, torch.float32, 64, cols=3)
         assert lib.rt_query_points_attr_device(renderer._ctx, ptr(p), ptr(rm), n, None, ptr(dist), ptr(tri), ptr(c if want_c else None), ptr(uv if want_uv else None),
                                                ptr(nrm if want_n else None)) == 0
         renderer.synchronize()
         ref = mp["ref"]
         assert np.array_equal(tri[:n].cpu().numpy(), ref["tri"][sel]) and same_floats(dist[:n].cpu().numpy(), ref["dist"][sel])
-        assert (dist[n:] == -7.0).all() and (tri[n:] == -7).all() and (c[n:] == -7.0).all() and (uv[n:] == -7.0).all() and (nrm[n:] == -7.0).all()
-        assert same_floats(c[:n].cpu().numpy(), ref["c"][sel]) if want_c else bool((c == -7.0).all())
-        assert (same_floats(uv[:n, 0].cpu().numpy(), ref["u"][sel]) and same_floats(uv[:n, 1].cpu().numpy(), ref["v"][sel])) if want_uv else bool((uv == -7.0).all())
-        assert same_floats(nrm[:n].cpu().numpy(), ref["normal"][sel]) if want_n else bool((nrm == -7.0).all())
+        assert still_sentinel(dist, 0, n) and still_sentinel(tri, 0, n) and still_sentinel(c, 0, n) and still_sentinel(uv, 0, n) and still_sentinel(nrm, 0, n)
+        assert same_floats(c[:n].cpu().numpy(), ref["c"][sel]) if want_c else still_sentinel(c)
+        assert (same_floats(uv[:n, 0].cpu().numpy(), ref["u"][sel]) and same_floats(uv[:n, 1].cpu().numpy(), ref["v"][sel])) if want_uv else still_sentinel(uv)
+        assert same_floats(nrm[:n].cpu().numpy(), ref["normal"][sel]) if want_n else still_sentinel(nrm)
     assert torch.equal(p.view(torch.int32), p0.view(torch.int32)) and torch.equal(rm.view(torch.int32), rm0.view(torch.int32))
     # the wrapper's out tensors are the ones it returns
-    t, tri, uv, nrm = (torch.full(s, -7, dtype=dt, device=dev()) for s, dt in (((n,), torch.float32), ((n,), torch.int32), ((n, 2), torch.float32), ((n, 3), torch.float32)))
+    t, tri, uv, nrm = sentinel(n, torch.float32), sentinel(n, torch.int32), sentinel(n, torch.float32, cols=2), sentinel(n, torch.float32, cols=3)
     got = renderer.query_rays(tdev(m["o"][sel]), tdev(m["d"][sel]), attributes=True, out=(t, tri, uv, nrm))
     assert [g.data_ptr() for g in got] == [x.data_ptr() for x in (t, tri, uv, nrm)]
 
@@ -310,19 +303,15 @@ def test_refusals_leave_all_outputs_untouched(renderer):
     import torch
 
     lib = R.load()
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
     n = 1000
-    host = np.zeros((n, 3), f32)
-    hp = C.c_void_p(host.ctypes.data)
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
-    end = TP._segment_end(big.data_ptr())
-    short3, short2, short1 = C.c_void_p(end - 12 * (n - 1)), C.c_void_p(end - 8 * (n - 1)), C.c_void_p(end - 4 * (n - 1))  # the allocation holds n - 1 rows from here
-    outs = [torch.full(s, -7, dtype=dt, device=dev()) for s, dt in (((n,), torch.float32), ((n,), torch.int32), ((n, 3), torch.float32), ((n, 2), torch.float32), ((n, 3), torch.float32))]
+    ends = bad_pointers(n, short3=12, short2=8, short1=4)  # the allocation holds n - 1 rows from the short ones
+    hp, big, short3, short2, short1 = ends.hp, ends.big, ends.short3, ends.short2, ends.short1
+    outs = [sentinel(n, torch.float32), sentinel(n, torch.int32), sentinel(n, torch.float32, cols=3), sentinel(n, torch.float32, cols=2), sentinel(n, torch.float32, cols=3)]
     t, tri, c, uv, nrm = outs
 
     def untouched():
         renderer.synchronize()
-        return all(bool((x == -7).all()) for x in outs) and bool((big == 0).all())
+        return all(still_sentinel(x) for x in outs) and bool((big == 0).all())
 
     b = TR.set_soup(renderer)
     o, d = tdev(b["o"][:n]), tdev(b["d"][:n])
@@ -381,29 +370,18 @@ def test_stream_order_with_interpolate_behind_the_query(renderer):
     o_half, d_half = tdev(b["o"] * f32(0.5)), tdev(b["d"] * f32(0.5))
     vattr = tdev(verts.reshape(-1, 3, 3)).double()
     ref_uv, ref_tri, ref_p = tdev(np.stack([ref["ub"], ref["vb"]], 1)).view(torch.int32), tdev(ref["tri"]), tdev(expect)
-    outs = [torch.full(s, -7, dtype=dt, device=dev()) for s, dt in (((n,), torch.float32), ((n,), torch.int32), ((n, 2), torch.float32), ((n, 3), torch.float32))]
-    pouts = [torch.full(s, -7, dtype=dt, device=dev()) for s, dt in (((n,), torch.float32), ((n,), torch.int32), ((n, 3), torch.float32), ((n, 2), torch.float32), ((n, 3), torch.float32))]
-    torch.cuda.synchronize()
-    s = torch.cuda.Stream(device=dev())
-    renderer.set_stream(s.cuda_stream)
-    try:
-        with torch.cuda.stream(s):
-            busy = torch.zeros(1 << 26, dtype=torch.float32, device=dev())
-            for _ in range(8):  # the stream has work to do when the query is enqueued
-                busy += 1.0
-            o, d = o_half * 2.0, d_half * 2.0  # (halving and doubling is exact)
-            t, tri, uv, nrm = renderer.query_rays(o, d, out=tuple(outs), sync=False, attributes=True)
-            P = R.Renderer.interpolate(tri, uv.double(), vattr)
-            wrong = (uv.view(torch.int32) != ref_uv).sum() + (tri != ref_tri).sum() + (~((P == ref_p) | (P.isnan() & ref_p.isnan()))).sum()
-            # the hit points as query points: their nearest triangle is at distance ~0, and the chained query reads what interpolate wrote
-            pts = torch.where(P.isnan(), torch.zeros_like(P), P).float().contiguous()
-            dist, ptri, c, puv, pn = renderer.query_points(pts, out=tuple(pouts), sync=False, attributes=True)
-            far = ((dist > 1e-4) & (tri >= 0)).sum()  # (miss rows ask about the origin of the coordinates)
-        s.synchronize()
-        assert int(wrong) == 0 and float(busy[0]) == 8.0 and int(far) == 0 and bool((ptri >= 0).all()) and bool(puv.isfinite().all())
-    finally:
-        renderer.synchronize()
-        renderer.set_stream(None)
+    outs = [sentinel(n, torch.float32), sentinel(n, torch.int32), sentinel(n, torch.float32, cols=2), sentinel(n, torch.float32, cols=3)]
+    pouts = [sentinel(n, torch.float32), sentinel(n, torch.int32), sentinel(n, torch.float32, cols=3), sentinel(n, torch.float32, cols=2), sentinel(n, torch.float32, cols=3)]
+    with busy_stream(renderer):
+        o, d = o_half * 2.0, d_half * 2.0  # (halving and doubling is exact)
+        t, tri, uv, nrm = renderer.query_rays(o, d, out=tuple(outs), sync=False, attributes=True)
+        P = R.Renderer.interpolate(tri, uv.double(), vattr)
+        wrong = (uv.view(torch.int32) != ref_uv).sum() + (tri != ref_tri).sum() + (~((P == ref_p) | (P.isnan() & ref_p.isnan()))).sum()
+        # the hit points as query points: their nearest triangle is at distance ~0, and the chained query reads what interpolate wrote
+        pts = torch.where(P.isnan(), torch.zeros_like(P), P).float().contiguous()
+        dist, ptri, c, puv, pn = renderer.query_points(pts, out=tuple(pouts), sync=False, attributes=True)
+        far = ((dist > 1e-4) & (tri >= 0)).sum()  # (miss rows ask about the origin of the coordinates)
+    assert int(wrong) == 0 and int(far) == 0 and bool((ptri >= 0).all()) and bool(puv.isfinite().all())
 
 
 # ---- 5. frames, sharing, statistics --------------------------------------------------------------------------------------------
@@ -415,9 +393,7 @@ def test_frames_sharing_and_statistics_are_undisturbed(renderer):
     kw = dict(pos=(0, 1, 0), spp=2, bounces=2, seed=3, sky=(0.2, 0.2, 0.3))
 
     def frame(r):
-        rgb = r.render_pt(**kw)
-        st = r.pt_stats()
-        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+        return pt_frame(r, **kw)
 
     before = frame(renderer)
     assert before[1][1] > 0 and before[1][2] > 0

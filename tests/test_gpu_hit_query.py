@@ -5,75 +5,31 @@ The reference is tests/hit_exact.py's native brute force (tests/native/hit_query
 triangles, sorted by (t, index), no tree), which the kernel must match bit for bit in counts, offsets and every list entry; that
 reference in turn is held to the oracle and to its own tree walk on the CPU (tests/test_hit_query_host.py).  The first tests run every
 family on its meshes; the others need ONE batch on ONE mesh whose size they can cut, tile and plant rays into: the 10 800 rays of the
-sphere's side case, shuffled, a third of them with a limit."""
-import ctypes as C
+sphere's side case, shuffled, a third of them with a limit.  The listing protocol's tests are tests/gpu_listing.py's, on this batch."""
 import functools
 
 import numpy as np
 import pytest
 
+import gpu_listing as L
 import hit_exact as H
 import ray_exact as X
 import sign_exact as SX
 import raytracing_engine_amd as R
+from gpu_query import RT_ERR_STATE, pt_frame, ptr, tdev
+from gpu_query import set_mesh_with_surface as set_mesh
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 INF = f32(np.inf)
-RT_ERR_INVALID, RT_ERR_STATE = -1, -4
 INVALID = H.INVALID
 ALL = SX.CLOSED + SX.OPEN
 
 
-def dev():
-    import torch
-
-    return torch.device("cuda", 0)
-
-
-def tdev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev())
-
-
-def ptr(x):
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
-def set_mesh(renderer, verts, **kw):
-    renderer.set_mesh(*X._with_surface(verts), **kw)
-
-
-def check_lists(got, ref, what):
-    """(offsets, t, tri, counts) as tensors against a reference dict, bit for bit."""
-    offsets, t, tri, counts = (x.cpu().numpy() for x in got)
-    assert counts.dtype == np.int32 and np.array_equal(counts, ref["count"]), (what, np.nonzero(counts != ref["count"])[0][:8])
-    assert offsets.dtype == np.int64 and np.array_equal(offsets, ref["offsets"]), what
-    assert t.dtype == f32 and tri.dtype == np.int32 and len(t) == len(tri)
-    assert H.same_bits(t[:ref["hits"]], ref["t"]) and np.array_equal(tri[:ref["hits"]], ref["tri"]), (what, np.nonzero(tri[:ref["hits"]] != ref["tri"])[0][:8])
-
-
 def check_case(renderer, o, d, tmax, ref, what, **kw):
     """The three ways to ask against the reference of rays (o, d, tmax): count, list without a capacity (count + fill), list with one."""
-    n, hits = len(o), ref["hits"]
-    to, td, tt = tdev(o), tdev(d), tdev(tmax)
-    counts = renderer.count_ray_hits(to, td, tt, **kw)
-    st = renderer.hit_query_stats()
-    assert np.array_equal(counts.cpu().numpy(), ref["count"]), (what, np.nonzero(counts.cpu().numpy() != ref["count"])[0][:8])
-    assert (st["rays"], st["invalid_rays"], st["hits"], st["hits_written"], st["stack_overflow"], st["launches"]) == (n, ref["invalid"], hits, 0, 0, 1) and st["ms"] > 0, (what, st)
-    got = renderer.list_ray_hits(to, td, tt, **kw)
-    st = renderer.hit_query_stats()  # of the fill step
-    assert len(got[1]) == hits
-    check_lists(got, ref, what)
-    assert (st["rays"], st["invalid_rays"], st["hits"], st["hits_written"], st["incomplete_rays"], st["slice_overflow"], st["stack_overflow"], st["launches"]) == \
-        (n, ref["invalid"], hits, hits, 0, 0, 0, 1), (what, st)
-    got = renderer.list_ray_hits(to, td, tt, capacity=hits + 3, **kw)
-    st = renderer.hit_query_stats()
-    check_lists(got, ref, what)
-    assert (st["rays"], st["invalid_rays"], st["hits"], st["hits_written"], st["incomplete_rays"], st["slice_overflow"], st["stack_overflow"], st["launches"]) == \
-        (n, ref["invalid"], hits, hits, 0, 0, 0, 5) and st["ms"] > 0, (what, st)
+    L.check_case(renderer, L.HITS, (o, d, tmax), ref, what, **kw)
 
 
 # ---- 1. every family, every tree ------------------------------------------------------------------------------------------------
@@ -162,6 +118,10 @@ def set_batch(renderer):
     return b
 
 
+def src(b):
+    return b["o"], b["d"], b["tmax"]
+
+
 def first(b, n):
     return b["o"][:n], b["d"][:n], b["tmax"][:n], H.rows(b["ref"], slice(0, n))
 
@@ -204,10 +164,7 @@ def test_the_scan_around_its_tile(renderer, n):
     """n + 1 offsets around the scan's 4 096-element tile, and several tiles."""
     b = set_batch(renderer)
     o, d, tmax, ref = scattered(b, n)
-    got = renderer.list_ray_hits(tdev(o), tdev(d), tdev(tmax), capacity=ref["hits"])
-    check_lists(got, ref, n)
-    st = renderer.hit_query_stats()
-    assert (st["rays"], st["hits"], st["hits_written"], st["incomplete_rays"], st["slice_overflow"], st["launches"]) == (n, ref["hits"], ref["hits"], 0, 0, 5), st
+    L.scan_around_its_tile(renderer, L.HITS, (o, d, tmax), ref, n)
 
 
 def test_more_rays_than_lanes(renderer):
@@ -232,111 +189,20 @@ def test_stack_spill(renderer):
 def test_capacity(renderer):
     """Capacity at the total, one below it, half of it and 0: a slice that does not fit is not touched, every other one is complete, the
     offsets are the full sums."""
-    import torch
-
     b = set_batch(renderer)
-    n, ref = b["n"], b["ref"]
-    hits, off = ref["hits"], ref["offsets"]
-    to, td, tt = tdev(b["o"]), tdev(b["d"]), tdev(b["tmax"])
-    for capacity in (hits, hits - 1, hits // 2, 0):
-        for kw in (dict(), dict(tune_max_blocks=1, tune_refill_min=1)):
-            t_buf = torch.full((capacity + 64,), -7.0, dtype=torch.float32, device=dev())
-            i_buf = torch.full((capacity + 64,), -7, dtype=torch.int32, device=dev())
-            offsets, t, tri, counts = renderer.list_ray_hits(to, td, tt, capacity=capacity, out=(None, t_buf[:capacity], i_buf[:capacity], None), **kw)
-            st = renderer.hit_query_stats()
-            fits = off[1:] <= capacity
-            written = int(off[1:][fits].max()) if fits.any() else 0  # the slices that fit are a prefix of the rays
-            incomplete = int(((ref["count"] > 0) & ~fits).sum())
-            assert np.array_equal(offsets.cpu().numpy(), off) and np.array_equal(counts.cpu().numpy(), ref["count"]), capacity
-            gt, gi = t_buf.cpu().numpy(), i_buf.cpu().numpy()
-            assert H.same_bits(gt[:written], ref["t"][:written]) and np.array_equal(gi[:written], ref["tri"][:written]), (capacity, kw)
-            assert (gt[written:] == -7.0).all() and (gi[written:] == -7).all(), (capacity, kw)
-            assert (st["hits"], st["hits_written"], st["incomplete_rays"], st["slice_overflow"], st["stack_overflow"]) == (hits, written, incomplete, 0, 0), (capacity, kw, st)
-            assert (capacity == hits) == (incomplete == 0) and (capacity > 0 or written == 0)
-    # the caller's second try: the fill step alone on the offsets it has
-    t, tri = torch.empty(hits, dtype=torch.float32, device=dev()), torch.empty(hits, dtype=torch.int32, device=dev())
-    prm = R.HitQueryParams()
-    assert R.load().rt_fill_ray_hits_device(renderer._ctx, ptr(to), ptr(td), ptr(tt), n, C.byref(prm), ptr(offsets), hits, ptr(t), ptr(tri)) == 0
-    st = renderer.hit_query_stats()  # (waits for it)
-    assert (st["hits"], st["hits_written"], st["incomplete_rays"], st["launches"]) == (hits, hits, 0, 1), st
-    check_lists((offsets, t, tri, counts), ref, "second try")
+    L.capacity(renderer, L.HITS, src(b), b["ref"])
 
 
 def test_foreign_offsets_are_safe(renderer):
     """The fill step on offsets it did not make: nothing outside [0, capacity) is written, a slice shorter than its ray's hits keeps the
     first of them, and slice_overflow counts the rest."""
-    import torch
-
-    lib = R.load()
     b = set_batch(renderer)
-    n, ref = b["n"], b["ref"]
-    hits, off, count = ref["hits"], ref["offsets"], ref["count"].astype(np.int64)
-    to, td, tt = tdev(b["o"]), tdev(b["d"]), tdev(b["tmax"])
-    guard = 4096
-    halves = off // 2
-    cases = {"halved": halves, "shifted up": off + 1000, "shifted down": off - 1000, "reversed": off[::-1].copy(), "far": off + (1 << 40),
-             "negative": -off - 1, "zeros": np.zeros(n + 1, np.int64)}
-    for name, foreign in cases.items():
-        for capacity in (hits, hits // 3):
-            t_buf = torch.full((capacity + 2 * guard,), -7.0, dtype=torch.float32, device=dev())
-            i_buf = torch.full((capacity + 2 * guard,), -7, dtype=torch.int32, device=dev())
-            fo = tdev(np.ascontiguousarray(foreign, np.int64))
-            assert lib.rt_fill_ray_hits_device(renderer._ctx, ptr(to), ptr(td), ptr(tt), n, None, ptr(fo), capacity, ptr(t_buf[guard:]), ptr(i_buf[guard:])) == 0
-            st = renderer.hit_query_stats()
-            lo, hi = foreign[:-1], foreign[1:]
-            length = np.maximum(hi - lo, 0)
-            room = np.where((lo >= 0) & (hi <= capacity), length, 0)
-            exp_t, exp_i = np.full(capacity + 2 * guard, -7.0, f32), np.full(capacity + 2 * guard, -7, np.int32)
-            keep = np.minimum(room, count)
-            src = np.repeat(off[:-1], keep) + (np.arange(keep.sum()) - np.repeat(np.cumsum(keep) - keep, keep))
-            dst = np.repeat(lo, keep) + (np.arange(keep.sum()) - np.repeat(np.cumsum(keep) - keep, keep))
-            exp_t[guard + dst], exp_i[guard + dst] = ref["t"][src], ref["tri"][src]
-            gt, gi = t_buf.cpu().numpy(), i_buf.cpu().numpy()
-            assert (gt[:guard] == -7.0).all() and (gt[guard + capacity:] == -7.0).all() and (gi[:guard] == -7).all() and (gi[guard + capacity:] == -7).all(), (name, capacity)
-            assert H.same_bits(gt, exp_t) and np.array_equal(gi, exp_i), (name, capacity)
-            beyond = int(np.maximum(count - length, 0).sum())
-            assert (st["hits"], st["hits_written"], st["slice_overflow"], st["stack_overflow"], st["launches"]) == (hits, int(keep.sum()), beyond, 0, 1), (name, capacity, st)
-            assert st["incomplete_rays"] == int(((count > 0) & (room != length)).sum()), (name, capacity, st)
-            if name in ("halved", "reversed", "negative", "zeros"):
-                assert st["slice_overflow"] > 0, name
-    # the count step's own offsets: no overflow (every other test asserts it too)
-    t_own, i_own = torch.empty(hits, dtype=torch.float32, device=dev()), torch.empty(hits, dtype=torch.int32, device=dev())
-    assert lib.rt_fill_ray_hits_device(renderer._ctx, ptr(to), ptr(td), ptr(tt), n, None, ptr(tdev(off)), hits, ptr(t_own), ptr(i_own)) == 0
-    assert renderer.hit_query_stats()["slice_overflow"] == 0
+    L.foreign_offsets(renderer, L.HITS, src(b), b["ref"])
 
 
 def test_list_is_count_then_fill(renderer):
-    import torch
-
-    lib = R.load()
     b = set_batch(renderer)
-    n, hits = b["n"], b["ref"]["hits"]
-    to, td, tt = tdev(b["o"]), tdev(b["d"]), tdev(b["tmax"])
-    new = lambda k, dt: torch.full((k,), -7, dtype=dt, device=dev())  # noqa: E731
-    for capacity in (hits, hits // 2):
-        c1, o1, t1, i1 = new(n, torch.int32), new(n + 1, torch.int64), new(capacity, torch.float32), new(capacity, torch.int32)
-        c2, o2, t2, i2 = new(n, torch.int32), new(n + 1, torch.int64), new(capacity, torch.float32), new(capacity, torch.int32)
-        prm = R.HitQueryParams(count_traversal=1)
-        assert lib.rt_list_ray_hits_device(renderer._ctx, ptr(to), ptr(td), ptr(tt), n, C.byref(prm), ptr(c1), ptr(o1), capacity, ptr(t1), ptr(i1)) == 0
-        both = renderer.hit_query_stats()
-        assert lib.rt_count_ray_hits_device(renderer._ctx, ptr(to), ptr(td), ptr(tt), n, C.byref(prm), ptr(c2), ptr(o2)) == 0
-        counted = renderer.hit_query_stats()
-        assert lib.rt_fill_ray_hits_device(renderer._ctx, ptr(to), ptr(td), ptr(tt), n, C.byref(prm), ptr(o2), capacity, ptr(t2), ptr(i2)) == 0
-        filled = renderer.hit_query_stats()
-        assert torch.equal(c1, c2) and torch.equal(o1, o2) and torch.equal(t1.view(torch.int32), t2.view(torch.int32)) and torch.equal(i1, i2)
-        assert (counted["launches"], filled["launches"], both["launches"]) == (4, 1, 5)
-        for key in ("rays", "invalid_rays", "hits"):
-            assert both[key] == counted[key] == filled[key], key
-        for key in ("hits_written", "incomplete_rays", "slice_overflow"):
-            assert both[key] == filled[key] and counted[key] == 0, key
-        for key in ("nodes_visited", "tris_tested"):  # the two walks are the same walk
-            assert counted[key] == filled[key] > 0 and both[key] == 2 * counted[key], key
-    # offsets without counts, counts without offsets
-    o3, c3 = new(n + 1, torch.int64), new(n, torch.int32)
-    assert lib.rt_count_ray_hits_device(renderer._ctx, ptr(to), ptr(td), ptr(tt), n, None, None, ptr(o3)) == 0
-    assert lib.rt_count_ray_hits_device(renderer._ctx, ptr(to), ptr(td), ptr(tt), n, None, ptr(c3), None) == 0
-    renderer.synchronize()
-    assert np.array_equal(o3.cpu().numpy(), b["ref"]["offsets"]) and np.array_equal(c3.cpu().numpy(), b["ref"]["count"])
+    L.list_is_count_then_fill(renderer, L.HITS, src(b), b["ref"])
 
 
 # ---- 4. invalid rays, bounds, refusals -------------------------------------------------------------------------------------------
@@ -392,145 +258,33 @@ def test_invalid_rays(renderer):
 
 def test_bounds_and_out_tensors(renderer):
     """Sentinels behind every output; the inputs are only read."""
-    import torch
-
     b = set_batch(renderer)
-    for n in (1, 65, b["n"]):
-        o, d, tmax, ref = first(b, n)
-        to, td, tt = tdev(o), tdev(d), tdev(tmax)
-        keep = [x.clone() for x in (to, td, tt)]
-        hits = ref["hits"]
-        c_buf = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
-        o_buf = torch.full((n + 1 + 64,), -7, dtype=torch.int64, device=dev())
-        t_buf = torch.full((hits + 64,), -7.0, dtype=torch.float32, device=dev())
-        i_buf = torch.full((hits + 64,), -7, dtype=torch.int32, device=dev())
-        got = renderer.list_ray_hits(to, td, tt, capacity=hits, out=(o_buf[:n + 1], t_buf[:hits], i_buf[:hits], c_buf[:n]))
-        assert [x.data_ptr() for x in got] == [o_buf.data_ptr(), t_buf.data_ptr() if hits else got[1].data_ptr(), i_buf.data_ptr() if hits else got[2].data_ptr(), c_buf.data_ptr()]
-        check_lists(got, ref, n)
-        assert (c_buf[n:] == -7).all() and (o_buf[n + 1:] == -7).all() and (t_buf[hits:] == -7.0).all() and (i_buf[hits:] == -7).all()
-        c_buf.fill_(-7)
-        counts = renderer.count_ray_hits(to, td, tt, out=c_buf[:n])
-        assert counts.data_ptr() == c_buf.data_ptr() and (c_buf[n:] == -7).all() and np.array_equal(counts.cpu().numpy(), ref["count"])
-        for x, y in zip((to, td, tt), keep):
-            assert torch.equal(x.view(torch.int32), y.view(torch.int32))
-    with pytest.raises(ValueError):
-        renderer.count_ray_hits(to, td, tt, out=c_buf[:n - 1])
-    with pytest.raises(ValueError):
-        renderer.list_ray_hits(to, td, tt, capacity=hits, out=(o_buf[:n], t_buf[:hits], i_buf[:hits], c_buf[:n]))
+    L.bounds_and_out_tensors(renderer, L.HITS, [(x[:3], x[3]) for x in (first(b, n) for n in (1, 65, b["n"]))])
 
 
 def test_stream_order(renderer):
     """Rays made by torch on a stream, the queries behind them on that stream without a host synchronisation, a torch reduction of the
     answers behind the queries; one synchronisation at the end.  (Halving and doubling is exact: the rays are the batch's.)"""
-    import torch
-
     b = set_batch(renderer)
-    n, ref = b["n"], b["ref"]
-    hits = ref["hits"]
-    o_half, td, tt = tdev(b["o"] * f32(0.5)), tdev(b["d"]), tdev(b["tmax"])
-    ref_c, ref_o, ref_t, ref_i = tdev(ref["count"]), tdev(ref["offsets"]), tdev(ref["t"]), tdev(ref["tri"])
-    counts = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    counts2 = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    offsets = torch.full((n + 1,), -7, dtype=torch.int64, device=dev())
-    t = torch.full((hits,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((hits,), -7, dtype=torch.int32, device=dev())
-    torch.cuda.synchronize()
-    s = torch.cuda.Stream(device=dev())
-    renderer.set_stream(s.cuda_stream)
-    try:
-        with torch.cuda.stream(s):
-            busy = torch.zeros(1 << 26, dtype=torch.float32, device=dev())
-            for _ in range(8):  # the stream has work to do when the queries are enqueued
-                busy += 1.0
-            o = o_half * 2.0
-            renderer.count_ray_hits(o, td, tt, out=counts2, sync=False)
-            renderer.list_ray_hits(o, td, tt, capacity=hits, out=(offsets, t, tri, counts), sync=False)
-            wrong = (counts != ref_c).sum() + (counts2 != ref_c).sum() + (offsets != ref_o).sum() + (t.view(torch.int32) != ref_t.view(torch.int32)).sum() + (tri != ref_i).sum()
-        s.synchronize()
-        assert int(wrong) == 0 and float(busy[0]) == 8.0
-    finally:
-        renderer.synchronize()
-        renderer.set_stream(None)
-
-
-def _segment_end(p):
-    """End address of the device allocation (caching-allocator segment) that holds `p`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= p < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
+    L.stream_order(renderer, L.HITS, src(b), b["ref"])
 
 
 def test_errors_write_nothing(renderer):
-    import torch
-
-    lib = R.load()
     b = set_batch(renderer)
     n = 1000
     o, d, tmax, ref = first(b, n)
-    cap = ref["hits"]
-    to, td, tt = tdev(o), tdev(d), tdev(tmax)
-    cnt = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    off = torch.full((n + 1,), -7, dtype=torch.int64, device=dev())
-    t = torch.full((cap,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((cap,), -7, dtype=torch.int32, device=dev())
-    good_off = tdev(ref["offsets"])
+    e = L.Refusals(renderer, L.HITS, (o, d, tmax), ref, short3=12)  # (one row short of n x 3)
     fresh = R.Renderer(0)
-    try:  # no mesh
-        assert lib.rt_count_ray_hits_device(fresh._ctx, ptr(to), ptr(td), ptr(tt), n, None, ptr(cnt), ptr(off)) == RT_ERR_STATE
-        assert lib.rt_fill_ray_hits_device(fresh._ctx, ptr(to), ptr(td), ptr(tt), n, None, ptr(good_off), cap, ptr(t), ptr(tri)) == RT_ERR_STATE
-        assert lib.rt_list_ray_hits_device(fresh._ctx, ptr(to), ptr(td), ptr(tt), n, None, ptr(cnt), ptr(off), cap, ptr(t), ptr(tri)) == RT_ERR_STATE
+    try:
+        e.every_entry(fresh._ctx, RT_ERR_STATE, "no mesh")
     finally:
         fresh.close()
-    ctx = renderer._ctx
-    host = np.zeros((n + 1, 3), np.float64)
-    hp = C.c_void_p(host.ctypes.data)
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
-    end = _segment_end(big.data_ptr())
-    short3, short1, short8, shortc = (C.c_void_p(end - k) for k in (12 * (n - 1), 4 * (n - 1), 8 * n, 4 * (cap - 1)))  # one row short of n x 3, n, n + 1 i64, capacity
-    P = R.HitQueryParams
-    bad_params = [C.byref(P(tune_refill_min=65)), C.byref(P(tune_blocks_per_cu=9)), C.byref(P(tune_lds_stack=79)), C.byref(P(count_traversal=2))]
-
-    def untouched(k):
-        renderer.synchronize()
-        assert (cnt == -7).all() and (off == -7).all() and (t == -7.0).all() and (tri == -7).all() and (big == 0).all(), k
-
-    rays = [(None, ptr(td), ptr(tt), n, None), (ptr(to), None, ptr(tt), n, None), (hp, ptr(td), ptr(tt), n, None), (ptr(to), hp, ptr(tt), n, None),
-            (ptr(to), ptr(td), hp, n, None), (short3, ptr(td), ptr(tt), n, None), (ptr(to), short3, ptr(tt), n, None), (ptr(to), ptr(td), short1, n, None),
-            (ptr(to), ptr(td), ptr(tt), (1 << 30) + 1, None)] + [(ptr(to), ptr(td), ptr(tt), n, prm) for prm in bad_params]
-    good = (ptr(to), ptr(td), ptr(tt), n, None)
-    count_calls = [r + (ptr(cnt), ptr(off)) for r in rays] + [good + x for x in ((None, None), (hp, ptr(off)), (ptr(cnt), hp), (short1, ptr(off)), (ptr(cnt), short8))]
-    for k, args in enumerate(count_calls):
-        assert lib.rt_count_ray_hits_device(ctx, *args) == RT_ERR_INVALID, k
-        untouched(("count", k))
-    fill_calls = [r + (ptr(good_off), cap, ptr(t), ptr(tri)) for r in rays] + \
-        [good + x for x in ((None, cap, ptr(t), ptr(tri)), (hp, cap, ptr(t), ptr(tri)), (short8, cap, ptr(t), ptr(tri)), (ptr(good_off), cap, None, ptr(tri)),
-                            (ptr(good_off), cap, ptr(t), None), (ptr(good_off), cap, hp, ptr(tri)), (ptr(good_off), cap, ptr(t), hp), (ptr(good_off), cap, shortc, ptr(tri)),
-                            (ptr(good_off), cap, ptr(t), shortc), (ptr(good_off), 1 << 62, ptr(t), ptr(tri)))]
-    for k, args in enumerate(fill_calls):
-        assert lib.rt_fill_ray_hits_device(ctx, *args) == RT_ERR_INVALID, k
-        untouched(("fill", k))
-    # the pair: a refusal of the SECOND step comes before the first step is enqueued
-    list_calls = [r + (ptr(cnt), ptr(off), cap, ptr(t), ptr(tri)) for r in rays] + \
-        [good + x for x in ((ptr(cnt), None, cap, ptr(t), ptr(tri)), (hp, ptr(off), cap, ptr(t), ptr(tri)), (ptr(cnt), hp, cap, ptr(t), ptr(tri)),
-                            (short1, ptr(off), cap, ptr(t), ptr(tri)), (ptr(cnt), short8, cap, ptr(t), ptr(tri)), (ptr(cnt), ptr(off), cap, None, ptr(tri)),
-                            (ptr(cnt), ptr(off), cap, ptr(t), None), (ptr(cnt), ptr(off), cap, hp, ptr(tri)), (ptr(cnt), ptr(off), cap, ptr(t), hp),
-                            (ptr(cnt), ptr(off), cap, shortc, ptr(tri)), (ptr(cnt), ptr(off), cap, ptr(t), shortc), (ptr(cnt), ptr(off), 1 << 62, ptr(t), ptr(tri)))]
-    for k, args in enumerate(list_calls):
-        assert lib.rt_list_ray_hits_device(ctx, *args) == RT_ERR_INVALID, k
-        untouched(("list", k))
-    # n = 0 is accepted, and does nothing
-    assert lib.rt_count_ray_hits_device(ctx, ptr(to), ptr(td), ptr(tt), 0, None, ptr(cnt), ptr(off)) == 0
-    assert lib.rt_count_ray_hits_device(ctx, None, None, None, 0, None, None, None) == 0
-    assert lib.rt_fill_ray_hits_device(ctx, None, None, None, 0, None, None, 0, None, None) == 0
-    assert lib.rt_list_ray_hits_device(ctx, None, None, None, 0, None, None, None, 0, None, None) == 0
-    untouched("n = 0")
-    assert len(renderer.count_ray_hits(to[:0], td[:0])) == 0
-    assert [len(x) for x in renderer.list_ray_hits(to[:0], td[:0])] == [1, 0, 0, 0] and [len(x) for x in renderer.list_ray_hits(to[:0], td[:0], capacity=5)] == [1, 5, 5, 0]
-    # the context still answers
-    check_lists(renderer.list_ray_hits(to, td, tt, capacity=cap, out=(off, t, tri, cnt)), ref, "after the refusals")
+    to, td, tt = (ptr(x) for x in e.t)
+    hp, short3, short1 = e.bp.hp, e.bp.short3, e.bp.short1
+    e.tables([(None, td, tt, n, None), (to, None, tt, n, None), (hp, td, tt, n, None), (to, hp, tt, n, None), (to, td, hp, n, None), (short3, td, tt, n, None),
+              (to, short3, tt, n, None), (to, td, short1, n, None), (to, td, tt, (1 << 30) + 1, None)] + [(to, td, tt, n, prm) for prm in e.bad_params])
+    e.nothing_to_do((e.t[0][:0], e.t[1][:0]), (e.t[0][:0], e.t[1][:0]))
+    e.still_answers()
 
 
 # ---- 5. what the rest of the process keeps ---------------------------------------------------------------------------------------
@@ -587,9 +341,7 @@ def test_rendering_and_sharing_are_undisturbed(renderer):
     kw = dict(pos=(0, 0.1, 4.0), spp=2, bounces=2, seed=3, sky=(0.2, 0.2, 0.3))
 
     def frame(r, **more):
-        rgb = r.render_pt(**kw, **more)
-        st = r.pt_stats()
-        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+        return pt_frame(r, **kw, **more)
 
     before, before_spilling = frame(renderer), frame(renderer, tune_lds_stack=1, tune_no_overlap=2)
     assert before[1][0] > 0 and before[1][3] == 0

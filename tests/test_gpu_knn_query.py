@@ -6,7 +6,6 @@ element of dist, tri and counts, padding and invalid rows included.  That refere
 query's and the closest-point reference and to float64 on the CPU (tests/test_knn_query_host.py).  The first tests run every family on
 its meshes under every k and radius; the others need ONE batch on ONE mesh whose size they can cut, tile and plant points into: family
 b's 300 points on the terrain under the ten finite radius variants and without a radius, shuffled, under k = 8."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -17,33 +16,14 @@ import neighbor_exact as NX
 import point_exact as PX
 import ray_exact as X
 import raytracing_engine_amd as R
+from gpu_query import RT_ERR_INVALID, RT_ERR_STATE, assert_untouched, bad_params, bad_pointers, busy_stream, dev, pt_frame, ptr, sentinel, still_sentinel, tdev
+from gpu_query import set_mesh_with_surface as set_mesh
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 INF = NX.INF
-RT_ERR_INVALID, RT_ERR_STATE = -1, -4
 MISS, INVALID = KX.MISS, KX.INVALID
-
-
-def dev():
-    import torch
-
-    return torch.device("cuda", 0)
-
-
-def tdev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev())
-
-
-def ptr(x):
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
-def set_mesh(renderer, verts, **kw):
-    renderer.set_mesh(*X._with_surface(verts), **kw)
 
 
 def check_rows(got, row, what):
@@ -178,8 +158,7 @@ def test_count_out_may_be_null(renderer):
     b = set_batch(renderer)
     n = b["n"]
     tp, tr = tdev(b["p"]), tdev(b["rmax"])
-    dist = torch.full((n, K), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n, K), -7, dtype=torch.int32, device=dev())
+    dist, tri = sentinel(n, torch.float32, cols=K), sentinel(n, torch.int32, cols=K)
     assert R.load().rt_query_knn_device(renderer._ctx, ptr(tp), ptr(tr), n, K, None, ptr(dist), ptr(tri), None) == 0
     st = renderer.knn_query_stats()
     assert KX.same_bits(dist.cpu().numpy(), b["row"]["dist"]) and np.array_equal(tri.cpu().numpy(), b["row"]["tri"])
@@ -300,15 +279,13 @@ def test_bounds_and_out_tensors(renderer):
         p, rmax, row = first(b, n, k)
         tp, tr = tdev(p), tdev(rmax)
         keep = [x.clone() for x in (tp, tr)]
-        d_buf = torch.full((n * k + 64,), -7.0, dtype=torch.float32, device=dev())
-        i_buf = torch.full((n * k + 64,), -7, dtype=torch.int32, device=dev())
-        c_buf = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
+        d_buf, i_buf, c_buf = sentinel(n * k, torch.float32, 64), sentinel(n * k, torch.int32, 64), sentinel(n, torch.int32, 64)
         out = (d_buf[:n * k].view(n, k), i_buf[:n * k].view(n, k), c_buf[:n])
         for again in range(2):  # reuse: the second call overwrites the first's answers with the same
             got = renderer.query_knn(tp, k, rmax=tr, out=out, **(dict(tune_max_blocks=1) if again else {}))
             assert [x.data_ptr() for x in got] == [d_buf.data_ptr(), i_buf.data_ptr(), c_buf.data_ptr()]
             check_rows(got, row, (n, k, again))
-            assert (d_buf[n * k:] == -7.0).all() and (i_buf[n * k:] == -7).all() and (c_buf[n:] == -7).all(), (n, k)
+            assert still_sentinel(d_buf, 0, n * k) and still_sentinel(i_buf, 0, n * k) and still_sentinel(c_buf, 0, n), (n, k)
             for x, y in zip((tp, tr), keep):
                 assert torch.equal(x.view(torch.int32), y.view(torch.int32))
     with pytest.raises(ValueError):
@@ -326,35 +303,12 @@ def test_stream_order(renderer):
     n, row = b["n"], b["row"]
     p_half, tr = tdev(b["p"] * f32(0.5)), tdev(b["rmax"])
     ref_c, ref_d, ref_i = tdev(row["count"]), tdev(row["dist"]), tdev(row["tri"])
-    counts = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    dist = torch.full((n, K), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n, K), -7, dtype=torch.int32, device=dev())
-    torch.cuda.synchronize()
-    s = torch.cuda.Stream(device=dev())
-    renderer.set_stream(s.cuda_stream)
-    try:
-        with torch.cuda.stream(s):
-            busy = torch.zeros(1 << 26, dtype=torch.float32, device=dev())
-            for _ in range(8):  # the stream has work to do when the query is enqueued
-                busy += 1.0
-            p = p_half * 2.0
-            renderer.query_knn(p, K, rmax=tr, out=(dist, tri, counts), sync=False)
-            wrong = (counts != ref_c).sum() + (dist.view(torch.int32) != ref_d.view(torch.int32)).sum() + (tri != ref_i).sum()
-        s.synchronize()
-        assert int(wrong) == 0 and float(busy[0]) == 8.0
-    finally:
-        renderer.synchronize()
-        renderer.set_stream(None)
-
-
-def _segment_end(p):
-    """End address of the device allocation (caching-allocator segment) that holds `p`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= p < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
+    counts, dist, tri = sentinel(n, torch.int32), sentinel(n, torch.float32, cols=K), sentinel(n, torch.int32, cols=K)
+    with busy_stream(renderer):
+        p = p_half * 2.0
+        renderer.query_knn(p, K, rmax=tr, out=(dist, tri, counts), sync=False)
+        wrong = (counts != ref_c).sum() + (dist.view(torch.int32) != ref_d.view(torch.int32)).sum() + (tri != ref_i).sum()
+    assert int(wrong) == 0
 
 
 def test_errors_write_nothing(renderer):
@@ -365,32 +319,24 @@ def test_errors_write_nothing(renderer):
     n = 1000
     p, rmax, row = first(b, n)
     tp, tr = tdev(p), tdev(rmax)
-    cnt = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    dist = torch.full((n, K), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n, K), -7, dtype=torch.int32, device=dev())
+    cnt, dist, tri = sentinel(n, torch.int32), sentinel(n, torch.float32, cols=K), sentinel(n, torch.int32, cols=K)
     fresh = R.Renderer(0)
     try:  # no mesh
         assert lib.rt_query_knn_device(fresh._ctx, ptr(tp), ptr(tr), n, K, None, ptr(dist), ptr(tri), ptr(cnt)) == RT_ERR_STATE
     finally:
         fresh.close()
     ctx = renderer._ctx
-    host = np.zeros((n * K + 1, 3), np.float64)
-    hp = C.c_void_p(host.ctypes.data)
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
-    end = _segment_end(big.data_ptr())
-    short3, short1, shortk = (C.c_void_p(end - x) for x in (12 * (n - 1), 4 * (n - 1), 4 * (n * K - 1)))  # one row short of n x 3 and n, one element short of n x k
-    P = R.KnnQueryParams
-    bad_params = [C.byref(P(tune_refill_min=65)), C.byref(P(tune_blocks_per_cu=9)), C.byref(P(tune_lds_stack=79)), C.byref(P(count_traversal=2))]
+    bp = bad_pointers(n, short3=12, short1=4, shortk=(4, n * K))  # one row short of n x 3 and n, one element short of n x k
+    hp, short3, short1, shortk = bp.hp, bp.short3, bp.short1, bp.shortk
 
     def untouched(what):
-        renderer.synchronize()
-        assert (cnt == -7).all() and (dist == -7.0).all() and (tri == -7).all() and (big == 0).all(), what
+        assert_untouched(renderer, (cnt, dist, tri), bp.big, what)
 
     outs = (ptr(dist), ptr(tri), ptr(cnt))
     calls = [(None, ptr(tr), n, K, None) + outs, (hp, ptr(tr), n, K, None) + outs, (ptr(tp), hp, n, K, None) + outs, (short3, ptr(tr), n, K, None) + outs,
              (ptr(tp), short1, n, K, None) + outs, (short3, None, n, K, None) + outs, (ptr(tp), ptr(tr), (1 << 30) + 1, K, None) + outs,
              (ptr(tp), ptr(tr), n, 0, None) + outs, (ptr(tp), ptr(tr), n, 1025, None) + outs, (ptr(tp), ptr(tr), n, 0xffffffff, None) + outs,]
-    calls += [(ptr(tp), ptr(tr), n, K, prm) + outs for prm in bad_params]
+    calls += [(ptr(tp), ptr(tr), n, K, prm) + outs for prm in bad_params(R.KnnQueryParams)]
     good = (ptr(tp), ptr(tr), n, K, None)
     calls += [good + x for x in ((None, ptr(tri), ptr(cnt)), (ptr(dist), None, ptr(cnt)), (hp, ptr(tri), ptr(cnt)), (ptr(dist), hp, ptr(cnt)), (ptr(dist), ptr(tri), hp),
                                  (shortk, ptr(tri), ptr(cnt)), (ptr(dist), shortk, ptr(cnt)), (ptr(dist), ptr(tri), short1))]
@@ -463,9 +409,7 @@ def test_rendering_and_sharing_are_undisturbed(renderer):
     kw = dict(pos=(0, 30.0, 40.0), spp=2, bounces=2, seed=3, sky=(0.2, 0.2, 0.3))
 
     def frame(r, **more):
-        rgb = r.render_pt(**kw, **more)
-        st = r.pt_stats()
-        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+        return pt_frame(r, **kw, **more)
 
     before, before_spilling = frame(renderer), frame(renderer, tune_lds_stack=1, tune_no_overlap=2)
     assert before[1][0] > 0 and before[1][3] == 0

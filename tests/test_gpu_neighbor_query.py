@@ -7,79 +7,37 @@ offsets and every list entry; its tree walk under the kernel's culling rule give
 That reference in turn is held to its own walk, to the closest-point reference and to float64 on the CPU
 (tests/test_neighbor_query_host.py).  The first tests run every family on its meshes under every radius; the others need ONE batch on
 ONE mesh whose size they can cut, tile and plant points into: family b's 300 points on the terrain under the ten finite radius
-variants, shuffled."""
+variants, shuffled.  The listing protocol's tests are tests/gpu_listing.py's, on this batch."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+import gpu_listing as L
 import neighbor_exact as NX
 import point_exact as PX
 import ray_exact as X
 import raytracing_engine_amd as R
+from gpu_query import RT_ERR_STATE, dev, pt_frame, ptr, tdev
+from gpu_query import set_mesh_with_surface as set_mesh
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 INF = NX.INF
-RT_ERR_INVALID, RT_ERR_STATE = -1, -4
 INVALID = NX.INVALID
-
-
-def dev():
-    import torch
-
-    return torch.device("cuda", 0)
-
-
-def tdev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev())
-
-
-def ptr(x):
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
-def set_mesh(renderer, verts, **kw):
-    renderer.set_mesh(*X._with_surface(verts), **kw)
 
 
 def check_lists(got, ref, what):
     """(offsets, dist, tri, counts) as tensors against a reference dict, bit for bit."""
-    offsets, dist, tri, counts = (x.cpu().numpy() for x in got)
-    assert counts.dtype == np.int32 and np.array_equal(counts, ref["count"]), (what, np.nonzero(counts != ref["count"])[0][:8])
-    assert offsets.dtype == np.int64 and np.array_equal(offsets, ref["offsets"]), what
-    assert dist.dtype == f32 and tri.dtype == np.int32 and len(dist) == len(tri)
-    k = ref["neighbors"]
-    assert NX.same_bits(dist[:k], ref["dist"]) and np.array_equal(tri[:k], ref["tri"]), (what, np.nonzero(tri[:k] != ref["tri"])[0][:8])
+    L.check_lists(L.NEIGHBORS, got, ref, what)
 
 
 def check_case(renderer, p, rmax, ref, what, exact_work=False, **kw):
     """The three ways to ask against the reference of points p under radii rmax: count, list without a capacity (count + fill), list with
     one.  exact_work: the tree is the host-built single-level one, whose walk the reference has made: nodes and triangles agree exactly."""
-    n, k = len(p), ref["neighbors"]
-    tp, tr = tdev(p), tdev(rmax)
-    counts = renderer.count_neighbors(tp, tr, count_traversal=True, **kw)
-    st = renderer.neighbor_query_stats()
-    assert np.array_equal(counts.cpu().numpy(), ref["count"]), (what, np.nonzero(counts.cpu().numpy() != ref["count"])[0][:8])
-    assert (st["points"], st["invalid_points"], st["neighbors"], st["neighbors_written"], st["stack_overflow"], st["launches"]) == (n, ref["invalid"], k, 0, 0, 1) \
-        and st["ms"] > 0, (what, st)
-    if exact_work:  # the bound is fixed, so the work does not depend on the order of the walk
-        assert (st["nodes_visited"], st["tris_tested"]) == (ref["nodes_total"], ref["tris_total"]), (what, st, ref["nodes_total"], ref["tris_total"])
-    got = renderer.list_neighbors(tp, tr, **kw)
-    st = renderer.neighbor_query_stats()  # of the fill step
-    assert len(got[1]) == k
-    check_lists(got, ref, what)
-    assert (st["points"], st["invalid_points"], st["neighbors"], st["neighbors_written"], st["incomplete_points"], st["slice_overflow"], st["stack_overflow"],
-            st["launches"], st["nodes_visited"]) == (n, ref["invalid"], k, k, 0, 0, 0, 1, 0), (what, st)
-    got = renderer.list_neighbors(tp, tr, capacity=k + 3, **kw)
-    st = renderer.neighbor_query_stats()
-    check_lists(got, ref, what)
-    assert (st["points"], st["invalid_points"], st["neighbors"], st["neighbors_written"], st["incomplete_points"], st["slice_overflow"], st["stack_overflow"],
-            st["launches"]) == (n, ref["invalid"], k, k, 0, 0, 0, 5) and st["ms"] > 0, (what, st)
+    L.check_case(renderer, L.NEIGHBORS, (p, rmax), ref, what, exact_work=exact_work, **kw)
 
 
 # ---- 1. every family, every radius, every tree ------------------------------------------------------------------------------------
@@ -177,6 +135,10 @@ def set_batch(renderer):
     return b
 
 
+def src(b):
+    return b["p"], b["rmax"]
+
+
 def first(b, n):
     return b["p"][:n], b["rmax"][:n], NX.rows(b["ref"], slice(0, n))
 
@@ -220,11 +182,7 @@ def test_the_scan_around_its_tile(renderer, n):
     """n + 1 = 4 095, 4 096, 4 097 offsets: around the scan's 4 096-element tile."""
     b = set_batch(renderer)
     p, rmax, ref = scattered(b, n)
-    got = renderer.list_neighbors(tdev(p), tdev(rmax), capacity=ref["neighbors"])
-    check_lists(got, ref, n)
-    st = renderer.neighbor_query_stats()
-    assert (st["points"], st["neighbors"], st["neighbors_written"], st["incomplete_points"], st["slice_overflow"], st["launches"]) == \
-        (n, ref["neighbors"], ref["neighbors"], 0, 0, 5), st
+    L.scan_around_its_tile(renderer, L.NEIGHBORS, (p, rmax), ref, n)
 
 
 def test_more_points_than_lanes(renderer):
@@ -252,110 +210,20 @@ def test_stack_spill(renderer):
 def test_capacity(renderer):
     """Capacity at the total, one below it, half of it and 0: a slice that does not fit is not touched, every other one is complete, the
     offsets are the full sums."""
-    import torch
-
     b = set_batch(renderer)
-    n, ref = b["n"], b["ref"]
-    total, off = ref["neighbors"], ref["offsets"]
-    tp, tr = tdev(b["p"]), tdev(b["rmax"])
-    for capacity in (total, total - 1, total // 2, 0):
-        for kw in (dict(), dict(tune_max_blocks=1, tune_refill_min=1)):
-            d_buf = torch.full((capacity + 64,), -7.0, dtype=torch.float32, device=dev())
-            i_buf = torch.full((capacity + 64,), -7, dtype=torch.int32, device=dev())
-            offsets, dist, tri, counts = renderer.list_neighbors(tp, tr, capacity=capacity, out=(None, d_buf[:capacity], i_buf[:capacity], None), **kw)
-            st = renderer.neighbor_query_stats()
-            fits = off[1:] <= capacity
-            written = int(off[1:][fits].max()) if fits.any() else 0  # the slices that fit are a prefix of the points
-            incomplete = int(((ref["count"] > 0) & ~fits).sum())
-            assert np.array_equal(offsets.cpu().numpy(), off) and np.array_equal(counts.cpu().numpy(), ref["count"]), capacity
-            gd, gi = d_buf.cpu().numpy(), i_buf.cpu().numpy()
-            assert NX.same_bits(gd[:written], ref["dist"][:written]) and np.array_equal(gi[:written], ref["tri"][:written]), (capacity, kw)
-            assert (gd[written:] == -7.0).all() and (gi[written:] == -7).all(), (capacity, kw)
-            assert (st["neighbors"], st["neighbors_written"], st["incomplete_points"], st["slice_overflow"], st["stack_overflow"]) == (total, written, incomplete, 0, 0), (capacity, kw, st)
-            assert (capacity == total) == (incomplete == 0) and (capacity > 0 or written == 0)
-    # the caller's second try: the fill step alone on the offsets it has
-    dist, tri = torch.empty(total, dtype=torch.float32, device=dev()), torch.empty(total, dtype=torch.int32, device=dev())
-    prm = R.NeighborQueryParams()
-    assert R.load().rt_fill_neighbors_device(renderer._ctx, ptr(tp), ptr(tr), 0.0, n, C.byref(prm), ptr(offsets), total, ptr(dist), ptr(tri)) == 0
-    st = renderer.neighbor_query_stats()  # (waits for it)
-    assert (st["neighbors"], st["neighbors_written"], st["incomplete_points"], st["launches"]) == (total, total, 0, 1), st
-    check_lists((offsets, dist, tri, counts), ref, "second try")
+    L.capacity(renderer, L.NEIGHBORS, src(b), b["ref"])
 
 
 def test_foreign_offsets_are_safe(renderer):
     """The fill step on offsets it did not make: nothing outside [0, capacity) is written, a slice shorter than its point's list keeps the
     first entries, and slice_overflow counts the rest."""
-    import torch
-
-    lib = R.load()
     b = set_batch(renderer)
-    n, ref = b["n"], b["ref"]
-    total, off, count = ref["neighbors"], ref["offsets"], ref["count"].astype(np.int64)
-    tp, tr = tdev(b["p"]), tdev(b["rmax"])
-    guard = 4096
-    cases = {"halved": off // 2, "shifted up": off + 1000, "shifted down": off - 1000, "reversed": off[::-1].copy(), "far": off + (1 << 40),
-             "negative": -off - 1, "zeros": np.zeros(n + 1, np.int64)}
-    for name, foreign in cases.items():
-        for capacity in (total, total // 3):
-            d_buf = torch.full((capacity + 2 * guard,), -7.0, dtype=torch.float32, device=dev())
-            i_buf = torch.full((capacity + 2 * guard,), -7, dtype=torch.int32, device=dev())
-            fo = tdev(np.ascontiguousarray(foreign, np.int64))
-            assert lib.rt_fill_neighbors_device(renderer._ctx, ptr(tp), ptr(tr), 0.0, n, None, ptr(fo), capacity, ptr(d_buf[guard:]), ptr(i_buf[guard:])) == 0
-            st = renderer.neighbor_query_stats()
-            lo, hi = foreign[:-1], foreign[1:]
-            length = np.maximum(hi - lo, 0)
-            room = np.where((lo >= 0) & (hi <= capacity), length, 0)
-            exp_d, exp_i = np.full(capacity + 2 * guard, -7.0, f32), np.full(capacity + 2 * guard, -7, np.int32)
-            keep = np.minimum(room, count)
-            src = np.repeat(off[:-1], keep) + (np.arange(keep.sum()) - np.repeat(np.cumsum(keep) - keep, keep))
-            dst = np.repeat(lo, keep) + (np.arange(keep.sum()) - np.repeat(np.cumsum(keep) - keep, keep))
-            gd, gi = d_buf.cpu().numpy(), i_buf.cpu().numpy()
-            assert (gd[:guard] == -7.0).all() and (gd[guard + capacity:] == -7.0).all() and (gi[:guard] == -7).all() and (gi[guard + capacity:] == -7).all(), (name, capacity)
-            exp_d[guard + dst], exp_i[guard + dst] = ref["dist"][src], ref["tri"][src]
-            assert NX.same_bits(gd, exp_d) and np.array_equal(gi, exp_i), (name, capacity)
-            beyond = int(np.maximum(count - length, 0).sum())
-            assert (st["neighbors"], st["neighbors_written"], st["slice_overflow"], st["stack_overflow"], st["launches"]) == (total, int(keep.sum()), beyond, 0, 1), (name, capacity, st)
-            assert st["incomplete_points"] == int(((count > 0) & (room != length)).sum()), (name, capacity, st)
-            if name in ("halved", "reversed", "negative", "zeros"):
-                assert st["slice_overflow"] > 0, name
-    # the count step's own offsets: no overflow (every other test asserts it too)
-    d_own, i_own = torch.empty(total, dtype=torch.float32, device=dev()), torch.empty(total, dtype=torch.int32, device=dev())
-    assert lib.rt_fill_neighbors_device(renderer._ctx, ptr(tp), ptr(tr), 0.0, n, None, ptr(tdev(off)), total, ptr(d_own), ptr(i_own)) == 0
-    assert renderer.neighbor_query_stats()["slice_overflow"] == 0
+    L.foreign_offsets(renderer, L.NEIGHBORS, src(b), b["ref"])
 
 
 def test_list_is_count_then_fill(renderer):
-    import torch
-
-    lib = R.load()
     b = set_batch(renderer)
-    n, total = b["n"], b["ref"]["neighbors"]
-    tp, tr = tdev(b["p"]), tdev(b["rmax"])
-    new = lambda k, dt: torch.full((k,), -7, dtype=dt, device=dev())  # noqa: E731
-    for capacity in (total, total // 2):
-        c1, o1, d1, i1 = new(n, torch.int32), new(n + 1, torch.int64), new(capacity, torch.float32), new(capacity, torch.int32)
-        c2, o2, d2, i2 = new(n, torch.int32), new(n + 1, torch.int64), new(capacity, torch.float32), new(capacity, torch.int32)
-        prm = R.NeighborQueryParams(count_traversal=1)
-        assert lib.rt_list_neighbors_device(renderer._ctx, ptr(tp), ptr(tr), 0.0, n, C.byref(prm), ptr(c1), ptr(o1), capacity, ptr(d1), ptr(i1)) == 0
-        both = renderer.neighbor_query_stats()
-        assert lib.rt_count_neighbors_device(renderer._ctx, ptr(tp), ptr(tr), 0.0, n, C.byref(prm), ptr(c2), ptr(o2)) == 0
-        counted = renderer.neighbor_query_stats()
-        assert lib.rt_fill_neighbors_device(renderer._ctx, ptr(tp), ptr(tr), 0.0, n, C.byref(prm), ptr(o2), capacity, ptr(d2), ptr(i2)) == 0
-        filled = renderer.neighbor_query_stats()
-        assert torch.equal(c1, c2) and torch.equal(o1, o2) and torch.equal(d1.view(torch.int32), d2.view(torch.int32)) and torch.equal(i1, i2)
-        assert (counted["launches"], filled["launches"], both["launches"]) == (4, 1, 5)
-        for key in ("points", "invalid_points", "neighbors"):
-            assert both[key] == counted[key] == filled[key], key
-        for key in ("neighbors_written", "incomplete_points", "slice_overflow"):
-            assert both[key] == filled[key] and counted[key] == 0, key
-        for key in ("nodes_visited", "tris_tested"):  # the two walks are the same walk
-            assert counted[key] == filled[key] > 0 and both[key] == 2 * counted[key], key
-    # offsets without counts, counts without offsets
-    o3, c3 = new(n + 1, torch.int64), new(n, torch.int32)
-    assert lib.rt_count_neighbors_device(renderer._ctx, ptr(tp), ptr(tr), 0.0, n, None, None, ptr(o3)) == 0
-    assert lib.rt_count_neighbors_device(renderer._ctx, ptr(tp), ptr(tr), 0.0, n, None, ptr(c3), None) == 0
-    renderer.synchronize()
-    assert np.array_equal(o3.cpu().numpy(), b["ref"]["offsets"]) and np.array_equal(c3.cpu().numpy(), b["ref"]["count"])
+    L.list_is_count_then_fill(renderer, L.NEIGHBORS, src(b), b["ref"])
 
 
 # ---- 4. invalid points, bounds, refusals -------------------------------------------------------------------------------------------
@@ -410,144 +278,33 @@ def test_invalid_points(renderer):
 
 def test_bounds_and_out_tensors(renderer):
     """Sentinels behind every output; the inputs are only read."""
-    import torch
-
     b = set_batch(renderer)
-    for n in (1, 65, b["n"]):
-        p, rmax, ref = first(b, n)
-        tp, tr = tdev(p), tdev(rmax)
-        keep = [x.clone() for x in (tp, tr)]
-        k = ref["neighbors"]
-        c_buf = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
-        o_buf = torch.full((n + 1 + 64,), -7, dtype=torch.int64, device=dev())
-        d_buf = torch.full((k + 64,), -7.0, dtype=torch.float32, device=dev())
-        i_buf = torch.full((k + 64,), -7, dtype=torch.int32, device=dev())
-        got = renderer.list_neighbors(tp, tr, capacity=k, out=(o_buf[:n + 1], d_buf[:k], i_buf[:k], c_buf[:n]))
-        assert [x.data_ptr() for x in got] == [o_buf.data_ptr(), d_buf.data_ptr() if k else got[1].data_ptr(), i_buf.data_ptr() if k else got[2].data_ptr(), c_buf.data_ptr()]
-        check_lists(got, ref, n)
-        assert (c_buf[n:] == -7).all() and (o_buf[n + 1:] == -7).all() and (d_buf[k:] == -7.0).all() and (i_buf[k:] == -7).all()
-        c_buf.fill_(-7)
-        counts = renderer.count_neighbors(tp, tr, out=c_buf[:n])
-        assert counts.data_ptr() == c_buf.data_ptr() and (c_buf[n:] == -7).all() and np.array_equal(counts.cpu().numpy(), ref["count"])
-        for x, y in zip((tp, tr), keep):
-            assert torch.equal(x.view(torch.int32), y.view(torch.int32))
-    with pytest.raises(ValueError):
-        renderer.count_neighbors(tp, tr, out=c_buf[:n - 1])
-    with pytest.raises(ValueError):
-        renderer.list_neighbors(tp, tr, capacity=k, out=(o_buf[:n], d_buf[:k], i_buf[:k], c_buf[:n]))
+    L.bounds_and_out_tensors(renderer, L.NEIGHBORS, [(x[:2], x[2]) for x in (first(b, n) for n in (1, 65, b["n"]))])
 
 
 def test_stream_order(renderer):
     """Points made by torch on a stream, the queries behind them on that stream without a host synchronisation, a torch reduction of the
     answers behind the queries; one synchronisation at the end.  (Halving and doubling is exact: the points are the batch's.)"""
-    import torch
-
     b = set_batch(renderer)
-    n, ref = b["n"], b["ref"]
-    k = ref["neighbors"]
-    p_half, tr = tdev(b["p"] * f32(0.5)), tdev(b["rmax"])
-    ref_c, ref_o, ref_d, ref_i = tdev(ref["count"]), tdev(ref["offsets"]), tdev(ref["dist"]), tdev(ref["tri"])
-    counts = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    counts2 = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    offsets = torch.full((n + 1,), -7, dtype=torch.int64, device=dev())
-    dist = torch.full((k,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((k,), -7, dtype=torch.int32, device=dev())
-    torch.cuda.synchronize()
-    s = torch.cuda.Stream(device=dev())
-    renderer.set_stream(s.cuda_stream)
-    try:
-        with torch.cuda.stream(s):
-            busy = torch.zeros(1 << 26, dtype=torch.float32, device=dev())
-            for _ in range(8):  # the stream has work to do when the queries are enqueued
-                busy += 1.0
-            p = p_half * 2.0
-            renderer.count_neighbors(p, tr, out=counts2, sync=False)
-            renderer.list_neighbors(p, tr, capacity=k, out=(offsets, dist, tri, counts), sync=False)
-            wrong = (counts != ref_c).sum() + (counts2 != ref_c).sum() + (offsets != ref_o).sum() + (dist.view(torch.int32) != ref_d.view(torch.int32)).sum() + (tri != ref_i).sum()
-        s.synchronize()
-        assert int(wrong) == 0 and float(busy[0]) == 8.0
-    finally:
-        renderer.synchronize()
-        renderer.set_stream(None)
-
-
-def _segment_end(p):
-    """End address of the device allocation (caching-allocator segment) that holds `p`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= p < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
+    L.stream_order(renderer, L.NEIGHBORS, src(b), b["ref"])
 
 
 def test_errors_write_nothing(renderer):
-    import torch
-
-    lib = R.load()
     b = set_batch(renderer)
     n = 1000
     p, rmax, ref = first(b, n)
-    cap = ref["neighbors"]
-    tp, tr = tdev(p), tdev(rmax)
-    cnt = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    off = torch.full((n + 1,), -7, dtype=torch.int64, device=dev())
-    dist = torch.full((cap,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((cap,), -7, dtype=torch.int32, device=dev())
-    good_off = tdev(ref["offsets"])
+    e = L.Refusals(renderer, L.NEIGHBORS, (p, rmax), ref, short3=12)  # (one row short of n x 3)
     fresh = R.Renderer(0)
-    try:  # no mesh
-        assert lib.rt_count_neighbors_device(fresh._ctx, ptr(tp), ptr(tr), 0.0, n, None, ptr(cnt), ptr(off)) == RT_ERR_STATE
-        assert lib.rt_fill_neighbors_device(fresh._ctx, ptr(tp), ptr(tr), 0.0, n, None, ptr(good_off), cap, ptr(dist), ptr(tri)) == RT_ERR_STATE
-        assert lib.rt_list_neighbors_device(fresh._ctx, ptr(tp), ptr(tr), 0.0, n, None, ptr(cnt), ptr(off), cap, ptr(dist), ptr(tri)) == RT_ERR_STATE
+    try:
+        e.every_entry(fresh._ctx, RT_ERR_STATE, "no mesh")
     finally:
         fresh.close()
-    ctx = renderer._ctx
-    host = np.zeros((n + 1, 3), np.float64)
-    hp = C.c_void_p(host.ctypes.data)
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
-    end = _segment_end(big.data_ptr())
-    short3, short1, short8, shortc = (C.c_void_p(end - k) for k in (12 * (n - 1), 4 * (n - 1), 8 * n, 4 * (cap - 1)))  # one row short of n x 3, n, n + 1 i64, capacity
-    P = R.NeighborQueryParams
-    bad_params = [C.byref(P(tune_refill_min=65)), C.byref(P(tune_blocks_per_cu=9)), C.byref(P(tune_lds_stack=79)), C.byref(P(count_traversal=2))]
-
-    def untouched(k):
-        renderer.synchronize()
-        assert (cnt == -7).all() and (off == -7).all() and (dist == -7.0).all() and (tri == -7).all() and (big == 0).all(), k
-
-    points = [(None, ptr(tr), 0.0, n, None), (hp, ptr(tr), 0.0, n, None), (ptr(tp), hp, 0.0, n, None), (short3, ptr(tr), 0.0, n, None), (ptr(tp), short1, 0.0, n, None),
-              (short3, None, 1.0, n, None), (ptr(tp), ptr(tr), 0.0, (1 << 30) + 1, None)] + [(ptr(tp), ptr(tr), 0.0, n, prm) for prm in bad_params]
-    good = (ptr(tp), ptr(tr), 0.0, n, None)
-    count_calls = [r + (ptr(cnt), ptr(off)) for r in points] + [good + x for x in ((None, None), (hp, ptr(off)), (ptr(cnt), hp), (short1, ptr(off)), (ptr(cnt), short8))]
-    for k, args in enumerate(count_calls):
-        assert lib.rt_count_neighbors_device(ctx, *args) == RT_ERR_INVALID, k
-        untouched(("count", k))
-    fill_calls = [r + (ptr(good_off), cap, ptr(dist), ptr(tri)) for r in points] + \
-        [good + x for x in ((None, cap, ptr(dist), ptr(tri)), (hp, cap, ptr(dist), ptr(tri)), (short8, cap, ptr(dist), ptr(tri)), (ptr(good_off), cap, None, ptr(tri)),
-                            (ptr(good_off), cap, ptr(dist), None), (ptr(good_off), cap, hp, ptr(tri)), (ptr(good_off), cap, ptr(dist), hp), (ptr(good_off), cap, shortc, ptr(tri)),
-                            (ptr(good_off), cap, ptr(dist), shortc), (ptr(good_off), 1 << 62, ptr(dist), ptr(tri)))]
-    for k, args in enumerate(fill_calls):
-        assert lib.rt_fill_neighbors_device(ctx, *args) == RT_ERR_INVALID, k
-        untouched(("fill", k))
-    # the pair: a refusal of the SECOND step comes before the first step is enqueued
-    list_calls = [r + (ptr(cnt), ptr(off), cap, ptr(dist), ptr(tri)) for r in points] + \
-        [good + x for x in ((ptr(cnt), None, cap, ptr(dist), ptr(tri)), (hp, ptr(off), cap, ptr(dist), ptr(tri)), (ptr(cnt), hp, cap, ptr(dist), ptr(tri)),
-                            (short1, ptr(off), cap, ptr(dist), ptr(tri)), (ptr(cnt), short8, cap, ptr(dist), ptr(tri)), (ptr(cnt), ptr(off), cap, None, ptr(tri)),
-                            (ptr(cnt), ptr(off), cap, ptr(dist), None), (ptr(cnt), ptr(off), cap, hp, ptr(tri)), (ptr(cnt), ptr(off), cap, ptr(dist), hp),
-                            (ptr(cnt), ptr(off), cap, shortc, ptr(tri)), (ptr(cnt), ptr(off), cap, ptr(dist), shortc), (ptr(cnt), ptr(off), 1 << 62, ptr(dist), ptr(tri)))]
-    for k, args in enumerate(list_calls):
-        assert lib.rt_list_neighbors_device(ctx, *args) == RT_ERR_INVALID, k
-        untouched(("list", k))
-    # n = 0 is accepted, and does nothing
-    assert lib.rt_count_neighbors_device(ctx, ptr(tp), ptr(tr), 0.0, 0, None, ptr(cnt), ptr(off)) == 0
-    assert lib.rt_count_neighbors_device(ctx, None, None, 1.0, 0, None, None, None) == 0
-    assert lib.rt_fill_neighbors_device(ctx, None, None, 1.0, 0, None, None, 0, None, None) == 0
-    assert lib.rt_list_neighbors_device(ctx, None, None, 1.0, 0, None, None, None, 0, None, None) == 0
-    untouched("n = 0")
-    assert len(renderer.count_neighbors(tp[:0], 1.0)) == 0
-    assert [len(x) for x in renderer.list_neighbors(tp[:0], 1.0)] == [1, 0, 0, 0] and [len(x) for x in renderer.list_neighbors(tp[:0], tr[:0], capacity=5)] == [1, 5, 5, 0]
-    # the context still answers
-    check_lists(renderer.list_neighbors(tp, tr, capacity=cap, out=(off, dist, tri, cnt)), ref, "after the refusals")
+    tp, tr = (ptr(x) for x in e.t)
+    hp, short3, short1 = e.bp.hp, e.bp.short3, e.bp.short1
+    e.tables([(None, tr, 0.0, n, None), (hp, tr, 0.0, n, None), (tp, hp, 0.0, n, None), (short3, tr, 0.0, n, None), (tp, short1, 0.0, n, None),
+              (short3, None, 1.0, n, None), (tp, tr, 0.0, (1 << 30) + 1, None)] + [(tp, tr, 0.0, n, prm) for prm in e.bad_params])
+    e.nothing_to_do((e.t[0][:0], 1.0), (e.t[0][:0], e.t[1][:0]))
+    e.still_answers()
 
 
 # ---- 5. what the rest of the process keeps ---------------------------------------------------------------------------------------
@@ -609,9 +366,7 @@ def test_rendering_and_sharing_are_undisturbed(renderer):
     kw = dict(pos=(0, 30.0, 40.0), spp=2, bounces=2, seed=3, sky=(0.2, 0.2, 0.3))
 
     def frame(r, **more):
-        rgb = r.render_pt(**kw, **more)
-        st = r.pt_stats()
-        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+        return pt_frame(r, **kw, **more)
 
     before, before_spilling = frame(renderer), frame(renderer, tune_lds_stack=1, tune_no_overlap=2)
     assert before[1][0] > 0 and before[1][3] == 0

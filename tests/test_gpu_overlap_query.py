@@ -6,79 +6,37 @@ over all pairs, no tree), which the kernel must match bit for bit in counts, off
 culling rule gives the nodes and records the kernel must count, exactly.  That reference in turn is held to its own walk, to answers
 computed by hand, to the all-hits reference and to float64 on the CPU (tests/test_overlap_query_host.py).  The first tests run every
 family on its meshes; the others need ONE batch on ONE mesh whose size they can cut: 600 query triangles of families a, b and c on the
-terrain, shuffled."""
-import ctypes as C
+terrain, shuffled.  The listing protocol's tests are tests/gpu_listing.py's, on this batch."""
 import functools
 
 import numpy as np
 import pytest
 
+import gpu_listing as L
+import gpu_query as Q
 import overlap_exact as OX
 import point_exact as PX
 import ray_exact as X
 import raytracing_engine_amd as R
+from gpu_query import RT_ERR_INVALID, RT_ERR_STATE, dev, ptr, tdev
+from gpu_query import set_mesh_with_surface as set_mesh
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-RT_ERR_INVALID, RT_ERR_STATE = -1, -4
 INVALID = OX.INVALID
-
-
-def dev():
-    import torch
-
-    return torch.device("cuda", 0)
-
-
-def tdev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev())
-
-
-def ptr(x):
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
-def set_mesh(renderer, verts, **kw):
-    renderer.set_mesh(*X._with_surface(verts), **kw)
 
 
 def check_lists(got, ref, what):
     """(offsets, tri, edges, counts) as tensors against a reference dict, bit for bit."""
-    offsets, tri, edges, counts = (x.cpu().numpy() for x in got)
-    assert counts.dtype == np.int32 and np.array_equal(counts, ref["count"]), (what, np.nonzero(counts != ref["count"])[0][:8])
-    assert offsets.dtype == np.int64 and np.array_equal(offsets, ref["offsets"]), what
-    assert tri.dtype == np.int32 and edges.dtype == np.int32 and len(tri) == len(edges)
-    k = ref["overlaps"]
-    assert np.array_equal(tri[:k], ref["tri"]) and np.array_equal(edges[:k], ref["edges"]), (what, np.nonzero(tri[:k] != ref["tri"])[0][:8])
+    L.check_lists(L.OVERLAPS, got, ref, what)
 
 
 def check_case(renderer, q, ref, what, exact_work=False, **kw):
     """The three ways to ask against the reference of the query triangles q: count, list without a capacity (count + fill), list with
     capacity k + 3.  exact_work: the tree is the host-built single-level one, whose walk the reference has made: nodes and records
     agree exactly."""
-    n, k = len(q), ref["overlaps"]
-    tq = tdev(q)
-    counts = renderer.count_overlaps(tq, count_traversal=True, **kw)
-    st = renderer.overlap_query_stats()
-    assert np.array_equal(counts.cpu().numpy(), ref["count"]), (what, np.nonzero(counts.cpu().numpy() != ref["count"])[0][:8])
-    assert (st["triangles"], st["invalid_triangles"], st["overlaps"], st["overlaps_written"], st["stack_overflow"], st["launches"]) == (n, ref["invalid"], k, 0, 0, 1) \
-        and st["ms"] > 0, (what, st)
-    if exact_work:  # the box is fixed, so the work does not depend on the order of the walk
-        assert (st["nodes_visited"], st["tris_tested"]) == (ref["nodes_total"], ref["tris_total"]), (what, st, ref["nodes_total"], ref["tris_total"])
-    got = renderer.list_overlaps(tq, **kw)
-    st = renderer.overlap_query_stats()  # of the fill step
-    assert len(got[1]) == k
-    check_lists(got, ref, what)
-    assert (st["triangles"], st["invalid_triangles"], st["overlaps"], st["overlaps_written"], st["incomplete_triangles"], st["slice_overflow"], st["stack_overflow"],
-            st["launches"], st["nodes_visited"]) == (n, ref["invalid"], k, k, 0, 0, 0, 1, 0), (what, st)
-    got = renderer.list_overlaps(tq, capacity=k + 3, **kw)
-    st = renderer.overlap_query_stats()
-    check_lists(got, ref, what)
-    assert (st["triangles"], st["invalid_triangles"], st["overlaps"], st["overlaps_written"], st["incomplete_triangles"], st["slice_overflow"], st["stack_overflow"],
-            st["launches"]) == (n, ref["invalid"], k, k, 0, 0, 0, 5) and st["ms"] > 0, (what, st)
+    L.check_case(renderer, L.OVERLAPS, (q,), ref, what, exact_work=exact_work, **kw)
 
 
 # ---- 1. every family, every tree ---------------------------------------------------------------------------------------------------
@@ -195,73 +153,19 @@ def test_capacity(renderer):
 
     b = set_batch(renderer)
     n, ref = b["n"], b["ref"]
-    total, off = ref["overlaps"], ref["offsets"]
-    tq = tdev(b["q"])
-    for capacity in (total, total - 1, total // 2, 0):
-        for kw in (dict(), dict(tune_max_blocks=1, tune_refill_min=1)):
-            t_buf = torch.full((capacity + 64,), -7, dtype=torch.int32, device=dev())
-            e_buf = torch.full((capacity + 64,), -7, dtype=torch.int32, device=dev())
-            offsets, tri, edges, counts = renderer.list_overlaps(tq, capacity=capacity, out=(None, t_buf[:capacity], e_buf[:capacity], None), **kw)
-            st = renderer.overlap_query_stats()
-            fits = off[1:] <= capacity
-            written = int(off[1:][fits].max()) if fits.any() else 0  # the slices that fit are a prefix of the queries
-            incomplete = int(((ref["count"] > 0) & ~fits).sum())
-            assert np.array_equal(offsets.cpu().numpy(), off) and np.array_equal(counts.cpu().numpy(), ref["count"]), capacity
-            gt, ge = t_buf.cpu().numpy(), e_buf.cpu().numpy()
-            assert np.array_equal(gt[:written], ref["tri"][:written]) and np.array_equal(ge[:written], ref["edges"][:written]), (capacity, kw)
-            assert (gt[written:] == -7).all() and (ge[written:] == -7).all(), (capacity, kw)
-            assert (st["overlaps"], st["overlaps_written"], st["incomplete_triangles"], st["slice_overflow"], st["stack_overflow"]) == (total, written, incomplete, 0, 0), (capacity, kw, st)
-            assert (capacity == total) == (incomplete == 0) and (capacity > 0 or written == 0)
+    L.capacity(renderer, L.OVERLAPS, (b["q"],), ref)
     # capacity 0 with NULL arrays
-    cnt, offs = torch.full((n,), -7, dtype=torch.int32, device=dev()), torch.full((n + 1,), -7, dtype=torch.int64, device=dev())
+    tq, cnt, offs = tdev(b["q"]), Q.sentinel(n, torch.int32), Q.sentinel(n + 1, torch.int64)
     assert R.load().rt_list_overlaps_device(renderer._ctx, ptr(tq), n, None, ptr(cnt), ptr(offs), 0, None, None) == 0
     assert renderer.overlap_query_stats()["overlaps_written"] == 0
-    assert np.array_equal(offs.cpu().numpy(), off) and np.array_equal(cnt.cpu().numpy(), ref["count"])
-    # the caller's second try: the fill step alone on the offsets it has
-    tri, edges = torch.empty(total, dtype=torch.int32, device=dev()), torch.empty(total, dtype=torch.int32, device=dev())
-    prm = R.OverlapQueryParams()
-    assert R.load().rt_fill_overlaps_device(renderer._ctx, ptr(tq), n, C.byref(prm), ptr(offs), total, ptr(tri), ptr(edges)) == 0
-    st = renderer.overlap_query_stats()  # (waits for it)
-    assert (st["overlaps"], st["overlaps_written"], st["incomplete_triangles"], st["launches"]) == (total, total, 0, 1), st
-    check_lists((offs, tri, edges, cnt), ref, "second try")
+    assert np.array_equal(offs.cpu().numpy(), ref["offsets"]) and np.array_equal(cnt.cpu().numpy(), ref["count"])
 
 
 def test_foreign_offsets_are_safe(renderer):
     """The fill step on offsets it did not make: nothing outside [0, capacity) is written, a slice shorter than its query's list keeps the
     entries with the lowest indices, and slice_overflow counts the rest."""
-    import torch
-
-    lib = R.load()
     b = set_batch(renderer)
-    n, ref = b["n"], b["ref"]
-    total, off, count = ref["overlaps"], ref["offsets"], ref["count"].astype(np.int64)
-    tq = tdev(b["q"])
-    guard = 4096
-    cases = {"halved": off // 2, "shifted up": off + 1000, "shifted down": off - 1000, "reversed": off[::-1].copy(), "far": off + (1 << 40),
-             "negative": -off - 1, "zeros": np.zeros(n + 1, np.int64)}
-    for name, foreign in cases.items():
-        for capacity in (total, total // 3):
-            t_buf = torch.full((capacity + 2 * guard,), -7, dtype=torch.int32, device=dev())
-            e_buf = torch.full((capacity + 2 * guard,), -7, dtype=torch.int32, device=dev())
-            fo = tdev(np.ascontiguousarray(foreign, np.int64))
-            assert lib.rt_fill_overlaps_device(renderer._ctx, ptr(tq), n, None, ptr(fo), capacity, ptr(t_buf[guard:]), ptr(e_buf[guard:])) == 0
-            st = renderer.overlap_query_stats()
-            lo, hi = foreign[:-1], foreign[1:]
-            length = np.maximum(hi - lo, 0)
-            room = np.where((lo >= 0) & (hi <= capacity), length, 0)
-            exp_t, exp_e = np.full(capacity + 2 * guard, -7, np.int32), np.full(capacity + 2 * guard, -7, np.int32)
-            keep = np.minimum(room, count)
-            src = np.repeat(off[:-1], keep) + (np.arange(keep.sum()) - np.repeat(np.cumsum(keep) - keep, keep))
-            dst = np.repeat(lo, keep) + (np.arange(keep.sum()) - np.repeat(np.cumsum(keep) - keep, keep))
-            gt, ge = t_buf.cpu().numpy(), e_buf.cpu().numpy()
-            assert (gt[:guard] == -7).all() and (gt[guard + capacity:] == -7).all() and (ge[:guard] == -7).all() and (ge[guard + capacity:] == -7).all(), (name, capacity)
-            exp_t[guard + dst], exp_e[guard + dst] = ref["tri"][src], ref["edges"][src]
-            assert np.array_equal(gt, exp_t) and np.array_equal(ge, exp_e), (name, capacity)
-            beyond = int(np.maximum(count - length, 0).sum())
-            assert (st["overlaps"], st["overlaps_written"], st["slice_overflow"], st["stack_overflow"], st["launches"]) == (total, int(keep.sum()), beyond, 0, 1), (name, capacity, st)
-            assert st["incomplete_triangles"] == int(((count > 0) & (room != length)).sum()), (name, capacity, st)
-            if name in ("halved", "reversed", "negative", "zeros"):
-                assert st["slice_overflow"] > 0, name
+    L.foreign_offsets(renderer, L.OVERLAPS, (b["q"],), b["ref"])
 
 
 # ---- 4. invalid queries, refusals ----------------------------------------------------------------------------------------------------
@@ -293,87 +197,22 @@ def test_invalid_triangles(renderer):
     assert (st["invalid_triangles"], st["overlaps"], st["overlaps_written"], st["triangles"]) == (n, 0, 0, n)
 
 
-def _segment_end(p):
-    """End address of the device allocation (caching-allocator segment) that holds `p`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= p < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
-
-
 def test_errors_write_nothing(renderer):
-    import torch
-
-    lib = R.load()
     b = set_batch(renderer)
     n, ref = b["n"], b["ref"]
-    cap = ref["overlaps"]
-    tq = tdev(b["q"])
-    cnt = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    off = torch.full((n + 1,), -7, dtype=torch.int64, device=dev())
-    tri = torch.full((cap,), -7, dtype=torch.int32, device=dev())
-    edges = torch.full((cap,), -7, dtype=torch.int32, device=dev())
-    good_off = tdev(ref["offsets"])
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
-
-    def untouched(k):
-        renderer.synchronize()
-        assert (cnt == -7).all() and (off == -7).all() and (tri == -7).all() and (edges == -7).all() and (big == 0).all(), k
-
-    def every_entry(ctx, code, what):
-        assert lib.rt_count_overlaps_device(ctx, ptr(tq), n, None, ptr(cnt), ptr(off)) == code, what
-        assert lib.rt_fill_overlaps_device(ctx, ptr(tq), n, None, ptr(good_off), cap, ptr(tri), ptr(edges)) == code, what
-        assert lib.rt_list_overlaps_device(ctx, ptr(tq), n, None, ptr(cnt), ptr(off), cap, ptr(tri), ptr(edges)) == code, what
-        untouched(what)
-
+    e = L.Refusals(renderer, L.OVERLAPS, (b["q"],), ref, short9=36)  # (one row short of n x 9)
     fresh = R.Renderer(0)
     try:
-        every_entry(fresh._ctx, RT_ERR_STATE, "no mesh")
+        e.every_entry(fresh._ctx, RT_ERR_STATE, "no mesh")
         set_mesh(fresh, np.ldexp(PX.mesh("grid"), 19).astype(f32))  # 5.3 x 2^19 > 2^20: taken as a mesh, refused by the queries
-        every_entry(fresh._ctx, RT_ERR_INVALID, "a mesh beyond 2^20")
+        e.every_entry(fresh._ctx, RT_ERR_INVALID, "a mesh beyond 2^20")
     finally:
         fresh.close()
-    ctx = renderer._ctx
-    host = np.zeros((n + 1, 9), np.float64)
-    hp = C.c_void_p(host.ctypes.data)
-    end = _segment_end(big.data_ptr())
-    short9, short1, short8, shortc = (C.c_void_p(end - k) for k in (36 * (n - 1), 4 * (n - 1), 8 * n, 4 * (cap - 1)))  # one row short of n x 9, n, n + 1 i64, capacity
-    P = R.OverlapQueryParams
-    bad_params = [C.byref(P(tune_refill_min=65)), C.byref(P(tune_blocks_per_cu=9)), C.byref(P(tune_lds_stack=79)), C.byref(P(count_traversal=2))]
-    sources = [(None, n, None), (hp, n, None), (short9, n, None), (ptr(tq), (1 << 30) + 1, None)] + [(ptr(tq), n, prm) for prm in bad_params]
-    good = (ptr(tq), n, None)
-    count_calls = [s + (ptr(cnt), ptr(off)) for s in sources] + [good + x for x in ((None, None), (hp, ptr(off)), (ptr(cnt), hp), (short1, ptr(off)), (ptr(cnt), short8))]
-    for k, args in enumerate(count_calls):
-        assert lib.rt_count_overlaps_device(ctx, *args) == RT_ERR_INVALID, k
-        untouched(("count", k))
-    fill_calls = [s + (ptr(good_off), cap, ptr(tri), ptr(edges)) for s in sources] + \
-        [good + x for x in ((None, cap, ptr(tri), ptr(edges)), (hp, cap, ptr(tri), ptr(edges)), (short8, cap, ptr(tri), ptr(edges)), (ptr(good_off), cap, None, ptr(edges)),
-                            (ptr(good_off), cap, ptr(tri), None), (ptr(good_off), cap, hp, ptr(edges)), (ptr(good_off), cap, ptr(tri), hp), (ptr(good_off), cap, shortc, ptr(edges)),
-                            (ptr(good_off), cap, ptr(tri), shortc), (ptr(good_off), 1 << 62, ptr(tri), ptr(edges)))]
-    for k, args in enumerate(fill_calls):
-        assert lib.rt_fill_overlaps_device(ctx, *args) == RT_ERR_INVALID, k
-        untouched(("fill", k))
-    # the pair: a refusal of the SECOND step comes before the first step is enqueued
-    list_calls = [s + (ptr(cnt), ptr(off), cap, ptr(tri), ptr(edges)) for s in sources] + \
-        [good + x for x in ((ptr(cnt), None, cap, ptr(tri), ptr(edges)), (hp, ptr(off), cap, ptr(tri), ptr(edges)), (ptr(cnt), hp, cap, ptr(tri), ptr(edges)),
-                            (short1, ptr(off), cap, ptr(tri), ptr(edges)), (ptr(cnt), short8, cap, ptr(tri), ptr(edges)), (ptr(cnt), ptr(off), cap, None, ptr(edges)),
-                            (ptr(cnt), ptr(off), cap, ptr(tri), None), (ptr(cnt), ptr(off), cap, hp, ptr(edges)), (ptr(cnt), ptr(off), cap, ptr(tri), hp),
-                            (ptr(cnt), ptr(off), cap, shortc, ptr(edges)), (ptr(cnt), ptr(off), cap, ptr(tri), shortc), (ptr(cnt), ptr(off), 1 << 62, ptr(tri), ptr(edges)))]
-    for k, args in enumerate(list_calls):
-        assert lib.rt_list_overlaps_device(ctx, *args) == RT_ERR_INVALID, k
-        untouched(("list", k))
-    # n = 0 is accepted, and does nothing
-    assert lib.rt_count_overlaps_device(ctx, ptr(tq), 0, None, ptr(cnt), ptr(off)) == 0
-    assert lib.rt_count_overlaps_device(ctx, None, 0, None, None, None) == 0
-    assert lib.rt_fill_overlaps_device(ctx, None, 0, None, None, 0, None, None) == 0
-    assert lib.rt_list_overlaps_device(ctx, None, 0, None, None, None, 0, None, None) == 0
-    untouched("n = 0")
-    assert len(renderer.count_overlaps(tq[:0])) == 0
-    assert [len(x) for x in renderer.list_overlaps(tq[:0])] == [1, 0, 0, 0] and [len(x) for x in renderer.list_overlaps(tq[:0], capacity=5)] == [1, 5, 5, 0]
+    tq, = e.t
+    e.tables([(None, n, None), (e.bp.hp, n, None), (e.bp.short9, n, None), (ptr(tq), (1 << 30) + 1, None)] + [(ptr(tq), n, prm) for prm in e.bad_params])
+    e.nothing_to_do((tq[:0],), (tq[:0],))
     # the context still answers; (n, 3, 3) and flat tensors are the same triangles
-    check_lists(renderer.list_overlaps(tq, capacity=cap, out=(off, tri, edges, cnt)), ref, "after the refusals")
+    e.still_answers()
     check_lists(renderer.list_overlaps(tq.view(n, 3, 3)), ref, "(n, 3, 3)")
     check_lists(renderer.list_overlaps(tq.view(-1)), ref, "flat")
 

@@ -5,7 +5,6 @@ reference (tests/native/overlap_segment_ref.cpp: csrc/tri_overlap.h + csrc/tri_s
 hand-computed answers, to its own selection rule and to float64 on the CPU (tests/test_overlap_segment_host.py).  What the call does
 with arrays it did not make - offsets that do not ascend, indices outside the mesh, a capacity that cuts a slice - is stated entry by
 entry by expect() below, from the header's rules and the same native program, and asserted behind guard words: no case provokes a fault."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -16,32 +15,13 @@ import point_exact as PX
 import ray_exact as X
 import raytracing_engine_amd as R
 import section_exact as SX
+from gpu_query import RT_ERR_INVALID, RT_ERR_STATE, assert_untouched, bad_pointers, dev, ptr, sentinel, still_sentinel, tdev
+from gpu_query import set_mesh_with_surface as set_mesh
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-RT_ERR_INVALID, RT_ERR_STATE = -1, -4
 GUARD = 256  # untouched entries asserted on either side of every output array of the raw calls
-
-
-def dev():
-    import torch
-
-    return torch.device("cuda", 0)
-
-
-def tdev(a):
-    import torch
-
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev())
-
-
-def ptr(x):
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
-def set_mesh(renderer, verts, **kw):
-    renderer.set_mesh(*X._with_surface(verts), **kw)
 
 
 def bits_of(mask):
@@ -201,8 +181,7 @@ def raw_call(renderer, b, offsets, tri, capacity, what, with_ends=True):
     import torch
 
     lib = R.load()
-    seg_buf = torch.full((capacity + 2 * GUARD, 6), -7.0, device=dev())
-    ends_buf = torch.full((capacity + 2 * GUARD,), -7, dtype=torch.int32, device=dev())
+    seg_buf, ends_buf = sentinel(capacity, torch.float32, 2 * GUARD, cols=6), sentinel(capacity, torch.int32, 2 * GUARD)
     tq, to, tt = tdev(b["q"]), tdev(np.ascontiguousarray(offsets, np.int64)), tdev(np.ascontiguousarray(tri, np.int32))
     assert len(tri) >= capacity
     torch.cuda.synchronize()
@@ -210,7 +189,7 @@ def raw_call(renderer, b, offsets, tri, capacity, what, with_ends=True):
     st = renderer.overlap_segment_stats()  # (waits for it)
     want_seg, want_ends, want_st = expect(b["v"], b["q"], offsets, tri, capacity)
     got_seg, got_ends = seg_buf.cpu().numpy(), ends_buf.cpu().numpy()
-    assert (got_seg[:GUARD] == -7).all() and (got_seg[GUARD + capacity:] == -7).all() and (got_ends[:GUARD] == -7).all() and (got_ends[GUARD + capacity:] == -7).all(), what
+    assert still_sentinel(got_seg, GUARD, GUARD + capacity) and still_sentinel(got_ends, GUARD, GUARD + capacity), what
     assert SX.same_bits(got_seg[GUARD:GUARD + capacity].reshape(-1, 2, 3), want_seg), what
     assert np.array_equal(got_ends[GUARD:GUARD + capacity], want_ends if with_ends else np.full(capacity, -7, np.int32)), what
     assert {k: st[k] for k in want_st} == want_st and st["launches"] == 2, (what, st, want_st)
@@ -226,8 +205,7 @@ def test_a_capacity_that_cuts_a_slice(renderer):
     off, count = b["sref"]["offsets"], b["sref"]["count"]
     j = int(np.nonzero((count >= 3) & (off[:-1] > 300))[0][0])
     for capacity in (int(off[j]) + 2, int(off[j]), b["sref"]["entries"] - 1):
-        t_buf = torch.full((b["sref"]["entries"],), -7, dtype=torch.int32, device=dev())
-        e_buf = torch.full((b["sref"]["entries"],), -7, dtype=torch.int32, device=dev())
+        t_buf, e_buf = sentinel(b["sref"]["entries"], torch.int32), sentinel(b["sref"]["entries"], torch.int32)
         offsets, tri, _, _ = renderer.list_overlaps(tdev(b["q"]), capacity=capacity, out=(None, t_buf[:capacity], e_buf[:capacity], None))
         assert np.array_equal(offsets.cpu().numpy(), off)
         st = raw_call(renderer, b, off, t_buf.cpu().numpy(), capacity, ("capacity", capacity))
@@ -278,16 +256,6 @@ def test_foreign_input_is_safe(renderer):
 
 # ---- 3. refusals ------------------------------------------------------------------------------------------------------------------
 
-def _segment_end(p):
-    """End address of the device allocation (caching-allocator segment) that holds `p`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= p < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
-
-
 def test_errors_write_nothing(renderer):
     import torch
 
@@ -295,13 +263,12 @@ def test_errors_write_nothing(renderer):
     b = set_batch(renderer)
     n, cap = b["n"], b["sref"]["entries"]
     tq, off, tri = tdev(b["q"]), tdev(b["sref"]["offsets"]), tdev(b["sref"]["tri"])
-    seg = torch.full((cap, 6), -7.0, device=dev())
-    ends = torch.full((cap,), -7, dtype=torch.int32, device=dev())
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
+    seg, ends = sentinel(cap, torch.float32, cols=6), sentinel(cap, torch.int32)
+    bp = bad_pointers(n, short9=36, short8=(8, n + 1), short4=(4, cap), short24=(24, cap))  # one row short each
+    hp, short9, short8, short4, short24 = bp.hp, bp.short9, bp.short8, bp.short4, bp.short24
 
     def untouched(k):
-        renderer.synchronize()
-        assert (seg == -7).all() and (ends == -7).all() and (big == 0).all(), k
+        assert_untouched(renderer, (seg, ends), bp.big, k)
 
     good = (ptr(tq), n, ptr(off), cap, ptr(tri), ptr(seg), ptr(ends))
     fresh = R.Renderer(0)
@@ -314,10 +281,6 @@ def test_errors_write_nothing(renderer):
     finally:
         fresh.close()
     ctx = renderer._ctx
-    host = np.zeros((cap + 1, 9), np.float64)
-    hp = C.c_void_p(host.ctypes.data)
-    end = _segment_end(big.data_ptr())
-    short9, short8, short4, short24 = (C.c_void_p(end - k) for k in (36 * (n - 1), 8 * n, 4 * (cap - 1), 24 * (cap - 1)))  # one row short each
     calls = []
     for at, bad in ((0, (None, hp, short9)), (2, (None, hp, short8)), (4, (None, hp, short4)), (5, (None, hp, short24)), (6, (hp, short4))):
         for x in bad:
@@ -369,12 +332,8 @@ def test_stream_order_behind_a_refit_and_a_list(renderer):
     renderer.set_mesh_device(*(tdev(x) for x in X._with_surface(still)))
     tq, moved = tdev(c["q"]), tdev(c["verts"])
     ref_seg, ref_ends = tdev(sref["seg"]).view(torch.int32), tdev(sref["ends"])
-    counts = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    offsets = torch.full((n + 1,), -7, dtype=torch.int64, device=dev())
-    tri = torch.full((k,), -7, dtype=torch.int32, device=dev())
-    edges = torch.full((k,), -7, dtype=torch.int32, device=dev())
-    seg = torch.full((k, 2, 3), -7.0, device=dev())
-    ends = torch.full((k,), -7, dtype=torch.int32, device=dev())
+    counts, offsets, tri, edges = sentinel(n, torch.int32), sentinel(n + 1, torch.int64), sentinel(k, torch.int32), sentinel(k, torch.int32)
+    seg, ends = torch.full((k, 2, 3), -7.0, device=dev()), sentinel(k, torch.int32)
     torch.cuda.synchronize()
     s = torch.cuda.Stream(device=dev())
     renderer.set_stream(s.cuda_stream)

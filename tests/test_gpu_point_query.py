@@ -6,7 +6,6 @@ contract, which its answers must satisfy on their own.  The first tests run ever
 on ONE mesh whose size they can cut, tile and plant points into: the 4 000 points of soup_batch() against the 2 000-triangle soup.  A
 distance limit needs no tolerance: the answer is defined as the (d2, index)-minimal triangle, so "hit when d2 < rmax * rmax" is decided
 by the reference's own d2."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -15,43 +14,21 @@ import pytest
 import point_exact as PX
 import ray_exact as X
 import raytracing_engine_amd as R
+from gpu_query import RT_ERR_INVALID, RT_ERR_STATE, assert_untouched, bad_params, bad_pointers, busy_stream, dev, pt_frame, ptr, same_floats, sentinel, still_sentinel, tdev
+from gpu_query import set_mesh_px_surface as set_mesh
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 INF = f32(np.inf)
-RT_ERR_INVALID, RT_ERR_STATE = -1, -4
 MISS, INVALID = -1, -2
 N = 4000
-
-
-def dev():
-    import torch
-
-    return torch.device("cuda", 0)
-
-
-def tdev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
 
 
 def query(renderer, p, rmax=None, **kw):
     """Numpy in, numpy out, through device tensors: (dist, tri, point)."""
     d, t, c = renderer.query_points(tdev(p), None if rmax is None else tdev(rmax), **kw)
     return d.cpu().numpy(), t.cpu().numpy(), None if c is None else c.cpu().numpy()
-
-
-def same_floats(a, b):
-    """Bit-equal, NaN for NaN (whatever its payload)."""
-    a, b = np.asarray(a, f32).ravel(), np.asarray(b, f32).ravel()
-    nan = np.isnan(a)
-    return a.shape == b.shape and np.array_equal(nan, np.isnan(b)) and np.array_equal(a[~nan].view(np.uint32), b[~nan].view(np.uint32))
-
-
-def set_mesh(renderer, verts, **kw):
-    renderer.set_mesh(verts, *PX.surface(verts), **kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -266,12 +243,10 @@ def test_bounds_and_out_tensors(renderer):
     for n in (1, 65, N):
         p, rm = tdev(b["p"][:n]), tdev(np.full(n, INF, f32))
         p0, rm0 = p.clone(), rm.clone()
-        d_buf = torch.full((n + 64,), -7.0, dtype=torch.float32, device=dev())
-        t_buf = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
-        c_buf = torch.full((n + 64, 3), -7.0, dtype=torch.float32, device=dev())
+        d_buf, t_buf, c_buf = sentinel(n, torch.float32, 64), sentinel(n, torch.int32, 64), sentinel(n, torch.float32, 64, cols=3)
         dist, tri, c = renderer.query_points(p, rm, out=(d_buf[:n], t_buf[:n], c_buf[:n]))
         assert dist.data_ptr() == d_buf.data_ptr() and tri.data_ptr() == t_buf.data_ptr() and c.data_ptr() == c_buf.data_ptr()
-        assert (d_buf[n:] == -7.0).all() and (t_buf[n:] == -7).all() and (c_buf[n:] == -7.0).all()
+        assert still_sentinel(d_buf, 0, n) and still_sentinel(t_buf, 0, n) and still_sentinel(c_buf, 0, n)
         assert_answers((dist.cpu().numpy(), tri.cpu().numpy(), c.cpu().numpy()), b["ref"], slice(0, n))
         for x, x0 in ((p, p0), (rm, rm0)):
             assert torch.equal(x.view(torch.int32), x0.view(torch.int32))
@@ -279,7 +254,7 @@ def test_bounds_and_out_tensors(renderer):
         d_buf.fill_(-7.0)
         t_buf.fill_(-7)
         dist, tri, none = renderer.query_points(p, out=(d_buf[:n], t_buf[:n]), want_points=False)
-        assert none is None and (d_buf[n:] == -7.0).all() and (t_buf[n:] == -7).all()
+        assert none is None and still_sentinel(d_buf, 0, n) and still_sentinel(t_buf, 0, n)
         assert_answers((dist.cpu().numpy(), tri.cpu().numpy(), None), b["ref"], slice(0, n))
     with pytest.raises(ValueError):
         renderer.query_points(p, out=(d_buf[:N], t_buf[:N - 1], c_buf[:N]))
@@ -295,35 +270,12 @@ def test_stream_order(renderer):
     b = set_soup(renderer)
     p_half = tdev(b["p"] * f32(0.5))
     ref_d, ref_t, ref_c = tdev(b["ref"]["dist"]).view(torch.int32), tdev(b["ref"]["tri"]), tdev(b["ref"]["c"]).view(torch.int32)
-    dist = torch.full((N,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((N,), -7, dtype=torch.int32, device=dev())
-    c = torch.full((N, 3), -7.0, dtype=torch.float32, device=dev())
-    torch.cuda.synchronize()
-    s = torch.cuda.Stream(device=dev())
-    renderer.set_stream(s.cuda_stream)
-    try:
-        with torch.cuda.stream(s):
-            busy = torch.zeros(1 << 26, dtype=torch.float32, device=dev())
-            for _ in range(8):  # the stream has work to do when the query is enqueued
-                busy += 1.0
-            p = p_half * 2.0
-            renderer.query_points(p, out=(dist, tri, c), sync=False)
-            wrong = (dist.view(torch.int32) != ref_d).sum() + (tri != ref_t).sum() + (c.view(torch.int32) != ref_c).sum()
-        s.synchronize()
-        assert int(wrong) == 0 and float(busy[0]) == 8.0
-    finally:
-        renderer.synchronize()
-        renderer.set_stream(None)
-
-
-def _segment_end(ptr):
-    """End address of the device allocation (caching-allocator segment) that holds `ptr`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= ptr < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
+    dist, tri, c = sentinel(N, torch.float32), sentinel(N, torch.int32), sentinel(N, torch.float32, cols=3)
+    with busy_stream(renderer):
+        p = p_half * 2.0
+        renderer.query_points(p, out=(dist, tri, c), sync=False)
+        wrong = (dist.view(torch.int32) != ref_d).sum() + (tri != ref_t).sum() + (c.view(torch.int32) != ref_c).sum()
+    assert int(wrong) == 0
 
 
 def test_errors_write_nothing(renderer):
@@ -333,38 +285,28 @@ def test_errors_write_nothing(renderer):
     b = set_soup(renderer)
     n = 1000
     p = tdev(b["p"][:n])
-    dist = torch.full((n,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    c = torch.full((n, 3), -7.0, dtype=torch.float32, device=dev())
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+    dist, tri, c = sentinel(n, torch.float32), sentinel(n, torch.int32), sentinel(n, torch.float32, cols=3)
     fresh = R.Renderer(0)
     try:
         assert lib.rt_query_points_device(fresh._ctx, ptr(p), None, n, None, ptr(dist), ptr(tri), ptr(c)) == RT_ERR_STATE  # no mesh
     finally:
         fresh.close()
     ctx = renderer._ctx
-    host = np.zeros((n, 3), f32)
-    hp = C.c_void_p(host.ctypes.data)
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
-    short3 = C.c_void_p(_segment_end(big.data_ptr()) - 12 * (n - 1))  # the allocation holds n - 1 rows from here
-    short1 = C.c_void_p(_segment_end(big.data_ptr()) - 4 * (n - 1))
-    P = R.PointQueryParams
+    bp = bad_pointers(n, short3=12, short1=4)  # the allocation holds n - 1 rows from the short ones
+    hp, big, short3, short1 = bp.hp, bp.big, bp.short3, bp.short1
     calls = [(None, None, n, None, ptr(dist), ptr(tri), ptr(c)), (ptr(p), None, n, None, None, ptr(tri), ptr(c)), (ptr(p), None, n, None, ptr(dist), None, ptr(c)),
              (hp, None, n, None, ptr(dist), ptr(tri), ptr(c)), (ptr(p), hp, n, None, ptr(dist), ptr(tri), ptr(c)), (ptr(p), None, n, None, hp, ptr(tri), ptr(c)),
              (ptr(p), None, n, None, ptr(dist), hp, ptr(c)), (ptr(p), None, n, None, ptr(dist), ptr(tri), hp),
              (short3, None, n, None, ptr(dist), ptr(tri), ptr(c)), (ptr(p), short1, n, None, ptr(dist), ptr(tri), ptr(c)),
              (ptr(p), None, n, None, short1, ptr(tri), ptr(c)), (ptr(p), None, n, None, ptr(dist), short1, ptr(c)), (ptr(p), None, n, None, ptr(dist), ptr(tri), short3),
-             (ptr(p), None, (1 << 30) + 1, None, ptr(dist), ptr(tri), ptr(c)),
-             (ptr(p), None, n, C.byref(P(tune_refill_min=65)), ptr(dist), ptr(tri), ptr(c)), (ptr(p), None, n, C.byref(P(tune_blocks_per_cu=9)), ptr(dist), ptr(tri), ptr(c)),
-             (ptr(p), None, n, C.byref(P(tune_lds_stack=79)), ptr(dist), ptr(tri), ptr(c)), (ptr(p), None, n, C.byref(P(count_traversal=2)), ptr(dist), ptr(tri), ptr(c))]
+             (ptr(p), None, (1 << 30) + 1, None, ptr(dist), ptr(tri), ptr(c))] + [(ptr(p), None, n, prm, ptr(dist), ptr(tri), ptr(c)) for prm in bad_params(R.PointQueryParams)]
     for k, args in enumerate(calls):
         assert lib.rt_query_points_device(ctx, *args) == RT_ERR_INVALID, k
-        renderer.synchronize()
-        assert (dist == -7.0).all() and (tri == -7).all() and (c == -7.0).all() and (big == 0).all(), k
+        assert_untouched(renderer, (dist, tri, c), big, k)
     assert lib.rt_query_points_device(ctx, ptr(p), None, 0, None, ptr(dist), ptr(tri), ptr(c)) == 0  # n = 0 is accepted, and does nothing
     assert lib.rt_query_points_device(ctx, None, None, 0, None, None, None, None) == 0
     renderer.synchronize()
-    assert (dist == -7.0).all() and (tri == -7).all() and (c == -7.0).all()
+    assert still_sentinel(dist) and still_sentinel(tri) and still_sentinel(c)
     e = renderer.query_points(p[:0])
     assert len(e[0]) == 0 and len(e[1]) == 0 and len(e[2]) == 0
     # the context still answers
@@ -417,9 +359,7 @@ def test_queries_leave_two_stream_frames_alone(renderer):
     o, d = np.concatenate([p["o"] for p in parts]), np.concatenate([p["d"] for p in parts])
 
     def frame(**more):
-        rgb = renderer.render_pt(**kw, **more)
-        st = renderer.pt_stats()
-        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+        return pt_frame(renderer, **kw, **more)
 
     before, before_spilling = frame(), frame(tune_lds_stack=1)
     assert before[1][1] > 0 and before[1][2] > 0 and before[1][3] == 0
@@ -439,9 +379,7 @@ def test_rendering_and_sharing_are_undisturbed(renderer):
     kw = dict(pos=(0, 1, 0), spp=2, bounces=2, seed=3, sky=(0.2, 0.2, 0.3))
 
     def frame(r):
-        rgb = r.render_pt(**kw)
-        st = r.pt_stats()
-        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+        return pt_frame(r, **kw)
 
     before = frame(renderer)
     assert before[1][1] > 0 and before[1][2] > 0

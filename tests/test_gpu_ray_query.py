@@ -16,26 +16,14 @@ import pytest
 import oracle as O
 import ray_exact as X
 import raytracing_engine_amd as R
+from gpu_query import RT_ERR_INVALID, RT_ERR_STATE, assert_untouched, bad_params, bad_pointers, busy_stream, dev, pt_frame, ptr, same_floats, sentinel, still_sentinel, tdev
 from test_gpu_ray_contract import family_data  # the per-family references, computed once for both modules
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 INF = f32(np.inf)
-RT_ERR_INVALID, RT_ERR_STATE = -1, -4
 MISS, INVALID = -1, -2
-
-
-def dev():
-    import torch
-
-    return torch.device("cuda", 0)
-
-
-def tdev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
 
 
 def query(renderer, o, d, tmax=None, any_hit=False, **kw):
@@ -44,10 +32,6 @@ def query(renderer, o, d, tmax=None, any_hit=False, **kw):
     if any_hit:
         return got.cpu().numpy()
     return got[0].cpu().numpy(), got[1].cpu().numpy()
-
-
-def same_floats(a, b):
-    return np.array_equal(np.asarray(a, f32).view(np.uint32), np.asarray(b, f32).view(np.uint32))
 
 
 @functools.lru_cache(maxsize=None)
@@ -275,15 +259,14 @@ def test_bounds_and_out_tensors(renderer):
     for n in (1, 65, 4000):
         o, d, tm = tdev(b["o"][:n]), tdev(b["d"][:n]), tdev(np.full(n, INF, f32))
         o0, d0, tm0 = o.clone(), d.clone(), tm.clone()
-        t_buf = torch.full((n + 64,), -7.0, dtype=torch.float32, device=dev())
-        tri_buf = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
+        t_buf, tri_buf = sentinel(n, torch.float32, 64), sentinel(n, torch.int32, 64)
         t, tri = renderer.query_rays(o, d, tm, out=(t_buf[:n], tri_buf[:n]))
         assert t.data_ptr() == t_buf.data_ptr() and tri.data_ptr() == tri_buf.data_ptr() and len(t) == len(tri) == n
-        assert (t_buf[n:] == -7.0).all() and (tri_buf[n:] == -7).all()
+        assert still_sentinel(t_buf, 0, n) and still_sentinel(tri_buf, 0, n)
         assert np.array_equal(tri.cpu().numpy(), b["tri"][:n]) and same_floats(t.cpu().numpy(), b["t"][:n])
-        occ_buf = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
+        occ_buf = sentinel(n, torch.int32, 64)
         occ = renderer.query_rays(o, d, tm, any_hit=True, out=occ_buf[:n])
-        assert occ.data_ptr() == occ_buf.data_ptr() and (occ_buf[n:] == -7).all()
+        assert occ.data_ptr() == occ_buf.data_ptr() and still_sentinel(occ_buf, 0, n)
         assert np.array_equal(occ.cpu().numpy(), (b["tri"][:n] >= 0).astype(np.int32))
         for x, x0 in ((o, o0), (d, d0), (tm, tm0)):
             assert torch.equal(x.view(torch.int32), x0.view(torch.int32))
@@ -307,39 +290,16 @@ def test_stream_order(renderer):
     o_half, d_half = tdev(b["o"] * f32(0.5)), tdev(b["d"] * f32(0.5))
     ref_t, ref_tri = tdev(b["t"]).view(torch.int32), tdev(b["tri"])
     ref_occ = tdev((b["tri"] >= 0) & (b["t"] < f32(X.T_SHADOW)))
-    t = torch.full((n,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    occ = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    torch.cuda.synchronize()
-    s = torch.cuda.Stream(device=dev())
-    renderer.set_stream(s.cuda_stream)
-    try:
-        with torch.cuda.stream(s):
-            busy = torch.zeros(1 << 26, dtype=torch.float32, device=dev())
-            for _ in range(8):  # the stream has work to do when the query is enqueued
-                busy += 1.0
-            o, d = o_half * 2.0, d_half * 2.0
-            renderer.query_rays(o, d, out=(t, tri), sync=False)
-            renderer.query_rays(o, d, any_hit=True, out=occ, sync=False)
-            wrong = (t.view(torch.int32) != ref_t).sum() + (tri != ref_tri).sum() + ((occ != 0) != ref_occ).sum()
-        s.synchronize()
-        assert int(wrong) == 0 and float(busy[0]) == 8.0
-    finally:
-        renderer.synchronize()
-        renderer.set_stream(None)
+    t, tri, occ = sentinel(n, torch.float32), sentinel(n, torch.int32), sentinel(n, torch.int32)
+    with busy_stream(renderer):
+        o, d = o_half * 2.0, d_half * 2.0
+        renderer.query_rays(o, d, out=(t, tri), sync=False)
+        renderer.query_rays(o, d, any_hit=True, out=occ, sync=False)
+        wrong = (t.view(torch.int32) != ref_t).sum() + (tri != ref_tri).sum() + ((occ != 0) != ref_occ).sum()
+    assert int(wrong) == 0
 
 
 # ---- 9. errors -----------------------------------------------------------------------------------------------------------------
-
-def _segment_end(ptr):
-    """End address of the device allocation (caching-allocator segment) that holds `ptr`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= ptr < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
-
 
 def test_errors_write_nothing(renderer):
     import torch
@@ -348,20 +308,15 @@ def test_errors_write_nothing(renderer):
     b = set_soup(renderer)
     n = 1000
     o, d = tdev(b["o"][:n]), tdev(b["d"][:n])
-    t = torch.full((n,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+    t, tri = sentinel(n, torch.float32), sentinel(n, torch.int32)
     fresh = R.Renderer(0)
     try:
         assert lib.rt_query_rays_device(fresh._ctx, ptr(o), ptr(d), None, n, None, ptr(t), ptr(tri)) == RT_ERR_STATE  # no mesh
     finally:
         fresh.close()
     ctx = renderer._ctx
-    host = np.zeros((n, 3), f32)
-    hp = C.c_void_p(host.ctypes.data)
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
-    short3 = C.c_void_p(_segment_end(big.data_ptr()) - 12 * (n - 1))  # the allocation holds n - 1 rays from here
-    short1 = C.c_void_p(_segment_end(big.data_ptr()) - 4 * (n - 1))
+    bp = bad_pointers(n, short3=12, short1=4)  # the allocation holds n - 1 rays from the short ones
+    hp, big, short3, short1 = bp.hp, bp.big, bp.short3, bp.short1
     anyp = R.RayQueryParams(any_hit=1)
     calls = [(None, ptr(d), None, n, None, ptr(t), ptr(tri)), (ptr(o), None, None, n, None, ptr(t), ptr(tri)),
              (ptr(o), ptr(d), None, n, None, None, ptr(tri)), (ptr(o), ptr(d), None, n, None, ptr(t), None),
@@ -371,19 +326,15 @@ def test_errors_write_nothing(renderer):
              (short3, ptr(d), None, n, None, ptr(t), ptr(tri)), (ptr(o), short3, None, n, None, ptr(t), ptr(tri)),
              (ptr(o), ptr(d), short1, n, None, ptr(t), ptr(tri)), (ptr(o), ptr(d), None, n, None, short1, ptr(tri)),
              (ptr(o), ptr(d), None, n, None, ptr(t), short1),
-             (ptr(o), ptr(d), None, (1 << 30) + 1, None, ptr(t), ptr(tri)),
-             (ptr(o), ptr(d), None, n, C.byref(R.RayQueryParams(tune_refill_min=65)), ptr(t), ptr(tri)),
-             (ptr(o), ptr(d), None, n, C.byref(R.RayQueryParams(tune_blocks_per_cu=9)), ptr(t), ptr(tri)),
-             (ptr(o), ptr(d), None, n, C.byref(R.RayQueryParams(tune_lds_stack=79)), ptr(t), ptr(tri)),
-             (ptr(o), ptr(d), None, n, C.byref(R.RayQueryParams(any_hit=2)), ptr(t), ptr(tri))]
+             (ptr(o), ptr(d), None, (1 << 30) + 1, None, ptr(t), ptr(tri))] + \
+        [(ptr(o), ptr(d), None, n, prm, ptr(t), ptr(tri)) for prm in bad_params(R.RayQueryParams, "any_hit")]
     for k, args in enumerate(calls):
         assert lib.rt_query_rays_device(ctx, *args) == RT_ERR_INVALID, k
-        renderer.synchronize()
-        assert (t == -7.0).all() and (tri == -7).all() and (big == 0).all(), k
+        assert_untouched(renderer, (t, tri), big, k)
     assert lib.rt_query_rays_device(ctx, ptr(o), ptr(d), None, 0, None, ptr(t), ptr(tri)) == 0  # n = 0 is accepted, and does nothing
     assert lib.rt_query_rays_device(ctx, None, None, None, 0, None, None, None) == 0
     renderer.synchronize()
-    assert (t == -7.0).all() and (tri == -7).all()
+    assert still_sentinel(t) and still_sentinel(tri)
     e = renderer.query_rays(o[:0], d[:0])
     assert len(e[0]) == 0 and len(e[1]) == 0
     # the context still answers
@@ -399,9 +350,7 @@ def test_rendering_is_undisturbed(renderer):
     kw = dict(pos=(0, 1, 0), spp=2, bounces=2, seed=3, sky=(0.2, 0.2, 0.3))
 
     def frame(r):
-        rgb = r.render_pt(**kw)
-        st = r.pt_stats()
-        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+        return pt_frame(r, **kw)
 
     before = frame(renderer)
     assert before[1][1] > 0 and before[1][2] > 0

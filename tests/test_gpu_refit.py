@@ -12,6 +12,7 @@ import pytest
 import oracle as O
 import raytracing_engine_amd as R
 from raytracing_engine_amd import scenes
+from gpu_query import ptr, segment_end
 from test_gpu_device_bvh import check_bvh, dev
 
 pytestmark = pytest.mark.gpu
@@ -275,16 +276,6 @@ def test_camera_range_follows_the_refit(renderer):
 
 # ---- 6. errors -------------------------------------------------------------------------------------------------------------
 
-def _segment_end(ptr):
-    """End address of the device allocation (caching-allocator segment) that holds `ptr`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= ptr < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
-
-
 def test_errors_leave_the_mesh(renderer):
     import torch
 
@@ -297,13 +288,12 @@ def test_errors_leave_the_mesh(renderer):
     bvh_before = renderer.read_bvh()
     n = len(mesh[0])
     ctx = renderer._ctx
-    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     v = tdev(mesh[0])
     host = np.zeros((n, 9), f32)
     assert lib.rt_refit_mesh_device(ctx, None, n) == RT_ERR_INVALID
     assert lib.rt_refit_mesh_device(ctx, C.c_void_p(host.ctypes.data), n) == RT_ERR_INVALID
     big = torch.zeros(1 << 20, dtype=torch.float32, device="cuda:0")
-    short = _segment_end(big.data_ptr()) - 36 * (n - 1)  # the allocation holds n - 1 triangles from here
+    short = segment_end(big.data_ptr()) - 36 * (n - 1)  # the allocation holds n - 1 triangles from here
     assert lib.rt_refit_mesh_device(ctx, C.c_void_p(short), n) == RT_ERR_INVALID
     v_more = tdev(np.concatenate([mesh[0], mesh[0][:1]]))
     assert lib.rt_refit_mesh_device(ctx, ptr(v_more), n + 1) == RT_ERR_INVALID

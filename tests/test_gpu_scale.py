@@ -18,7 +18,7 @@ import oracle as O
 import point_exact as PX
 import raytracing_engine_amd as R
 import scale_exact as S
-from test_gpu_point_query import dev, same_floats, tdev
+from gpu_query import dev, ptr, same_floats, tdev
 
 pytestmark = pytest.mark.gpu
 
@@ -259,7 +259,6 @@ def test_a_mesh_beyond_the_limit_is_refused_by_every_entry_before_anything_is_wr
     o, d, p = tdev(S.scaled(c["o"][:n], k)), tdev(c["d"][:n]), tdev(S.scaled(c["o"][:n], k))
     full = lambda shape, dt: torch.full(shape, -7, dtype=dt, device=dev())  # noqa: E731
     ff, fi, fl = (lambda *s: full(s, torch.float32)), (lambda *s: full(s, torch.int32)), (lambda *s: full(s, torch.int64))  # noqa: E731
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
     rot, pos = np.array([0, 0, 0, 1], f32), np.zeros(3, f32)
     fptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
     prm = r.pt_params(spp=1, bounces=1, sky=(0.2, 0.2, 0.25))

@@ -15,43 +15,21 @@ import pytest
 import ray_exact as X
 import sign_exact as SX
 import raytracing_engine_amd as R
+from gpu_query import RT_ERR_INVALID, RT_ERR_STATE, assert_untouched, bad_params, bad_pointers, busy_stream, dev, pt_frame, ptr, same_floats, sentinel, still_sentinel, tdev
+from gpu_query import set_mesh_with_surface as set_mesh
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 INF = f32(np.inf)
-RT_ERR_INVALID, RT_ERR_STATE = -1, -4
 MISS, INVALID = SX.MISS, SX.INVALID
 ALL = SX.CLOSED + SX.OPEN
-
-
-def dev():
-    import torch
-
-    return torch.device("cuda", 0)
-
-
-def tdev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
 
 
 def sides(renderer, p, **kw):
     """Numpy in, numpy out, through device tensors: inside, or (inside, crossings) with want_crossings."""
     out = renderer.query_sides(tdev(p), **kw)
     return tuple(x.cpu().numpy() for x in out) if isinstance(out, tuple) else out.cpu().numpy()
-
-
-def set_mesh(renderer, verts, **kw):
-    renderer.set_mesh(*X._with_surface(verts), **kw)
-
-
-def same_floats(a, b):
-    """Bit-equal, NaN for NaN (whatever its payload)."""
-    a, b = np.asarray(a, f32).ravel(), np.asarray(b, f32).ravel()
-    nan = np.isnan(a)
-    return a.shape == b.shape and np.array_equal(nan, np.isnan(b)) and np.array_equal(a[~nan].view(np.uint32), b[~nan].view(np.uint32))
 
 
 def check_case(renderer, p, ref, what):
@@ -200,8 +178,7 @@ def test_invalid_points(renderer):
     for kw in (dict(), dict(tune_max_blocks=1, tune_refill_min=1)):
         import torch
 
-        cr = torch.full((n, 3), -7, dtype=torch.int32, device=dev())
-        ins = torch.full((n,), -7, dtype=torch.int32, device=dev())
+        cr, ins = sentinel(n, torch.int32, cols=3), sentinel(n, torch.int32)
         renderer.query_sides(tdev(p), out=(ins, cr), want_crossings=True, **kw)
         assert np.array_equal(ins.cpu().numpy(), exp["inside"]), kw
         got = cr.cpu().numpy()
@@ -244,14 +221,13 @@ def test_dist_inout_entries(renderer):
     exp_inside[10] = INVALID
     walked = (exp_inside >= 0)
     exp_dist = np.where(walked & (ref["inside"] == 1), -dist, dist).astype(f32)
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
     for kw in (dict(), dict(tune_max_blocks=1, tune_refill_min=1)):
         tp, td = tdev(p), tdev(dist)
-        ins = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
+        ins = sentinel(n, torch.int32, 64)
         prm = R.SideQueryParams(**kw)
         assert lib.rt_query_sides_device(renderer._ctx, ptr(tp), n, C.byref(prm), ptr(ins), None, ptr(td)) == 0
         st = renderer.side_query_stats()
-        assert np.array_equal(ins.cpu().numpy()[:n], exp_inside) and (ins[n:] == -7).all(), kw
+        assert np.array_equal(ins.cpu().numpy()[:n], exp_inside) and still_sentinel(ins, 0, n), kw
         assert same_floats(td.cpu().numpy(), exp_dist), kw
         zero = td.cpu().numpy()[(kind == 3) & walked]
         assert np.array_equal(np.signbit(zero), ref["inside"][(kind == 3) & walked] == 1)  # 0 becomes -0 inside
@@ -282,14 +258,13 @@ def test_signed_distance(renderer):
     # a narrow band: beyond rmax nothing is walked and the entry stays +inf; want_points=False; out tensors with sentinels behind them
     rmax = np.full(n, f32(0.05))
     rmax[::7] = INF
-    d_buf = torch.full((n + 64,), -7.0, dtype=torch.float32, device=dev())
-    t_buf = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
+    d_buf, t_buf = sentinel(n, torch.float32, 64), sentinel(n, torch.int32, 64)
     sd, tri3, none = renderer.query_signed_distance(tp, rmax=tdev(rmax), out=(d_buf[:n], t_buf[:n]), want_points=False)
     ps, ss = renderer.point_query_stats(), renderer.side_query_stats()
     dl, tl, _ = renderer.query_points(tp, tdev(rmax), want_points=False)
     beyond = np.isinf(dl.cpu().numpy()) & valid  # as the point query itself decides it (d2 < rmax * rmax in fp32)
     assert 0.3 < beyond.mean() < 0.95 and (d[beyond] >= f32(0.999) * rmax[beyond]).all() and (d[valid & ~beyond] <= f32(1.001) * rmax[valid & ~beyond]).all()
-    assert none is None and sd.data_ptr() == d_buf.data_ptr() and (d_buf[n:] == -7.0).all() and (t_buf[n:] == -7).all()
+    assert none is None and sd.data_ptr() == d_buf.data_ptr() and still_sentinel(d_buf, 0, n) and still_sentinel(t_buf, 0, n)
     s = sd.cpu().numpy()
     assert same_floats(np.abs(s), dl.cpu().numpy()) and torch.equal(tri3, tl)
     assert (s[beyond] == INF).all() and (tri3.cpu().numpy()[beyond] == MISS).all()
@@ -300,13 +275,11 @@ def test_signed_distance(renderer):
     assert ps["points"] == n and torch.equal(tp.view(torch.int32), tdev(p).view(torch.int32))
     # inside_out through the C entry
     lib = R.load()
-    ins = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
-    c_buf = torch.full((n, 3), -7.0, dtype=torch.float32, device=dev())
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+    ins, c_buf = sentinel(n, torch.int32, 64), sentinel(n, torch.float32, cols=3)
     assert lib.rt_query_signed_distance_device(renderer._ctx, ptr(tp), None, n, None, None, ptr(d_buf), ptr(t_buf), ptr(c_buf), ptr(ins)) == 0
     renderer.synchronize()
-    assert np.array_equal(ins.cpu().numpy()[:n], np.where(valid, ref["inside"], INVALID)) and (ins[n:] == -7).all()
-    assert same_floats(c_buf.cpu().numpy(), c.cpu().numpy()) and (d_buf[n:] == -7.0).all()
+    assert np.array_equal(ins.cpu().numpy()[:n], np.where(valid, ref["inside"], INVALID)) and still_sentinel(ins, 0, n)
+    assert same_floats(c_buf.cpu().numpy(), c.cpu().numpy()) and still_sentinel(d_buf, 0, n)
 
 
 def test_pruning_happens(renderer):
@@ -333,15 +306,14 @@ def test_bounds_and_out_tensors(renderer):
     for n in (1, 65, b["n"]):
         p = tdev(b["p"][:n])
         p0 = p.clone()
-        i_buf = torch.full((n + 64,), -7, dtype=torch.int32, device=dev())
-        x_buf = torch.full((n + 64, 3), -7, dtype=torch.int32, device=dev())
+        i_buf, x_buf = sentinel(n, torch.int32, 64), sentinel(n, torch.int32, 64, cols=3)
         inside, crossings = renderer.query_sides(p, out=(i_buf[:n], x_buf[:n]), want_crossings=True)
         assert inside.data_ptr() == i_buf.data_ptr() and crossings.data_ptr() == x_buf.data_ptr()
-        assert (i_buf[n:] == -7).all() and (x_buf[n:] == -7).all()
+        assert still_sentinel(i_buf, 0, n) and still_sentinel(x_buf, 0, n)
         assert np.array_equal(inside.cpu().numpy(), b["ref"]["inside"][:n]) and np.array_equal(crossings.cpu().numpy(), b["ref"]["brute"][:n])
         i_buf.fill_(-7)
         inside = renderer.query_sides(p, out=i_buf[:n])
-        assert inside.data_ptr() == i_buf.data_ptr() and (i_buf[n:] == -7).all() and np.array_equal(inside.cpu().numpy(), b["ref"]["inside"][:n])
+        assert inside.data_ptr() == i_buf.data_ptr() and still_sentinel(i_buf, 0, n) and np.array_equal(inside.cpu().numpy(), b["ref"]["inside"][:n])
         assert torch.equal(p.view(torch.int32), p0.view(torch.int32))
     with pytest.raises(ValueError):
         renderer.query_sides(p, out=i_buf[:n - 1])
@@ -358,37 +330,13 @@ def test_stream_order(renderer):
     n = b["n"]
     p_half = tdev(b["p"] * f32(0.5))
     ref_i, ref_x = tdev(b["ref"]["inside"]), tdev(b["ref"]["brute"])
-    inside = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    crossings = torch.full((n, 3), -7, dtype=torch.int32, device=dev())
-    sd = torch.full((n,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    torch.cuda.synchronize()
-    s = torch.cuda.Stream(device=dev())
-    renderer.set_stream(s.cuda_stream)
-    try:
-        with torch.cuda.stream(s):
-            busy = torch.zeros(1 << 26, dtype=torch.float32, device=dev())
-            for _ in range(8):  # the stream has work to do when the queries are enqueued
-                busy += 1.0
-            p = p_half * 2.0
-            renderer.query_sides(p, out=(inside, crossings), want_crossings=True, sync=False)
-            renderer.query_signed_distance(p, out=(sd, tri), want_points=False, sync=False)
-            wrong = (inside != ref_i).sum() + (crossings != ref_x).sum() + ((sd < 0) != (ref_i == 1)).sum() + (tri < 0).sum()
-        s.synchronize()
-        assert int(wrong) == 0 and float(busy[0]) == 8.0
-    finally:
-        renderer.synchronize()
-        renderer.set_stream(None)
-
-
-def _segment_end(ptr):
-    """End address of the device allocation (caching-allocator segment) that holds `ptr`."""
-    import torch
-
-    for seg in torch.cuda.memory_snapshot():
-        if seg["address"] <= ptr < seg["address"] + seg["total_size"]:
-            return seg["address"] + seg["total_size"]
-    raise AssertionError("pointer not in any segment")
+    inside, crossings, sd, tri = sentinel(n, torch.int32), sentinel(n, torch.int32, cols=3), sentinel(n, torch.float32), sentinel(n, torch.int32)
+    with busy_stream(renderer):
+        p = p_half * 2.0
+        renderer.query_sides(p, out=(inside, crossings), want_crossings=True, sync=False)
+        renderer.query_signed_distance(p, out=(sd, tri), want_points=False, sync=False)
+        wrong = (inside != ref_i).sum() + (crossings != ref_x).sum() + ((sd < 0) != (ref_i == 1)).sum() + (tri < 0).sum()
+    assert int(wrong) == 0
 
 
 def test_errors_write_nothing(renderer):
@@ -398,12 +346,8 @@ def test_errors_write_nothing(renderer):
     b = set_batch(renderer)
     n = 1000
     p = tdev(b["p"][:n])
-    ins = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    cr = torch.full((n, 3), -7, dtype=torch.int32, device=dev())
-    dist = torch.full((n,), -7.0, dtype=torch.float32, device=dev())
-    tri = torch.full((n,), -7, dtype=torch.int32, device=dev())
-    c = torch.full((n, 3), -7.0, dtype=torch.float32, device=dev())
-    ptr = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+    ins, cr = sentinel(n, torch.int32), sentinel(n, torch.int32, cols=3)
+    dist, tri, c = sentinel(n, torch.float32), sentinel(n, torch.int32), sentinel(n, torch.float32, cols=3)
     fresh = R.Renderer(0)
     try:
         assert lib.rt_query_sides_device(fresh._ctx, ptr(p), n, None, ptr(ins), ptr(cr), ptr(dist)) == RT_ERR_STATE  # no mesh
@@ -411,23 +355,18 @@ def test_errors_write_nothing(renderer):
     finally:
         fresh.close()
     ctx = renderer._ctx
-    host = np.zeros((n, 3), f32)
-    hp = C.c_void_p(host.ctypes.data)
-    big = torch.zeros(1 << 20, dtype=torch.float32, device=dev())
-    short3 = C.c_void_p(_segment_end(big.data_ptr()) - 12 * (n - 1))  # the allocation holds n - 1 rows from here
-    short1 = C.c_void_p(_segment_end(big.data_ptr()) - 4 * (n - 1))
+    bp = bad_pointers(n, short3=12, short1=4)  # the allocation holds n - 1 rows from the short ones
+    hp, short3, short1 = bp.hp, bp.short3, bp.short1
     S, P = R.SideQueryParams, R.PointQueryParams
 
     def untouched(k):
-        renderer.synchronize()
-        assert (ins == -7).all() and (cr == -7).all() and (dist == -7.0).all() and (tri == -7).all() and (c == -7.0).all() and (big == 0).all(), k
+        assert_untouched(renderer, (ins, cr, dist, tri, c), bp.big, k)
 
     calls = [(None, n, None, ptr(ins), ptr(cr), ptr(dist)), (ptr(p), n, None, None, ptr(cr), ptr(dist)), (hp, n, None, ptr(ins), ptr(cr), ptr(dist)),
              (ptr(p), n, None, hp, ptr(cr), ptr(dist)), (ptr(p), n, None, ptr(ins), hp, ptr(dist)), (ptr(p), n, None, ptr(ins), ptr(cr), hp),
              (short3, n, None, ptr(ins), ptr(cr), ptr(dist)), (ptr(p), n, None, short1, ptr(cr), ptr(dist)), (ptr(p), n, None, ptr(ins), short3, ptr(dist)),
-             (ptr(p), n, None, ptr(ins), ptr(cr), short1), (ptr(p), (1 << 30) + 1, None, ptr(ins), ptr(cr), ptr(dist)),
-             (ptr(p), n, C.byref(S(tune_refill_min=65)), ptr(ins), ptr(cr), ptr(dist)), (ptr(p), n, C.byref(S(tune_blocks_per_cu=9)), ptr(ins), ptr(cr), ptr(dist)),
-             (ptr(p), n, C.byref(S(tune_lds_stack=79)), ptr(ins), ptr(cr), ptr(dist)), (ptr(p), n, C.byref(S(count_traversal=2)), ptr(ins), ptr(cr), ptr(dist))]
+             (ptr(p), n, None, ptr(ins), ptr(cr), short1), (ptr(p), (1 << 30) + 1, None, ptr(ins), ptr(cr), ptr(dist))] + \
+        [(ptr(p), n, prm, ptr(ins), ptr(cr), ptr(dist)) for prm in bad_params(S)]
     for k, args in enumerate(calls):
         assert lib.rt_query_sides_device(ctx, *args) == RT_ERR_INVALID, k
         untouched(k)
@@ -496,9 +435,7 @@ def test_rendering_and_sharing_are_undisturbed(renderer):
     kw = dict(pos=(0, 0.1, 4.0), spp=2, bounces=2, seed=3, sky=(0.2, 0.2, 0.3))
 
     def frame(r, **more):
-        rgb = r.render_pt(**kw, **more)
-        st = r.pt_stats()
-        return rgb, (st["camera_rays"], st["bounce_rays"], st["shadow_rays"], st["stack_overflow"])
+        return pt_frame(r, **kw, **more)
 
     before, before_spilling = frame(renderer), frame(renderer, tune_lds_stack=1, tune_no_overlap=2)
     assert before[1][0] > 0 and before[1][3] == 0

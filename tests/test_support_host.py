@@ -1,6 +1,7 @@
 """CPU tests of what the tests share: tests/abi_boundary.py's layout check fails on a wrong mirror, a wrong member list and a wrong
-constant; tests/native_ref.py's unpack consumes its stream exactly and its run refuses a program that fails or does not say OK; and
-abi_boundary.cpu_renderer() refuses what Renderer's own tensor checks refuse apart from the device."""
+constant; tests/native_ref.py's unpack consumes its stream exactly and its run refuses a program that fails or does not say OK;
+abi_boundary.cpu_renderer() refuses what Renderer's own tensor checks refuse apart from the device; and of tests/gpu_listing.py what
+is pure: expected_fill on a case computed by hand, and the three Listing descriptions against the product's names."""
 import ctypes as C
 import subprocess
 
@@ -8,8 +9,10 @@ import numpy as np
 import pytest
 
 import abi_boundary as AB
+import gpu_listing as L
 import native_ref as NR
 import raytracing_engine_amd as R
+from raytracing_engine_amd import _lib
 
 KNN = AB.Kind(functions=(), params="KnnQueryParams", stats="KnnQueryStats", params_c="rt_knn_query_params", stats_c="rt_knn_query_stats",
               params_fields=["tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks", "count_traversal"],
@@ -113,3 +116,42 @@ def test_the_cpu_renderer_refuses_what_the_renderer_refuses_apart_from_the_devic
                 assert verdict(real, check, t, *args) == ("refused", None), (check, t)  # (the device is what the real one refuses a CPU tensor for)
             seen.add(want[0])
         assert seen == {"ok", "refused"}, check
+
+
+def test_expected_fill_on_three_items_by_hand():
+    """Three items with lists of 2, 3 and 1 entries at [0, 2), [2, 5), [5, 6) of the reference; 8 entries of room."""
+    offsets, count, capacity = [0, 2, 5, 6], [2, 3, 1], 8
+    # [1, 3) fits its 2 entries; [3, 5) is one short of its 3: the first 2, 1 beyond; [5, 9) ends beyond the capacity: untouched, incomplete
+    got = L.expected_fill([1, 3, 5, 9], capacity, offsets, count)
+    assert got["dst"].tolist() == [1, 2, 3, 4] and got["src"].tolist() == [0, 1, 2, 3] and (got["written"], got["beyond"], got["incomplete"]) == (4, 1, 1)
+    # [4, 2) is reversed and [2, 2) empty: nothing written, all 2 + 3 entries beyond, but nothing that a capacity would mend; [2, 3) fits
+    got = L.expected_fill([4, 2, 2, 3], capacity, offsets, count)
+    assert got["dst"].tolist() == [2] and got["src"].tolist() == [5] and (got["written"], got["beyond"], got["incomplete"]) == (1, 5, 0)
+    # [-1, 1) begins below 0: untouched though long enough, incomplete; the other two fit
+    got = L.expected_fill([-1, 1, 4, 5], capacity, offsets, count)
+    assert got["dst"].tolist() == [1, 2, 3, 4] and got["src"].tolist() == [2, 3, 4, 5] and (got["written"], got["beyond"], got["incomplete"]) == (4, 0, 1)
+    # the count step's own offsets: everything, in place
+    got = L.expected_fill(offsets, capacity, offsets, count)
+    assert got["dst"].tolist() == got["src"].tolist() == list(range(6)) and (got["written"], got["beyond"], got["incomplete"]) == (6, 0, 0)
+    # an invalid item (a negative count) has no entries, whatever its slice
+    got = L.expected_fill([0, 2, 5, 6], capacity, offsets, [2, -2, 1])
+    assert got["dst"].tolist() == [0, 1, 5] and got["src"].tolist() == [0, 1, 5] and (got["written"], got["beyond"], got["incomplete"]) == (3, 0, 0)
+
+
+@pytest.mark.parametrize("kind", L.KINDS, ids=[k.stem for k in L.KINDS])
+def test_a_listing_names_what_the_product_has(kind):
+    stats, params = getattr(_lib, kind.stats_class), getattr(_lib, kind.params)
+    members = [n for n, _ in stats._fields_]
+    for name in (kind.items, kind.invalid, kind.found, kind.written, kind.incomplete, "slice_overflow", "stack_overflow", "nodes_visited", "tris_tested", "launches", "ms"):
+        assert name in members, name
+    assert len({kind.items, kind.invalid, kind.found, kind.written, kind.incomplete}) == 5
+    assert "count_traversal" in [n for n, _ in params._fields_] and getattr(R, kind.params) is params
+    for name in kind.functions():
+        assert name in _lib.PROTOTYPES, name
+    count, fill, lst = (_lib.PROTOTYPES[name][1] for name in kind.functions())
+    source = len(kind.null_source)
+    assert len(count) == 1 + source + 4 and len(fill) == 1 + source + 6 and len(lst) == 1 + source + 7  # ctx, the source, n, params, the outputs
+    assert count[1 + source + 1] == fill[1 + source + 1] == lst[1 + source + 1] == C.POINTER(params)
+    for method in ("count_" + kind.stem, "list_" + kind.stem, kind.stats):
+        assert callable(getattr(R.Renderer, method)), method
+    assert (kind.key_dtype == np.int32) == kind.tri_first and [key for key, _ in kind.payload] == (["tri", kind.key] if kind.tri_first else [kind.key, "tri"])
