@@ -19,7 +19,7 @@
  *     submit + fence  src/main.rs:909-927                          rt_render / rt_render_spp /
  *                                                                  rt_render_device
  *   swapchain *_UNORM colour attachment  src/main.rs:471-486       rt_read_rgba8
- *   (none: the reference cannot read a pyramid level back)         rt_read_level / rt_read_level_image  [test hooks]
+ *   (none: the reference cannot read a pyramid level back)         rt_read_level / rt_read_level_image / rt_render_chains  [test hooks]
  *   FPS println  src/main.rs:719,730                               rt_get_stats
  *   swapchain images + one fence per image: wait the image's fence,
  *     record, submit after the previous frame, present
@@ -206,6 +206,15 @@ int rt_read_level(rt_ctx* ctx, uint32_t level, float* out, uint32_t* w, uint32_t
  * batch's last image (RT_ERR_INVALID beyond it), *sample = the sample index that image belongs to (the batch's first sample +
  * image).  rt_read_level is this call with the last image, which holds the frame's last sample. */
 int rt_read_level_image(rt_ctx* ctx, uint32_t level, uint32_t image, float* out, uint32_t* w, uint32_t* h, uint32_t* sample);
+/* Test hook: rt_render (1 spp, jitter 0, the whole frame; rgb_out and depth_out bit-equal to its) that also returns what every
+ * secondary march did.  chain_out: host, width*height*(reflections + transmissions)*7 f32, rows by pixel (row-major), the mirror
+ * bounces first, in order, then the transmission passes; a row is eye[3], dir[3], len: eye = the point the formulas at
+ * rt_config.reflections / transmissions call P (mirror ray) or Q (transmitted ray) - the march starts at eye + dir -, dir = r or D,
+ * len = 1 + traceCone(...) exactly as computed (a value >= render_dist ends the chain and is still recorded).  A march that did
+ * not run - a miss pixel, a chain that ended earlier, k < 0 or k2 < 0 in a refraction - leaves seven NaNs.
+ * RT_ERR_INVALID for a NULL output, RT_ERR_STATE when reflections and transmissions are both 0 or the partition has more than
+ * one rank; nothing is written then. */
+int rt_render_chains(rt_ctx* ctx, const float rot[4], const float pos[3], float* rgb_out, float* depth_out, float* chain_out);
 /* Last frame as a *_UNORM swapchain would hold it (src/main.rs:471-486): linear, clamped,
  * round-to-nearest, alpha = 255 (never written by fragment.glsl:138,159). width*height*4 bytes. */
 int rt_read_rgba8(rt_ctx* ctx, uint8_t* rgba_out);

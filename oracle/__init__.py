@@ -79,6 +79,8 @@ def lib():
         L.ora_render_a.argtypes = [C.POINTER(Scene), C.POINTER(Config), C.c_uint32, C.c_uint32, fp, fp, fp, fp,
                                    C.POINTER(fp), fp, C.POINTER(Counters), C.c_int]
         L.ora_render_a.restype = C.c_int
+        L.ora_render_a_chains.argtypes = L.ora_render_a.argtypes + [fp]
+        L.ora_render_a_chains.restype = C.c_int
         for name in ("ora_trace_bruteforce", "ora_trace_cone", "ora_shadow_ray"):
             f = getattr(L, name)
             f.argtypes = [C.POINTER(Scene), C.POINTER(Config), fp, fp, C.c_float]
@@ -136,8 +138,9 @@ def rotate(q, v):
 
 
 def render_a(scene, width, height, rot=(0, 0, 0, 1), pos=(0, 0, 0), ratio=None, cfg=None, jitter=(0, 0),
-             want_levels=True, want_rgb=True, threads=0):
-    """One path-A frame. Returns dict(levels=[...], rgb=HxWx3, counters={...})."""
+             want_levels=True, want_rgb=True, threads=0, want_chains=False):
+    """One path-A frame. Returns dict(levels=[...], rgb=HxWx3, counters={...}); want_chains: and chains = H x W x (reflections +
+    transmissions) x 7, what every secondary march did (ora_render_a_chains)."""
     L = lib()
     cfg = cfg or default_config()
     if ratio is None:
@@ -158,12 +161,19 @@ def render_a(scene, width, height, rot=(0, 0, 0, 1), pos=(0, 0, 0), ratio=None, 
             lv_ptrs[i] = a.ctypes.data_as(fp)
     rgb = np.zeros((height, width, 3), np.float32) if want_rgb else None
     ct = Counters()
-    rc = L.ora_render_a(C.byref(scene), C.byref(cfg), width, height, ratio_p, rot_p, pos_p, jit_p,
-                        lv_ptrs if want_levels else None, rgb.ctypes.data_as(fp) if want_rgb else None,
-                        C.byref(ct), threads)
+    args = (C.byref(scene), C.byref(cfg), width, height, ratio_p, rot_p, pos_p, jit_p,
+            lv_ptrs if want_levels else None, rgb.ctypes.data_as(fp) if want_rgb else None, C.byref(ct), threads)
+    out = {"levels": levels, "rgb": rgb}
+    if want_chains:
+        assert want_rgb
+        out["chains"] = np.zeros((height, width, cfg.reflections + cfg.transmissions, 7), np.float32)
+        rc = L.ora_render_a_chains(*args, out["chains"].ctypes.data_as(fp))
+    else:
+        rc = L.ora_render_a(*args)
     if rc != 0:
         raise RuntimeError(f"ora_render_a failed: {rc}")
-    return {"levels": levels, "rgb": rgb, "counters": ct.as_dict()}
+    out["counters"] = ct.as_dict()
+    return out
 
 
 def trace_cone(scene, origin, direction, threshold, cfg=None, brute=False):

@@ -115,6 +115,13 @@ void ora_camera_quat(float yaw, float pitch, float out[4]);
 int ora_render_a(const ora_scene* scene, const ora_config* cfg, uint32_t width, uint32_t height,
                  const float ratio[2], const float rot[4], const float pos[3], const float jitter[2],
                  float* const* levels, float* rgb, ora_counters* counters, int threads);
+/* The same frame, and what every secondary march did: chains (needs rgb; may be NULL) receives width*height*(reflections +
+ * transmissions) rows of eye[3], dir[3], len, by pixel, the mirror bounces first, then the transmission passes; eye = P (mirror
+ * ray) or Q (transmitted ray) of the formulas above, dir = r or D, len = 1 + traceCone(eye + dir, dir, RAY_RADIUS) as computed
+ * (>= RENDER_DIST ends the chain and is recorded); seven NaNs for a march that did not run. */
+int ora_render_a_chains(const ora_scene* scene, const ora_config* cfg, uint32_t width, uint32_t height,
+                        const float ratio[2], const float rot[4], const float pos[3], const float jitter[2],
+                        float* const* levels, float* rgb, ora_counters* counters, int threads, float* chains);
 
 /* brute-force marcher ("algorithm 1", shaders/tracing_algorithms.txt:2-13) for one ray:
  * independent cross-check of traceCone; returns the accumulated length */

@@ -356,10 +356,19 @@ static inline void shade_point(const ora_scene* sc, const ora_config* cfg, v3 po
     surf->object = object;
 }
 
+static inline void record_march(float* row, v3 eye, v3 dir, float len) {
+    row[0] = eye.x; row[1] = eye.y; row[2] = eye.z;
+    row[3] = dir.x; row[4] = dir.y; row[5] = dir.z;
+    row[6] = len;
+}
+
 /* ---- shaders/fragment.glsl:127-187 main, one invocation -------------------------------- */
 static inline void shade_pixel(const ora_scene* sc, const ora_config* cfg, uint32_t px, uint32_t py, const float view[2],
                                const float ratio[2], const float rot[4], v3 pos, const float jitter[2], float total_dist,
-                               float out[3], ora_counters* ct) {
+                               float out[3], ora_counters* ct, float* rec) {
+    /* rec (ora_render_a_chains; may be NULL): (reflections + transmissions) rows of eye[3], dir[3], len, one per secondary march */
+    if (rec)
+        for (uint32_t q = 0; q < (cfg->reflections + cfg->transmissions) * 7u; q++) rec[q] = NAN;
     /* :129  gl_FragCoord.xy * 2 / cs.view - 1.0, gl_FragCoord = pixel + 0.5 */
     float nx = (((float)px + 0.5f) * 2.0f) / view[0] - 1.0f + jitter[0];
     float ny = (((float)py + 0.5f) * 2.0f) / view[1] - 1.0f + jitter[1];
@@ -386,6 +395,7 @@ static inline void shade_pixel(const ora_scene* sc, const ora_config* cfg, uint3
         uint64_t dummy_steps = 0, dummy_sdf = 0;
         ct->reflection_rays++;
         const float len = 1.0f + trace_cone3(sc, cfg, v3_add(position, r), r, cfg->ray_radius, &dummy_steps, &dummy_sdf);
+        if (rec) record_march(rec + (size_t)bounce * 7u, position, r, len);
         if (!(len < cfg->render_dist)) break;
         const v3 hit = v3_fma(r, fmaxf(len, 0.0f), position);
         float rgb[3];
@@ -435,6 +445,7 @@ static inline void shade_pixel(const ora_scene* sc, const ora_config* cfg, uint3
         uint64_t dummy_steps = 0, dummy_sdf = 0;
         ct->transmission_rays++;
         const float len = 1.0f + trace_cone3(sc, cfg, v3_add(Q, D), D, cfg->ray_radius, &dummy_steps, &dummy_sdf);
+        if (rec) record_march(rec + (size_t)(cfg->reflections + pass) * 7u, Q, D, len);
         if (!(len < cfg->render_dist)) break;
         const v3 hit = v3_fma(D, fmaxf(len, 0.0f), Q);
         float rgb[3];
@@ -455,6 +466,13 @@ static int scene_valid(const ora_scene* s) {
 int ora_render_a(const ora_scene* scene, const ora_config* cfg, uint32_t width, uint32_t height, const float ratio[2],
                  const float rot[4], const float pos[3], const float jitter[2], float* const* levels, float* rgb,
                  ora_counters* counters, int threads) {
+    return ora_render_a_chains(scene, cfg, width, height, ratio, rot, pos, jitter, levels, rgb, counters, threads, NULL);
+}
+
+int ora_render_a_chains(const ora_scene* scene, const ora_config* cfg, uint32_t width, uint32_t height, const float ratio[2],
+                        const float rot[4], const float pos[3], const float jitter[2], float* const* levels, float* rgb,
+                        ora_counters* counters, int threads, float* chains) {
+    if (chains && !rgb) return -1;
     if (!scene || !cfg || !ratio || !rot || !pos || width == 0 || height == 0) return -1;
     if (!scene_valid(scene)) return -2;
     static const float zero2[2] = {0.0f, 0.0f};
@@ -504,7 +522,8 @@ int ora_render_a(const ora_scene* scene, const ora_config* cfg, uint32_t width, 
             memset(&ct, 0, sizeof ct);
             for (uint32_t px = 0; px < width; px++)
                 shade_pixel(scene, cfg, px, py, view, ratio, rot, p, jitter, prev[(size_t)py * prev_w + px],
-                            rgb + ((size_t)py * width + px) * 3, &ct);
+                            rgb + ((size_t)py * width + px) * 3, &ct,
+                            chains ? chains + ((size_t)py * width + px) * (cfg->reflections + cfg->transmissions) * 7u : NULL);
             hit += ct.hit_pixels; srays += ct.shadow_rays; ssteps += ct.shadow_steps; ssdf += ct.shadow_sdf; rrays += ct.reflection_rays; trays += ct.transmission_rays;
         }
         total.hit_pixels = hit; total.shadow_rays = srays; total.shadow_steps = ssteps; total.shadow_sdf = ssdf; total.reflection_rays = rrays; total.transmission_rays = trays;

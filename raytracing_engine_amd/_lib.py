@@ -232,6 +232,7 @@ PROTOTYPES = {
     "rt_tile_info": (C.c_int, [_vp, _u32p, _u32p, _u32p]),
     "rt_set_stream": (C.c_int, [_vp, _vp]),
     "rt_render": (C.c_int, [_vp, _fp, _fp, _fp, _fp]),
+    "rt_render_chains": (C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp]),
     "rt_render_spp": (C.c_int, [_vp, _fp, _fp, C.c_uint32, _fp]),
     "rt_render_device": (C.c_int, [_vp, _fp, _fp, C.c_uint32, _vp, C.c_int]),
     "rt_detile_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp]),

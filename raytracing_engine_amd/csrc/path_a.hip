@@ -286,9 +286,24 @@ __device__ __forceinline__ void shade_point(const ShadeSet& S, const ShadeParams
 // unit off the surface (the shadowRay idiom of :176) and is marched by compute.glsl's own loop with cone threshold RAY_RADIUS;
 // a hit is shaded with the previous hit as the eye and added with weight prod(reflectivity * mat.specular).
 // n_points / n_refl count the shaded reflection hits and the mirror rays of this lane.
-template <int N, bool REP, bool REFL>
+// REC (test hook rt_render_chains): every secondary march leaves eye[3], dir[3], len in row `march` of this pixel's rows at `rec`
+// (mirror bounces first, then the transmission passes); REC = false compiles to nothing.
+template <bool REC>
+__device__ __forceinline__ void record_march(float* rec, uint32_t march, v3 eye, v3 dir, float len) {
+    if (!REC) return;
+    float* row = rec + (size_t)march * 7u;
+    row[0] = eye.x;
+    row[1] = eye.y;
+    row[2] = eye.z;
+    row[3] = dir.x;
+    row[4] = dir.y;
+    row[5] = dir.z;
+    row[6] = len;
+}
+
+template <int N, bool REP, bool REFL, bool REC = false>
 __device__ __forceinline__ bool shade_pixel(const ShadeSet S, const ShadeParams p, float jx, float jy, uint32_t px, uint32_t py, float total_dist, float& r,
-                                            float& g, float& b, uint32_t& n_points, uint32_t& n_refl, uint32_t& n_trans) {
+                                            float& g, float& b, uint32_t& n_points, uint32_t& n_refl, uint32_t& n_trans, float* rec = nullptr) {
     r = g = b = 0.0f;
     if (!(total_dist < p.render_dist)) return false;  // :137-140
     // :129-133  gl_FragCoord.xy * 2 / cs.view - 1.0   (gl_FragCoord = pixel + 0.5)
@@ -312,6 +327,7 @@ __device__ __forceinline__ bool shade_pixel(const ShadeSet S, const ShadeParams 
             const v3 rd = mk(__builtin_fmaf(-kk, surf.normal.x, step.x), __builtin_fmaf(-kk, surf.normal.y, step.y), __builtin_fmaf(-kk, surf.normal.z, step.z));
             n_refl++;
             const float len = 1.0f + trace_cone<N, 3, REP>(S.sphere, position + rd, rd, p.ray_radius, p.render_dist, p.max_steps, rep);
+            record_march<REC>(rec, bounce, position, rd, len);
             if (!(len < p.render_dist)) break;
             const v3 hit = fma3(rd, fmax_(len, 0.0f), position);
             float rr, rg, rb;
@@ -360,6 +376,7 @@ __device__ __forceinline__ bool shade_pixel(const ShadeSet S, const ShadeParams 
             }
             n_trans++;
             const float len = 1.0f + trace_cone<N, 3, REP>(S.sphere, Q + D, D, p.ray_radius, p.render_dist, p.max_steps, rep);
+            record_march<REC>(rec, p.reflections + pass, Q, D, len);
             if (!(len < p.render_dist)) break;
             const v3 hit = fma3(D, fmax_(len, 0.0f), Q);
             float rr, rg, rb;
@@ -391,7 +408,11 @@ __device__ __forceinline__ float quad_bcast(float v, int j) {
 // per pixel, one sample each per round of four; lane 0 of the quad then adds the four colours in sample order (the other lanes'
 // values through DPP quad broadcasts) - the same sum, bit for bit, from four times as many waves of a quarter the length: a frame's
 // last waves (the pixels with the longest shadow marches) hold the machine for a quarter of the time.
-template <int N, bool REP, bool REFL, bool SP = false>
+// REC (rt_render_chains only, on the one-sample non-SP launch): the secondary marches are recorded, (reflections + transmissions)
+// rows of 7 floats per pixel of the full frame, row-major by pixel, NaNs for a march that did not run.  The records' address
+// travels in the word behind the counter slots (counters[kChainSlot]), so the kernel's arguments are those of every other instantiation.
+constexpr uint32_t kChainSlot = 4u * 1024u;
+template <int N, bool REP, bool REFL, bool SP = false, bool REC = false>
 __global__ __launch_bounds__(256) void shade_kernel(const ShadeSet S, const ShadeParams p, const float* __restrict__ depth,
                                                     float* __restrict__ dst, uint64_t* __restrict__ counters) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -421,7 +442,13 @@ __global__ __launch_bounds__(256) void shade_kernel(const ShadeSet S, const Shad
         const uint32_t sb = SP ? sb0 + smp : sb0;
         float jx, jy, sr = 0.0f, sg = 0.0f, sbl = 0.0f;
         sample_jitter(p.sample0 + sb, p.n_strata, p.width, p.height, &jx, &jy);
-        const bool hit = inside && shade_pixel<N, REP, REFL>(S, p, jx, jy, px, py, depth[(size_t)sb * p.depth_stride + (size_t)py * p.depth_w + px], sr, sg, sbl, n_points, n_refl, n_trans);  // :135
+        float* rec = nullptr;
+        if (REC && inside) {
+            const uint32_t rows = p.reflections + p.transmissions;
+            rec = reinterpret_cast<float*>(counters[kChainSlot]) + ((size_t)py * p.width + px) * rows * 7u;
+            for (uint32_t q = 0; q < rows * 7u; q++) rec[q] = __builtin_nanf("");
+        }
+        const bool hit = inside && shade_pixel<N, REP, REFL, REC>(S, p, jx, jy, px, py, depth[(size_t)sb * p.depth_stride + (size_t)py * p.depth_w + px], sr, sg, sbl, n_points, n_refl, n_trans, rec);  // :135
 #pragma unroll
         for (int j = 0; j < (SP ? 4 : 1); j++) {  // the round's samples in index order (SP: sample j sits in lane j of the quad)
             const float cr = SP ? quad_bcast(sr, j) : sr, cg = SP ? quad_bcast(sg, j) : sg, cb = SP ? quad_bcast(sbl, j) : sbl;
@@ -603,8 +630,13 @@ static void cone_launch_n(hipStream_t st, dim3 grid, const SphereSet& S, const C
 }
 template <int N>
 static void shade_launch_n(hipStream_t st, dim3 grid, const ShadeSet& S, const ShadeParams& p, const float* depth, float* dst,
-                           uint64_t* counters) {
+                           uint64_t* counters, bool chain) {
     const bool rep = p.repeat[0] > 0.0f || p.repeat[1] > 0.0f || p.repeat[2] > 0.0f;
+    if (chain) {  // rt_render_chains: the recording instantiation, nowhere else
+        if (rep) hipLaunchKernelGGL((shade_kernel<N, true, true, false, true>), grid, dim3(256), 0, st, S, p, depth, dst, counters);
+        else hipLaunchKernelGGL((shade_kernel<N, false, true, false, true>), grid, dim3(256), 0, st, S, p, depth, dst, counters);
+        return;
+    }
     // the reference as shipped (no reflections, no transmission, no repetition) first; the sketched variants behind it
     if (p.reflections == 0 && p.transmissions == 0) {
         if (rep) hipLaunchKernelGGL((shade_kernel<N, true, false>), grid, dim3(256), 0, st, S, p, depth, dst, counters);
@@ -638,24 +670,26 @@ int launch_cone_level(Ctx* c, const SphereSet& S, uint32_t n_obj, const ConeLeve
     return RT_OK;
 }
 
-int launch_shade(Ctx* c, const ShadeSet& S, uint32_t n_obj, const ShadeParams& p, const float* depth, float* dst, uint64_t* counters) {
+int launch_shade(Ctx* c, const ShadeSet& S, uint32_t n_obj, const ShadeParams& p, const float* depth, float* dst, uint64_t* counters, bool chain) {
     if (n_obj < 1 || n_obj > RT_MAX_OBJECTS) return c->fail(RT_ERR_INVALID, "objCount %u out of [1,8]", n_obj);
     if (p.depth_w < p.width) return c->fail(RT_ERR_INVALID, "depth pitch %u < width %u", p.depth_w, p.width);
     if (p.n_batch < 1 || p.n_strata < 1) return c->fail(RT_ERR_INVALID, "sample batch %u / strata %u", p.n_batch, p.n_strata);
+    // the recorded rows are indexed by the pixel of the full frame: one sample, the whole frame, a chain to record
+    if (chain && (p.n_batch != 1 || p.tile_major || p.part.n_ranks != 1 || p.reflections + p.transmissions == 0)) return c->fail(RT_ERR_INVALID, "chain recording needs one sample of the whole frame and a chain");
     const uint32_t total = p.part.tiles_x * p.part.tiles_y;
     if (p.part.n_ranks == 0 || p.part.rank >= p.part.n_ranks) return c->fail(RT_ERR_INVALID, "bad partition");
     const uint32_t owned = total > p.part.rank ? (total - p.part.rank + p.part.n_ranks - 1u) / p.part.n_ranks : 0u;
     if (owned == 0) return RT_OK;
     const dim3 grid(owned * 16u);
     switch (n_obj) {
-        case 1: shade_launch_n<1>(c->stream, grid, S, p, depth, dst, counters); break;
-        case 2: shade_launch_n<2>(c->stream, grid, S, p, depth, dst, counters); break;
-        case 3: shade_launch_n<3>(c->stream, grid, S, p, depth, dst, counters); break;
-        case 4: shade_launch_n<4>(c->stream, grid, S, p, depth, dst, counters); break;
-        case 5: shade_launch_n<5>(c->stream, grid, S, p, depth, dst, counters); break;
-        case 6: shade_launch_n<6>(c->stream, grid, S, p, depth, dst, counters); break;
-        case 7: shade_launch_n<7>(c->stream, grid, S, p, depth, dst, counters); break;
-        default: shade_launch_n<8>(c->stream, grid, S, p, depth, dst, counters); break;
+        case 1: shade_launch_n<1>(c->stream, grid, S, p, depth, dst, counters, chain); break;
+        case 2: shade_launch_n<2>(c->stream, grid, S, p, depth, dst, counters, chain); break;
+        case 3: shade_launch_n<3>(c->stream, grid, S, p, depth, dst, counters, chain); break;
+        case 4: shade_launch_n<4>(c->stream, grid, S, p, depth, dst, counters, chain); break;
+        case 5: shade_launch_n<5>(c->stream, grid, S, p, depth, dst, counters, chain); break;
+        case 6: shade_launch_n<6>(c->stream, grid, S, p, depth, dst, counters, chain); break;
+        case 7: shade_launch_n<7>(c->stream, grid, S, p, depth, dst, counters, chain); break;
+        default: shade_launch_n<8>(c->stream, grid, S, p, depth, dst, counters, chain); break;
     }
     RT_HIP(c, hipGetLastError());
     return RT_OK;

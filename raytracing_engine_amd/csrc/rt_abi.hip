@@ -204,7 +204,7 @@ int enqueue_samples(Ctx* c, const float rot[4], const float pos[3], uint32_t s0,
     int rc;
     {
         rt::RoctxRange rr("rt.path_a.shade");
-        rc = rt::launch_shade(c, set, c->scene.objCount, sp, c->d_level[count - 1], dst, c->d_counters);
+        rc = rt::launch_shade(c, set, c->scene.objCount, sp, c->d_level[count - 1], dst, c->d_counters, c->d_chain != nullptr);
     }
     if (rc) return rc;
     if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++], c->stream));
@@ -224,6 +224,8 @@ int render_common(Ctx* c, const float rot[4], const float pos[3], uint32_t spp, 
 
     const bool stage_events = c->cfg.profile_stages != 0;
     RT_HIP(c, hipMemsetAsync(c->d_counters, 0, 4 * 1024 * sizeof(uint64_t), c->stream));
+    // rt_render_chains: the records' address, in the word behind the slots (the source outlives the copy: the call synchronises before it clears d_chain)
+    if (c->d_chain) RT_HIP(c, hipMemcpyAsync(c->d_counters + 4 * 1024, &c->d_chain, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     RT_HIP(c, hipEventRecord(c->ev_begin, c->stream));
     const uint32_t batch = c->cfg.fuse_levels ? 1u : std::min(spp, kSampleBatch);
     if (int rc = ensure_levels(c, batch)) return rc;
@@ -362,7 +364,7 @@ int rt_create(rt_ctx** out, int device_ordinal) {
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&c->ev_begin);
     if (e == hipSuccess) e = hipEventCreate(&c->ev_end);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_counters, 4 * 1024 * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->d_counters, (4 * 1024 + 1) * sizeof(uint64_t));
     for (uint32_t i = 0; e == hipSuccess && i < RT_MAX_LEVELS + 2; i++) {
         hipEvent_t ev;
         e = hipEventCreate(&ev);
@@ -536,6 +538,36 @@ int rt_render(rt_ctx* ctx, const float rot[4], const float pos[3], float* rgb_ou
         const uint32_t l = c->level_count - 1;
         RT_HIP(c, hipMemcpy(depth_out, c->d_level[l] + (size_t)c->last_image * c->dims[l][0] * c->dims[l][1], (size_t)c->dims[l][0] * c->dims[l][1] * sizeof(float), hipMemcpyDeviceToHost));
     }
+    return RT_OK;
+}
+
+int rt_render_chains(rt_ctx* ctx, const float rot[4], const float pos[3], float* rgb_out, float* depth_out, float* chain_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    if (!rot || !pos || !rgb_out || !depth_out || !chain_out) return c->fail(RT_ERR_INVALID, "rot, pos and the three outputs must not be NULL");
+    if (!c->have_scene) return c->fail(RT_ERR_STATE, "rt_set_scene has not been called");
+    if (!c->width) return c->fail(RT_ERR_STATE, "rt_resize has not been called");
+    const uint32_t rows = c->cfg.reflections + c->cfg.transmissions;
+    if (rows == 0) return c->fail(RT_ERR_STATE, "no chain to record: reflections and transmissions are both 0");
+    if (c->part.n_ranks > 1) return c->fail(RT_ERR_STATE, "the chain hook records the whole frame: partition %u of %u", c->part.rank, c->part.n_ranks);
+    if (int rc = rt::bind(c)) return rc;
+    const size_t n = (size_t)c->width * c->height * rows * 7u;
+    float* d_chain = nullptr;
+    if (hipMalloc((void**)&d_chain, n * sizeof(float)) != hipSuccess) return c->fail(RT_ERR_OOM, "chain records (%zu bytes)", n * sizeof(float));
+    c->d_chain = d_chain;
+    int rc = render_common(c, rot, pos, 1, c->d_rgb, 0, true);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing may still read d_chain or write the records when they go
+    c->d_chain = nullptr;
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        const uint32_t l = c->level_count - 1;
+        e = hipMemcpy(rgb_out, c->d_rgb, (size_t)c->width * c->height * 3 * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(depth_out, c->d_level[l] + (size_t)c->last_image * c->dims[l][0] * c->dims[l][1], (size_t)c->dims[l][0] * c->dims[l][1] * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(chain_out, d_chain, n * sizeof(float), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_chain);
+    if (rc) return rc;
+    RT_HIP(c, e);
     return RT_OK;
 }
 

@@ -483,8 +483,9 @@ struct Ctx {
     uint32_t last_image = 0;             // image of the batch that holds the last sample rendered
     uint32_t last_sample0 = 0;           // sample index of image 0 of that batch (rt_read_level_image)
     float* d_rgb = nullptr;         // full frame, f32 x 3
+    float* d_chain = nullptr;       // set only inside rt_render_chains: the shade launch records the secondary marches here
     uint8_t* d_rgba8 = nullptr;     // rt_read_rgba8 staging, width*height*4, allocated on first use, freed with the frame
-    uint64_t* d_counters = nullptr;  // 4 x 1024 slots: hit pixels, secondary hits shaded, mirror rays, transmitted rays; summed on the host
+    uint64_t* d_counters = nullptr;  // 4 x 1024 slots: hit pixels, secondary hits shaded, mirror rays, transmitted rays; summed on the host; + 1 word: d_chain for the recording kernel
     Partition part{0, 1, 0, 0};
 
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
@@ -533,8 +534,10 @@ void pt_free_mesh(PtData& pt);     // rt_abi_mesh.hip: this context's hold on it
 // path_a.hip
 int launch_cone_level(Ctx* c, const SphereSet& spheres, uint32_t n_obj, const ConeLevelParams& p, const float* parent,
                       float* out, uint32_t batch);
+// chain (rt_render_chains only): the recording kernel; the address of the records ((reflections + transmissions) x 7 floats per
+// pixel of the full frame) stands in counters[4096], the word behind the four groups of counter slots
 int launch_shade(Ctx* c, const ShadeSet& set, uint32_t n_obj, const ShadeParams& p, const float* depth, float* dst,
-                 uint64_t* counters);
+                 uint64_t* counters, bool chain = false);
 int launch_pyramid_fused(Ctx* c, const SphereSet& spheres, uint32_t n_obj, const PyramidParams& fp);
 int launch_selftest_sqrt(Ctx* c, unsigned long long* mismatches_dev);
 int launch_detile(Ctx* c, const float* tiles, uint32_t n_ranks, uint32_t tiles_per_rank, float* rgb);

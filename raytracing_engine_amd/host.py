@@ -132,6 +132,7 @@ class Renderer:
         if rc != 0:
             raise RtError(rc, self._lib.rt_last_error(None).decode())
         self.width = self.height = 0
+        self._chain_rows = 0
 
     def _check(self, rc):
         if rc != 0:
@@ -161,6 +162,7 @@ class Renderer:
 
     def set_config(self, cfg):
         self._check(self._lib.rt_set_config(self._ctx, C.byref(cfg)))
+        self._chain_rows = int(cfg.reflections) + int(cfg.transmissions)
 
     def set_scene(self, scene):
         raw = bytes(scene) if not isinstance(scene, (bytes, bytearray)) else bytes(scene)
@@ -206,6 +208,19 @@ class Renderer:
             return (rgb, depth) if want_depth else rgb
         self._check(self._lib.rt_render_spp(self._ctx, _fptr(rot), _fptr(pos), spp, _fptr(rgb)))
         return rgb
+
+    def render_chains(self, rot=(0, 0, 0, 1), pos=(0, 0, 0)):
+        """Test hook (rt_render_chains): render(rot, pos, want_depth=True) plus what every secondary march did ->
+        (rgb, depth, chains); chains (H, W, reflections + transmissions, 7): eye[3], dir[3], len, NaN where no march ran."""
+        rot = np.ascontiguousarray(rot, np.float32)
+        pos = np.ascontiguousarray(pos, np.float32)
+        rows = self._chain_rows  # as of the last set_config (the default config has no chain: the call refuses)
+        rgb = np.empty((self.height, self.width, 3), np.float32)
+        w, h = self.level_info()[-1]
+        depth = np.empty((h, w), np.float32)
+        chains = np.empty((self.height, self.width, rows, 7), np.float32)
+        self._check(self._lib.rt_render_chains(self._ctx, _fptr(rot), _fptr(pos), _fptr(rgb), _fptr(depth), _fptr(chains)))
+        return rgb, depth, chains
 
     def render_device(self, rot, pos, spp, dev_ptr, tile_major=False):
         """Asynchronous: enqueue a frame into a device buffer (e.g. torch tensor .data_ptr())."""

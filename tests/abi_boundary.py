@@ -39,6 +39,10 @@ class Kind:
                 ((self.params, self.params_c, self.params_fields), (self.stats, self.stats_c, self.stats_fields)) if cls is not None]
 
 
+# the test hook that returns path A's secondary marches (rt_render_chains; no struct of its own)
+CHAIN_HOOK = Kind(functions=("rt_render_chains",), methods=("render_chains",), null_calls=(("rt_render_chains", (None, None, None, None, None)),))
+
+
 def exports(kind):
     lib = R.load()
     for name in kind.functions:

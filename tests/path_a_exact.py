@@ -4,7 +4,8 @@ Test helper (imported by tests/test_path_a_exact_host.py and tests/test_gpu_path
 numpy float64 only: nothing from `oracle`, nothing from librt_amd at module level.  Written from the specification (include/rt_abi.h,
 oracle/oracle.h, DESIGN.md sections 4-5), not from oracle_a.c / path_a.hip, which mirror each other line by line and would share any
 misreading.  It covers the reference as shipped (march algorithm 3, 1 spp, jitter 0), multi-sample frames (every sample a full frame
-with its own jitter, averaged in sample order) and march algorithm 1; no repeat(), no mirror or transmission chains, no algorithm 2.
+with its own jitter, averaged in sample order), march algorithm 1, and the mirror and transmission chains (CHAINS below); no repeat(),
+no algorithm 2, no camera inside a sphere under algorithm 1 or with chains.
 There is no stepping loop over a ray anywhere in this file: the scene is at most 8 spheres, so what the marches approximate has a
 closed form, and what they leave open (WHERE a march samples) is held in an interval.
 
@@ -69,6 +70,40 @@ Shares of the hit pixels, same command: ambiguous 0 - 0.37 %; pinned 57 - 100 % 
 width of the room's RGB intervals 0.0004 - 0.045.  Averaged frames (4, 9, 16 spp; shares of the pixels some sample hit): ambiguous
 0 - 0.68 % (17 x 9) and <= 0.38 % elsewhere, every hit sample pinned 53 - 94 % (open) and 24 - 33 % (rooms), room median width 0.012 - 0.0451.
 Algorithm 1: ambiguous <= 0.37 %, pinned 55 - 100 % / 25 - 31 %, room median width 0.017 - 0.047.
+
+CHAINS, chain_bands(frame) (rt_config.reflections / transmissions in include/rt_abi.h, ora_config in oracle/oracle.h).  A chain cannot
+be judged end to end from the primary depth: an fp32 rounding of 1e-6 in a hit point on a sphere of radius r is 2 L / r times that in
+the next hit.  The frame therefore carries what every secondary march did (Frame.chains: rt_render_chains / ora_render_a_chains;
+(h, w, reflections + transmissions, 7) = eye[3], dir[3], len per possible march, mirror bounces first, NaN where none ran), and every
+link is computed from the RECORDED values of the link before it, so nothing is carried across links.  For every hit pixel, from the
+frame's own depth: step, P0 = pos + d step, nearest sphere, n0.
+    mirror bounce j:   H_{j-1} = eye_{j-1} + dir_{j-1} max(len_{j-1}, 0)  (H_{-1} = P0, dir_{-1} = step); its nearest sphere gives n,
+        specular; expected eye_j = H_{j-1}, dir_j = reflect(dir_{j-1}, n), w_j = w_{j-1} reflectivity specular
+    transmission pass j:  starts again at P0, step, w = 1; T = I or normalize(refract(I, n, 1 / index)); oc = P - c, b = oc.T,
+        disc = b^2 - (oc.oc - r^2), t = max(disc > 0 ? sqrt(disc) - b : 0, 0), Q = P + T t, n2 = normalize(oc + T t), D = T or
+        normalize(refract(T, -n2, index)); expected eye_j = Q, dir_j = D, w_j = w_{j-1} transparency diffuse; k < 0 or k2 < 0 ends it
+    either:  len_j in ray_band(o = eye_j + dir_j, u = dir_j, len0 = 1, tau = ray_radius) under the hit / miss rules of a level texel;
+        len_j < render_dist adds w_j shade_point(H_j, eye = eye_j, view = dir_j) and the chain goes on, otherwise it ends and every
+        later row is NaN
+The pixel's RGB interval is the primary one plus the weighted secondary ones; the NaN pattern is the walk's; reflection_rays /
+transmission_rays = the non-NaN rows, shadow_rays = lightCount (hit pixels + rows with len < render_dist).  The silhouette ring where
+only the cone touched the sphere is predicted, not left out: disc <= 0, t = 0, Q = P.  Left out: a shaded chain point with its two
+smallest SDFs closer than AMBIGUOUS, and a branch decided inside a guard (|disc| < GUARD_DISC r^2, |k| or |k2| < GUARD_K).
+Measured by the same command over CHAIN_FRAMES + GPU_ONLY_CHAIN_FRAMES (oracle A on the CPU), constants = four times:
+    guards: the formula in fp32 against float64 from the same recorded inputs:  k, k2 1.697e-06 -> GUARD_K = 6.788e-06;
+            disc / r^2 6.815e-07 -> GUARD_DISC = 2.726e-06;  left out 0 - 0.59 % of the hit pixels (cap 1 %)
+    eye, relative to 1 + |eye|:       1.805e-07 -> EPS_CHAIN_EYE = 7.218e-07
+    dir, relative to 1 + |eye| / r:   9.854e-07 -> EPS_CHAIN_DIR = 3.941e-06   (a normal is a position over a radius: half an ulp of the
+                                      fp32 hit point is eps |eye| / r in dir; measured plainly 3.05e-06 on the room's radius-1 ball)
+    len outside its band, / (1 + len): 1.141e-06 -> EPS_CHAIN_LEN = 4.562e-06
+    rgb:                              5.104e-06 -> EPS_CHAIN_RGB = 2.042e-05
+disc cancels (b^2 against oc.oc - r^2), so fp32 holds it to GUARD_DISC r^2 at best and t = sqrt(disc) - b, hence Q, only to
+GUARD_DISC r^2 / (2 sqrt(disc)) (4e-5 of |Q| measured near grazing incidence); through n2 and sqrt(k2) the same reaches D near the
+critical angle (1.7e-4).  Those first-order bounds are taken off the eye / dir differences before the constants apply (chain_bands,
+t_allow / dir_allow); nothing is taken off for t = 0 or a straight ray, and the next link starts from the recorded values anyway.
+Every case (CHAIN_CASES) gives each sphere its own diffuse and specular in (0, 1), has secondary light above 100 EPS_RGB on >= 10 % of
+its hit pixels (10.9 - 98.3 %) and a march of each kind that ends by a miss.  WRONG_CHAINS are the misreadings whose references must
+reject the right recordings (tests/test_path_a_exact_host.py).
 """
 import sys
 
@@ -81,6 +116,16 @@ PINNED_WIDTH = 1e-6
 # python tests/path_a_exact.py  (see the module docstring)
 EPS_DEPTH = 2.369e-06
 EPS_RGB = 3.737e-05
+# the chains (CHAINS in the module docstring): four times the largest excursion of oracle A's recordings over CHAIN_FRAMES + GPU_ONLY_CHAIN_FRAMES
+EPS_CHAIN_EYE = 7.218e-07 # recorded eye against the expected one, relative to 1 + |eye|
+EPS_CHAIN_DIR = 3.941e-06 # recorded dir against the expected one, relative to 1 + |eye| / r (the normal is a position over a radius)
+EPS_CHAIN_LEN = 4.562e-06 # recorded len outside its band, relative to 1 + len
+EPS_CHAIN_RGB = 2.042e-05 # RGB outside the summed interval
+# A branch decided inside these widths is one fp32 cannot decide and the pixel is left out: four times the largest difference between
+# the formula evaluated in fp32 and in float64 from the same recorded inputs, same command
+GUARD_K = 6.788e-06       # k and k2 of the two refractions against 0
+GUARD_DISC = 2.726e-06   # disc of the crossing against 0, relative to r^2
+CHAIN_COVERED = 0.10    # share of a case's hit pixels that must receive a secondary contribution above 100 EPS_RGB
 
 
 # ---- inputs --------------------------------------------------------------------------------------------------------------------
@@ -106,15 +151,22 @@ def parse_scene(raw):
     lights = np.frombuffer(raw, np.float32, 64, 16 + 256 + 128).reshape(8, 8).astype(np.float64)
     n_obj, n_light = int(n_obj), int(n_light)
     return dict(c=objs[:n_obj, :3], r=objs[:n_obj, 3], color=mats[:n_obj, :3], shine=mats[:n_obj, 5], ambient=mats[:n_obj, 6],
-                lpos=lights[:n_light, :3], lcol=lights[:n_light, 4:7])
+                diffuse=mats[:n_obj, 3], specular=mats[:n_obj, 4], lpos=lights[:n_light, :3], lcol=lights[:n_light, 4:7])
 
 
 class Frame:
     """Everything the two band functions read: the scene, the view, the config scalars, and the frame's own levels and RGB."""
 
     def __init__(self, scene, width, height, rot=(0, 0, 0, 1), pos=(0, 0, 0), ratio=None, render_dist=1000.0, cam_fall_off=0.01,
-                 light_fall_off=0.01, ray_radius=0.01, levels=None, rgb=None, jitter=(0, 0), march_algorithm=3):
+                 light_fall_off=0.01, ray_radius=0.01, levels=None, rgb=None, jitter=(0, 0), march_algorithm=3, reflections=0, reflectivity=0.5,
+                 transmissions=0, transparency=0.5, refraction_index=1.0, chains=None):
         self.scene = parse_scene(scene)
+        # the chains (chain_bands): the config scalars as fp32 holds them, and the recorded marches (h, w, reflections + transmissions, 7)
+        self.reflections, self.transmissions = int(reflections), int(transmissions)
+        self.reflectivity, self.transparency, self.refraction_index = (float(np.float32(v)) for v in (reflectivity, transparency, refraction_index))
+        self.chains = None if chains is None else np.asarray(chains, np.float64)
+        if self.chains is not None:
+            assert self.chains.shape == (int(height), int(width), self.reflections + self.transmissions, 7)
         self.jitter = np.asarray(jitter, np.float32).astype(np.float64)  # added to the normalised coordinates, before the ratio
         assert march_algorithm in (1, 3)
         self.alg = int(march_algorithm)
@@ -213,8 +265,19 @@ def depth_bands_chunk(fr, i, texels):
     u = rays(fr, (2.0 * gx + 1.0) * isx - 1.0, (2.0 * gy + 1.0) * isy - 1.0)
     len0 = np.ones(len(gx)) if i == 0 else fr.levels[i - 1][gy >> 1, gx >> 1]
     o = fr.pos + len0[:, None] * u
-    c, r = fr.scene["c"], fr.scene["r"]
-    RD = fr.render_dist
+    out = ray_band(o, u, len0, tau, fr.scene, fr.render_dist, fr.alg)
+    out.update(gy=gy, gx=gx, tau=tau)
+    return out
+
+
+def ray_band(o, u, len0, tau, scene, render_dist, alg=3):
+    """The band of ANY cone march: origin o (T, 3), unit direction u (T, 3), the length len0 (T,) its result is added to, cone factor
+    tau; what the module docstring says under DEPTH, for algorithm `alg`.  A level texel marches o = pos + len0 u with its level's
+    tau; a mirror or transmitted ray marches o = eye + dir with len0 = 1 and tau = ray_radius (chain_bands).
+    Returns dict(lo, hi (nan where F is empty), empty, crossed (the centre line crosses a surface before render_dist), len0)."""
+    n_rays = len(len0)
+    c, r = scene["c"], scene["r"]
+    RD = render_dist
     oc = o[:, None, :] - c[None]                    # (T, n, 3)
     b = (oc * u[:, None, :]).sum(-1)                # (T, n)
     cc = (oc * oc).sum(-1)
@@ -227,14 +290,14 @@ def depth_bands_chunk(fr, i, texels):
     a = a_k.min(1)
     cut = np.minimum(a, RD)
 
-    if fr.alg == 1 and tau >= 1.0:
+    if alg == 1 and tau >= 1.0:
         # f(0) (1 - tau) <= 0 <= tau: the first sample stops the march, the band is one point
         f0 = (np.sqrt(cc) - r).min(1)
         assert (f0 >= 0.0).all(), "algorithm 1 from inside a sphere is not covered"
         point = np.maximum(len0 + f0 * (1.0 - tau) - tau, 0.0)
-        return dict(lo=point, hi=point.copy(), empty=np.zeros(len(gx), bool), crossed=a < RD, len0=len0, gy=gy, gx=gx, tau=tau)
+        return dict(lo=point, hi=point.copy(), empty=np.zeros(n_rays, bool), crossed=a < RD, len0=len0)
     # the radius factor of the touch sets {f_k <= (t + 1) tq}; algorithm 1 stops on f (1 - tau) <= (s + 1) tau
-    tq = tau if fr.alg == 3 else tau / (1.0 - tau)
+    tq = tau if alg == 3 else tau / (1.0 - tau)
     lo_k, hi_k = _touch_intervals(np.full_like(b, 1.0 - tq * tq), b - tq * (r + tq), cc - (r + tq) ** 2)
     lo_k = np.maximum(lo_k, 0.0)
     hi_k = np.minimum(hi_k, cut[:, None, None])
@@ -243,7 +306,7 @@ def depth_bands_chunk(fr, i, texels):
         p = oc[idx][:, None, :, :] + s[:, :, None, None] * u[idx][:, None, None, :]
         return (np.sqrt((p * p).sum(-1)) - r).min(-1)
 
-    if fr.alg == 3:
+    if alg == 3:
         lipschitz = 2.0 + tau
 
         def g_of(s, f):  # what a march that stops at s returns, relative to len0
@@ -254,8 +317,8 @@ def depth_bands_chunk(fr, i, texels):
         def g_of(s, f):  # f >= 0 on F, the march never crosses a surface: the clamp only takes the rounding at the cut
             return (s + np.maximum(f, 0.0)) * (1.0 - tau) - tau
 
-    gmin = np.full(len(gx), np.inf)
-    gmax = np.full(len(gx), -np.inf)
+    gmin = np.full(n_rays, np.inf)
+    gmax = np.full(n_rays, -np.inf)
     frac = np.linspace(0.0, 1.0, N_SAMPLE)
     for k in range(len(r)):
         for j in range(2):
@@ -278,7 +341,20 @@ def depth_bands_chunk(fr, i, texels):
     with np.errstate(invalid="ignore"):
         lo = np.where(empty, np.nan, np.maximum(len0 + gmin, 0.0))
         hi = np.where(empty, np.nan, np.maximum(len0 + gmax, 0.0))
-    return dict(lo=lo, hi=hi, empty=empty, crossed=a < RD, len0=len0, gy=gy, gx=gx, tau=tau)
+    return dict(lo=lo, hi=hi, empty=empty, crossed=a < RD, len0=len0)
+
+
+def march_rules(v, bd, render_dist, eps):
+    """The hit and miss rules of the module docstring for marched values v against their ray_band bd.  Returns (ok, excursion, miss):
+    excursion = the distance outside the band relative to 1 + v, 0 where a rule holds, inf for a rule with no distance."""
+    with np.errstate(invalid="ignore"):
+        out = np.maximum(np.maximum(bd["lo"] - v, v - bd["hi"]), 0.0) / (1.0 + v)  # nan where F is empty
+    in_band = ~bd["empty"] & (out <= eps)
+    miss = v >= render_dist
+    # a march that ran out left the loop at a relative fp32 length >= render_dist; the one rounding of len0 + length is monotone
+    ran_out = miss & ~bd["crossed"] & (v >= (bd["len0"] + render_dist) * (1.0 - 2.0 ** -23))
+    ok = np.where(miss, in_band | ran_out, in_band)
+    return ok, np.where(ok, 0.0, np.where(np.isfinite(out), out, np.inf)), miss
 
 
 def check_depth(fr, i, eps=None, texels=None, bands=None):
@@ -293,14 +369,7 @@ def check_depth(fr, i, eps=None, texels=None, bands=None):
     bd = bands if bands is not None else depth_bands(fr, i, (gy, gx))
     v = fr.levels[i][gy, gx]
     RD = fr.render_dist
-    with np.errstate(invalid="ignore"):
-        out = np.maximum(np.maximum(bd["lo"] - v, v - bd["hi"]), 0.0) / (1.0 + v)  # nan where F is empty
-    in_band = ~bd["empty"] & (out <= eps)
-    miss = v >= RD
-    # a march that ran out left the loop at a relative fp32 length >= render_dist; the one rounding of len0 + length is monotone
-    ran_out = miss & ~bd["crossed"] & (v >= (bd["len0"] + RD) * (1.0 - 2.0 ** -23))
-    ok = np.where(miss, in_band | ran_out, in_band)
-    exc = np.where(ok, 0.0, np.where(np.isfinite(out), out, np.inf))
+    ok, exc, miss = march_rules(v, bd, RD, eps)
     far = bd["len0"] >= RD
     return dict(n=len(v), bad=int(np.count_nonzero(~ok)), excursion=float(exc.max()) if len(v) else 0.0,
                 far_bad=int(np.count_nonzero(far & ~miss)), hits=int(np.count_nonzero(~miss)))
@@ -333,37 +402,41 @@ def _segment_min(o, d, end, c, r):
     return m, np.where(a <= end, a, np.inf), f0
 
 
-def shade_bands(fr, pixels=None):
-    """RGB intervals of the pixels whose own finest-level depth is < render_dist.  Returns dict(py, px: the hit pixels; lo, hi (n, 3);
-    ambiguous, pinned (n,) bool; width (n,) = the largest component of hi - lo)."""
+def _unit(v):
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def _dot(a, b):
+    return (a * b).sum(-1)
+
+
+def _nearest(fr, P):
+    """(nearest sphere by strict '<', first wins; outward normal there; two smallest SDFs closer than AMBIGUOUS) at points P (n, 3)."""
     sc = fr.scene
-    depth = fr.levels[-1][:fr.h, :fr.w]
-    if pixels is None:
-        py, px = np.nonzero(depth < fr.render_dist)
-    else:
-        py, px = pixels
-        keep = depth[py, px] < fr.render_dist
-        py, px = py[keep], px[keep]
-    d = depth[py, px]
-    step = rays(fr, (px + 0.5) * 2.0 / fr.w - 1.0, (py + 0.5) * 2.0 / fr.h - 1.0)
-    P = fr.pos + d[:, None] * step
     sdf = np.linalg.norm(P[:, None, :] - sc["c"][None], axis=-1) - sc["r"]
-    best = sdf.argmin(1)  # strict '<', first wins
+    best = sdf.argmin(1)
     if sdf.shape[1] > 1:
         two = np.partition(sdf, 1, axis=1)
-        ambiguous = (two[:, 1] - two[:, 0]) < AMBIGUOUS
+        amb = (two[:, 1] - two[:, 0]) < AMBIGUOUS
     else:
-        ambiguous = np.zeros(len(d), bool)
-    cam_dist = np.linalg.norm(P - fr.pos, axis=-1)
+        amb = np.zeros(len(P), bool)
+    return best, _unit(P - sc["c"][best]), amb
+
+
+def shade_point(fr, P, eye, view):
+    """RGB interval of surface points P (n, 3) seen from `eye` (n, 3) along the unit directions `view` (n, 3): the camera ray has
+    eye = pos and view = step, a mirror ray eye = the previous hit, a transmitted ray eye = Q.  Returns dict(lo, hi (n, 3); best (n,) =
+    the nearest sphere, strict '<', first wins; normal (n, 3); ambiguous (n,) = the two smallest SDFs at P closer than AMBIGUOUS)."""
+    sc = fr.scene
+    best, normal, ambiguous = _nearest(fr, P)
+    cam_dist = np.linalg.norm(P - eye, axis=-1)
     cam_fall = np.maximum(fr.cam_fall_off * (cam_dist * cam_dist + 1.0), 1.0)
-    normal = P - sc["c"][best]
-    normal /= np.linalg.norm(normal, axis=-1, keepdims=True)
-    cam_dir = -step
+    cam_dir = -view
     normal_fall = np.maximum((normal * cam_dir).sum(-1), 0.0)
     color, shine, ambient = sc["color"][best], sc["shine"][best], sc["ambient"][best]
     rr = fr.ray_radius
-    lo = np.zeros((len(d), 3))
-    hi = np.zeros((len(d), 3))
+    lo = np.zeros((len(P), 3))
+    hi = np.zeros((len(P), 3))
     for lp, lc in zip(sc["lpos"], sc["lcol"]):
         to = lp - P
         light_dist = np.linalg.norm(to, axis=-1)
@@ -385,8 +458,27 @@ def shade_bands(fr, pixels=None):
             direct = (s[:, None] * lc[None] / light_fall[:, None]) * soft[:, None]
             acc += (ambient[:, None] + direct) / cam_fall[:, None] * normal_fall[:, None] * color
     lo, hi = np.minimum(lo, hi), np.maximum(lo, hi)
+    return dict(lo=lo, hi=hi, best=best, normal=normal, ambiguous=ambiguous)
+
+
+def shade_bands(fr, pixels=None):
+    """RGB intervals of the pixels whose own finest-level depth is < render_dist.  Returns dict(py, px: the hit pixels; lo, hi (n, 3);
+    ambiguous, pinned (n,) bool; width (n,) = the largest component of hi - lo; and of the primary hit: step, P, best, normal)."""
+    depth = fr.levels[-1][:fr.h, :fr.w]
+    if pixels is None:
+        py, px = np.nonzero(depth < fr.render_dist)
+    else:
+        py, px = pixels
+        keep = depth[py, px] < fr.render_dist
+        py, px = py[keep], px[keep]
+    d = depth[py, px]
+    step = rays(fr, (px + 0.5) * 2.0 / fr.w - 1.0, (py + 0.5) * 2.0 / fr.h - 1.0)
+    P = fr.pos + d[:, None] * step
+    sp = shade_point(fr, P, np.broadcast_to(fr.pos, P.shape), step)
+    lo, hi, ambiguous = sp["lo"], sp["hi"], sp["ambiguous"]
     width = (hi - lo).max(1) if len(d) else np.zeros(0)
-    return dict(py=py, px=px, lo=lo, hi=hi, ambiguous=ambiguous, pinned=~ambiguous & (width < PINNED_WIDTH), width=width)
+    return dict(py=py, px=px, lo=lo, hi=hi, ambiguous=ambiguous, pinned=~ambiguous & (width < PINNED_WIDTH), width=width,
+                step=step, P=P, best=sp["best"], normal=sp["normal"])
 
 
 def check_rgb(fr, eps=None, bands=None):
@@ -457,6 +549,310 @@ def check_samples(frames, rgb, eps_depth=None, eps_rgb=None, limit=100_000):
     res = check_samples_rgb(frames, rgb, eps_rgb)
     res["depth"] = [[check_depth(fr, i, eps_depth, sample_texels(fr, i, limit)) for i in range(fr.count)] for fr in frames]
     return res
+
+
+# ---- the mirror and transmission chains ----------------------------------------------------------------------------------------
+def reflect(i, n):
+    """GLSL reflect(I, N) = I - 2 dot(N, I) N."""
+    return i - 2.0 * _dot(n, i)[:, None] * n
+
+
+def refract(i, n, eta):
+    """GLSL refract(I, N, eta): k = 1 - eta^2 (1 - dot(N, I)^2); eta I - (eta dot(N, I) + sqrt(k)) N for k >= 0.  Returns (vector, k)."""
+    ci = _dot(n, i)
+    k = 1.0 - eta * eta * (1.0 - ci * ci)
+    return eta * i - (eta * ci + np.sqrt(np.maximum(k, 0.0)))[:, None] * n, k
+
+
+def _trans_branches(P, I, c, rad, index, dt):
+    """The three quantities that decide a branch of the transmission formula, evaluated in the number format dt from the same
+    inputs: k of the entry refraction, disc / r^2 of the crossing, k2 of the exit refraction (k = k2 = 1 for index 1)."""
+    P, I, c, rad, index = (np.asarray(a, np.float64).astype(dt) for a in (P, I, c, rad, index))
+    one = dt(1.0)
+    oc = P - c
+    nrm = oc / np.sqrt((oc * oc).sum(-1))[:, None]
+    k = np.ones(len(P), dt)
+    Tdir = I
+    if index != one:
+        eta = one / index
+        ci = (nrm * I).sum(-1)
+        k = one - eta * eta * (one - ci * ci)
+        v = eta * I - (eta * ci + np.sqrt(np.maximum(k, dt(0))))[:, None] * nrm
+        Tdir = v / np.sqrt((v * v).sum(-1))[:, None]
+    b = (oc * Tdir).sum(-1)
+    disc = b * b - ((oc * oc).sum(-1) - rad * rad)
+    t = np.maximum(np.where(disc > 0, np.sqrt(np.maximum(disc, dt(0))) - b, dt(0)), dt(0))
+    k2 = np.ones(len(P), dt)
+    if index != one:
+        e = oc + Tdir * t[:, None]
+        n2 = e / np.sqrt((e * e).sum(-1))[:, None]
+        ce = (n2 * Tdir).sum(-1)
+        k2 = one - index * index * (one - ce * ce)
+    return k, disc / (rad * rad), k2
+
+
+# What a wrong reading of the specification would compute: chain_bands(fr, wrong=<one of these>) is that reading's reference, which
+# has to REJECT the right recordings (tests/test_path_a_exact_host.py).  "mirror" / "trans": the chain kind it needs; 2: at least two
+# links of that kind; "both": both chains; "bend": refraction_index != 1.
+WRONG_CHAINS = {
+    "reflect sign flipped": "mirror",          # I + 2 dot(N, I) N
+    "index and 1/index exchanged": "bend",
+    "exit normal not negated": "bend",         # refract(T, n2, index)
+    "weight from the surface hit": "any",      # the surface the ray arrives at instead of the one it leaves
+    "weight from the surface before": "any2",  # the surface left one link earlier
+    "weight not accumulated": "any2",
+    "cam_fall from the camera": "any",
+    "transmission from the mirror chain's end": "both",
+    "near root": "trans",                      # -sqrt(disc) - b
+    "finest level's tau": "any",
+    "len0 = 0": "any",
+    "started at eye": "any",
+    "first contribution dropped": "any",
+    "first contribution twice": "any",
+}
+
+
+def wrong_applies(wrong, fr, res):
+    """Does the wrong reading differ from the right one on this frame?  res: check_chains(fr) of the right reading.  A weight that
+    depends on an earlier link needs a second or later link of a chain that found a surface (later_hits); measuring cam_fall from
+    the camera changes nothing where the fall-off is clamped to 1 for either eye, that is where every shaded point lies within
+    sqrt(1 / cam_fall_off - 1) of both (CAM_FALL_FLAT; the test asserts that the two readings' intervals are then the same)."""
+    need = WRONG_CHAINS[wrong]
+    r, t = fr.reflections, fr.transmissions
+    if wrong == "cam_fall from the camera" and getattr(fr, "name", None) in CAM_FALL_FLAT:
+        return False
+    return {"mirror": r > 0, "trans": t > 0, "bend": t > 0 and fr.refraction_index != 1.0, "any": r + t > 0,
+            "any2": max(r, t) >= 2 and res["later_hits"] > 0, "both": r > 0 and t > 0}[need]
+
+
+CAM_FALL_FLAT = ("mirror_r2",)  # both spheres within 9.95 = sqrt(1 / 0.01 - 1) of the camera and of each other
+
+
+def chain_bands(fr, wrong=None):
+    """What the recorded secondary marches of fr (fr.chains) and its RGB have to be, link by link; see CHAINS in the module docstring.
+    Every expected value of link j is computed from the RECORDED values of link j - 1 (and the frame's own depth for link 0), so no
+    rounding is carried from one link to the next.  Over the hit pixels (shade_bands' order) returns dict(py, px; lo, hi (n, 3): the
+    RGB interval, primary plus the weighted secondary intervals; secondary (n,): the largest component of the summed lower ends of
+    the secondary intervals; left_out (n,): ambiguous at some shaded point, or a branch of the formula decided inside a guard;
+    nan_bad (n,): recordings where the walk predicts none, or none where it predicts one; eye_exc, dir_exc, len_exc (n,): the largest
+    excursions of the pixel's recorded eye (relative to 1 + |eye|), dir and len (outside its band, relative to 1 + len; inf for a
+    forbidden or forced miss); n_mirror, n_trans, n_points: non-NaN mirror / transmission recordings and those with len <
+    render_dist, over the hit pixels; miss_mirror, miss_trans: recorded marches that ended by a miss; later_hits: second and later
+    links of a chain that found a surface; guard_k, guard_disc: the largest fp32 - float64 differences of the branch quantities;
+    miss_recorded: values that are not NaN at miss pixels)."""
+    assert wrong is None or wrong in WRONG_CHAINS
+    sb = shade_bands(fr)
+    py, px = sb["py"], sb["px"]
+    n = len(py)
+    sc, RD = fr.scene, fr.render_dist
+    R, T = fr.reflections, fr.transmissions
+    rec = fr.chains[py, px]                      # (n, R + T, 7)
+    lo, hi = sb["lo"].copy(), sb["hi"].copy()
+    sec_lo = np.zeros((n, 3))
+    left_out = sb["ambiguous"].copy()
+    nan_bad = np.zeros(n, bool)
+    eye_exc, dir_exc, len_exc = np.zeros(n), np.zeros(n), np.zeros(n)
+    counts = dict(n_mirror=0, n_trans=0, n_points=0, miss_mirror=0, miss_trans=0, later_hits=0, guard_k=0.0, guard_disc=0.0)
+    tau = fr.ray_radius
+    if wrong == "finest level's tau":
+        tau = SQRT2_8 / fr.w
+    pos_all = np.broadcast_to(fr.pos, (n, 3))
+
+    def link(row, alive, eye_x, dir_x, weight, kind, first, radius, eye_allow=None, dir_allow=None):
+        """One recorded march: rows `row` of the pixels `alive` against the expected eye / dir, its band, and its weighted shading.
+        radius: of the sphere whose normal made dir; eye_allow, dir_allow: what the conditioning of the crossing and of the exit
+        refraction leaves open (absolute, taken off the differences first).  Returns (hit: the march ran and found a surface, H: the recorded hit point, the recorded dir)."""
+        r7 = rec[:, row]
+        has = ~np.isnan(r7).any(1)
+        nan_bad[:] |= (has != alive) | (np.isnan(r7).any(1) != np.isnan(r7).all(1))
+        idx = np.nonzero(alive & has)[0]
+        hit = np.zeros(n, bool)
+        H = np.full((n, 3), np.nan)
+        if not len(idx):
+            return hit, H, r7[:, 3:6]
+        eye, dr, ln = r7[idx, 0:3], r7[idx, 3:6], r7[idx, 6]
+        counts["n_" + kind] += len(idx)
+        size = np.linalg.norm(eye_x[idx], axis=1)
+        ea = 0.0 if eye_allow is None else eye_allow[idx]
+        da = 0.0 if dir_allow is None else dir_allow[idx]
+        np.maximum.at(eye_exc, idx, np.maximum(np.abs(eye - eye_x[idx]).max(1) - ea, 0.0) / (1.0 + size))
+        np.maximum.at(dir_exc, idx, np.maximum(np.abs(dr - dir_x[idx]).max(1) - da, 0.0) / (1.0 + size / radius[idx]))
+        u = _unit(dr)
+        if wrong == "len0 = 0":
+            bd = ray_band(eye + dr, u, np.zeros(len(idx)), tau, sc, RD)
+        elif wrong == "started at eye":
+            bd = ray_band(eye, u, np.zeros(len(idx)), tau, sc, RD)
+        else:
+            bd = ray_band(eye + dr, u, np.ones(len(idx)), tau, sc, RD)
+        ok, exc, miss = march_rules(ln, bd, RD, 0.0)
+        np.maximum.at(len_exc, idx, exc)
+        counts["miss_" + kind] += int(np.count_nonzero(miss))
+        h = idx[~miss]
+        hit[h] = True
+        counts["n_points"] += len(h)
+        if not first:
+            counts["later_hits"] += len(h)
+        H[h] = r7[h, 0:3] + r7[h, 3:6] * np.maximum(r7[h, 6], 0.0)[:, None]
+        if len(h):
+            sp = shade_point(fr, H[h], pos_all[h] if wrong == "cam_fall from the camera" else r7[h, 0:3], _unit(r7[h, 3:6]))
+            left_out[h] |= sp["ambiguous"]
+            w = weight[h]
+            if wrong == "weight from the surface hit":  # this link's factor (weight_factor, scale, per_surface: the calling loop's) retaken at H
+                w = w / weight_factor[h] * scale * per_surface[sp["best"]]
+            times = {"first contribution dropped": 0.0, "first contribution twice": 2.0}.get(wrong, 1.0) if first else 1.0
+            lo[h] += times * w[:, None] * sp["lo"]
+            hi[h] += times * w[:, None] * sp["hi"]
+            sec_lo[h] += w[:, None] * sp["lo"]
+        return hit, H, r7[:, 3:6]
+
+    first = True
+    last_mirror = None  # (alive, H, dir) where the mirror chain's last link hit
+    # ---- mirror bounces: r = reflect(dir, n), eye = the previous hit, weight prod(reflectivity * specular) over the surfaces left
+    scale, per_surface = fr.reflectivity, sc["specular"]
+    alive = np.ones(n, bool)
+    H, dprev = sb["P"], sb["step"]
+    weight = np.ones(n)
+    factors = []
+    for j in range(R):
+        safe = np.where(np.isnan(H).any(1)[:, None], 0.0, H)
+        best, nrm, amb = _nearest(fr, safe)
+        left_out |= alive & amb
+        weight_factor = scale * per_surface[best]
+        factors.append(weight_factor)
+        if wrong == "weight not accumulated":
+            weight = weight_factor.copy()
+        elif wrong == "weight from the surface before" and j > 0:
+            weight = weight * factors[j - 1]
+        else:
+            weight = weight * weight_factor
+        d_in = _unit(np.where(np.isnan(dprev).any(1)[:, None], 1.0, dprev))
+        dir_x = reflect(d_in, nrm) if wrong != "reflect sign flipped" else d_in + 2.0 * _dot(nrm, d_in)[:, None] * nrm
+        hit, Hn, dn = link(j, alive, safe, dir_x, weight, "mirror", first, sc["r"][best])
+        first = False
+        alive = hit
+        if alive.any():
+            last_mirror = (alive.copy(), Hn.copy(), dn.copy())
+        H, dprev = Hn, dn
+    # ---- transmission passes: again from the camera ray's hit, weight prod(transparency * diffuse) over the surfaces left
+    scale, per_surface = fr.transparency, sc["diffuse"]
+    idxr = fr.refraction_index
+    bend = idxr != 1.0
+    alive = np.ones(n, bool)
+    H, dprev = sb["P"], sb["step"]
+    if wrong == "transmission from the mirror chain's end" and last_mirror is not None:
+        m_alive, m_H, m_d = last_mirror
+        H = np.where(m_alive[:, None], m_H, H)
+        dprev = np.where(m_alive[:, None], m_d, dprev)
+    weight = np.ones(n)
+    factors = []
+    first = True
+    for j in range(T):
+        P = np.where(np.isnan(H).any(1)[:, None], 0.0, H)
+        I = _unit(np.where(np.isnan(dprev).any(1)[:, None], 1.0, dprev))
+        best, nrm, amb = _nearest(fr, P)
+        left_out |= alive & amb
+        weight_factor = scale * per_surface[best]
+        factors.append(weight_factor)
+        if wrong == "weight not accumulated":
+            weight = weight_factor.copy()
+        elif wrong == "weight from the surface before" and j > 0:
+            weight = weight * factors[j - 1]
+        else:
+            weight = weight * weight_factor
+        eta_in, eta_out = (1.0 / idxr, idxr) if wrong != "index and 1/index exchanged" else (idxr, 1.0 / idxr)
+        Tdir = I
+        if bend:
+            v, k = refract(I, nrm, eta_in)
+            left_out |= alive & (np.abs(k) < GUARD_K)
+            alive = alive & (k >= 0.0)
+            Tdir = _unit(np.where((k >= 0.0)[:, None], v, I))
+        c, rad = sc["c"][best], sc["r"][best]
+        if alive.any():  # what fp32 makes of the three deciding quantities, for the guards' measurement
+            q32, q64 = _trans_branches(P, I, c, rad, idxr, np.float32), _trans_branches(P, I, c, rad, idxr, np.float64)
+            for key, a32, a64 in zip(("guard_k", "guard_disc", "guard_k"), q32, q64):
+                counts[key] = max(counts[key], float(np.abs(a32.astype(np.float64) - a64)[alive].max()))
+        oc = P - c
+        b = _dot(oc, Tdir)
+        disc = b * b - (_dot(oc, oc) - rad * rad)
+        left_out |= alive & (np.abs(disc) < GUARD_DISC * rad * rad)
+        root = np.sqrt(np.maximum(disc, 0.0))
+        t = np.maximum(np.where(disc > 0.0, (root if wrong != "near root" else -root) - b, 0.0), 0.0)
+        Q = P + Tdir * t[:, None]
+        # fp32 holds disc only to GUARD_DISC r^2, so t = sqrt(disc) - b and Q only to that over 2 sqrt(disc) (nothing for t = 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t_allow = np.where((disc > 0.0) & (t > 0.0), GUARD_DISC * rad * rad / (2.0 * root), 0.0)
+        D = Tdir
+        dir_allow = np.zeros(n)
+        if bend:
+            n2 = _unit(oc + Tdir * t[:, None])
+            v, k2 = refract(Tdir, -n2 if wrong != "exit normal not negated" else n2, eta_out)
+            left_out |= alive & (np.abs(k2) < GUARD_K)
+            alive = alive & (k2 >= 0.0)
+            D = _unit(np.where((k2 >= 0.0)[:, None], v, Tdir))
+            # n2 moves by t_allow / r, k2 = 1 - index^2 (1 - ce^2) by GUARD_K + 2 index^2 |ce| dn2, sqrt(k2) by that over 2 sqrt(k2);
+            # D = index T + (sqrt(k2) - index ce) n2
+            ce = np.abs(_dot(n2, Tdir))
+            dn2 = t_allow / rad
+            with np.errstate(divide="ignore", invalid="ignore"):
+                sq = np.sqrt(np.maximum(k2, 0.0))
+                dir_allow = np.where(k2 > 0.0, (GUARD_K + 2.0 * eta_out * eta_out * ce * dn2) / (2.0 * sq) + (sq + 2.0 * eta_out * ce) * dn2, 0.0)
+        hit, Hn, dn = link(R + j, alive, Q, D, weight, "trans", first, rad, t_allow, dir_allow)
+        first = False
+        alive = hit
+        H, dprev = Hn, dn
+    missed = fr.levels[-1][:fr.h, :fr.w] >= RD
+    out = dict(py=py, px=px, lo=lo, hi=hi, secondary=sec_lo.max(1) if n else np.zeros(0), left_out=left_out, nan_bad=nan_bad,
+               eye_exc=eye_exc, dir_exc=dir_exc, len_exc=len_exc, miss_recorded=int(np.count_nonzero(~np.isnan(fr.chains[missed]))))
+    out.update(counts)
+    return out
+
+
+def check_chains(fr, eps_eye=None, eps_dir=None, eps_len=None, eps_rgb=None, wrong=None):
+    """fr's recorded marches and RGB against chain_bands.  Returns dict(hits; bad_nan, bad_eye, bad_dir, bad_len, bad_rgb: pixels that
+    break that rule by more than its tolerance, left-out pixels not counted (what their guard leaves open includes whether a march
+    runs at all); bad = pixels that break any; eye, dir, len, rgb: the largest excursions;
+    left_out (share of the hit pixels); covered = share of the hit pixels whose secondary contribution exceeds 100 EPS_RGB;
+    miss_nonblack, miss_recorded; the counters of chain_bands)."""
+    eps_eye = EPS_CHAIN_EYE if eps_eye is None else eps_eye
+    eps_dir = EPS_CHAIN_DIR if eps_dir is None else eps_dir
+    eps_len = EPS_CHAIN_LEN if eps_len is None else eps_len
+    eps_rgb = EPS_CHAIN_RGB if eps_rgb is None else eps_rgb
+    cb = chain_bands(fr, wrong)
+    n = len(cb["py"])
+    keep = ~cb["left_out"]
+    got = fr.rgb[cb["py"], cb["px"]]
+    rgb_exc = np.maximum(np.maximum(cb["lo"] - got, got - cb["hi"]), 0.0).max(1) if n else np.zeros(0)
+    rgb_exc = np.where(np.isfinite(rgb_exc), rgb_exc, np.inf)
+    bad = {"nan": cb["nan_bad"] & keep, "eye": (cb["eye_exc"] > eps_eye) & keep, "dir": (cb["dir_exc"] > eps_dir) & keep,
+           "len": (cb["len_exc"] > eps_len) & keep, "rgb": (rgb_exc > eps_rgb) & keep}
+    any_bad = np.zeros(n, bool)
+    for v in bad.values():
+        any_bad |= v
+    missed = fr.levels[-1][:fr.h, :fr.w] >= fr.render_dist
+
+    def worst(a):
+        return float(a[keep].max()) if keep.any() else 0.0
+
+    res = dict(hits=n, bad=int(np.count_nonzero(any_bad)), eye=worst(cb["eye_exc"]), dir=worst(cb["dir_exc"]), len=worst(cb["len_exc"]), rgb=worst(rgb_exc),
+               left_out=float(np.count_nonzero(cb["left_out"])) / max(n, 1), covered=float(np.count_nonzero(cb["secondary"] > 100.0 * EPS_RGB)) / max(n, 1),
+               miss_nonblack=int(np.count_nonzero(fr.rgb[missed])))
+    res.update({"bad_" + k: int(np.count_nonzero(v)) for k, v in bad.items()})
+    res.update({k: cb[k] for k in ("n_mirror", "n_trans", "n_points", "miss_mirror", "miss_trans", "miss_recorded", "later_hits", "guard_k", "guard_disc")})
+    return res
+
+
+def assert_chains(fr, res, counters=None):
+    """What every chain case asserts of a check_chains result (and of the frame's counters: hit_pixels, shadow_rays,
+    reflection_rays, transmission_rays)."""
+    assert res["bad"] == 0 and res["miss_nonblack"] == 0 and res["miss_recorded"] == 0, res
+    assert res["left_out"] <= CAP_AMBIGUOUS, res
+    assert res["covered"] >= CHAIN_COVERED, res
+    assert (res["miss_mirror"] > 0 or not fr.reflections) and (res["miss_trans"] > 0 or not fr.transmissions), res
+    if counters is not None:
+        n_light = len(fr.scene["lpos"])
+        assert counters["hit_pixels"] == res["hits"], (counters, res)
+        assert counters["reflection_rays"] == res["n_mirror"] and counters["transmission_rays"] == res["n_trans"], (counters, res)
+        assert counters["shadow_rays"] == n_light * (res["hits"] + res["n_points"]), (counters, res)
 
 
 # ---- the cases both test files run ---------------------------------------------------------------------------------------------
@@ -538,8 +934,55 @@ GPU_ONLY_SAMPLE_FRAMES = [("startup", 512, 288, 4)]
 # march algorithm 1 at 1 spp (17 x 9: tau = 1.33 at level 0, the one-point band); no camera inside a sphere
 ALG1_FRAMES = [("startup",) + SMALL, ("startup",) + MID, ("startup_turned",) + PADDED, ("room_turned",) + MID, ("room",) + PADDED,
                ("random_8_8",) + MID, ("random_5_2",) + PADDED, ("all_miss",) + MID, ("config",) + MID]
+# ---- chain cases: name -> (scene, view keywords, config keywords, sizes) ----------------------------------------------------------
+# mat.diffuse / mat.specular (the per-material scales of the transmission / mirror weights; 1 in every scene above) pairwise different
+# and strictly between 0 and 1, so that a weight taken from the wrong surface shows
+SURFACES = [(0.9, 0.35), (0.8, 0.45), (0.7, 0.55), (0.6, 0.65), (0.5, 0.75), (0.4, 0.85), (0.3, 0.95), (0.95, 0.25)]
+
+
+def with_surfaces(scene, pairs=SURFACES):
+    """The scene image with (mat.diffuse, mat.specular) of material k set to pairs[k]."""
+    raw = bytearray(scene)
+    for k, pair in enumerate(pairs):
+        raw[16 + 32 * k + 12:16 + 32 * k + 20] = np.array(pair, np.float32).tobytes()
+    return bytes(raw)
+
+
+def mirror_scene():
+    """tests/test_oracle_a.py::test_mirror_reflection_known_answers: a grey sphere facing a lit red one, the red one larger and nearer
+    (radius 4 at (7, 4, 0) for 2 at (6, 6, 0)): as drawn there only 6.8 % of the hit pixels show the other sphere (CHAIN_COVERED)."""
+    return with_surfaces(_pack_scene([(0, 10, 0, 4), (7, 4, 0, 4)], [(0.9, 0.9, 0.9, 4, 0.05), (1.0, 0.2, 0.2, 4, 0.05)], [((0, 0, 12), (2, 2, 2))]))
+
+
+def lens_scene():
+    """tests/test_oracle_a.py::test_transmission_known_answers: a clear sphere in front of a lit red one, a ball lens."""
+    return with_surfaces(_pack_scene([(0, 10, 0, 3), (0, 24, 0, 5)], [(0.9, 0.9, 0.9, 4, 0.05), (1.0, 0.2, 0.2, 4, 0.05)], [((0, 14, 14), (2, 2, 2))]))
+
+
+def _chain(reflections=0, transmissions=0, index=1.0, **other):
+    return dict(reflections=reflections, reflectivity=0.75, transmissions=transmissions, transparency=0.625, refraction_index=index, **other)
+
+
+CHAIN_CASES = {
+    "mirror_r2": (mirror_scene(), {}, _chain(2), [MID]),
+    "lens_t2_n1.5": (lens_scene(), {}, _chain(0, 2, 1.5), [MID]),
+    "lens_t1_n1": (lens_scene(), {}, _chain(0, 1, 1.0), [MID]),
+    "room_r1": (with_surfaces(room_scene()), {}, _chain(1), [PADDED]),
+    "room_turned_r2": (with_surfaces(room_scene()), TURNED, _chain(2), [MID]),
+    "room_turned_r4": (with_surfaces(room_scene()), TURNED, _chain(4), [MID, PADDED]),
+    "room_t1_n1": (with_surfaces(room_scene()), {}, _chain(0, 1, 1.0), [PADDED]),
+    "room_turned_t2_n1.33": (with_surfaces(room_scene()), TURNED, _chain(0, 2, 1.33), [MID]),
+    "room_turned_t3_n1.5": (with_surfaces(room_scene()), TURNED, _chain(0, 3, 1.5), [MID, PADDED]),
+    "room_turned_r2_t2_n1.5": (with_surfaces(room_scene()), TURNED, _chain(2, 2, 1.5), [MID]),
+    "room_r2_t2_n1.5": (with_surfaces(room_scene()), {}, _chain(2, 2, 1.5), [PADDED]),
+    # from the origin 4.9 % of the hit pixels show another sphere; from (2, 8, 1), among the spheres and outside every one, 10.9 %
+    "random_8_8_r2": (with_surfaces(random_scene(8, 8)), dict(pos=(2.0, 8.0, 1.0)), _chain(2), [MID]),
+    "config_r1_t1_n1.33": (with_surfaces(startup_scene()), {}, _chain(1, 1, 1.33, **OTHER_CONFIG), [MID]),  # ray_radius 0.02
+}
+CHAIN_FRAMES = [(name, w, h) for name, case in CHAIN_CASES.items() for w, h in case[3]]
+GPU_ONLY_CHAIN_FRAMES = [("room_r2_t2_n1.5", 512, 288)]
 CAP_AMBIGUOUS = 0.01
-CAP_PINNED = {"open": 0.50, "room": 0.20}
+CAP_PINNED ={"open": 0.50, "room": 0.20}
 CAP_ROOM_MEDIAN_WIDTH = 0.05
 
 
@@ -567,6 +1010,39 @@ def oracle_frame(name, w, h, jitter=(0, 0), march_algorithm=3):
     fr = Frame(scene, w, h, levels=ref["levels"], rgb=ref["rgb"], jitter=jitter, march_algorithm=march_algorithm, **view, **conf)
     fr.name = name
     return fr
+
+
+def oracle_chain_frame(name, w, h):
+    """The chain case rendered by oracle A (CPU) with its recorded marches; fr.counters = the oracle's counters."""
+    import oracle as O
+
+    scene, view, conf = CHAIN_CASES[name][:3]
+    cfg = O.default_config()
+    for k, v in conf.items():
+        setattr(cfg, k, v)
+    ref = O.render_a(O.scene_from_bytes(scene), w, h, cfg=cfg, want_chains=True, **view)
+    fr = Frame(scene, w, h, levels=ref["levels"], rgb=ref["rgb"], chains=ref["chains"], **view, **conf)
+    fr.name, fr.counters = name, ref["counters"]
+    return fr
+
+
+def measure_chains(out=sys.stdout):
+    """Largest excursions of oracle A's recorded marches and chain RGB over every chain case, with no tolerance, and the largest
+    fp32-against-float64 differences of the branch quantities (the guards are not applied to themselves: they are measured over all
+    pixels; the excursions over the pixels the committed guards keep)."""
+    worst = dict(eye=0.0, dir=0.0, len=0.0, rgb=0.0, guard_k=0.0, guard_disc=0.0)
+    for name, w, h in CHAIN_FRAMES + GPU_ONLY_CHAIN_FRAMES:
+        fr = oracle_chain_frame(name, w, h)
+        res = check_chains(fr, 0.0, 0.0, 0.0, 0.0)
+        for k in worst:
+            worst[k] = max(worst[k], res[k])
+        print(f"{name} {w}x{h}: eye {res['eye']:.3g} dir {res['dir']:.3g} len {res['len']:.3g} rgb {res['rgb']:.3g} | NaN pattern wrong {res['bad_nan']} | "
+              f"left out {100 * res['left_out']:.2f} %, secondary light on {100 * res['covered']:.1f} % of {res['hits']} hit pixels | marches: mirror "
+              f"{res['n_mirror']} ({res['miss_mirror']} missed), transmitted {res['n_trans']} ({res['miss_trans']} missed) | fp32 - float64: k {res['guard_k']:.3g}, "
+              f"disc / r^2 {res['guard_disc']:.3g}", file=out)
+    for k, label in (("eye", "EPS_CHAIN_EYE"), ("dir", "EPS_CHAIN_DIR"), ("len", "EPS_CHAIN_LEN"), ("rgb", "EPS_CHAIN_RGB"), ("guard_k", "GUARD_K"), ("guard_disc", "GUARD_DISC")):
+        print(f"chains: largest {k} = {worst[k]:.4g}  -> {label} = {4 * worst[k]:.4g}", file=out)
+    return worst
 
 
 def average(rgbs):
@@ -616,4 +1092,6 @@ if __name__ == "__main__":
     import os
 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    measure()
+    if sys.argv[1:] != ["chains"]:  # `chains`: only the new measurements
+        measure()
+    measure_chains()

@@ -282,6 +282,47 @@ def test_transmission(renderer, transmissions, transparency, index, reflections,
         renderer.set_config(renderer.default_config())
 
 
+@pytest.mark.parametrize("reflections,transmissions,index", [(2, 0, 1.0), (0, 2, 1.0), (2, 2, 1.5), (1, 3, 1.33)])
+@pytest.mark.parametrize("n_obj", [4, 8])
+@pytest.mark.parametrize("repeat", [(0.0, 0.0, 0.0), (40.0, 0.0, 40.0)])
+def test_recorded_chains_match_the_oracle(renderer, reflections, transmissions, index, n_obj, repeat):
+    """rt_render_chains against ora_render_a_chains: the same marches ran (NaN pattern identical), every recorded len is the
+    oracle's bit for bit (as the depth pyramid is), eye and dir within the RGB tolerance; RGB and depth are rt_render's."""
+    scene = R.default_scene() if n_obj == 4 else R.cornell_scene()
+    w, h = 200, 120
+    rot, pos = host.camera_quat(0.3, -0.1), (0.5, -1.0, 0.2)
+    ocfg = O.default_config()
+    ocfg.transmissions, ocfg.transparency, ocfg.refraction_index, ocfg.max_steps = transmissions, 0.7, index, 4096
+    ocfg.reflections, ocfg.reflectivity = reflections, 0.6
+    ocfg.repeat[:] = repeat
+    ref = O.render_a(oracle_scene(scene), w, h, rot=rot, pos=pos, cfg=ocfg, want_chains=True)
+    want = ref["chains"]
+    assert want.shape == (h, w, reflections + transmissions, 7) and not np.isnan(want[..., 0, 6]).all()
+    try:
+        cfg = renderer.default_config()
+        cfg.transmissions, cfg.transparency, cfg.refraction_index, cfg.max_steps = transmissions, 0.7, index, 4096
+        cfg.reflections, cfg.reflectivity = reflections, 0.6
+        cfg.repeat[:] = repeat
+        renderer.set_config(cfg)
+        renderer.set_scene(scene)
+        renderer.resize(w, h)
+        rgb1, depth1 = renderer.render(rot, pos, want_depth=True)
+        rgb, depth, got = renderer.render_chains(rot, pos)
+        st = renderer.stats()
+    finally:
+        renderer.set_config(renderer.default_config())
+    assert np.array_equal(rgb, rgb1) and np.array_equal(depth, depth1) and np.array_equal(depth, ref["levels"][-1])
+    assert np.abs(rgb - ref["rgb"]).max() <= RGB_TOL
+    assert got.shape == want.shape and np.array_equal(np.isnan(got), np.isnan(want))
+    ran = ~np.isnan(want[..., 6])
+    assert np.array_equal(got[..., 6][ran], want[..., 6][ran])
+    err = np.abs(got[..., :6][ran] - want[..., :6][ran]).max()
+    print(f"{int(ran.sum())} marches, largest eye / dir difference {err:.3g}")
+    assert err <= RGB_TOL
+    assert (st["reflection_rays"], st["transmission_rays"]) == (int(ran[..., :reflections].sum()), int(ran[..., reflections:].sum()))
+    assert (st["reflection_rays"], st["transmission_rays"]) == (ref["counters"]["reflection_rays"], ref["counters"]["transmission_rays"])
+
+
 def test_sketched_variants_error_behaviour(renderer):
     cfg = renderer.default_config()
     cfg.march_algorithm = 4

@@ -14,6 +14,10 @@ averaged frame to the averaged intervals; 4 (SP), 9 (in-thread loop) and 16 spp 
 bands.  Without any band: the batched schedule and the one-sample-per-launch schedule give the same frame bit for bit at 4, 9, 16,
 25 (16 SP + 9 continuing the sum) and 36 spp (16 + 16 + 4), at widths that are no multiple of 4 or 64; SP with tile-major output and
 a partition de-tiles to the single frame; a frame slot at 16 spp delivers the synchronous frame.
+
+The mirror and transmission chains (X.CHAIN_FRAMES): rt_render_chains returns what every secondary march did, and every link is
+held to the closed forms from the recorded link before it (X.chain_bands), with the NaN pattern, the summed RGB and the counters;
+its RGB and depth are rt_render's bit for bit, and the batched schedule it does not enter is tied to it bit for bit at 4 and 16 spp.
 """
 import numpy as np
 import pytest
@@ -240,3 +244,126 @@ def test_a_frame_slot_at_16_spp_delivers_the_synchronous_frame(renderer):
         renderer.resize(64, 64)  # releases the slot
         renderer.set_config(renderer.default_config())
     assert want.any() and np.array_equal(got, want)
+
+
+# ---- the mirror and transmission chains: rt_render_chains returns every secondary march, each judged from the link before it -------
+def setup_chain(r, name, w, h, fused=0, chains=True):
+    """Config, scene and size of chain case `name` (chains = False: the same frame with both counts 0) -> (scene, view, conf, rot, pos)."""
+    scene, view, conf = X.CHAIN_CASES[name][:3]
+    cfg = r.default_config()
+    for k, v in conf.items():
+        setattr(cfg, k, v)
+    if not chains:
+        cfg.reflections = cfg.transmissions = 0
+    cfg.fuse_levels = int(fused)
+    r.set_config(cfg)
+    r.set_scene(scene)
+    r.resize(w, h, view.get("ratio"))
+    return scene, view, conf, view.get("rot", (0, 0, 0, 1)), view.get("pos", (0, 0, 0))
+
+
+@pytest.mark.parametrize("fused", [0, 1])
+@pytest.mark.parametrize("name,w,h", X.CHAIN_FRAMES + X.GPU_ONLY_CHAIN_FRAMES)
+def test_chain_frames_lie_inside_every_band(renderer, name, w, h, fused):
+    """The frame without chains passes check_frame (pyramid and primary colour); with them, rt_render_chains returns the RGB and
+    depth of rt_render bit for bit, the pyramid is the same, and every recorded march, the summed RGB, the NaN pattern, the caps,
+    the coverage conditions and the counters are what X.chain_bands derives link by link (constants measured on the CPU)."""
+    try:
+        scene, view, conf, rot, pos = setup_chain(renderer, name, w, h, fused, chains=False)
+        rgb0, depth0 = renderer.render(rot, pos, want_depth=True)
+        levels0 = [renderer.read_level(i) for i in range(len(renderer.level_info()))]
+        setup_chain(renderer, name, w, h, fused)
+        rgb1, depth1 = renderer.render(rot, pos, want_depth=True)
+        stats1 = renderer.stats()
+        rgb, depth, chains = renderer.render_chains(rot, pos)
+        stats = renderer.stats()
+        levels = [renderer.read_level(i) for i in range(len(renderer.level_info()))]
+    finally:
+        renderer.set_config(renderer.default_config())
+    assert np.array_equal(rgb, rgb1) and np.array_equal(depth, depth1) and np.array_equal(depth, levels[-1])
+    assert all(np.array_equal(a, b) for a, b in zip(levels, levels0))
+    for k in ("hit_pixels", "shadow_rays", "reflection_rays", "transmission_rays"):
+        assert stats[k] == stats1[k], k
+    plain = X.Frame(scene, w, h, levels=levels0, rgb=rgb0, **view, **{k: v for k, v in conf.items() if k in X.OTHER_CONFIG})
+    depth_res, rgb_res = X.check_frame(plain)
+    for i, lv in enumerate(depth_res):
+        assert lv["bad"] == 0 and lv["far_bad"] == 0, (i, lv)
+    assert rgb_res["bad"] == 0 and rgb_res["miss_nonblack"] == 0 and rgb_res["ambiguous"] <= X.CAP_AMBIGUOUS, rgb_res
+    assert chains.shape == (h, w, conf["reflections"] + conf["transmissions"], 7)
+    fr = X.Frame(scene, w, h, levels=levels, rgb=rgb, chains=chains, **view, **conf)
+    res = X.check_chains(fr)
+    print(res)
+    X.assert_chains(fr, res, stats)
+    assert res["hits"] > 0.05 * w * h
+
+
+def test_the_chain_hook_refuses_and_writes_nothing(renderer):
+    """NULL outputs (RT_ERR_INVALID), both counts 0 and a partition of more than one rank (RT_ERR_STATE): sentinels stay."""
+    import ctypes as C
+
+    import raytracing_engine_amd as R
+
+    def sentinels(rows):
+        return np.full((64, 96, 3), 7.0, np.float32), np.full(renderer.level_info()[-1][::-1], 7.0, np.float32), np.full((64, 96, rows, 7), 7.0, np.float32)
+
+    def ptr(a):
+        return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+
+    try:
+        scene, view, conf, rot, pos = setup_chain(renderer, "room_turned_r2_t2_n1.5", 96, 64)
+        rot, pos = np.ascontiguousarray(rot, np.float32), np.ascontiguousarray(pos, np.float32)
+        lib = R.load()
+        for missing in range(3):
+            outs = sentinels(4)
+            args = [None if k == missing else a for k, a in enumerate(outs)]
+            assert lib.rt_render_chains(renderer._ctx, ptr(rot), ptr(pos), *[ptr(a) for a in args]) == -1
+            assert all((a == 7.0).all() for a in outs)
+        renderer.set_partition(1, 2)
+        outs = sentinels(4)
+        assert lib.rt_render_chains(renderer._ctx, ptr(rot), ptr(pos), *[ptr(a) for a in outs]) == -4
+        assert all((a == 7.0).all() for a in outs)
+        with pytest.raises(R.RtError) as e:
+            renderer.render_chains(rot, pos)
+        assert e.value.code == -4
+        renderer.set_partition(0, 1)
+        setup_chain(renderer, "room_turned_r2_t2_n1.5", 96, 64, chains=False)
+        outs = sentinels(1)
+        assert lib.rt_render_chains(renderer._ctx, ptr(rot), ptr(pos), *[ptr(a) for a in outs]) == -4
+        assert all((a == 7.0).all() for a in outs)
+        with pytest.raises(R.RtError) as e:
+            renderer.render_chains(rot, pos)
+        assert e.value.code == -4
+        # and the context renders on: the hook right after the refusals
+        setup_chain(renderer, "room_turned_r2_t2_n1.5", 96, 64)
+        rgb, depth, chains = renderer.render_chains(rot, pos)
+        assert rgb.any() and not np.isnan(chains[..., 0, :]).all()
+    finally:
+        renderer.set_partition(0, 1)
+        renderer.set_config(renderer.default_config())
+
+
+@pytest.mark.parametrize("spp", [4, 16])
+def test_batched_and_one_sample_per_launch_chain_frames_are_bit_identical(renderer, spp):
+    """test_batched_and_one_sample_per_launch_frames_are_bit_identical with both chains on (reflections 2, transmissions 2, index
+    1.5, the room): the batched launches, which rt_render_chains does not enter, give bit for bit the average of the one-sample
+    launches that it pins."""
+    name, w, h = "room_r2_t2_n1.5", 200, 120
+    try:
+        scene, view, conf, rot, pos = setup_chain(renderer, name, w, h, fused=0)
+        batched = renderer.render(rot, pos, spp=spp)
+        top = len(renderer.level_info()) - 1
+        level, sample = renderer.read_level(top, spp - 1)
+        stats = renderer.stats()
+        setup_chain(renderer, name, w, h, fused=1)
+        single = renderer.render(rot, pos, spp=spp)
+        level1, sample1 = renderer.read_level(top, 0)
+        stats1 = renderer.stats()
+    finally:
+        renderer.set_config(renderer.default_config())
+    assert sample == sample1 == spp - 1
+    assert np.array_equal(level[:h, :w], level1[:h, :w])
+    diff = np.flatnonzero((batched != single).any(-1))
+    assert not len(diff), (len(diff), np.abs(batched - single).max())
+    for k in ("hit_pixels", "shadow_rays", "reflection_rays", "transmission_rays"):
+        assert stats[k] == stats1[k] and stats[k] > 0, k
+    assert batched.any()

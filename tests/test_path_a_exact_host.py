@@ -369,3 +369,149 @@ def test_algorithm_1_depths_moved_by_one_cone_radius_are_rejected(frames, name, 
         res = X.check_depth(copy_of(fr, levels=levels), i)
         print(f"level {i}: rejected {res['bad']} of {res['hits']} hit texels ({100.0 * res['bad'] / max(res['hits'], 1):.1f} %)")
         assert res["bad"] > 0, (i, res)
+
+
+# ---- the mirror and transmission chains: every recorded march judged from the recorded link before it ----------------------------
+@pytest.fixture(scope="module")
+def chain_frames():
+    """Oracle frames with their recorded marches and the right reading's result, rendered once and never modified."""
+    cache = {}
+
+    def get(name, w, h):
+        if (name, w, h) not in cache:
+            fr = X.oracle_chain_frame(name, w, h)
+            cache[name, w, h] = (fr, X.check_chains(fr))
+        return cache[name, w, h]
+
+    return get
+
+
+def chain_copy(fr, chains=None, rgb=None):
+    scene, view, conf = X.CHAIN_CASES[fr.name][:3]
+    out = X.Frame(scene, fr.w, fr.h, levels=fr.levels, rgb=fr.rgb if rgb is None else rgb, chains=fr.chains if chains is None else chains, **view, **conf)
+    out.name = fr.name
+    return out
+
+
+def test_the_chain_cases_give_every_surface_its_own_scales():
+    for name, (scene, _, conf, _) in X.CHAIN_CASES.items():
+        sc = X.parse_scene(scene)
+        for key in ("diffuse", "specular"):
+            v = sc[key]
+            assert len(set(v.tolist())) == len(v) and (v > 0).all() and (v < 1).all(), (name, key, v)
+        assert conf["reflections"] + conf["transmissions"] > 0 and 0 < conf["reflectivity"] < 1 and 0 < conf["transparency"] < 1
+
+
+@pytest.mark.parametrize("name,w,h", X.CHAIN_FRAMES)
+def test_oracle_chains_lie_inside_every_band(chain_frames, name, w, h):
+    """The pyramid and the primary colour are those of a frame without chains (check_frame's depth part; the RGB now holds the
+    secondary light, so it is judged by the chain check alone); every recorded march against the link before it; the caps, the
+    coverage conditions and the counter identities."""
+    fr, res = chain_frames(name, w, h)
+    for i in range(fr.count):
+        lv = X.check_depth(fr, i)
+        assert lv["bad"] == 0 and lv["far_bad"] == 0, (i, lv)
+    print(res)
+    X.assert_chains(fr, res, fr.counters)
+    assert res["hits"] > 0.05 * w * h
+
+
+def test_the_chain_rows_hold_what_render_a_returns_without_them():
+    """want_chains changes nothing else: levels, RGB and counters are those of the plain call; mirror rows first."""
+    scene, view, conf = X.CHAIN_CASES["room_turned_r2_t2_n1.5"][:3]
+    cfg = O.default_config()
+    for k, v in conf.items():
+        setattr(cfg, k, v)
+    plain = O.render_a(O.scene_from_bytes(scene), 96, 64, cfg=cfg, **view)
+    rec = O.render_a(O.scene_from_bytes(scene), 96, 64, cfg=cfg, want_chains=True, **view)
+    assert "chains" not in plain and rec["chains"].shape == (64, 96, 4, 7)
+    assert np.array_equal(plain["rgb"], rec["rgb"]) and plain["counters"] == rec["counters"]
+    assert all(np.array_equal(a, b) for a, b in zip(plain["levels"], rec["levels"]))
+    ran = ~np.isnan(rec["chains"][..., 6])
+    assert ran[..., 0].sum() == (rec["levels"][-1][:64, :96] < cfg.render_dist).sum()  # every hit pixel marches its first mirror ray
+    assert not (ran[..., 1] & ~ran[..., 0]).any() and not (ran[..., 3] & ~ran[..., 2]).any()  # a later link only behind an earlier one
+    assert (ran[..., 2] & ~ran[..., 1]).any()  # the transmission chain does not wait for the mirror chain
+
+
+def test_the_chain_constants_are_the_measured_ones_and_under_the_bar():
+    """Lengths, positions and directions under 1e-5 relative to their magnitude, RGB under 1e-4; the guards are widths of the same
+    kind (a difference of two evaluations of one formula) and far below the 1 % they may cost."""
+    assert 0 < X.EPS_CHAIN_EYE <= 1e-5 and 0 < X.EPS_CHAIN_DIR <= 1e-5 and 0 < X.EPS_CHAIN_LEN <= 1e-5 and 0 < X.EPS_CHAIN_RGB <= 1e-4
+    assert 0 < X.GUARD_K <= 1e-5 and 0 < X.GUARD_DISC <= 1e-5 and X.CHAIN_COVERED == 0.10
+
+
+def test_the_chain_constants_are_four_times_the_measurement(chain_frames):
+    """Over the CPU cases (the 512 x 288 frame of `python tests/path_a_exact.py` is not rendered here, so: at most the constant / 4)."""
+    worst = {}
+    for name, w, h in X.CHAIN_FRAMES:
+        fr, _ = chain_frames(name, w, h)
+        res = X.check_chains(fr, 0.0, 0.0, 0.0, 0.0)
+        for k in ("eye", "dir", "len", "rgb", "guard_k", "guard_disc"):
+            worst[k] = max(worst.get(k, 0.0), res[k])
+    print(worst)
+    for k, c in (("eye", X.EPS_CHAIN_EYE), ("dir", X.EPS_CHAIN_DIR), ("len", X.EPS_CHAIN_LEN), ("rgb", X.EPS_CHAIN_RGB), ("guard_k", X.GUARD_K), ("guard_disc", X.GUARD_DISC)):
+        assert 0.5 * c / 4 <= worst[k] <= c / 4 * (1 + 1e-3), (k, worst[k], c)
+
+
+@pytest.mark.parametrize("wrong", X.WRONG_CHAINS)
+@pytest.mark.parametrize("name,w,h", X.CHAIN_FRAMES)
+def test_a_wrong_reading_of_the_chains_is_rejected(chain_frames, name, w, h, wrong):
+    """The recordings are the oracle's, the reference is what a misreading of rt_abi.h would compute: it has to reject them on every
+    case where the two readings differ (X.wrong_applies)."""
+    fr, right = chain_frames(name, w, h)
+    assert right["bad"] == 0
+    if not X.wrong_applies(wrong, fr, right):
+        if wrong == "cam_fall from the camera" and fr.reflections + fr.transmissions:
+            a, b = X.chain_bands(fr), X.chain_bands(fr, wrong)
+            assert np.array_equal(a["lo"], b["lo"]) and np.array_equal(a["hi"], b["hi"])  # clamped fall-off: the same intervals
+        return
+    res = X.check_chains(fr, wrong=wrong)
+    print(f"{wrong}: {res['bad']} of {res['hits']} hit pixels reject it (nan {res['bad_nan']}, eye {res['bad_eye']}, dir {res['bad_dir']}, len {res['bad_len']}, rgb {res['bad_rgb']})")
+    assert res["bad"] > 0, res
+
+
+def test_every_wrong_reading_is_tried_on_some_case(chain_frames):
+    for wrong in X.WRONG_CHAINS:
+        assert sum(X.wrong_applies(wrong, *chain_frames(name, w, h)) for name, w, h in X.CHAIN_FRAMES) >= 2, wrong
+
+
+@pytest.mark.parametrize("name,w,h", X.CHAIN_FRAMES)
+def test_exchanged_recordings_are_rejected(chain_frames, name, w, h):
+    """Two hit pixels' recordings exchanged (a row written to the wrong pixel): both pixels reject theirs."""
+    fr, right = chain_frames(name, w, h)
+    cb = X.chain_bands(fr)
+    k = len(cb["py"])
+    a, b = (cb["py"][k // 3], cb["px"][k // 3]), (cb["py"][2 * k // 3], cb["px"][2 * k // 3])
+    chains = fr.chains.copy()
+    chains[a], chains[b] = fr.chains[b], fr.chains[a]
+    res = X.check_chains(chain_copy(fr, chains=chains))
+    print(f"{res['bad']} of {res['hits']} hit pixels reject the exchange")
+    assert right["bad"] == 0 and res["bad"] == 2, res
+
+
+@pytest.mark.parametrize("name,w,h", X.CHAIN_FRAMES)
+def test_edited_recordings_are_rejected(chain_frames, name, w, h):
+    """The first link of every pixel rolled by one pixel, moved by one cone radius along the ray, and erased."""
+    fr, right = chain_frames(name, w, h)
+    rolled = fr.chains.copy()
+    rolled[:, :, 0] = np.roll(fr.chains[:, :, 0], 1, axis=1)
+    moved = fr.chains.copy()
+    moved[:, :, 0, 6] = np.where(moved[:, :, 0, 6] < fr.render_dist, moved[:, :, 0, 6] * (1.0 + fr.ray_radius) + fr.ray_radius, moved[:, :, 0, 6])
+    erased = fr.chains.copy()
+    erased[:, :, 0] = np.nan
+    for label, chains in (("rolled", rolled), ("moved", moved), ("erased", erased)):
+        res = X.check_chains(chain_copy(fr, chains=chains))
+        print(f"{label}: {res['bad']} of {res['hits']} hit pixels reject it")
+        assert res["bad"] > 0.02 * res["hits"], (label, res)
+
+
+def test_the_chain_hook_is_exported_and_bound(tmp_path):
+    import abi_boundary as AB
+
+    AB.exports(AB.CHAIN_HOOK)
+    AB.null_context(AB.CHAIN_HOOK)
+    import raytracing_engine_amd as R
+
+    out = np.full(7, 7.0, np.float32)
+    p = out.ctypes.data_as(C.POINTER(C.c_float))
+    assert R.load().rt_render_chains(None, p, p, p, p, p) == -1 and (out == 7.0).all()  # no context: nothing written
