@@ -47,12 +47,8 @@ class Config(C.Structure):
                 ("transmissions", C.c_uint32), ("transparency", C.c_float), ("refraction_index", C.c_float)]
 
 
-class Stats(C.Structure):
-    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("level_count", C.c_uint32), ("spp", C.c_uint32),
-                ("frames", C.c_uint64), ("primary_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
-                ("hit_pixels", C.c_uint64), ("cone_threads", C.c_uint64), ("ms_total", C.c_float),
-                ("ms_cone", C.c_float), ("ms_shade", C.c_float), ("ms_level", C.c_float * RT_MAX_LEVELS), ("ms_fused", C.c_float),
-                ("reflection_rays", C.c_uint64), ("transmission_rays", C.c_uint64)]
+class _Record(C.Structure):
+    """A struct the library fills for its caller: as_dict() is {member: value}, an array member as a list."""
 
     def as_dict(self):
         d = {}
@@ -60,6 +56,14 @@ class Stats(C.Structure):
             v = getattr(self, n)
             d[n] = list(v) if hasattr(v, "__len__") else v
         return d
+
+
+class Stats(_Record):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("level_count", C.c_uint32), ("spp", C.c_uint32),
+                ("frames", C.c_uint64), ("primary_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
+                ("hit_pixels", C.c_uint64), ("cone_threads", C.c_uint64), ("ms_total", C.c_float),
+                ("ms_cone", C.c_float), ("ms_shade", C.c_float), ("ms_level", C.c_float * RT_MAX_LEVELS), ("ms_fused", C.c_float),
+                ("reflection_rays", C.c_uint64), ("transmission_rays", C.c_uint64)]
 
 
 class PtParams(C.Structure):  # rt_pt_params
@@ -73,7 +77,7 @@ class MeshOptions(C.Structure):  # rt_mesh_options
     _fields_ = [("bvh_levels", C.c_uint32), ("blas_chunks", C.c_uint32)]
 
 
-class PtStats(C.Structure):  # rt_pt_stats
+class PtStats(_Record):  # rt_pt_stats
     _fields_ = [("n_tris", C.c_uint32), ("n_nodes", C.c_uint32), ("bvh_depth", C.c_uint32), ("n_lights", C.c_uint32),
                 ("stack_need", C.c_uint32), ("bvh_build_ms", C.c_float), ("stack_overflow", C.c_uint32), ("camera_rays", C.c_uint64),
                 ("bounce_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("nodes_visited", C.c_uint64),
@@ -88,20 +92,14 @@ class PtStats(C.Structure):  # rt_pt_stats
                 ("ms_build_blas", C.c_float), ("ms_build_tlas", C.c_float), ("ms_build_flatten", C.c_float),
                 ("pool_flushes", C.c_uint64), ("wave_rounds_all", C.c_uint64)]
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
-
 
 class RayQueryParams(C.Structure):  # rt_ray_query_params
     _fields_ = [("any_hit", C.c_uint32), ("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32),
                 ("tune_max_blocks", C.c_uint32)]
 
 
-class RayQueryStats(C.Structure):  # rt_ray_query_stats
+class RayQueryStats(_Record):  # rt_ray_query_stats
     _fields_ = [("rays", C.c_uint64), ("invalid_rays", C.c_uint64), ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 RAY_MISS, RAY_INVALID = -1, -2  # RT_RAY_MISS, RT_RAY_INVALID
@@ -115,12 +113,9 @@ class PointQueryParams(C.Structure):  # rt_point_query_params
     _fields_ = _TUNE_AND_COUNT
 
 
-class PointQueryStats(C.Structure):  # rt_point_query_stats
+class PointQueryStats(_Record):  # rt_point_query_stats
     _fields_ = [("points", C.c_uint64), ("invalid_points", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
                 ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 POINT_MISS, POINT_INVALID = RAY_MISS, RAY_INVALID  # RT_POINT_MISS, RT_POINT_INVALID
@@ -131,83 +126,62 @@ class SideQueryParams(C.Structure):  # rt_side_query_params
     _fields_ = _TUNE_AND_COUNT
 
 
-class SideQueryStats(C.Structure):  # rt_side_query_stats
+class SideQueryStats(_Record):  # rt_side_query_stats
     _fields_ = [("points", C.c_uint64), ("invalid_points", C.c_uint64), ("skipped_points", C.c_uint64), ("walks", C.c_uint64), ("third_walks", C.c_uint64),
                 ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64), ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class HitQueryParams(C.Structure):  # rt_hit_query_params
     _fields_ = _TUNE_AND_COUNT
 
 
-class HitQueryStats(C.Structure):  # rt_hit_query_stats
+class HitQueryStats(_Record):  # rt_hit_query_stats
     _fields_ = [("rays", C.c_uint64), ("invalid_rays", C.c_uint64), ("hits", C.c_uint64), ("hits_written", C.c_uint64), ("incomplete_rays", C.c_uint64),
                 ("slice_overflow", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64), ("stack_overflow", C.c_uint32),
                 ("launches", C.c_uint32), ("ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class NeighborQueryParams(C.Structure):  # rt_neighbor_query_params
     _fields_ = _TUNE_AND_COUNT
 
 
-class NeighborQueryStats(C.Structure):  # rt_neighbor_query_stats
+class NeighborQueryStats(_Record):  # rt_neighbor_query_stats
     _fields_ = [("points", C.c_uint64), ("invalid_points", C.c_uint64), ("neighbors", C.c_uint64), ("neighbors_written", C.c_uint64),
                 ("incomplete_points", C.c_uint64), ("slice_overflow", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
                 ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class OverlapQueryParams(C.Structure):  # rt_overlap_query_params
     _fields_ = _TUNE_AND_COUNT
 
 
-class OverlapQueryStats(C.Structure):  # rt_overlap_query_stats
+class OverlapQueryStats(_Record):  # rt_overlap_query_stats
     _fields_ = [("triangles", C.c_uint64), ("invalid_triangles", C.c_uint64), ("overlaps", C.c_uint64), ("overlaps_written", C.c_uint64),
                 ("incomplete_triangles", C.c_uint64), ("slice_overflow", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
                 ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
-
-class OverlapSegmentStats(C.Structure):  # rt_overlap_segment_stats
+class OverlapSegmentStats(_Record):  # rt_overlap_segment_stats
     _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("touches", C.c_uint64), ("skipped_incomplete", C.c_uint64), ("bad_entries", C.c_uint64),
                 ("launches", C.c_uint32), ("ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class ClearanceQueryParams(C.Structure):  # rt_clearance_query_params
     _fields_ = _TUNE_AND_COUNT
 
 
-class ClearanceQueryStats(C.Structure):  # rt_clearance_query_stats
+class ClearanceQueryStats(_Record):  # rt_clearance_query_stats
     _fields_ = [("queries", C.c_uint64), ("invalid_triangles", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
                 ("stack_overflow", C.c_uint32), ("ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class KnnQueryParams(C.Structure):  # rt_knn_query_params
     _fields_ = _TUNE_AND_COUNT
 
 
-class KnnQueryStats(C.Structure):  # rt_knn_query_stats
+class KnnQueryStats(_Record):  # rt_knn_query_stats
     _fields_ = [("points", C.c_uint64), ("invalid_points", C.c_uint64), ("neighbors", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
                 ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 assert C.sizeof(MutableData) == 656 and C.sizeof(Material) == 32 and C.sizeof(Object) == 16 and C.sizeof(Light) == 32

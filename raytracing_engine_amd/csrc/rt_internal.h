@@ -386,11 +386,50 @@ struct QueryState {
     hipEvent_t ev[2] = {nullptr, nullptr};  // around the launch
     bool pending = false;  // a query has been enqueued whose counters and time rt_get_*_query_stats has not read yet
 };
-// A listing kind's QueryState (no LDS beside the stacks, one set of spill columns: one group per level) and its pending call's steps
-struct ListingState {
-    explicit ListingState(const char* what) : qs(LQ_STAT_WORDS, what, 0u, 1u) {}
+// One query kind in a context: what is in flight and the public statistics of the kind's last query (what the host knows at the
+// enqueue; rt_get_*_query_stats adds the counters and the time)
+template <class Stats>
+struct QueryKind {
+    QueryKind(uint32_t k, const char* what, uint32_t lds, uint32_t halves) : qs(k, what, lds, halves) {}
     QueryState qs;
+    Stats stats{};
+};
+// A listing kind (no LDS beside the stacks, one set of spill columns: one group per level) and its pending call's steps
+template <class Stats>
+struct ListingKind : QueryKind<Stats> {
+    explicit ListingKind(const char* what) : QueryKind<Stats>(LQ_STAT_WORDS, what, 0u, 1u) {}
     uint32_t steps = 0;  // bit 0: the count step ran, bit 1: the fill step
+};
+// Device scratch that grows by size class (powers of two), first use only
+template <class T>
+struct Scratch {
+    DevPtr<T> d;
+    size_t words = 0;
+};
+// Every query kind of a context, and the scratch two of them keep; nothing outside rt_abi_query.hip looks inside.  A new kind is a
+// member here, a line in for_each and its entries there.
+struct Queries {
+    // (rays: the 2 KiB octant table, two spill halves as the frames hold; the others: no table, one set of columns)
+    QueryKind<rt_ray_query_stats> rays{RQ_STAT_WORDS, "ray-query", 2048u, 2u};
+    QueryKind<rt_point_query_stats> points{PQ_STAT_WORDS, "point-query", 0u, 1u};
+    QueryKind<rt_side_query_stats> sides{SQ_STAT_WORDS, "side-query", 0u, 1u};
+    ListingKind<rt_hit_query_stats> hits{"hit-query"};                 // rt_count / fill / list_ray_hits_device
+    ListingKind<rt_neighbor_query_stats> neighbors{"neighbor-query"};  // rt_count / fill / list_neighbors_device
+    ListingKind<rt_overlap_query_stats> overlaps{"overlap-query"};     // rt_count / fill / list_overlaps_device
+    // rt_overlap_segments_device: a flat kernel, no stack (the block's stream heads stay unused)
+    QueryKind<rt_overlap_segment_stats> segments{SG_STAT_WORDS, "overlap-segments", 0u, 0u};
+    QueryKind<rt_clearance_query_stats> clearance{CQ_STAT_WORDS, "clearance-query", 0u, 1u};  // rt_query_clearance_device: the points' walk, one set of columns
+    QueryKind<rt_knn_query_stats> knn{KQ_STAT_WORDS, "knn-query", 0u, 1u};                    // rt_query_knn_device: the points' walk, one set of columns
+    // rt_overlap_segments_device: original triangle index -> leaf position of the current mesh, rewritten by every call; the context's own
+    // (a DeviceMesh is shared read-only, §6.12)
+    Scratch<uint32_t> tri_inverse;
+    // the listing kinds' scan: the 64-bit count column (n + 1), the scan's tile sums and its total
+    Scratch<unsigned long long> list_scan;
+
+    template <class F>
+    void for_each(F&& f) {
+        f(rays), f(points), f(sides), f(hits), f(neighbors), f(overlaps), f(segments), f(clearance), f(knn);
+    }
 };
 
 // A mesh resident on the device: the arrays the kernels read and what the host knows about them.  Made by the host build
@@ -437,30 +476,9 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
     DevPtr<uint32_t> d_ctr;
     DevPtr<unsigned long long> d_stats;  // PT_STAT_WORDS words
     rt_pt_stats stats{};
-    // the query kinds (rays, closest points, sides, all hits, neighbours, overlaps, overlap segments, clearance, k-nearest): what is in flight, and the statistics of the last query of each kind
-    // (rays: the 2 KiB octant table, two spill halves as the frames hold; the others: no table, one set of columns)
-    QueryState ray_query{RQ_STAT_WORDS, "ray-query", 2048u, 2u}, point_query{PQ_STAT_WORDS, "point-query", 0u, 1u}, side_query{SQ_STAT_WORDS, "side-query", 0u, 1u};
-    ListingState hit_query{"hit-query"}, neighbor_query{"neighbor-query"};  // rt_count / fill / list_ray_hits_device, rt_count / fill / list_neighbors_device
-    ListingState overlap_query{"overlap-query"};                            // rt_count / fill / list_overlaps_device
-    QueryState segment_query{SG_STAT_WORDS, "overlap-segments", 0u, 0u};    // rt_overlap_segments_device: a flat kernel, no stack (the block's stream heads stay unused)
-    QueryState clearance_query{CQ_STAT_WORDS, "clearance-query", 0u, 1u};   // rt_query_clearance_device: the points' walk, one set of columns
-    QueryState knn_query{KQ_STAT_WORDS, "knn-query", 0u, 1u};               // rt_query_knn_device: the points' walk, one set of columns
-    rt_knn_query_stats knn_query_stats{};
-    rt_ray_query_stats ray_query_stats{};
-    rt_point_query_stats point_query_stats{};
-    rt_side_query_stats side_query_stats{};
-    rt_hit_query_stats hit_query_stats{};
-    rt_neighbor_query_stats neighbor_query_stats{};
-    rt_overlap_query_stats overlap_query_stats{};
-    rt_overlap_segment_stats segment_stats{};
-    rt_clearance_query_stats clearance_query_stats{};
-    // rt_overlap_segments_device: original triangle index -> leaf position of the current mesh, rewritten by every call; the context's own
-    // (a DeviceMesh is shared read-only, §6.12); grows by size class, first use only
-    DevPtr<uint32_t> d_tri_inverse;
-    size_t tri_inverse_words = 0;
-    // the listing kinds' scan: the 64-bit count column (n + 1), the scan's tile sums and its total; grows by size class, first use only
-    DevPtr<unsigned long long> d_list_scan;
-    size_t list_scan_words = 0;
+    // the query kinds (rays, closest points, sides, all hits, neighbours, overlaps, overlap segments, clearance, k-nearest): what is in
+    // flight, the statistics of the last query of each kind and their scratch
+    Queries queries;
 };
 
 struct Ctx {

@@ -328,6 +328,10 @@ class Renderer:
         opt = _lib.MeshOptions(bvh_levels, blas_chunks)
         self._check(self._lib.rt_set_mesh_ex(self._ctx, _fptr(verts), _fptr(albedo), _fptr(emission), len(verts), C.byref(opt)))
 
+    def _on_device(self, t):
+        """Does torch tensor `t` lie on this renderer's device?  What every tensor check below asks, and nothing else does."""
+        return t.device.type == "cuda" and t.device.index == self.device
+
     def _device_rows(self, t, name, width):
         """Rows of `width` floats in torch tensor `t`, which must be float32, contiguous, on this renderer's device and of shape
         (n, width) or flat; ValueError otherwise."""
@@ -339,7 +343,7 @@ class Renderer:
             raise ValueError(f"{name} must be float32, got {t.dtype}")
         if not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous")
-        if t.device.type != "cuda" or t.device.index != self.device:
+        if not self._on_device(t):
             raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
         if t.dim() == 2 and t.shape[1] == width:
             return t.shape[0]
@@ -462,26 +466,23 @@ class Renderer:
     RAY_MISS, RAY_INVALID = _lib.RAY_MISS, _lib.RAY_INVALID
 
     def _device_ints(self, t, name, n, kind):
-        """`t` must be a contiguous torch tensor of n elements of the integer type `kind` on this renderer's device; ValueError otherwise."""
+        """`t` must be a contiguous torch tensor of the integer type `kind` on this renderer's device, of n elements in one dimension or,
+        where n is a tuple, of that shape; ValueError otherwise."""
         import torch
 
-        dtype = getattr(torch, kind)
+        shape = n if isinstance(n, tuple) else (n,)
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
-        if t.dtype != dtype or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device or t.dim() != 1 or t.numel() != n:
-            raise ValueError(f"{name} must be a contiguous {kind} tensor of shape ({n},) on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if t.dtype != getattr(torch, kind) or not t.is_contiguous() or not self._on_device(t) or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a contiguous {kind} tensor of shape {shape} on cuda:{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
     def _device_i32(self, t, name, n):
         """_device_ints for int32."""
         self._device_ints(t, name, n, "int32")
 
     def _device_i32_rows(self, t, name, n, cols):
-        """`t` must be a contiguous int32 torch tensor of shape (n, cols) on this renderer's device; ValueError otherwise."""
-        import torch
-
-        if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device
-                or tuple(t.shape) != (n, cols)):
-            raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({n}, {cols}) on cuda:{self.device}")
+        """_device_ints for int32 of shape (n, cols)."""
+        self._device_ints(t, name, (n, cols), "int32")
 
     def _device_i64(self, t, name, n):
         """_device_ints for int64."""
@@ -495,17 +496,31 @@ class Renderer:
                 raise TypeError(f"{method}() got an unexpected keyword argument {k!r}")
             setattr(params, k, int(v))
 
-    def _query_out(self, t, name, n, dtype, dev, cols=1):
-        """The out tensor `name` of a query over n items: a new one (t is None), or t once it is what the query can fill."""
+    def _query_out(self, t, name, n, dtype, dev, cols=1, exact=False):
+        """The out tensor `name` of a query over n items: a new one (t is None), or t once it is what the query can fill.  A float32
+        tensor of several columns may be flat unless `exact`; an integer one has the shape (n, cols), and `exact` says so of one column."""
         import torch
 
+        shape = (n,) if cols == 1 and not exact else (n, cols)
         if t is None:
-            return torch.empty(n if cols == 1 else (n, cols), dtype=dtype, device=dev)
-        if dtype in (torch.int32, torch.int64):
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if dtype == torch.int32 and len(shape) == 2:  # (no int64 output has columns)
+            self._device_i32_rows(t, name, n, cols)
+        elif dtype in (torch.int32, torch.int64):
             (self._device_i32 if dtype == torch.int32 else self._device_i64)(t, name, n)
-        elif self._device_rows(t, name, cols) != n or (cols == 1 and t.dim() != 1):
-            raise ValueError(f"{name} must have shape ({n},), got {tuple(t.shape)}" if cols == 1 else f"{name} must hold {n} rows of {cols}")
+        elif self._device_rows(t, name, cols) != n or ((cols == 1 or exact) and tuple(t.shape) != shape):
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}" if cols == 1 or exact else f"{name} must hold {n} rows of {cols}")
         return t
+
+    @staticmethod
+    def _out_tensors(out, k, message, room=None):
+        """The k tensors of `out`, which must be a tuple or list of exactly k (ValueError(message) otherwise), padded with None to
+        `room`; as many None where out is None."""
+        if out is None:
+            return (None,) * (room or k)
+        if not isinstance(out, (tuple, list)) or len(out) != k:
+            raise ValueError(message)
+        return tuple(out) + (None,) * ((room or k) - k)
 
     def _query_call(self, sync, fn, *args):
         """The C call of a query between the two halves of `sync`: torch's current stream is finished before, ours after."""
@@ -542,9 +557,7 @@ class Renderer:
         """The (dist, tri, point) tensors of query_points / query_signed_distance: new ones, or those of `out`.  first: dist's name."""
         import torch
 
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != (3 if want_points else 2)):
-            raise ValueError(f"out must be ({first}, tri, point), or the pair ({first}, tri) with want_points=False")
-        dist, tri, pt = (tuple(out) + (None,))[:3] if out is not None else (None, None, None)
+        dist, tri, pt = self._out_tensors(out, 3 if want_points else 2, f"out must be ({first}, tri, point), or the pair ({first}, tri) with want_points=False", room=3)
         dist = self._query_out(dist, f"out {first}", n, torch.float32, dev)
         tri = self._query_out(tri, "out tri", n, torch.int32, dev)
         if want_points:
@@ -575,10 +588,8 @@ class Renderer:
         if any_hit:
             t, tri = None, out
         else:
-            k = 4 if attributes else 2
-            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != k):
-                raise ValueError("out must be (t, tri, uv, normal) with attributes=True" if attributes else "out must be the pair (t, tri) for a closest-hit query")
-            t, tri, uv, normal = (tuple(out) + (None, None))[:4] if out is not None else (None,) * 4
+            t, tri, uv, normal = self._out_tensors(out, 4 if attributes else 2, "out must be (t, tri, uv, normal) with attributes=True" if attributes else
+                                                   "out must be the pair (t, tri) for a closest-hit query", room=4)
         tri = self._query_out(tri, "out tri", n, torch.int32, origins.device)
         if not any_hit:
             t = self._query_out(t, "out t", n, torch.float32, origins.device)
@@ -621,10 +632,9 @@ class Renderer:
             self._query_call(sync, self._lib.rt_query_points_device, points, rmax, n, C.byref(p), dist, tri, pt)
             return dist, tri, pt
         k = 3 if want_points else 2
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != k + 2):
-            raise ValueError("out must be (dist, tri, point, uv, normal) with attributes=True, or (dist, tri, uv, normal) with want_points=False")
-        dist, tri, pt = self._point_out(None if out is None else tuple(out)[:k], "dist", n, points.device, want_points)
-        uv, normal = tuple(out)[k:] if out is not None else (None, None)
+        out = self._out_tensors(out, k + 2, "out must be (dist, tri, point, uv, normal) with attributes=True, or (dist, tri, uv, normal) with want_points=False")
+        dist, tri, pt = self._point_out(out[:k], "dist", n, points.device, want_points)
+        uv, normal = out[k:]
         uv = self._query_out(uv, "out uv", n, torch.float32, points.device, cols=2)
         normal = self._query_out(normal, "out normal", n, torch.float32, points.device, cols=3)
         self._query_call(sync, self._lib.rt_query_points_attr_device, points, rmax, n, C.byref(p), dist, tri, pt, uv, normal)
@@ -669,21 +679,14 @@ class Renderer:
         p.count_traversal = int(bool(count_traversal))
         self._query_tune(p, tune, "query_sides")
         if want_crossings:
-            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-                raise ValueError("out must be the pair (inside, crossings) with want_crossings=True")
-            inside, crossings = out if out is not None else (None, None)
+            inside, crossings = self._out_tensors(out, 2, "out must be the pair (inside, crossings) with want_crossings=True")
         else:
             if isinstance(out, (tuple, list)):
                 raise ValueError("out must be the inside tensor, or (inside, crossings) with want_crossings=True")
             inside, crossings = out, None
         inside = self._query_out(inside, "out inside", n, torch.int32, points.device)
         if want_crossings:
-            if crossings is None:
-                crossings = torch.empty((n, 3), dtype=torch.int32, device=points.device)
-            else:
-                if not isinstance(crossings, torch.Tensor) or crossings.dim() != 2 or crossings.shape[1] != 3:
-                    raise ValueError(f"out crossings must have shape ({n}, 3)")
-                self._device_i32(crossings.view(-1) if crossings.is_contiguous() else crossings, "out crossings", 3 * n)
+            crossings = self._query_out(crossings, "out crossings", n, torch.int32, points.device, cols=3)
         self._query_call(sync, self._lib.rt_query_sides_device, points, n, C.byref(p), inside, crossings, None)
         return (inside, crossings) if want_crossings else inside
 
@@ -752,9 +755,7 @@ class Renderer:
         capacity = int(capacity)
         if capacity < 0:
             raise ValueError(f"capacity must be >= 0, got {capacity}")
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 4):
-            raise ValueError("out must be (offsets, tri, edges, counts)" if tri_first else f"out must be (offsets, {key}, tri, counts)")
-        offsets, keys, tri, counts = out if out is not None else (None, None, None, None)
+        offsets, keys, tri, counts = self._out_tensors(out, 4, "out must be (offsets, tri, edges, counts)" if tri_first else f"out must be (offsets, {key}, tri, counts)")
         keys, tri = order(keys, tri)  # (its own inverse)
         offsets = self._query_out(offsets, "out offsets", n + 1, torch.int64, dev)
         keys = self._query_out(keys, f"out {key}", capacity, key_dtype, dev)
@@ -933,9 +934,8 @@ class Renderer:
         p = ClearanceQueryParams()
         p.count_traversal = int(bool(count_traversal))
         self._query_tune(p, tune, "query_clearance")
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != (4 if want_points else 2)):
-            raise ValueError("out must be (dist, tri, point_query, point_mesh), or the pair (dist, tri) with want_points=False")
-        dist, tri, pq, pm = (tuple(out) + (None, None))[:4] if out is not None else (None,) * 4
+        dist, tri, pq, pm = self._out_tensors(out, 4 if want_points else 2, "out must be (dist, tri, point_query, point_mesh), or the pair (dist, tri) with want_points=False",
+                                              room=4)
         dist = self._query_out(dist, "out dist", n, torch.float32, tris.device)
         tri = self._query_out(tri, "out tri", n, torch.int32, tris.device)
         if want_points:
@@ -978,17 +978,9 @@ class Renderer:
         p = KnnQueryParams()
         p.count_traversal = int(bool(count_traversal))
         self._query_tune(p, tune, "query_knn")
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
-            raise ValueError("out must be (dist, tri, counts)")
-        dist, tri, counts = out if out is not None else (None, None, None)
-        if dist is None:
-            dist = torch.empty((n, k), dtype=torch.float32, device=points.device)
-        elif not isinstance(dist, torch.Tensor) or dist.dim() != 2 or tuple(dist.shape) != (n, k) or self._device_rows(dist, "out dist", k) != n:
-            raise ValueError(f"out dist must be a contiguous float32 tensor of shape ({n}, {k}) on cuda:{self.device}")
-        if tri is None:
-            tri = torch.empty((n, k), dtype=torch.int32, device=points.device)
-        else:
-            self._device_i32_rows(tri, "out tri", n, k)
+        dist, tri, counts = self._out_tensors(out, 3, "out must be (dist, tri, counts)")
+        dist = self._query_out(dist, "out dist", n, torch.float32, points.device, cols=k, exact=True)
+        tri = self._query_out(tri, "out tri", n, torch.int32, points.device, cols=k, exact=True)
         counts = self._query_out(counts, "out counts", n, torch.int32, points.device)
         self._query_call(sync, self._lib.rt_query_knn_device, points, rmax, n, k, C.byref(p), dist, tri, counts)
         return dist, tri, counts

@@ -98,37 +98,12 @@ def default_params(kind):
 
 
 class OnCpu(R.Renderer):
-    """A renderer whose tensor checks are Renderer's own without the device: a CPU tensor of the right type, layout and shape passes,
-    so that what a wrapper refuses behind those checks is reached without a GPU (tests/test_support_host.py compares the two)."""
+    """A renderer whose tensor checks are Renderer's own, told that every tensor lies on its device: a CPU tensor of the right type,
+    layout and shape passes, so that what a wrapper refuses behind those checks is reached without a GPU (tests/test_support_host.py
+    compares the two)."""
 
-    def _device_rows(self, t, name, width):
-        import torch
-
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous float32 torch tensor")
-        if t.dim() == 2 and t.shape[1] == width:
-            return t.shape[0]
-        if t.dim() == 1 and t.numel() % width == 0:
-            return t.numel() // width
-        raise ValueError(f"{name} must have shape (n, {width}) or ({width} n,), got {tuple(t.shape)}")
-
-    def _device_ints(self, t, name, n, kind):
-        import torch
-
-        if not isinstance(t, torch.Tensor) or t.dtype != getattr(torch, kind) or not t.is_contiguous() or t.dim() != 1 or t.numel() != n:
-            raise ValueError(f"{name} must be a contiguous {kind} tensor of shape ({n},)")
-
-    def _device_i32(self, t, name, n):
-        self._device_ints(t, name, n, "int32")
-
-    def _device_i64(self, t, name, n):
-        self._device_ints(t, name, n, "int64")
-
-    def _device_i32_rows(self, t, name, n, cols):
-        import torch
-
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (n, cols):
-            raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({n}, {cols})")
+    def _on_device(self, t):
+        return True
 
 
 def cpu_renderer():
