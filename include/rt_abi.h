@@ -859,6 +859,46 @@ int rt_query_knn_device(rt_ctx* ctx, const void* points_dev, const void* rmax_de
                         const rt_knn_query_params* params /* NULL = defaults */, void* dist_out_dev /* n x k f32 */,
                         void* tri_out_dev /* n x k i32 */, void* count_out_dev /* n i32, may be NULL */);
 int rt_get_knn_query_stats(rt_ctx* ctx, rt_knn_query_stats* stats); /* synchronises the stream; the last query */
+/* Sphere-cast (sweep) queries on device arrays: a sphere of radius r[i] starts with its centre at o[i] and moves
+ * along d[i]; how far does it get before it touches the current mesh, which triangle does it touch first, and where?  Enqueued on
+ * the context's stream behind the work already there; no host synchronisation, and no allocation after the first query of a mesh or
+ * size class.  origins_dev, dirs_dev: n x 3 f32; radius_dev: n f32; tmax_dev: n f32 or NULL (+inf); device memory of the context's
+ * device, only read.  d is not normalised: t is in units of |d|, as for rt_query_rays_device, and the centre at t is o + t d, one
+ * fma per component.  The arithmetic is csrc/sweep_tri.h, fp32 only, on the resident record words v0, e1, e2 of each triangle T:
+ * toi(T) = 0 when the start touches, closest_on_tri(o, T).d2 <= r * r (csrc/point_tri.h; the product in fp32); otherwise the
+ * smallest accepted candidate among the entry times into the seven features of the sphere-swept triangle - the face's plane offset
+ * by r towards the origin's side, the three edge cylinders where the contact parameter lies in [0, 1], the three vertex spheres -
+ * each only where the centre approaches the feature, a candidate at or below 0 raised to the smallest positive normal float.  A
+ * candidate t is accepted when the centre at t evaluates to a distance of at most r + 2^-21 S from T with closest_on_tri, S =
+ * max(|o|_inf, r, |v0|_inf + max(|e1|_inf, |e2|_inf)): a feature proposes, the evaluated distance decides, so a needle cannot
+ * pick a wrong feature and a triangle without area is the capsules and spheres it consists of.  A zero direction touches only at
+ * t = 0; r = 0 is a ray against the closed triangle.  The answer for item i is the lexicographic minimum of (toi, original triangle
+ * index) over all triangles with toi < tmax[i] (strictly) and toi <= FLT_MAX: among several triangles touched at the start the
+ * lowest index wins.  t_out_dev[i] = toi (f32), tri_out_dev[i] = the original triangle index (i32), point_out_dev (n x 3 f32, may be
+ * NULL) = the contact point: closest_on_tri of the centre at t against that triangle.  A miss is +inf, RT_RAY_MISS and NaNs;
+ * !(tmax > 0) misses without a walk.  An item with a non-finite component of o or d, a radius that is NaN, negative or above
+ * 32 x max(1, largest |vertex coordinate| of the mesh), a NaN tmax, or an origin component beyond that same reach is not answered:
+ * tri_out = RT_RAY_INVALID, NaNs, counted in invalid_sweeps.  d . d must neither overflow nor underflow to 0 in fp32, else the item
+ * is answered from its start alone.  Nothing beyond element n - 1 of an output is written.  Lifetime rules, meshes (every kind; the
+ * mesh is only read, a shared mesh stays shared) and errors are rt_query_points_device's, all before anything is enqueued or
+ * written.  n == 0: RT_OK, nothing is done. */
+typedef struct rt_sweep_query_params {
+    uint32_t tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks; /* as rt_point_query_params */
+    uint32_t count_traversal;                                                      /* 1: fill nodes_visited / tris_tested */
+} rt_sweep_query_params;
+typedef struct rt_sweep_query_stats {
+    uint64_t sweeps, invalid_sweeps;     /* the last query with n > 0: items asked, items answered RT_RAY_INVALID */
+    uint64_t hits;                       /* items answered with a triangle */
+    uint64_t nodes_visited, tris_tested; /* count_traversal = 1 only: node records fetched, triangle records fetched, over all items */
+    uint32_t stack_overflow;             /* must be 0 */
+    uint32_t launches;                   /* kernel launches of that query */
+    float ms;                            /* HIP-event time of its launch */
+} rt_sweep_query_stats;
+int rt_default_sweep_query_params(rt_sweep_query_params* p);
+int rt_query_sweeps_device(rt_ctx* ctx, const void* origins_dev, const void* dirs_dev, const void* radius_dev, const void* tmax_dev /* may be NULL */,
+                           uint32_t n, const rt_sweep_query_params* params /* NULL = defaults */, void* t_out_dev /* f32 n */,
+                           void* tri_out_dev /* i32 n */, void* point_out_dev /* f32 3n, may be NULL */);
+int rt_get_sweep_query_stats(rt_ctx* ctx, rt_sweep_query_stats* stats); /* synchronises the stream; the last query */
 /* Test hook (the product entry is rt_query_rays_device): trace n caller-supplied rays (host arrays, n*3 each).  any_hit = 0: closest hit,
  * t_out[i] = distance (inf on miss), tri_out[i] = original triangle index or -1;
  * any_hit = 1: tri_out[i] = 1 if the open segment (o, o + 0.999*d) is occluded. */

@@ -106,7 +106,7 @@ RAY_MISS, RAY_INVALID = -1, -2  # RT_RAY_MISS, RT_RAY_INVALID
 
 
 _TUNE_AND_COUNT = [("tune_refill_min", C.c_uint32), ("tune_blocks_per_cu", C.c_uint32), ("tune_lds_stack", C.c_uint32), ("tune_max_blocks", C.c_uint32),
-                   ("count_traversal", C.c_uint32)]  # rt_point / side / hit / neighbor / overlap_query_params alike
+                   ("count_traversal", C.c_uint32)]  # rt_point / side / hit / neighbor / overlap / clearance / knn / sweep_query_params alike
 
 
 class PointQueryParams(C.Structure):  # rt_point_query_params
@@ -181,6 +181,15 @@ class KnnQueryParams(C.Structure):  # rt_knn_query_params
 
 class KnnQueryStats(_Record):  # rt_knn_query_stats
     _fields_ = [("points", C.c_uint64), ("invalid_points", C.c_uint64), ("neighbors", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
+                ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
+
+
+class SweepQueryParams(C.Structure):  # rt_sweep_query_params
+    _fields_ = _TUNE_AND_COUNT
+
+
+class SweepQueryStats(_Record):  # rt_sweep_query_stats
+    _fields_ = [("sweeps", C.c_uint64), ("invalid_sweeps", C.c_uint64), ("hits", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64),
                 ("stack_overflow", C.c_uint32), ("launches", C.c_uint32), ("ms", C.c_float)]
 
 
@@ -273,6 +282,9 @@ PROTOTYPES = {
     "rt_default_knn_query_params": (C.c_int, [C.POINTER(KnnQueryParams)]),
     "rt_query_knn_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(KnnQueryParams), _vp, _vp, _vp]),
     "rt_get_knn_query_stats": (C.c_int, [_vp, C.POINTER(KnnQueryStats)]),
+    "rt_default_sweep_query_params": (C.c_int, [C.POINTER(SweepQueryParams)]),
+    "rt_query_sweeps_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(SweepQueryParams), _vp, _vp, _vp]),
+    "rt_get_sweep_query_stats": (C.c_int, [_vp, C.POINTER(SweepQueryStats)]),
     "rt_trace_rays": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32)]),
     "rt_trace_rays_counted": (C.c_int, [_vp, _fp, _fp, C.c_uint32, C.c_int, _fp, C.POINTER(C.c_int32), _u32p]),
 }

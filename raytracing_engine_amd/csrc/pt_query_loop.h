@@ -1,8 +1,8 @@
 // pt_query_loop.h — path B, device side: what the persistent query kernels share: the refilling loop
 // over pt_queue.h's streams (RT_QUERY_LOOP), and the two walks that a kind puts inside it - the nearest-first walk (clearance,
-// k-nearest) and the group walk (sides, neighbours, overlaps; the ray queries' round is pt_traverse.h's inline_round).
+// k-nearest, sphere casts) and the group walk (sides, neighbours, overlaps; the ray queries' round is pt_traverse.h's inline_round).
 // Used by pt_query_rays (pt_trace.hip) and by pt_side_query.hip, pt_neighbor_query.hip, pt_overlap_query.hip,
-// pt_clearance_query.hip and pt_knn_query.hip.  pt_query_points and pt_query_hits keep their own text of the loop and of their
+// pt_clearance_query.hip, pt_knn_query.hip and pt_sweep_query.hip.  pt_query_points and pt_query_hits keep their own text of the loop and of their
 // walks: as lanes they were slower (profiles/refactor_query_loop.txt).  The render loops of pt_trace.hip (two queues, a
 // software-pipelined head) are their own.
 #pragma once

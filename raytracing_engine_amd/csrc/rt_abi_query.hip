@@ -1,6 +1,6 @@
 // rt_abi_query.hip — C-ABI entry points of path B's queries on device arrays: rays, closest points (§6.14),
 // sides (§6.15), all hits (§6.16), neighbours (§6.17), the attribute variants of the first two (§6.18), overlaps (§6.20) and their
-// segments (§6.21: a flat kernel over a list, with an enqueue of its own), clearance (§6.22), k nearest (§6.23).  Host code only.
+// segments (§6.21: a flat kernel over a list, with an enqueue of its own), clearance (§6.22), k nearest (§6.23), sphere casts (§6.24).  Host code only.
 // A kind is a parameter struct, its arrays, a launcher and its counters; its state in the context is a member of rt::Queries
 // (rt_internal.h).  What the kinds share is written once here:
 //   the refusals before a parameter struct is looked at (check_query_items) and those of the struct (check_query_params), the
@@ -9,7 +9,7 @@
 //   a kind's first use (ensure_block), scratch that grows by size class (grow_scratch), the plan and the enqueue (prepare_query,
 //   run_query);
 //   the read-back: query_stats over a kind's table of (member, counter word).
-// A single-answer kind - rays, points, sides, clearance, k nearest - is prepare_* (the array checks, the query struct, the plan:
+// A single-answer kind - rays, points, sides, clearance, k nearest, sphere casts - is prepare_* (the array checks, the query struct, the plan:
 // everything that can refuse) and run_* (the launch and the host's part of the statistics); its entry is the prologue, prepare, run,
 // and rt_query_signed_distance_device is two prepares and then two runs.  The listing kinds - all hits, neighbours, overlaps - are a
 // description each (HitKind, NeighborKind, OverlapKind); their protocol of a count step, a fill step or both in one call is
@@ -157,7 +157,7 @@ int run_query(Ctx* c, QueryState& qs, QueryPlan plan, const char* range, Launch&
 // The pending query's qs.n_counters counters and its time (waits for it)
 constexpr uint32_t kMaxStatWords = rt::LQ_STAT_WORDS;
 static_assert(rt::RQ_STAT_WORDS <= kMaxStatWords && rt::PQ_STAT_WORDS <= kMaxStatWords && rt::SQ_STAT_WORDS <= kMaxStatWords && rt::SG_STAT_WORDS <= kMaxStatWords &&
-                  rt::CQ_STAT_WORDS <= kMaxStatWords && rt::KQ_STAT_WORDS <= kMaxStatWords,
+                  rt::CQ_STAT_WORDS <= kMaxStatWords && rt::KQ_STAT_WORDS <= kMaxStatWords && rt::WQ_STAT_WORDS <= kMaxStatWords,
               "read_query's callers hold kMaxStatWords words");
 
 int read_query(Ctx* c, QueryState& qs, unsigned long long* counters, float* ms) {
@@ -209,6 +209,7 @@ using SideStats = rt_side_query_stats;
 using ClearanceStats = rt_clearance_query_stats;
 using KnnStats = rt_knn_query_stats;
 using SegmentStats = rt_overlap_segment_stats;
+using SweepStats = rt_sweep_query_stats;
 constexpr StatWord<RayStats> kRayStats[] = {{&RayStats::invalid_rays, rt::RQ_STAT_INVALID}, {&RayStats::stack_overflow, rt::RQ_STAT_OVERFLOW}};
 constexpr StatWord<PointStats> kPointStats[] = {{&PointStats::invalid_points, rt::PQ_STAT_INVALID}, {&PointStats::stack_overflow, rt::PQ_STAT_OVERFLOW},
                                                 {&PointStats::nodes_visited, rt::PQ_STAT_NODES}, {&PointStats::tris_tested, rt::PQ_STAT_TRIS}};
@@ -221,6 +222,9 @@ constexpr StatWord<ClearanceStats> kClearanceStats[] = {{&ClearanceStats::invali
 constexpr StatWord<KnnStats> kKnnStats[] = {{&KnnStats::invalid_points, rt::KQ_STAT_INVALID}, {&KnnStats::neighbors, rt::KQ_STAT_NEIGHBORS},
                                             {&KnnStats::stack_overflow, rt::KQ_STAT_OVERFLOW}, {&KnnStats::nodes_visited, rt::KQ_STAT_NODES},
                                             {&KnnStats::tris_tested, rt::KQ_STAT_TRIS}};
+constexpr StatWord<SweepStats> kSweepStats[] = {{&SweepStats::invalid_sweeps, rt::WQ_STAT_INVALID}, {&SweepStats::hits, rt::WQ_STAT_HITS},
+                                                {&SweepStats::stack_overflow, rt::WQ_STAT_OVERFLOW}, {&SweepStats::nodes_visited, rt::WQ_STAT_NODES},
+                                                {&SweepStats::tris_tested, rt::WQ_STAT_TRIS}};
 constexpr StatWord<SegmentStats> kSegmentStats[] = {{&SegmentStats::entries, rt::SG_STAT_ENTRIES}, {&SegmentStats::touches, rt::SG_STAT_TOUCHES},
                                                     {&SegmentStats::skipped_incomplete, rt::SG_STAT_SKIPPED}, {&SegmentStats::bad_entries, rt::SG_STAT_BAD}};
 
@@ -404,6 +408,40 @@ int run_knn(Ctx* c, const rt::KnnQuery& q, const rt_knn_query_params& prm, const
     if (int rc = run_query(c, k.qs, plan, "rt.path_b.query_knn", launch)) return rc;
     k.stats = rt_knn_query_stats{};
     k.stats.points = q.n;
+    k.stats.launches = 1;
+    return RT_OK;
+}
+
+// ---- sphere casts: the rays' inputs and a radius each ----
+int prepare_sweeps(Ctx* c, const void* origins, const void* dirs, const void* radius, const void* tmax, uint32_t n, const rt_sweep_query_params& prm, void* t_out,
+                   void* tri_out, void* point_out, rt::SweepQuery* q, QueryPlan* plan) {
+    const rt::DeviceMesh& mesh = c->pt.mesh();
+    if (int rc = check_arrays(c, {{origins, (size_t)n * 12, "origins_dev"}, {dirs, (size_t)n * 12, "dirs_dev"}, {radius, (size_t)n * 4, "radius_dev"},
+                                  {tmax, (size_t)n * 4, "tmax_dev", false}, {t_out, (size_t)n * 4, "t_out_dev"}, {tri_out, (size_t)n * 4, "tri_out_dev"},
+                                  {point_out, (size_t)n * 12, "point_out_dev", false}}))
+        return rc;
+    *q = rt::SweepQuery{};
+    q->origins = static_cast<const float*>(origins);
+    q->dirs = static_cast<const float*>(dirs);
+    q->radius = static_cast<const float*>(radius);
+    q->tmax = static_cast<const float*>(tmax);
+    q->t_out = static_cast<float*>(t_out);
+    q->tri_out = static_cast<int*>(tri_out);
+    q->point_out = static_cast<float*>(point_out);
+    q->n = n;
+    q->reach = rt::kCameraReach * mesh.maxabs;
+    // the points' walk: point_stack_need entries per lane; the grid is what the kernel's register budget keeps resident
+    return prepare_query(c, c->pt.queries.sweeps.qs, n, prm, rt::point_stack_need(mesh.depth), plan, (uint32_t)c->n_cus * (uint32_t)rt::kSweepWaves);
+}
+
+int run_sweeps(Ctx* c, const rt::SweepQuery& q, const rt_sweep_query_params& prm, const QueryPlan& plan) {
+    rt::QueryKind<rt_sweep_query_stats>& k = c->pt.queries.sweeps;
+    const auto launch = [&](uint32_t* head, unsigned long long* stats, uint32_t grid, const rt::StackCfg& sk, uint32_t refill_min) {
+        return rt::launch_pt_query_sweeps(c, rt::scene_view(c->pt.mesh()), q, prm.count_traversal != 0u, head, stats, grid, sk, refill_min);  // (byte 1 has no meaning here)
+    };
+    if (int rc = run_query(c, k.qs, plan, "rt.path_b.query_sweeps", launch)) return rc;
+    k.stats = rt_sweep_query_stats{};
+    k.stats.sweeps = q.n;
     k.stats.launches = 1;
     return RT_OK;
 }
@@ -851,5 +889,24 @@ int rt_query_knn_device(rt_ctx* ctx, const void* points, const void* rmax, uint3
 }
 
 int rt_get_knn_query_stats(rt_ctx* ctx, rt_knn_query_stats* stats) { return query_stats(ctx, &rt::Queries::knn, kKnnStats, stats); }
+
+// ---- sphere casts ----
+int rt_default_sweep_query_params(rt_sweep_query_params* p) { return default_params(p); }
+
+int rt_query_sweeps_device(rt_ctx* ctx, const void* origins, const void* dirs, const void* radius, const void* tmax, uint32_t n, const rt_sweep_query_params* prm,
+                           void* t_out, void* tri_out, void* point_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) return RT_ERR_INVALID;
+    const rt_sweep_query_params defaults{};
+    int done;
+    if (int rc = enter_query(c, n, prm, defaults, &done)) return rc;
+    if (done) return RT_OK;
+    rt::SweepQuery q{};
+    QueryPlan plan{};
+    if (int rc = prepare_sweeps(c, origins, dirs, radius, tmax, n, *prm, t_out, tri_out, point_out, &q, &plan)) return rc;
+    return run_sweeps(c, q, *prm, plan);
+}
+
+int rt_get_sweep_query_stats(rt_ctx* ctx, rt_sweep_query_stats* stats) { return query_stats(ctx, &rt::Queries::sweeps, kSweepStats, stats); }
 
 }  // extern "C"

@@ -340,6 +340,23 @@ struct KnnQuery {
 };
 // Counters of a k-nearest query
 enum { KQ_STAT_INVALID = 0, KQ_STAT_OVERFLOW = 1, KQ_STAT_NODES = 2, KQ_STAT_TRIS = 3, KQ_STAT_NEIGHBORS = 4, KQ_STAT_WORDS = 5 };
+// rt_query_sweeps_device: the sphere casts of one query and where their answers go.  Item i is queue entry i.
+struct SweepQuery {
+    const float* origins;  // n x 3
+    const float* dirs;     // n x 3
+    const float* radius;   // n
+    const float* tmax;     // n, or nullptr: +inf
+    float* t_out;          // n
+    int* tri_out;          // n
+    float* point_out;      // n x 3, or nullptr: the contact point
+    uint32_t n;
+    float reach;  // |origin component| and radius limit: kCameraReach x the mesh's maxabs
+};
+// Counters of a sphere-cast query (SQ_ is the sides')
+enum { WQ_STAT_INVALID = 0, WQ_STAT_OVERFLOW = 1, WQ_STAT_NODES = 2, WQ_STAT_TRIS = 3, WQ_STAT_HITS = 4, WQ_STAT_WORDS = 5 };
+// Waves per SIMD pt_query_sweeps is bounded to, = its workgroups per CU (the compiler's figures: DESIGN.md §6.24); the host caps the
+// persistent grid to it.
+constexpr int kSweepWaves = 4;
 // Counters of a listing query (all hits, neighbours, overlaps): one set per step (the fill step's LQ_STEP_WORDS words behind the count step's),
 // so that the two launches of a list call report side by side.  FOUND: hits / neighbours met.
 enum { LQ_STAT_INVALID = 0, LQ_STAT_OVERFLOW = 1, LQ_STAT_NODES = 2, LQ_STAT_TRIS = 3, LQ_STAT_FOUND = 4, LQ_STAT_WRITTEN = 5, LQ_STAT_INCOMPLETE = 6,
@@ -379,7 +396,7 @@ constexpr size_t kQueryHeadBytes = (size_t)PT_HEADS * PT_HEAD_STRIDE * sizeof(ui
 constexpr size_t query_block_bytes(uint32_t n_counters) { return kQueryHeadBytes + (size_t)n_counters * sizeof(unsigned long long); }
 struct QueryState {
     QueryState(uint32_t k, const char* what, uint32_t lds, uint32_t halves) : n_counters(k), name(what), fixed_lds_bytes(lds), spill_halves(halves) {}
-    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS / SQ_STAT_WORDS / LQ_STAT_WORDS / SG_STAT_WORDS / CQ_STAT_WORDS / KQ_STAT_WORDS
+    uint32_t n_counters;  // RQ_STAT_WORDS / PQ_STAT_WORDS / SQ_STAT_WORDS / LQ_STAT_WORDS / SG_STAT_WORDS / CQ_STAT_WORDS / KQ_STAT_WORDS / WQ_STAT_WORDS
     const char* name;     // for messages
     uint32_t fixed_lds_bytes, spill_halves;  // pt_stack_config's: the kernel's LDS beside the stacks, the sets of spill columns it is given
     DevPtr<char> block;
@@ -420,6 +437,7 @@ struct Queries {
     QueryKind<rt_overlap_segment_stats> segments{SG_STAT_WORDS, "overlap-segments", 0u, 0u};
     QueryKind<rt_clearance_query_stats> clearance{CQ_STAT_WORDS, "clearance-query", 0u, 1u};  // rt_query_clearance_device: the points' walk, one set of columns
     QueryKind<rt_knn_query_stats> knn{KQ_STAT_WORDS, "knn-query", 0u, 1u};                    // rt_query_knn_device: the points' walk, one set of columns
+    QueryKind<rt_sweep_query_stats> sweeps{WQ_STAT_WORDS, "sweep-query", 0u, 1u};             // rt_query_sweeps_device: the points' walk, one set of columns
     // rt_overlap_segments_device: original triangle index -> leaf position of the current mesh, rewritten by every call; the context's own
     // (a DeviceMesh is shared read-only, §6.12)
     Scratch<uint32_t> tri_inverse;
@@ -428,7 +446,7 @@ struct Queries {
 
     template <class F>
     void for_each(F&& f) {
-        f(rays), f(points), f(sides), f(hits), f(neighbors), f(overlaps), f(segments), f(clearance), f(knn);
+        f(rays), f(points), f(sides), f(hits), f(neighbors), f(overlaps), f(segments), f(clearance), f(knn), f(sweeps);
     }
 };
 
@@ -562,7 +580,7 @@ int launch_detile(Ctx* c, const float* tiles, uint32_t n_ranks, uint32_t tiles_p
 int launch_to_rgba8(Ctx* c, const float* rgb, uint8_t* rgba, uint64_t n_pixels);
 
 // path_b.hip (generate, shade, scatter_surfaces, resolve), pt_trace.hip (trace, trace_fused, pool_lds_bytes, trace_rays, query_rays), pt_packet.hip (trace_packet),
-// pt_point_query.hip (query_points), pt_side_query.hip (query_sides), pt_hit_query.hip (query_hits), pt_neighbor_query.hip (query_neighbors), pt_overlap_query.hip (query_overlaps), pt_knn_query.hip (query_knn): every unit ends with the launchers of its own kernels
+// pt_point_query.hip (query_points), pt_side_query.hip (query_sides), pt_hit_query.hip (query_hits), pt_neighbor_query.hip (query_neighbors), pt_overlap_query.hip (query_overlaps), pt_knn_query.hip (query_knn), pt_sweep_query.hip (query_sweeps): every unit ends with the launchers of its own kernels
 int launch_pt_generate(Ctx* c, const PtFrame& f, const PtState& st, uint32_t* queue, uint32_t* ctr);
 int launch_pt_trace(Ctx* c, hipStream_t stream, const PtScene& sc, const PtState& st, const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head,
                     unsigned long long* stats, bool any_hit, bool count, uint32_t grid, const StackCfg& stack_cap, uint32_t refill_min, uint32_t tri_mode,
@@ -609,6 +627,9 @@ int launch_pt_query_clearance(Ctx* c, const PtScene& sc, const ClearanceQuery& q
 // pt_knn_query.hip: the persistent refilling k-nearest kernel (stats: KQ_STAT_WORDS words)
 int launch_pt_query_knn(Ctx* c, const PtScene& sc, const KnnQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid, const StackCfg& sk,
                         uint32_t refill_min);
+// pt_sweep_query.hip: the persistent refilling sphere-cast kernel (stats: WQ_STAT_WORDS words)
+int launch_pt_query_sweeps(Ctx* c, const PtScene& sc, const SweepQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid, const StackCfg& sk,
+                           uint32_t refill_min);
 void pt_free(Ctx* c);
 void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block and events
 

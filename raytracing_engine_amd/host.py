@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (ClearanceQueryParams, ClearanceQueryStats, Config, HitQueryParams, HitQueryStats, KnnQueryParams, KnnQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, OverlapQueryParams, OverlapQueryStats, OverlapSegmentStats, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats,
+from ._lib import (ClearanceQueryParams, ClearanceQueryStats, Config, HitQueryParams, HitQueryStats, KnnQueryParams, KnnQueryStats, Light, Material, MutableData, NeighborQueryParams, NeighborQueryStats, Object, OverlapQueryParams, OverlapQueryStats, OverlapSegmentStats, PointQueryParams, PointQueryStats, PtParams, PtStats, RayQueryParams, RayQueryStats, SweepQueryParams, SweepQueryStats,
                    RtError, SideQueryParams, SideQueryStats, Stats)
 
 # src/main.rs:343-364
@@ -489,7 +489,7 @@ class Renderer:
         self._device_ints(t, name, n, "int64")
 
     def _query_tune(self, params, tune, method):
-        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors / count_overlaps / list_overlaps / query_clearance / query_knn) into its parameter struct;
+        """The tune_* keywords of `method` (query_rays / query_points / query_sides / query_signed_distance / count_ray_hits / list_ray_hits / count_neighbors / list_neighbors / count_overlaps / list_overlaps / query_clearance / query_knn / query_sweeps) into its parameter struct;
         TypeError for any other keyword."""
         for k, v in tune.items():
             if k not in ("tune_refill_min", "tune_blocks_per_cu", "tune_lds_stack", "tune_max_blocks"):
@@ -989,6 +989,43 @@ class Renderer:
         """rt_knn_query_stats of the last k-nearest query as a dict (waits for it): points, invalid_points, neighbors (the sum of the
         counts that are not negative), nodes_visited, tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
         return self._query_stats(KnnQueryStats(), "rt_get_knn_query_stats")
+
+    def query_sweeps(self, origins, dirs, radius, tmax=None, out=None, sync=True, want_points=True, count_traversal=False, **tune):
+        """How far does a sphere get before it touches the current mesh, which triangle does it touch first, and where?
+        (rt_query_sweeps_device)  origins, dirs, tmax as for query_rays: the centre starts at origins[i] and moves
+        along dirs[i] (not normalised; t is in units of |dir|), only contacts with t < tmax count (strictly; default +inf).  radius: a
+        float32 device tensor of n elements, or a float for all items - it becomes a filled device tensor; 0 is a ray against the closed
+        triangles.  Returns (t, tri, point): float32 times of impact (+inf on a miss; 0 where the sphere touches at the start, the
+        lowest triangle index among those it touches), int32 original triangle indices (RAY_MISS = -1) and the (n, 3) contact points on
+        triangle tri (NaN on a miss), or None in its place with want_points=False; the contact normal is (origin + t dir - point) /
+        radius.  Invalid items (a non-finite component, a NaN tmax, a radius that is NaN, negative or above 32 x the mesh's largest
+        |coordinate|, an origin beyond that reach) get RAY_INVALID = -2 and NaNs.  out: the tensors to fill - (t, tri, point), or (t, tri)
+        with want_points=False - instead of new ones.  sync as for query_rays.  count_traversal=True: sweep_query_stats() reports
+        nodes_visited / tris_tested.  tune: tune_refill_min, tune_blocks_per_cu, tune_lds_stack, tune_max_blocks of
+        rt_sweep_query_params."""
+        import torch
+
+        n = self._ray_rows(origins, dirs, tmax)
+        if isinstance(radius, torch.Tensor):
+            if self._device_rows(radius, "radius", 1) != n or radius.dim() != 1:
+                raise ValueError(f"radius must have shape ({n},), got {tuple(radius.shape)}")
+        else:
+            if isinstance(radius, bool) or not isinstance(radius, (int, float, np.floating, np.integer)):
+                raise ValueError(f"radius must be a float or a float32 tensor of shape ({n},), got {type(radius).__name__}")
+            if not float(radius) >= 0.0 or float(radius) == float("inf"):
+                raise ValueError(f"radius must be finite and not negative, got {float(radius)}")
+            radius = torch.full((n,), float(radius), dtype=torch.float32, device=origins.device)
+        p = SweepQueryParams()
+        p.count_traversal = int(bool(count_traversal))
+        self._query_tune(p, tune, "query_sweeps")
+        t, tri, pt = self._point_out(out, "t", n, origins.device, want_points)
+        self._query_call(sync, self._lib.rt_query_sweeps_device, origins, dirs, radius, tmax, n, C.byref(p), t, tri, pt)
+        return t, tri, pt
+
+    def sweep_query_stats(self):
+        """rt_sweep_query_stats of the last sphere-cast query as a dict (waits for it): sweeps, invalid_sweeps, hits, nodes_visited,
+        tris_tested (count_traversal=True only), stack_overflow, launches, ms."""
+        return self._query_stats(SweepQueryStats(), "rt_get_sweep_query_stats")
 
     def trace_rays(self, origins, dirs, any_hit=False, counted=False):
         """Test hook (query_rays is the product entry): closest hit (t, original triangle index) or occlusion flags for a ray batch;
