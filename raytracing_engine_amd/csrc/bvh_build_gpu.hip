@@ -699,15 +699,7 @@ int read_back(Ctx* c, T* host, const T* dev, size_t count) {
     return RT_OK;
 }
 
-struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
-int build(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out, DevPtr<char>& scratch, Events& ev) {
+int build(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out, DevPtr<char>& scratch, Event (&ev)[2]) {
     const size_t m = std::max<uint32_t>(n - 1u, 1u);
     Bump sizing;
     Scratch s{};
@@ -715,12 +707,11 @@ int build(Ctx* c, const float* verts, const float* albedo, const float* emission
     if (!dalloc(scratch, sizing.used)) return c->fail(RT_ERR_OOM, "device BVH build: %zu bytes of scratch for %u triangles", sizing.used, n);
     Bump bump{scratch.get(), 0};
     carve(bump, s, n);
-    RT_HIP(c, hipEventCreate(&ev.e[0]));
-    RT_HIP(c, hipEventCreate(&ev.e[1]));
+    for (Event& e : ev) RT_HIP(c, make_event(e));
     const uint32_t red_blocks = std::min<uint32_t>(kReduceBlocks, blocks_for(n));
 
     // 1. validate and measure: the only step that can refuse the input
-    RT_HIP(c, hipEventRecord(ev.e[0], c->stream));
+    RT_HIP(c, hipEventRecord(ev[0].get(), c->stream));
     hipLaunchKernelGGL(bvhd_validate, dim3(red_blocks), dim3(kThreads), 0, c->stream, verts, n, s.part_max, s.part_bad);
     BVHD_LAUNCH(c);
     std::vector<float> pmax(red_blocks);
@@ -823,10 +814,10 @@ int build(Ctx* c, const float* verts, const float* albedo, const float* emission
     hipLaunchKernelGGL(bvhd_lights, dim3(blocks_for(n)), dim3(kThreads), 0, c->stream, (const uint32_t*)s.flag, (const uint32_t*)s.flag_excl,
                        (const uint32_t*)s.leaf_pos, n, n_lights, out->lights.get());
     BVHD_LAUNCH(c);
-    RT_HIP(c, hipEventRecord(ev.e[1], c->stream));
+    RT_HIP(c, hipEventRecord(ev[1].get(), c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
-    RT_HIP(c, hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    RT_HIP(c, hipEventElapsedTime(&ms, ev[0].get(), ev[1].get()));
     out->build_ms = ms;
     out->n_tris = n;
     out->n_lights = n_lights;
@@ -904,7 +895,7 @@ int refit_write(Ctx* c, const float* verts, uint32_t n, float pad, uint32_t n_no
 
 int build_bvh_device(Ctx* c, const float* verts, const float* albedo, const float* emission, uint32_t n, DeviceMesh* out) {
     DevPtr<char> scratch;  // freed here; the mesh's own arrays go to *out
-    Events ev;
+    Event ev[2];
     const int rc = build(c, verts, albedo, emission, n, out, scratch, ev);
     if (rc != RT_OK) {
         (void)hipStreamSynchronize(c->stream);  // nothing enqueued may still use the scratch or the arrays when they are freed

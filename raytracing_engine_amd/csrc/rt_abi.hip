@@ -38,14 +38,9 @@ void level_dims_for(uint32_t width, uint32_t height, uint32_t count, uint32_t le
 }
 
 void free_frame(Ctx* c) {
-    for (auto& p : c->d_level) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    if (c->d_rgb) (void)hipFree(c->d_rgb);
-    c->d_rgb = nullptr;
-    if (c->d_rgba8) (void)hipFree(c->d_rgba8);
-    c->d_rgba8 = nullptr;
+    for (auto& p : c->d_level) p.reset();
+    c->d_rgb.reset();
+    c->d_rgba8.reset();
     c->level_batch = 0;
     c->last_image = 0;
     c->last_sample0 = 0;
@@ -89,17 +84,14 @@ constexpr uint32_t kSampleBatch = 16;
 int ensure_levels(Ctx* c, uint32_t batch) {
     if (batch <= c->level_batch) return RT_OK;
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < c->level_count; i++) {
-        if (c->d_level[i]) (void)hipFree(c->d_level[i]);
-        c->d_level[i] = nullptr;
-    }
+    for (auto& p : c->d_level) p.reset();  // all of them before the first new one: the old and the new batch never stand side by side
     c->level_batch = 0;
     c->frame_valid = false;
     for (uint32_t i = 0; i < c->level_count; i++) {
-        const size_t bytes = (size_t)c->dims[i][0] * c->dims[i][1] * sizeof(float) * batch;
+        const size_t floats = (size_t)c->dims[i][0] * c->dims[i][1] * batch, bytes = floats * sizeof(float);
         // zero-filled ON THE CONTEXT'S STREAM: its streams are non-blocking, so a hipMemset on the null stream (asynchronous
         // to the host for device memory) would not be ordered before the level kernels that follow and could wipe their output
-        if (hipMalloc((void**)&c->d_level[i], bytes) != hipSuccess || hipMemsetAsync(c->d_level[i], 0, bytes, c->stream) != hipSuccess)
+        if (!dalloc(c->d_level[i], floats) || hipMemsetAsync(c->d_level[i].get(), 0, bytes, c->stream) != hipSuccess)
             return c->fail(RT_ERR_OOM, "pyramid level %u x %u samples (%zu bytes)", i, batch, bytes);
     }
     c->level_batch = batch;
@@ -135,10 +127,10 @@ int enqueue_samples(Ctx* c, const float rot[4], const float pos[3], uint32_t s0,
             fp.image_size[i][0] = pw / (float)c->width;
             fp.image_size[i][1] = pw / (float)c->height;
             fp.level_w[i] = c->dims[i][0];
-            fp.level[i] = c->d_level[i];
+            fp.level[i] = c->d_level[i].get();
         }
         rt::RoctxRange rr("rt.path_a.pyramid_fused");
-        if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++], c->stream));
+        if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++].get(), c->stream));
         if (int rc = rt::launch_pyramid_fused(c, spheres, c->scene.objCount, fp)) return rc;
     } else {
         const bool partitioned = c->part.n_ranks > 1;
@@ -166,12 +158,12 @@ int enqueue_samples(Ctx* c, const float rot[4], const float pos[3], uint32_t s0,
             p.alg = c->cfg.march_algorithm ? c->cfg.march_algorithm : 3u;
             std::memcpy(p.repeat, c->cfg.repeat, sizeof p.repeat);
             rt::RoctxRange rr("rt.path_a.cone_level", i);
-            if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++], c->stream));
-            int rc = rt::launch_cone_level(c, spheres, c->scene.objCount, p, i ? c->d_level[i - 1] : nullptr, c->d_level[i], nb);
+            if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++].get(), c->stream));
+            int rc = rt::launch_cone_level(c, spheres, c->scene.objCount, p, i ? c->d_level[i - 1].get() : nullptr, c->d_level[i].get(), nb);
             if (rc) return rc;
         }
     }
-    if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++], c->stream));
+    if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++].get(), c->stream));
 
     rt::ShadeSet set;
     fill_shade_set(c->scene, &set);
@@ -204,10 +196,10 @@ int enqueue_samples(Ctx* c, const float rot[4], const float pos[3], uint32_t s0,
     int rc;
     {
         rt::RoctxRange rr("rt.path_a.shade");
-        rc = rt::launch_shade(c, set, c->scene.objCount, sp, c->d_level[count - 1], dst, c->d_counters, c->d_chain != nullptr);
+        rc = rt::launch_shade(c, set, c->scene.objCount, sp, c->d_level[count - 1].get(), dst, c->d_counters.get(), c->d_chain != nullptr);
     }
     if (rc) return rc;
-    if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++], c->stream));
+    if (stage_events) RT_HIP(c, hipEventRecord(c->ev_stage[ev++].get(), c->stream));
     c->last_image = nb - 1u;
     c->last_sample0 = s0;
     return RT_OK;
@@ -223,10 +215,10 @@ int render_common(Ctx* c, const float rot[4], const float pos[3], uint32_t spp, 
     if (int rc = rt::bind(c)) return rc;
 
     const bool stage_events = c->cfg.profile_stages != 0;
-    RT_HIP(c, hipMemsetAsync(c->d_counters, 0, 4 * 1024 * sizeof(uint64_t), c->stream));
+    RT_HIP(c, hipMemsetAsync(c->d_counters.get(), 0, 4 * 1024 * sizeof(uint64_t), c->stream));
     // rt_render_chains: the records' address, in the word behind the slots (the source outlives the copy: the call synchronises before it clears d_chain)
-    if (c->d_chain) RT_HIP(c, hipMemcpyAsync(c->d_counters + 4 * 1024, &c->d_chain, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    RT_HIP(c, hipEventRecord(c->ev_begin, c->stream));
+    if (c->d_chain) RT_HIP(c, hipMemcpyAsync(c->d_counters.get() + 4 * 1024, &c->d_chain, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    RT_HIP(c, hipEventRecord(c->ev_begin.get(), c->stream));
     const uint32_t batch = c->cfg.fuse_levels ? 1u : std::min(spp, kSampleBatch);
     if (int rc = ensure_levels(c, batch)) return rc;
     for (uint32_t s = 0; s < spp; s += batch) {
@@ -235,7 +227,7 @@ int render_common(Ctx* c, const float rot[4], const float pos[3], uint32_t spp, 
         int rc = enqueue_samples(c, rot, pos, s, nb, n_strata, spp, dst_dev, tile_major, stage_events && s + nb == spp);
         if (rc) return rc;
     }
-    RT_HIP(c, hipEventRecord(c->ev_end, c->stream));
+    RT_HIP(c, hipEventRecord(c->ev_end.get(), c->stream));
     c->frame_valid = true;
     c->stats.frames++;
     c->stats.spp = spp;
@@ -246,7 +238,7 @@ int render_common(Ctx* c, const float rot[4], const float pos[3], uint32_t spp, 
     if (sync) {
         RT_HIP(c, hipStreamSynchronize(c->stream));
         uint64_t slots[4 * 1024], counters[4] = {0, 0, 0, 0};  // hit pixels, secondary hits shaded, mirror rays, transmitted rays
-        RT_HIP(c, hipMemcpy(slots, c->d_counters, sizeof slots, hipMemcpyDeviceToHost));
+        RT_HIP(c, hipMemcpy(slots, c->d_counters.get(), sizeof slots, hipMemcpyDeviceToHost));
         for (int k = 0; k < 4 * 1024; k++) counters[k >> 10] += slots[k];
         uint64_t owned_px = 0;
         {  // pixels inside the frame that belong to this rank's tiles
@@ -262,20 +254,20 @@ int render_common(Ctx* c, const float rot[4], const float pos[3], uint32_t spp, 
         c->stats.shadow_rays = (counters[0] + counters[1]) * c->scene.lightCount;  // one shadowRay per light per shaded surface point
         c->stats.reflection_rays = counters[2];
         c->stats.transmission_rays = counters[3];
-        RT_HIP(c, hipEventElapsedTime(&c->stats.ms_total, c->ev_begin, c->ev_end));
+        RT_HIP(c, hipEventElapsedTime(&c->stats.ms_total, c->ev_begin.get(), c->ev_end.get()));
         c->stats.ms_cone = c->stats.ms_shade = 0.0f;
         std::memset(c->stats.ms_level, 0, sizeof c->stats.ms_level);
         c->stats.ms_fused = 0.0f;
         if (stage_events && c->cfg.fuse_levels) {
-            RT_HIP(c, hipEventElapsedTime(&c->stats.ms_fused, c->ev_stage[0], c->ev_stage[1]));
+            RT_HIP(c, hipEventElapsedTime(&c->stats.ms_fused, c->ev_stage[0].get(), c->ev_stage[1].get()));
             c->stats.ms_cone = c->stats.ms_fused;
-            RT_HIP(c, hipEventElapsedTime(&c->stats.ms_shade, c->ev_stage[1], c->ev_stage[2]));
+            RT_HIP(c, hipEventElapsedTime(&c->stats.ms_shade, c->ev_stage[1].get(), c->ev_stage[2].get()));
         } else if (stage_events) {
             for (uint32_t i = 0; i < c->level_count; i++) {
-                RT_HIP(c, hipEventElapsedTime(&c->stats.ms_level[i], c->ev_stage[i], c->ev_stage[i + 1]));
+                RT_HIP(c, hipEventElapsedTime(&c->stats.ms_level[i], c->ev_stage[i].get(), c->ev_stage[i + 1].get()));
                 c->stats.ms_cone += c->stats.ms_level[i];
             }
-            RT_HIP(c, hipEventElapsedTime(&c->stats.ms_shade, c->ev_stage[c->level_count], c->ev_stage[c->level_count + 1]));
+            RT_HIP(c, hipEventElapsedTime(&c->stats.ms_shade, c->ev_stage[c->level_count].get(), c->ev_stage[c->level_count + 1].get()));
         }
     }
     return RT_OK;
@@ -361,21 +353,18 @@ int rt_create(rt_ctx** out, int device_ordinal) {
     c->device = device_ordinal;
     rt_default_config(&c->cfg);
     hipError_t e = hipSetDevice(device_ordinal);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&c->ev_begin);
-    if (e == hipSuccess) e = hipEventCreate(&c->ev_end);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_counters, (4 * 1024 + 1) * sizeof(uint64_t));
-    for (uint32_t i = 0; e == hipSuccess && i < RT_MAX_LEVELS + 2; i++) {
-        hipEvent_t ev;
-        e = hipEventCreate(&ev);
-        if (e == hipSuccess) c->ev_stage.push_back(ev);
-    }
+    if (e == hipSuccess) e = rt::make_stream(c->own_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = rt::make_event(c->ev_begin);
+    if (e == hipSuccess) e = rt::make_event(c->ev_end);
+    if (e == hipSuccess && !dalloc(c->d_counters, 4 * 1024 + 1)) e = hipErrorOutOfMemory;
+    for (rt::Event& ev : c->ev_stage)
+        if (e == hipSuccess) e = rt::make_event(ev);
     if (e != hipSuccess) {
         g_create_err = std::string("HIP initialisation failed: ") + hipGetErrorString(e);
         rt_destroy(reinterpret_cast<rt_ctx*>(c));
         return RT_ERR_HIP;
     }
-    c->stream = c->own_stream;
+    c->stream = c->own_stream.get();
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cus > 0) c->n_cus = cus;
     *out = reinterpret_cast<rt_ctx*>(c);
@@ -385,20 +374,13 @@ int rt_create(rt_ctx** out, int device_ordinal) {
 void rt_destroy(rt_ctx* ctx) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
-    rt::frames_free(c);
-    rt::comm_free(c);
-    free_frame(c);
-    rt::pt_free(c);
-    if (c->d_counters) (void)hipFree(c->d_counters);
-    for (auto ev : c->ev_stage) (void)hipEventDestroy(ev);
-    if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
-    if (c->ev_end) (void)hipEventDestroy(c->ev_end);
-    if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    // The order of a context's end, the only place it is written down:
+    (void)hipSetDevice(c->device);                                       // 1. bind the device
+    if (c->stream) (void)hipStreamSynchronize(c->stream);                // 2. nothing of the context is running any more
+    if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream.get());
+    c->frames.reset();  // 3. the frame slots (frames_release: the copy stream is idle before any slot goes), whose lanes borrow this context's mesh
+    c->comm.reset();    // 4. the communicator
+    delete c;           // 5. everything else, each member through its owner, in any order; 6. the two streams, which Ctx declares first, last
 }
 
 const char* rt_last_error(const rt_ctx* ctx) {
@@ -447,7 +429,7 @@ int rt_resize(rt_ctx* ctx, uint32_t width, uint32_t height, const float ratio[2]
     if (width == 0 || height == 0 || width > 16384 || height > 16384) return c->fail(RT_ERR_INVALID, "view %ux%u out of range", width, height);
     if (int rc = rt::bind(c)) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    rt::frames_free(c);  // slots are sized for the old view
+    c->frames.reset();  // slots are sized for the old view
     free_frame(c);
     c->width = c->height = 0;
     const uint32_t count = level_count_for(width);
@@ -458,7 +440,7 @@ int rt_resize(rt_ctx* ctx, uint32_t width, uint32_t height, const float ratio[2]
         c->level_count = 0;
         return rc;
     }
-    if (hipMalloc((void**)&c->d_rgb, (size_t)width * height * 3 * sizeof(float)) != hipSuccess) {
+    if (!dalloc(c->d_rgb, (size_t)width * height * 3)) {
         free_frame(c);
         return c->fail(RT_ERR_OOM, "frame buffer");
     }
@@ -512,7 +494,7 @@ int rt_set_stream(rt_ctx* ctx, void* hip_stream) {
     if (!c) return RT_ERR_INVALID;
     if (int rc = rt::bind(c)) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    c->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    c->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream.get();
     return RT_OK;
 }
 
@@ -522,11 +504,11 @@ int rt_render_spp(rt_ctx* ctx, const float rot[4], const float pos[3], uint32_t 
     if (c->part.n_ranks > 1) {
         // a partitioned context only fills its own tiles; clear the rest so the frame is defined
         if (int rc = rt::bind(c)) return rc;
-        if (c->d_rgb) RT_HIP(c, hipMemsetAsync(c->d_rgb, 0, (size_t)c->width * c->height * 3 * sizeof(float), c->stream));
+        if (c->d_rgb) RT_HIP(c, hipMemsetAsync(c->d_rgb.get(), 0, (size_t)c->width * c->height * 3 * sizeof(float), c->stream));
     }
-    int rc = render_common(c, rot, pos, spp, c->d_rgb, 0, true);
+    int rc = render_common(c, rot, pos, spp, c->d_rgb.get(), 0, true);
     if (rc) return rc;
-    if (rgb_out) RT_HIP(c, hipMemcpy(rgb_out, c->d_rgb, (size_t)c->width * c->height * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (rgb_out) RT_HIP(c, hipMemcpy(rgb_out, c->d_rgb.get(), (size_t)c->width * c->height * 3 * sizeof(float), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -536,7 +518,7 @@ int rt_render(rt_ctx* ctx, const float rot[4], const float pos[3], float* rgb_ou
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (depth_out) {
         const uint32_t l = c->level_count - 1;
-        RT_HIP(c, hipMemcpy(depth_out, c->d_level[l] + (size_t)c->last_image * c->dims[l][0] * c->dims[l][1], (size_t)c->dims[l][0] * c->dims[l][1] * sizeof(float), hipMemcpyDeviceToHost));
+        RT_HIP(c, hipMemcpy(depth_out, c->d_level[l].get() + (size_t)c->last_image * c->dims[l][0] * c->dims[l][1], (size_t)c->dims[l][0] * c->dims[l][1] * sizeof(float), hipMemcpyDeviceToHost));
     }
     return RT_OK;
 }
@@ -552,21 +534,17 @@ int rt_render_chains(rt_ctx* ctx, const float rot[4], const float pos[3], float*
     if (c->part.n_ranks > 1) return c->fail(RT_ERR_STATE, "the chain hook records the whole frame: partition %u of %u", c->part.rank, c->part.n_ranks);
     if (int rc = rt::bind(c)) return rc;
     const size_t n = (size_t)c->width * c->height * rows * 7u;
-    float* d_chain = nullptr;
-    if (hipMalloc((void**)&d_chain, n * sizeof(float)) != hipSuccess) return c->fail(RT_ERR_OOM, "chain records (%zu bytes)", n * sizeof(float));
-    c->d_chain = d_chain;
-    int rc = render_common(c, rot, pos, 1, c->d_rgb, 0, true);
+    rt::DevPtr<float> records;  // this call's own: they go on every return below
+    if (!dalloc(records, n)) return c->fail(RT_ERR_OOM, "chain records (%zu bytes)", n * sizeof(float));
+    c->d_chain = records.get();
+    int rc = render_common(c, rot, pos, 1, c->d_rgb.get(), 0, true);
     if (rc) (void)hipStreamSynchronize(c->stream);  // nothing may still read d_chain or write the records when they go
     c->d_chain = nullptr;
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        const uint32_t l = c->level_count - 1;
-        e = hipMemcpy(rgb_out, c->d_rgb, (size_t)c->width * c->height * 3 * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(depth_out, c->d_level[l] + (size_t)c->last_image * c->dims[l][0] * c->dims[l][1], (size_t)c->dims[l][0] * c->dims[l][1] * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(chain_out, d_chain, n * sizeof(float), hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_chain);
     if (rc) return rc;
+    const uint32_t l = c->level_count - 1;
+    hipError_t e = hipMemcpy(rgb_out, c->d_rgb.get(), (size_t)c->width * c->height * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(depth_out, c->d_level[l].get() + (size_t)c->last_image * c->dims[l][0] * c->dims[l][1], (size_t)c->dims[l][0] * c->dims[l][1] * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(chain_out, records.get(), n * sizeof(float), hipMemcpyDeviceToHost);
     RT_HIP(c, e);
     return RT_OK;
 }
@@ -596,7 +574,7 @@ int rt_synchronize(rt_ctx* ctx) {
     RT_HIP(c, hipStreamSynchronize(c->stream));
     if (c->frame_valid && c->ev_end) {
         float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev_begin, c->ev_end) == hipSuccess) c->stats.ms_total = ms;
+        if (hipEventElapsedTime(&ms, c->ev_begin.get(), c->ev_end.get()) == hipSuccess) c->stats.ms_total = ms;
     }
     return RT_OK;
 }
@@ -613,7 +591,7 @@ int rt_read_level_image(rt_ctx* ctx, uint32_t level, uint32_t image, float* out,
     if (sample) *sample = c->last_sample0 + image;
     if (out) {
         RT_HIP(c, hipStreamSynchronize(c->stream));
-        RT_HIP(c, hipMemcpy(out, c->d_level[level] + (size_t)image * c->dims[level][0] * c->dims[level][1], (size_t)c->dims[level][0] * c->dims[level][1] * sizeof(float),
+        RT_HIP(c, hipMemcpy(out, c->d_level[level].get() + (size_t)image * c->dims[level][0] * c->dims[level][1], (size_t)c->dims[level][0] * c->dims[level][1] * sizeof(float),
                             hipMemcpyDeviceToHost));
     }
     return RT_OK;
@@ -633,13 +611,10 @@ int rt_read_rgba8(rt_ctx* ctx, uint8_t* rgba_out) {
     if (int rc = rt::bind(c)) return rc;
     const uint64_t n = (uint64_t)c->width * c->height;
     // staging buffer of the view's size, kept until rt_resize / rt_destroy: this call sits in a per-frame loop
-    if (!c->d_rgba8 && hipMalloc((void**)&c->d_rgba8, n * 4) != hipSuccess) {
-        c->d_rgba8 = nullptr;
-        return c->fail(RT_ERR_OOM, "rgba8 staging buffer");
-    }
-    if (int rc = rt::launch_to_rgba8(c, c->d_rgb, c->d_rgba8, n)) return rc;
+    if (!c->d_rgba8 && !dalloc(c->d_rgba8, n * 4)) return c->fail(RT_ERR_OOM, "rgba8 staging buffer");
+    if (int rc = rt::launch_to_rgba8(c, c->d_rgb.get(), c->d_rgba8.get(), n)) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    RT_HIP(c, hipMemcpy(rgba_out, c->d_rgba8, n * 4, hipMemcpyDeviceToHost));
+    RT_HIP(c, hipMemcpy(rgba_out, c->d_rgba8.get(), n * 4, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -648,15 +623,14 @@ int rt_selftest_math(rt_ctx* ctx, uint64_t* mismatches) {
     if (!c) return RT_ERR_INVALID;
     if (!mismatches) return c->fail(RT_ERR_INVALID, "mismatches is NULL");
     if (int rc = rt::bind(c)) return rc;
-    unsigned long long* d = nullptr;
-    if (hipMalloc((void**)&d, sizeof *d) != hipSuccess) return c->fail(RT_ERR_OOM, "self-test counter");
-    hipError_t e = hipMemsetAsync(d, 0, sizeof *d, c->stream);
-    int rc = e == hipSuccess ? rt::launch_selftest_sqrt(c, d) : RT_OK;
+    rt::DevPtr<unsigned long long> d;  // this call's own: it goes on every return below
+    if (!dalloc(d, 1)) return c->fail(RT_ERR_OOM, "self-test counter");
+    hipError_t e = hipMemsetAsync(d.get(), 0, sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess)
+        if (int rc = rt::launch_selftest_sqrt(c, d.get())) return rc;
     unsigned long long h = 0;
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (rc) return rc;
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(&h, d.get(), sizeof h, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return c->fail(RT_ERR_HIP, "math self-test: %s", hipGetErrorString(e));
     *mismatches = h;
     return RT_OK;

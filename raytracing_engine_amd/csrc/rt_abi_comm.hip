@@ -70,11 +70,8 @@ int nccl_fail(Ctx* c, const char* what, ncclResult_t e) {
 }  // namespace
 
 namespace rt {
-void comm_free(Ctx* c) {
-    if (c->comm) {
-        if (Rccl* r = rccl()) (void)r->CommDestroy(static_cast<ncclComm_t>(c->comm));
-        c->comm = nullptr;
-    }
+void comm_destroy(ncclComm* comm) {
+    if (Rccl* r = rccl()) (void)r->CommDestroy(comm);
 }
 }  // namespace rt
 
@@ -98,13 +95,13 @@ int rt_comm_init(rt_ctx* ctx, const uint8_t id[RT_COMM_ID_BYTES], uint32_t rank,
     Rccl* r = rccl();
     if (!r) return c->fail(RT_ERR_NO_DEVICE, "librccl.so could not be loaded");
     RT_HIP(c, hipSetDevice(c->device));
-    rt::comm_free(c);
+    c->comm.reset();
     ncclUniqueId u;
     std::memcpy(&u, id, sizeof u);
     ncclComm_t comm = nullptr;
     const ncclResult_t e = r->CommInitRank(&comm, (int)n_ranks, u, (int)rank);
     if (e != ncclSuccess) return nccl_fail(c, "ncclCommInitRank", e);
-    c->comm = comm;
+    c->comm.reset(comm);
     c->comm_rank = rank;
     c->comm_ranks = n_ranks;
     c->part.rank = rank;  // the communicator's ranks are the framebuffer partition's ranks
@@ -130,7 +127,7 @@ int rt_gather_tiles(rt_ctx* ctx, const void* tiles_dev, void* gathered_dev, uint
     RT_HIP(c, hipSetDevice(c->device));
     const size_t tile_floats = (size_t)RT_TILE * RT_TILE * 3;
     const size_t block = (size_t)tiles_per_rank * tile_floats;  // floats per rank in gathered_dev
-    ncclComm_t comm = static_cast<ncclComm_t>(c->comm);
+    ncclComm_t comm = c->comm.get();
     ncclResult_t e = r->GroupStart();
     if (e != ncclSuccess) return nccl_fail(c, "ncclGroupStart", e);
     if (c->comm_rank == 0) {
@@ -152,7 +149,7 @@ int rt_comm_destroy(rt_ctx* ctx) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    rt::comm_free(c);
+    c->comm.reset();
     return RT_OK;
 }
 

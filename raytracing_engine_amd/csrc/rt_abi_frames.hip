@@ -16,49 +16,44 @@
 #include "rt_internal.h"
 
 using rt::Ctx;
+using rt::Frames;
 
-namespace {
-
+namespace rt {
 struct Slot {
-    rt_ctx* lane = nullptr;     // child context that renders this slot's frames
+    // (members go in reverse order: the lane first - rt_destroy synchronises its streams - then what it rendered into)
+    DevPtr<float> d_rgb;       // render target (f32 x 3)
+    DevPtr<uint8_t> d_rgba;    // RT_FRAME_RGBA8 only
+    Pinned h_pixels;
+    Event ev_rendered, ev_ready;
+    Lane lane;                  // child context that renders this slot's frames
     uint64_t lane_version = 0;  // parent state_version the lane was last synchronised with
-    float* d_rgb = nullptr;     // render target (f32 x 3)
-    uint8_t* d_rgba = nullptr;  // RT_FRAME_RGBA8 only
-    void* h_pixels = nullptr;   // pinned
-    hipEvent_t ev_rendered = nullptr, ev_ready = nullptr;
-    bool pending = false;    // submitted and not yet known to be complete
-    bool submitted = false;  // holds (or will hold) a frame
+    bool pending = false;       // submitted and not yet known to be complete
+    bool submitted = false;     // holds (or will hold) a frame
 };
 
 struct Frames {
+    Stream copy_stream;  // declared before the slots: it goes after them
     std::vector<Slot> slots;
     uint32_t format = RT_FRAME_F32;
     uint32_t width = 0, height = 0;
     size_t bytes = 0;  // per host frame
-    hipStream_t copy_stream = nullptr;
 };
 
-void release(Frames* f) {
-    if (!f) return;
-    if (f->copy_stream) (void)hipStreamSynchronize(f->copy_stream);
-    for (Slot& s : f->slots) {
-        if (s.lane) rt_destroy(s.lane);  // synchronises the lane's streams first
-        if (s.d_rgb) (void)hipFree(s.d_rgb);
-        if (s.d_rgba) (void)hipFree(s.d_rgba);
-        if (s.h_pixels) (void)hipHostFree(s.h_pixels);
-        if (s.ev_rendered) (void)hipEventDestroy(s.ev_rendered);
-        if (s.ev_ready) (void)hipEventDestroy(s.ev_ready);
-    }
-    if (f->copy_stream) (void)hipStreamDestroy(f->copy_stream);
+void frames_release(Frames* f) {
+    if (f->copy_stream) (void)hipStreamSynchronize(f->copy_stream.get());  // before any slot goes
     delete f;
 }
+}  // namespace rt
+
+namespace {
+using rt::Slot;
 
 // Bring a slot's lane up to date with the parent's configuration, scene and mesh.
 int sync_lane(Ctx* c, Slot& s) {
     if (s.lane_version == c->state_version) return RT_OK;
-    Ctx* l = reinterpret_cast<Ctx*>(s.lane);
+    Ctx* l = reinterpret_cast<Ctx*>(s.lane.get());
     RT_HIP(c, hipStreamSynchronize(l->stream));
-    if (l->aux_stream) RT_HIP(c, hipStreamSynchronize(l->aux_stream));
+    if (l->aux_stream) RT_HIP(c, hipStreamSynchronize(l->aux_stream.get()));
     l->cfg = c->cfg;
     l->scene = c->scene;
     l->have_scene = c->have_scene;
@@ -71,28 +66,28 @@ int sync_lane(Ctx* c, Slot& s) {
 // frame into the slot's device buffer on the slot's lane.
 template <typename Render>
 int submit(Ctx* c, uint32_t slot, Render render) {
-    Frames* f = static_cast<Frames*>(c->frames);
+    Frames* f = c->frames.get();
     if (!f) return c->fail(RT_ERR_STATE, "rt_frames_configure has not been called (or the view was resized since)");
     if (slot >= f->slots.size()) return c->fail(RT_ERR_INVALID, "slot %u of %zu", slot, f->slots.size());
     if (c->part.n_ranks > 1) return c->fail(RT_ERR_STATE, "frames in flight need an unpartitioned context");
     RT_HIP(c, hipSetDevice(c->device));
     Slot& s = f->slots[slot];
     if (s.pending) {  // the image fence: the slot's previous frame must have left the device (src/main.rs:882-884)
-        RT_HIP(c, hipEventSynchronize(s.ev_ready));
+        RT_HIP(c, hipEventSynchronize(s.ev_ready.get()));
         s.pending = false;
     }
     if (int rc = sync_lane(c, s)) return rc;
-    Ctx* l = reinterpret_cast<Ctx*>(s.lane);
-    if (int rc = render(s.lane, s.d_rgb)) return c->fail(rc, "%s", rt_last_error(s.lane));
-    const void* src = s.d_rgb;
+    Ctx* l = reinterpret_cast<Ctx*>(s.lane.get());
+    if (int rc = render(s.lane.get(), s.d_rgb.get())) return c->fail(rc, "%s", rt_last_error(s.lane.get()));
+    const void* src = s.d_rgb.get();
     if (f->format == RT_FRAME_RGBA8) {
-        if (int rc = rt::launch_to_rgba8(l, s.d_rgb, s.d_rgba, (uint64_t)f->width * f->height)) return c->fail(rc, "%s", rt_last_error(s.lane));
-        src = s.d_rgba;
+        if (int rc = rt::launch_to_rgba8(l, s.d_rgb.get(), s.d_rgba.get(), (uint64_t)f->width * f->height)) return c->fail(rc, "%s", rt_last_error(s.lane.get()));
+        src = s.d_rgba.get();
     }
-    RT_HIP(c, hipEventRecord(s.ev_rendered, l->stream));
-    RT_HIP(c, hipStreamWaitEvent(f->copy_stream, s.ev_rendered, 0));
-    RT_HIP(c, hipMemcpyAsync(s.h_pixels, src, f->bytes, hipMemcpyDeviceToHost, f->copy_stream));
-    RT_HIP(c, hipEventRecord(s.ev_ready, f->copy_stream));
+    RT_HIP(c, hipEventRecord(s.ev_rendered.get(), l->stream));
+    RT_HIP(c, hipStreamWaitEvent(f->copy_stream.get(), s.ev_rendered.get(), 0));
+    RT_HIP(c, hipMemcpyAsync(s.h_pixels.get(), src, f->bytes, hipMemcpyDeviceToHost, f->copy_stream.get()));
+    RT_HIP(c, hipEventRecord(s.ev_ready.get(), f->copy_stream.get()));
     s.pending = true;
     s.submitted = true;
     return RT_OK;
@@ -101,19 +96,14 @@ int submit(Ctx* c, uint32_t slot, Render render) {
 }  // namespace
 
 namespace rt {
-void frames_free(Ctx* c) {
-    release(static_cast<Frames*>(c->frames));
-    c->frames = nullptr;
-}
-
 void frames_drop_mesh(Ctx* c) {
-    Frames* f = static_cast<Frames*>(c->frames);
+    Frames* f = c->frames.get();
     if (!f) return;
     for (Slot& s : f->slots) {
-        Ctx* l = reinterpret_cast<Ctx*>(s.lane);
+        Ctx* l = reinterpret_cast<Ctx*>(s.lane.get());
         if (!l) continue;
         (void)hipStreamSynchronize(l->stream);
-        if (l->aux_stream) (void)hipStreamSynchronize(l->aux_stream);
+        if (l->aux_stream) (void)hipStreamSynchronize(l->aux_stream.get());
         pt_borrow_mesh(l, nullptr);
         s.lane_version = 0;
     }
@@ -130,8 +120,9 @@ int rt_frames_configure(rt_ctx* ctx, uint32_t n_slots, uint32_t format) {
     if (!c->width) return c->fail(RT_ERR_STATE, "rt_resize has not been called");
     RT_HIP(c, hipSetDevice(c->device));
     if (c->stream) RT_HIP(c, hipStreamSynchronize(c->stream));
-    rt::frames_free(c);
-    Frames* f = new (std::nothrow) Frames;
+    c->frames.reset();
+    rt::FramesPtr frames(new (std::nothrow) Frames);  // the context's only once every slot is complete
+    Frames* f = frames.get();
     if (!f) return c->fail(RT_ERR_OOM, "frame slots");
     f->format = format;
     f->width = c->width;
@@ -143,20 +134,19 @@ int rt_frames_configure(rt_ctx* ctx, uint32_t n_slots, uint32_t format) {
     // read-backs never queue up behind a lane's kernels (streams of one priority share a handful of queues)
     int prio_low = 0, prio_high = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
-    hipError_t e = hipStreamCreateWithPriority(&f->copy_stream, hipStreamNonBlocking, prio_high);
+    hipError_t e = rt::make_stream(f->copy_stream, hipStreamNonBlocking, &prio_high);
     for (Slot& s : f->slots) {
-        if (e == hipSuccess && (rt_create(&s.lane, c->device) != RT_OK || rt_resize(s.lane, c->width, c->height, c->ratio) != RT_OK)) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hipMalloc((void**)&s.d_rgb, px * 3 * sizeof(float));
-        if (e == hipSuccess && format == RT_FRAME_RGBA8) e = hipMalloc((void**)&s.d_rgba, px * 4);
-        if (e == hipSuccess) e = hipHostMalloc(&s.h_pixels, f->bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_rendered, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_ready, hipEventDisableTiming);
+        rt_ctx* lane = nullptr;
+        if (e == hipSuccess && rt_create(&lane, c->device) != RT_OK) e = hipErrorOutOfMemory;
+        s.lane.reset(lane);
+        if (e == hipSuccess && rt_resize(lane, c->width, c->height, c->ratio) != RT_OK) e = hipErrorOutOfMemory;
+        if (e == hipSuccess && (!dalloc(s.d_rgb, px * 3) || (format == RT_FRAME_RGBA8 && !dalloc(s.d_rgba, px * 4)))) e = hipErrorOutOfMemory;
+        if (e == hipSuccess) e = rt::make_pinned(s.h_pixels, f->bytes);
+        if (e == hipSuccess) e = rt::make_event(s.ev_rendered, hipEventDisableTiming);
+        if (e == hipSuccess) e = rt::make_event(s.ev_ready, hipEventDisableTiming);
     }
-    if (e != hipSuccess) {
-        release(f);
-        return c->fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, "frame slots: %s", hipGetErrorString(e));
-    }
-    c->frames = f;
+    if (e != hipSuccess) return c->fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, "frame slots: %s", hipGetErrorString(e));
+    c->frames = std::move(frames);
     return RT_OK;
 }
 
@@ -175,15 +165,15 @@ int rt_frame_submit_pt(rt_ctx* ctx, uint32_t slot, const float rot[4], const flo
 int rt_frame_wait(rt_ctx* ctx, uint32_t slot, const void** pixels, size_t* bytes) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
-    Frames* f = static_cast<Frames*>(c->frames);
+    Frames* f = c->frames.get();
     if (!f) return c->fail(RT_ERR_STATE, "rt_frames_configure has not been called (or the view was resized since)");
     if (slot >= f->slots.size() || !pixels) return c->fail(RT_ERR_INVALID, "slot %u of %zu / NULL output", slot, f->slots.size());
     Slot& s = f->slots[slot];
     if (!s.submitted) return c->fail(RT_ERR_STATE, "slot %u holds no frame", slot);
     RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, hipEventSynchronize(s.ev_ready));
+    RT_HIP(c, hipEventSynchronize(s.ev_ready.get()));
     s.pending = false;
-    *pixels = s.h_pixels;
+    *pixels = s.h_pixels.get();
     if (bytes) *bytes = f->bytes;
     return RT_OK;
 }
@@ -191,13 +181,13 @@ int rt_frame_wait(rt_ctx* ctx, uint32_t slot, const void** pixels, size_t* bytes
 int rt_frame_poll(rt_ctx* ctx, uint32_t slot, int* ready) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) return RT_ERR_INVALID;
-    Frames* f = static_cast<Frames*>(c->frames);
+    Frames* f = c->frames.get();
     if (!f) return c->fail(RT_ERR_STATE, "rt_frames_configure has not been called (or the view was resized since)");
     if (slot >= f->slots.size() || !ready) return c->fail(RT_ERR_INVALID, "slot %u of %zu / NULL output", slot, f->slots.size());
     Slot& s = f->slots[slot];
     if (!s.submitted) return c->fail(RT_ERR_STATE, "slot %u holds no frame", slot);
     RT_HIP(c, hipSetDevice(c->device));
-    const hipError_t e = hipEventQuery(s.ev_ready);
+    const hipError_t e = hipEventQuery(s.ev_ready.get());
     if (e != hipSuccess && e != hipErrorNotReady) return c->fail(RT_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
     *ready = e == hipSuccess ? 1 : 0;
     if (e == hipSuccess) s.pending = false;

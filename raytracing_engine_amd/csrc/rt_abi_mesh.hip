@@ -28,10 +28,7 @@ void pt_free_mesh(PtData& pt) {
     pt.d_spill.reset();
     pt.spill_words = 0;
     pt.d_refit.reset();
-    for (hipEvent_t& e : pt.ev_refit) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
+    for (rt::Event& e : pt.ev_refit) e.reset();
     pt.stats = rt_pt_stats{};
 }
 
@@ -129,7 +126,7 @@ float ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::d
 // Everything that renders the context's mesh goes idle, the mesh is freed, the frame-slot lanes re-sync on their next submit
 int retire_mesh(Ctx* c) {
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream.get()));
     rt::frames_drop_mesh(c);  // frame-slot lanes render with this mesh
     pt_free_mesh(c->pt);
     c->state_version++;
@@ -198,7 +195,7 @@ int detach_mesh(Ctx* c) {
     if (int rc = clone_mesh(c, *pt.own, copy.get())) return rc;
     // the context's own frames may still read the arrays it lets go of, which the other holders may free at any time
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream.get()));
     rt::frames_drop_mesh(c);
     pt.own = std::move(copy);
     return RT_OK;
@@ -305,7 +302,7 @@ int update_chunk_impl(Ctx* c, uint32_t chunk, const float* verts, uint32_t n_tri
         if (!std::isfinite(verts[i])) return c->fail(RT_ERR_INVALID, "vertex data is not finite at float %zu", i);
     if (int rc = rt::bind(c)) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream.get()));
     rt::frames_drop_mesh(c);  // lanes re-borrow the mesh on their next submit
     c->state_version++;
     if (int rc = detach_mesh(c)) return rc;  // from here on `tl` may be another context's
@@ -429,16 +426,20 @@ int refit_mesh_device_impl(Ctx* c, const void* verts, uint32_t n_tris) {
     if (n_tris != pt.own->n_tris) return c->fail(RT_ERR_INVALID, "the mesh holds %u triangles, n_tris is %u", pt.own->n_tris, n_tris);
     if (int rc = rt::bind(c)) return rc;
     if (int rc = check_device_array(c, verts, (size_t)n_tris * 36, "verts")) return rc;
-    if (!pt.d_refit) {  // first refit of this mesh: scratch and timing events stay until the mesh is freed
-        if (!dalloc(pt.d_refit, rt::refit_scratch_size(pt.own->n_nodes))) return c->fail(RT_ERR_OOM, "refit scratch for %u nodes", pt.own->n_nodes);
-        for (hipEvent_t& e : pt.ev_refit)
-            if (!e) RT_HIP(c, hipEventCreate(&e));
+    if (!pt.d_refit) {  // first refit of this mesh: scratch and timing events, all of them or none, stay until the mesh is freed
+        rt::DevPtr<char> scratch;
+        rt::Event ev[2];
+        if (!dalloc(scratch, rt::refit_scratch_size(pt.own->n_nodes))) return c->fail(RT_ERR_OOM, "refit scratch for %u nodes", pt.own->n_nodes);
+        for (rt::Event& e : ev) RT_HIP_AS(c, rt::kTextEventCreate, rt::make_event(e));
+        pt.d_refit = std::move(scratch);
+        pt.ev_refit[0] = std::move(ev[0]);
+        pt.ev_refit[1] = std::move(ev[1]);
     }
     // 1. validate and measure: the last point at which the call may refuse; nothing of the mesh has been written
     const float* v = static_cast<const float*>(verts);
     float maxabs = 0.0f;
-    if (int rc = rt::refit_measure(c, v, n_tris, pt.d_refit.get(), pt.ev_refit[0], &maxabs)) return rc;
-    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    if (int rc = rt::refit_measure(c, v, n_tris, pt.d_refit.get(), pt.ev_refit[0].get(), &maxabs)) return rc;
+    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream.get()));
     if (int rc = detach_mesh(c)) return rc;  // a mesh other contexts render too is left to them
     DeviceMesh& m = *pt.own;
     // 2. commit: frame-slot lanes are idled (they re-borrow the mesh on their next submit), then the arrays are rewritten in place
@@ -446,7 +447,7 @@ int refit_mesh_device_impl(Ctx* c, const void* verts, uint32_t n_tris) {
     c->state_version++;
     const float maxabs1 = std::max(maxabs, 1.0f), pad = 2e-5f * maxabs1;  // build_bvh's padding, for the NEW coordinate range
     float ms = 0.0f;
-    if (int rc = rt::refit_write(c, v, n_tris, pad, m.n_nodes, m.nodes.get(), m.tris.get(), m.level_start, pt.d_refit.get(), pt.ev_refit[0], pt.ev_refit[1], &ms)) {
+    if (int rc = rt::refit_write(c, v, n_tris, pad, m.n_nodes, m.nodes.get(), m.tris.get(), m.level_start, pt.d_refit.get(), pt.ev_refit[0].get(), pt.ev_refit[1].get(), &ms)) {
         (void)rc;
         (void)hipStreamSynchronize(c->stream);
         (void)hipGetLastError();
@@ -490,7 +491,7 @@ int set_surfaces_impl(Ctx* c, const uint32_t* kind, const float* ior, uint32_t n
     if (int rc = rt::bind(c)) return rc;
     rt::DevPtr<float> d_w;
     if (!w.empty() && !dalloc(d_w, w.size())) return c->fail(RT_ERR_OOM, "surface words of %u triangles", n_tris);
-    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream.get()));
     if (int rc = detach_mesh(c)) return rc;  // a mesh other contexts render too is left to them
     DeviceMesh& m = *pt.own;
     // commit: frame-slot lanes are idled (they re-borrow the mesh and its flag on their next submit), then albedo.w is rewritten

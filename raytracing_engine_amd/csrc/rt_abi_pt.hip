@@ -68,21 +68,21 @@ constexpr float rt_pt_stats::* kStageMs[STAGE_COUNT] = {&rt_pt_stats::ms_generat
 struct StageTimer {  // HIP-event pairs around launches, summed per stage after the frame
     Ctx* c;
     bool on;
-    std::vector<hipEvent_t>& pool;  // the context's own events: created after hipSetDevice(c->device), freed by pt_free
+    std::vector<rt::Event>& pool;  // the context's own events: created after hipSetDevice(c->device), they go with the context
     std::vector<std::pair<Stage, size_t>> marks;  // stage, index of begin event
     size_t used = 0;
     hipError_t err = hipSuccess;  // first failure of an event call (reported by the frame)
     hipEvent_t next() {
         if (used == pool.size()) {
-            hipEvent_t e;
-            const hipError_t rc = hipEventCreate(&e);
+            rt::Event e;  // owned from the moment it exists, whatever the pool's growth does
+            const hipError_t rc = rt::make_event(e);
             if (rc != hipSuccess) {
                 if (err == hipSuccess) err = rc;
                 return nullptr;
             }
-            pool.push_back(e);
+            pool.push_back(std::move(e));
         }
-        return pool[used++];
+        return pool[used++].get();
     }
     void record() {
         hipEvent_t e = next();
@@ -174,11 +174,14 @@ int plan_frame(Ctx* c, const float rot[4], const float pos[3], const rt_pt_param
     // not occupy two; falls back to 1 under per-stage timing);  1 one launch after the other on one stream.
     const uint32_t overlap_mode = mesh.n_lights == 0 ? 1u : (timed && prm->tune_no_overlap == 2u) ? 1u : prm->tune_no_overlap;  // per-stage timing needs one stream
     p->fused = overlap_mode == 0u;
-    if (overlap_mode == 2u && !c->aux_stream) RT_HIP(c, hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-    p->overlap = overlap_mode == 2u && c->aux_stream != nullptr;
-    if (p->overlap && !c->pt.ev_shaded) {
-        RT_HIP(c, hipEventCreateWithFlags(&c->pt.ev_shaded, hipEventDisableTiming));
-        RT_HIP(c, hipEventCreateWithFlags(&c->pt.ev_shadowed, hipEventDisableTiming));
+    if (overlap_mode == 2u && !c->aux_stream) RT_HIP_AS(c, rt::kTextAuxStream, rt::make_stream(c->aux_stream, hipStreamNonBlocking));
+    p->overlap = overlap_mode == 2u && c->aux_stream;
+    if (p->overlap && !c->pt.ev_shaded) {  // both events or neither: a frame that fails here leaves the next one to try again from nothing
+        rt::Event shaded, shadowed;
+        RT_HIP_AS(c, rt::kTextEvShaded, rt::make_event(shaded, hipEventDisableTiming));
+        RT_HIP_AS(c, rt::kTextEvShadowed, rt::make_event(shadowed, hipEventDisableTiming));
+        c->pt.ev_shaded = std::move(shaded);
+        c->pt.ev_shadowed = std::move(shadowed);
     }
     return RT_OK;
 }
@@ -223,7 +226,7 @@ int enqueue_batch(Ctx* c, const FramePlan& p, const rt::PtScene& sc, const rt::P
         }
         n.launches_closest++;
         if (shadow_pending) {  // shade(d) adds sky/emission after shadow(d-1)'s contribution
-            RT_HIP(c, hipStreamWaitEvent(c->stream, pt.ev_shadowed, 0));
+            RT_HIP(c, hipStreamWaitEvent(c->stream, pt.ev_shadowed.get(), 0));
             shadow_pending = false;
         }
         {
@@ -245,9 +248,9 @@ int enqueue_batch(Ctx* c, const FramePlan& p, const rt::PtScene& sc, const rt::P
         hipStream_t shadow_stream = c->stream;
         if (p.overlap) {
             sk2.spill = p.stack.spill + p.spill_half;
-            shadow_stream = c->aux_stream;
-            RT_HIP(c, hipEventRecord(pt.ev_shaded, c->stream));
-            RT_HIP(c, hipStreamWaitEvent(shadow_stream, pt.ev_shaded, 0));
+            shadow_stream = c->aux_stream.get();
+            RT_HIP(c, hipEventRecord(pt.ev_shaded.get(), c->stream));
+            RT_HIP(c, hipStreamWaitEvent(shadow_stream, pt.ev_shaded.get(), 0));
         }
         {
             rt::RoctxRange rr("rt.path_b.trace_shadow depth", d);
@@ -258,12 +261,12 @@ int enqueue_batch(Ctx* c, const FramePlan& p, const rt::PtScene& sc, const rt::P
             tm.end();
         }
         if (p.overlap) {
-            RT_HIP(c, hipEventRecord(pt.ev_shadowed, shadow_stream));
+            RT_HIP(c, hipEventRecord(pt.ev_shadowed.get(), shadow_stream));
             shadow_pending = true;
         }
         n.launches_shadow++;
     }
-    if (shadow_pending) RT_HIP(c, hipStreamWaitEvent(c->stream, pt.ev_shadowed, 0));
+    if (shadow_pending) RT_HIP(c, hipStreamWaitEvent(c->stream, pt.ev_shadowed.get(), 0));
     rt::RoctxRange rr("rt.path_b.resolve");
     tm.begin(STAGE_RESOLVE);
     if (int rc = rt::launch_pt_resolve(c, f, pt.st, pt.d_acc, dst_dev, tile_major)) return rc;
@@ -319,11 +322,11 @@ int read_frame_stats(Ctx* c, const StageTimer& tm, const FrameCounts& n) {
     s.pool_flushes = st[rt::PT_STAT_FLUSHES];
     s.wave_rounds_all = st[rt::PT_STAT_ROUNDS_ALL];
     s.stack_overflow = (uint32_t)st[rt::PT_STAT_OVERFLOW];
-    RT_HIP(c, hipEventElapsedTime(&s.ms_total, c->ev_begin, c->ev_end));
+    RT_HIP(c, hipEventElapsedTime(&s.ms_total, c->ev_begin.get(), c->ev_end.get()));
     for (auto field : kStageMs) s.*field = 0.0f;
     for (auto& m : tm.marks) {
         float ms = 0.0f;
-        if (m.second + 1 < tm.used && hipEventElapsedTime(&ms, pt.ev_pool[m.second], pt.ev_pool[m.second + 1]) == hipSuccess) s.*kStageMs[m.first] += ms;
+        if (m.second + 1 < tm.used && hipEventElapsedTime(&ms, pt.ev_pool[m.second].get(), pt.ev_pool[m.second + 1].get()) == hipSuccess) s.*kStageMs[m.first] += ms;
     }
     return RT_OK;
 }
@@ -357,7 +360,7 @@ int render_pt_common(Ctx* c, const float rot[4], const float pos[3], const rt_pt
 
     rt::RoctxRange frame_range("rt.path_b.frame");
     RT_HIP(c, hipMemsetAsync(pt.d_stats.get(), 0, rt::PT_STAT_WORDS * sizeof(unsigned long long), c->stream));
-    RT_HIP(c, hipEventRecord(c->ev_begin, c->stream));
+    RT_HIP(c, hipEventRecord(c->ev_begin.get(), c->stream));
     FrameCounts n;
     std::vector<uint32_t> h_ctr((size_t)rt::PT_CTR_STRIDE * (prm->bounces + 2));
     for (uint32_t s0 = 0; s0 < prm->spp; s0 += plan.spp_batch) {
@@ -368,7 +371,7 @@ int render_pt_common(Ctx* c, const float rot[4], const float pos[3], const rt_pt
         if (sync)
             if (int rc = count_batch_rays(c, plan, f, h_ctr, n)) return rc;
     }
-    RT_HIP(c, hipEventRecord(c->ev_end, c->stream));
+    RT_HIP(c, hipEventRecord(c->ev_end.get(), c->stream));
     if (tm.err != hipSuccess) return c->fail(RT_ERR_HIP, "stage-timing event: %s", hipGetErrorString(tm.err));
     c->frame_valid = true;
     pt.stats.launches_trace_closest = n.launches_closest;
@@ -410,19 +413,6 @@ int pt_stack_config(Ctx* c, uint32_t need, uint32_t fixed_lds_bytes, uint32_t sp
     sk->spill = pt.d_spill.get();
     return RT_OK;
 }
-
-void pt_free(Ctx* c) {
-    free_wavefront(c->pt);
-    pt_free_mesh(c->pt);
-    query_free(c);
-    c->pt.d_ctr.reset();
-    c->pt.d_stats.reset();
-    if (c->pt.ev_shaded) (void)hipEventDestroy(c->pt.ev_shaded);
-    if (c->pt.ev_shadowed) (void)hipEventDestroy(c->pt.ev_shadowed);
-    c->pt.ev_shaded = c->pt.ev_shadowed = nullptr;
-    for (hipEvent_t e : c->pt.ev_pool) (void)hipEventDestroy(e);
-    c->pt.ev_pool.clear();
-}
 }  // namespace rt
 
 extern "C" {
@@ -452,8 +442,8 @@ int rt_render_pt(rt_ctx* ctx, const float rot[4], const float pos[3], const rt_p
     if (!c->width) return c->fail(RT_ERR_STATE, "rt_resize has not been called");
     if (int rc = rt::bind(c)) return rc;
     const size_t bytes = (size_t)c->width * c->height * 3 * sizeof(float);
-    if (int rc = render_pt_common(c, rot, pos, params, c->d_rgb, 0, true, bytes)) return rc;
-    if (rgb_out) RT_HIP(c, hipMemcpy(rgb_out, c->d_rgb, bytes, hipMemcpyDeviceToHost));
+    if (int rc = render_pt_common(c, rot, pos, params, c->d_rgb.get(), 0, true, bytes)) return rc;
+    if (rgb_out) RT_HIP(c, hipMemcpy(rgb_out, c->d_rgb.get(), bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

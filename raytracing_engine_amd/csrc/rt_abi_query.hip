@@ -91,12 +91,17 @@ int check_arrays(Ctx* c, std::initializer_list<ArrayArg> arrays) {
     return RT_OK;
 }
 
-// A kind's first use: its device block and the two events.  `part`: what the kind has in the block, for the message
+// A kind's first use: its device block and the two events, all of them or none (a first use that fails leaves the next query of the
+// kind to try again from nothing).  `part`: what the kind has in the block, for the message
 int ensure_block(Ctx* c, QueryState& qs, const char* part) {
     if (qs.block) return RT_OK;
-    if (!dalloc(qs.block, rt::query_block_bytes(qs.n_counters))) return c->fail(RT_ERR_OOM, "%s %s", qs.name, part);
-    for (hipEvent_t& e : qs.ev)
-        if (!e) RT_HIP(c, hipEventCreate(&e));
+    rt::DevPtr<char> block;
+    rt::Event ev[2];
+    if (!dalloc(block, rt::query_block_bytes(qs.n_counters))) return c->fail(RT_ERR_OOM, "%s %s", qs.name, part);
+    for (rt::Event& e : ev) RT_HIP_AS(c, rt::kTextEventCreate, rt::make_event(e));
+    qs.block = std::move(block);
+    qs.ev[0] = std::move(ev[0]);
+    qs.ev[1] = std::move(ev[1]);
     return RT_OK;
 }
 
@@ -146,9 +151,9 @@ int run_query(Ctx* c, QueryState& qs, QueryPlan plan, const char* range, Launch&
     unsigned long long* stats = reinterpret_cast<unsigned long long*>(qs.block.get() + rt::kQueryHeadBytes);
     rt::RoctxRange rr(range);
     RT_HIP(c, hipMemsetAsync(qs.block.get(), 0, first ? rt::query_block_bytes(qs.n_counters) : rt::kQueryHeadBytes, c->stream));
-    if (first) RT_HIP(c, hipEventRecord(qs.ev[0], c->stream));
+    if (first) RT_HIP(c, hipEventRecord(qs.ev[0].get(), c->stream));
     if (int rc = launch(head, stats, plan.grid, plan.sk, plan.refill_min)) return rc;
-    if (last) RT_HIP(c, hipEventRecord(qs.ev[1], c->stream));
+    if (last) RT_HIP(c, hipEventRecord(qs.ev[1].get(), c->stream));
     qs.pending = true;
     return RT_OK;
 }
@@ -164,7 +169,7 @@ int read_query(Ctx* c, QueryState& qs, unsigned long long* counters, float* ms) 
     if (int rc = rt::bind(c)) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
     RT_HIP(c, hipMemcpy(counters, qs.block.get() + rt::kQueryHeadBytes, qs.n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    RT_HIP(c, hipEventElapsedTime(ms, qs.ev[0], qs.ev[1]));
+    RT_HIP(c, hipEventElapsedTime(ms, qs.ev[0].get(), qs.ev[1].get()));
     qs.pending = false;
     return RT_OK;
 }
@@ -576,7 +581,7 @@ int run_count(Ctx* c, typename K::Query q, const typename K::Params& prm, const 
         if (int rc = rt::scan_u64_device(c, ls.counts, static_cast<unsigned long long*>(offsets_out), (size_t)q.n + 1, ls.sums, ls.total)) return rc;
         st.stats.launches += 3;
     }
-    if (last) RT_HIP(c, hipEventRecord(st.qs.ev[1], c->stream));
+    if (last) RT_HIP(c, hipEventRecord(st.qs.ev[1].get(), c->stream));
     return RT_OK;
 }
 
@@ -658,23 +663,6 @@ int listing_stats(rt_ctx* ctx, typename K::Stats* stats) {
 }
 
 }  // namespace
-
-namespace rt {
-void query_free(Ctx* c) {
-    Queries& q = c->pt.queries;
-    q.list_scan = {};
-    q.tri_inverse = {};
-    q.for_each([](auto& kind) {
-        QueryState& qs = kind.qs;
-        qs.block.reset();
-        for (hipEvent_t& e : qs.ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        qs.pending = false;
-    });
-}
-}  // namespace rt
 
 extern "C" {
 
@@ -836,10 +824,10 @@ int rt_overlap_segments_device(rt_ctx* ctx, const void* tris, uint32_t n, const 
     rt::RoctxRange rr("rt.path_b.overlap_segments");
     unsigned long long* stats = reinterpret_cast<unsigned long long*>(qs.block.get() + rt::kQueryHeadBytes);
     RT_HIP(c, hipMemsetAsync(stats, 0, qs.n_counters * sizeof(unsigned long long), c->stream));
-    RT_HIP(c, hipEventRecord(qs.ev[0], c->stream));
+    RT_HIP(c, hipEventRecord(qs.ev[0].get(), c->stream));
     if (int rc = rt::launch_pt_tri_inverse(c, rt::scene_view(mesh), qr.tri_inverse.d.get())) return rc;
     if (int rc = rt::launch_pt_overlap_segments(c, rt::scene_view(mesh), q, qr.tri_inverse.d.get(), stats)) return rc;
-    RT_HIP(c, hipEventRecord(qs.ev[1], c->stream));
+    RT_HIP(c, hipEventRecord(qs.ev[1].get(), c->stream));
     qs.pending = true;
     qr.segments.stats = rt_overlap_segment_stats{};
     qr.segments.stats.launches = 2;

@@ -1,4 +1,6 @@
 // rt_internal.h — context object and launch-parameter blocks shared by the .hip files.
+// Nothing is freed by hand: every device allocation is a DevPtr, every other handle an Owned (rt_owned.h) member of what holds it, made
+// by the helpers next to dalloc, and goes when its holder does.  What has an order is written down at rt_destroy.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +13,9 @@
 
 #include "../../include/rt_abi.h"
 #include "bvh_build.h"
+#include "rt_owned.h"
+
+struct ncclComm;  // RCCL's communicator (rt_abi_comm.hip)
 
 static_assert(sizeof(rt_material) == 32, "std140 Material stride");
 static_assert(sizeof(rt_object) == 16, "std140 Object stride");
@@ -389,9 +394,53 @@ bool dalloc(DevPtr<T>& p, size_t count) {  // frees what p held first; false: ou
     return true;
 }
 
+// The other handles of a context, each with its owner (rt_owned.h).  The make_* helpers free what the owner held first and leave it
+// empty on failure.
+inline void destroy_event(hipEvent_t e) { (void)hipEventDestroy(e); }
+inline void destroy_stream(hipStream_t s) { (void)hipStreamDestroy(s); }
+inline void free_pinned(void* p) { (void)hipHostFree(p); }
+struct Frames;                      // the frames-in-flight slots (rt_abi_frames.hip)
+void frames_release(Frames* f);     // rt_abi_frames.hip: waits for the frames in flight, then every slot goes
+void comm_destroy(ncclComm* comm);  // rt_abi_comm.hip: ncclCommDestroy, found at run time
+using Event = Owned<hipEvent_t, destroy_event>;
+using Stream = Owned<hipStream_t, destroy_stream>;
+using Pinned = Owned<void*, free_pinned>;
+using Lane = Owned<rt_ctx*, rt_destroy>;  // a child context
+using FramesPtr = Owned<Frames*, frames_release>;
+using CommPtr = Owned<ncclComm*, comm_destroy>;
+
+inline hipError_t make_event(Event& ev, unsigned flags = hipEventDefault) {  // (hipEventDefault: what hipEventCreate makes)
+    ev.reset();
+    hipEvent_t raw = nullptr;
+    const hipError_t e = hipEventCreateWithFlags(&raw, flags);
+    if (e == hipSuccess) ev.reset(raw);
+    return e;
+}
+inline hipError_t make_stream(Stream& s, unsigned flags, const int* priority = nullptr) {
+    s.reset();
+    hipStream_t raw = nullptr;
+    const hipError_t e = priority ? hipStreamCreateWithPriority(&raw, flags, *priority) : hipStreamCreateWithFlags(&raw, flags);
+    if (e == hipSuccess) s.reset(raw);
+    return e;
+}
+inline hipError_t make_pinned(Pinned& p, size_t bytes) {
+    p.reset();
+    void* raw = nullptr;
+    const hipError_t e = hipHostMalloc(&raw, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) p.reset(raw);
+    return e;
+}
+// The HIP call that a helper makes at each first-use site, as that site's failure message names it (RT_HIP_AS): the text is part of
+// the message, like the code, and names the call by what it creates
+constexpr char kTextEventCreate[] = "hipEventCreate(&e)";  // a query kind's and the refit's events
+constexpr char kTextAuxStream[] = "hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking)";
+constexpr char kTextEvShaded[] = "hipEventCreateWithFlags(&c->pt.ev_shaded, hipEventDisableTiming)";
+constexpr char kTextEvShadowed[] = "hipEventCreateWithFlags(&c->pt.ev_shadowed, hipEventDisableTiming)";
+
 // What a context keeps per query kind.  The device block is PT_HEADS stream heads (PT_HEAD_STRIDE words apart), then the kind's
 // 64-bit counters; it is cleared before every launch.  One block per kind: a query's counters stay until rt_get_*_query_stats reads
-// them, whatever the other kinds do meanwhile.  Allocated by the kind's first query, freed with the context (rt_abi_query.hip).
+// them, whatever the other kinds do meanwhile.  The block and the two events are made together by the kind's first query (ensure_block,
+// rt_abi_query.hip: all of them or none) and go with the context.
 constexpr size_t kQueryHeadBytes = (size_t)PT_HEADS * PT_HEAD_STRIDE * sizeof(uint32_t);
 constexpr size_t query_block_bytes(uint32_t n_counters) { return kQueryHeadBytes + (size_t)n_counters * sizeof(unsigned long long); }
 struct QueryState {
@@ -400,7 +449,7 @@ struct QueryState {
     const char* name;     // for messages
     uint32_t fixed_lds_bytes, spill_halves;  // pt_stack_config's: the kernel's LDS beside the stacks, the sets of spill columns it is given
     DevPtr<char> block;
-    hipEvent_t ev[2] = {nullptr, nullptr};  // around the launch
+    Event ev[2];  // around the launch
     bool pending = false;  // a query has been enqueued whose counters and time rt_get_*_query_stats has not read yet
 };
 // One query kind in a context: what is in flight and the public statistics of the kind's last query (what the host knows at the
@@ -424,7 +473,7 @@ struct Scratch {
     size_t words = 0;
 };
 // Every query kind of a context, and the scratch two of them keep; nothing outside rt_abi_query.hip looks inside.  A new kind is a
-// member here, a line in for_each and its entries there.
+// member here and its entries there.
 struct Queries {
     // (rays: the 2 KiB octant table, two spill halves as the frames hold; the others: no table, one set of columns)
     QueryKind<rt_ray_query_stats> rays{RQ_STAT_WORDS, "ray-query", 2048u, 2u};
@@ -443,11 +492,6 @@ struct Queries {
     Scratch<uint32_t> tri_inverse;
     // the listing kinds' scan: the 64-bit count column (n + 1), the scan's tile sums and its total
     Scratch<unsigned long long> list_scan;
-
-    template <class F>
-    void for_each(F&& f) {
-        f(rays), f(points), f(sides), f(hits), f(neighbors), f(overlaps), f(segments), f(clearance), f(knn), f(sweeps);
-    }
 };
 
 // A mesh resident on the device: the arrays the kernels read and what the host knows about them.  Made by the host build
@@ -478,12 +522,13 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
         return borrowed ? *borrowed : own ? *own : none;
     }
     MeshHost* host() const { return own ? own->host.get() : nullptr; }  // lanes do not see it
-    DevPtr<char> d_refit;  // rt_refit_mesh_device scratch (refit_scratch_size), allocated by the first refit, freed with the mesh
-    hipEvent_t ev_refit[2] = {nullptr, nullptr};
+    // rt_refit_mesh_device: scratch (refit_scratch_size) and timing events, made together by the first refit (all of them or none), go with the mesh
+    DevPtr<char> d_refit;
+    Event ev_refit[2];
     DevPtr<unsigned long long> d_spill;
     size_t spill_words = 0;
-    hipEvent_t ev_shaded = nullptr, ev_shadowed = nullptr;  // ordering between the main and the auxiliary stream
-    std::vector<hipEvent_t> ev_pool;  // profile_stages: timing events, created on this context's device, freed by pt_free
+    Event ev_shaded, ev_shadowed;  // ordering between the main and the auxiliary stream; made together by the first frame on two streams
+    std::vector<Event> ev_pool;    // profile_stages: timing events, created on this context's device
     // wavefront buffers, sized for cap_paths; st, d_queue and d_acc point into the allocations `wavefront` owns
     uint64_t cap_paths = 0;
     DevPtr<char> wavefront[11];
@@ -501,9 +546,11 @@ struct PtData {  // device residency of one mesh + the wavefront buffers
 
 struct Ctx {
     int device = -1;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipStream_t aux_stream = nullptr;  // path B: shadow kernel beside the next closest-hit kernel
+    // The two streams are declared before everything that has ever been used on them: members go in reverse order, so the streams go last
+    // (rt_destroy's step 6)
+    Stream own_stream;
+    Stream aux_stream;             // path B: shadow kernel beside the next closest-hit kernel; made by the first frame that wants it
+    hipStream_t stream = nullptr;  // own_stream, or the caller's (rt_set_stream): borrowed, never destroyed
     std::string err;
 
     rt_config cfg{};
@@ -514,25 +561,25 @@ struct Ctx {
     float ratio[2] = {1.0f, 1.0f};
     uint32_t level_count = 0;
     uint32_t dims[RT_MAX_LEVELS][2] = {};
-    float* d_level[RT_MAX_LEVELS] = {};  // level i: level_batch images of dims[i], one per sample of a batch
-    uint32_t level_batch = 0;            // images allocated per level
-    uint32_t last_image = 0;             // image of the batch that holds the last sample rendered
-    uint32_t last_sample0 = 0;           // sample index of image 0 of that batch (rt_read_level_image)
-    float* d_rgb = nullptr;         // full frame, f32 x 3
-    float* d_chain = nullptr;       // set only inside rt_render_chains: the shade launch records the secondary marches here
-    uint8_t* d_rgba8 = nullptr;     // rt_read_rgba8 staging, width*height*4, allocated on first use, freed with the frame
-    uint64_t* d_counters = nullptr;  // 4 x 1024 slots: hit pixels, secondary hits shaded, mirror rays, transmitted rays; summed on the host; + 1 word: d_chain for the recording kernel
+    DevPtr<float> d_level[RT_MAX_LEVELS];  // level i: level_batch images of dims[i], one per sample of a batch
+    uint32_t level_batch = 0;              // images allocated per level
+    uint32_t last_image = 0;               // image of the batch that holds the last sample rendered
+    uint32_t last_sample0 = 0;             // sample index of image 0 of that batch (rt_read_level_image)
+    DevPtr<float> d_rgb;                   // full frame, f32 x 3
+    float* d_chain = nullptr;  // borrowed, set only inside rt_render_chains (which owns the records): the shade launch records the secondary marches here
+    DevPtr<uint8_t> d_rgba8;   // rt_read_rgba8 staging, width*height*4, allocated on first use, goes with the frame
+    DevPtr<uint64_t> d_counters;  // 4 x 1024 slots: hit pixels, secondary hits shaded, mirror rays, transmitted rays; summed on the host; + 1 word: d_chain for the recording kernel
     Partition part{0, 1, 0, 0};
 
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    std::vector<hipEvent_t> ev_stage;  // profile_stages
+    Event ev_begin, ev_end;
+    Event ev_stage[RT_MAX_LEVELS + 2];  // profile_stages
     rt_stats stats{};
     bool frame_valid = false;
     PtData pt;
     int n_cus = 256;
-    void* frames = nullptr;  // frames-in-flight slots (rt_abi_frames.hip)
+    FramesPtr frames;  // frames-in-flight slots (rt_abi_frames.hip); their lanes borrow pt's mesh and go before it (rt_destroy's step 3)
     uint64_t state_version = 1;  // bumped by rt_set_config / rt_set_scene / rt_set_mesh: frame-slot lanes re-sync on submit
-    void* comm = nullptr;  // ncclComm_t once rt_comm_init ran (rt_abi_comm.hip)
+    CommPtr comm;  // once rt_comm_init ran (rt_abi_comm.hip)
     uint32_t comm_rank = 0, comm_ranks = 1;
 
     int fail(int code, const char* fmt, ...) {
@@ -546,11 +593,13 @@ struct Ctx {
     }
 };
 
-#define RT_HIP(ctx, call)                                                                          \
+// RT_HIP_AS: the message names `text` instead of the expression: for a call through a make_* helper, whose message names the HIP call
+#define RT_HIP_AS(ctx, text, call)                                                                 \
     do {                                                                                           \
         hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return (ctx)->fail(RT_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return (ctx)->fail(RT_ERR_HIP, "%s: %s", text, hipGetErrorString(e_)); \
     } while (0)
+#define RT_HIP(ctx, call) RT_HIP_AS(ctx, #call, call)
 
 inline int bind(Ctx* c) {
     RT_HIP(c, hipSetDevice(c->device));
@@ -562,7 +611,6 @@ inline uint32_t owned_tiles(const Partition& p) {
     return total > p.rank ? (total - p.rank + p.n_ranks - 1u) / p.n_ranks : 0u;
 }
 
-void frames_free(Ctx* c);          // rt_abi_frames.hip: waits for frames in flight, releases every slot
 void frames_drop_mesh(Ctx* c);     // rt_abi_frames.hip: the parent's mesh is about to be freed: idle the lanes, forget the borrowed mesh
 void pt_borrow_mesh(Ctx* lane, const Ctx* owner);  // rt_abi_mesh.hip: lane renders with owner's device mesh
 void pt_free_mesh(PtData& pt);     // rt_abi_mesh.hip: this context's hold on its mesh (held or borrowed) and everything sized for it
@@ -630,8 +678,6 @@ int launch_pt_query_knn(Ctx* c, const PtScene& sc, const KnnQuery& q, bool count
 // pt_sweep_query.hip: the persistent refilling sphere-cast kernel (stats: WQ_STAT_WORDS words)
 int launch_pt_query_sweeps(Ctx* c, const PtScene& sc, const SweepQuery& q, bool count, uint32_t* head, unsigned long long* stats, uint32_t grid, const StackCfg& sk,
                            uint32_t refill_min);
-void pt_free(Ctx* c);
-void query_free(Ctx* c);  // rt_abi_query.hip: every query kind's device block and events
 
 // |coordinate| limit of a camera position, a query ray's origin and a query point in units of DeviceMesh::maxabs (plan_frame, rt_abi_pt.hip)
 constexpr float kCameraReach = 32.0f;
@@ -663,7 +709,6 @@ int pt_stack_config(Ctx* c, uint32_t need, uint32_t fixed_lds_bytes, uint32_t sp
                     StackCfg* sk, uint32_t* grid);
 // rt_abi_mesh.hip: RT_OK when p is a device allocation of c's device that holds at least `bytes` bytes from p on, else RT_ERR_INVALID
 int check_device_array(Ctx* c, const void* p, size_t bytes, const char* what);
-void comm_free(Ctx* c);  // rt_abi_comm.hip
 
 // bvh_build_gpu.hip: path B mesh built on the GPU from device-resident triangles (rt_set_mesh_device), on c->stream.
 // On failure *out is empty and nothing else has changed.
